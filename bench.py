@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the Qwen3-ASR hot path on MI355X (contract: see the task statement / DESIGN.md section 6).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -11,8 +11,8 @@ over one batch of synthetic 30 s clips.  Default workload = BASELINE.json config
 the speech rate the survey fixes).  Rank 0 prints ONE JSON line.
 
 Launching.  N = 1: `python bench.py`.  N > 1: one process per GPU under torch.distributed.run (the driver's command above);
-a bare `python bench.py --gpus N` re-executes itself under torch.distributed.run on 127.0.0.1 with a free port, so the
-same command shape works at every N.  With N > 1 the line also carries an `extra` leg: BASELINE configs[4]'s per-GPU
+a bare `python bench.py --gpus N` starts itself under torch.distributed.run on 127.0.0.1 with a free port (a child process), so
+the same command shape works at every N.  With N > 1 the line also carries an `extra` leg: BASELINE configs[4]'s per-GPU
 workload (Qwen3-ASR-1.7B, 32 clips per GPU, weights shipped with ONE RCCL broadcast of the arena); the q3a_group_* leg (on by default; --no-native-group-leg) adds
 the native q3a_group_* path (one process, one host thread per GPU, RCCL called from C++), run as a child process with a time limit so
 that neither a crash nor a hang inside it can cost the line.
@@ -219,7 +219,8 @@ def algorithmic_bytes(dims, B, P, new_tokens):
 
 
 def timed_region(eng, clips, steps, warmup, new_tokens, sync_all):
-    """W untimed + K timed steps, PCM resident, ids fetched inside the clock.  Returns elapsed seconds (this rank)."""
+    """W untimed + K timed steps, PCM resident, ids fetched inside the clock.  Returns (elapsed seconds on this rank, the ids of the
+    last timed step: one list of new_tokens ids per clip)."""
     eng.upload_pcm(clips)  # inputs resident in HBM before the timed region
     for _ in range(warmup):
         eng.run_resident(None, 0, new_tokens)
@@ -232,7 +233,20 @@ def timed_region(eng, clips, steps, warmup, new_tokens, sync_all):
     sync_all()
     elapsed = time.perf_counter() - t0
     assert len(ids) == len(clips) and all(len(x) == new_tokens for x in ids)
-    return elapsed
+    return elapsed, ids
+
+
+def dump_outputs(out_dir, name, ids, limit_bytes=64 << 20):
+    """--dump-outputs: the ids the timed path returned in its last step as <out_dir>/<name>.npy, float64 [clips, new_tokens] (ids are
+    exact in float64).  Above limit_bytes a fixed, seeded sample of clips is kept and their indices go to <name>_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    a = np.asarray(ids, dtype=np.float64)
+    if a.nbytes > limit_bytes:
+        keep = max(1, (limit_bytes - 4096) // (a.itemsize * a.shape[1] + 8))  # 4 KiB for the two .npy headers
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+        a = a[rows]
+        np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def host_to_host(eng, clips, steps, new_tokens):
@@ -450,7 +464,7 @@ def free_port() -> int:
 
 
 def multi_gpu_command(n_gpus: int, argv, port: int = 0):
-    """The command a bare `python bench.py --gpus N` (N > 1, no WORLD_SIZE in the environment) re-executes itself as:
+    """The command a bare `python bench.py --gpus N` (N > 1, no WORLD_SIZE in the environment) runs as its child:
     one process per GPU under torch.distributed.run, rendezvous on 127.0.0.1 (the container hostname may not resolve)."""
     return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n_gpus}",
             "--master-addr", "127.0.0.1", "--master-port", str(port or free_port()), os.path.join(ROOT, "bench.py")] + list(argv)
@@ -461,7 +475,7 @@ def launch_check(args):
     under torch.distributed.run, rendezvous on 127.0.0.1, barrier, max over ranks, one JSON line from rank 0."""
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         cmd = multi_gpu_command(args.gpus, sys.argv[1:])
-        os.execv(cmd[0], cmd)
+        raise SystemExit(subprocess.call(cmd))
     import torch.distributed as dist
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     if world != args.gpus:
@@ -537,7 +551,7 @@ def config4_leg(dist, dev, rank, world, local_rank, seconds, new_tokens, steps, 
     def sync_all():
         torch.cuda.synchronize(); dist.barrier(); torch.cuda.synchronize()
 
-    elapsed = timed_region(eng, clips, steps, warmup, new_tokens, sync_all)
+    elapsed, _ = timed_region(eng, clips, steps, warmup, new_tokens, sync_all)
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     stage = eng.timings()
@@ -613,7 +627,7 @@ def extra_leg(preset, B, seconds, new_tokens, steps, warmup, precise, do_trace=T
     t_ck = time.time()
     _, eng = make_engine(preset, None, 0, precise, new_tokens)
     clips = [synthetic.synthetic_clip(i, seconds) for i in range(B)]
-    elapsed = timed_region(eng, clips, steps, warmup, new_tokens, torch.cuda.synchronize)
+    elapsed, _ = timed_region(eng, clips, steps, warmup, new_tokens, torch.cuda.synchronize)
     stage = eng.timings()
     P = int(stage["total_prompt_tokens"]) // B
     ab = algorithmic_bytes(eng.dims, B, P, new_tokens)
@@ -654,15 +668,27 @@ def main():
     ap.add_argument("--native-group-leg", action="store_true", help="(accepted for compatibility: the leg is on by default since round 4)")
     ap.add_argument("--ckpt-dir", default=None)
     ap.add_argument("--trace-out", default=None, help="write the per-kernel table of the in-situ rocprofv3 kernel trace to this file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the ids of the last timed step to DIR/ids.npy (float64 [clips, new_tokens]; "
+                         "N > 1: DIR/ids_rank<r>.npy per rank); the inputs are seeded, so two builds can be compared output for output")
     ap.add_argument("--inner", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--inner-group", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--launch-check", action="store_true",
                     help="only exercise the N > 1 launch path (self re-launch, rendezvous, barrier, max over ranks) on the gloo backend: no GPU needed")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.launch_check:
         return launch_check(args)
 
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not (args.inner or args.inner_group):
+        # bare `python bench.py --gpus N`: same command shape as the N = 1 line -> one process per GPU, children of this process,
+        # which waits for them without ever opening the GPU itself
+        cmd = multi_gpu_command(args.gpus, sys.argv[1:])
+        sys.stderr.write("[bench] launching: " + " ".join(cmd) + "\n")
+        sys.stderr.flush()
+        raise SystemExit(subprocess.call(cmd))
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a HIP device: the engine has no CPU fallback")
     if args.inner:
@@ -673,16 +699,10 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # bare `python bench.py --gpus N`: same command shape as the N = 1 line -> one process per GPU
-        if torch.cuda.device_count() < args.gpus:
-            raise SystemExit(f"--gpus {args.gpus}: only {torch.cuda.device_count()} HIP device(s) visible")
-        cmd = multi_gpu_command(args.gpus, sys.argv[1:])
-        sys.stderr.write("[bench] re-launching as: " + " ".join(cmd) + "\n")
-        sys.stderr.flush()
-        os.execv(cmd[0], cmd)
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} does not match WORLD_SIZE {world}")
+    if torch.cuda.device_count() < world:
+        raise SystemExit(f"--gpus {args.gpus}: only {torch.cuda.device_count()} HIP device(s) visible")
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
 
@@ -733,7 +753,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    elapsed = timed_region(eng, clips, args.steps, args.warmup, args.new_tokens, sync_all)
+    elapsed, last_ids = timed_region(eng, clips, args.steps, args.warmup, args.new_tokens, sync_all)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "ids" if world == 1 else f"ids_rank{rank}", last_ids)
     if dist is not None:
         mine = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         every = [torch.zeros_like(mine) for _ in range(world)]
@@ -815,7 +837,7 @@ def main():
         if world == 1 and not args.no_extra and B == 1 and not args.precise:
             try:  # the exact-ids mode has a number too: fp32 activations split hi + lo, fp32 KV cache
                 _, peng = make_engine(args.preset, args.ckpt_dir, local_rank, True, args.new_tokens)
-                pel = timed_region(peng, clips, 3, 1, args.new_tokens, torch.cuda.synchronize)
+                pel, _ = timed_region(peng, clips, 3, 1, args.new_tokens, torch.cuda.synchronize)
                 pst = peng.timings()
                 peng.close()
                 out["precise_mode"] = {"value": round(B * args.seconds * 3 / pel, 3), "unit": "audio-seconds/sec", "ms_per_step": round(pel / 3 * 1e3, 3),

@@ -339,6 +339,32 @@ def test_bench_native_group_leg_is_a_bounded_child(monkeypatch):
     assert bench.native_group_child(args, 2, 1)["value"] == 7.0
 
 
+def test_bench_dump_outputs_writes_the_ids_exactly_within_the_limit(tmp_path):
+    """--dump-outputs: the last timed step's ids as float64 <name>.npy, exact; an output over the size limit becomes the same seeded
+    sample of clips every time, with the clip indices beside it, and both files together stay within the limit."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    ids = [[151643, 0, 7], [1, 2, 151645]]
+    bench.dump_outputs(str(tmp_path / "a"), "ids", ids)
+    a = np.load(tmp_path / "a" / "ids.npy")
+    assert a.dtype == np.float64 and a.tolist() == ids and not (tmp_path / "a" / "ids_rows.npy").exists()
+    big = [[i, i + 1, i + 2, i + 3] for i in range(1000)]
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), "ids", big, limit_bytes=20000)
+    a, rows = np.load(tmp_path / "b" / "ids.npy"), np.load(tmp_path / "b" / "ids_rows.npy")
+    assert 0 < len(rows) < 1000 and a.tolist() == [big[int(r)] for r in rows]
+    assert os.path.getsize(tmp_path / "b" / "ids.npy") + os.path.getsize(tmp_path / "b" / "ids_rows.npy") <= 20000
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "ids_rows.npy")) and np.array_equal(a, np.load(tmp_path / "c" / "ids.npy"))
+
+
+def test_bench_refuses_fewer_than_one_timed_step():
+    """--steps sets the number of timed steps and ms_per_step divides by it: 0 is refused before anything else runs."""
+    import subprocess, sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr, r.stderr[-2000:]
+
+
 def _cpp_function_body(src: str, signature_start: str) -> str:
     """Text of the brace-balanced body that follows `signature_start` in a C++ source."""
     i = src.index(signature_start)
