@@ -229,7 +229,9 @@ int32_t q3a_measure_peaks(int32_t device, int32_t reps, q3a_peaks* out);
 
 /* Debug taps (opts.debug_taps=1): copy a named intermediate to host. `bytes` = capacity of dst;
  * *actual receives the tap size. Names: mel conv1 conv2 conv3 enc_in enc_layer0 enc_last
- * audio_embeds dec_embed dec_layer0 dec_last_hidden logits. */
+ * audio_embeds dec_embed dec_layer0 dec_last_hidden logits lm_head_bound ([vocab][2] fp32: approximate logit and its error bound
+ * of the pruned one-sequence argmax, written next to the stored logits).  "lm_head_prune_stats" (int32[2]: 16-row blocks rescored
+ * by the pruned argmax, its launches; cumulative over the engine's life) is readable without debug taps. */
 int32_t q3a_debug_read(q3a_engine* e, const char* name, void* dst, uint64_t bytes, uint64_t* actual);
 
 /* ---- pipeline shell: host-only helpers around the hot path -------------- */
@@ -292,6 +294,10 @@ int32_t q3a_capitalize_first(const char* s, char* out, int32_t cap);
  *                        workgroup with at most one workgroup per CU (hidden 2048 / inter 6144: 256 workgroups), it runs in that
  *                        form: every CU streams the same number of weight bytes and the activations once; 0: never; 2: whenever
  *                        the shape allows (tests).  Same arithmetic.  Taken at the next prefill.
+ *   "lm_head_prune"      1 (default): the argmax of a one-sequence decode step whose logits nobody reads comes from an int8 pre-pass
+ *                        over the lm_head (approximate logits with a rigorous error bound) and a bf16 rescore of the 16-row blocks
+ *                        that can still hold the maximum: the ids are bit-identical to 0, the full bf16 GEMV.  Taken at the next
+ *                        batch set-up.
  * Round 6 removed the keys whose A/B is settled, together with the code only they selected (docs/HISTORY.md "Pruned in round 6"):
  * fuse_qkv_attn, dattn_pair_split, fattn_pipe, rope_variant, rope_twice, gemm16_ring, gemm256_resid_prefetch, live_key_splits,
  * skinny_glu_2pass.  An unknown key returns non-zero. */

@@ -114,6 +114,7 @@ Knobs& knobs() {
     env("Q3A_SKINNY_Q", k.skinny_q);
     env("Q3A_EOS_RUN_AHEAD", k.eos_run_ahead);
     env("Q3A_SKINNY_GLU_HP3", k.skinny_glu_hp3);
+    env("Q3A_LM_HEAD_PRUNE", k.lm_head_prune);
   });
   return k;
 }
@@ -152,6 +153,10 @@ struct q3a_engine {
   DevBuf ids, audio_rowmap, row_seq, row_pos, dec_segs, last_rows;
   DevBuf dec_x, dec_ln, dec_qkv, dec_ctx, dec_act, kcache, vcache;
   DevBuf x_dec, d_pos, next_tok, out_ids, step_count, done, s_ln, s_qkv, s_ctx, s_act, logits, forced_tok, part_val, part_idx;
+  DevBuf blk_lo, blk_hi;  // pruned lm_head argmax: per 16-row block bounds (pass 1 -> pass 2)
+  DevBuf lm_q, lm_qs;     // int8 lm_head copy + per-row scale and norms (init_lm_head_q)
+  int lm_q_cols = 0;      // 0: no copy
+  DevBuf prune_stats;     // [2] candidate blocks rescored, pass-2 launches (q3a_debug_read "lm_head_prune_stats"; never read by the step)
   DevBuf attn_pm, attn_pl, attn_po;
   DevBuf nn_x, nn_ss;  // pre-normalised residual row for the next skinny GEMM: [32 * hidden] bf16 fragment order, [hidden/16][32] f32
   DevBuf rope_cur;  // [B][128] cos|sin row of each sequence's current position (kept by argmax_finalize for decode attention)
@@ -169,7 +174,7 @@ struct q3a_engine {
   int gsize = 32;  // sequences per group of the batched decode step (<= 32: one skinny-GEMM weight sweep), fixed per batch
   // knobs that shape the decode step, latched per batch in setup_prompts: producers outside the captured graph (prefill
   // finalize, set_tokens) and the captured step must agree on them, and the graph signature names them
-  int k_parallel_groups = 1, k_skinny_q = 1, k_dattn_batched_min_wgs = 128, k_skinny_glu_hp3 = 1;
+  int k_parallel_groups = 1, k_skinny_q = 1, k_dattn_batched_min_wgs = 128, k_skinny_glu_hp3 = 1, k_lm_head_prune = 1;
   std::vector<hipStream_t> chain_streams;
   std::vector<hipEvent_t> join_ev;
   hipEvent_t fork_ev = nullptr;
@@ -287,6 +292,8 @@ struct q3a_engine {
     memset(host_prog, 0, 64);
     HIPCHK(hipHostGetDevicePointer((void**)&host_prog_dev, host_prog, 0));
     n_done.ensure(64);
+    prune_stats.ensure(8);
+    HIPCHK(hipMemsetAsync(prune_stats.p, 0, 8, stream));
   }
 
   void init_tables() {
@@ -312,6 +319,18 @@ struct q3a_engine {
     upload(rope_sin, s, stream);
     HIPCHK(hipStreamSynchronize(stream));
     rope_positions = n;
+  }
+
+  // int8 copy of the lm_head for the pruned one-sequence argmax (kernels.h LmHeadPruneArgs), built once from the arena's bf16
+  // matrix; not in the precise mode, which never uses it (vocab * 1024 (2048) + vocab * 16 bytes of device memory)
+  void init_lm_head_q() {
+    const int cols = lm_head_q_cols(d.hidden);
+    if (precise() || cols == 0 || d.hidden % 8 != 0) return;
+    lm_q.ensure((size_t)d.vocab * cols);
+    lm_qs.ensure((size_t)d.vocab * 16);
+    KCHK(launch_lm_head_quantize(wh(L.lm_head), d.vocab, d.hidden, lm_q.as<int8_t>(), lm_qs.as<float>(), stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    lm_q_cols = cols;
   }
 
   void check_arena_header() {
@@ -705,6 +724,7 @@ struct q3a_engine {
       k_parallel_groups = kn.decode_parallel_groups.load(); k_skinny_q = kn.skinny_q.load();
       k_dattn_batched_min_wgs = kn.dattn_batched_min_wgs.load();
       k_skinny_glu_hp3 = kn.skinny_glu_hp3.load();
+      k_lm_head_prune = kn.lm_head_prune.load();
     }
     const size_t ng = (size_t)n_groups(b);  // groups of <= gsize sequences of the batched decode step
     nn_x.ensure(ng * 32 * H * 2); nn_ss.ensure((size_t)ng * (H / 8) * 32 * 4);  // room for the finer (8-column) partial rows whichever shape the knob selects later
@@ -715,6 +735,10 @@ struct q3a_engine {
     s_act.ensure(ng * 32 * d.inter * 4); logits.ensure((size_t)b * d.vocab * 4);
     part_stride = std::max(128, (d.vocab + 3) / 4);  // >= blocks of the lm_head GEMV at 1 row per wave
     part_val.ensure((size_t)b * part_stride * 4); part_idx.ensure((size_t)b * part_stride * 4);
+    {
+      const size_t nblk4 = ((size_t)(d.vocab + 15) / 16 + 3) & ~size_t(3);  // lm_head_prune_blocks, rounded up for float4 reads
+      blk_lo.ensure(nblk4 * 4); blk_hi.ensure(nblk4 * 4);
+    }
     attn_nsplit = (max_ctx + dattn_keys_per_split(kv_f32()) - 1) / dattn_keys_per_split(kv_f32());
     attn_pm.ensure((size_t)b * d.n_q * attn_nsplit * 4); attn_pl.ensure((size_t)b * d.n_q * attn_nsplit * 4);
     attn_po.ensure((size_t)b * d.n_q * attn_nsplit * 128 * 4);
@@ -742,7 +766,7 @@ struct q3a_engine {
   // source for DevBuf members and fails when one is missing here.
   std::vector<DevBuf*> step_bufs() {
     return {&kcache, &vcache, &x_dec, &d_pos, &next_tok, &out_ids, &step_count, &done, &s_ln, &s_qkv, &s_ctx, &s_act, &logits,
-            &part_val, &part_idx, &attn_pm, &attn_pl, &attn_po, &nn_x, &nn_ss, &rope_cur, &rope_cos, &rope_sin, &n_done, &forced_tok};
+            &part_val, &part_idx, &blk_lo, &blk_hi, &prune_stats, &attn_pm, &attn_pl, &attn_po, &nn_x, &nn_ss, &rope_cur, &rope_cos, &rope_sin, &n_done, &forced_tok};
   }
   std::vector<const DevBuf*> step_bufs() const {
     auto v = const_cast<q3a_engine*>(this)->step_bufs();
@@ -751,6 +775,13 @@ struct q3a_engine {
 
   void* kc_layer(int l) { return (uint8_t*)kcache.p + (size_t)l * kv_layer_elems * kv_elem(); }
   void* vc_layer(int l) { return (uint8_t*)vcache.p + (size_t)l * kv_layer_elems * kv_elem(); }
+
+  LmHeadPruneArgs prune_args(const GemvArgs& g) {
+    LmHeadPruneArgs pa{};
+    pa.g = g; pa.Wq = lm_q.as<int8_t>(); pa.qcols = lm_q_cols; pa.qs = lm_qs.as<float>();
+    pa.blk_lo = blk_lo.as<float>(); pa.blk_hi = blk_hi.as<float>(); pa.stats = prune_stats.as<int>();
+    return pa;
+  }
 
   // final norm + lm_head on x_dec -> logits (+ block argmax partials), then argmax/finalize
   void run_head(int advance) {
@@ -764,8 +795,26 @@ struct q3a_engine {
       g.x = x_dec.as<float>(); g.ldx = H; g.rms_w = wf(L.final_norm); g.eps = d.rms_eps;
       g.W = wh(L.lm_head); g.N = V; g.K = H; g.mode = 3; g.out = logits.as<float>(); g.ldo = V;
       g.part_val = part_val.as<float>(); g.part_idx = part_idx.as<int>(); g.part_stride = part_stride;
-      n_part = gemv_blocks(g);
-      timed(Q3A_KC_GEMV_LM_HEAD, wbytes, [&] { KCHK(launch_gemv(g, S, stream)); });
+      LmHeadPruneArgs pa{};
+      const bool prunable = S == 1 && !precise() && lm_q_cols > 0 && (pa = prune_args(g), !lm_head_prune_check(pa));
+      if (prunable && opts.debug_taps == 1) {  // (debug taps) approximate logits and their bounds next to the stored logits
+        DevBuf& t = taps["lm_head_bound"];
+        t.ensure((size_t)V * 8);
+        tap_bytes["lm_head_bound"] = (size_t)V * 8;
+        LmHeadPruneArgs pd = pa;
+        pd.dbg = t.as<float>(); pd.stats = nullptr;
+        KCHK(launch_lm_head_approx(pd, stream));
+      }
+      if (prunable && k_lm_head_prune && !head_logits_) {
+        // nobody reads the logits: the exact argmax from the int8 pre-pass + a bf16 rescore of the candidate blocks
+        g.out = nullptr; pa.g.out = nullptr;
+        n_part = lm_head_rescore_groups(g, n_cu);
+        timed(Q3A_KC_GEMV_LM_HEAD, (double)V * lm_q_cols, [&] { KCHK(launch_lm_head_approx(pa, stream)); });
+        timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_lm_head_rescore(pa, n_part, stream)); });
+      } else {
+        n_part = gemv_blocks(g);
+        timed(Q3A_KC_GEMV_LM_HEAD, wbytes, [&] { KCHK(launch_gemv(g, S, stream)); });
+      }
     } else if (!precise()) {
       // default mode: bf16 normed rows, then the LDS-DMA GEMM at M = S (32-row tiles) -- the vocabulary matrix is
       // streamed once through double-buffered LDS; the skinny kernel re-reads x per 16 vocabulary rows (3x slower here)
@@ -1072,8 +1121,8 @@ struct q3a_engine {
     }
     char buf[256];
     // (one field per latched knob, as latched: packing several into one integer let distinct settings collide -- ADVICE r5)
-    snprintf(buf, sizeof(buf), "%d.%d.%d.%d.%d.%d.%d.%d/%d/%d/%d/%p/%016llx", B, gsize, k_parallel_groups, k_skinny_q,
-             k_dattn_batched_min_wgs, k_skinny_glu_hp3, (int)(min_P_ < 256), (int)head_logits_, live_nsplit_, max_ctx, max_new, (const void*)arena, (unsigned long long)h);
+    snprintf(buf, sizeof(buf), "%d.%d.%d.%d.%d.%d.%d.%d.%d/%d/%d/%d/%p/%016llx", B, gsize, k_parallel_groups, k_skinny_q,
+             k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, (int)(min_P_ < 256), (int)head_logits_, live_nsplit_, max_ctx, max_new, (const void*)arena, (unsigned long long)h);
     return buf;
   }
 
@@ -1327,6 +1376,7 @@ static int32_t create_impl(const char* model_dir, int32_t device, void* dev_aren
     }
     e->check_arena_header();
     e->init_tables();
+    e->init_lm_head_q();
     *out = e;
     return 0;
   } catch (const std::exception& ex) {
@@ -1673,6 +1723,15 @@ int32_t q3a_debug_read(q3a_engine* e, const char* name, void* dst, uint64_t byte
   if (!e) return 1;
   Q3A_TRY(e)
   HIPCHK(hipSetDevice(e->device));
+  if (strcmp(name, "lm_head_prune_stats") == 0) {  // counters, not a tap: readable without opts.debug_taps
+    if (actual) *actual = 8;
+    if (dst) {
+      if (bytes < 8) fail("q3a_debug_read: destination too small");
+      HIPCHK(hipStreamSynchronize(e->stream));
+      HIPCHK(hipMemcpy(dst, e->prune_stats.p, 8, hipMemcpyDeviceToHost));
+    }
+    return 0;
+  }
   auto it = e->taps.find(name);
   if (it == e->taps.end()) fail(std::string("q3a_debug_read: no tap named '") + name + "' (opts.debug_taps set?)");
   size_t n = e->tap_bytes[name];
@@ -1698,6 +1757,7 @@ int32_t q3a_debug_set(const char* key, int32_t value) {
   if (strcmp(key, "skinny_q") == 0) { kn.skinny_q = value; return 0; }
   if (strcmp(key, "eos_run_ahead") == 0) { kn.eos_run_ahead = value; return 0; }
   if (strcmp(key, "skinny_glu_hp3") == 0) { kn.skinny_glu_hp3 = value; return 0; }
+  if (strcmp(key, "lm_head_prune") == 0) { kn.lm_head_prune = value; return 0; }
   g_last_error = std::string("q3a_debug_set: unknown key '") + key + "'";
   return 1;
 }

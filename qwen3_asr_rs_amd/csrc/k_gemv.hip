@@ -17,6 +17,8 @@
 //      instead of every element (the reference's (x*rstd)*w differs by fp32 rounding only);
 //   4. wavefront reduction on DPP (no LDS crossbar), fused epilogue.
 // x can also be assembled on the fly from the flash-decoding partials of k_dattn.hip (o_proj input).
+#include <algorithm>
+
 #include "dev.h"
 #include "kernels.h"
 
@@ -486,6 +488,317 @@ __global__ __launch_bounds__(256) void gemv1_kernel(GemvArgs a) {
   Q3A_STAMP_AT(a.stamp, blockIdx.x, 4);  // reduced and stored
 }
 
+// ---- lm_head (mode 3, one sequence, fused final RMSNorm) -------------------------------------------------
+// One 16-row argmax block (4 waves x PR rows) of the one-sequence lm_head: the arithmetic of gemv1_kernel<PR, KI, true, false>
+// (same lane / column assignment, same order of the products and sums, same rstd, first-index tie rule).  Used by the
+// unpruned launch (gemv1_head_kernel: block = blockIdx.x) AND by the rescore of the pruned argmax (lm_head_rescore_kernel): the
+// two cannot drift apart.  Ends with a barrier; the block's (value, row) is valid in thread 0.
+template <int PR, int KI>
+__device__ __forceinline__ void gemv1_head_block(const GemvArgs& a, int blk, float (&am_v)[4][1], int (&am_i)[4][1],
+                                                 float& out_v, int& out_i) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int K = a.K;
+  const int g = blk * 4 + wave;
+  int prow[PR];
+  gemv_rows<PR>(a, g, prow);
+  bool kin[KI];
+  int kk[KI];
+#pragma unroll
+  for (int it = 0; it < KI; ++it) {
+    const int k = lane * 8 + it * 512;
+    kin[it] = k < K;
+    kk[it] = kin[it] ? k : 0;
+  }
+  float4 xr[KI][2], nr[KI][2];
+  uint4 wq[KI][PR];
+#pragma unroll
+  for (int it = 0; it < KI; ++it) {  // x and the norm weight first (L2 hits), then the weight stream
+    xr[it][0] = *reinterpret_cast<const float4*>(a.x + kk[it]);
+    xr[it][1] = *reinterpret_cast<const float4*>(a.x + kk[it] + 4);
+    nr[it][0] = *reinterpret_cast<const float4*>(a.rms_w + kk[it]);
+    nr[it][1] = *reinterpret_cast<const float4*>(a.rms_w + kk[it] + 4);
+  }
+#pragma unroll
+  for (int it = 0; it < KI; ++it)
+#pragma unroll
+    for (int i = 0; i < PR; ++i) {
+      const int row = prow[i] >= 0 ? prow[i] : a.N - 1;
+      wq[it][i] = ld_stream16(a.W + (size_t)row * K + kk[it]);
+    }
+  float bv[PR];
+#pragma unroll
+  for (int i = 0; i < PR; ++i) bv[i] = a.bias ? a.bias[prow[i] >= 0 ? prow[i] : 0] : 0.f;
+  __builtin_amdgcn_sched_barrier(0);  // every request is issued before anything is waited for
+  float x[KI][8];
+  float ss = 0.f;
+#pragma unroll
+  for (int it = 0; it < KI; ++it) {
+    const float4 v0 = xr[it][0], v1 = xr[it][1];
+    const float xv[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) x[it][e] = (K == KI * 512 || kin[it]) ? xv[e] : 0.f;
+    const float4 w0 = nr[it][0], w1 = nr[it][1];
+    const float wv[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { ss += x[it][e] * x[it][e]; x[it][e] *= wv[e]; }
+  }
+  float acc[PR];
+#pragma unroll
+  for (int i = 0; i < PR; ++i) acc[i] = 0.f;
+#pragma unroll
+  for (int it = 0; it < KI; ++it)
+#pragma unroll
+    for (int i = 0; i < PR; ++i) acc[i] = dot8(wq[it][i], x[it], acc[i]);
+  const float rstd = rstd_of(wave_sum_fast(ss) / (float)K + a.eps, a.fast_math != 0);  // a wave covers all of K
+#pragma unroll
+  for (int i = 0; i < PR; ++i) acc[i] = wave_sum_fast(acc[i]) * rstd + bv[i];
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+#pragma unroll
+  for (int i = 0; i < PR; ++i) {
+    if (prow[i] < 0) continue;
+    if (lane == 0 && a.out) a.out[prow[i]] = acc[i];
+    if (acc[i] > best) { best = acc[i]; bi = prow[i]; }
+  }
+  if (lane == 0) { am_v[wave][0] = best; am_i[wave][0] = bi; }
+  __syncthreads();
+  if (tid == 0) {
+    float v = am_v[0][0];
+    int ix = am_i[0][0];
+    for (int w = 1; w < 4; ++w)
+      if (am_v[w][0] > v || (am_v[w][0] == v && am_i[w][0] < ix)) { v = am_v[w][0]; ix = am_i[w][0]; }
+    out_v = v;
+    out_i = ix;
+  }
+}
+
+template <int PR, int KI>
+__global__ __launch_bounds__(256) void gemv1_head_kernel(GemvArgs a) {
+  __shared__ float am_v[4][1];
+  __shared__ int am_i[4][1];
+  float v;
+  int ix;
+  gemv1_head_block<PR, KI>(a, blockIdx.x, am_v, am_i, v, ix);
+  if (threadIdx.x == 0) {
+    a.part_val[blockIdx.x] = v;
+    a.part_idx[blockIdx.x] = ix;
+  }
+}
+
+// ---- pruned argmax of the one-sequence lm_head ------------------------------------------------------------
+// The decode step only needs argmax_r l_r, l_r = rstd * sum_k y_k W_rk (y = x o w_norm, fp32; W bf16).  Pass 1 streams the int8 copy
+// Q (model.h lm_head_q: half the bytes) and gives every row an approximate logit a_r and a bound e_r with |a_r - l_r| <= e_r, where
+// l_r is the fp32 value gemv1_head_block computes.  T = max_r (a_r - e_r) is then <= the logit of some row, so a row with
+// a_r + e_r < T cannot be the maximum, nor tie with it.  Pass 2 recomputes, with gemv1_head_block, every 16-row block whose
+// hi_b = max (a_r + e_r) is not below T and reduces them to one (value, row) partial per workgroup.  The ids are those of the
+// unpruned launch; the worst case (every block a candidate) is one extra full pass.
+//
+// The bound.  Let ŷ_k be the fp32 products x_k * w_k both passes form (the same lanes, the same instruction), G = sum ŷ_k W_rk and
+// P = sum ŷ_k Q_rk exactly, Ĝ and P̂ their fp32 evaluations, s = s_r.  Each term of either dot product passes through at most
+// K/64 + 1 roundings in its lane (the product -- none if fused -- and the chain of packed adds and FMAs over the lane's K/64
+// columns) and 6 in the 64-lane wave_sum_fast tree; whatever the order and the fusing, the classic bound (Higham, Accuracy and
+// Stability of Numerical Algorithms, 3.1) gives |Ĝ - G| <= γ sum|ŷ_k W_rk| with γ = n u / (1 - n u), u = 2^-24, n any upper bound
+// on the roundings per term.  n = cols >= K/64 + 7 (cols = 1024 or 2048 padded columns) is used.  With Cauchy-Schwarz:
+//   |Ĝ - G| <= γ ||ŷ|| ||W_r||,   |s P̂ - s P| <= γ ||ŷ|| ||s Q_r||,   |G - s P| = |ŷ . (W_r - s Q_r)| <= ||ŷ|| ||W_r - s Q_r||
+//   => |Ĝ - s P̂| <= ||ŷ|| (dn_r + γ (wn_r + qn_r)),  and  l_r = fl(Ĝ rstd), a_r = fl(fl(P̂ s) rstd).
+// The three roundings of the final products add at most 3.1 u (|a_r| + |l_r - a_r|); the fp32 evaluation of ||ŷ|| (relative
+// error <= γ/2 + u) and of e_r itself (< 8 u) are covered by the relative margin 2^-10; 2^-20 |a_r| covers the final roundings,
+// and 1e-30 the absolute error of products that underflow.  dn, wn, qn are rounded up by the packer.
+// NaN or infinite bounds make the block a candidate (hi = +inf): such rows are rescored, never skipped.
+struct LmHeadArgsDev {
+  GemvArgs g;
+  const int8_t* Wq; const float* qs; int qcols;
+  float gamma;
+  float* blk_lo; float* blk_hi; int n_blk;
+  float* dbg;  // [N][2] (a_r, e_r), debug taps only
+  int* stats;  // [2] += candidate blocks, += 1 per step (pass 2; never read by the step)
+};
+
+__device__ __forceinline__ float dotq8(uint32_t lo, uint32_t hi, const float (&x)[8], float s) {
+  f32x2_t a = f32x2_t{(float)(int8_t)lo, (float)(int8_t)(lo >> 8)} * f32x2_t{x[0], x[1]};
+  a += f32x2_t{(float)(int8_t)(lo >> 16), (float)((int32_t)lo >> 24)} * f32x2_t{x[2], x[3]};
+  a += f32x2_t{(float)(int8_t)hi, (float)(int8_t)(hi >> 8)} * f32x2_t{x[4], x[5]};
+  a += f32x2_t{(float)(int8_t)(hi >> 16), (float)((int32_t)hi >> 24)} * f32x2_t{x[6], x[7]};
+  return s + (a.x + a.y);
+}
+
+// The int8 copy: one wave per row.  Every value is formed in fp64 from the bf16 weights; the three norms are rounded up to fp32
+// after a relative margin of 2^-40 that covers the fp64 summation.
+__global__ __launch_bounds__(256) void lm_head_quantize_kernel(const uint16_t* W, int N, int K, int cols, int8_t* Q, float* qs) {
+  const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= N) return;  // wave-uniform
+  const uint16_t* w = W + (size_t)r * K;
+  float m = 0.f;
+  for (int k = lane; k < K; k += 64) m = fmaxf(m, fabsf(__uint_as_float((uint32_t)w[k] << 16)));
+  m = wave_max(m);
+  const bool fin = isfinite(m);  // (fmaxf drops NaN: a NaN row is caught by the norms below)
+  const float s = fin ? (float)((double)m / 127.0) : 0.f;
+  double dn = 0.0, wn = 0.0, qn = 0.0;
+  for (int k = lane; k < K; k += 64) {
+    const double v = __uint_as_float((uint32_t)w[k] << 16);
+    const double q = s > 0.f ? fmin(127.0, fmax(-127.0, rint(v / (double)s))) : 0.0;
+    Q[(size_t)r * cols + ((k % 512) / 8) * (cols / 64) + (k / 512) * 8 + k % 8] = (int8_t)q;
+    const double e = v - (double)s * q;
+    dn += e * e; wn += v * v; qn += q * q;
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    dn += __shfl_xor(dn, o); wn += __shfl_xor(wn, o); qn += __shfl_xor(qn, o);
+  }
+  if (lane == 0) {
+    auto up = [](double v) {  // smallest float >= v (1 + 2^-40: the fp64 sums' own rounding)
+      v *= 1.0 + 0x1p-40;
+      const float f = (float)v;
+      return (double)f < v ? nextafterf(f, INFINITY) : f;
+    };
+    float4 o = make_float4(s, up(sqrt(dn)), up(sqrt(wn)), up((double)s * sqrt(qn)));
+    if (!fin || !isfinite(o.y) || !isfinite(o.z)) o = make_float4(0.f, INFINITY, INFINITY, 0.f);  // no bound: always rescored
+    reinterpret_cast<float4*>(qs)[r] = o;
+  }
+}
+
+// Pass 1: one wave per 16-row block, 16 rows x cols/64 bytes per lane in flight (the bf16 launch: 4 rows x 2 x cols/64); no barrier
+template <int KI>
+__global__ __launch_bounds__(256) void lm_head_approx_kernel(LmHeadArgsDev p) {
+  constexpr int R = 16, NQ = KI / 2;  // rows per wave; 16-byte pieces of an int8 row per lane
+  const GemvArgs& a = p.g;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int K = a.K, blk = blockIdx.x * 4 + wave;
+  if (blk >= p.n_blk) return;  // wave-uniform
+  bool kin[KI];
+  int kk[KI];
+#pragma unroll
+  for (int it = 0; it < KI; ++it) {
+    const int k = lane * 8 + it * 512;
+    kin[it] = k < K;
+    kk[it] = kin[it] ? k : 0;
+  }
+  float4 xr[KI][2], nr[KI][2];
+#pragma unroll
+  for (int it = 0; it < KI; ++it) {
+    xr[it][0] = *reinterpret_cast<const float4*>(a.x + kk[it]);
+    xr[it][1] = *reinterpret_cast<const float4*>(a.x + kk[it] + 4);
+    nr[it][0] = *reinterpret_cast<const float4*>(a.rms_w + kk[it]);
+    nr[it][1] = *reinterpret_cast<const float4*>(a.rms_w + kk[it] + 4);
+  }
+  uint4 wq[R][NQ];
+#pragma unroll
+  for (int i = 0; i < R; ++i) {
+    const int r = blk * R + i, row = r < a.N ? r : a.N - 1;
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) wq[i][j] = ld_stream16(p.Wq + (size_t)row * p.qcols + lane * (KI * 8) + j * 16);
+  }
+  const int my_r = blk * R + lane;  // lanes 0..15 finish one row each
+  const bool my_valid = lane < R && my_r < a.N;
+  const float4 q = reinterpret_cast<const float4*>(p.qs)[my_valid ? my_r : 0];  // {s, dn, wn, qn}
+  __builtin_amdgcn_sched_barrier(0);  // every request is issued before anything is waited for
+  float x[KI][8];
+  float ss = 0.f, yy = 0.f;
+#pragma unroll
+  for (int it = 0; it < KI; ++it) {  // exactly gemv1_head_block's x, sum(x^2) and ŷ
+    const float4 v0 = xr[it][0], v1 = xr[it][1];
+    const float xv[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) x[it][e] = (K == KI * 512 || kin[it]) ? xv[e] : 0.f;
+    const float4 w0 = nr[it][0], w1 = nr[it][1];
+    const float wv[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { ss += x[it][e] * x[it][e]; x[it][e] *= wv[e]; }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) yy += x[it][e] * x[it][e];
+  }
+  float acc[R];
+#pragma unroll
+  for (int i = 0; i < R; ++i) {
+    acc[i] = 0.f;
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {  // piece j: columns of it = 2j (bytes 0..7) and it = 2j + 1 (bytes 8..15)
+      acc[i] = dotq8(wq[i][j].x, wq[i][j].y, x[2 * j], acc[i]);
+      acc[i] = dotq8(wq[i][j].z, wq[i][j].w, x[2 * j + 1], acc[i]);
+    }
+  }
+  const float rstd = rstd_of(wave_sum_fast(ss) / (float)K + a.eps, a.fast_math != 0);
+  const float ny = sqrtf(wave_sum_fast(yy));
+  float mine = 0.f;
+#pragma unroll
+  for (int i = 0; i < R; ++i) {
+    const float t = wave_sum_fast(acc[i]);
+    if (lane == i) mine = t;
+  }
+  const float av = (mine * q.x) * rstd;
+  const float ev = (rstd * ny) * (q.y + p.gamma * (q.z + q.w)) * (1.0f + 0x1p-10f) + fabsf(av) * 0x1p-20f + 1e-30f;
+  float lo = -INFINITY, hi = -INFINITY;
+  if (my_valid) {
+    lo = av - ev;
+    hi = av + ev;
+    if (!(lo <= hi) || hi == INFINITY) { lo = -INFINITY; hi = INFINITY; }  // NaN / overflow: always rescored
+    if (p.dbg) { p.dbg[(size_t)my_r * 2] = av; p.dbg[(size_t)my_r * 2 + 1] = ev; }
+  }
+  lo = wave_max(lo);
+  hi = wave_max(hi);
+  if (lane == 0) { p.blk_lo[blk] = lo; p.blk_hi[blk] = hi; }
+}
+
+// Pass 2: T over every block, then this workgroup's blocks blockIdx.x + j * gridDim.x (at most 256) that pass hi_b >= T,
+// rescored in ascending order; one (value, row) partial per workgroup.  No workgroup waits for another.
+template <int PR, int KI>
+__global__ __launch_bounds__(256) void lm_head_rescore_kernel(LmHeadArgsDev p) {
+  __shared__ float am_v[4][1];
+  __shared__ int am_i[4][1];
+  __shared__ float red[4];
+  __shared__ int cand[256];
+  constexpr int PRE = 10;  // float4 of block minima per thread in the first batch (40 960 blocks); more are folded by the loop below
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nb = p.n_blk, n4 = (nb + 3) / 4, G = gridDim.x;
+  const float4* lo4 = reinterpret_cast<const float4*>(p.blk_lo);
+  float4 lv[PRE];
+#pragma unroll
+  for (int j = 0; j < PRE; ++j) {
+    const int i4 = tid + j * 256;
+    lv[j] = lo4[i4 < n4 ? i4 : n4 - 1];
+  }
+  const int mb = blockIdx.x + tid * G;  // this thread's block
+  const float hv = p.blk_hi[mb < nb ? mb : nb - 1];
+  float t = -INFINITY;
+  auto fold = [&](const float4& v, int i4) {
+    const int i = i4 * 4;
+    if (i < nb) t = fmaxf(t, v.x);
+    if (i + 1 < nb) t = fmaxf(t, v.y);
+    if (i + 2 < nb) t = fmaxf(t, v.z);
+    if (i + 3 < nb) t = fmaxf(t, v.w);
+  };
+#pragma unroll
+  for (int j = 0; j < PRE; ++j) fold(lv[j], tid + j * 256);
+  for (int i4 = tid + PRE * 256; i4 < n4; i4 += 256) fold(lo4[i4], i4);
+  t = wave_max(t);
+  if (lane == 0) red[wave] = t;
+  cand[tid] = 0;
+  __syncthreads();
+  const float T = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  if (mb < nb) cand[tid] = !(hv < T);
+  __syncthreads();
+  const int nj = (nb - blockIdx.x + G - 1) / G;
+  float bv = -INFINITY;
+  int bi = 0x7fffffff, nc = 0;
+  for (int j = 0; j < nj; ++j) {
+    if (!cand[j]) continue;  // uniform
+    float v = 0.f;
+    int ix = 0;
+    gemv1_head_block<PR, KI>(p.g, blockIdx.x + j * G, am_v, am_i, v, ix);
+    if (tid == 0 && (v > bv || (v == bv && ix < bi))) { bv = v; bi = ix; }
+    ++nc;
+    __syncthreads();  // am_v / am_i are reused by the next candidate
+  }
+  if (tid == 0) {
+    p.g.part_val[blockIdx.x] = bv;
+    p.g.part_idx[blockIdx.x] = bi;
+    if (p.stats) {
+      if (nc) atomicAdd(&p.stats[0], nc);
+      if (blockIdx.x == 0) atomicAdd(&p.stats[1], 1);
+    }
+  }
+}
+
 // ---- NB in {2, 4}: x staged through LDS once per workgroup ---------------------------------------------
 template <int NB, int PR, int PF>
 __global__ __launch_bounds__(256) void gemvn_kernel(GemvArgs a) {
@@ -586,9 +899,8 @@ void launch1k(const GemvArgs& a, hipStream_t s) {
     // (round 6: 609.7 -> 595.1 us per step at 0.6B, ids identical; profiles/r6_ab_gemv_x_lds.txt).  Not where it was measured to
     // lose: K = 2048 (+18 %: 32 KiB of LDS per workgroup halves the residency of the 1536-workgroup gate / up launch), the down
     // projection (+4 %: x in front of the weights delays them), the lm_head (+1.3 %: a barrier in each of 9496 workgroups).
-    if constexpr (KI == 2) {
-      if (a.mode != 3) { hipLaunchKernelGGL((gemv1_kernel<PR, KI, true, false, 0, true>), grid, block, 0, s, a); return; }
-    }
+    if (a.mode == 3) { hipLaunchKernelGGL((gemv1_head_kernel<PR, KI>), grid, block, 0, s, a); return; }
+    if constexpr (KI == 2) { hipLaunchKernelGGL((gemv1_kernel<PR, KI, true, false, 0, true>), grid, block, 0, s, a); return; }
     hipLaunchKernelGGL((gemv1_kernel<PR, KI, true, false>), grid, block, 0, s, a);
   } else {
     hipLaunchKernelGGL((gemv1_kernel<PR, KI, false, false>), grid, block, 0, s, a);
@@ -608,6 +920,51 @@ void launchn(const GemvArgs& a, hipStream_t s) {
 }
 
 }  // namespace
+
+static LmHeadArgsDev lm_head_dev_args(const LmHeadPruneArgs& a) {
+  LmHeadArgsDev p{};
+  p.g = a.g; p.Wq = a.Wq; p.qs = a.qs; p.qcols = a.qcols; p.blk_lo = a.blk_lo; p.blk_hi = a.blk_hi; p.n_blk = lm_head_prune_blocks(a.g);
+  p.dbg = a.dbg; p.stats = a.stats;
+  const double nu = (double)a.qcols * 0x1p-24;  // γ of the bound above, n = cols
+  p.gamma = (float)(nu / (1.0 - nu)) * (1.0f + 0x1p-20f);
+  return p;
+}
+int lm_head_prune_blocks(const GemvArgs& g) { return (g.N + 15) / 16; }
+const char* launch_lm_head_quantize(const uint16_t* W, int N, int K, int8_t* Q, float* qs, hipStream_t s) {
+  const int cols = lm_head_q_cols(K);
+  if (cols == 0 || K % 8 != 0) return "lm_head_quantize: hidden size beyond the one-sequence GEMV";
+  if (hipMemsetAsync(Q, 0, (size_t)N * cols, s) != hipSuccess) return "lm_head_quantize: memset failed";
+  hipLaunchKernelGGL(lm_head_quantize_kernel, dim3((N + 3) / 4), dim3(256), 0, s, W, N, K, cols, Q, qs);
+  return nullptr;
+}
+const char* lm_head_prune_check(const LmHeadPruneArgs& a) {
+  const GemvArgs& g = a.g;
+  if (g.mode != 3 || !g.rms_w || !g.x || g.attn_po || g.bias) return "lm_head_prune: needs the plain mode-3 GEMV with a fused norm";
+  if (gemv_rows_per_wave(g) != 4 || gemv_blocks(g) != lm_head_prune_blocks(g)) return "lm_head_prune: the GEMV does not run 16-row blocks here";
+  if (g.K % 8 != 0 || a.qcols != lm_head_q_cols(g.K)) return "lm_head_prune: int8 row width does not match the hidden size";
+  if (!a.Wq || !a.qs || !a.blk_lo || !a.blk_hi || !g.part_val || !g.part_idx) return "lm_head_prune: missing buffer";
+  return nullptr;
+}
+const char* launch_lm_head_approx(const LmHeadPruneArgs& a, hipStream_t s) {
+  if (const char* e = lm_head_prune_check(a)) return e;
+  const LmHeadArgsDev p = lm_head_dev_args(a);
+  const dim3 grid((p.n_blk + 3) / 4), block(256);
+  if (a.qcols == 1024) hipLaunchKernelGGL(lm_head_approx_kernel<2>, grid, block, 0, s, p);
+  else hipLaunchKernelGGL(lm_head_approx_kernel<4>, grid, block, 0, s, p);
+  return nullptr;
+}
+int lm_head_rescore_groups(const GemvArgs& g, int n_cu) {
+  const int nb = lm_head_prune_blocks(g);
+  return std::min(nb, std::max(n_cu > 0 ? n_cu : 256, (nb + 255) / 256));
+}
+const char* launch_lm_head_rescore(const LmHeadPruneArgs& a, int groups, hipStream_t s) {
+  if (const char* e = lm_head_prune_check(a)) return e;
+  const LmHeadArgsDev p = lm_head_dev_args(a);
+  if (groups < 1 || groups > a.g.part_stride || (p.n_blk + groups - 1) / groups > 256) return "lm_head_prune: bad rescore grid";
+  if (a.qcols == 1024) hipLaunchKernelGGL((lm_head_rescore_kernel<4, 2>), dim3(groups), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((lm_head_rescore_kernel<4, 4>), dim3(groups), dim3(256), 0, s, p);
+  return nullptr;
+}
 
 const char* launch_gemv(const GemvArgs& a0, int NB, hipStream_t s) {
   if (a0.K % 8 != 0) return "gemv: K must be a multiple of 8";

@@ -66,6 +66,7 @@ struct Knobs {
   std::atomic<int> skinny_q{1};                 // Q3A_SKINNY_Q: quarter workgroups for the o / down projections
   std::atomic<int> eos_run_ahead{1};            // Q3A_EOS_RUN_AHEAD: decode steps kept enqueued ahead of the device in natural-EOS mode.  1: exactly the steps needed are executed; paired with a fixed-N run of the same engine (profiles/r5_eos_run_ahead_ab.txt, two processes): 1 costs +0.03 / +1.24 ms per 100 tokens, 2 costs +2.07 / +1.86 ms (one wasted step + the same launch latency), 3 +1.3 / +1.2, 4 +3.3 / +3.1
   std::atomic<int> skinny_glu_hp3{1};           // Q3A_SKINNY_GLU_HP3: gate/up skinny GEMM as 3 half-pair tiles per workgroup when the pair form has more workgroups than CUs (k_skinny.hip HP; 0 = off, 2 = whenever the shape allows)
+  std::atomic<int> lm_head_prune{1};            // Q3A_LM_HEAD_PRUNE: one-sequence decode argmax from an int8 pre-pass + bf16 rescore of the candidate blocks (k_gemv.hip; bit-identical ids)
   // Round 6 removed nine knobs together with the code only they selected (docs/HISTORY.md "Pruned in round 6"; last present at commit
   // caf7a05): fuse_qkv_attn, dattn_pair_split, fattn_pipe, rope_variant, rope_twice (measured alternatives that lost / finished debug
   // aids), gemm16_ring, gemm256_resid_prefetch, live_key_splits, skinny_glu_2pass (the winning form is now the only form).
@@ -186,6 +187,30 @@ const char* launch_gemv(const GemvArgs& a, int NB, hipStream_t s);
 constexpr int GEMV_ATTN_MAX_TABLE = 1024;  // min(NB,4) * heads * nsplit must fit (else merge with launch_attn_combine first)
 int gemv_blocks(const GemvArgs& a);        // grid size launch_gemv uses (= number of argmax partials in mode 3)
 int gemv_rows_per_wave(const GemvArgs& a);
+
+// Exact argmax of the one-sequence lm_head (mode 3, fused final norm) from an int8 pre-pass (k_gemv.hip): pass 1 streams the int8
+// copy and writes per 16-row block lo_b / hi_b of the approximate logits +- a rigorous bound; pass 2 (`groups` workgroups) rescores
+// with the bf16 arithmetic of the unpruned launch only the blocks with hi_b >= max lo_b and leaves ONE argmax partial per workgroup in
+// g.part_val / g.part_idx (argmax_finalize with n_part = groups).  The ids are those of launch_gemv.
+struct LmHeadPruneArgs {
+  GemvArgs g;                   // the mode-3 launch it replaces (g.out is not written by pass 1; pass 2 stores rescored rows if set)
+  const int8_t* Wq; int qcols;  // launch_lm_head_quantize: [N][qcols], columns in the GEMV's lane order
+  const float* qs;              // [N][4] {s, ||W - sQ||, ||W||, ||sQ||}
+  float* blk_lo; float* blk_hi; // [lm_head_prune_blocks(g)] (pass 1 -> pass 2; blk_lo readable as float4: round up to 4)
+  float* dbg;                   // nullable: [N][2] (approximate logit, bound) per row (pass 1)
+  int* stats;                   // nullable: [2] += candidate blocks, += 1 per pass 2 (debug; the step never reads it)
+};
+// columns of one int8 lm_head row (a multiple of 1024: 16 (32) bytes per lane of a wave), 0 = hidden size beyond the GEMV
+inline int lm_head_q_cols(int hidden) { return hidden <= 1024 ? 1024 : hidden <= 2048 ? 2048 : 0; }
+// int8 copy of a bf16 [N][K] lm_head for LmHeadPruneArgs (one launch at engine set-up): Q [N][cols] zero-padded, row r scaled by
+// s_r = max|W_r| / 127 (rounded to nearest), columns in the GEMV's lane order (lane l owns columns l*8 + it*512 + e, it < cols/512,
+// e < 8, as ONE piece of cols/64 bytes); qs [N][4] = {s, ||W - sQ||, ||W||, ||sQ||}, the norms in fp64, rounded up to fp32
+const char* launch_lm_head_quantize(const uint16_t* W, int N, int K, int8_t* Q, float* qs, hipStream_t s);
+int lm_head_prune_blocks(const GemvArgs& g);
+int lm_head_rescore_groups(const GemvArgs& g, int n_cu);
+const char* lm_head_prune_check(const LmHeadPruneArgs& a);  // null when both passes can run on these arguments
+const char* launch_lm_head_approx(const LmHeadPruneArgs& a, hipStream_t s);
+const char* launch_lm_head_rescore(const LmHeadPruneArgs& a, int groups, hipStream_t s);
 
 // Skinny MFMA GEMM (k_skinny.hip): 4 < S <= 32 sequences, weights streamed once.
 struct SkinnyArgs {
