@@ -35,10 +35,14 @@ typedef struct q3a_opts {
   int32_t debug_taps;     /* 1: keep per-stage intermediate tensors readable through q3a_debug_read      */
   int32_t valu_attention; /* 1: use the fp32 VALU attention kernels in default mode too (A/B against the
                              MFMA flash-attention kernels; precise mode always uses them)                 */
-  int32_t reserved[11];
+  int32_t token_logprobs; /* 1: every generated id also gets its log-probability logit[id] - logsumexp(logits), computed on
+                             the device inside the step (graph-replayed or eager) and read with q3a_fetch_logprobs.
+                             The one-sequence step then runs the full lm_head GEMV instead of the pruned argmax
+                             (same ids).  0 (default): today's kernels, launches and ids                  */
+  int32_t reserved[10];
 } q3a_opts;
 
-/* Fill `o` with the defaults (precise=0, max_new_tokens=4096, use_graph=1, debug_taps=0). */
+/* Fill `o` with the defaults (precise=0, max_new_tokens=4096, use_graph=1, debug_taps=0, token_logprobs=0). */
 void q3a_opts_default(q3a_opts* o);
 
 /* Model dimensions as parsed from config.json (replaces AsrConfig::from_file, src/config.rs:115-121). */
@@ -134,6 +138,14 @@ int32_t q3a_run_resident(q3a_engine* e, const int32_t* lang_prefix_ids, int32_t 
 /* Generated ids of the last q3a_run_resident: out_ids host [B][stride], out_lens [B] (EOS excluded,
  * as generated_ids in src/inference.rs:167). */
 int32_t q3a_fetch_ids(q3a_engine* e, int32_t* out_ids, int32_t stride, int32_t* out_lens);
+
+/* Log-probability (natural log, fp32) of every id q3a_fetch_ids returns for the last run, same order, same lengths
+ * (EOS excluded in the natural-EOS mode): out_lp host [B][stride], out_lens [B].  Needs opts.token_logprobs = 1; works after
+ * q3a_run_resident, q3a_transcribe_batch[_ptrs] and the stage API (q3a_prefill + q3a_decode_step: the lp of each step's argmax,
+ * also when the next token is forced).  Whisper's avg_logprob is the mean of a row.  Fails (q3a_last_error) on an engine created
+ * without the option and before anything has been generated.  q3a_group_transcribe returns no log-probabilities: a caller that
+ * needs them runs each rank's slice (q3a_group_partition) on q3a_group_engine's handle and fetches them there. */
+int32_t q3a_fetch_logprobs(q3a_engine* e, float* out_lp, int32_t stride, int32_t* out_lens);
 
 /* upload + run + fetch: AsrInference::transcribe steps 2-8 (src/inference.rs:95-200) for B utterances, host PCM in,
  * generated ids on the host out -- the window SURVEY.md section 8d times.  The input copy is overlapped with the front

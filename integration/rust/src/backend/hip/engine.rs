@@ -22,7 +22,8 @@ pub struct q3a_opts {
     pub use_graph: i32,
     pub debug_taps: i32,
     pub valu_attention: i32,
-    pub reserved: [i32; 11],
+    pub token_logprobs: i32,
+    pub reserved: [i32; 10],
 }
 
 #[link(name = "q3asr_hip")]
@@ -34,6 +35,7 @@ extern "C" {
     pub fn q3a_last_error(e: *const q3a_engine) -> *const c_char;
     pub fn q3a_transcribe_batch(e: *mut q3a_engine, pcm16k: *const f32, n_samples: *const i64, b: i32, lang_prefix_ids: *const i32,
                                 n_prefix: i32, max_new: i32, fixed_new_tokens: i32, out_ids: *mut i32, stride: i32, out_lens: *mut i32) -> i32;
+    pub fn q3a_fetch_logprobs(e: *mut q3a_engine, out_lp: *mut f32, stride: i32, out_lens: *mut i32) -> i32;
     pub fn q3a_transcribe_batch_ptrs(e: *mut q3a_engine, pcm16k: *const *const f32, n_samples: *const i64, b: i32, lang_prefix_ids: *const i32,
                                      n_prefix: i32, max_new: i32, fixed_new_tokens: i32, out_ids: *mut i32, stride: i32, out_lens: *mut i32) -> i32;
     pub fn q3a_group_create(model_dir: *const c_char, n_gpus: i32, devices: *const i32, opts: *const q3a_opts, out: *mut *mut q3a_group) -> i32;

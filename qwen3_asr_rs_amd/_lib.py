@@ -14,7 +14,7 @@ SYMBOLS = [
     "q3a_opts_default", "q3a_device_count", "q3a_engine_create", "q3a_arena_bytes", "q3a_arena_pack", "q3a_engine_create_from_arena",
     "q3a_engine_destroy", "q3a_last_error", "q3a_get_dims", "q3a_weights_rounded", "q3a_num_frames", "q3a_num_audio_tokens",
     "q3a_build_prompt", "q3a_mel", "q3a_encode", "q3a_prefill", "q3a_decode_step", "q3a_set_next_tokens",
-    "q3a_upload_pcm", "q3a_run_resident", "q3a_fetch_ids", "q3a_transcribe_batch", "q3a_transcribe_batch_ptrs", "q3a_io_timings_last", "q3a_stage_timings",
+    "q3a_upload_pcm", "q3a_run_resident", "q3a_fetch_ids", "q3a_fetch_logprobs", "q3a_transcribe_batch", "q3a_transcribe_batch_ptrs", "q3a_io_timings_last", "q3a_stage_timings",
     "q3a_profile_decode_step", "q3a_profile_weight_stream", "q3a_measure_peaks", "q3a_debug_read", "q3a_debug_set", "q3a_selftest_gemm", "q3a_selftest_gemm16",
     "q3a_load_audio", "q3a_resample", "q3a_resample_rubato", "q3a_free", "q3a_tokenizer_create", "q3a_tokenizer_destroy",
     "q3a_tokenizer_decode", "q3a_tokenizer_encode", "q3a_normalize_nfc", "q3a_parse_asr_output", "q3a_capitalize_first",
@@ -31,7 +31,7 @@ class Peaks(C.Structure):
 
 class Opts(C.Structure):
     _fields_ = [("precise", C.c_int32), ("max_new_tokens", C.c_int32), ("use_graph", C.c_int32),
-                ("debug_taps", C.c_int32), ("valu_attention", C.c_int32), ("reserved", C.c_int32 * 11)]
+                ("debug_taps", C.c_int32), ("valu_attention", C.c_int32), ("token_logprobs", C.c_int32), ("reserved", C.c_int32 * 10)]
 
 
 class DimsC(C.Structure):
@@ -96,6 +96,7 @@ def load() -> C.CDLL:
         "q3a_upload_pcm": (i32, [P, f32p, i64p, i32]),
         "q3a_run_resident": (i32, [P, i32p, i32, i32, i32]),
         "q3a_fetch_ids": (i32, [P, i32p, i32, i32p]),
+        "q3a_fetch_logprobs": (i32, [P, f32p, i32, i32p]),
         "q3a_transcribe_batch": (i32, [P, f32p, i64p, i32, i32p, i32, i32, i32, i32p, i32, i32p]),
         "q3a_transcribe_batch_ptrs": (i32, [P, C.POINTER(P), i64p, i32, i32p, i32, i32, i32, i32p, i32, i32p]),
         "q3a_io_timings_last": (i32, [P, C.POINTER(IoTimings)]),

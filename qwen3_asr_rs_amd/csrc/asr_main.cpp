@@ -2,8 +2,12 @@
 // Same argv contract, same usage text on stderr + exit status 1, same stdout ("Language: ...\nText: ...").
 // Logging: RUST_LOG=info|debug (default info) prints the reference's progress lines to stderr
 // (src/inference.rs:31-103,203-205).  Input: WAV files (the FFmpeg path of src/audio.rs is out of scope).
+// Q3A_TOKEN_LOGPROBS=1 adds one stdout line after "Text:": "Confidence: avg_logprob <mean token log-probability>
+// min_token_prob <smallest token probability>" (q3a_fetch_logprobs); without it stdout and stderr are unchanged.
 #include <sys/stat.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -51,6 +55,9 @@ int main(int argc, char** argv) {
   logf(1, "Loading model from \"%s\"", model_path);
   q3a_opts opts;
   q3a_opts_default(&opts);
+  const char* lp_env = getenv("Q3A_TOKEN_LOGPROBS");
+  const bool want_lp = lp_env && atoi(lp_env) != 0;
+  opts.token_logprobs = want_lp ? 1 : 0;
   q3a_engine* eng = nullptr;
   if (q3a_engine_create(model_path, 0, &opts, &eng) != 0) return die(std::string("Failed to load model: ") + q3a_last_error(nullptr));
   if (q3a_weights_rounded(eng))
@@ -89,6 +96,14 @@ int main(int argc, char** argv) {
                            ids.data(), max_new, &len) != 0)
     return die(std::string("Transcription failed: ") + q3a_last_error(eng));
   q3a_free(pcm);
+  std::vector<float> lps;
+  if (want_lp) {
+    lps.resize((size_t)max_new);
+    int32_t lp_len = 0;
+    if (q3a_fetch_logprobs(eng, lps.data(), max_new, &lp_len) != 0)
+      return die(std::string("Transcription failed: ") + q3a_last_error(eng));
+    lps.resize((size_t)lp_len);
+  }
   q3a_timings tm;
   q3a_stage_timings(eng, &tm);
   if (g_level >= 1) {
@@ -108,6 +123,13 @@ int main(int argc, char** argv) {
   q3a_parse_asr_output(raw.c_str(), language != nullptr, lang.data(), (int32_t)lang.size(), text.data(), (int32_t)text.size());
   printf("Language: %s\n", lang.data());  // main.rs:77-78
   printf("Text: %s\n", text.data());
+  if (want_lp) {  // mean over the generated tokens (Whisper's avg_logprob) and the least likely token
+    double sum = 0.0;
+    float mn = INFINITY;
+    for (float v : lps) { sum += v; mn = std::min(mn, v); }
+    const double avg = lps.empty() ? NAN : sum / (double)lps.size();
+    printf("Confidence: avg_logprob %.6f min_token_prob %.6f\n", avg, lps.empty() ? NAN : std::exp((double)mn));
+  }
   q3a_tokenizer_destroy(tok);
   q3a_engine_destroy(eng);
   return 0;

@@ -154,6 +154,7 @@ struct q3a_engine {
   DevBuf dec_x, dec_ln, dec_qkv, dec_ctx, dec_act, kcache, vcache;
   DevBuf x_dec, d_pos, next_tok, out_ids, step_count, done, s_ln, s_qkv, s_ctx, s_act, logits, forced_tok, part_val, part_idx;
   DevBuf blk_lo, blk_hi;  // pruned lm_head argmax: per 16-row block bounds (pass 1 -> pass 2)
+  DevBuf part_sum, out_lp;  // opts.token_logprobs: log-sum channel of the argmax partials, [B][max_new] log-probabilities next to out_ids
   DevBuf lm_q, lm_qs;     // int8 lm_head copy + per-row scale and norms (init_lm_head_q)
   int lm_q_cols = 0;      // 0: no copy
   DevBuf prune_stats;     // [2] candidate blocks rescored, pass-2 launches (q3a_debug_read "lm_head_prune_stats"; never read by the step)
@@ -211,6 +212,7 @@ struct q3a_engine {
   std::map<std::string, size_t> tap_bytes;
 
   bool precise() const { return opts.precise != 0; }
+  bool token_lp() const { return opts.token_logprobs != 0; }
   bool kv_f32() const { return opts.precise != 0; }
   size_t kv_elem() const { return kv_f32() ? 4 : 2; }
   // GEMM-input activations (conv maps, norm outputs, attention context, FFN hidden) are stored as bf16 in the default
@@ -735,6 +737,7 @@ struct q3a_engine {
     s_act.ensure(ng * 32 * d.inter * 4); logits.ensure((size_t)b * d.vocab * 4);
     part_stride = std::max(128, (d.vocab + 3) / 4);  // >= blocks of the lm_head GEMV at 1 row per wave
     part_val.ensure((size_t)b * part_stride * 4); part_idx.ensure((size_t)b * part_stride * 4);
+    if (token_lp()) { part_sum.ensure((size_t)b * part_stride * 4); out_lp.ensure((size_t)b * max_new * 4); }
     {
       const size_t nblk4 = ((size_t)(d.vocab + 15) / 16 + 3) & ~size_t(3);  // lm_head_prune_blocks, rounded up for float4 reads
       blk_lo.ensure(nblk4 * 4); blk_hi.ensure(nblk4 * 4);
@@ -746,6 +749,7 @@ struct q3a_engine {
     HIPCHK(hipMemsetAsync(done.p, 0, (size_t)b, stream));
     HIPCHK(hipMemsetAsync(n_done.p, 0, 64, stream));
     HIPCHK(hipMemsetAsync(out_ids.p, 0, (size_t)b * max_new * 4, stream));
+    if (token_lp()) HIPCHK(hipMemsetAsync(out_lp.p, 0, (size_t)b * max_new * 4, stream));
     // drain the stream -- and the group streams: a run that threw mid-loop may have left run-ahead steps enqueued whose
     // argmax_finalize would still write the progress words -- BEFORE the words are reset
     HIPCHK(hipStreamSynchronize(stream));
@@ -766,7 +770,7 @@ struct q3a_engine {
   // source for DevBuf members and fails when one is missing here.
   std::vector<DevBuf*> step_bufs() {
     return {&kcache, &vcache, &x_dec, &d_pos, &next_tok, &out_ids, &step_count, &done, &s_ln, &s_qkv, &s_ctx, &s_act, &logits,
-            &part_val, &part_idx, &blk_lo, &blk_hi, &prune_stats, &attn_pm, &attn_pl, &attn_po, &nn_x, &nn_ss, &rope_cur, &rope_cos, &rope_sin, &n_done, &forced_tok};
+            &part_val, &part_idx, &part_sum, &out_lp, &blk_lo, &blk_hi, &prune_stats, &attn_pm, &attn_pl, &attn_po, &nn_x, &nn_ss, &rope_cur, &rope_cos, &rope_sin, &n_done, &forced_tok};
   }
   std::vector<const DevBuf*> step_bufs() const {
     auto v = const_cast<q3a_engine*>(this)->step_bufs();
@@ -789,12 +793,15 @@ struct q3a_engine {
     tap("head_in", x_dec.p, (size_t)S * H * 4);  // (debug taps) last-layer residual rows the final norm + lm_head read
     const double wbytes = 2.0 * V * H;
     int n_part = 0;
+    // token log-probabilities: every producer of argmax partials also writes their log-sum channel (null: off, today's kernels)
+    float* const psum = token_lp() ? part_sum.as<float>() : nullptr;
     if (S <= kGemvMaxSeq) {
       GemvArgs g{};
       g.fast_math = precise() ? 0 : 1;
       g.x = x_dec.as<float>(); g.ldx = H; g.rms_w = wf(L.final_norm); g.eps = d.rms_eps;
       g.W = wh(L.lm_head); g.N = V; g.K = H; g.mode = 3; g.out = logits.as<float>(); g.ldo = V;
-      g.part_val = part_val.as<float>(); g.part_idx = part_idx.as<int>(); g.part_stride = part_stride;
+      g.part_val = part_val.as<float>(); g.part_idx = part_idx.as<int>(); g.part_stride = part_stride; g.part_sum = psum;
+      // (with the log-sum channel lm_head_prune_check refuses: the pruned argmax never computes most logits, the full GEMV runs)
       LmHeadPruneArgs pa{};
       const bool prunable = S == 1 && !precise() && lm_q_cols > 0 && (pa = prune_args(g), !lm_head_prune_check(pa));
       if (prunable && opts.debug_taps == 1) {  // (debug taps) approximate logits and their bounds next to the stored logits
@@ -823,22 +830,23 @@ struct q3a_engine {
       if (S <= 32 && V % 4 == 0 && H % 64 == 0 && part_stride >= (V + 63) / 64) {
         // the argmax partials are the GEMM's epilogue (one per 64-column tile and row), and inside q3a_transcribe_batch /
         // q3a_run_resident nobody reads the logits: they are not stored (19 MB per step at 32 sequences)
-        ep.part_val = part_val.as<float>(); ep.part_idx = part_idx.as<int>(); ep.part_stride = part_stride;
+        ep.part_val = part_val.as<float>(); ep.part_idx = part_idx.as<int>(); ep.part_stride = part_stride; ep.part_sum = psum;
         if (!head_logits_) ep.out = nullptr;
         n_part = (V + 63) / 64;
         timed(Q3A_KC_GEMM, wbytes, [&] { KCHK(launch_gemm16(s_ln.as<uint16_t>(), H, wh(L.lm_head), S, V, H, ep, false, stream)); });
       } else {
         timed(Q3A_KC_GEMM, wbytes, [&] { KCHK(launch_gemm16(s_ln.as<uint16_t>(), H, wh(L.lm_head), S, V, H, ep, false, stream)); });
         n_part = 128;
-        timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_partials(logits.as<float>(), V, S, part_val.as<float>(), part_idx.as<int>(), part_stride, n_part, stream)); });
+        timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_partials(logits.as<float>(), V, S, part_val.as<float>(), part_idx.as<int>(), part_stride, n_part, stream, psum)); });
       }
     } else {
       timed(Q3A_KC_NORM, 0, [&] { KCHK(launch_rmsnorm(x_dec.as<float>(), wf(L.final_norm), s_ln.as<float>(), S, H, d.rms_eps, stream)); });
       timed(Q3A_KC_GEMM, wbytes, [&] { batched_proj(s_ln.as<float>(), H, wh(L.lm_head), V, H, nullptr, 0, logits.as<float>(), V, nullptr); });
       n_part = 128;
-      timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_partials(logits.as<float>(), V, S, part_val.as<float>(), part_idx.as<int>(), part_stride, n_part, stream)); });
+      timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_partials(logits.as<float>(), V, S, part_val.as<float>(), part_idx.as<int>(), part_stride, n_part, stream, psum)); });
     }
     FinalizeArgs f{};
+    f.part_sum = psum; f.out_lp = psum ? out_lp.as<float>() : nullptr;
     f.part_val = part_val.as<float>(); f.part_idx = part_idx.as<int>(); f.part_stride = part_stride; f.n_part = n_part;
     f.V = V; f.next_tok = next_tok.as<int>(); f.out_ids = out_ids.as<int>();
     f.out_stride = max_new; f.step_count = step_count.as<int>(); f.pos = d_pos.as<int>(); f.advance = advance;
@@ -1121,8 +1129,9 @@ struct q3a_engine {
     }
     char buf[256];
     // (one field per latched knob, as latched: packing several into one integer let distinct settings collide -- ADVICE r5)
-    snprintf(buf, sizeof(buf), "%d.%d.%d.%d.%d.%d.%d.%d.%d/%d/%d/%d/%p/%016llx", B, gsize, k_parallel_groups, k_skinny_q,
-             k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, (int)(min_P_ < 256), (int)head_logits_, live_nsplit_, max_ctx, max_new, (const void*)arena, (unsigned long long)h);
+    snprintf(buf, sizeof(buf), "%d.%d.%d.%d.%d.%d.%d.%d.%d.%d/%d/%d/%d/%p/%016llx", B, gsize, k_parallel_groups, k_skinny_q,
+             k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, (int)(min_P_ < 256), (int)head_logits_, (int)token_lp(), live_nsplit_,
+             max_ctx, max_new, (const void*)arena, (unsigned long long)h);
     return buf;
   }
 
@@ -1280,8 +1289,15 @@ struct q3a_engine {
 
   void fetch_ids(int32_t* out, int stride, int32_t* out_lens) {
     if (!have_prefill) fail("q3a_fetch_ids: nothing generated");
-    std::vector<int> all((size_t)B * max_new), sc(B);
+    std::vector<int> all((size_t)B * max_new);
     HIPCHK(hipMemcpy(all.data(), out_ids.p, all.size() * 4, hipMemcpyDeviceToHost));
+    generated_lens(all, out_lens);
+    for (int s = 0; s < B; ++s)
+      for (int i = 0; i < std::min(out_lens[s], stride); ++i) out[(size_t)s * stride + i] = all[(size_t)s * max_new + i];
+  }
+  // lengths of the generated ids per sequence (all = out_ids on the host)
+  void generated_lens(const std::vector<int>& all, int32_t* out_lens) {
+    std::vector<int> sc(B);
     HIPCHK(hipMemcpy(sc.data(), step_count.p, (size_t)B * 4, hipMemcpyDeviceToHost));
     for (int s = 0; s < B; ++s) {
       int n = std::min(sc[s], max_new), len = 0;
@@ -1290,8 +1306,19 @@ struct q3a_engine {
         if (!fixed_mode_ && (t == kEos0 || t == kEos1)) break;  // generated_ids excludes EOS (inference.rs:163-167)
       }
       out_lens[s] = len;
-      for (int i = 0; i < std::min(len, stride); ++i) out[(size_t)s * stride + i] = all[(size_t)s * max_new + i];
     }
+  }
+  // opts.token_logprobs: the log-probability of every id fetch_ids returns, same order and lengths
+  void fetch_logprobs(float* out, int stride, int32_t* out_lens) {
+    if (!token_lp()) fail("q3a_fetch_logprobs: the engine was created without opts.token_logprobs = 1");
+    if (!have_prefill) fail("q3a_fetch_logprobs: nothing generated");
+    std::vector<int> all((size_t)B * max_new);
+    std::vector<float> lp((size_t)B * max_new);
+    HIPCHK(hipMemcpy(all.data(), out_ids.p, all.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(lp.data(), out_lp.p, lp.size() * 4, hipMemcpyDeviceToHost));
+    generated_lens(all, out_lens);
+    for (int s = 0; s < B; ++s)
+      for (int i = 0; i < std::min(out_lens[s], stride); ++i) out[(size_t)s * stride + i] = lp[(size_t)s * max_new + i];
   }
   bool fixed_mode_ = false;
   bool head_logits_ = true;  // store the logits of a batched decode step (step API, debug taps); off inside run_resident
@@ -1306,6 +1333,7 @@ struct q3a_engine {
                       &enc_x, &enc_ln, &enc_qkv, &enc_ctx, &enc_ffn, &enc_segs, &audio_embeds, &ids, &audio_rowmap, &row_seq,
                       &row_pos, &dec_segs, &last_rows, &dec_x, &dec_ln, &dec_qkv, &dec_ctx, &dec_act, &kcache, &vcache, &x_dec,
                       &d_pos, &next_tok, &out_ids, &step_count, &done, &s_ln, &s_qkv, &s_ctx, &s_act, &logits, &forced_tok, &part_val, &part_idx, &attn_pm, &attn_pl, &attn_po,
+                      &part_sum, &out_lp,
                       &enc_ctx16, &dec_ctx16, &dec_q16, &zero_page, &rope_cur, &nn_x, &nn_ss, &n_done};
     for (auto* b : bufs) b->release();
     for (auto& kv : taps) kv.second.release();
@@ -1571,6 +1599,15 @@ int32_t q3a_fetch_ids(q3a_engine* e, int32_t* out_ids, int32_t stride, int32_t* 
   Q3A_TRY(e)
   HIPCHK(hipSetDevice(e->device));
   e->fetch_ids(out_ids, stride, out_lens);
+  Q3A_CATCH(e)
+}
+
+int32_t q3a_fetch_logprobs(q3a_engine* e, float* out_lp, int32_t stride, int32_t* out_lens) {
+  if (!e) return 1;
+  Q3A_TRY(e)
+  if (!out_lens || (stride > 0 && !out_lp)) fail("q3a_fetch_logprobs: bad argument");
+  HIPCHK(hipSetDevice(e->device));
+  e->fetch_logprobs(out_lp, stride, out_lens);
   Q3A_CATCH(e)
 }
 

@@ -73,7 +73,8 @@ template <int N> __device__ __forceinline__ void g16_wait_vm() {  // N = (A_LOAD
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-template <int BM, int BN, int BK, bool GLU, class ALoader, int NS = 2>
+// LP (token log-probabilities, M <= 32 argmax tile only): the argmax partials also carry ep.part_sum (dev.h lse_term)
+template <int BM, int BN, int BK, bool GLU, class ALoader, int NS = 2, bool LP = false>
 __global__ __launch_bounds__(256) void gemm16_kernel(ALoader A, const uint16_t* __restrict__ Wt, int M, int N, int K,
                                                      GemmEpilogue ep) {
   constexpr int CPR = BK / 8;                   // 16-B chunks per tile row
@@ -251,8 +252,14 @@ __global__ __launch_bounds__(256) void gemm16_kernel(ALoader A, const uint16_t* 
   if (!GLU && vec) {
     if (!pre) load_operands();
     constexpr bool ARGMAX = BM == 32 && MI == 1;  // only the M <= 32 tile carries the code
+    static_assert(!LP || ARGMAX, "the log-sum channel rides on the argmax partials");
     float bestv = -INFINITY;
     int besti = 0x7fffffff;
+    float lv[LP ? NI : 1][4];  // LP: this lane's logits (-inf where a row or column is out of range)
+    if constexpr (LP) {
+#pragma unroll
+      for (int j = 0; j < NI; ++j) lv[j][0] = lv[j][1] = lv[j][2] = lv[j][3] = -INFINITY;
+    }
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
       if (mrow[i] >= M || orow[i] < 0) continue;
@@ -272,6 +279,10 @@ __global__ __launch_bounds__(256) void gemm16_kernel(ALoader A, const uint16_t* 
 #pragma unroll
           for (int r = 0; r < 4; ++r)
             if (v[r] > bestv) { bestv = v[r]; besti = n + r; }
+          if constexpr (LP) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) lv[j][r] = v[r];
+          }
         }
         if (ep.out16) {
           uint2 pk;
@@ -287,16 +298,30 @@ __global__ __launch_bounds__(256) void gemm16_kernel(ALoader A, const uint16_t* 
       if (ep.part_val) {  // uniform
         // row m = lane & 15 of this wave's 16 rows: its four column groups sit in lanes l, l+16, l+32, l+48; then the two
         // column halves (waves wc = 0 / 1) meet in LDS (every wave has left the K loop: barrier first, the stages are free)
+        float sumv = 0.f;  // LP: sum of exp(l - bestv) over this lane's columns of row m
+        if constexpr (LP) {
+#pragma unroll
+          for (int j = 0; j < NI; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sumv += lse_term(1.f, lv[j][r], bestv);
+        }
 #pragma unroll
         for (int o = 16; o <= 32; o <<= 1) {
           const float ov = __shfl_xor(bestv, o, 64);
           const int oi = __shfl_xor(besti, o, 64);
+          const float os = LP ? __shfl_xor(sumv, o, 64) : 0.f;
+          const float pb = bestv;
           if (ov > bestv || (ov == bestv && oi < besti)) { bestv = ov; besti = oi; }
+          if constexpr (LP) sumv = lse_term(sumv, pb, bestv) + lse_term(os, ov, bestv);
         }
         __syncthreads();
         float* pv = reinterpret_cast<float*>(lds);        // [wc][32 rows]
         int* pi = reinterpret_cast<int*>(lds) + 64;
-        if (lane < 16) { pv[wc * 32 + wr * 16 + lane] = bestv; pi[wc * 32 + wr * 16 + lane] = besti; }
+        float* psm = reinterpret_cast<float*>(lds) + 128;  // (LP)
+        if (lane < 16) {
+          pv[wc * 32 + wr * 16 + lane] = bestv; pi[wc * 32 + wr * 16 + lane] = besti;
+          if constexpr (LP) psm[wc * 32 + wr * 16 + lane] = sumv;
+        }
         __syncthreads();
         if (tid < 32 && m0 + tid < M) {
           float v = pv[tid];
@@ -304,6 +329,7 @@ __global__ __launch_bounds__(256) void gemm16_kernel(ALoader A, const uint16_t* 
           if (pv[32 + tid] > v || (pv[32 + tid] == v && pi[32 + tid] < ix)) { v = pv[32 + tid]; ix = pi[32 + tid]; }
           ep.part_val[(size_t)(m0 + tid) * ep.part_stride + tn] = v;
           ep.part_idx[(size_t)(m0 + tid) * ep.part_stride + tn] = ix;
+          if constexpr (LP) ep.part_sum[(size_t)(m0 + tid) * ep.part_stride + tn] = lse_term(psm[tid], pv[tid], v) + lse_term(psm[32 + tid], pv[32 + tid], v);
         }
       }
     }
@@ -564,8 +590,11 @@ __global__ __launch_bounds__(256) void gemm16k_kernel(ALoader A, const uint16_t*
   Q3A_STAMP_AT(ep.stamp, blockIdx.x, 3);  // stores issued
 }
 
-template <int BM, int BN, int BK, bool GLU, class ALoader>
+template <int BM, int BN, int BK, bool GLU, class ALoader, bool LP = false>
 void launch16(const ALoader& A, const uint16_t* W, int M, int N, int K, const GemmEpilogue& ep, hipStream_t s) {
+  if constexpr (!LP && BM == 32 && !GLU && std::is_same<ALoader, DenseA16>::value) {
+    if (ep.part_sum) return launch16<BM, BN, BK, GLU, ALoader, true>(A, W, M, N, K, ep, s);  // (token log-probabilities)
+  }
   const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
   // Dense operands, BK = 64, tiles up to 64x64, (the A/B knob gemm16_ring of rounds 3-5 is gone: the ring won) a ring of
   // LDS stages as deep as still lets every workgroup of the launch be resident at once (64x64: 16 KiB per stage, 160 KiB per
@@ -574,15 +603,15 @@ void launch16(const ALoader& A, const uint16_t* W, int M, int N, int K, const Ge
   constexpr bool ring = std::is_same<ALoader, DenseA16>::value && BK == 64 && BM <= 64 && BN <= 64;
   if constexpr (ring) {
     if (tiles <= 512) {
-      hipLaunchKernelGGL((gemm16_kernel<BM, BN, BK, GLU, ALoader, 4>), dim3(tiles), dim3(256), 0, s, A, W, M, N, K, ep);
+      hipLaunchKernelGGL((gemm16_kernel<BM, BN, BK, GLU, ALoader, 4, LP>), dim3(tiles), dim3(256), 0, s, A, W, M, N, K, ep);
       return;
     }
     if (tiles <= 768) {
-      hipLaunchKernelGGL((gemm16_kernel<BM, BN, BK, GLU, ALoader, 3>), dim3(tiles), dim3(256), 0, s, A, W, M, N, K, ep);
+      hipLaunchKernelGGL((gemm16_kernel<BM, BN, BK, GLU, ALoader, 3, LP>), dim3(tiles), dim3(256), 0, s, A, W, M, N, K, ep);
       return;
     }
   }
-  hipLaunchKernelGGL((gemm16_kernel<BM, BN, BK, GLU, ALoader, 2>), dim3(tiles), dim3(256), 0, s, A, W, M, N, K, ep);
+  hipLaunchKernelGGL((gemm16_kernel<BM, BN, BK, GLU, ALoader, 2, LP>), dim3(tiles), dim3(256), 0, s, A, W, M, N, K, ep);
 }
 
 inline long tiles_of(int M, int N, int bm, int bn) { return (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn); }
@@ -636,6 +665,7 @@ const char* launch_gemm16_small(const uint16_t* X, int lda, const uint16_t* W, i
   if (glu && N % 32 != 0) return "gemm16: GLU needs N % 32 == 0";
   if (ep.part_val && (M > 32 || glu || N % 4 != 0 || ep.ldo % 4 != 0 || K % 64 != 0 || ep.rowmap || ep.part_stride < (N + 63) / 64))
     return "gemm16: argmax partials need M <= 32, 4 | N, 4 | ldo, 64 | K, no row map and part_stride >= ceil(N / 64)";
+  if (ep.part_sum && !ep.part_val) return "gemm16: the log-sum channel needs the argmax partials";
   DenseA16 A{X, lda};
   // few tiles and a long K: 32x32 tiles whose 4 waves split K (A/B knob: Q3A_GEMM16_KSPLIT=0 disables)
   static const bool ksplit_on = [] { const char* e = getenv("Q3A_GEMM16_KSPLIT"); return !e || atoi(e) != 0; }();

@@ -183,18 +183,24 @@ __device__ __forceinline__ float dot8(const uint4& w, const float (&x)[8], float
   return s + (a.x + a.y);
 }
 
-// epilogue shared by both variants; acc holds the finished (rstd-scaled) dot products, valid on every lane
-template <int NB, int PR>
+// epilogue shared by both variants; acc holds the finished (rstd-scaled) dot products, valid on every lane.
+// LP (mode 3, token log-probabilities): also the block's sum of exp(logit - block max) -> a.part_sum (dev.h lse_term); am_s as am_v.
+template <int NB, int PR, bool LP = false>
 __device__ __forceinline__ void gemv_epilogue(const GemvArgs& a, int g, const int (&prow)[PR], float (&acc)[PR][NB],
-                                              float (*am_v)[NB], int (*am_i)[NB]) {
+                                              float (*am_v)[NB], int (*am_i)[NB], float (*am_s)[NB] = nullptr) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (a.mode == 3) {  // logits + argmax partial (first-index tie-break: rows ascend with i, wave, block)
     float bv[NB];
     int bi[NB];
+    float lv[LP ? PR : 1][NB];  // LP: the wave's logits (-inf for rows past N)
 #pragma unroll
     for (int b = 0; b < NB; ++b) { bv[b] = -INFINITY; bi[b] = 0x7fffffff; }
 #pragma unroll
     for (int i = 0; i < PR; ++i) {
+      if constexpr (LP) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b) lv[i][b] = -INFINITY;
+      }
       if (prow[i] < 0) continue;
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
@@ -202,20 +208,33 @@ __device__ __forceinline__ void gemv_epilogue(const GemvArgs& a, int g, const in
         if (a.bias) v += a.bias[prow[i]];
         if (lane == 0 && a.out) a.out[(size_t)b * a.ldo + prow[i]] = v;
         if (v > bv[b]) { bv[b] = v; bi[b] = prow[i]; }
+        if constexpr (LP) lv[i][b] = v;
       }
     }
     if (lane == 0) {
 #pragma unroll
-      for (int b = 0; b < NB; ++b) { am_v[wave][b] = bv[b]; am_i[wave][b] = bi[b]; }
+      for (int b = 0; b < NB; ++b) {
+        am_v[wave][b] = bv[b]; am_i[wave][b] = bi[b];
+        if constexpr (LP) {
+          float ws = 0.f;
+#pragma unroll
+          for (int i = 0; i < PR; ++i) ws += lse_term(1.f, lv[i][b], bv[b]);
+          am_s[wave][b] = ws;
+        }
+      }
     }
     __syncthreads();
     if (tid < NB) {
-      float v = am_v[0][tid];
+      float v = am_v[0][tid], vs = LP ? am_s[0][tid] : 0.f;
       int ix = am_i[0][tid];
-      for (int w = 1; w < 4; ++w)
+      for (int w = 1; w < 4; ++w) {
+        const float pv = v;
         if (am_v[w][tid] > v || (am_v[w][tid] == v && am_i[w][tid] < ix)) { v = am_v[w][tid]; ix = am_i[w][tid]; }
+        if constexpr (LP) vs = lse_term(vs, pv, v) + lse_term(am_s[w][tid], am_v[w][tid], v);
+      }
       a.part_val[(size_t)tid * a.part_stride + (g >> 2)] = v;
       a.part_idx[(size_t)tid * a.part_stride + (g >> 2)] = ix;
+      if constexpr (LP) a.part_sum[(size_t)tid * a.part_stride + (g >> 2)] = vs;
     }
     return;
   }
@@ -492,10 +511,11 @@ __global__ __launch_bounds__(256) void gemv1_kernel(GemvArgs a) {
 // One 16-row argmax block (4 waves x PR rows) of the one-sequence lm_head: the arithmetic of gemv1_kernel<PR, KI, true, false>
 // (same lane / column assignment, same order of the products and sums, same rstd, first-index tie rule).  Used by the
 // unpruned launch (gemv1_head_kernel: block = blockIdx.x) AND by the rescore of the pruned argmax (lm_head_rescore_kernel): the
-// two cannot drift apart.  Ends with a barrier; the block's (value, row) is valid in thread 0.
-template <int PR, int KI>
+// two cannot drift apart.  Ends with a barrier; the block's (value, row) is valid in thread 0.  LP (token log-probabilities): also
+// the block's sum of exp(logit - value) in *out_s (am_s: 4 floats of LDS); the value / row arithmetic is the same either way.
+template <int PR, int KI, bool LP = false>
 __device__ __forceinline__ void gemv1_head_block(const GemvArgs& a, int blk, float (&am_v)[4][1], int (&am_i)[4][1],
-                                                 float& out_v, int& out_i) {
+                                                 float& out_v, int& out_i, float* am_s = nullptr, float* out_s = nullptr) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int K = a.K;
   const int g = blk * 4 + wave;
@@ -561,27 +581,39 @@ __device__ __forceinline__ void gemv1_head_block(const GemvArgs& a, int blk, flo
     if (acc[i] > best) { best = acc[i]; bi = prow[i]; }
   }
   if (lane == 0) { am_v[wave][0] = best; am_i[wave][0] = bi; }
+  if constexpr (LP) {
+    float ws = 0.f;
+#pragma unroll
+    for (int i = 0; i < PR; ++i) ws += prow[i] < 0 ? 0.f : lse_term(1.f, acc[i], best);
+    if (lane == 0) am_s[wave] = ws;
+  }
   __syncthreads();
   if (tid == 0) {
-    float v = am_v[0][0];
+    float v = am_v[0][0], vs = LP ? am_s[0] : 0.f;
     int ix = am_i[0][0];
-    for (int w = 1; w < 4; ++w)
+    for (int w = 1; w < 4; ++w) {
+      const float pv = v;
       if (am_v[w][0] > v || (am_v[w][0] == v && am_i[w][0] < ix)) { v = am_v[w][0]; ix = am_i[w][0]; }
+      if constexpr (LP) vs = lse_term(vs, pv, v) + lse_term(am_s[w], am_v[w][0], v);
+    }
     out_v = v;
     out_i = ix;
+    if constexpr (LP) *out_s = vs;
   }
 }
 
-template <int PR, int KI>
+template <int PR, int KI, bool LP = false>
 __global__ __launch_bounds__(256) void gemv1_head_kernel(GemvArgs a) {
   __shared__ float am_v[4][1];
   __shared__ int am_i[4][1];
-  float v;
+  __shared__ float am_s[LP ? 4 : 1];
+  float v, vs;
   int ix;
-  gemv1_head_block<PR, KI>(a, blockIdx.x, am_v, am_i, v, ix);
+  gemv1_head_block<PR, KI, LP>(a, blockIdx.x, am_v, am_i, v, ix, am_s, &vs);
   if (threadIdx.x == 0) {
     a.part_val[blockIdx.x] = v;
     a.part_idx[blockIdx.x] = ix;
+    if constexpr (LP) a.part_sum[blockIdx.x] = vs;
   }
 }
 
@@ -800,12 +832,13 @@ __global__ __launch_bounds__(256) void lm_head_rescore_kernel(LmHeadArgsDev p) {
 }
 
 // ---- NB in {2, 4}: x staged through LDS once per workgroup ---------------------------------------------
-template <int NB, int PR, int PF>
+template <int NB, int PR, int PF, bool LP = false>
 __global__ __launch_bounds__(256) void gemvn_kernel(GemvArgs a) {
   extern __shared__ __attribute__((aligned(16))) float xs[];  // [NB][K]
   __shared__ float red[NB][4];
   __shared__ float am_v[4][NB];
   __shared__ int am_i[4][NB];
+  __shared__ float am_s[4][LP ? NB : 1];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int K = a.K;
   const int g = blockIdx.x * 4 + wave;
@@ -883,7 +916,8 @@ __global__ __launch_bounds__(256) void gemvn_kernel(GemvArgs a) {
 #pragma unroll
     for (int i = 0; i < PR; ++i) acc[i][b] = wave_sum_fast(acc[i][b]) * rstd;
   }
-  gemv_epilogue<NB, PR>(a, g, prow, acc, am_v, am_i);
+  if constexpr (LP) gemv_epilogue<NB, PR, true>(a, g, prow, acc, am_v, am_i, am_s);
+  else gemv_epilogue<NB, PR>(a, g, prow, acc, am_v, am_i);
 }
 
 template <int PR, int KI>
@@ -899,7 +933,11 @@ void launch1k(const GemvArgs& a, hipStream_t s) {
     // (round 6: 609.7 -> 595.1 us per step at 0.6B, ids identical; profiles/r6_ab_gemv_x_lds.txt).  Not where it was measured to
     // lose: K = 2048 (+18 %: 32 KiB of LDS per workgroup halves the residency of the 1536-workgroup gate / up launch), the down
     // projection (+4 %: x in front of the weights delays them), the lm_head (+1.3 %: a barrier in each of 9496 workgroups).
-    if (a.mode == 3) { hipLaunchKernelGGL((gemv1_head_kernel<PR, KI>), grid, block, 0, s, a); return; }
+    if (a.mode == 3) {
+      if (a.part_sum) hipLaunchKernelGGL((gemv1_head_kernel<PR, KI, true>), grid, block, 0, s, a);
+      else hipLaunchKernelGGL((gemv1_head_kernel<PR, KI>), grid, block, 0, s, a);
+      return;
+    }
     if constexpr (KI == 2) { hipLaunchKernelGGL((gemv1_kernel<PR, KI, true, false, 0, true>), grid, block, 0, s, a); return; }
     hipLaunchKernelGGL((gemv1_kernel<PR, KI, true, false>), grid, block, 0, s, a);
   } else {
@@ -916,7 +954,8 @@ void launch1(const GemvArgs& a, hipStream_t s) {
 }
 template <int NB, int PR, int PF>
 void launchn(const GemvArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL((gemvn_kernel<NB, PR, PF>), dim3(gemv_blocks(a)), dim3(256), (size_t)NB * a.K * sizeof(float), s, a);
+  if (a.part_sum) hipLaunchKernelGGL((gemvn_kernel<NB, PR, PF, true>), dim3(gemv_blocks(a)), dim3(256), (size_t)NB * a.K * sizeof(float), s, a);
+  else hipLaunchKernelGGL((gemvn_kernel<NB, PR, PF>), dim3(gemv_blocks(a)), dim3(256), (size_t)NB * a.K * sizeof(float), s, a);
 }
 
 }  // namespace
@@ -940,6 +979,7 @@ const char* launch_lm_head_quantize(const uint16_t* W, int N, int K, int8_t* Q, 
 const char* lm_head_prune_check(const LmHeadPruneArgs& a) {
   const GemvArgs& g = a.g;
   if (g.mode != 3 || !g.rms_w || !g.x || g.attn_po || g.bias) return "lm_head_prune: needs the plain mode-3 GEMV with a fused norm";
+  if (g.part_sum) return "lm_head_prune: token log-probabilities need every logit (the full GEMV)";
   if (gemv_rows_per_wave(g) != 4 || gemv_blocks(g) != lm_head_prune_blocks(g)) return "lm_head_prune: the GEMV does not run 16-row blocks here";
   if (g.K % 8 != 0 || a.qcols != lm_head_q_cols(g.K)) return "lm_head_prune: int8 row width does not match the hidden size";
   if (!a.Wq || !a.qs || !a.blk_lo || !a.blk_hi || !g.part_val || !g.part_idx) return "lm_head_prune: missing buffer";
@@ -975,6 +1015,9 @@ const char* launch_gemv(const GemvArgs& a0, int NB, hipStream_t s) {
   if (a0.attn_po && (a0.K % 128 != 0 || a0.K != a0.attn_heads * 128)) return "gemv: attention-partial input needs K = heads*128";
   if (a0.attn_po && a0.rms_w) return "gemv: attention-partial input cannot be combined with a fused RMSNorm";
   if (a0.attn_po && (NB < 4 ? NB : 4) * a0.attn_heads * a0.attn_nsplit > ATTN_F_MAX) return "gemv: too many attention splits for the LDS scale table";
+  // the log-sum channel: mode 3 only, and for one sequence only in the fused-norm head kernel (gemv1_kernel's mode 3 has none)
+  if (a0.part_sum && (a0.mode != 3 || a0.attn_po || (NB % 2 == 1 && !a0.rms_w)))
+    return "gemv: log-sum partials need mode 3 and, for an odd batch, the fused final norm";
   const int pr = gemv_rows_per_wave(a0);
   const int nb_cap = (int)((64 * 1024) / ((size_t)a0.K * 4));  // rows of x that fit in 64 KiB of LDS
   int done = 0;
@@ -984,6 +1027,7 @@ const char* launch_gemv(const GemvArgs& a0, int NB, hipStream_t s) {
     if (a0.out) a.out = a0.out + (size_t)done * a0.ldo;
     if (a0.resid) a.resid = a0.resid + (size_t)done * a0.ldo;
     if (a0.part_val) { a.part_val = a0.part_val + (size_t)done * a0.part_stride; a.part_idx = a0.part_idx + (size_t)done * a0.part_stride; }
+    if (a0.part_sum) a.part_sum = a0.part_sum + (size_t)done * a0.part_stride;
     if (a0.attn_po) {
       const size_t adv = (size_t)done * a0.attn_heads * a0.attn_nsplit;
       a.attn_pm = a0.attn_pm + adv; a.attn_pl = a0.attn_pl + adv; a.attn_po = a0.attn_po + adv * 128;

@@ -32,6 +32,7 @@ struct GemmEpilogue {
   float* part_val = nullptr;
   int* part_idx = nullptr;
   int part_stride = 0;
+  float* part_sum = nullptr;  // with part_val, optional: sum over the tile's columns of exp(logit - part_val) (token log-probabilities)
   Q3A_STAMP_FIELD
 };
 // Y = X[M][K](fp32, row stride lda) . W[N][K]^T(bf16).  glu: W rows are [16 gate|16 up] blocks, out has N/2 columns.
@@ -176,6 +177,8 @@ struct GemvArgs {
   float* out; int ldo;
   const float* resid;
   float* part_val; int* part_idx; int part_stride;  // mode 3: [NB][part_stride], entry = blockIdx.x
+  float* part_sum;              // mode 3, optional (token log-probabilities): the same layout, sum over the block's rows of
+                                // exp(logit - part_val); the fused-norm one-sequence head and the NB in {2, 4} kernels only
   // optional: x = attention output merged on the fly from the flash-decoding partials of launch_decode_attn
   // (x/ldx ignored; K must equal attn_heads*128)
   const float* attn_pm; const float* attn_pl; const float* attn_po; int attn_nsplit; int attn_heads;
@@ -316,10 +319,14 @@ struct FinalizeArgs {
   const float* cos_t; const float* sin_t;  // RoPE tables [max_pos][64]
   float* rope_cur;         // [S][128] (written): cos | sin row of the updated pos[s] (DecodeAttnArgs::rope_cur); nullable
   NextNormOut nn;          // pre-normalised copy of x_next for the first layer's qkv GEMM (skinny path)
+  // token log-probabilities (both set or both null): part_sum [S][part_stride] = sum exp(logit - part_val) per partial; out_lp
+  // [S][out_stride] receives logit[id] - logsumexp(logits) of the chosen id next to out_ids (NaN where the all-NaN guard fires)
+  const float* part_sum;
+  float* out_lp;
 };
-// block partials of logits [S][V] (GEMM decode path; the GEMV lm_head produces its own)
+// block partials of logits [S][V] (GEMM decode path; the GEMV lm_head produces its own); psum nullable: the log-sum channel
 const char* launch_argmax_partials(const float* logits, int V, int S, float* pval, int* pidx, int stride, int nblk,
-                                   hipStream_t s);
+                                   hipStream_t s, float* psum = nullptr);
 const char* launch_argmax_finalize(const FinalizeArgs& a, int S, hipStream_t s);
 // x_next[s] = embed[tok[s]]; next_tok[s] = tok[s]  (teacher forcing)
 const char* launch_set_tokens(const int* tok, int S, const uint16_t* embed, int H, float* x_next, int* next_tok, hipStream_t s,

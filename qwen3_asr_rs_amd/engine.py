@@ -44,7 +44,7 @@ class HipEngine:
 
     def __init__(self, model_dir: str, device: int = 0, precise: bool = False, max_new_tokens: int = 4096,
                  use_graph: bool = True, debug_taps: bool = False, device_arena: Optional[Tuple[int, int]] = None,
-                 valu_attention: bool = False):
+                 valu_attention: bool = False, token_logprobs: bool = False):
         self._lib = _lib.load()
         self._h = C.c_void_p()
         opts = _lib.Opts()
@@ -54,6 +54,8 @@ class HipEngine:
         opts.use_graph = int(use_graph)
         opts.debug_taps = int(debug_taps)
         opts.valu_attention = int(valu_attention)
+        opts.token_logprobs = int(token_logprobs)
+        self.token_logprobs = bool(token_logprobs)
         md = os.fsencode(model_dir)
         if device_arena is None:
             rc = self._lib.q3a_engine_create(md, device, C.byref(opts), C.byref(self._h))
@@ -171,6 +173,16 @@ class HipEngine:
         lens = np.zeros(self.batch, dtype=np.int32)
         self._chk(self._lib.q3a_fetch_ids(self._h, _i32p(out), stride, _i32p(lens)))
         return [out[b, :min(int(lens[b]), stride)].tolist() for b in range(self.batch)]
+
+    def fetch_logprobs(self) -> List[np.ndarray]:
+        """q3a_fetch_logprobs: per utterance, the natural-log probability (float32) of every id fetch_ids / transcribe_batch returned
+        for the last run or stage-API step, same order and lengths.  Needs token_logprobs=True."""
+        lens = np.zeros(self.batch, dtype=np.int32)
+        self._chk(self._lib.q3a_fetch_logprobs(self._h, None, 0, _i32p(lens)))  # lengths first
+        stride = max(1, int(lens.max()) if len(lens) else 1)
+        out = np.zeros((self.batch, stride), dtype=np.float32)
+        self._chk(self._lib.q3a_fetch_logprobs(self._h, _f32p(out), stride, _i32p(lens)))
+        return [out[b, :int(lens[b])].copy() for b in range(self.batch)]
 
     @staticmethod
     def _ptrs(clips: Sequence[np.ndarray]):
@@ -344,11 +356,14 @@ from .audio import AsrTokenizer, capitalize_first, load_audio, parse_asr_output 
 
 @dataclass
 class TranscribeResult:
-    """src/inference.rs:269-274 (+ the raw ids, which is where parity is pinned)."""
+    """src/inference.rs:269-274 (+ the raw ids, which is where parity is pinned).  With an engine created with token_logprobs=True
+    also the log-probability of every id and their mean (Whisper's avg_logprob; None when no token was generated)."""
     text: str
     language: str
     raw_output: str
     ids: List[int]
+    token_logprobs: Optional[List[float]] = None
+    avg_logprob: Optional[float] = None
 
 
 class AsrInference:
@@ -383,4 +398,9 @@ class AsrInference:
         ids = self.engine.transcribe_batch([samples], prefix, max_new_tokens)[0]
         raw = self.tokenizer.decode(ids, True) if self.tokenizer is not None else ""
         lang, text = parse_asr_output(raw, language is not None)
-        return TranscribeResult(text, lang, raw, ids)
+        res = TranscribeResult(text, lang, raw, ids)
+        if self.engine.token_logprobs:
+            lp = self.engine.fetch_logprobs()[0]
+            res.token_logprobs = [float(v) for v in lp]
+            res.avg_logprob = float(np.mean(lp, dtype=np.float64)) if len(lp) else None
+        return res
