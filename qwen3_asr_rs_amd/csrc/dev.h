@@ -158,11 +158,6 @@ __device__ __forceinline__ float rstd_of(float mean_sq_plus_eps, bool fast) {
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + expf(-x)); }
 __device__ __forceinline__ float silu_sel(float x, bool fast) { return (Q3A_FAST_EPILOGUE && fast) ? silu_fast(x) : silu_f(x); }
 
-// Token log-probabilities (opts.token_logprobs): an argmax partial also carries s = sum exp(l - m) over the logits it covers, m being
-// its own maximum.  Two pairs merge into the pair of their union as s = s_a e^(m_a - m) + s_b e^(m_b - m), m = the merged maximum;
-// this is one such term.  A pair that covers no logit (m_s = -inf, s = 0) contributes 0, never NaN.
-__device__ __forceinline__ float lse_term(float s, float m_s, float m) { return m_s == -INFINITY ? 0.f : s * __expf(m_s - m); }
-
 // The lane id from a statement hipcc may not merge with an earlier one: what is derived from it is recomputed where it is used instead
 // of living in registers across a loop that does not need it (the epilogue constants and row-pointer inputs of k_gemm256.hip's walk)
 __device__ __forceinline__ int lane_id_fresh() {

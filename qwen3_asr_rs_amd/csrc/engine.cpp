@@ -793,14 +793,15 @@ struct q3a_engine {
     tap("head_in", x_dec.p, (size_t)S * H * 4);  // (debug taps) last-layer residual rows the final norm + lm_head read
     const double wbytes = 2.0 * V * H;
     int n_part = 0;
-    // token log-probabilities: every producer of argmax partials also writes their log-sum channel (null: off, today's kernels)
-    float* const psum = token_lp() ? part_sum.as<float>() : nullptr;
+    // the argmax partials every producer below writes and argmax_finalize merges; with token log-probabilities also their log-sum
+    // channel (null: off, the kernels without it)
+    const ArgmaxPartials part{part_val.as<float>(), part_idx.as<int>(), token_lp() ? part_sum.as<float>() : nullptr, part_stride};
     if (S <= kGemvMaxSeq) {
       GemvArgs g{};
       g.fast_math = precise() ? 0 : 1;
       g.x = x_dec.as<float>(); g.ldx = H; g.rms_w = wf(L.final_norm); g.eps = d.rms_eps;
       g.W = wh(L.lm_head); g.N = V; g.K = H; g.mode = 3; g.out = logits.as<float>(); g.ldo = V;
-      g.part_val = part_val.as<float>(); g.part_idx = part_idx.as<int>(); g.part_stride = part_stride; g.part_sum = psum;
+      g.part = part;
       // (with the log-sum channel lm_head_prune_check refuses: the pruned argmax never computes most logits, the full GEMV runs)
       LmHeadPruneArgs pa{};
       const bool prunable = S == 1 && !precise() && lm_q_cols > 0 && (pa = prune_args(g), !lm_head_prune_check(pa));
@@ -830,24 +831,23 @@ struct q3a_engine {
       if (S <= 32 && V % 4 == 0 && H % 64 == 0 && part_stride >= (V + 63) / 64) {
         // the argmax partials are the GEMM's epilogue (one per 64-column tile and row), and inside q3a_transcribe_batch /
         // q3a_run_resident nobody reads the logits: they are not stored (19 MB per step at 32 sequences)
-        ep.part_val = part_val.as<float>(); ep.part_idx = part_idx.as<int>(); ep.part_stride = part_stride; ep.part_sum = psum;
+        ep.part = part;
         if (!head_logits_) ep.out = nullptr;
         n_part = (V + 63) / 64;
         timed(Q3A_KC_GEMM, wbytes, [&] { KCHK(launch_gemm16(s_ln.as<uint16_t>(), H, wh(L.lm_head), S, V, H, ep, false, stream)); });
       } else {
         timed(Q3A_KC_GEMM, wbytes, [&] { KCHK(launch_gemm16(s_ln.as<uint16_t>(), H, wh(L.lm_head), S, V, H, ep, false, stream)); });
         n_part = 128;
-        timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_partials(logits.as<float>(), V, S, part_val.as<float>(), part_idx.as<int>(), part_stride, n_part, stream, psum)); });
+        timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_partials(logits.as<float>(), V, S, part, n_part, stream)); });
       }
     } else {
       timed(Q3A_KC_NORM, 0, [&] { KCHK(launch_rmsnorm(x_dec.as<float>(), wf(L.final_norm), s_ln.as<float>(), S, H, d.rms_eps, stream)); });
       timed(Q3A_KC_GEMM, wbytes, [&] { batched_proj(s_ln.as<float>(), H, wh(L.lm_head), V, H, nullptr, 0, logits.as<float>(), V, nullptr); });
       n_part = 128;
-      timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_partials(logits.as<float>(), V, S, part_val.as<float>(), part_idx.as<int>(), part_stride, n_part, stream, psum)); });
+      timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_partials(logits.as<float>(), V, S, part, n_part, stream)); });
     }
     FinalizeArgs f{};
-    f.part_sum = psum; f.out_lp = psum ? out_lp.as<float>() : nullptr;
-    f.part_val = part_val.as<float>(); f.part_idx = part_idx.as<int>(); f.part_stride = part_stride; f.n_part = n_part;
+    f.part = part; f.n_part = n_part; f.out_lp = part.sum ? out_lp.as<float>() : nullptr;
     f.V = V; f.next_tok = next_tok.as<int>(); f.out_ids = out_ids.as<int>();
     f.out_stride = max_new; f.step_count = step_count.as<int>(); f.pos = d_pos.as<int>(); f.advance = advance;
     f.done = done.as<uint8_t>(); f.n_done = n_done.as<int>(); f.n_seq = S; f.host_progress = host_prog_dev; f.embed = wh(L.embed); f.H = H; f.x_next = x_dec.as<float>(); f.eos0 = kEos0; f.eos1 = kEos1;

@@ -8,8 +8,7 @@
 //   argmax_finalize_kernel  argmax (first-index tie-break, src/tensor.rs:370-372), EOS flag, id store and the
 //                           embedding of the chosen token for the next step -- no per-token D2H sync
 //                           (the reference does int64_value per token, src/inference.rs:161)
-#include "dev.h"
-#include "kernels.h"
+#include "argmax.h"
 
 namespace q3a {
 
@@ -109,63 +108,45 @@ __global__ __launch_bounds__(256) void qknorm_rope_kv_kernel(RopeKvArgs a, int r
 
 // --------------------------------------------------------------------------------------------------
 // argmax, stage 1 (GEMM path only; the GEMV lm_head writes its partials itself): block partial maxima.  LP: also the log-sum
-// channel psum = sum exp(l - best) over the block (dev.h lse_term), kept online per thread and merged as (max, sum) pairs.
+// channel over the block (argmax.h), kept online per thread.
 template <bool LP>
-__global__ __launch_bounds__(256) void argmax_partial_kernel(const float* __restrict__ logits, int V, float* __restrict__ pval,
-                                                             int* __restrict__ pidx, int stride, float* __restrict__ psum) {
+__global__ __launch_bounds__(256) void argmax_partial_kernel(const float* __restrict__ logits, int V, ArgmaxPartials p) {
   __shared__ float bv[4], bs[LP ? 4 : 1];
   __shared__ int bi[4];
   const int s = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int per = (V + gridDim.x - 1) / gridDim.x;
   const int lo = blockIdx.x * per, hi = min(V, lo + per);
   const float* lg = logits + (size_t)s * V;
-  float best = -INFINITY, sum = 0.f;
-  int idx = 0x7fffffff;
+  ArgmaxAcc<LP> m;
   for (int i = lo + tid; i < hi; i += 256) {
     const float v = lg[i];
     if constexpr (LP) {
-      if (v > best) sum = lse_term(sum, best, v) + 1.f;
-      else sum += lse_term(1.f, v, best);
+      if (v > m.v) m.s = lse_term(m.s, m.v, v) + 1.f;
+      else m.s += lse_term(1.f, v, m.v);
     }
-    if (v > best) { best = v; idx = i; }
+    if (v > m.v) { m.v = v; m.i = i; }
   }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(idx, o, 64);
-    const float os = LP ? __shfl_xor(sum, o, 64) : 0.f;
-    const float pb = best;
-    if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
-    if constexpr (LP) sum = lse_term(sum, pb, best) + lse_term(os, ov, best);
-  }
+  for (int o = 32; o > 0; o >>= 1) m.merge_lane(o);
   if (lane == 0) {
-    bv[wave] = best; bi[wave] = idx;
-    if constexpr (LP) bs[wave] = sum;
+    bv[wave] = m.v; bi[wave] = m.i;
+    if constexpr (LP) bs[wave] = m.s;
   }
   __syncthreads();
   if (tid == 0) {
-    for (int w = 1; w < 4; ++w) {
-      const float pb = best;
-      if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
-      if constexpr (LP) sum = lse_term(sum, pb, best) + lse_term(bs[w], bv[w], best);
-    }
-    pval[(size_t)s * stride + blockIdx.x] = best;
-    pidx[(size_t)s * stride + blockIdx.x] = idx;
-    if constexpr (LP) psum[(size_t)s * stride + blockIdx.x] = sum;
+    for (int w = 1; w < 4; ++w) m.merge(bv[w], bi[w], bs[LP ? w : 0]);
+    m.store(p, s, blockIdx.x);
   }
 }
 
-// argmax, stage 2 + bookkeeping of the greedy loop.  LP (token log-probabilities): the partials' log-sum channel is merged with
-// the maxima as (max, sum) pairs; the chosen id's logit IS the global maximum M, so lp = -log sum_p part_sum[p] e^(part_val[p] - M)
-// (<= 0: the partial that holds M contributes at least e^0 = 1).
+// argmax, stage 2 + bookkeeping of the greedy loop.  LP (token log-probabilities): the chosen id's logit IS the global maximum M, so
+// lp = -log sum_p part.sum[p] e^(part.val[p] - M), the merged sum (<= 0: the partial that holds M contributes at least e^0 = 1).
 template <bool LP>
 __global__ __launch_bounds__(1024) void argmax_finalize_kernel(FinalizeArgs a) {
   __shared__ float bv[16], bs[LP ? 16 : 1];
   __shared__ int bi[16];
   __shared__ int tok_s;
   const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float* pv = a.part_val + (size_t)s * a.part_stride;
-  const int* pi = a.part_idx + (size_t)s * a.part_stride;
   // Everything that does not depend on the chosen token is requested up front, in ONE batch: the sequence's counters, the partial
   // maxima (up to FIN_PRE per lane, clamped addresses -- round 6: the plain loop `for (i = tid; i < n_part; i += 1024)` compiled to
   // two loads and a vmcnt(0) per iteration, ten dependent L2 round trips for the 9496 partials of the one-sequence lm_head) and,
@@ -174,49 +155,34 @@ __global__ __launch_bounds__(1024) void argmax_finalize_kernel(FinalizeArgs a) {
   const int np = a.pos[s] + a.advance;
   const int sc = a.step_count[s];
   const int was_done = a.done[s];
-  const float* ps = LP ? a.part_sum + (size_t)s * a.part_stride : nullptr;
-  float pre_v[FIN_PRE], pre_s[LP ? FIN_PRE : 1];
-  int pre_i[FIN_PRE];
+  ArgmaxAcc<LP> pre[FIN_PRE];
 #pragma unroll
   for (int j = 0; j < FIN_PRE; ++j) {
-    const int i = tid + j * 1024, ic = i < a.n_part ? i : a.n_part - 1;
-    pre_v[j] = pv[ic];
-    pre_i[j] = pi[ic];
-    if constexpr (LP) pre_s[j] = ps[ic];  // in the same batch: no extra round trip
+    const int i = tid + j * 1024;
+    pre[j] = ArgmaxAcc<LP>::load(a.part, s, i < a.n_part ? i : a.n_part - 1);  // all three channels in the same batch
   }
   float rope_v = 0.f;
   if (a.rope_cur && tid < 128) rope_v = tid < 64 ? a.cos_t[(size_t)np * 64 + tid] : a.sin_t[(size_t)np * 64 + tid - 64];
-  float best = -INFINITY, sum = 0.f;
-  int idx = 0x7fffffff;
-  // one (max, index[, sum]) merge: the first-index rule picks the pair, the sums are rescaled to its maximum
-  auto merge = [&](float v, int ix, float vs) {
-    const float pb = best;
-    if (v > best || (v == best && ix < idx)) { best = v; idx = ix; }
-    if constexpr (LP) sum = lse_term(sum, pb, best) + lse_term(vs, v, best);
-  };
+  ArgmaxAcc<LP> m;
 #pragma unroll
   for (int j = 0; j < FIN_PRE; ++j) {
     const bool in = tid + j * 1024 < a.n_part;
-    merge(in ? pre_v[j] : -INFINITY, pre_i[j], LP && in ? pre_s[LP ? j : 0] : 0.f);
+    m.merge(in ? pre[j].v : -INFINITY, pre[j].i, LP && in ? pre[j].s : 0.f);
   }
-  for (int i = tid + FIN_PRE * 1024; i < a.n_part; i += 1024) merge(pv[i], pi[i], LP ? ps[i] : 0.f);
+  for (int i = tid + FIN_PRE * 1024; i < a.n_part; i += 1024) m.merge(ArgmaxAcc<LP>::load(a.part, s, i));
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(idx, o, 64);
-    const float os = LP ? __shfl_xor(sum, o, 64) : 0.f;
-    merge(ov, oi, os);
-  }
+  for (int o = 32; o > 0; o >>= 1) m.merge_lane(o);
   if (lane == 0) {
-    bv[wave] = best; bi[wave] = idx;
-    if constexpr (LP) bs[wave] = sum;
+    bv[wave] = m.v; bi[wave] = m.i;
+    if constexpr (LP) bs[wave] = m.s;
   }
   __syncthreads();
   if (tid == 0) {
-    for (int w = 1; w < 16; ++w) merge(bv[w], bi[w], LP ? bs[w] : 0.f);
+    for (int w = 1; w < 16; ++w) m.merge(bv[w], bi[w], bs[LP ? w : 0]);
+    int idx = m.i;
     float lp = 0.f;
     if constexpr (LP) {
-      lp = -logf(sum);
+      lp = -logf(m.s);
       if (lp > 0.f) lp = 0.f;  // (rounding; NaN passes through)
     }
     if (idx < 0 || idx >= a.V) { idx = 0; lp = __int_as_float(0x7fc00000); }  // all-NaN guard
@@ -266,18 +232,20 @@ const char* launch_qknorm_rope_kv(const RopeKvArgs& a, int rows, bool kv_f32, hi
   else hipLaunchKernelGGL((qknorm_rope_kv_kernel<uint16_t>), dim3(blocks), dim3(256), 0, s, a, rows);
   return nullptr;
 }
-const char* launch_argmax_partials(const float* logits, int V, int S, float* pval, int* pidx, int stride, int nblk,
-                                   hipStream_t s, float* psum) {
+const char* launch_argmax_partials(const float* logits, int V, int S, const ArgmaxPartials& p, int nblk, hipStream_t s) {
   if (S <= 0) return nullptr;
-  if (nblk > stride) return "argmax: partial buffer too small";
-  if (psum) hipLaunchKernelGGL(argmax_partial_kernel<true>, dim3(nblk, S), dim3(256), 0, s, logits, V, pval, pidx, stride, psum);
-  else hipLaunchKernelGGL(argmax_partial_kernel<false>, dim3(nblk, S), dim3(256), 0, s, logits, V, pval, pidx, stride, psum);
+  if (!p.val) return "argmax: partial buffer missing";
+  if (const char* e = argmax_partials_check(p, nblk)) return e;
+  if (p.sum) hipLaunchKernelGGL(argmax_partial_kernel<true>, dim3(nblk, S), dim3(256), 0, s, logits, V, p);
+  else hipLaunchKernelGGL(argmax_partial_kernel<false>, dim3(nblk, S), dim3(256), 0, s, logits, V, p);
   return nullptr;
 }
 const char* launch_argmax_finalize(const FinalizeArgs& a, int S, hipStream_t s) {
   if (S <= 0) return nullptr;
-  if (!a.part_sum != !a.out_lp) return "argmax_finalize: part_sum and out_lp go together";
-  if (a.part_sum) hipLaunchKernelGGL(argmax_finalize_kernel<true>, dim3(S), dim3(1024), 0, s, a);
+  if (!a.part.val) return "argmax_finalize: partial buffer missing";
+  if (const char* e = argmax_partials_check(a.part, a.n_part)) return e;
+  if (!a.part.sum != !a.out_lp) return "argmax_finalize: part.sum and out_lp go together";
+  if (a.part.sum) hipLaunchKernelGGL(argmax_finalize_kernel<true>, dim3(S), dim3(1024), 0, s, a);
   else hipLaunchKernelGGL(argmax_finalize_kernel<false>, dim3(S), dim3(1024), 0, s, a);
   return nullptr;
 }

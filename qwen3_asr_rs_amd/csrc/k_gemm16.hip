@@ -26,8 +26,7 @@
 
 #include <type_traits>
 
-#include "dev.h"
-#include "kernels.h"
+#include "argmax.h"
 
 namespace q3a {
 namespace {
@@ -73,7 +72,7 @@ template <int N> __device__ __forceinline__ void g16_wait_vm() {  // N = (A_LOAD
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// LP (token log-probabilities, M <= 32 argmax tile only): the argmax partials also carry ep.part_sum (dev.h lse_term)
+// LP (token log-probabilities, M <= 32 argmax tile only): the argmax partials also carry the log-sum channel (argmax.h)
 template <int BM, int BN, int BK, bool GLU, class ALoader, int NS = 2, bool LP = false>
 __global__ __launch_bounds__(256) void gemm16_kernel(ALoader A, const uint16_t* __restrict__ Wt, int M, int N, int K,
                                                      GemmEpilogue ep) {
@@ -253,8 +252,7 @@ __global__ __launch_bounds__(256) void gemm16_kernel(ALoader A, const uint16_t* 
     if (!pre) load_operands();
     constexpr bool ARGMAX = BM == 32 && MI == 1;  // only the M <= 32 tile carries the code
     static_assert(!LP || ARGMAX, "the log-sum channel rides on the argmax partials");
-    float bestv = -INFINITY;
-    int besti = 0x7fffffff;
+    ArgmaxAcc<LP> best;
     float lv[LP ? NI : 1][4];  // LP: this lane's logits (-inf where a row or column is out of range)
     if constexpr (LP) {
 #pragma unroll
@@ -275,10 +273,10 @@ __global__ __launch_bounds__(256) void gemm16_kernel(ALoader A, const uint16_t* 
           for (int r = 0; r < 4; ++r) v[r] = gelu_fast(v[r]);
         }
         if (ep.resid) { v[0] += rs[i][j].x; v[1] += rs[i][j].y; v[2] += rs[i][j].z; v[3] += rs[i][j].w; }
-        if (ARGMAX && ep.part_val) {  // columns ascend with j and r: a strict > keeps the first index on ties
+        if (ARGMAX && ep.part.val) {  // columns ascend with j and r: a strict > keeps the first index on ties
 #pragma unroll
           for (int r = 0; r < 4; ++r)
-            if (v[r] > bestv) { bestv = v[r]; besti = n + r; }
+            if (v[r] > best.v) { best.v = v[r]; best.i = n + r; }
           if constexpr (LP) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) lv[j][r] = v[r];
@@ -295,41 +293,30 @@ __global__ __launch_bounds__(256) void gemm16_kernel(ALoader A, const uint16_t* 
       }
     }
     if constexpr (ARGMAX) {
-      if (ep.part_val) {  // uniform
+      if (ep.part.val) {  // uniform
         // row m = lane & 15 of this wave's 16 rows: its four column groups sit in lanes l, l+16, l+32, l+48; then the two
         // column halves (waves wc = 0 / 1) meet in LDS (every wave has left the K loop: barrier first, the stages are free)
-        float sumv = 0.f;  // LP: sum of exp(l - bestv) over this lane's columns of row m
-        if constexpr (LP) {
+        if constexpr (LP) {  // sum of exp(l - best.v) over this lane's columns of row m
 #pragma unroll
           for (int j = 0; j < NI; ++j)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) sumv += lse_term(1.f, lv[j][r], bestv);
+            for (int r = 0; r < 4; ++r) best.s += lse_term(1.f, lv[j][r], best.v);
         }
 #pragma unroll
-        for (int o = 16; o <= 32; o <<= 1) {
-          const float ov = __shfl_xor(bestv, o, 64);
-          const int oi = __shfl_xor(besti, o, 64);
-          const float os = LP ? __shfl_xor(sumv, o, 64) : 0.f;
-          const float pb = bestv;
-          if (ov > bestv || (ov == bestv && oi < besti)) { bestv = ov; besti = oi; }
-          if constexpr (LP) sumv = lse_term(sumv, pb, bestv) + lse_term(os, ov, bestv);
-        }
+        for (int o = 16; o <= 32; o <<= 1) best.merge_lane(o);
         __syncthreads();
         float* pv = reinterpret_cast<float*>(lds);        // [wc][32 rows]
         int* pi = reinterpret_cast<int*>(lds) + 64;
         float* psm = reinterpret_cast<float*>(lds) + 128;  // (LP)
         if (lane < 16) {
-          pv[wc * 32 + wr * 16 + lane] = bestv; pi[wc * 32 + wr * 16 + lane] = besti;
-          if constexpr (LP) psm[wc * 32 + wr * 16 + lane] = sumv;
+          pv[wc * 32 + wr * 16 + lane] = best.v; pi[wc * 32 + wr * 16 + lane] = best.i;
+          if constexpr (LP) psm[wc * 32 + wr * 16 + lane] = best.s;
         }
         __syncthreads();
         if (tid < 32 && m0 + tid < M) {
-          float v = pv[tid];
-          int ix = pi[tid];
-          if (pv[32 + tid] > v || (pv[32 + tid] == v && pi[32 + tid] < ix)) { v = pv[32 + tid]; ix = pi[32 + tid]; }
-          ep.part_val[(size_t)(m0 + tid) * ep.part_stride + tn] = v;
-          ep.part_idx[(size_t)(m0 + tid) * ep.part_stride + tn] = ix;
-          if constexpr (LP) ep.part_sum[(size_t)(m0 + tid) * ep.part_stride + tn] = lse_term(psm[tid], pv[tid], v) + lse_term(psm[32 + tid], pv[32 + tid], v);
+          ArgmaxAcc<LP> h{pv[tid], pi[tid], LP ? psm[tid] : 0.f};
+          h.merge(pv[32 + tid], pi[32 + tid], LP ? psm[32 + tid] : 0.f);
+          h.store(ep.part, m0 + tid, tn);
         }
       }
     }
@@ -593,7 +580,7 @@ __global__ __launch_bounds__(256) void gemm16k_kernel(ALoader A, const uint16_t*
 template <int BM, int BN, int BK, bool GLU, class ALoader, bool LP = false>
 void launch16(const ALoader& A, const uint16_t* W, int M, int N, int K, const GemmEpilogue& ep, hipStream_t s) {
   if constexpr (!LP && BM == 32 && !GLU && std::is_same<ALoader, DenseA16>::value) {
-    if (ep.part_sum) return launch16<BM, BN, BK, GLU, ALoader, true>(A, W, M, N, K, ep, s);  // (token log-probabilities)
+    if (ep.part.sum) return launch16<BM, BN, BK, GLU, ALoader, true>(A, W, M, N, K, ep, s);  // (token log-probabilities)
   }
   const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
   // Dense operands, BK = 64, tiles up to 64x64, (the A/B knob gemm16_ring of rounds 3-5 is gone: the ring won) a ring of
@@ -654,7 +641,7 @@ const char* launch_gemm16(const uint16_t* X, int lda, const uint16_t* W, int M, 
                           bool glu, hipStream_t s) {
   if (M <= 0) return nullptr;
   if (K % 32 != 0 || lda % 8 != 0) return "gemm16: K must be a multiple of 32 and lda of 8";
-  if (K % 64 == 0 && !ep.part_val && gemm256_eligible(M, N, K)) return launch_gemm256(X, lda, W, M, N, K, ep, glu, s);
+  if (K % 64 == 0 && !ep.part.val && gemm256_eligible(M, N, K)) return launch_gemm256(X, lda, W, M, N, K, ep, glu, s);
   return launch_gemm16_small(X, lda, W, M, N, K, ep, glu, s);
 }
 
@@ -663,13 +650,13 @@ const char* launch_gemm16_small(const uint16_t* X, int lda, const uint16_t* W, i
   if (M <= 0) return nullptr;
   if (K % 32 != 0 || lda % 8 != 0) return "gemm16: K must be a multiple of 32 and lda of 8";
   if (glu && N % 32 != 0) return "gemm16: GLU needs N % 32 == 0";
-  if (ep.part_val && (M > 32 || glu || N % 4 != 0 || ep.ldo % 4 != 0 || K % 64 != 0 || ep.rowmap || ep.part_stride < (N + 63) / 64))
-    return "gemm16: argmax partials need M <= 32, 4 | N, 4 | ldo, 64 | K, no row map and part_stride >= ceil(N / 64)";
-  if (ep.part_sum && !ep.part_val) return "gemm16: the log-sum channel needs the argmax partials";
+  if (const char* e = argmax_partials_check(ep.part, (N + 63) / 64)) return e;
+  if (ep.part.val && (M > 32 || glu || N % 4 != 0 || ep.ldo % 4 != 0 || K % 64 != 0 || ep.rowmap))
+    return "gemm16: argmax partials need M <= 32, 4 | N, 4 | ldo, 64 | K and no row map";
   DenseA16 A{X, lda};
   // few tiles and a long K: 32x32 tiles whose 4 waves split K (A/B knob: Q3A_GEMM16_KSPLIT=0 disables)
   static const bool ksplit_on = [] { const char* e = getenv("Q3A_GEMM16_KSPLIT"); return !e || atoi(e) != 0; }();
-  if (ksplit_on && !glu && !ep.part_val && tiles_of(M, N, 32, 64) < 384 && K >= 512 && K % 128 == 0 && N % 4 == 0 && ep.ldo % 4 == 0) {
+  if (ksplit_on && !glu && !ep.part.val && tiles_of(M, N, 32, 64) < 384 && K >= 512 && K % 128 == 0 && N % 4 == 0 && ep.ldo % 4 == 0) {
     const int tiles = ((M + 31) / 32) * ((N + 31) / 32);
     // K steps of 256 in two stages (32 KiB in flight per workgroup); where 256 does not divide K (the encoder's d_model 896)
     // steps of 128 in a ring of four stages (48 KiB in flight) instead of two (16 KiB): 6.5 vs 7.9 us on enc out.  The ring

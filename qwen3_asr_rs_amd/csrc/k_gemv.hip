@@ -19,8 +19,7 @@
 // x can also be assembled on the fly from the flash-decoding partials of k_dattn.hip (o_proj input).
 #include <algorithm>
 
-#include "dev.h"
-#include "kernels.h"
+#include "argmax.h"
 
 
 namespace q3a {
@@ -184,17 +183,14 @@ __device__ __forceinline__ float dot8(const uint4& w, const float (&x)[8], float
 }
 
 // epilogue shared by both variants; acc holds the finished (rstd-scaled) dot products, valid on every lane.
-// LP (mode 3, token log-probabilities): also the block's sum of exp(logit - block max) -> a.part_sum (dev.h lse_term); am_s as am_v.
-template <int NB, int PR, bool LP = false>
+// LP (mode 3, token log-probabilities): also the log-sum channel (argmax.h); am_s as am_v.
+template <int NB, int PR, bool LP>
 __device__ __forceinline__ void gemv_epilogue(const GemvArgs& a, int g, const int (&prow)[PR], float (&acc)[PR][NB],
-                                              float (*am_v)[NB], int (*am_i)[NB], float (*am_s)[NB] = nullptr) {
+                                              float (*am_v)[NB], int (*am_i)[NB], float (*am_s)[NB]) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (a.mode == 3) {  // logits + argmax partial (first-index tie-break: rows ascend with i, wave, block)
-    float bv[NB];
-    int bi[NB];
+  if (a.mode == 3) {  // logits + argmax partial (rows ascend with i, wave, block)
+    ArgmaxAcc<LP> m[NB];
     float lv[LP ? PR : 1][NB];  // LP: the wave's logits (-inf for rows past N)
-#pragma unroll
-    for (int b = 0; b < NB; ++b) { bv[b] = -INFINITY; bi[b] = 0x7fffffff; }
 #pragma unroll
     for (int i = 0; i < PR; ++i) {
       if constexpr (LP) {
@@ -207,34 +203,27 @@ __device__ __forceinline__ void gemv_epilogue(const GemvArgs& a, int g, const in
         float v = acc[i][b];
         if (a.bias) v += a.bias[prow[i]];
         if (lane == 0 && a.out) a.out[(size_t)b * a.ldo + prow[i]] = v;
-        if (v > bv[b]) { bv[b] = v; bi[b] = prow[i]; }
+        if (v > m[b].v) { m[b].v = v; m[b].i = prow[i]; }
         if constexpr (LP) lv[i][b] = v;
       }
     }
     if (lane == 0) {
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
-        am_v[wave][b] = bv[b]; am_i[wave][b] = bi[b];
+        am_v[wave][b] = m[b].v; am_i[wave][b] = m[b].i;
         if constexpr (LP) {
           float ws = 0.f;
 #pragma unroll
-          for (int i = 0; i < PR; ++i) ws += lse_term(1.f, lv[i][b], bv[b]);
+          for (int i = 0; i < PR; ++i) ws += lse_term(1.f, lv[i][b], m[b].v);
           am_s[wave][b] = ws;
         }
       }
     }
     __syncthreads();
     if (tid < NB) {
-      float v = am_v[0][tid], vs = LP ? am_s[0][tid] : 0.f;
-      int ix = am_i[0][tid];
-      for (int w = 1; w < 4; ++w) {
-        const float pv = v;
-        if (am_v[w][tid] > v || (am_v[w][tid] == v && am_i[w][tid] < ix)) { v = am_v[w][tid]; ix = am_i[w][tid]; }
-        if constexpr (LP) vs = lse_term(vs, pv, v) + lse_term(am_s[w][tid], am_v[w][tid], v);
-      }
-      a.part_val[(size_t)tid * a.part_stride + (g >> 2)] = v;
-      a.part_idx[(size_t)tid * a.part_stride + (g >> 2)] = ix;
-      if constexpr (LP) a.part_sum[(size_t)tid * a.part_stride + (g >> 2)] = vs;
+      ArgmaxAcc<LP> r{am_v[0][tid], am_i[0][tid], LP ? am_s[0][tid] : 0.f};
+      for (int w = 1; w < 4; ++w) r.merge(am_v[w][tid], am_i[w][tid], LP ? am_s[w][tid] : 0.f);
+      r.store(a.part, tid, g >> 2);
     }
     return;
   }
@@ -284,8 +273,6 @@ template <int PR, int KI, bool RMS, bool ATTN, int MF = 0, bool XL = false>
 __global__ __launch_bounds__(256) void gemv1_kernel(GemvArgs a) {
   static_assert(!XL || !ATTN, "the merged attention vector already goes through LDS");
   __shared__ __attribute__((aligned(16))) float xl_x[XL ? KI * 512 : 4], xl_w[(XL && RMS) ? KI * 512 : 4];
-  __shared__ float am_v[4][1];
-  __shared__ int am_i[4][1];
   __shared__ __attribute__((aligned(16))) float x_s[ATTN ? KI * 512 : 4];  // only the attention merge goes through LDS
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   Q3A_STAMP_AT(a.stamp, blockIdx.x, 0);  // entry
@@ -472,28 +459,7 @@ __global__ __launch_bounds__(256) void gemv1_kernel(GemvArgs a) {
   if (RMS) rstd = rstd_of(wave_sum_fast(ss) / (float)K + a.eps, a.fast_math != 0);  // a wave covers all of K
 #pragma unroll
   for (int i = 0; i < PR; ++i) acc[i][0] = wave_sum_fast(acc[i][0]) * rstd + bv[i];
-  // epilogue (bias already added; acc is valid on every lane)
-  if (a.mode == 3) {  // logits + argmax partial (first-index tie-break: rows ascend with i, wave, block)
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-#pragma unroll
-    for (int i = 0; i < PR; ++i) {
-      if (prow[i] < 0) continue;
-      if (lane == 0 && a.out) a.out[prow[i]] = acc[i][0];
-      if (acc[i][0] > best) { best = acc[i][0]; bi = prow[i]; }
-    }
-    if (lane == 0) { am_v[wave][0] = best; am_i[wave][0] = bi; }
-    __syncthreads();
-    if (tid == 0) {
-      float v = am_v[0][0];
-      int ix = am_i[0][0];
-      for (int w = 1; w < 4; ++w)
-        if (am_v[w][0] > v || (am_v[w][0] == v && am_i[w][0] < ix)) { v = am_v[w][0]; ix = am_i[w][0]; }
-      a.part_val[blockIdx.x] = v;
-      a.part_idx[blockIdx.x] = ix;
-    }
-    return;
-  }
+  // epilogue (bias already added; acc is valid on every lane; mode 3 runs gemv1_head_kernel)
   if (lane != 0) return;
   if (a.mode != 2) {
 #pragma unroll
@@ -511,11 +477,11 @@ __global__ __launch_bounds__(256) void gemv1_kernel(GemvArgs a) {
 // One 16-row argmax block (4 waves x PR rows) of the one-sequence lm_head: the arithmetic of gemv1_kernel<PR, KI, true, false>
 // (same lane / column assignment, same order of the products and sums, same rstd, first-index tie rule).  Used by the
 // unpruned launch (gemv1_head_kernel: block = blockIdx.x) AND by the rescore of the pruned argmax (lm_head_rescore_kernel): the
-// two cannot drift apart.  Ends with a barrier; the block's (value, row) is valid in thread 0.  LP (token log-probabilities): also
-// the block's sum of exp(logit - value) in *out_s (am_s: 4 floats of LDS); the value / row arithmetic is the same either way.
+// two cannot drift apart.  Ends with a barrier; the block's partial is valid in thread 0's `out`.  LP (token log-probabilities):
+// with the log-sum channel (am_s: 4 floats of LDS); the value / row arithmetic is the same either way.
 template <int PR, int KI, bool LP = false>
-__device__ __forceinline__ void gemv1_head_block(const GemvArgs& a, int blk, float (&am_v)[4][1], int (&am_i)[4][1],
-                                                 float& out_v, int& out_i, float* am_s = nullptr, float* out_s = nullptr) {
+__device__ __forceinline__ void gemv1_head_block(const GemvArgs& a, int blk, float (&am_v)[4][1], int (&am_i)[4][1], float* am_s,
+                                                 ArgmaxAcc<LP>& out) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int K = a.K;
   const int g = blk * 4 + wave;
@@ -572,33 +538,24 @@ __device__ __forceinline__ void gemv1_head_block(const GemvArgs& a, int blk, flo
   const float rstd = rstd_of(wave_sum_fast(ss) / (float)K + a.eps, a.fast_math != 0);  // a wave covers all of K
 #pragma unroll
   for (int i = 0; i < PR; ++i) acc[i] = wave_sum_fast(acc[i]) * rstd + bv[i];
-  float best = -INFINITY;
-  int bi = 0x7fffffff;
+  ArgmaxAcc<LP> m;
 #pragma unroll
   for (int i = 0; i < PR; ++i) {
     if (prow[i] < 0) continue;
     if (lane == 0 && a.out) a.out[prow[i]] = acc[i];
-    if (acc[i] > best) { best = acc[i]; bi = prow[i]; }
+    if (acc[i] > m.v) { m.v = acc[i]; m.i = prow[i]; }
   }
-  if (lane == 0) { am_v[wave][0] = best; am_i[wave][0] = bi; }
+  if (lane == 0) { am_v[wave][0] = m.v; am_i[wave][0] = m.i; }
   if constexpr (LP) {
     float ws = 0.f;
 #pragma unroll
-    for (int i = 0; i < PR; ++i) ws += prow[i] < 0 ? 0.f : lse_term(1.f, acc[i], best);
+    for (int i = 0; i < PR; ++i) ws += prow[i] < 0 ? 0.f : lse_term(1.f, acc[i], m.v);
     if (lane == 0) am_s[wave] = ws;
   }
   __syncthreads();
   if (tid == 0) {
-    float v = am_v[0][0], vs = LP ? am_s[0] : 0.f;
-    int ix = am_i[0][0];
-    for (int w = 1; w < 4; ++w) {
-      const float pv = v;
-      if (am_v[w][0] > v || (am_v[w][0] == v && am_i[w][0] < ix)) { v = am_v[w][0]; ix = am_i[w][0]; }
-      if constexpr (LP) vs = lse_term(vs, pv, v) + lse_term(am_s[w], am_v[w][0], v);
-    }
-    out_v = v;
-    out_i = ix;
-    if constexpr (LP) *out_s = vs;
+    out = {am_v[0][0], am_i[0][0], LP ? am_s[0] : 0.f};
+    for (int w = 1; w < 4; ++w) out.merge(am_v[w][0], am_i[w][0], LP ? am_s[w] : 0.f);
   }
 }
 
@@ -607,14 +564,9 @@ __global__ __launch_bounds__(256) void gemv1_head_kernel(GemvArgs a) {
   __shared__ float am_v[4][1];
   __shared__ int am_i[4][1];
   __shared__ float am_s[LP ? 4 : 1];
-  float v, vs;
-  int ix;
-  gemv1_head_block<PR, KI, LP>(a, blockIdx.x, am_v, am_i, v, ix, am_s, &vs);
-  if (threadIdx.x == 0) {
-    a.part_val[blockIdx.x] = v;
-    a.part_idx[blockIdx.x] = ix;
-    if constexpr (LP) a.part_sum[blockIdx.x] = vs;
-  }
+  ArgmaxAcc<LP> r;
+  gemv1_head_block<PR, KI, LP>(a, blockIdx.x, am_v, am_i, am_s, r);
+  if (threadIdx.x == 0) r.store(a.part, 0, blockIdx.x);
 }
 
 // ---- pruned argmax of the one-sequence lm_head ------------------------------------------------------------
@@ -810,20 +762,18 @@ __global__ __launch_bounds__(256) void lm_head_rescore_kernel(LmHeadArgsDev p) {
   if (mb < nb) cand[tid] = !(hv < T);
   __syncthreads();
   const int nj = (nb - blockIdx.x + G - 1) / G;
-  float bv = -INFINITY;
-  int bi = 0x7fffffff, nc = 0;
+  ArgmaxAcc<false> best;
+  int nc = 0;
   for (int j = 0; j < nj; ++j) {
     if (!cand[j]) continue;  // uniform
-    float v = 0.f;
-    int ix = 0;
-    gemv1_head_block<PR, KI>(p.g, blockIdx.x + j * G, am_v, am_i, v, ix);
-    if (tid == 0 && (v > bv || (v == bv && ix < bi))) { bv = v; bi = ix; }
+    ArgmaxAcc<false> r;
+    gemv1_head_block<PR, KI>(p.g, blockIdx.x + j * G, am_v, am_i, nullptr, r);
+    if (tid == 0) best.merge(r);
     ++nc;
     __syncthreads();  // am_v / am_i are reused by the next candidate
   }
   if (tid == 0) {
-    p.g.part_val[blockIdx.x] = bv;
-    p.g.part_idx[blockIdx.x] = bi;
+    best.store(p.g.part, 0, blockIdx.x);
     if (p.stats) {
       if (nc) atomicAdd(&p.stats[0], nc);
       if (blockIdx.x == 0) atomicAdd(&p.stats[1], 1);
@@ -838,7 +788,7 @@ __global__ __launch_bounds__(256) void gemvn_kernel(GemvArgs a) {
   __shared__ float red[NB][4];
   __shared__ float am_v[4][NB];
   __shared__ int am_i[4][NB];
-  __shared__ float am_s[4][LP ? NB : 1];
+  __shared__ float am_s[LP ? 4 : 1][NB];  // (LP only)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int K = a.K;
   const int g = blockIdx.x * 4 + wave;
@@ -916,8 +866,7 @@ __global__ __launch_bounds__(256) void gemvn_kernel(GemvArgs a) {
 #pragma unroll
     for (int i = 0; i < PR; ++i) acc[i][b] = wave_sum_fast(acc[i][b]) * rstd;
   }
-  if constexpr (LP) gemv_epilogue<NB, PR, true>(a, g, prow, acc, am_v, am_i, am_s);
-  else gemv_epilogue<NB, PR>(a, g, prow, acc, am_v, am_i);
+  gemv_epilogue<NB, PR, LP>(a, g, prow, acc, am_v, am_i, am_s);
 }
 
 template <int PR, int KI>
@@ -925,16 +874,19 @@ void launch1k(const GemvArgs& a, hipStream_t s) {
   const dim3 grid(gemv_blocks(a)), block(256);
   // up to 8 key splits (contexts up to 1024 keys): the merge's partials go in FRONT of the weight stream (round 6: -1.2 % per step at
   // 0.6B x 1 and x 2, neutral at 1.7B; profiles/r6_ab_merge_first.txt); beyond, the chunked merge behind it
-  if (a.attn_po && KI <= 4 && a.attn_nsplit <= 4) hipLaunchKernelGGL((gemv1_kernel<PR, KI, false, true, 4>), grid, block, 0, s, a);
-  else if (a.attn_po && KI <= 4 && a.attn_nsplit <= 8) hipLaunchKernelGGL((gemv1_kernel<PR, KI, false, true, 8>), grid, block, 0, s, a);
-  else if (a.attn_po) hipLaunchKernelGGL((gemv1_kernel<PR, KI, false, true>), grid, block, 0, s, a);
-  else if (a.rms_w) {
+  if (a.attn_po) {
+    if constexpr (KI <= 4) {  // (not instantiated beyond: never launched)
+      if (a.attn_nsplit <= 4) { hipLaunchKernelGGL((gemv1_kernel<PR, KI, false, true, 4>), grid, block, 0, s, a); return; }
+      if (a.attn_nsplit <= 8) { hipLaunchKernelGGL((gemv1_kernel<PR, KI, false, true, 8>), grid, block, 0, s, a); return; }
+    }
+    hipLaunchKernelGGL((gemv1_kernel<PR, KI, false, true>), grid, block, 0, s, a);
+  } else if (a.rms_w) {
     // Norm-fused projections at K <= 1024 (qkv, gate / up at hidden 1024): x and the norm weight once per workgroup through LDS
     // (round 6: 609.7 -> 595.1 us per step at 0.6B, ids identical; profiles/r6_ab_gemv_x_lds.txt).  Not where it was measured to
     // lose: K = 2048 (+18 %: 32 KiB of LDS per workgroup halves the residency of the 1536-workgroup gate / up launch), the down
     // projection (+4 %: x in front of the weights delays them), the lm_head (+1.3 %: a barrier in each of 9496 workgroups).
     if (a.mode == 3) {
-      if (a.part_sum) hipLaunchKernelGGL((gemv1_head_kernel<PR, KI, true>), grid, block, 0, s, a);
+      if (a.part.sum) hipLaunchKernelGGL((gemv1_head_kernel<PR, KI, true>), grid, block, 0, s, a);
       else hipLaunchKernelGGL((gemv1_head_kernel<PR, KI>), grid, block, 0, s, a);
       return;
     }
@@ -954,7 +906,7 @@ void launch1(const GemvArgs& a, hipStream_t s) {
 }
 template <int NB, int PR, int PF>
 void launchn(const GemvArgs& a, hipStream_t s) {
-  if (a.part_sum) hipLaunchKernelGGL((gemvn_kernel<NB, PR, PF, true>), dim3(gemv_blocks(a)), dim3(256), (size_t)NB * a.K * sizeof(float), s, a);
+  if (a.part.sum) hipLaunchKernelGGL((gemvn_kernel<NB, PR, PF, true>), dim3(gemv_blocks(a)), dim3(256), (size_t)NB * a.K * sizeof(float), s, a);
   else hipLaunchKernelGGL((gemvn_kernel<NB, PR, PF>), dim3(gemv_blocks(a)), dim3(256), (size_t)NB * a.K * sizeof(float), s, a);
 }
 
@@ -979,10 +931,11 @@ const char* launch_lm_head_quantize(const uint16_t* W, int N, int K, int8_t* Q, 
 const char* lm_head_prune_check(const LmHeadPruneArgs& a) {
   const GemvArgs& g = a.g;
   if (g.mode != 3 || !g.rms_w || !g.x || g.attn_po || g.bias) return "lm_head_prune: needs the plain mode-3 GEMV with a fused norm";
-  if (g.part_sum) return "lm_head_prune: token log-probabilities need every logit (the full GEMV)";
+  if (g.part.sum) return "lm_head_prune: token log-probabilities need every logit (the full GEMV)";
   if (gemv_rows_per_wave(g) != 4 || gemv_blocks(g) != lm_head_prune_blocks(g)) return "lm_head_prune: the GEMV does not run 16-row blocks here";
   if (g.K % 8 != 0 || a.qcols != lm_head_q_cols(g.K)) return "lm_head_prune: int8 row width does not match the hidden size";
-  if (!a.Wq || !a.qs || !a.blk_lo || !a.blk_hi || !g.part_val || !g.part_idx) return "lm_head_prune: missing buffer";
+  if (!a.Wq || !a.qs || !a.blk_lo || !a.blk_hi || !g.part.val) return "lm_head_prune: missing buffer";
+  if (const char* e = argmax_partials_check(g.part, 1)) return e;  // (the rescore grid against the stride: launch_lm_head_rescore)
   return nullptr;
 }
 const char* launch_lm_head_approx(const LmHeadPruneArgs& a, hipStream_t s) {
@@ -1000,7 +953,7 @@ int lm_head_rescore_groups(const GemvArgs& g, int n_cu) {
 const char* launch_lm_head_rescore(const LmHeadPruneArgs& a, int groups, hipStream_t s) {
   if (const char* e = lm_head_prune_check(a)) return e;
   const LmHeadArgsDev p = lm_head_dev_args(a);
-  if (groups < 1 || groups > a.g.part_stride || (p.n_blk + groups - 1) / groups > 256) return "lm_head_prune: bad rescore grid";
+  if (groups < 1 || groups > a.g.part.stride || (p.n_blk + groups - 1) / groups > 256) return "lm_head_prune: bad rescore grid";
   if (a.qcols == 1024) hipLaunchKernelGGL((lm_head_rescore_kernel<4, 2>), dim3(groups), dim3(256), 0, s, p);
   else hipLaunchKernelGGL((lm_head_rescore_kernel<4, 4>), dim3(groups), dim3(256), 0, s, p);
   return nullptr;
@@ -1010,14 +963,13 @@ const char* launch_gemv(const GemvArgs& a0, int NB, hipStream_t s) {
   if (a0.K % 8 != 0) return "gemv: K must be a multiple of 8";
   if (a0.K > 6144) return "gemv: K > 6144 unsupported";
   if (a0.mode == 2 && a0.N % 32 != 0) return "gemv: GLU needs N % 32 == 0";
-  if (a0.mode == 3 && (!a0.part_val || !a0.part_idx || gemv_blocks(a0) > a0.part_stride))
-    return "gemv: argmax partial buffer missing/too small";
+  if (a0.mode == 3 && !a0.rms_w) return "gemv: mode 3 (the lm_head) needs the fused final norm";
+  if (a0.mode == 3 && !a0.part.val) return "gemv: argmax partial buffer missing";
+  if (const char* e = argmax_partials_check(a0.part, a0.mode == 3 ? gemv_blocks(a0) : 0)) return e;
+  if (a0.part.sum && a0.mode != 3) return "gemv: log-sum partials need mode 3";
   if (a0.attn_po && (a0.K % 128 != 0 || a0.K != a0.attn_heads * 128)) return "gemv: attention-partial input needs K = heads*128";
   if (a0.attn_po && a0.rms_w) return "gemv: attention-partial input cannot be combined with a fused RMSNorm";
   if (a0.attn_po && (NB < 4 ? NB : 4) * a0.attn_heads * a0.attn_nsplit > ATTN_F_MAX) return "gemv: too many attention splits for the LDS scale table";
-  // the log-sum channel: mode 3 only, and for one sequence only in the fused-norm head kernel (gemv1_kernel's mode 3 has none)
-  if (a0.part_sum && (a0.mode != 3 || a0.attn_po || (NB % 2 == 1 && !a0.rms_w)))
-    return "gemv: log-sum partials need mode 3 and, for an odd batch, the fused final norm";
   const int pr = gemv_rows_per_wave(a0);
   const int nb_cap = (int)((64 * 1024) / ((size_t)a0.K * 4));  // rows of x that fit in 64 KiB of LDS
   int done = 0;
@@ -1026,8 +978,7 @@ const char* launch_gemv(const GemvArgs& a0, int NB, hipStream_t s) {
     if (a0.x) a.x = a0.x + (size_t)done * a0.ldx;
     if (a0.out) a.out = a0.out + (size_t)done * a0.ldo;
     if (a0.resid) a.resid = a0.resid + (size_t)done * a0.ldo;
-    if (a0.part_val) { a.part_val = a0.part_val + (size_t)done * a0.part_stride; a.part_idx = a0.part_idx + (size_t)done * a0.part_stride; }
-    if (a0.part_sum) a.part_sum = a0.part_sum + (size_t)done * a0.part_stride;
+    a.part = a0.part.at(done);
     if (a0.attn_po) {
       const size_t adv = (size_t)done * a0.attn_heads * a0.attn_nsplit;
       a.attn_pm = a0.attn_pm + adv; a.attn_pl = a0.attn_pl + adv; a.attn_po = a0.attn_po + adv * 128;

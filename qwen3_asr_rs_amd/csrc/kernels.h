@@ -16,6 +16,29 @@
 
 namespace q3a {
 
+// ---- argmax partials ----------------------------------------------------------------------------------
+// What every producer of the decode step's argmax writes and argmax_finalize merges: per row (sequence) and partial (a block of
+// the vocabulary) the block maximum val, its first index idx and, for token log-probabilities, sum = sum exp(logit - val) over
+// the block; entry [row * stride + col].  sum is null when that channel is off.  The tie rule and the (max, sum) merge live in
+// ONE place, argmax.h ArgmaxAcc.
+struct ArgmaxPartials {
+  float* val = nullptr;
+  int* idx = nullptr;
+  float* sum = nullptr;
+  int stride = 0;
+  ArgmaxPartials at(size_t rows) const {  // the same partials from row `rows` on
+    const size_t o = rows * stride;
+    return {val ? val + o : nullptr, idx ? idx + o : nullptr, sum ? sum + o : nullptr, stride};
+  }
+};
+// the rules every producer and argmax_finalize share: val and idx go together, sum needs them, a row holds n_part entries
+inline const char* argmax_partials_check(const ArgmaxPartials& p, int n_part) {
+  if (!p.val != !p.idx) return "argmax partials: val and idx go together";
+  if (p.sum && !p.val) return "argmax partials: the log-sum channel needs val and idx";
+  if (p.val && p.stride < n_part) return "argmax partials: buffer too small";
+  return nullptr;
+}
+
 // ---- GEMM (k_gemm.hip) -----------------------------------------------------------------------------
 struct GemmEpilogue {
   float* out = nullptr;          // [rows][ldo] fp32
@@ -27,12 +50,9 @@ struct GemmEpilogue {
   const int* rowmap = nullptr;   // GEMM row m -> output row (negative: drop the row); null = identity
   const float* addend = nullptr; // [addend_period][ldo] added before the activation (positional embedding)
   int addend_period = 1;
-  // k_gemm16.hip, M <= 32 (lm_head of a batched decode step): per output row the maximum of each 64-column tile and its
-  // column (first index on ties) -> part_val / part_idx[row * part_stride + tile]; `out` may then be null (no logits stored)
-  float* part_val = nullptr;
-  int* part_idx = nullptr;
-  int part_stride = 0;
-  float* part_sum = nullptr;  // with part_val, optional: sum over the tile's columns of exp(logit - part_val) (token log-probabilities)
+  // k_gemm16.hip, M <= 32 (lm_head of a batched decode step): one argmax partial per output row and 64-column tile (col = tile);
+  // `out` may then be null (no logits stored)
+  ArgmaxPartials part;
   Q3A_STAMP_FIELD
 };
 // Y = X[M][K](fp32, row stride lda) . W[N][K]^T(bf16).  glu: W rows are [16 gate|16 up] blocks, out has N/2 columns.
@@ -173,12 +193,10 @@ struct GemvArgs {
   const uint16_t* W; int N; int K;
   const float* bias;            // [N] or null
   int mode;                     // 0: store, 1: out = resid + y, 2: GLU (W rows in [16 gate|16 up] blocks; N = 2*inter),
-                                // 3: logits (out nullable) + per-block argmax partials
+                                // 3 (needs rms_w: the lm_head): logits (out nullable) + per-block argmax partials
   float* out; int ldo;
   const float* resid;
-  float* part_val; int* part_idx; int part_stride;  // mode 3: [NB][part_stride], entry = blockIdx.x
-  float* part_sum;              // mode 3, optional (token log-probabilities): the same layout, sum over the block's rows of
-                                // exp(logit - part_val); the fused-norm one-sequence head and the NB in {2, 4} kernels only
+  ArgmaxPartials part;          // mode 3: one partial per sequence and workgroup (col = blockIdx.x)
   // optional: x = attention output merged on the fly from the flash-decoding partials of launch_decode_attn
   // (x/ldx ignored; K must equal attn_heads*128)
   const float* attn_pm; const float* attn_pl; const float* attn_po; int attn_nsplit; int attn_heads;
@@ -194,7 +212,7 @@ int gemv_rows_per_wave(const GemvArgs& a);
 // Exact argmax of the one-sequence lm_head (mode 3, fused final norm) from an int8 pre-pass (k_gemv.hip): pass 1 streams the int8
 // copy and writes per 16-row block lo_b / hi_b of the approximate logits +- a rigorous bound; pass 2 (`groups` workgroups) rescores
 // with the bf16 arithmetic of the unpruned launch only the blocks with hi_b >= max lo_b and leaves ONE argmax partial per workgroup in
-// g.part_val / g.part_idx (argmax_finalize with n_part = groups).  The ids are those of launch_gemv.
+// g.part (argmax_finalize with n_part = groups; no log-sum channel).  The ids are those of launch_gemv.
 struct LmHeadPruneArgs {
   GemvArgs g;                   // the mode-3 launch it replaces (g.out is not written by pass 1; pass 2 stores rescored rows if set)
   const int8_t* Wq; int qcols;  // launch_lm_head_quantize: [N][qcols], columns in the GEMV's lane order
@@ -297,9 +315,8 @@ const char* launch_attn_combine(const float* pm, const float* pl, const float* p
 // out16 != null: bf16 there instead of out; frag: in skinny_frag_index order (S <= 32)
 
 struct FinalizeArgs {
-  const float* part_val;   // [S][part_stride] block-partial maxima ...
-  const int* part_idx;     // ... and their vocabulary indices
-  int part_stride, n_part;
+  ArgmaxPartials part;     // [S] rows of n_part partials
+  int n_part;
   int V;
   int* next_tok;           // [S] token to feed next (written)
   int* out_ids;            // [S][out_stride] generated ids (written at step_count[s])
@@ -319,14 +336,12 @@ struct FinalizeArgs {
   const float* cos_t; const float* sin_t;  // RoPE tables [max_pos][64]
   float* rope_cur;         // [S][128] (written): cos | sin row of the updated pos[s] (DecodeAttnArgs::rope_cur); nullable
   NextNormOut nn;          // pre-normalised copy of x_next for the first layer's qkv GEMM (skinny path)
-  // token log-probabilities (both set or both null): part_sum [S][part_stride] = sum exp(logit - part_val) per partial; out_lp
-  // [S][out_stride] receives logit[id] - logsumexp(logits) of the chosen id next to out_ids (NaN where the all-NaN guard fires)
-  const float* part_sum;
+  // token log-probabilities (with part.sum, else null): [S][out_stride] logit[id] - logsumexp(logits) of the chosen id next to
+  // out_ids (NaN where the all-NaN guard fires)
   float* out_lp;
 };
-// block partials of logits [S][V] (GEMM decode path; the GEMV lm_head produces its own); psum nullable: the log-sum channel
-const char* launch_argmax_partials(const float* logits, int V, int S, float* pval, int* pidx, int stride, int nblk,
-                                   hipStream_t s, float* psum = nullptr);
+// nblk block partials per row of logits [S][V] (GEMM decode path; the GEMV lm_head produces its own)
+const char* launch_argmax_partials(const float* logits, int V, int S, const ArgmaxPartials& p, int nblk, hipStream_t s);
 const char* launch_argmax_finalize(const FinalizeArgs& a, int S, hipStream_t s);
 // x_next[s] = embed[tok[s]]; next_tok[s] = tok[s]  (teacher forcing)
 const char* launch_set_tokens(const int* tok, int S, const uint16_t* embed, int H, float* x_next, int* next_tok, hipStream_t s,

@@ -7,6 +7,7 @@ engine's own logits, the values against the fp32 oracle at the 0.6B dimensions, 
 that a cached graph of another batch shape is never replayed for the channel, the error cases and the CLI's confidence line."""
 import os
 import re
+import shutil
 import subprocess
 
 import numpy as np
@@ -46,12 +47,35 @@ def _stage_run(eng, clips, steps):
     return L, T, eng.fetch_logprobs()
 
 
-@pytest.mark.parametrize("precise,B", [(False, 1), (False, 2), (False, 5), (False, 32), (False, 40), (True, 1), (True, 5)])
-def test_logprobs_match_log_softmax_of_the_engines_logits(tiny_dir, precise, B):
+@pytest.fixture(scope="module")
+def twin_rows_dir(tiny_untied_dir):
+    """The untied tiny checkpoint with lm_head rows V/2 .. V-1 replaced by rows 0 .. V/2-1: every logit has an exact twin V/2 rows
+    later, in another block, wave, workgroup and partial, so every path's argmax meets a tie at its maximum."""
+    d = "/tmp/q3a_ckpt_tiny_untied_twin_rows"
+    if os.path.exists(d):
+        shutil.rmtree(d)
+    shutil.copytree(tiny_untied_dir, d)
+    key = synthetic.output_embedding_key(d)
+    head = synthetic.read_tensor(d, key).astype(np.float32)
+    h = head.shape[0] // 2
+    assert head.shape[0] == 2 * h
+    head[h:] = head[:h]
+    synthetic.overwrite_tensor(d, key, head)
+    return d
+
+
+_PATHS = [(False, 1), (False, 2), (False, 5), (False, 32), (False, 40), (True, 1), (True, 5)]
+
+
+@pytest.mark.parametrize("precise,B,head", [pytest.param(p, b, "tiny", id=f"{p}-{b}") for p, b in _PATHS] +
+                         [pytest.param(p, b, "twin_rows", id=f"{p}-{b}-twin_rows") for p, b in _PATHS])
+def test_logprobs_match_log_softmax_of_the_engines_logits(request, precise, B, head):
     """One path per case: B = 1 the fused-norm GEMV head, 2 the two-sequence GEMV, 5 / 32 the gemm16 argmax epilogue, 40 (two
-    decode groups) and the precise mode argmax_partial_kernel.  Graph-replayed stage API, so the first step is the prefill's."""
+    decode groups) and the precise mode argmax_partial_kernel.  Graph-replayed stage API, so the first step is the prefill's.
+    twin_rows: the tie rule (the first index wins) on every path -- every id lies in the first half of the vocabulary."""
     steps = 6
-    eng = HipEngine(tiny_dir, 0, precise=precise, max_new_tokens=16, token_logprobs=True)
+    d = request.getfixturevalue("tiny_dir" if head == "tiny" else "twin_rows_dir")
+    eng = HipEngine(d, 0, precise=precise, max_new_tokens=16, token_logprobs=True)
     L, T, lp = _stage_run(eng, _clips(B), steps)
     eng.close()
     assert len(lp) == B
@@ -60,12 +84,14 @@ def test_logprobs_match_log_softmax_of_the_engines_logits(tiny_dir, precise, B):
         assert len(lp[b]) == steps, (b, len(lp[b]))   # random weights: no EOS within a few steps
         for s in range(steps):
             assert int(T[s][b]) == int(np.argmax(L[s][b])), (b, s)
+            if head == "twin_rows":
+                assert int(T[s][b]) < len(L[s][b]) // 2, (precise, B, b, s, int(T[s][b]))
             ref = _log_softmax_at(L[s][b], int(T[s][b]))
             err = abs(float(lp[b][s]) - ref)
             worst = max(worst, err)
             assert err <= 1e-4, (precise, B, b, s, float(lp[b][s]), ref)
     assert np.all(np.concatenate(lp) <= 0.0)
-    print(f"[logprobs] precise={precise} B={B}: {B * steps} values, worst |lp - log_softmax| {worst:.2e}")
+    print(f"[logprobs] {head} precise={precise} B={B}: {B * steps} values, worst |lp - log_softmax| {worst:.2e}")
 
 
 def test_logprobs_against_the_oracle_0p6b_dims():

@@ -85,17 +85,24 @@ def test_transcribe_result_constructs_from_the_four_old_fields():
     assert r2.avg_logprob == -0.5
 
 
-def test_engine_routes_the_channel_to_every_argmax_producer():
+def test_engine_hands_one_argmax_descriptor_to_every_producer():
     """The engine passes the log-sum channel to each producer of argmax partials that run_head can launch, the finalize writes
     out_lp, the option is part of the graph signature, and the pruned one-sequence argmax is refused with it (the full GEMV runs)."""
     src = _read("qwen3_asr_rs_amd", "csrc", "engine.cpp")
     head = src[src.index("  void run_head(int advance) {"):]
     head = head[:head.index("\n  }\n")]
-    assert "g.part_sum = psum" in head and "ep.part_sum = psum" in head
-    assert head.count("launch_argmax_partials(") == head.count("stream, psum)") == 2
-    assert "f.part_sum = psum" in head and "out_lp" in head
+    # ONE descriptor, built once, that carries the sum exactly when token_lp() ...
+    decl = re.findall(r"const ArgmaxPartials part\{([^;]*)\};", head)
+    assert len(decl) == 1, decl
+    assert re.search(r"token_lp\(\)\s*\?\s*part_sum\.as<float>\(\)\s*:\s*nullptr", decl[0]), decl[0]
+    assert head.count("ArgmaxPartials") == 1 and "part_sum" not in head.replace(decl[0], "")
+    # ... handed to every producer run_head can launch (the GEMV head, whose prune args copy g; the gemm16 epilogue; both
+    # argmax_partial launches) and to the finalize, which writes out_lp with it
+    assert "g.part = part;" in head and "pa = prune_args(g)" in head and "ep.part = part;" in head
+    assert head.count("launch_argmax_partials(") == head.count("launch_argmax_partials(logits.as<float>(), V, S, part, n_part, stream)") == 2
+    assert "f.part = part;" in head and re.search(r"f\.out_lp = part\.sum \? out_lp\.as<float>\(\) : nullptr;", head)
     sig = src[src.index("std::string make_graph_sig() const"):]
     assert "token_lp()" in sig[:sig.index("return buf;")]
     gemv = _read("qwen3_asr_rs_amd", "csrc", "k_gemv.hip")
     check = gemv[gemv.index("const char* lm_head_prune_check("):]
-    assert "g.part_sum" in check[:check.index("\n}\n")]
+    assert re.search(r"if \(g\.part\.sum\) return", check[:check.index("\n}\n")])
