@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the Qwen3-ASR hot path on MI355X (contract: see the task statement / DESIGN.md section 6).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -10,14 +10,22 @@ over one batch of synthetic 30 s clips.  Default workload = BASELINE.json config
 1 clip per GPU, 100 new tokens (EOS ignored: the weights are synthetic, so natural EOS never fires; 100 tokens / 30 s is
 the speech rate the survey fixes).  Rank 0 prints ONE JSON line.
 
+Plain run and --full.  A plain run does only what the headline needs: it writes the seeded checkpoint into a temporary
+directory of its own (removed at exit, so no run reads what an earlier one wrote), builds the engine, runs W untimed and K
+timed steps, writes --dump-outputs and prints the headline fields (metric, value, unit, n_gpus, steps, warmup, ms_per_step,
+higher_is_better, scaling, vs_baseline, dtype, data, config, stage_ms).  Everything else below (host_to_host, roofline and
+its rocprofv3 child passes, measured_peaks, precise_mode, cpu_baseline, natural_eos, two_streams, extra, multi_gpu) is
+measured only with --full, which uses the shared checkpoint directories under /tmp as before; --no-cpu-baseline, --no-rocprof,
+--no-pmc, --no-peaks, --no-extra and --no-native-group-leg trim a --full run.  The timed steps are the same in both.
+
 Launching.  N = 1: `python bench.py`.  N > 1: one process per GPU under torch.distributed.run (the driver's command above);
 a bare `python bench.py --gpus N` starts itself under torch.distributed.run on 127.0.0.1 with a free port (a child process), so
-the same command shape works at every N.  With N > 1 the line also carries an `extra` leg: BASELINE configs[4]'s per-GPU
+the same command shape works at every N.  With N > 1 the --full line also carries an `extra` leg: BASELINE configs[4]'s per-GPU
 workload (Qwen3-ASR-1.7B, 32 clips per GPU, weights shipped with ONE RCCL broadcast of the arena); the q3a_group_* leg (on by default; --no-native-group-leg) adds
 the native q3a_group_* path (one process, one host thread per GPU, RCCL called from C++), run as a child process with a time limit so
 that neither a crash nor a hang inside it can cost the line.
 
-What is inside the clock
+What is inside the clock (the fields after `value` are --full only)
   value               PCM already resident in HBM when the clock starts (the task contract: the PCIe-inclusive rate is never
                       `value`), generated ids fetched to the host inside the clock (q3a_run_resident + q3a_fetch_ids).
   value_host_to_host  = host_to_host.value: q3a_transcribe_batch_ptrs, host PCM -> H2D -> hot path -> ids on the host (SURVEY.md
@@ -52,6 +60,7 @@ roofline (dominant kernel = the one with the largest share of kernel time IN THE
 from __future__ import annotations
 
 import argparse
+import atexit
 import glob
 import json
 import os
@@ -531,6 +540,34 @@ def two_streams_leg(model_dir, clips, new_tokens, precise, batches=6):
             "one_engine": {"value": round(seconds / one, 3), "ms_per_batch": round(one * 1e3, 3)}, "ids_equal_to_one_engine": same}
 
 
+def broadcast_arena_checked(dist, dev, rank, model_dir):
+    """--full, N > 1: the arena broadcast of the set-up, timed, with the checks of the self-validating line: how
+    many ranks RCCL itself saw (a device all-reduce of ones), the time of the ONE arena broadcast (rank 0 packs on the host first: pack
+    and wire time apart) and the wire time and bit-identity of a second, device-to-device broadcast.  Returns (arena, multi_gpu block)."""
+    from qwen3_asr_rs_amd.distributed import broadcast_arena
+    ones = torch.ones(1, dtype=torch.int32, device=dev)
+    dist.all_reduce(ones, op=dist.ReduceOp.SUM)
+    torch.cuda.synchronize()
+    t_b0 = time.perf_counter()
+    arena = broadcast_arena(model_dir, dev, src=0)  # one RCCL broadcast of the weight arena over xGMI
+    torch.cuda.synchronize()
+    t_b1 = time.perf_counter()
+    warm = torch.empty_like(arena)
+    if rank == 0:
+        warm.copy_(arena)
+    torch.cuda.synchronize(); dist.barrier(); torch.cuda.synchronize()
+    t_b2 = time.perf_counter()
+    dist.broadcast(warm, src=0)       # the same bytes once more, device to device only: the wire time of the broadcast
+    torch.cuda.synchronize()
+    t_b3 = time.perf_counter()
+    same = bool(torch.equal(warm, arena))
+    del warm
+    return arena, {"rccl_ranks_seen": int(ones.item()), "backend": dist.get_backend(), "world_size": dist.get_world_size(),
+                   "arena_bytes": int(arena.numel()), "arena_pack_plus_broadcast_s": round(t_b1 - t_b0, 3),
+                   "arena_broadcast_wire_s": round(t_b3 - t_b2, 4), "arena_broadcast_GBps": round(arena.numel() / max(t_b3 - t_b2, 1e-9) / 1e9, 1),
+                   "second_broadcast_bit_identical": same}
+
+
 def config4_leg(dist, dev, rank, world, local_rank, seconds, new_tokens, steps, warmup, precise):
     """BASELINE configs[4] scaled to this N: Qwen3-ASR-1.7B, 32 clips per GPU, weights packed on rank 0 and shipped with one
     RCCL broadcast of the arena; all ranks time the same window (barrier + max over ranks)."""
@@ -649,6 +686,29 @@ def extra_leg(preset, B, seconds, new_tokens, steps, warmup, precise, do_trace=T
             "setup_s": round(time.time() - t_ck - elapsed, 1)}
 
 
+def headline(args, world, elapsed, stage):
+    """The fields of the line every run prints (a plain run prints nothing else): `elapsed` = the timed steps' seconds (max over
+    ranks), `stage` = the engine's stage timings of the last step."""
+    B = args.batch
+    return {
+        "metric": "audio-seconds/sec (RTFx) Qwen3-ASR-0.6B greedy, 30s clips" if args.preset == "0.6b"
+                  else f"audio-seconds/sec (RTFx) Qwen3-ASR-{args.preset} greedy, 30s clips",
+        "value": round(world * B * args.seconds * args.steps / elapsed, 3),
+        "unit": "audio-seconds/sec",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "bf16" if not args.precise else "bf16x2-split",
+        "data": "synthetic (seeded speech-band noise clips; random-init weights in the reference's safetensors layout)",
+        "config": {"workload": f"Qwen3-ASR-{args.preset} bf16, batch={B} x {args.seconds:.0f}s synthetic 16kHz clip per GPU, "
+                               f"{args.new_tokens} new tokens (fixed, EOS ignored)",
+                   "clips_per_gpu": B, "clip_seconds": args.seconds, "new_tokens": args.new_tokens,
+                   "timed_window": "PCM resident in HBM -> generated ids on the host",
+                   "parallelism": f"dp{world} (independent utterances per GPU, no data-path collective)"},
+        "stage_ms": {k: round(float(v), 3) for k, v in stage.items() if k.endswith("_ms")},
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -659,6 +719,9 @@ def main():
     ap.add_argument("--seconds", type=float, default=30.0)
     ap.add_argument("--new-tokens", type=int, default=100)
     ap.add_argument("--precise", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline (host_to_host, roofline + rocprofv3 child passes, measured_peaks, "
+                         "precise_mode, cpu_baseline, natural_eos, two_streams, extra legs, multi_gpu); the --no-* options trim it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-rocprof", action="store_true", help="skip the rocprofv3 child passes (roofline falls back to the microbenchmark)")
     ap.add_argument("--no-pmc", action="store_true", help="skip the two PMC child passes (roofline.traffic = null)")
@@ -678,6 +741,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.trace_out and not args.full:
+        ap.error("--trace-out needs --full (the kernel trace is a child pass of the full run)")
 
     if args.launch_check:
         return launch_check(args)
@@ -712,37 +777,29 @@ def main():
     if world > 1:
         import torch.distributed as dist  # noqa: F811
         dist.init_process_group("nccl", device_id=dev)  # nccl == RCCL on ROCm
-        model_dir = args.ckpt_dir or f"/tmp/q3a_ckpt_{args.preset.replace('.', 'p')}"
+    model_dir = args.ckpt_dir
+    if model_dir is None and not args.full:
+        # A plain run writes the seeded checkpoint afresh into a directory of its own, so neither its result nor its wall time depends
+        # on an earlier run.  --full keeps the shared /tmp directories, where its rocprofv3 children and extra legs find them.
+        holder = [tempfile.mkdtemp(prefix="q3a_bench_ckpt_") if rank == 0 else None]
+        if dist is not None:
+            dist.broadcast_object_list(holder, src=0)
+        model_dir = holder[0]
+        if rank == 0:
+            atexit.register(shutil.rmtree, model_dir, True)
+    if world > 1:
+        model_dir = model_dir or f"/tmp/q3a_ckpt_{args.preset.replace('.', 'p')}"
         if rank == 0:
             synthetic.write_checkpoint(model_dir, args.preset, seed=0, shards=2 if args.preset == "1.7b" else 1, embed_scale=synthetic.PEAKED_EMBED_SCALE)
         dist.barrier()
-        from qwen3_asr_rs_amd.distributed import broadcast_arena
-        # self-validating N > 1 line: how many ranks RCCL itself saw (a device all-reduce of ones), the time of the
-        # ONE arena broadcast (rank 0 packs on the host first: pack and wire time apart), and below every rank's own elapsed time
-        ones = torch.ones(1, dtype=torch.int32, device=dev)
-        dist.all_reduce(ones, op=dist.ReduceOp.SUM)
-        torch.cuda.synchronize()
-        t_b0 = time.perf_counter()
-        arena = broadcast_arena(model_dir, dev, src=0)  # one RCCL broadcast of the weight arena over xGMI
-        torch.cuda.synchronize()
-        t_b1 = time.perf_counter()
-        warm = torch.empty_like(arena)
-        if rank == 0:
-            warm.copy_(arena)
-        torch.cuda.synchronize(); dist.barrier(); torch.cuda.synchronize()
-        t_b2 = time.perf_counter()
-        dist.broadcast(warm, src=0)       # the same bytes once more, device to device only: the wire time of the broadcast
-        torch.cuda.synchronize()
-        t_b3 = time.perf_counter()
-        same = bool(torch.equal(warm, arena))
-        del warm
-        multi_info = {"rccl_ranks_seen": int(ones.item()), "backend": dist.get_backend(), "world_size": dist.get_world_size(),
-                      "arena_bytes": int(arena.numel()), "arena_pack_plus_broadcast_s": round(t_b1 - t_b0, 3),
-                      "arena_broadcast_wire_s": round(t_b3 - t_b2, 4), "arena_broadcast_GBps": round(arena.numel() / max(t_b3 - t_b2, 1e-9) / 1e9, 1),
-                      "second_broadcast_bit_identical": same}
+        if args.full:
+            arena, multi_info = broadcast_arena_checked(dist, dev, rank, model_dir)
+        else:
+            from qwen3_asr_rs_amd.distributed import broadcast_arena
+            arena = broadcast_arena(model_dir, dev, src=0)  # one RCCL broadcast of the weight arena over xGMI
         model_dir, eng = make_engine(args.preset, model_dir, local_rank, args.precise, args.new_tokens, arena)
     else:
-        model_dir, eng = make_engine(args.preset, args.ckpt_dir, local_rank, args.precise, args.new_tokens)
+        model_dir, eng = make_engine(args.preset, model_dir, local_rank, args.precise, args.new_tokens)
 
     B = args.batch
     clips = [synthetic.synthetic_clip(rank * B + i, args.seconds) for i in range(B)]
@@ -758,24 +815,28 @@ def main():
         dump_outputs(args.dump_outputs, "ids" if world == 1 else f"ids_rank{rank}", last_ids)
     if dist is not None:
         mine = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-        every = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(every, mine)
-        per_rank_s = [float(x.item()) for x in every]
+        if args.full:
+            every = [torch.zeros_like(mine) for _ in range(world)]
+            dist.all_gather(every, mine)
+            per_rank_s = [float(x.item()) for x in every]
+            multi_info["per_rank_value"] = [round(B * args.seconds * args.steps / x, 3) for x in per_rank_s]
+            multi_info["per_rank_ms_per_step"] = [round(x / args.steps * 1e3, 3) for x in per_rank_s]
         t = mine.clone()
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        multi_info["per_rank_value"] = [round(B * args.seconds * args.steps / x, 3) for x in per_rank_s]
-        multi_info["per_rank_ms_per_step"] = [round(x / args.steps * 1e3, 3) for x in per_rank_s]
     stage = eng.timings()
-    h2h, h2h_io = host_to_host(eng, clips, args.steps, args.new_tokens) if rank == 0 else (None, None)
-    gemv_path = B <= 2
-    stream_prof = eng.profile_weight_stream(reps=4) if gemv_path else None  # back-to-back microbenchmark
-    dims = eng.dims
-    P = int(stage["total_prompt_tokens"]) // B
-    ab = algorithmic_bytes(dims, B, P, args.new_tokens)
+    if args.full:
+        h2h, h2h_io = host_to_host(eng, clips, args.steps, args.new_tokens) if rank == 0 else (None, None)
+        gemv_path = B <= 2
+        stream_prof = eng.profile_weight_stream(reps=4) if gemv_path else None  # back-to-back microbenchmark
+        dims = eng.dims
+        P = int(stage["total_prompt_tokens"]) // B
+        ab = algorithmic_bytes(dims, B, P, args.new_tokens)
     eng.close()
+    if rank == 0 and not args.full:
+        print(json.dumps(headline(args, world, elapsed, stage)), flush=True)
     multi_extra = []
-    if dist is not None and not args.no_extra:
+    if args.full and dist is not None and not args.no_extra:
         try:  # every rank takes part (collectives inside)
             multi_extra.append(config4_leg(dist, dev, rank, world, local_rank, args.seconds, args.new_tokens, 2, 1, args.precise))
         except Exception as ex:  # noqa: BLE001
@@ -790,8 +851,7 @@ def main():
                 multi_extra.append(native_group_child(args, world, B))
             dist.barrier(group=cpu_pg)
 
-    if rank == 0:
-        audio_seconds = world * B * args.seconds * args.steps
+    if rank == 0 and args.full:
         dec_us = stage["decode_ms"] * 1e3 / max(int(stage["decode_steps"]), 1)
         peaks = None
         if world == 1 and not args.no_peaks:
@@ -808,25 +868,9 @@ def main():
                               n_trace=3, do_trace=(world == 1 and not args.no_rocprof), do_pmc=not args.no_pmc, trace_out=args.trace_out,
                               measured_read_gbps=(peaks or {}).get("hbm_read_GBps"))
 
-        out = {
-            "metric": "audio-seconds/sec (RTFx) Qwen3-ASR-0.6B greedy, 30s clips" if args.preset == "0.6b"
-                      else f"audio-seconds/sec (RTFx) Qwen3-ASR-{args.preset} greedy, 30s clips",
-            "value": round(audio_seconds / elapsed, 3),
-            "unit": "audio-seconds/sec",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "bf16" if not args.precise else "bf16x2-split",
-            "data": "synthetic (seeded speech-band noise clips; random-init weights in the reference's safetensors layout)",
-            "config": {"workload": f"Qwen3-ASR-{args.preset} bf16, batch={B} x {args.seconds:.0f}s synthetic 16kHz clip per GPU, "
-                                   f"{args.new_tokens} new tokens (fixed, EOS ignored)",
-                       "clips_per_gpu": B, "clip_seconds": args.seconds, "new_tokens": args.new_tokens,
-                       "timed_window": "PCM resident in HBM -> generated ids on the host",
-                       "parallelism": f"dp{world} (independent utterances per GPU, no data-path collective)"},
-            "stage_ms": {k: round(float(v), 3) for k, v in stage.items() if k.endswith("_ms")},
-            "host_to_host": h2h_record(B, args.seconds, args.steps, h2h, h2h_io, elapsed / args.steps * 1e3),
-            "roofline": roof,
-        }
+        out = headline(args, world, elapsed, stage)
+        out["host_to_host"] = h2h_record(B, args.seconds, args.steps, h2h, h2h_io, elapsed / args.steps * 1e3)
+        out["roofline"] = roof
         # SURVEY 8d's window (host PCM -> ids on the host) beside the contract's `value` (PCM resident in HBM when the clock starts -- the
         # task contract forbids the PCIe-inclusive rate as `value`): same engine, same steps, rank 0
         out["value_host_to_host"] = out["host_to_host"]["value"]

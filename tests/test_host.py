@@ -365,6 +365,77 @@ def test_bench_refuses_fewer_than_one_timed_step():
     assert r.returncode == 2 and "--steps must be at least 1" in r.stderr, r.stderr[-2000:]
 
 
+def test_bench_plain_run_does_only_the_headline_and_full_does_the_rest(monkeypatch, capsys):
+    """A plain run builds its engine on a checkpoint directory of its own (fresh, removed at exit), runs the warm-up and timed steps
+    and prints the headline fields alone; every other leg runs only with --full, which keeps the shared checkpoint directories.
+    --trace-out without --full is refused.  No GPU: a stand-in engine, every leg replaced by a recorder."""
+    import sys
+    import types
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Eng:
+        dims = types.SimpleNamespace(hidden_size=8, intermediate_size=16, vocab_size=32, num_q_heads=2, num_kv_heads=1, head_dim=4, dec_layers=2)
+
+        def upload_pcm(self, clips):
+            self.n = len(clips)
+
+        def run_resident(self, *a):
+            pass
+
+        def fetch_ids(self, n):
+            return [[7] * n for _ in range(self.n)]
+
+        def timings(self):
+            return {"decode_ms": 1.0, "decode_steps": 3, "total_prompt_tokens": 10, "total_ms": 2.0}
+
+        def profile_weight_stream(self, reps):
+            calls.append("profile_weight_stream")
+            return None
+
+        def close(self):
+            pass
+
+    made, calls, at_exit = [], [], []
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setattr(bench.torch.cuda, "is_available", lambda: True)
+    monkeypatch.setattr(bench.torch.cuda, "device_count", lambda: 1)
+    monkeypatch.setattr(bench.torch.cuda, "set_device", lambda d: None)
+    monkeypatch.setattr(bench.torch.cuda, "synchronize", lambda: None)
+    monkeypatch.setattr(bench.atexit, "register", lambda f, *a: at_exit.append((f, a)))
+    monkeypatch.setattr(bench, "make_engine", lambda preset, ckpt_dir, *a, **k: (made.append(ckpt_dir), (ckpt_dir, Eng()))[1])
+    stubs = {"host_to_host": (1.0, {}), "roofline_block": {}, "cpu_baseline": {}, "natural_eos_leg": {}, "two_streams_leg": {}, "extra_leg": {}}
+    for name, ret in stubs.items():
+        monkeypatch.setattr(bench, name, lambda *a, _n=name, _r=ret, **k: (calls.append(_n), _r)[1])
+    headline = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                "dtype", "data", "config", "stage_ms"}
+    common = ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--seconds", "1"]
+
+    monkeypatch.setattr(sys, "argv", common)
+    bench.main()
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert set(line) == headline and line["steps"] == 2 and line["warmup"] == 1 and calls == []
+    assert len(made) == 1 and os.path.isdir(made[0]) and not os.listdir(made[0]) and made[0] != "/tmp/q3a_ckpt_0p6b"
+    assert len(at_exit) == 1 and at_exit[0][1][0] == made[0]
+    at_exit[0][0](*at_exit[0][1])
+    assert not os.path.exists(made[0])
+
+    made.clear()
+    monkeypatch.setattr(sys, "argv", common + ["--full", "--no-peaks"])
+    bench.main()
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert headline < set(line) and {"host_to_host", "roofline", "value_host_to_host", "precise_mode", "cpu_baseline", "natural_eos",
+                                     "two_streams", "extra"} <= set(line)
+    assert sorted(set(calls)) == sorted(set(stubs) | {"profile_weight_stream"}) and calls.count("extra_leg") == 2
+    assert made == [None, None] and len(at_exit) == 1  # the headline's and the precise-mode engine: the shared directories, as before
+
+    monkeypatch.setattr(sys, "argv", common + ["--trace-out", "t.txt"])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2 and "--trace-out needs --full" in capsys.readouterr().err
+
+
 def _cpp_function_body(src: str, signature_start: str) -> str:
     """Text of the brace-balanced body that follows `signature_start` in a C++ source."""
     i = src.index(signature_start)

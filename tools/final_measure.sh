@@ -1,6 +1,6 @@
 #!/bin/bash
 # The measurement set committed under profiles/ at the end of a round (run on the GPU box): bash tools/final_measure.sh rN
-# Round 6: the default bench line now carries every leg (configs[1..3] with their own in-situ roofline + PMC traffic, measured
+# Round 6: the --full bench line carries every leg (configs[1..3] with their own in-situ roofline + PMC traffic, measured
 # peaks, precise mode, natural EOS, two engines), so the separate batch-32 / 1.7B bench runs of round 5 are gone; their traces
 # come out of the same run (--trace-out FILE -> FILE, FILE.0p6b_b32, FILE.1p7b_b16).
 r=${1:-r6}; out=gpurun_out/final_$r; mkdir -p $out; R=$PWD
@@ -9,7 +9,7 @@ step() { echo "=== $1 ($(date +%T))" | tee -a $out/steps.log; }
 step gputest
 timeout 1500 python -m pytest tests -m gpu -q -s 2>&1 | tail -120 > $out/${r}_gputest_final.log; tail -3 $out/${r}_gputest_final.log
 step bench
-timeout 900 python bench.py --steps 20 --warmup 5 --trace-out $out/${r}_kernel_trace_b1.txt > $out/${r}_bench_final.json 2> $out/bench.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 --trace-out $out/${r}_kernel_trace_b1.txt > $out/${r}_bench_final.json 2> $out/bench.err
 mv $out/${r}_kernel_trace_b1.txt.0p6b_b32 $out/${r}_kernel_trace_b32.txt 2>/dev/null
 mv $out/${r}_kernel_trace_b1.txt.1p7b_b16 $out/${r}_kernel_trace_1p7b_b16.txt 2>/dev/null
 step bench_1p7b_b32
