@@ -281,6 +281,45 @@ int32_t q3a_parse_asr_output(const char* raw, int32_t language_forced, char* lan
                              int32_t text_cap);
 int32_t q3a_capitalize_first(const char* s, char* out, int32_t cap);
 
+/* ---- forced aligner (Qwen3-ForcedAligner: word timestamps) ------------------------------------------------------------------
+ * An aligner checkpoint is the ASR network with a classifier head over classify_num time classes (timestamp_segment_time ms
+ * each) in place of the vocabulary lm_head; config.json: thinker_config.classify_num, timestamp_token_id and
+ * timestamp_segment_time at the top level or in thinker_config (defaults 151705 / 80 ms).  Its input is the audio followed by
+ * the transcript's words, each followed by two <timestamp> markers; one prefill, no decode: the argmax class at a marker row
+ * times timestamp_segment_time is the start (first marker) or end (second) of the word.  An aligner engine refuses
+ * q3a_prefill, q3a_decode_step, q3a_run_resident, q3a_transcribe_batch* and q3a_group_create; an ASR engine refuses q3a_align*. */
+
+/* classify_num (0 for an ASR engine), timestamp_token_id and ms per class (0 for an ASR engine). */
+int32_t q3a_aligner_info(const q3a_engine* e, int32_t* classify_num, int32_t* timestamp_token_id, float* segment_ms);
+/* The aligner prompt: <|audio_start|> <|audio_pad|> x num_audio_tokens <|audio_end|> text_ids, where text_ids is the word and
+ * marker part (q3a_align_text_ids).  `ids` may be NULL to query the length (*len = num_audio_tokens + 2 + n_text). */
+int32_t q3a_build_align_prompt(int32_t num_audio_tokens, const int32_t* text_ids, int32_t n_text, int32_t* ids, int32_t* len);
+/* Stage form, after q3a_mel + q3a_encode of the same B utterances: one prefill of the B prompts ids / lens (concatenated),
+ * then the head at every id equal to timestamp_token_id.  out_classes host [B][stride] (utterance b's markers in prompt order),
+ * out_counts [B] markers per utterance (0 for an empty transcript); fails when a count exceeds stride.  logits_out (nullable):
+ * host fp32 [sum of out_counts][classify_num], the markers of all utterances in order. */
+int32_t q3a_align(q3a_engine* e, const int32_t* ids, const int32_t* lens, int32_t B, int32_t* out_classes, int32_t stride,
+                  int32_t* out_counts, float* logits_out);
+/* Whole path, host PCM in (as q3a_transcribe_batch_ptrs): text_ids = the word and marker parts of the B utterances
+ * concatenated, text_lens [B]; the prompts are built with q3a_build_align_prompt.  Outputs as q3a_align.  q3a_stage_timings
+ * reports mel, encoder and prefill (the head included) with decode_steps = 0. */
+int32_t q3a_align_batch_ptrs(q3a_engine* e, const float* const* pcm16k, const int64_t* n_samples, int32_t B, const int32_t* text_ids,
+                             const int32_t* text_lens, int32_t* out_classes, int32_t stride, int32_t* out_counts);
+/* Host helpers (no engine).  Words of a transcript as the original aligner splits them for languages other than Japanese and
+ * Korean: every CJK ideograph is a word of its own, whitespace separates words, and only letters, numbers, apostrophes and CJK
+ * ideographs are kept.  language (nullable): "japanese" / "ja" and "korean" / "ko" need morphological analysers and are
+ * refused.  out: the words joined by '\n' and NUL-terminated; *n_words; *len = bytes needed (excluding NUL). */
+int32_t q3a_split_words_for_alignment(const char* utf8, const char* language, char* out, int32_t cap, int32_t* n_words,
+                                      int32_t* len);
+/* The word and marker part of the prompt: for each of the n_words words (UTF-8) encode(word) then two timestamp_token_id.
+ * *n = ids needed; at most cap are written. */
+int32_t q3a_align_text_ids(const q3a_tokenizer* t, const char* const* words, int32_t n_words, int32_t timestamp_token_id,
+                           int32_t* ids, int32_t cap, int32_t* n);
+/* Monotone word times from raw marker times (ms): the longest non-decreasing subsequence is kept, runs of at most 2 other
+ * values snap to the nearer kept neighbour (the left one on a tie), longer runs are interpolated linearly between their kept
+ * neighbours; results are truncated to whole ms.  out may alias ms. */
+int32_t q3a_fix_timestamps(const float* ms, int32_t n, float* out);
+
 /* A/B knobs for kernel experiments (process-wide atomics, read from the environment once; not part of the reference
  * interface).  The knobs that shape the decode step are latched per batch at the next prefill and are part of the captured
  * graph's signature, so changing one on a live engine re-captures instead of replaying a stale graph.  Keys:

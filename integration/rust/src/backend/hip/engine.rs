@@ -13,6 +13,8 @@ use std::path::Path;
 pub struct q3a_engine { _private: [u8; 0] }
 #[repr(C)]
 pub struct q3a_group { _private: [u8; 0] }
+#[repr(C)]
+pub struct q3a_tokenizer { _private: [u8; 0] }
 
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -47,6 +49,18 @@ extern "C" {
                                 n_prefix: i32, max_new: i32, fixed_new_tokens: i32, out_ids: *mut i32, stride: i32, out_lens: *mut i32) -> i32;
     pub fn q3a_group_transcribe_ptrs(g: *mut q3a_group, pcm16k: *const *const f32, n_samples: *const i64, b: i32, lang_prefix_ids: *const i32,
                                      n_prefix: i32, max_new: i32, fixed_new_tokens: i32, out_ids: *mut i32, stride: i32, out_lens: *mut i32) -> i32;
+    // forced aligner (word timestamps; include/q3asr.h "forced aligner")
+    pub fn q3a_aligner_info(e: *const q3a_engine, classify_num: *mut i32, timestamp_token_id: *mut i32, segment_ms: *mut f32) -> i32;
+    pub fn q3a_build_align_prompt(num_audio_tokens: i32, text_ids: *const i32, n_text: i32, ids: *mut i32, len: *mut i32) -> i32;
+    pub fn q3a_align(e: *mut q3a_engine, ids: *const i32, lens: *const i32, b: i32, out_classes: *mut i32, stride: i32,
+                     out_counts: *mut i32, logits_out: *mut f32) -> i32;
+    pub fn q3a_align_batch_ptrs(e: *mut q3a_engine, pcm16k: *const *const f32, n_samples: *const i64, b: i32, text_ids: *const i32,
+                                text_lens: *const i32, out_classes: *mut i32, stride: i32, out_counts: *mut i32) -> i32;
+    pub fn q3a_split_words_for_alignment(utf8: *const c_char, language: *const c_char, out: *mut c_char, cap: i32, n_words: *mut i32,
+                                         len: *mut i32) -> i32;
+    pub fn q3a_align_text_ids(t: *const q3a_tokenizer, words: *const *const c_char, n_words: i32, timestamp_token_id: i32, ids: *mut i32,
+                              cap: i32, n: *mut i32) -> i32;
+    pub fn q3a_fix_timestamps(ms: *const f32, n: i32, out: *mut f32) -> i32;
 }
 
 /// src/main.rs:51-65 for the `hip` feature: HIP devices visible to this process (0: none -- there is no CPU path).

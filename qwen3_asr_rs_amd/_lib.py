@@ -20,6 +20,8 @@ SYMBOLS = [
     "q3a_tokenizer_decode", "q3a_tokenizer_encode", "q3a_normalize_nfc", "q3a_parse_asr_output", "q3a_capitalize_first",
     "q3a_group_create", "q3a_group_destroy", "q3a_group_size", "q3a_group_used_rccl", "q3a_group_last_error",
     "q3a_group_engine", "q3a_group_partition", "q3a_group_transcribe", "q3a_group_transcribe_ptrs", "q3a_group_startup_seconds",
+    "q3a_aligner_info", "q3a_build_align_prompt", "q3a_align", "q3a_align_batch_ptrs", "q3a_split_words_for_alignment",
+    "q3a_align_text_ids", "q3a_fix_timestamps",
 ]
 
 
@@ -129,6 +131,13 @@ def load() -> C.CDLL:
         "q3a_group_partition": (None, [i32, i32, i32, i32p, i32p]),
         "q3a_group_transcribe": (i32, [P, f32p, i64p, i32, i32p, i32, i32, i32, i32p, i32, i32p]),
         "q3a_group_transcribe_ptrs": (i32, [P, C.POINTER(P), i64p, i32, i32p, i32, i32, i32, i32p, i32, i32p]),
+        "q3a_aligner_info": (i32, [P, i32p, i32p, f32p]),
+        "q3a_build_align_prompt": (i32, [i32, i32p, i32, i32p, i32p]),
+        "q3a_align": (i32, [P, i32p, i32p, i32, i32p, i32, i32p, f32p]),
+        "q3a_align_batch_ptrs": (i32, [P, C.POINTER(P), i64p, i32, i32p, i32p, i32p, i32, i32p]),
+        "q3a_split_words_for_alignment": (i32, [C.c_char_p, C.c_char_p, C.c_char_p, i32, i32p, i32p]),
+        "q3a_align_text_ids": (i32, [P, C.POINTER(C.c_char_p), i32, i32, i32p, i32, i32p]),
+        "q3a_fix_timestamps": (i32, [f32p, i32, f32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -75,6 +75,18 @@ class AsrTokenizer:
             raise RuntimeError(_err())
         return ids[:n.value].tolist()
 
+    def align_text_ids(self, words: Sequence[str], timestamp_token_id: int) -> List[int]:
+        """The word and marker part of a forced-aligner prompt: encode(word) + two markers per word (q3a_align_text_ids)."""
+        arr = (C.c_char_p * max(len(words), 1))(*[w.encode("utf-8") for w in words])
+        n = C.c_int32()
+        if self._lib.q3a_align_text_ids(self._h, arr, len(words), int(timestamp_token_id), None, 0, C.byref(n)) != 0:
+            raise RuntimeError(_err())
+        ids = np.zeros(max(n.value, 1), dtype=np.int32)
+        if self._lib.q3a_align_text_ids(self._h, arr, len(words), int(timestamp_token_id), ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                        len(ids), C.byref(n)) != 0:
+            raise RuntimeError(_err())
+        return ids[:n.value].tolist()
+
     def __del__(self):
         try:
             if self._h.value:
@@ -110,3 +122,40 @@ def normalize_nfc(s: str) -> str:
     if lib.q3a_normalize_nfc(raw, out, len(out), C.byref(n)) != 0:
         raise RuntimeError(_err())
     return out.raw[:n.value].decode("utf-8")
+
+
+def split_words_for_alignment(text: str, language: Optional[str] = None) -> List[str]:
+    """Words of a transcript as the forced aligner splits them (csrc/host_align.cpp; Japanese / Korean are refused)."""
+    lib = _lib.load()
+    raw = text.encode("utf-8")
+    n_words, n = C.c_int32(), C.c_int32()
+    lang = language.encode("utf-8") if language else None
+    out = C.create_string_buffer(len(raw) * 2 + 16)
+    if lib.q3a_split_words_for_alignment(raw, lang, out, len(out), C.byref(n_words), C.byref(n)) != 0:
+        raise RuntimeError(_err())
+    s = out.raw[:n.value].decode("utf-8")
+    return s.split("\n") if n_words.value else []
+
+
+def fix_timestamps(ms: Sequence[float]) -> List[int]:
+    """Monotone marker times in ms (csrc/host_align.cpp q3a_fix_timestamps: LIS, snapping, interpolation)."""
+    lib = _lib.load()
+    a = np.ascontiguousarray(np.asarray(ms, dtype=np.float32))
+    out = np.zeros(max(len(a), 1), dtype=np.float32)
+    fp = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+    if lib.q3a_fix_timestamps(fp(a), len(a), fp(out)) != 0:
+        raise RuntimeError(_err())
+    return [int(v) for v in out[:len(a)]]
+
+
+def build_align_prompt(num_audio_tokens: int, text_ids: Sequence[int]) -> List[int]:
+    """The forced aligner's prompt (q3a_build_align_prompt): audio start, pads, audio end, then the word and marker ids."""
+    lib = _lib.load()
+    t = np.ascontiguousarray(np.asarray(list(text_ids), dtype=np.int32))
+    tp = t.ctypes.data_as(C.POINTER(C.c_int32)) if len(t) else None
+    n = C.c_int32()
+    if lib.q3a_build_align_prompt(int(num_audio_tokens), tp, len(t), None, C.byref(n)) != 0:
+        raise RuntimeError(_err())
+    ids = np.zeros(n.value, dtype=np.int32)
+    lib.q3a_build_align_prompt(int(num_audio_tokens), tp, len(t), ids.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n))
+    return ids.tolist()

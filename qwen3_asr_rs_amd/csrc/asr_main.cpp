@@ -4,6 +4,8 @@
 // (src/inference.rs:31-103,203-205).  Input: WAV files (the FFmpeg path of src/audio.rs is out of scope).
 // Q3A_TOKEN_LOGPROBS=1 adds one stdout line after "Text:": "Confidence: avg_logprob <mean token log-probability>
 // min_token_prob <smallest token probability>" (q3a_fetch_logprobs); without it stdout and stderr are unchanged.
+// Q3A_ALIGNER=<forced-aligner model dir> aligns the transcript just produced to the audio (q3a_align_batch_ptrs) and adds one stdout
+// line per word after those: "Word: <start s> <end s> <word>"; without it nothing is printed and no aligner is loaded.
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -25,6 +27,64 @@ static void logf(int level, const char* fmt, const std::string& a = "") {
 }
 static bool exists(const char* p) { struct stat st; return stat(p, &st) == 0; }
 static int die(const std::string& msg) { fprintf(stderr, "Error: %s\n", msg.c_str()); return 1; }
+
+// Q3A_ALIGNER: word times of `text` in the audio (the forced aligner's word split, prompt, head and monotonicity fix-up)
+static int print_word_times(const char* aligner_dir, const float* pcm, int64_t n, const char* text, const char* language) {
+  int32_t nw = 0, need = 0;
+  if (q3a_split_words_for_alignment(text, language, nullptr, 0, &nw, &need) != 0)
+    return die(std::string("Alignment failed: ") + q3a_last_error(nullptr));
+  std::string joined((size_t)need + 1, '\0');
+  q3a_split_words_for_alignment(text, language, &joined[0], need + 1, &nw, &need);
+  joined.resize((size_t)need);
+  std::vector<std::string> words;
+  for (size_t b = 0; nw > 0 && b <= joined.size();) {
+    size_t e = joined.find('\n', b);
+    if (e == std::string::npos) e = joined.size();
+    words.push_back(joined.substr(b, e - b));
+    b = e + 1;
+  }
+  logf(1, "Loading forced aligner from \"%s\"", aligner_dir);
+  q3a_opts opts;
+  q3a_opts_default(&opts);
+  q3a_engine* al = nullptr;
+  if (q3a_engine_create(aligner_dir, 0, &opts, &al) != 0) return die(std::string("Failed to load aligner: ") + q3a_last_error(nullptr));
+  q3a_tokenizer* atok = nullptr;
+  const std::string tj = std::string(aligner_dir) + "/tokenizer.json";
+  if (q3a_tokenizer_create(tj.c_str(), &atok) != 0) {
+    std::string m = q3a_last_error(nullptr);
+    q3a_engine_destroy(al);
+    return die("Failed to load aligner tokenizer: " + m);
+  }
+  int32_t classify_num = 0, ts_id = 0;
+  float seg_ms = 0.f;
+  q3a_aligner_info(al, &classify_num, &ts_id, &seg_ms);
+  std::vector<const char*> wp;
+  for (auto& w : words) wp.push_back(w.c_str());
+  int32_t nt = 0;
+  int rc = 0;
+  std::vector<int32_t> tids;
+  std::vector<int32_t> classes((size_t)2 * words.size() + 1);
+  int32_t count = 0;
+  if (q3a_align_text_ids(atok, wp.data(), (int32_t)wp.size(), ts_id, nullptr, 0, &nt) != 0) {
+    rc = die(std::string("Alignment failed: ") + q3a_last_error(nullptr));
+  } else {
+    tids.resize((size_t)nt + 1);
+    q3a_align_text_ids(atok, wp.data(), (int32_t)wp.size(), ts_id, tids.data(), nt, &nt);
+    const float* ptrs[1] = {pcm};
+    if (q3a_align_batch_ptrs(al, ptrs, &n, 1, tids.data(), &nt, classes.data(), (int32_t)classes.size(), &count) != 0)
+      rc = die(std::string("Alignment failed: ") + q3a_last_error(al));
+  }
+  if (rc == 0) {
+    std::vector<float> ms((size_t)count + 1);
+    for (int32_t i = 0; i < count; ++i) ms[i] = (float)classes[i] * seg_ms;
+    q3a_fix_timestamps(ms.data(), count, ms.data());
+    for (size_t w = 0; w < words.size() && 2 * w + 1 < (size_t)count; ++w)
+      printf("Word: %.3f %.3f %s\n", ms[2 * w] / 1000.0, ms[2 * w + 1] / 1000.0, words[w].c_str());
+  }
+  q3a_tokenizer_destroy(atok);
+  q3a_engine_destroy(al);
+  return rc;
+}
 
 int main(int argc, char** argv) {
   if (const char* rl = getenv("RUST_LOG")) {
@@ -95,7 +155,6 @@ int main(int argc, char** argv) {
   if (q3a_transcribe_batch(eng, pcm, &n, 1, prefix.empty() ? nullptr : prefix.data(), (int32_t)prefix.size(), max_new, 0,
                            ids.data(), max_new, &len) != 0)
     return die(std::string("Transcription failed: ") + q3a_last_error(eng));
-  q3a_free(pcm);
   std::vector<float> lps;
   if (want_lp) {
     lps.resize((size_t)max_new);
@@ -130,7 +189,11 @@ int main(int argc, char** argv) {
     const double avg = lps.empty() ? NAN : sum / (double)lps.size();
     printf("Confidence: avg_logprob %.6f min_token_prob %.6f\n", avg, lps.empty() ? NAN : std::exp((double)mn));
   }
+  const char* aligner_dir = getenv("Q3A_ALIGNER");
+  int rc = 0;
+  if (aligner_dir && *aligner_dir) rc = print_word_times(aligner_dir, pcm, n, text.data(), language);
+  q3a_free(pcm);
   q3a_tokenizer_destroy(tok);
   q3a_engine_destroy(eng);
-  return 0;
+  return rc;
 }

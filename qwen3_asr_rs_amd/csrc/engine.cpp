@@ -327,7 +327,7 @@ struct q3a_engine {
   // matrix; not in the precise mode, which never uses it (vocab * 1024 (2048) + vocab * 16 bytes of device memory)
   void init_lm_head_q() {
     const int cols = lm_head_q_cols(d.hidden);
-    if (precise() || cols == 0 || d.hidden % 8 != 0) return;
+    if (precise() || d.aligner() || cols == 0 || d.hidden % 8 != 0) return;  // (an aligner has no vocabulary lm_head)
     lm_q.ensure((size_t)d.vocab * cols);
     lm_qs.ensure((size_t)d.vocab * 16);
     KCHK(launch_lm_head_quantize(wh(L.lm_head), d.vocab, d.hidden, lm_q.as<int8_t>(), lm_qs.as<float>(), stream));
@@ -857,6 +857,20 @@ struct q3a_engine {
   }
 
   void run_prefill() {
+    run_prefill_layers();
+    const int H = d.hidden;
+    // only the last row of every sequence feeds the lm_head (the reference computes all rows and keeps
+    // the last, text_decoder.rs:111-112 + inference.rs:156)
+    KCHK(launch_gather_rows(dec_x.as<float>(), last_rows.as<int>(), B, H, x_dec.as<float>(), stream));
+    tap("dec_last_hidden", x_dec.p, (size_t)B * H * 4);
+    run_head(0);
+    tap("logits", logits.p, (size_t)B * d.vocab * 4);
+    HIPCHK(hipGetLastError());
+    have_prefill = true;
+  }
+
+  // embedding, audio rows and every decoder layer of the prompts: dec_x holds the last layer's residual stream afterwards
+  void run_prefill_layers() {
     const int H = d.hidden, I = d.inter, QD = d.q_dim(), QKV = d.qkv_dim();
     const bool sp = precise();
     KCHK(launch_embed(ids.as<int>(), total_P, wh(L.embed), H, kAudioPad, dec_x.as<float>(), stream));
@@ -933,15 +947,72 @@ struct q3a_engine {
       ltap("x", dec_x.p, (size_t)total_P * H * 4);
       if (li == 0) tap("dec_layer0", dec_x.p, (size_t)total_P * H * 4);
     }
-    // only the last row of every sequence feeds the lm_head (the reference computes all rows and keeps
-    // the last, text_decoder.rs:111-112 + inference.rs:156)
-    KCHK(launch_gather_rows(dec_x.as<float>(), last_rows.as<int>(), B, H, x_dec.as<float>(), stream));
-    tap("dec_last_hidden", x_dec.p, (size_t)B * H * 4);
-    run_head(0);
-    tap("logits", logits.p, (size_t)B * d.vocab * 4);
-    HIPCHK(hipGetLastError());
-    have_prefill = true;
   }
+
+  // =====================================================================================
+  // forced aligner (Qwen3-ForcedAligner): one prefill of the aligner prompts, then the classifier head at every marker row
+  // (k_align.hip); no vocabulary lm_head, no argmax_finalize, no decode state
+  void require_asr(const char* what) const {
+    if (d.aligner()) fail(std::string(what) + ": this engine holds a forced aligner (classify_num in config.json); use q3a_align*");
+  }
+  void require_aligner(const char* what) const {
+    if (!d.aligner()) fail(std::string(what) + ": not a forced-aligner checkpoint (config.json has no thinker_config.classify_num)");
+  }
+  // marker rows of the prompts (ids_h as setup_prompts takes them) and their count per utterance; refuses a short stride
+  std::vector<int> align_marker_rows(const int32_t* ids_h, const int32_t* lens, int b, int stride, int32_t* counts) const {
+    std::vector<int> rows;
+    int off = 0;
+    for (int s = 0; s < b; ++s) {
+      int n = 0;
+      for (int i = 0; i < lens[s]; ++i)
+        if (ids_h[off + i] == d.timestamp_token_id) { rows.push_back(off + i); ++n; }
+      if (n > stride)
+        fail("q3a_align: utterance " + std::to_string(s) + " has " + std::to_string(n) + " timestamp markers, more than stride " + std::to_string(stride));
+      counts[s] = n;
+      off += lens[s];
+    }
+    return rows;
+  }
+  // prefill layers + head; prompts already set up (setup_prompts).  Events: ev[2] before the prefill (recorded here),
+  // ev[3] after the layers, ev[4] after the head.  Classes (and logits) to the host, [utterance][stride].
+  void run_align(const std::vector<int>& rows, const int32_t* counts, int stride, int32_t* out_classes, float* logits_out) {
+    const int M = (int)rows.size(), N = d.classify_num, H = d.hidden;
+    have_prefill = false;
+    HIPCHK(hipEventRecord(ev[2], stream));
+    run_prefill_layers();
+    HIPCHK(hipEventRecord(ev[3], stream));
+    if (M > 0) {
+      upload(align_rows, rows, stream);
+      const int planes = precise() ? 2 : 1, n_part = align_head_parts(N);
+      align_xn.ensure((size_t)planes * align_rows_padded(M) * H * 2);
+      align_pval.ensure((size_t)M * n_part * 4); align_pidx.ensure((size_t)M * n_part * 4);
+      align_cls.ensure((size_t)M * 4);
+      if (logits_out) align_logits.ensure((size_t)M * N * 4);
+      AlignHeadArgs a{};
+      a.x = dec_x.as<float>(); a.ldx = H; a.rows = align_rows.as<int>(); a.M = M;
+      a.norm_w = wf(L.final_norm); a.eps = d.rms_eps; a.W = wh(L.lm_head); a.N = N; a.K = H;
+      a.planes = planes; a.xn = align_xn.as<uint16_t>();
+      a.part = ArgmaxPartials{align_pval.as<float>(), align_pidx.as<int>(), nullptr, n_part};
+      a.classes = align_cls.as<int>();
+      a.logits = logits_out ? align_logits.as<float>() : nullptr; a.ldl = N;
+      KCHK(launch_align_head(a, stream));
+    }
+    HIPCHK(hipEventRecord(ev[4], stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    std::vector<int> cls((size_t)M);
+    if (M > 0) HIPCHK(hipMemcpy(cls.data(), align_cls.p, (size_t)M * 4, hipMemcpyDeviceToHost));
+    if (M > 0 && logits_out) HIPCHK(hipMemcpy(logits_out, align_logits.p, (size_t)M * N * 4, hipMemcpyDeviceToHost));
+    for (int s = 0, k = 0; s < B; ++s)
+      for (int i = 0; i < counts[s]; ++i) out_classes[(size_t)s * stride + i] = cls[k++];
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, ev[2], ev[4])); timings.prefill_ms = ms;
+    HIPCHK(hipEventElapsedTime(&ms, ev[3], ev[4])); align_head_ms = ms;
+    timings.decode_ms = 0.f; timings.decode_steps = 0; timings.batch = B; timings.total_audio_tokens = total_T;
+    timings.total_prompt_tokens = total_P;
+  }
+  DevBuf align_rows, align_xn, align_pval, align_pidx, align_cls, align_logits;
+  float align_head_ms = 0.f;  // the head's launches of the last align call (q3a_debug_read "align_head_ms")
 
   void scatter_audio_rows();
 
@@ -1334,7 +1405,8 @@ struct q3a_engine {
                       &row_pos, &dec_segs, &last_rows, &dec_x, &dec_ln, &dec_qkv, &dec_ctx, &dec_act, &kcache, &vcache, &x_dec,
                       &d_pos, &next_tok, &out_ids, &step_count, &done, &s_ln, &s_qkv, &s_ctx, &s_act, &logits, &forced_tok, &part_val, &part_idx, &attn_pm, &attn_pl, &attn_po,
                       &part_sum, &out_lp,
-                      &enc_ctx16, &dec_ctx16, &dec_q16, &zero_page, &rope_cur, &nn_x, &nn_ss, &n_done};
+                      &enc_ctx16, &dec_ctx16, &dec_q16, &zero_page, &rope_cur, &nn_x, &nn_ss, &n_done,
+                      &align_rows, &align_xn, &align_pval, &align_pidx, &align_cls, &align_logits};
     for (auto* b : bufs) b->release();
     for (auto& kv : taps) kv.second.release();
     if (own_arena && arena) (void)hipFree(arena);
@@ -1489,6 +1561,67 @@ int32_t q3a_build_prompt(int32_t num_audio_tokens, const int32_t* lang_prefix_id
   return 0;
 }
 
+int32_t q3a_aligner_info(const q3a_engine* e, int32_t* classify_num, int32_t* timestamp_token_id, float* segment_ms) {
+  if (!e) return 1;
+  if (classify_num) *classify_num = e->d.classify_num;
+  if (timestamp_token_id) *timestamp_token_id = e->d.aligner() ? e->d.timestamp_token_id : 0;
+  if (segment_ms) *segment_ms = e->d.aligner() ? e->d.timestamp_segment_ms : 0.f;
+  return 0;
+}
+
+int32_t q3a_align(q3a_engine* e, const int32_t* ids, const int32_t* lens, int32_t B, int32_t* out_classes, int32_t stride,
+                  int32_t* out_counts, float* logits_out) {
+  if (!e) return 1;
+  Q3A_TRY(e)
+  e->require_aligner("q3a_align");
+  if (!ids || !lens || B < 1 || !out_counts || stride < 0 || (stride > 0 && !out_classes)) fail("q3a_align: bad argument");
+  HIPCHK(hipSetDevice(e->device));
+  if (!e->have_enc) fail("q3a_align: no encoder output (call q3a_encode first)");
+  if (B != e->B) fail("q3a_align: batch size differs from the encoded batch");
+  const std::vector<int> rows = e->align_marker_rows(ids, lens, B, stride, out_counts);
+  e->setup_prompts(ids, lens, B, 1);
+  e->timings = q3a_timings{};
+  e->run_align(rows, out_counts, stride, out_classes, logits_out);
+  Q3A_CATCH(e)
+}
+
+int32_t q3a_align_batch_ptrs(q3a_engine* e, const float* const* pcm16k, const int64_t* n_samples, int32_t B, const int32_t* text_ids,
+                             const int32_t* text_lens, int32_t* out_classes, int32_t stride, int32_t* out_counts) {
+  if (!e) return 1;
+  Q3A_TRY(e)
+  e->require_aligner("q3a_align_batch");
+  if (!pcm16k || !n_samples || !text_lens || B < 1 || !out_counts || stride < 0 || (stride > 0 && !out_classes))
+    fail("q3a_align_batch: bad argument");
+  for (int u = 0; u < B; ++u)
+    if (!pcm16k[u]) fail("q3a_align_batch: null utterance pointer");
+  HIPCHK(hipSetDevice(e->device));
+  e->have_prefill = false;
+  e->set_batch(n_samples, B);  // geometry first: the prompts only need the lengths
+  std::vector<int32_t> ids_v, lens(B);
+  int64_t toff = 0;
+  for (int s = 0; s < B; ++s) {
+    if (text_lens[s] < 0 || (text_lens[s] > 0 && !text_ids)) fail("q3a_align_batch: bad text");
+    int32_t len = 0;
+    q3a_build_align_prompt(e->T[s], text_ids ? text_ids + toff : nullptr, text_lens[s], nullptr, &len);
+    const size_t o = ids_v.size();
+    ids_v.resize(o + len);
+    q3a_build_align_prompt(e->T[s], text_ids ? text_ids + toff : nullptr, text_lens[s], ids_v.data() + o, &len);
+    lens[s] = len;
+    toff += text_lens[s];
+  }
+  const std::vector<int> rows = e->align_marker_rows(ids_v.data(), lens.data(), B, stride, out_counts);
+  e->setup_prompts(ids_v.data(), lens.data(), B, 1, true);
+  e->timings = q3a_timings{};
+  e->upload_ptrs_and_mel(pcm16k, n_samples, B);
+  e->run_encoder();
+  e->run_align(rows, out_counts, stride, out_classes, nullptr);
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, e->ev[0], e->ev[1])); e->timings.mel_ms = ms;
+  HIPCHK(hipEventElapsedTime(&ms, e->ev[1], e->ev[2])); e->timings.encoder_ms = ms;
+  HIPCHK(hipEventElapsedTime(&ms, e->ev[0], e->ev[4])); e->timings.total_ms = ms;
+  Q3A_CATCH(e)
+}
+
 int32_t q3a_upload_pcm(q3a_engine* e, const float* pcm16k, const int64_t* n_samples, int32_t B) {
   if (!e) return 1;
   Q3A_TRY(e)
@@ -1534,6 +1667,7 @@ int32_t q3a_prefill(q3a_engine* e, const int32_t* ids, const int32_t* lens, int3
                     int32_t* next_ids) {
   if (!e) return 1;
   Q3A_TRY(e)
+  e->require_asr("q3a_prefill");
   HIPCHK(hipSetDevice(e->device));
   e->fixed_mode_ = false;
   e->head_logits_ = true;
@@ -1549,6 +1683,7 @@ int32_t q3a_prefill(q3a_engine* e, const int32_t* ids, const int32_t* lens, int3
 int32_t q3a_decode_step(q3a_engine* e, int32_t* next_ids, uint8_t* done, float* logits_out) {
   if (!e) return 1;
   Q3A_TRY(e)
+  e->require_asr("q3a_decode_step");
   HIPCHK(hipSetDevice(e->device));
   {
     // capacity guard: position of the token being fed must stay inside the cache
@@ -1585,6 +1720,7 @@ int32_t q3a_run_resident(q3a_engine* e, const int32_t* lang_prefix_ids, int32_t 
                          int32_t fixed_new_tokens) {
   if (!e) return 1;
   Q3A_TRY(e)
+  e->require_asr("q3a_run_resident");
   HIPCHK(hipSetDevice(e->device));
   e->fixed_mode_ = fixed_new_tokens > 0;
   e->head_logits_ = e->opts.debug_taps != 0;
@@ -1616,6 +1752,7 @@ int32_t q3a_transcribe_batch_ptrs(q3a_engine* e, const float* const* pcm16k, con
                                   int32_t* out_ids, int32_t stride, int32_t* out_lens) {
   if (!e) return 1;
   Q3A_TRY(e)
+  e->require_asr("q3a_transcribe_batch");
   if (!pcm16k || !n_samples || B < 1) fail("q3a_transcribe_batch: bad argument");
   for (int u = 0; u < B; ++u)
     if (!pcm16k[u]) fail("q3a_transcribe_batch: null utterance pointer");
@@ -1642,6 +1779,10 @@ int32_t q3a_transcribe_batch(q3a_engine* e, const float* pcm16k, const int64_t* 
                              const int32_t* lang_prefix_ids, int32_t n_prefix, int32_t max_new, int32_t fixed_new_tokens,
                              int32_t* out_ids, int32_t stride, int32_t* out_lens) {
   if (!e) return 1;
+  if (e->d.aligner()) {
+    e->err = g_last_error = "q3a_transcribe_batch: this engine holds a forced aligner (classify_num in config.json); use q3a_align*";
+    return 1;
+  }
   if (!pcm16k || !n_samples || B < 1) { e->err = "q3a_transcribe_batch: bad argument"; return 1; }
   std::vector<const float*> ptrs((size_t)B);
   int64_t off = 0;
@@ -1766,6 +1907,14 @@ int32_t q3a_debug_read(q3a_engine* e, const char* name, void* dst, uint64_t byte
       if (bytes < 8) fail("q3a_debug_read: destination too small");
       HIPCHK(hipStreamSynchronize(e->stream));
       HIPCHK(hipMemcpy(dst, e->prune_stats.p, 8, hipMemcpyDeviceToHost));
+    }
+    return 0;
+  }
+  if (strcmp(name, "align_head_ms") == 0) {  // float: the aligner head's launches (norm, classifier, merge) of the last align call
+    if (actual) *actual = 4;
+    if (dst) {
+      if (bytes < 4) fail("q3a_debug_read: destination too small");
+      memcpy(dst, &e->align_head_ms, 4);
     }
     return 0;
   }

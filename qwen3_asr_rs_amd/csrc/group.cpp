@@ -115,6 +115,8 @@ int32_t q3a_group_create(const char* model_dir, int32_t n_gpus, const int32_t* d
         if (j == dv) fail("q3a_group_create: a GPU may appear only once in a group");
       g->devices.push_back(dv);
     }
+    if (parse_config_file(std::string(model_dir) + "/config.json").aligner())
+      fail("q3a_group_create: a forced-aligner checkpoint cannot serve a transcription group (use one aligner engine per GPU and q3a_align*)");
     uint64_t bytes = 0;
     if (q3a_arena_bytes(model_dir, &bytes) != 0) fail(q3a_last_error(nullptr));
     g->arena_bytes = bytes;

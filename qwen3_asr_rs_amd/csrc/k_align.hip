@@ -1,0 +1,192 @@
+// Forced-aligner head (kernels.h AlignHeadArgs): at the marker rows of the aligner prompt, the final RMSNorm, the classifier
+// [classify_num][hidden] and the argmax over the time classes.  Three launches:
+//   1. align_norm_kernel: one wave per marker row gathers the row from the residual stream, applies the final RMSNorm in fp32
+//      (k_norm.hip's arithmetic) and writes bf16 operand planes: plane 0 = bf16(y); in the precise mode plane 1 = bf16(y - plane 0),
+//      the hi + lo split of k_gemm.hip.  Rows M .. padded(M) are written as zeros, so the GEMM reads whole 64-row tiles.
+//   2. align_head_kernel: 64 x 128 output tiles, 4 waves as 2 (rows) x 2 (columns) of 32 x 64, mfma_f32_16x16x32_bf16 over
+//      64-deep K tiles staged in LDS (registers prefetch tile k + 1 while tile k is multiplied).  Every plane accumulates into the
+//      same fp32 accumulators.  Epilogue: one argmax partial per row and 64-column strip (col = 2 * tile + wave column), the logits
+//      only when asked for.
+//   3. align_merge_kernel: one thread per row merges its partials in column order -> class.
+// The tie rule (larger value, then smaller index) is argmax.h ArgmaxAcc's.
+#include "argmax.h"
+#include "dev.h"
+#include "kernels.h"
+
+namespace q3a {
+namespace {
+
+constexpr int BM = 64, BN = 128, BK = 64, LDSK = BK + 8;  // LDS rows padded by 16 B against bank conflicts of the fragment reads
+
+__global__ __launch_bounds__(256) void align_norm_kernel(const float* __restrict__ x, int ldx, const int* __restrict__ rows, int M,
+                                                         int Mp, const float* __restrict__ w, float eps, int K, int planes,
+                                                         uint16_t* __restrict__ xn) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= Mp) return;
+  const int nv = K / 4;  // float4 per row (K <= 2048: at most 8 per lane)
+  uint16_t* o0 = xn + (size_t)r * K;
+  uint16_t* o1 = xn + ((size_t)Mp + r) * K;
+  if (r >= M) {
+    for (int c = lane; c < nv; c += 64) {
+      *reinterpret_cast<uint2*>(o0 + 4 * c) = make_uint2(0u, 0u);
+      if (planes == 2) *reinterpret_cast<uint2*>(o1 + 4 * c) = make_uint2(0u, 0u);
+    }
+    return;
+  }
+  const float* xr = x + (size_t)rows[r] * ldx;
+  float4 v[8];
+  float sum = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int c = lane + i * 64;
+    v[i] = c < nv ? reinterpret_cast<const float4*>(xr)[c] : make_float4(0.f, 0.f, 0.f, 0.f);
+    sum += v[i].x * v[i].x + v[i].y * v[i].y + v[i].z * v[i].z + v[i].w * v[i].w;
+  }
+  sum = wave_sum(sum);
+  const float rstd = 1.0f / sqrtf(sum / (float)K + eps);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int c = lane + i * 64;
+    if (c >= nv) break;
+    const float4 wv = reinterpret_cast<const float4*>(w)[c];
+    const float y0 = (v[i].x * rstd) * wv.x, y1 = (v[i].y * rstd) * wv.y, y2 = (v[i].z * rstd) * wv.z, y3 = (v[i].w * rstd) * wv.w;
+    const uint2 hi = make_uint2(pack_bf16x2(y0, y1), pack_bf16x2(y2, y3));
+    *reinterpret_cast<uint2*>(o0 + 4 * c) = hi;
+    if (planes == 2) {
+      const uint2 lo = make_uint2(pack_bf16x2(y0 - bf16lo(hi.x), y1 - bf16hi(hi.x)), pack_bf16x2(y2 - bf16lo(hi.y), y3 - bf16hi(hi.y)));
+      *reinterpret_cast<uint2*>(o1 + 4 * c) = lo;
+    }
+  }
+}
+
+template <int NP, bool LOGITS>
+__global__ __launch_bounds__(256) void align_head_kernel(const uint16_t* __restrict__ xn, int Mp, int M, const uint16_t* __restrict__ W,
+                                                         int N, int K, ArgmaxPartials part, float* __restrict__ logits, int ldl) {
+  __shared__ __attribute__((aligned(16))) uint16_t As[NP][BM * LDSK];
+  __shared__ __attribute__((aligned(16))) uint16_t Bs[BN * LDSK];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave >> 1, wn = wave & 1;
+  const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
+  // staging: 16-B chunks, 8 per 64-deep row; A: 2 per thread and plane, B: 4 per thread (rows beyond N read row N - 1).  Chunk
+  // c = t + 256 j sits at row (t >> 3) + 32 j, column 8 (t & 7) of its tile.
+  const int srow = t >> 3, skc = (t & 7) * 8;
+  const uint16_t* ga = xn + (size_t)(m0 + srow) * K + skc;
+  const uint16_t* gb = W + (size_t)min(n0 + srow, N - 1) * K + skc;
+  const size_t ga_plane = (size_t)Mp * K;
+  int gb_row[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) gb_row[j] = min(n0 + srow + 32 * j, N - 1) - min(n0 + srow, N - 1);
+  // (named registers, not arrays: the compiler kept arrays filled inside the k loop in scratch)
+  uint4 ra0, ra1, rl0, rl1, rb0, rb1, rb2, rb3;
+  const size_t a1 = (size_t)32 * K;
+  const size_t b1 = (size_t)gb_row[1] * K, b2 = (size_t)gb_row[2] * K, b3 = (size_t)gb_row[3] * K;
+#define ALIGN_LOAD(k0)                                                                           \
+  do {                                                                                           \
+    ra0 = *reinterpret_cast<const uint4*>(ga + (k0));                                            \
+    ra1 = *reinterpret_cast<const uint4*>(ga + a1 + (k0));                                       \
+    if constexpr (NP == 2) {                                                                     \
+      rl0 = *reinterpret_cast<const uint4*>(ga + ga_plane + (k0));                               \
+      rl1 = *reinterpret_cast<const uint4*>(ga + ga_plane + a1 + (k0));                          \
+    }                                                                                            \
+    rb0 = *reinterpret_cast<const uint4*>(gb + (k0));                                            \
+    rb1 = *reinterpret_cast<const uint4*>(gb + b1 + (k0));                                       \
+    rb2 = *reinterpret_cast<const uint4*>(gb + b2 + (k0));                                       \
+    rb3 = *reinterpret_cast<const uint4*>(gb + b3 + (k0));                                       \
+  } while (0)
+  f32x4_t acc[2][4];
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  const int nk = K / BK;
+  ALIGN_LOAD(0);
+  for (int kt = 0; kt < nk; ++kt) {
+    if (kt > 0) __syncthreads();  // every wave is done with the previous tile
+    *reinterpret_cast<uint4*>(&As[0][srow * LDSK + skc]) = ra0;
+    *reinterpret_cast<uint4*>(&As[0][(srow + 32) * LDSK + skc]) = ra1;
+    if constexpr (NP == 2) {
+      *reinterpret_cast<uint4*>(&As[NP - 1][srow * LDSK + skc]) = rl0;
+      *reinterpret_cast<uint4*>(&As[NP - 1][(srow + 32) * LDSK + skc]) = rl1;
+    }
+    *reinterpret_cast<uint4*>(&Bs[srow * LDSK + skc]) = rb0;
+    *reinterpret_cast<uint4*>(&Bs[(srow + 32) * LDSK + skc]) = rb1;
+    *reinterpret_cast<uint4*>(&Bs[(srow + 64) * LDSK + skc]) = rb2;
+    *reinterpret_cast<uint4*>(&Bs[(srow + 96) * LDSK + skc]) = rb3;
+    __syncthreads();
+    if (kt + 1 < nk) ALIGN_LOAD((kt + 1) * BK);
+#pragma unroll
+    for (int kk = 0; kk < BK / 32; ++kk) {
+      const int kof = kk * 32 + 8 * (lane >> 4);
+      bf16x8_t b[4];
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni)
+        b[ni] = *reinterpret_cast<const bf16x8_t*>(&Bs[(64 * wn + 16 * ni + (lane & 15)) * LDSK + kof]);
+#pragma unroll
+      for (int p = 0; p < NP; ++p)
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi) {
+          const bf16x8_t a = *reinterpret_cast<const bf16x8_t*>(&As[p][(32 * wm + 16 * mi + (lane & 15)) * LDSK + kof]);
+#pragma unroll
+          for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b[ni], acc[mi][ni], 0, 0, 0);
+        }
+    }
+  }
+  // epilogue: lane holds rows 4 (lane >> 4) + r of each 16 x 16 tile, column lane & 15; a lane's columns ascend with ni
+  const int strip = blockIdx.x * 2 + wn;
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int m = m0 + 32 * wm + 16 * mi + 4 * (lane >> 4) + r;
+      ArgmaxAcc<false> best;
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni) {
+        const int n = n0 + 64 * wn + 16 * ni + (lane & 15);
+        const float v = acc[mi][ni][r];
+        if (n < N && v > best.v) { best.v = v; best.i = n; }
+        if (LOGITS && n < N && m < M) logits[(size_t)m * ldl + n] = v;
+      }
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) best.merge_lane(o);
+      if ((lane & 15) == 0 && m < M) best.store(part, m, strip);
+    }
+#undef ALIGN_LOAD
+}
+
+__global__ __launch_bounds__(256) void align_merge_kernel(ArgmaxPartials part, int n_part, int M, int N, int* __restrict__ classes) {
+  const int m = blockIdx.x * 256 + threadIdx.x;
+  if (m >= M) return;
+  ArgmaxAcc<false> best;
+  for (int c = 0; c < n_part; ++c) best.merge(ArgmaxAcc<false>::load(part, m, c));
+  classes[m] = best.i < N ? best.i : 0;  // (no finite logit in the row: class 0)
+}
+
+}  // namespace
+
+int align_rows_padded(int M) { return (M + BM - 1) / BM * BM; }
+int align_head_parts(int N) { return 2 * ((N + BN - 1) / BN); }
+
+const char* launch_align_head(const AlignHeadArgs& a, hipStream_t s) {
+  if (a.M <= 0) return nullptr;
+  if (!a.x || !a.rows || !a.norm_w || !a.W || !a.xn || !a.classes || !a.part.val) return "align head: null argument";
+  if (a.planes != 1 && a.planes != 2) return "align head: planes must be 1 or 2";
+  if (a.K % BK != 0 || a.K > 2048 || a.N <= 0) return "align head: hidden must be a multiple of 64 and at most 2048";
+  if (a.part.sum) return "align head: no log-sum channel";
+  const int n_part = align_head_parts(a.N);
+  if (const char* e = argmax_partials_check(a.part, n_part)) return e;
+  if (a.logits && a.ldl < a.N) return "align head: logits row stride below classify_num";
+  const int Mp = align_rows_padded(a.M);
+  hipLaunchKernelGGL(align_norm_kernel, dim3(Mp / 4), dim3(256), 0, s, a.x, a.ldx, a.rows, a.M, Mp, a.norm_w, a.eps, a.K, a.planes, a.xn);
+  const dim3 grid((a.N + BN - 1) / BN, Mp / BM);
+  if (a.planes == 1) {
+    if (a.logits) hipLaunchKernelGGL((align_head_kernel<1, true>), grid, dim3(256), 0, s, a.xn, Mp, a.M, a.W, a.N, a.K, a.part, a.logits, a.ldl);
+    else hipLaunchKernelGGL((align_head_kernel<1, false>), grid, dim3(256), 0, s, a.xn, Mp, a.M, a.W, a.N, a.K, a.part, a.logits, a.ldl);
+  } else {
+    if (a.logits) hipLaunchKernelGGL((align_head_kernel<2, true>), grid, dim3(256), 0, s, a.xn, Mp, a.M, a.W, a.N, a.K, a.part, a.logits, a.ldl);
+    else hipLaunchKernelGGL((align_head_kernel<2, false>), grid, dim3(256), 0, s, a.xn, Mp, a.M, a.W, a.N, a.K, a.part, a.logits, a.ldl);
+  }
+  hipLaunchKernelGGL(align_merge_kernel, dim3((a.M + 255) / 256), dim3(256), 0, s, a.part, n_part, a.M, a.N, a.classes);
+  return nullptr;
+}
+
+}  // namespace q3a

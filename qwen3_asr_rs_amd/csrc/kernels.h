@@ -39,6 +39,24 @@ inline const char* argmax_partials_check(const ArgmaxPartials& p, int n_part) {
   return nullptr;
 }
 
+// ---- forced-aligner head (k_align.hip) -----------------------------------------------------------------
+// At the M marker rows of an aligner prefill: final RMSNorm, classifier W [N = classify_num][K = hidden] (bf16) and the argmax
+// over the N time classes.  The logits are written only when `logits` is set.
+struct AlignHeadArgs {
+  const float* x; int ldx;        // residual stream after the last decoder layer, fp32 [rows][ldx]
+  const int* rows; int M;         // [M] marker rows of x (device)
+  const float* norm_w; float eps; // final RMSNorm
+  const uint16_t* W; int N; int K;
+  int planes;                     // 1: bf16 operand (default mode); 2: hi + lo bf16 split of the fp32 normed rows (precise mode)
+  uint16_t* xn;                   // workspace [planes][align_rows_padded(M)][K]
+  ArgmaxPartials part;            // [M] rows x align_head_parts(N) partials, no log-sum channel
+  int* classes;                   // [M] argmax (first index on ties)
+  float* logits; int ldl;         // nullable: [M][ldl] fp32
+};
+int align_rows_padded(int M);
+int align_head_parts(int N);
+const char* launch_align_head(const AlignHeadArgs& a, hipStream_t s);
+
 // ---- GEMM (k_gemm.hip) -----------------------------------------------------------------------------
 struct GemmEpilogue {
   float* out = nullptr;          // [rows][ldo] fp32

@@ -32,6 +32,23 @@ static bool file_exists(const std::string& p) {
 // ---------------------------------------------------------------------------------------------------
 // config.json (src/config.rs)
 // ---------------------------------------------------------------------------------------------------
+// The forced aligner's keys, in one place: NOT pinned against a published checkpoint.  An aligner is a
+// checkpoint whose thinker_config has classify_num; timestamp_token_id / timestamp_segment_time may sit at the top level or in
+// thinker_config (HF's defaults otherwise).  Its head is thinker.lm_head.weight [classify_num][hidden] (pack_arena).
+static void parse_aligner_config(const Json& root, const Json& th, Dims& d) {
+  const Json* cn = th.find("classify_num");
+  if (!cn || cn->kind != Json::Num) return;
+  d.classify_num = (int)cn->num;
+  if (d.classify_num <= 0) fail("config.json: classify_num must be positive");
+  auto pick = [&](const char* key, double dflt) {
+    if (const Json* v = root.find(key); v && v->kind == Json::Num) return v->num;
+    if (const Json* v = th.find(key); v && v->kind == Json::Num) return v->num;
+    return dflt;
+  };
+  d.timestamp_token_id = (int)pick("timestamp_token_id", d.timestamp_token_id);
+  d.timestamp_segment_ms = (float)pick("timestamp_segment_time", d.timestamp_segment_ms);
+}
+
 Dims parse_config_file(const std::string& path) {
   Json root = parse_json(read_text(path));
   const Json& th = root.at("thinker_config");
@@ -70,6 +87,7 @@ Dims parse_config_file(const std::string& path) {
       d.mrope_interleaved = rs->bool_or("mrope_interleaved", false) || rs->bool_or("interleaved", false);
     }
   }
+  parse_aligner_config(root, th, d);
   return d;
 }
 
@@ -91,6 +109,11 @@ void validate_dims(const Dims& d) {
   req(d.n_mels == 128, "num_mel_bins must be 128");
   req(d.hidden <= 2048 && d.enc_d <= 2048, "hidden sizes above 2048 need a wider norm kernel");
   req(d.inter <= 16384 && d.q_dim() <= 16384, "decoder width too large for the GEMV staging buffer");
+  if (d.aligner()) {
+    req(!d.tie_embeddings, "an aligner's classifier (thinker.lm_head.weight) cannot be tied to the token embedding");
+    req(d.timestamp_token_id >= 0 && d.timestamp_token_id < d.vocab, "timestamp_token_id must be a vocabulary id");
+    req(d.hidden % 64 == 0, "aligner head: hidden_size must be a multiple of 64");
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -274,7 +297,7 @@ ArenaLayout plan_arena(const Dims& d) {
   L.proj2_w = p.bf16((int64_t)d.enc_out * D); L.proj2_b = p.f32(d.enc_out);
   const int64_t H = d.hidden, I = d.inter, V = d.vocab;
   L.embed = p.bf16(V * H);
-  L.lm_head = d.tie_embeddings ? L.embed : p.bf16(V * H);
+  L.lm_head = d.tie_embeddings ? L.embed : p.bf16((int64_t)d.head_rows() * H);  // (an aligner: the classifier)
   L.dec.resize(d.dec_layers);
   for (auto& l : L.dec) {
     l.in_ln = p.f32(H);
@@ -289,7 +312,7 @@ ArenaLayout plan_arena(const Dims& d) {
   L.total = p.cur;
   // per decode token: every decoder matrix once + lm_head once (bf16)
   double per_layer = 2.0 * ((double)d.qkv_dim() * H + (double)H * d.q_dim() + 2.0 * I * H + (double)H * I);
-  L.decode_weight_bytes = per_layer * d.dec_layers + 2.0 * V * H;
+  L.decode_weight_bytes = per_layer * d.dec_layers + 2.0 * d.head_rows() * H;
   return L;
 }
 
@@ -389,8 +412,15 @@ void pack_arena(const Dims& d, const ArenaLayout& L, const Checkpoint& ck, uint8
   const std::string tm = "thinker.model";  // inference.rs:57
   const int64_t H = d.hidden, I = d.inter, V = d.vocab;
   put_bf16_rows(dst, L.embed, 0, ck.get(tm + ".embed_tokens.weight"), V, H, tm + ".embed_tokens.weight");
-  if (!d.tie_embeddings)  // text_decoder.rs:71-79
+  if (d.aligner()) {  // the classifier of the forced aligner (parse_aligner_config)
+    const TensorView* w = ck.get_opt("thinker.lm_head.weight");
+    if (!w) fail("aligner checkpoint: classifier weight thinker.lm_head.weight not found");
+    if (w->shape.size() != 2 || w->shape[0] != d.classify_num)
+      fail("aligner checkpoint: thinker.lm_head.weight must have classify_num = " + std::to_string(d.classify_num) + " rows");
+    put_bf16_rows(dst, L.lm_head, 0, *w, d.classify_num, H, "thinker.lm_head.weight");
+  } else if (!d.tie_embeddings) {  // text_decoder.rs:71-79
     put_bf16_rows(dst, L.lm_head, 0, ck.get("thinker.lm_head.weight"), V, H, "thinker.lm_head.weight");
+  }
   for (int i = 0; i < d.dec_layers; ++i) {  // layers.rs:271-276,390-392,424-438
     const DecLayerOff& l = L.dec[i];
     std::string p = tm + ".layers." + std::to_string(i);

@@ -24,6 +24,12 @@ struct Dims {
   bool tie_embeddings = true;
   std::vector<int> mrope_section{24, 20, 20};
   bool mrope_interleaved = false;
+  // forced aligner (Qwen3-ForcedAligner): the lm_head is a classifier over classify_num time classes of timestamp_segment_ms
+  // each, applied at the rows whose id is timestamp_token_id.  classify_num = 0: an ASR checkpoint (parse_aligner_config)
+  int classify_num = 0, timestamp_token_id = 151705;
+  float timestamp_segment_ms = 80.f;
+  bool aligner() const { return classify_num > 0; }
+  int head_rows() const { return aligner() ? classify_num : vocab; }  // rows of the arena's lm_head
 
   // derived
   int chunk_frames() const { return n_window * 2; }                       // audio_encoder.rs:83

@@ -238,6 +238,50 @@ class HipEngine:
         self._chk(self._lib.q3a_debug_read(self._h, name.encode(), out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
         return out
 
+    # ---- forced aligner -----------------------------------------------------------------------------
+    def aligner_info(self) -> dict:
+        """classify_num (0: not an aligner), timestamp_token_id and ms per class (q3a_aligner_info)."""
+        n, tid, seg = C.c_int32(), C.c_int32(), C.c_float()
+        self._chk(self._lib.q3a_aligner_info(self._h, C.byref(n), C.byref(tid), C.byref(seg)))
+        return {"classify_num": int(n.value), "timestamp_token_id": int(tid.value), "segment_ms": float(seg.value)}
+
+    def align(self, prompts: Sequence[Sequence[int]], stride: Optional[int] = None, want_logits: bool = False):
+        """Stage form after mel() + encode(): one prefill of the aligner prompts and the classifier head at every marker row.
+        Returns (classes per utterance, logits [markers][classify_num] or None)."""
+        B = len(prompts)
+        lens = np.array([len(p) for p in prompts], dtype=np.int32)
+        ids = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.int32) for p in prompts]))
+        tid = self.aligner_info()["timestamp_token_id"]
+        if stride is None:
+            stride = max(1, max(int(np.sum(np.asarray(p) == tid)) for p in prompts))
+        out = np.zeros((B, max(stride, 1)), dtype=np.int32)
+        counts = np.zeros(B, dtype=np.int32)
+        logits = None
+        if want_logits:
+            total = int(sum(int(np.sum(np.asarray(p) == tid)) for p in prompts))
+            logits = np.zeros((max(total, 1), self.aligner_info()["classify_num"]), dtype=np.float32)
+        self._chk(self._lib.q3a_align(self._h, _i32p(ids), _i32p(lens), B, _i32p(out), stride, _i32p(counts),
+                                      _f32p(logits) if want_logits else None))
+        cls = [out[b, :int(counts[b])].tolist() for b in range(B)]
+        if want_logits:
+            logits = logits[:int(counts.sum())]
+        return cls, logits
+
+    def align_batch(self, clips: Sequence[np.ndarray], text_ids: Sequence[Sequence[int]], stride: Optional[int] = None) -> List[List[int]]:
+        """Whole path (q3a_align_batch_ptrs): host PCM + the word and marker ids of each utterance -> marker classes."""
+        arrs, ptrs, ns = self._ptrs(clips)
+        B = len(arrs)
+        tl = np.array([len(t) for t in text_ids], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(t, dtype=np.int32) for t in text_ids] + [np.zeros(1, np.int32)]))
+        if stride is None:
+            tid = self.aligner_info()["timestamp_token_id"]
+            stride = max(1, max(int(np.sum(np.asarray(t) == tid)) for t in text_ids))
+        out = np.zeros((B, max(stride, 1)), dtype=np.int32)
+        counts = np.zeros(B, dtype=np.int32)
+        self._chk(self._lib.q3a_align_batch_ptrs(self._h, ptrs, _i64p(ns), B, _i32p(flat), _i32p(tl), _i32p(out), stride, _i32p(counts)))
+        self.batch = B
+        return [out[b, :int(counts[b])].tolist() for b in range(B)]
+
     def debug_read_raw(self, name: str) -> np.ndarray:
         """The same as bytes (records of mixed types: tools/soak_engines.py)."""
         n = C.c_uint64()
@@ -351,7 +395,7 @@ def selftest_gemm(M: int, N: int, K: int, split: bool = False, device: int = 0) 
 # ------------------------------------------------------------------------------------------------------
 # Reference-shaped front door
 # ------------------------------------------------------------------------------------------------------
-from .audio import AsrTokenizer, capitalize_first, load_audio, parse_asr_output  # noqa: E402  (C++ host code behind the C ABI)
+from .audio import AsrTokenizer, capitalize_first, fix_timestamps, load_audio, parse_asr_output, split_words_for_alignment  # noqa: E402  (C++ host code behind the C ABI)
 
 
 @dataclass
@@ -404,3 +448,40 @@ class AsrInference:
             res.token_logprobs = [float(v) for v in lp]
             res.avg_logprob = float(np.mean(lp, dtype=np.float64)) if len(lp) else None
         return res
+
+
+class ForcedAligner:
+    """Word timestamps with a Qwen3-ForcedAligner checkpoint (HF Qwen3ASRProcessor.prepare_forced_aligner_inputs +
+    Qwen3ASRForTokenClassification + decode_forced_alignment), every number from the HIP engine."""
+
+    def __init__(self, engine: HipEngine, tokenizer: AsrTokenizer):
+        info = engine.aligner_info()
+        if info["classify_num"] <= 0:
+            raise Q3aError("ForcedAligner: not a forced-aligner checkpoint (config.json has no thinker_config.classify_num)")
+        self.engine, self.tokenizer = engine, tokenizer
+        self.timestamp_token_id, self.segment_ms = info["timestamp_token_id"], info["segment_ms"]
+
+    @classmethod
+    def load(cls, model_dir: str, device: int = 0, precise: bool = False) -> "ForcedAligner":
+        return cls(HipEngine(model_dir, device, precise=precise, max_new_tokens=1), AsrTokenizer.from_dir(model_dir))
+
+    def _text_ids(self, words: Sequence[str]) -> List[int]:
+        return self.tokenizer.align_text_ids(words, self.timestamp_token_id)
+
+    def _decode(self, words: Sequence[str], classes: Sequence[int]) -> List[dict]:
+        ms = fix_timestamps([float(c) * self.segment_ms for c in classes]) if len(classes) else []
+        return [{"text": w, "start_time": round(ms[2 * i] / 1000.0, 3), "end_time": round(ms[2 * i + 1] / 1000.0, 3)}
+                for i, w in enumerate(words)]
+
+    def align_batch(self, clips: Sequence, transcripts: Sequence[str], language: Optional[str] = None) -> List[List[dict]]:
+        """One list of {"text", "start_time", "end_time"} (seconds, rounded to ms) per clip."""
+        if len(clips) != len(transcripts):
+            raise Q3aError(f"ForcedAligner: {len(transcripts)} transcript(s) for {len(clips)} clip(s)")
+        samples = [load_audio(os.fspath(a), 16000) if isinstance(a, (str, os.PathLike)) else np.asarray(a, dtype=np.float32)
+                   for a in clips]
+        words = [split_words_for_alignment(t, language) for t in transcripts]
+        classes = self.engine.align_batch(samples, [self._text_ids(w) for w in words])
+        return [self._decode(w, c) for w, c in zip(words, classes)]
+
+    def align(self, audio, transcript: str, language: Optional[str] = None) -> List[dict]:
+        return self.align_batch([audio], [transcript], language)[0]

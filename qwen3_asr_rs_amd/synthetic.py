@@ -57,7 +57,18 @@ CONFIG_TINY_UNTIED = {
 # ~0.015, so 7-15 % of the greedy steps were undecidable; at 0.04 the gaps are 0.2-0.55 at |logit| <= 6 (measured with the oracle
 # at the 0.6B dimensions), i.e. 10x the rounding noise -- closer to a trained checkpoint's peaked distributions.
 PEAKED_EMBED_SCALE = 0.04
-PRESETS = {"0.6b": CONFIG_0P6B, "1.7b": CONFIG_1P7B, "tiny": CONFIG_TINY, "tiny_untied": CONFIG_TINY_UNTIED}
+# Forced aligners (Qwen3-ForcedAligner): the ASR network with an untied classifier over classify_num time classes of
+# timestamp_segment_time ms in place of the vocabulary lm_head (thinker.lm_head.weight [classify_num][hidden]).  The keys are the
+# engine's unpinned mapping (csrc/model.cpp parse_aligner_config).
+def _aligner(cfg: dict) -> dict:
+    return dict(cfg, text_config=dict(cfg["text_config"], tie_word_embeddings=False), classify_num=5000,
+                timestamp_token_id=151705, timestamp_segment_time=80)
+
+
+CONFIG_TINY_ALIGNER = _aligner(CONFIG_TINY)
+CONFIG_0P6B_ALIGNER = _aligner(CONFIG_0P6B)
+PRESETS = {"0.6b": CONFIG_0P6B, "1.7b": CONFIG_1P7B, "tiny": CONFIG_TINY, "tiny_untied": CONFIG_TINY_UNTIED,
+           "tiny_aligner": CONFIG_TINY_ALIGNER, "0.6b_aligner": CONFIG_0P6B_ALIGNER}
 
 
 def tensor_specs(cfg: dict, embed_scale: float = 0.02) -> List[Tuple[str, Tuple[int, ...], str, float]]:
@@ -100,7 +111,9 @@ def tensor_specs(cfg: dict, embed_scale: float = 0.02) -> List[Tuple[str, Tuple[
               (f"{p}.mlp.up_proj.weight", (inter, h), "w", 1.0 / h ** 0.5),
               (f"{p}.mlp.down_proj.weight", (h, inter), "w", 0.5 / inter ** 0.5)]
     s += [(f"{tm}.norm.weight", (h,), "g", 0.1)]
-    if not t.get("tie_word_embeddings", True):
+    if cfg.get("classify_num"):  # forced aligner: the classifier, rows of log-normal scale ("h", _gen_tensor)
+        s += [("thinker.lm_head.weight", (cfg["classify_num"], h), "h", 1.0 / h ** 0.5)]
+    elif not t.get("tie_word_embeddings", True):
         s += [("thinker.lm_head.weight", (t["vocab_size"], h), "w", 0.02)]
     return s
 
@@ -112,6 +125,9 @@ def _gen_tensor(shape, kind, scale, gen: torch.Generator) -> torch.Tensor:
     v = torch.randn(n, generator=gen, dtype=torch.float32) * scale
     if kind == "g":
         v = v + 1.0
+    if kind == "h":  # classifier rows of log-normal scale: a few classes dominate, as in a trained head, so that the top-1/top-2
+        # margins of the time classes stand well above a bf16 engine's logit error (iid rows: 2-3 % of the argmaxes inside it)
+        v = v.reshape(shape[0], -1) * torch.exp(0.4 * torch.randn(shape[0], 1, generator=gen, dtype=torch.float32))
     return v.reshape(shape).to(torch.bfloat16)
 
 
