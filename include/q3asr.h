@@ -349,6 +349,12 @@ int32_t q3a_fix_timestamps(const float* ms, int32_t n, float* out);
  *                        over the lm_head (approximate logits with a rigorous error bound) and a bf16 rescore of the 16-row blocks
  *                        that can still hold the maximum: the ids are bit-identical to 0, the full bf16 GEMV.  Taken at the next
  *                        batch set-up.
+ *   "layer_taps"         (debug aid) 1: an engine created with debug taps also keeps raw copies of every encoder / decoder
+ *                        prefill layer's intermediate buffers (taps "E%02d_x", "L%02d_ln1" / "_q" (default mode) / "_k" / "_v" /
+ *                        "_attn" / "_o" / "_ln2" / "_act" / "_x"; the environment's Q3A_DEBUG_LAYER_TAPS=1 sets it).  Taken at the
+ *                        next prefill.
+ *   "poison_attn_partials"  (debug aid) 1: every batch set-up fills the decode attention's split statistics and partial outputs
+ *                        with 0xFF bytes (NaN), so that a merge reading an entry no attention launch wrote shows up.
  * Round 6 removed the keys whose A/B is settled, together with the code only they selected (docs/HISTORY.md "Pruned in round 6"):
  * fuse_qkv_attn, dattn_pair_split, fattn_pipe, rope_variant, rope_twice, gemm16_ring, gemm256_resid_prefetch, live_key_splits,
  * skinny_glu_2pass.  An unknown key returns non-zero. */

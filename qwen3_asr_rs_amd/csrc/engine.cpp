@@ -115,6 +115,7 @@ Knobs& knobs() {
     env("Q3A_EOS_RUN_AHEAD", k.eos_run_ahead);
     env("Q3A_SKINNY_GLU_HP3", k.skinny_glu_hp3);
     env("Q3A_LM_HEAD_PRUNE", k.lm_head_prune);
+    env("Q3A_DEBUG_LAYER_TAPS", k.layer_taps);
   });
   return k;
 }
@@ -633,8 +634,7 @@ struct q3a_engine {
         act_gemm(enc_ffn, Fn, wh(e.fc2_w), total_T, D, Fn, ep, false);
       }
       if (li == 0) tap("enc_layer0", enc_x.p, Tt * D * 4);
-      static const bool enc_layer_taps = [] { const char* e = getenv("Q3A_DEBUG_LAYER_TAPS"); return e && atoi(e) != 0; }();
-      if (enc_layer_taps && opts.debug_taps == 1) {  // (tools/bisect_layers.py)
+      if (opts.debug_taps == 1 && knobs().layer_taps.load() != 0) {  // (tools/bisect_layers.py)
         char name[32];
         snprintf(name, sizeof(name), "E%02d_x", li);
         tap(name, enc_x.p, Tt * D * 4);
@@ -743,8 +743,16 @@ struct q3a_engine {
       blk_lo.ensure(nblk4 * 4); blk_hi.ensure(nblk4 * 4);
     }
     attn_nsplit = (max_ctx + dattn_keys_per_split(kv_f32()) - 1) / dattn_keys_per_split(kv_f32());
-    attn_pm.ensure((size_t)b * d.n_q * attn_nsplit * 4); attn_pl.ensure((size_t)b * d.n_q * attn_nsplit * 4);
-    attn_po.ensure((size_t)b * d.n_q * attn_nsplit * 128 * 4);
+    {  // (+8 floats: the merge-first o_proj GEMV reads a head's statistics 16 bytes at a time, up to 7 entries past the last head's)
+      const size_t n_stat = (size_t)b * d.n_q * attn_nsplit;
+      attn_pm.ensure((n_stat + 8) * 4); attn_pl.ensure((n_stat + 8) * 4);
+      attn_po.ensure(n_stat * 128 * 4);
+      if (knobs().poison_attn_partials.load() != 0) {  // (tests) NaN wherever no decode attention launch has written yet
+        HIPCHK(hipMemsetAsync(attn_pm.p, 0xFF, attn_pm.cap, stream));
+        HIPCHK(hipMemsetAsync(attn_pl.p, 0xFF, attn_pl.cap, stream));
+        HIPCHK(hipMemsetAsync(attn_po.p, 0xFF, attn_po.cap, stream));
+      }
+    }
     HIPCHK(hipMemsetAsync(step_count.p, 0, (size_t)b * 4, stream));
     HIPCHK(hipMemsetAsync(done.p, 0, (size_t)b, stream));
     HIPCHK(hipMemsetAsync(n_done.p, 0, 64, stream));
@@ -888,9 +896,20 @@ struct q3a_engine {
     const DevBuf& ctx_in = (valu_attn && !sp) ? dec_ctx16 : dec_ctx;  // what the o projection reads
     const bool qkv_bias = arena_flags & kFlagDecQkvBias, o_bias = arena_flags & kFlagDecOBias, mlp_bias = arena_flags & kFlagDecMlpBias;
     const bool fuse_rope = knobs().fuse_qkrope.load() != 0 && !valu_attn && !precise() && d.head_dim == 128 && gemm256_eligible(total_P, QKV, H) && H % 64 == 0;
+    // (debug_taps + layer_taps: raw copies of every prefill layer's intermediate buffers, for bisecting a run-to-run difference
+    // to one launch -- tools/bisect_layers.py -- and for checking one launch against a reference on its own input)
+    const bool layer_taps = opts.debug_taps && knobs().layer_taps.load() != 0;
+    const size_t act_b = sp ? 4 : 2;  // bytes per activation element (bf16 in the default mode)
     for (int li = 0; li < d.dec_layers; ++li) {
       const DecLayerOff& l = L.dec[li];
+      auto ltap = [&](const char* what, const void* ptr, size_t bytes) {
+        if (!layer_taps) return;
+        char name[32];
+        snprintf(name, sizeof(name), "L%02d_%s", li, what);
+        tap(name, ptr, bytes);
+      };
       KCHK(launch_rmsnorm(dec_x.as<float>(), wf(l.in_ln), dec_ln.as<float>(), total_P, H, d.rms_eps, stream, act16(dec_ln)));
+      ltap("ln1", dec_ln.p, (size_t)total_P * H * act_b);
       RopeKvArgs rk{};
       rk.qkv = dec_qkv.as<float>(); rk.row_seq = row_seq.as<int>(); rk.row_pos = row_pos.as<int>();
       rk.q_norm = wf(l.q_norm); rk.k_norm = wf(l.k_norm); rk.eps = d.rms_eps;
@@ -906,19 +925,10 @@ struct q3a_engine {
         KCHK(launch_qknorm_rope_kv(rk, total_P, kv_f32(), stream));
       }
       at.k = kc_layer(li); at.v = vc_layer(li);
-      // (debug_taps + Q3A_DEBUG_LAYER_TAPS=1: raw copies of every prefill layer's intermediate buffers, for bisecting a
-      // run-to-run difference to one launch -- tools/bisect_layers.py)
-      static const bool layer_taps = [] { const char* e = getenv("Q3A_DEBUG_LAYER_TAPS"); return e && atoi(e) != 0; }();
-      auto ltap = [&](const char* what, const void* ptr, size_t bytes) {
-        if (!layer_taps || !opts.debug_taps) return;
-        char name[32];
-        snprintf(name, sizeof(name), "L%02d_%s", li, what);
-        tap(name, ptr, bytes);
-      };
-      const size_t act_b = sp ? 4 : 2;  // bytes per activation element (bf16 in the default mode)
       if (fuse_rope) {
         ltap("qkvs", dec_qkv.p, std::min((size_t)1024, (size_t)total_P) * QKV * 4);  // fp32 scratch of the trailing rows (small GEMM -> separate rope kernel)
       }
+      if (!valu_attn) ltap("q", dec_q16.p, (size_t)total_P * QD * 2);  // q after QK-norm + RoPE, bf16 [rows][QD]
       ltap("k", kc_layer(li), (size_t)B * d.n_kv * max_ctx * 128 * kv_elem());
       ltap("v", vc_layer(li), (size_t)B * d.n_kv * max_ctx * 128 * kv_elem());
       if (valu_attn) {
@@ -1944,6 +1954,8 @@ int32_t q3a_debug_set(const char* key, int32_t value) {
   if (strcmp(key, "eos_run_ahead") == 0) { kn.eos_run_ahead = value; return 0; }
   if (strcmp(key, "skinny_glu_hp3") == 0) { kn.skinny_glu_hp3 = value; return 0; }
   if (strcmp(key, "lm_head_prune") == 0) { kn.lm_head_prune = value; return 0; }
+  if (strcmp(key, "layer_taps") == 0) { kn.layer_taps = value; return 0; }
+  if (strcmp(key, "poison_attn_partials") == 0) { kn.poison_attn_partials = value; return 0; }
   g_last_error = std::string("q3a_debug_set: unknown key '") + key + "'";
   return 1;
 }

@@ -334,7 +334,8 @@ __global__ __launch_bounds__(256) void gemv1_kernel(GemvArgs a) {
     const int kc = mg_k < K ? mg_k : 0;
     const int h = kc >> 7, d = kc & 127, ns = a.attn_nsplit, base = h * ns;
     // A head's statistics are ns consecutive floats: 16-byte loads (4-byte aligned; entries past the head's own belong to the next
-    // head or to the allocation's 256-byte rounding and are voided) instead of one 4-byte load per split -- and NO branch around
+    // head or to the allocation's padding, hold anything -- NaN included -- and are voided, m AND l: 0 * NaN is NaN) instead of
+    // one 4-byte load per split -- and NO branch around
     // loads: a uniform `if` whose arms load made hipcc wait at the join before requesting anything else (tests/test_isa_hazards.py).
     typedef float __attribute__((ext_vector_type(4), aligned(4))) f4u_t;
 #pragma unroll
@@ -343,7 +344,7 @@ __global__ __launch_bounds__(256) void gemv1_kernel(GemvArgs a) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         mg_m[j + e] = j + e < ns ? m4[e] : -INFINITY;
-        mg_l[j + e] = l4[e];
+        mg_l[j + e] = j + e < ns ? l4[e] : 0.f;
       }
     }
 #pragma unroll

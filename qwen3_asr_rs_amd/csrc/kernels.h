@@ -106,6 +106,9 @@ struct Knobs {
   std::atomic<int> eos_run_ahead{1};            // Q3A_EOS_RUN_AHEAD: decode steps kept enqueued ahead of the device in natural-EOS mode.  1: exactly the steps needed are executed; paired with a fixed-N run of the same engine (profiles/r5_eos_run_ahead_ab.txt, two processes): 1 costs +0.03 / +1.24 ms per 100 tokens, 2 costs +2.07 / +1.86 ms (one wasted step + the same launch latency), 3 +1.3 / +1.2, 4 +3.3 / +3.1
   std::atomic<int> skinny_glu_hp3{1};           // Q3A_SKINNY_GLU_HP3: gate/up skinny GEMM as 3 half-pair tiles per workgroup when the pair form has more workgroups than CUs (k_skinny.hip HP; 0 = off, 2 = whenever the shape allows)
   std::atomic<int> lm_head_prune{1};            // Q3A_LM_HEAD_PRUNE: one-sequence decode argmax from an int8 pre-pass + bf16 rescore of the candidate blocks (k_gemv.hip; bit-identical ids)
+  // debug aids (tests): no effect on what a run computes
+  std::atomic<int> layer_taps{0};               // Q3A_DEBUG_LAYER_TAPS: with debug taps, raw copies of every encoder / decoder prefill layer's intermediate buffers
+  std::atomic<int> poison_attn_partials{0};     // every batch set-up fills the decode attention's split partials (m, l, o) with NaN bytes
   // Round 6 removed nine knobs together with the code only they selected (docs/HISTORY.md "Pruned in round 6"; last present at commit
   // caf7a05): fuse_qkv_attn, dattn_pair_split, fattn_pipe, rope_variant, rope_twice (measured alternatives that lost / finished debug
   // aids), gemm16_ring, gemm256_resid_prefetch, live_key_splits, skinny_glu_2pass (the winning form is now the only form).

@@ -71,8 +71,18 @@ PRESETS = {"0.6b": CONFIG_0P6B, "1.7b": CONFIG_1P7B, "tiny": CONFIG_TINY, "tiny_
            "tiny_aligner": CONFIG_TINY_ALIGNER, "0.6b_aligner": CONFIG_0P6B_ALIGNER}
 
 
-def tensor_specs(cfg: dict, embed_scale: float = 0.02) -> List[Tuple[str, Tuple[int, ...], str, float]]:
-    """(key, shape, kind, scale) for every tensor of the reference key map (W2)."""
+# Decoder projection biases (optional in the reference's Linear::load: src/layers.rs).  "attn": q/k/v/o_proj.bias (what
+# HuggingFace's Qwen3 attention_bias=True adds); "all": also gate/up/down_proj.bias.
+DEC_BIAS_PROJ = {"attn": ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj"),
+                 "all": ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj",
+                         "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj")}
+
+
+def tensor_specs(cfg: dict, embed_scale: float = 0.02, dec_bias: str = "",
+                 dec_bias_std: float = 0.1) -> List[Tuple[str, Tuple[int, ...], str, float]]:
+    """(key, shape, kind, scale) for every tensor of the reference key map (W2).  dec_bias ("attn" / "all", DEC_BIAS_PROJ):
+    decoder projection biases of std dec_bias_std, listed after every other tensor -- so the rest of the checkpoint draws the
+    same numbers as the one without them."""
     a, t = cfg["audio_config"], cfg["text_config"]
     d, ffn, ch, mel = a["d_model"], a["encoder_ffn_dim"], a["downsample_hidden_size"], a["num_mel_bins"]
     f3 = ((((mel - 1) // 2 + 1) - 1) // 2 + 1 - 1) // 2 + 1   # mel bins after three stride-2 convs (16)
@@ -115,6 +125,11 @@ def tensor_specs(cfg: dict, embed_scale: float = 0.02) -> List[Tuple[str, Tuple[
         s += [("thinker.lm_head.weight", (cfg["classify_num"], h), "h", 1.0 / h ** 0.5)]
     elif not t.get("tie_word_embeddings", True):
         s += [("thinker.lm_head.weight", (t["vocab_size"], h), "w", 0.02)]
+    if dec_bias:
+        rows = {"q_proj": nq * hd, "k_proj": nkv * hd, "v_proj": nkv * hd, "o_proj": h, "gate_proj": inter, "up_proj": inter,
+                "down_proj": h}
+        for i in range(t["num_hidden_layers"]):
+            s += [(f"{tm}.layers.{i}.{pr}.bias", (rows[pr.split(".")[1]],), "b", dec_bias_std) for pr in DEC_BIAS_PROJ[dec_bias]]
     return s
 
 
@@ -154,17 +169,22 @@ def _write_safetensors(path: str, tensors: List[Tuple[str, torch.Tensor]], dtype
 
 
 def write_checkpoint(model_dir: str, preset: str = "tiny", seed: int = 0, shards: int = 1,
-                     cfg: Optional[dict] = None, eos_trap: bool = False, dtype: str = "BF16", embed_scale: float = 0.02) -> str:
+                     cfg: Optional[dict] = None, eos_trap: bool = False, dtype: str = "BF16", embed_scale: float = 0.02,
+                     dec_bias: str = "", dec_bias_std: float = 0.1) -> str:
     """Write config.json + model.safetensors (or `shards` shard files + index json, exercising
     the sharded path of src/weights.rs:29-58).  Idempotent: a finished directory is reused.
     eos_trap (untied lm_head only): column 0 of the lm_head is zeroed except +/-64 on the two EOS rows,
     so every argmax is an EOS token -- exercises the stop condition of src/inference.rs:163-165.
     embed_scale: std of the token-embedding rows.  With the default 0.02 the decoder state is dominated by the audio context
     and greedy decoding repeats one token; a large value (with an untied lm_head) makes the state follow the token just fed,
-    so the greedy trajectory wanders through the vocabulary -- what plant_eos needs to place stops at chosen steps."""
+    so the greedy trajectory wanders through the vocabulary -- what plant_eos needs to place stops at chosen steps.
+    dec_bias ("attn" / "all"): decoder projection biases of std dec_bias_std (tensor_specs); off, the bytes and the tag are
+    those of a checkpoint written without the option."""
     cfg = cfg or PRESETS[preset]
+    assert dec_bias in ("",) + tuple(DEC_BIAS_PROJ), dec_bias
     tag = hashlib.sha1(json.dumps([cfg, seed, shards, eos_trap] + ([dtype] if dtype != "BF16" else [])
-                                  + ([embed_scale] if embed_scale != 0.02 else []), sort_keys=True).encode()).hexdigest()[:12]
+                                  + ([embed_scale] if embed_scale != 0.02 else [])
+                                  + ([dec_bias, dec_bias_std] if dec_bias else []), sort_keys=True).encode()).hexdigest()[:12]
     done = os.path.join(model_dir, f".complete.{tag}")
     if os.path.exists(done):
         return model_dir
@@ -175,7 +195,7 @@ def write_checkpoint(model_dir: str, preset: str = "tiny", seed: int = 0, shards
     with open(os.path.join(model_dir, "config.json"), "w") as f:
         json.dump({"thinker_config": cfg}, f, indent=1)
     gen = torch.Generator().manual_seed(seed)
-    specs = tensor_specs(cfg, embed_scale)
+    specs = tensor_specs(cfg, embed_scale, dec_bias, dec_bias_std)
     tensors = [(k, _gen_tensor(shape, kind, scale, gen)) for k, shape, kind, scale in specs]
     if eos_trap:
         assert not cfg["text_config"].get("tie_word_embeddings", True), "eos_trap needs an untied lm_head"

@@ -44,6 +44,9 @@ def load_hf(model_dir: str):
     from transformers import Qwen3ASRConfig, Qwen3ASRForConditionalGeneration
     cfg = O.AsrConfig.from_file(os.path.join(model_dir, "config.json"))
     a, t = cfg.audio, cfg.text
+    weights = O.load_model_weights(model_dir)  # fp32, reference key names
+    # HF's Qwen3 attention has q/k/v/o biases or none (its MLP has none): the checkpoint decides
+    attention_bias = "thinker.model.layers.0.self_attn.q_proj.bias" in weights
     hf_cfg = Qwen3ASRConfig(
         audio_config=dict(num_mel_bins=a.num_mel_bins, encoder_layers=a.encoder_layers,
                           encoder_attention_heads=a.encoder_attention_heads, encoder_ffn_dim=a.encoder_ffn_dim,
@@ -54,11 +57,10 @@ def load_hf(model_dir: str):
                          num_attention_heads=t.num_attention_heads, num_key_value_heads=t.num_key_value_heads,
                          head_dim=t.head_dim, rms_norm_eps=t.rms_norm_eps, max_position_embeddings=65536,
                          rope_parameters={"rope_type": "default", "rope_theta": t.rope_theta},
-                         tie_word_embeddings=t.tie_word_embeddings, attention_bias=False),
+                         tie_word_embeddings=t.tie_word_embeddings, attention_bias=attention_bias),
         tie_word_embeddings=t.tie_word_embeddings)
     hf_cfg._attn_implementation = "eager"
     model = Qwen3ASRForConditionalGeneration(hf_cfg).to(torch.float32).eval()
-    weights = O.load_model_weights(model_dir)  # fp32, reference key names
     sd = {remap_key(k): v for k, v in weights.items()}
     if t.tie_word_embeddings:
         sd["lm_head.weight"] = sd["model.language_model.embed_tokens.weight"]
@@ -104,7 +106,9 @@ def main():
              ("untied", "/tmp/q3a_ckpt_tiny_untied", dict(preset="tiny_untied", seed=2, shards=3), synthetic.synthetic_clip(2, 4.0)),
              # round 6: ONE case at the real 0.6B dimensions (18 + 28 layers, 14 / 16 heads, 4 attention windows, P = 405) on the
              # checkpoint and the clip bench.py and tests/test_gpu_configs.py use -- the dimensions the GPU configs are judged at
-             ("0p6b", "/tmp/q3a_ckpt_0p6b_peaked", dict(preset="0.6b", seed=0, embed_scale=synthetic.PEAKED_EMBED_SCALE), synthetic.synthetic_clip(0, 30.0))]
+             ("0p6b", "/tmp/q3a_ckpt_0p6b_peaked", dict(preset="0.6b", seed=0, embed_scale=synthetic.PEAKED_EMBED_SCALE), synthetic.synthetic_clip(0, 30.0)),
+             # decoder q/k/v/o biases (HF's attention_bias=True; its Qwen3 MLP has no bias)
+             ("decbias", "/tmp/q3a_ckpt_tiny_attnbias", dict(preset="tiny", seed=1, dec_bias="attn"), synthetic.synthetic_clip(2, 4.0))]
     only = sys.argv[1:]
     if only:  # regenerate the named cases only, keep the others as committed
         out.update({k: v for k, v in np.load(os.path.join(HERE, "hf_pin.npz")).items()})

@@ -279,6 +279,16 @@ def test_quarter_workgroup_skinny_gemm_matches_full_tiles(tiny_dir):
     """Batched decode step: the o / down projections as 8-row x 16-sequence workgroups (default) against the 16-row x
     32-sequence shape on the same inputs -- same K slices and reduction order per output, only the RMSNorm partial sums
     are grouped differently -- for a full group (32 = two sequence halves), a short group (8) and 16 < S < 32."""
+    _quarter_workgroup_forms(tiny_dir)
+
+
+def test_quarter_workgroup_skinny_gemm_matches_full_tiles_with_decoder_biases():
+    """The same with all seven decoder projection biases (tests/bias_ref.py): the bias epilogues of both workgroup shapes."""
+    import bias_ref
+    _quarter_workgroup_forms(bias_ref.write("tiny"))
+
+
+def _quarter_workgroup_forms(tiny_dir):
     from qwen3_asr_rs_amd import _lib
     lib = _lib.load()
     clips = [synthetic.synthetic_clip(80 + i, 1.0 + 0.11 * (i % 7)) for i in range(40)]
@@ -313,12 +323,22 @@ def test_gate_up_skinny_gemm_forms_are_bit_identical():
     element: logits of two teacher-forced steps must agree BIT FOR BIT -- 32 sequences (two sequence halves), 16 and 5 at the 0.6B
     dimensions, 16 and 32 (BASELINE configs[3] / configs[4] per GPU) at the 1.7B dimensions.  (Round 5 also held the single-pass
     pair form at the 1.7B dimensions to the same bits; its knob went with the round-6 pruning.)"""
+    _gate_up_forms([(synthetic.write_checkpoint("/tmp/q3a_ckpt_0p6b", "0.6b", seed=0), (32, 16, 5), (("pair", 0), ("half pair", 2))),
+                    (synthetic.write_checkpoint("/tmp/q3a_ckpt_1p7b", "1.7b", seed=0, shards=2), (16, 32), (("pair", 0), ("half pair", 1)))])
+
+
+def test_gate_up_skinny_gemm_forms_are_bit_identical_with_decoder_biases():
+    """The same at the 0.6B dimensions with all seven decoder projection biases (tests/bias_ref.py): the gate / up biases,
+    interleaved in 16-row blocks like the weight rows, enter the pair and the half-pair SwiGLU epilogues."""
+    import bias_ref
+    _gate_up_forms([(bias_ref.write("0.6b"), (32, 16, 5), (("pair", 0), ("half pair", 2)))])
+
+
+def _gate_up_forms(cases):
     from qwen3_asr_rs_amd import _lib
     from qwen3_asr_rs_amd.distributed import pack_arena_host
     lib = _lib.load()
     clips = [synthetic.synthetic_clip(200 + i, 1.2 + 0.09 * (i % 9)) for i in range(32)]
-    cases = [(synthetic.write_checkpoint("/tmp/q3a_ckpt_0p6b", "0.6b", seed=0), (32, 16, 5), (("pair", 0), ("half pair", 2))),
-             (synthetic.write_checkpoint("/tmp/q3a_ckpt_1p7b", "1.7b", seed=0, shards=2), (16, 32), (("pair", 0), ("half pair", 1)))]
     try:
         for d, sizes, forms in cases:
             arena = pack_arena_host(d).to("cuda:0")  # one upload per model, an engine per form on top of it
@@ -375,10 +395,20 @@ def test_gemm256_persistent_walk_is_bit_identical_to_one_workgroup_per_tile():
     decode steps read), gate / up (SwiGLU, 1224); the 196 / 204-tile residual shapes run one round either way.  The tile ORDER (knob
     gemm256_group_m: groups of 8 tile rows on the wide matrices by default) only changes which workgroup computes which tile.  Compared: audio
     embeddings, prefill logits, two decode steps' logits (they read the cache rows the fused epilogue wrote)."""
+    _gemm256_walks(synthetic.write_checkpoint("/tmp/q3a_ckpt_0p6b", "0.6b", seed=0))
+
+
+def test_gemm256_persistent_walk_is_bit_identical_to_one_workgroup_per_tile_with_decoder_biases():
+    """The same at the 0.6B dimensions with all seven decoder projection biases (tests/bias_ref.py): the qkv epilogue loads the
+    bias of each element and of its RoPE partner, the SwiGLU and residual epilogues theirs, at every tile seam of the walk."""
+    import bias_ref
+    _gemm256_walks(bias_ref.write("0.6b"))
+
+
+def _gemm256_walks(d):
     from qwen3_asr_rs_amd import _lib
     from qwen3_asr_rs_amd.distributed import pack_arena_host
     lib = _lib.load()
-    d = synthetic.write_checkpoint("/tmp/q3a_ckpt_0p6b", "0.6b", seed=0)
     clips = [synthetic.synthetic_clip(300 + i, 30.0) for i in range(32)]
     arena = pack_arena_host(d).to("cuda:0")
     torch.cuda.synchronize()

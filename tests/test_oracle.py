@@ -114,6 +114,23 @@ def test_oracle_matches_independent_hf_transformers_implementation(tiny_oracle, 
             np.testing.assert_allclose(top.values.numpy(), g[f"{name}_top_val"][s], atol=2e-5)
 
 
+def test_oracle_matches_hf_transformers_pin_with_decoder_attention_biases():
+    """The same pin on the tiny checkpoint with q/k/v/o_proj biases (HF's attention_bias=True; its Qwen3 MLP has none): the oracle
+    adds each bias where HuggingFace's independent implementation does -- before QK-norm and RoPE, after the attention."""
+    g = np.load(os.path.join(GOLDEN, "hf_pin.npz"))
+    d = synthetic.write_checkpoint("/tmp/q3a_ckpt_tiny_attnbias", "tiny", seed=1, dec_bias="attn")
+    r = O.AsrOracle(d).transcribe_ids(synthetic.synthetic_clip(2, 4.0), fixed_new_tokens=9, want_taps=True)
+    assert r.num_audio_tokens == int(g["decbias_T"])
+    ae = r.taps["audio_embeds"].numpy()
+    np.testing.assert_allclose(ae[::7], g["decbias_audio_embeds_q"], atol=2e-6)
+    np.testing.assert_allclose(r.step_logits[0].numpy()[::97], g["decbias_logits0_q"], atol=2e-5)
+    assert r.all_step_ids[:8] == g["decbias_ids"].tolist()
+    for s in range(9):
+        top = r.step_logits[s].topk(4)
+        assert top.indices.tolist() == g["decbias_top_idx"][s].tolist(), s
+        np.testing.assert_allclose(top.values.numpy(), g["decbias_top_val"][s], atol=2e-5)
+
+
 def test_oracle_matches_hf_transformers_pin_at_0p6b_dims():
     """The same pin at the REAL 0.6B dimensions (round 6): 18 encoder layers x 14 heads, 28 decoder layers,
     GQA 16 / 8, vocabulary 151 936, a 30 s clip = 4 attention windows (104, 104, 104, 78 tokens), P = 405 -- the checkpoint and the
