@@ -320,6 +320,40 @@ int32_t q3a_align_text_ids(const q3a_tokenizer* t, const char* const* words, int
  * neighbours; results are truncated to whole ms.  out may alias ms. */
 int32_t q3a_fix_timestamps(const float* ms, int32_t n, float* out);
 
+/* ---- scoring a given transcript: per-token log-probabilities in one prefill ---------------------------------------------------
+ * Given audio and a transcript somebody else wrote (a label, another system's hypothesis), how likely does this model find it,
+ * token by token, and what would it have written instead?  For utterance b with prompt P_b (length p; what q3a_build_prompt
+ * returns) and targets y_0 .. y_{n-1} (n = target_lens[b], may be 0) the engine prefills P_b ++ y_0 .. y_{n-2} ONCE (the last target
+ * is never fed); row p - 1 + i of the final residual stream predicts y_i.  With l = lm_head(final_norm(row)) in fp32:
+ *   out_lp[b][i]      = l[y_i] - logsumexp(l)                (natural log)
+ *   out_top_ids[b][i] = argmax l                             (larger value, then smaller index)
+ *   out_top_lp[b][i]  = l[top id] - logsumexp(l)
+ * -- what a greedy loop fed y_0 .. y_{i-1} instead of its own argmax would see at step i.  l[y_i] is the accumulator the maximum
+ * is taken over: out_lp <= 0 always, and out_lp == out_top_lp bit for bit where y_i is the argmax.  The ids are scored exactly as
+ * given: append 151645 (<|im_end|>) as the last target to score "stop here".  The rows x vocabulary logits are never stored (the
+ * lm_head reduces in its epilogue) unless logits_out asks for them.
+ * Refused: a target < 0 or >= vocabulary, a target equal to <|audio_pad|> (151676: the engine finds audio rows by this id),
+ * target_lens[b] > stride, an aligner engine, the stage form without q3a_encode.  n = 0 for every utterance is valid and returns
+ * nothing.  No engine option is needed (opts.token_logprobs is about generated ids) and both modes work.  Afterwards the engine
+ * holds no decode state, as after q3a_align: until the next prefill q3a_decode_step, q3a_set_next_tokens and q3a_fetch_ids
+ * fail.  q3a_stage_timings reports mel, encoder and prefill (the head included; total_ms = mel through head) with decode_steps =
+ * 0 and total_prompt_tokens = the rows prefilled; q3a_debug_read(e, "score_head_ms", ..) is the head's own time (a float).
+ * Results are bit-identical from run to run on the same engine and inputs.
+ * Out of scope: q3a_group_* (score each rank's slice on q3a_group_engine's handle, as for log-probabilities), several hypotheses
+ * sharing one encoder pass, continuing generation after a forced prefix. */
+
+/* Stage form, after q3a_mel + q3a_encode of the same B utterances.  prompt_ids / target_ids are concatenated over the batch;
+ * outputs are host [B][stride], entries past target_lens[b] untouched; out_top_ids / out_top_lp nullable.  logits_out (nullable;
+ * tests and debugging): host fp32 [sum of target_lens][vocab], the scored rows of all utterances in order. */
+int32_t q3a_score(q3a_engine* e, const int32_t* prompt_ids, const int32_t* prompt_lens, const int32_t* target_ids,
+                  const int32_t* target_lens, int32_t B, float* out_lp, int32_t* out_top_ids, float* out_top_lp, int32_t stride,
+                  float* logits_out);
+/* Whole path, host PCM in (as q3a_transcribe_batch_ptrs: overlapped upload, prompts set up before the encoder); the prompts are
+ * q3a_build_prompt(T_b, lang_prefix_ids, n_prefix): one language prefix for the batch. */
+int32_t q3a_score_batch_ptrs(q3a_engine* e, const float* const* pcm16k, const int64_t* n_samples, int32_t B,
+                             const int32_t* lang_prefix_ids, int32_t n_prefix, const int32_t* target_ids, const int32_t* target_lens,
+                             float* out_lp, int32_t* out_top_ids, float* out_top_lp, int32_t stride);
+
 /* A/B knobs for kernel experiments (process-wide atomics, read from the environment once; not part of the reference
  * interface).  The knobs that shape the decode step are latched per batch at the next prefill and are part of the captured
  * graph's signature, so changing one on a live engine re-captures instead of replaying a stale graph.  Keys:

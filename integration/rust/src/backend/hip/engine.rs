@@ -61,6 +61,12 @@ extern "C" {
     pub fn q3a_align_text_ids(t: *const q3a_tokenizer, words: *const *const c_char, n_words: i32, timestamp_token_id: i32, ids: *mut i32,
                               cap: i32, n: *mut i32) -> i32;
     pub fn q3a_fix_timestamps(ms: *const f32, n: i32, out: *mut f32) -> i32;
+    // scoring a given transcript (per-token log-probabilities in one prefill; include/q3asr.h "scoring a given transcript")
+    pub fn q3a_score(e: *mut q3a_engine, prompt_ids: *const i32, prompt_lens: *const i32, target_ids: *const i32, target_lens: *const i32,
+                     b: i32, out_lp: *mut f32, out_top_ids: *mut i32, out_top_lp: *mut f32, stride: i32, logits_out: *mut f32) -> i32;
+    pub fn q3a_score_batch_ptrs(e: *mut q3a_engine, pcm16k: *const *const f32, n_samples: *const i64, b: i32, lang_prefix_ids: *const i32,
+                                n_prefix: i32, target_ids: *const i32, target_lens: *const i32, out_lp: *mut f32, out_top_ids: *mut i32,
+                                out_top_lp: *mut f32, stride: i32) -> i32;
 }
 
 /// src/main.rs:51-65 for the `hip` feature: HIP devices visible to this process (0: none -- there is no CPU path).

@@ -21,7 +21,7 @@ SYMBOLS = [
     "q3a_group_create", "q3a_group_destroy", "q3a_group_size", "q3a_group_used_rccl", "q3a_group_last_error",
     "q3a_group_engine", "q3a_group_partition", "q3a_group_transcribe", "q3a_group_transcribe_ptrs", "q3a_group_startup_seconds",
     "q3a_aligner_info", "q3a_build_align_prompt", "q3a_align", "q3a_align_batch_ptrs", "q3a_split_words_for_alignment",
-    "q3a_align_text_ids", "q3a_fix_timestamps",
+    "q3a_align_text_ids", "q3a_fix_timestamps", "q3a_score", "q3a_score_batch_ptrs",
 ]
 
 
@@ -138,6 +138,8 @@ def load() -> C.CDLL:
         "q3a_split_words_for_alignment": (i32, [C.c_char_p, C.c_char_p, C.c_char_p, i32, i32p, i32p]),
         "q3a_align_text_ids": (i32, [P, C.POINTER(C.c_char_p), i32, i32, i32p, i32, i32p]),
         "q3a_fix_timestamps": (i32, [f32p, i32, f32p]),
+        "q3a_score": (i32, [P, i32p, i32p, i32p, i32p, i32, f32p, i32p, f32p, i32, f32p]),
+        "q3a_score_batch_ptrs": (i32, [P, C.POINTER(P), i64p, i32, i32p, i32, i32p, i32p, f32p, i32p, f32p, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -6,6 +6,10 @@
 // min_token_prob <smallest token probability>" (q3a_fetch_logprobs); without it stdout and stderr are unchanged.
 // Q3A_ALIGNER=<forced-aligner model dir> aligns the transcript just produced to the audio (q3a_align_batch_ptrs) and adds one stdout
 // line per word after those: "Word: <start s> <end s> <word>"; without it nothing is printed and no aligner is loaded.
+// Q3A_SCORE_TEXT=<path of a UTF-8 file> with a `language` argument scores that transcript of the audio (q3a_score_batch_ptrs on the
+// ids of "<asr_text>" + text + <|im_end|>, the language prefix in the prompt) after the lines above and adds "Score: avg_logprob <mean
+// token log-probability> min_token_prob <smallest token probability> tokens <n> disagree <rows whose argmax is another id>"; without it
+// nothing changes.
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -84,6 +88,36 @@ static int print_word_times(const char* aligner_dir, const float* pcm, int64_t n
   q3a_tokenizer_destroy(atok);
   q3a_engine_destroy(al);
   return rc;
+}
+
+// Q3A_SCORE_TEXT: the log-probability the model gives the transcript in `path`, token by token, in one prefill
+static int print_score(q3a_engine* eng, q3a_tokenizer* tok, const float* pcm, int64_t n, const std::vector<int32_t>& prefix, const char* path) {
+  FILE* f = fopen(path, "rb");
+  if (!f) return die(std::string("Scoring failed: cannot read ") + path);
+  std::string text;
+  char buf[4096];
+  for (size_t got; (got = fread(buf, 1, sizeof(buf), f)) > 0;) text.append(buf, got);
+  fclose(f);
+  while (!text.empty() && (text.back() == '\n' || text.back() == '\r')) text.pop_back();
+  const std::string full = "<asr_text>" + text;
+  int32_t nt = 0;
+  std::vector<int32_t> ids(full.size() + 8);
+  if (q3a_tokenizer_encode(tok, full.c_str(), ids.data(), (int32_t)ids.size(), &nt) != 0)
+    return die(std::string("Scoring failed: ") + q3a_last_error(nullptr));
+  ids.resize((size_t)nt);
+  ids.push_back(151645);  // <|im_end|>: "the transcript stops here" is scored too
+  nt = (int32_t)ids.size();
+  std::vector<float> lp((size_t)nt), top_lp((size_t)nt);
+  std::vector<int32_t> top((size_t)nt);
+  const float* ptrs[1] = {pcm};
+  if (q3a_score_batch_ptrs(eng, ptrs, &n, 1, prefix.data(), (int32_t)prefix.size(), ids.data(), &nt, lp.data(), top.data(), top_lp.data(), nt) != 0)
+    return die(std::string("Scoring failed: ") + q3a_last_error(eng));
+  double sum = 0.0;
+  float mn = INFINITY;
+  int disagree = 0;
+  for (int32_t i = 0; i < nt; ++i) { sum += lp[i]; mn = std::min(mn, lp[i]); disagree += top[i] != ids[i]; }
+  printf("Score: avg_logprob %.6f min_token_prob %.6f tokens %d disagree %d\n", sum / (double)nt, std::exp((double)mn), nt, disagree);
+  return 0;
 }
 
 int main(int argc, char** argv) {
@@ -189,9 +223,11 @@ int main(int argc, char** argv) {
     const double avg = lps.empty() ? NAN : sum / (double)lps.size();
     printf("Confidence: avg_logprob %.6f min_token_prob %.6f\n", avg, lps.empty() ? NAN : std::exp((double)mn));
   }
-  const char* aligner_dir = getenv("Q3A_ALIGNER");
   int rc = 0;
-  if (aligner_dir && *aligner_dir) rc = print_word_times(aligner_dir, pcm, n, text.data(), language);
+  const char* score_path = getenv("Q3A_SCORE_TEXT");
+  if (score_path && *score_path && language) rc = print_score(eng, tok, pcm, n, prefix, score_path);
+  const char* aligner_dir = getenv("Q3A_ALIGNER");
+  if (rc == 0 && aligner_dir && *aligner_dir) rc = print_word_times(aligner_dir, pcm, n, text.data(), language);
   q3a_free(pcm);
   q3a_tokenizer_destroy(tok);
   q3a_engine_destroy(eng);

@@ -983,16 +983,39 @@ struct q3a_engine {
     }
     return rows;
   }
-  // prefill layers + head; prompts already set up (setup_prompts).  Events: ev[2] before the prefill (recorded here),
-  // ev[3] after the layers, ev[4] after the head.  Classes (and logits) to the host, [utterance][stride].
-  void run_align(const std::vector<int>& rows, const int32_t* counts, int stride, int32_t* out_classes, float* logits_out) {
-    const int M = (int)rows.size(), N = d.classify_num, H = d.hidden;
+  // The skeleton the aligner and the scoring call share: prefill layers, then a head at a list of rows of the last layer's residual
+  // stream (uploaded to align_rows), no decode state.  Prompts already set up (setup_prompts).  Events: ev[2] before the prefill
+  // (recorded here), ev[3] after the layers, ev[4] after the head; the stream is idle on return.
+  template <class Head>
+  void run_prefill_then_head(const std::vector<int>& rows, float& head_ms, Head&& enqueue_head) {
     have_prefill = false;
     HIPCHK(hipEventRecord(ev[2], stream));
     run_prefill_layers();
     HIPCHK(hipEventRecord(ev[3], stream));
-    if (M > 0) {
+    if (!rows.empty()) {
       upload(align_rows, rows, stream);
+      enqueue_head();
+    }
+    HIPCHK(hipEventRecord(ev[4], stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, ev[2], ev[4])); timings.prefill_ms = ms;
+    HIPCHK(hipEventElapsedTime(&ms, ev[3], ev[4])); head_ms = ms;
+    timings.decode_ms = 0.f; timings.decode_steps = 0; timings.batch = B; timings.total_audio_tokens = total_T;
+    timings.total_prompt_tokens = total_P;
+  }
+  // whole-path callers: mel and encoder times of the events upload_ptrs_and_mel / the caller recorded, total = mel through head
+  void head_call_front_timings() {
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1])); timings.mel_ms = ms;
+    HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2])); timings.encoder_ms = ms;
+    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[4])); timings.total_ms = ms;
+  }
+  // Classes (and logits) to the host, [utterance][stride].
+  void run_align(const std::vector<int>& rows, const int32_t* counts, int stride, int32_t* out_classes, float* logits_out) {
+    const int M = (int)rows.size(), N = d.classify_num, H = d.hidden;
+    run_prefill_then_head(rows, align_head_ms, [&] {
       const int planes = precise() ? 2 : 1, n_part = align_head_parts(N);
       align_xn.ensure((size_t)planes * align_rows_padded(M) * H * 2);
       align_pval.ensure((size_t)M * n_part * 4); align_pidx.ensure((size_t)M * n_part * 4);
@@ -1006,23 +1029,88 @@ struct q3a_engine {
       a.classes = align_cls.as<int>();
       a.logits = logits_out ? align_logits.as<float>() : nullptr; a.ldl = N;
       KCHK(launch_align_head(a, stream));
-    }
-    HIPCHK(hipEventRecord(ev[4], stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    HIPCHK(hipGetLastError());
+    });
     std::vector<int> cls((size_t)M);
     if (M > 0) HIPCHK(hipMemcpy(cls.data(), align_cls.p, (size_t)M * 4, hipMemcpyDeviceToHost));
     if (M > 0 && logits_out) HIPCHK(hipMemcpy(logits_out, align_logits.p, (size_t)M * N * 4, hipMemcpyDeviceToHost));
     for (int s = 0, k = 0; s < B; ++s)
       for (int i = 0; i < counts[s]; ++i) out_classes[(size_t)s * stride + i] = cls[k++];
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, ev[2], ev[4])); timings.prefill_ms = ms;
-    HIPCHK(hipEventElapsedTime(&ms, ev[3], ev[4])); align_head_ms = ms;
-    timings.decode_ms = 0.f; timings.decode_steps = 0; timings.batch = B; timings.total_audio_tokens = total_T;
-    timings.total_prompt_tokens = total_P;
   }
   DevBuf align_rows, align_xn, align_pval, align_pidx, align_cls, align_logits;
   float align_head_ms = 0.f;  // the head's launches of the last align call (q3a_debug_read "align_head_ms")
+
+  // =====================================================================================
+  // scoring a given transcript (q3a_score*): ONE causal prefill over prompt + targets[:-1], then the lm_head at the rows that
+  // predict the targets with a reducing epilogue (k_align.hip launch_score_head); no argmax_finalize, no decode state.
+  struct ScorePlan {
+    std::vector<int32_t> ids, lens;  // what is prefilled: per utterance prompt ++ targets[0 .. n-2]
+    std::vector<int> rows, targets;  // per scored position: row of the residual stream that predicts it, and its id
+  };
+  // prompt_ids / target_ids concatenated over the batch; refuses what the header lists
+  ScorePlan score_plan(const char* what, const int32_t* prompt_ids, const int32_t* prompt_lens, const int32_t* target_ids,
+                       const int32_t* target_lens, int b, int stride) const {
+    ScorePlan sp;
+    sp.lens.resize(b);
+    size_t po = 0, to = 0;
+    for (int s = 0; s < b; ++s) {
+      const int p = prompt_lens[s], n = target_lens[s];
+      if (p <= 0) fail(std::string(what) + ": empty prompt");
+      if (n < 0 || (n > 0 && !target_ids)) fail(std::string(what) + ": bad target length");
+      if (n > stride)
+        fail(std::string(what) + ": utterance " + std::to_string(s) + " has " + std::to_string(n) + " targets, more than stride " + std::to_string(stride));
+      const int row0 = (int)sp.ids.size() + p - 1;
+      sp.ids.insert(sp.ids.end(), prompt_ids + po, prompt_ids + po + p);
+      for (int i = 0; i < n; ++i) {
+        const int32_t y = target_ids[to + i];
+        if (y < 0 || y >= d.vocab) fail(std::string(what) + ": target id " + std::to_string(y) + " out of range (vocabulary " + std::to_string(d.vocab) + ")");
+        if (y == kAudioPad) fail(std::string(what) + ": <|audio_pad|> (" + std::to_string(kAudioPad) + ") cannot be a target: the engine finds audio rows by this id");
+        if (i + 1 < n) sp.ids.push_back(y);  // the last target is never fed
+        sp.rows.push_back(row0 + i);
+        sp.targets.push_back(y);
+      }
+      sp.lens[s] = p + std::max(n - 1, 0);
+      po += p; to += n;
+    }
+    return sp;
+  }
+  // prompts of sp already set up.  Results to the host [utterance][stride]; logits_out (nullable): [rows][vocab].
+  void run_score(const ScorePlan& sp, const int32_t* target_lens, int stride, float* out_lp, int32_t* out_top_ids, float* out_top_lp,
+                 float* logits_out) {
+    const int M = (int)sp.rows.size(), V = d.vocab, H = d.hidden;
+    run_prefill_then_head(sp.rows, score_head_ms, [&] {
+      const int planes = precise() ? 2 : 1, n_part = align_head_parts(V);
+      upload(score_tgt, sp.targets, stream);
+      align_xn.ensure((size_t)planes * align_rows_padded(M) * H * 2);
+      align_pval.ensure((size_t)M * n_part * 4); align_pidx.ensure((size_t)M * n_part * 4); score_psum.ensure((size_t)M * n_part * 4);
+      score_out.ensure((size_t)M * 4 * 4);  // tgt_logit | lp | top_id | top_lp
+      if (logits_out) align_logits.ensure((size_t)M * V * 4);  // the only M x vocab buffer, and only on request
+      ScoreHeadArgs a{};
+      a.x = dec_x.as<float>(); a.ldx = H; a.rows = align_rows.as<int>(); a.M = M;
+      a.norm_w = wf(L.final_norm); a.eps = d.rms_eps; a.W = wh(L.lm_head); a.N = V; a.K = H;
+      a.planes = planes; a.xn = align_xn.as<uint16_t>();
+      a.part = ArgmaxPartials{align_pval.as<float>(), align_pidx.as<int>(), score_psum.as<float>(), n_part};
+      a.targets = score_tgt.as<int>();
+      a.tgt_logit = score_out.as<float>(); a.lp = score_out.as<float>() + M;
+      a.top_id = score_out.as<int>() + 2 * (size_t)M; a.top_lp = score_out.as<float>() + 3 * (size_t)M;
+      a.logits = logits_out ? align_logits.as<float>() : nullptr; a.ldl = (size_t)V;
+      KCHK(launch_score_head(a, stream));
+    });
+    if (M == 0) return;
+    std::vector<float> res((size_t)M * 4);
+    HIPCHK(hipMemcpy(res.data(), score_out.p, res.size() * 4, hipMemcpyDeviceToHost));
+    if (logits_out) HIPCHK(hipMemcpy(logits_out, align_logits.p, (size_t)M * V * 4, hipMemcpyDeviceToHost));
+    const float* lp = res.data() + M;
+    const int32_t* ti = reinterpret_cast<const int32_t*>(res.data()) + 2 * (size_t)M;
+    const float* tl = res.data() + 3 * (size_t)M;
+    for (int s = 0, k = 0; s < B; ++s)
+      for (int i = 0; i < target_lens[s]; ++i, ++k) {
+        out_lp[(size_t)s * stride + i] = lp[k];
+        if (out_top_ids) out_top_ids[(size_t)s * stride + i] = ti[k];
+        if (out_top_lp) out_top_lp[(size_t)s * stride + i] = tl[k];
+      }
+  }
+  DevBuf score_tgt, score_psum, score_out;
+  float score_head_ms = 0.f;  // the head's launches of the last score call (q3a_debug_read "score_head_ms")
 
   void scatter_audio_rows();
 
@@ -1416,7 +1504,7 @@ struct q3a_engine {
                       &d_pos, &next_tok, &out_ids, &step_count, &done, &s_ln, &s_qkv, &s_ctx, &s_act, &logits, &forced_tok, &part_val, &part_idx, &attn_pm, &attn_pl, &attn_po,
                       &part_sum, &out_lp,
                       &enc_ctx16, &dec_ctx16, &dec_q16, &zero_page, &rope_cur, &nn_x, &nn_ss, &n_done,
-                      &align_rows, &align_xn, &align_pval, &align_pidx, &align_cls, &align_logits};
+                      &align_rows, &align_xn, &align_pval, &align_pidx, &align_cls, &align_logits, &score_tgt, &score_psum, &score_out};
     for (auto* b : bufs) b->release();
     for (auto& kv : taps) kv.second.release();
     if (own_arena && arena) (void)hipFree(arena);
@@ -1625,10 +1713,56 @@ int32_t q3a_align_batch_ptrs(q3a_engine* e, const float* const* pcm16k, const in
   e->upload_ptrs_and_mel(pcm16k, n_samples, B);
   e->run_encoder();
   e->run_align(rows, out_counts, stride, out_classes, nullptr);
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, e->ev[0], e->ev[1])); e->timings.mel_ms = ms;
-  HIPCHK(hipEventElapsedTime(&ms, e->ev[1], e->ev[2])); e->timings.encoder_ms = ms;
-  HIPCHK(hipEventElapsedTime(&ms, e->ev[0], e->ev[4])); e->timings.total_ms = ms;
+  e->head_call_front_timings();
+  Q3A_CATCH(e)
+}
+
+int32_t q3a_score(q3a_engine* e, const int32_t* prompt_ids, const int32_t* prompt_lens, const int32_t* target_ids,
+                  const int32_t* target_lens, int32_t B, float* out_lp, int32_t* out_top_ids, float* out_top_lp, int32_t stride,
+                  float* logits_out) {
+  if (!e) return 1;
+  Q3A_TRY(e)
+  e->require_asr("q3a_score");
+  if (!prompt_ids || !prompt_lens || !target_lens || B < 1 || stride < 0 || (stride > 0 && !out_lp)) fail("q3a_score: bad argument");
+  HIPCHK(hipSetDevice(e->device));
+  if (!e->have_enc) fail("q3a_score: no encoder output (call q3a_encode first)");
+  if (B != e->B) fail("q3a_score: batch size differs from the encoded batch");
+  const auto sp = e->score_plan("q3a_score", prompt_ids, prompt_lens, target_ids, target_lens, B, stride);
+  e->have_prefill = false;
+  e->setup_prompts(sp.ids.data(), sp.lens.data(), B, 1);
+  e->timings = q3a_timings{};
+  e->run_score(sp, target_lens, stride, out_lp, out_top_ids, out_top_lp, logits_out);
+  Q3A_CATCH(e)
+}
+
+int32_t q3a_score_batch_ptrs(q3a_engine* e, const float* const* pcm16k, const int64_t* n_samples, int32_t B,
+                             const int32_t* lang_prefix_ids, int32_t n_prefix, const int32_t* target_ids, const int32_t* target_lens,
+                             float* out_lp, int32_t* out_top_ids, float* out_top_lp, int32_t stride) {
+  if (!e) return 1;
+  Q3A_TRY(e)
+  e->require_asr("q3a_score_batch");
+  if (!pcm16k || !n_samples || !target_lens || B < 1 || stride < 0 || (stride > 0 && !out_lp) || n_prefix < 0) fail("q3a_score_batch: bad argument");
+  for (int u = 0; u < B; ++u)
+    if (!pcm16k[u]) fail("q3a_score_batch: null utterance pointer");
+  HIPCHK(hipSetDevice(e->device));
+  e->have_prefill = false;
+  e->set_batch(n_samples, B);  // geometry first: the prompts only need the lengths
+  std::vector<int32_t> pids, plens(B);
+  for (int s = 0; s < B; ++s) {
+    int32_t len = 0;
+    q3a_build_prompt(e->T[s], lang_prefix_ids, n_prefix, nullptr, &len);
+    const size_t o = pids.size();
+    pids.resize(o + len);
+    q3a_build_prompt(e->T[s], lang_prefix_ids, n_prefix, pids.data() + o, &len);
+    plens[s] = len;
+  }
+  const auto sp = e->score_plan("q3a_score_batch", pids.data(), plens.data(), target_ids, target_lens, B, stride);
+  e->setup_prompts(sp.ids.data(), sp.lens.data(), B, 1, true);
+  e->timings = q3a_timings{};
+  e->upload_ptrs_and_mel(pcm16k, n_samples, B);
+  e->run_encoder();
+  e->run_score(sp, target_lens, stride, out_lp, out_top_ids, out_top_lp, nullptr);
+  e->head_call_front_timings();
   Q3A_CATCH(e)
 }
 
@@ -1925,6 +2059,14 @@ int32_t q3a_debug_read(q3a_engine* e, const char* name, void* dst, uint64_t byte
     if (dst) {
       if (bytes < 4) fail("q3a_debug_read: destination too small");
       memcpy(dst, &e->align_head_ms, 4);
+    }
+    return 0;
+  }
+  if (strcmp(name, "score_head_ms") == 0) {  // float: the scoring head's launches (norm, lm_head with the reducing epilogue, merge) of the last score call
+    if (actual) *actual = 4;
+    if (dst) {
+      if (bytes < 4) fail("q3a_debug_read: destination too small");
+      memcpy(dst, &e->score_head_ms, 4);
     }
     return 0;
   }

@@ -9,6 +9,14 @@
 //      only when asked for.
 //   3. align_merge_kernel: one thread per row merges its partials in column order -> class.
 // The tie rule (larger value, then smaller index) is argmax.h ArgmaxAcc's.
+//
+// Scoring head (kernels.h ScoreHeadArgs): the same norm launch and the same 64 x 128 tile (head_tile<.., LP = true>) against the
+// vocabulary lm_head at the rows that predict a given transcript.  The M x vocab logits are never stored (unless asked for): per row
+// and 64-column strip the epilogue leaves one (max, first index, sum exp(l - max)) partial, and the one lane that holds column
+// target[row] stores that accumulator to tgt_logit[row] (single writer).  score_head_kernel walks the tiles M fastest inside the
+// contiguous chunk of tile ids its XCD receives, so the row tiles that share a 128-row slab of the lm_head run together on one L2.
+// score_merge_kernel: one wave per row merges the row's partials (lane l takes partials l, l + 64, ... in ascending order, then the
+// xor butterfly 32 .. 1: a fixed order) and writes lp = l[target] - logsumexp, top_id, top_lp = -log(sum).
 #include "argmax.h"
 #include "dev.h"
 #include "kernels.h"
@@ -60,13 +68,16 @@ __global__ __launch_bounds__(256) void align_norm_kernel(const float* __restrict
   }
 }
 
-template <int NP, bool LOGITS>
-__global__ __launch_bounds__(256) void align_head_kernel(const uint16_t* __restrict__ xn, int Mp, int M, const uint16_t* __restrict__ W,
-                                                         int N, int K, ArgmaxPartials part, float* __restrict__ logits, int ldl) {
+// One 64 x 128 output tile at (m0, n0 = 128 tile_n).  LP (scoring head): the partials carry the log-sum channel and the lane that
+// holds column targets[m] stores its accumulator to tgt_logit[m].
+template <int NP, bool LOGITS, bool LP>
+__device__ __forceinline__ void head_tile(const uint16_t* __restrict__ xn, int Mp, int M, const uint16_t* __restrict__ W, int N, int K,
+                                          const ArgmaxPartials& part, float* __restrict__ logits, size_t ldl, int m0, int tile_n,
+                                          const int* __restrict__ targets, float* __restrict__ tgt_logit) {
   __shared__ __attribute__((aligned(16))) uint16_t As[NP][BM * LDSK];
   __shared__ __attribute__((aligned(16))) uint16_t Bs[BN * LDSK];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave >> 1, wn = wave & 1;
-  const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
+  const int n0 = tile_n * BN;
   // staging: 16-B chunks, 8 per 64-deep row; A: 2 per thread and plane, B: 4 per thread (rows beyond N read row N - 1).  Chunk
   // c = t + 256 j sits at row (t >> 3) + 32 j, column 8 (t & 7) of its tile.
   const int srow = t >> 3, skc = (t & 7) * 8;
@@ -132,25 +143,79 @@ __global__ __launch_bounds__(256) void align_head_kernel(const uint16_t* __restr
     }
   }
   // epilogue: lane holds rows 4 (lane >> 4) + r of each 16 x 16 tile, column lane & 15; a lane's columns ascend with ni
-  const int strip = blockIdx.x * 2 + wn;
+  const int strip = tile_n * 2 + wn;
 #pragma unroll
   for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int m = m0 + 32 * wm + 16 * mi + 4 * (lane >> 4) + r;
-      ArgmaxAcc<false> best;
+      int tgt = -1;
+      if constexpr (LP) tgt = m < M ? targets[m] : -1;
+      ArgmaxAcc<LP> best;
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
         const int n = n0 + 64 * wn + 16 * ni + (lane & 15);
         const float v = acc[mi][ni][r];
         if (n < N && v > best.v) { best.v = v; best.i = n; }
         if (LOGITS && n < N && m < M) logits[(size_t)m * ldl + n] = v;
+        if constexpr (LP) {
+          if (n == tgt && n < N) tgt_logit[m] = v;  // (m < M: tgt is -1 otherwise) the accumulator the max channel sees
+        }
+      }
+      if constexpr (LP) {  // this lane's log-sum around its own maximum (a lane whose columns are all beyond N keeps s = 0)
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) {
+          const int n = n0 + 64 * wn + 16 * ni + (lane & 15);
+          if (n < N) best.s += __expf(acc[mi][ni][r] - best.v);
+        }
       }
 #pragma unroll
       for (int o = 1; o < 16; o <<= 1) best.merge_lane(o);
       if ((lane & 15) == 0 && m < M) best.store(part, m, strip);
     }
 #undef ALIGN_LOAD
+}
+
+template <int NP, bool LOGITS>
+__global__ __launch_bounds__(256) void align_head_kernel(const uint16_t* __restrict__ xn, int Mp, int M, const uint16_t* __restrict__ W,
+                                                         int N, int K, ArgmaxPartials part, float* __restrict__ logits, int ldl) {
+  head_tile<NP, LOGITS, false>(xn, Mp, M, W, N, K, part, logits, (size_t)ldl, blockIdx.y * BM, blockIdx.x, nullptr, nullptr);
+}
+
+// 1-D grid of 8 * ceil(tiles / 8) workgroups: the hardware deals workgroup ids round-robin to the 8 XCDs, so workgroup w walks tile
+// (w % 8) * chunk + w / 8 -- every XCD a contiguous chunk of the tile order, in which the row tiles (m_tiles of them) are fastest
+template <int NP, bool LOGITS>
+__global__ __launch_bounds__(256) void score_head_kernel(const uint16_t* __restrict__ xn, int Mp, int M, const uint16_t* __restrict__ W,
+                                                         int N, int K, ArgmaxPartials part, float* __restrict__ logits, size_t ldl,
+                                                         const int* __restrict__ targets, float* __restrict__ tgt_logit, int m_tiles,
+                                                         int tiles) {
+  const int chunk = gridDim.x >> 3;
+  const int id = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+  if (id >= tiles) return;  // (the whole workgroup)
+  head_tile<NP, LOGITS, true>(xn, Mp, M, W, N, K, part, logits, ldl, (id % m_tiles) * BM, id / m_tiles, targets, tgt_logit);
+}
+
+__global__ __launch_bounds__(256) void score_merge_kernel(ArgmaxPartials part, int n_part, int M, int N, const float* __restrict__ tgt_logit,
+                                                          float* __restrict__ lp, int* __restrict__ top_id, float* __restrict__ top_lp) {
+  const int lane = threadIdx.x & 63;
+  const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (m >= M) return;  // (the whole wave)
+  ArgmaxAcc<true> best;
+  for (int c = lane; c < n_part; c += 64) best.merge(ArgmaxAcc<true>::load(part, m, c));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) best.merge_lane(o);
+  if (lane != 0) return;
+  // logsumexp = max + log(sum): the top logit IS the max, so top_lp = -log(sum) and lp = (l[target] - max) - log(sum) equals it
+  // bit for bit when the target is the argmax
+  const float ls = logf(best.s);
+  float tl = -ls, yl = (tgt_logit[m] - best.v) - ls;
+  if (tl > 0.f) tl = 0.f;  // (rounding; NaN passes through)
+  if (yl > 0.f) yl = 0.f;
+  int idx = best.i;
+  if (idx < 0 || idx >= N) { idx = 0; tl = yl = __int_as_float(0x7fc00000); }  // no finite logit in the row
+  lp[m] = yl;
+  if (top_id) top_id[m] = idx;
+  if (top_lp) top_lp[m] = tl;
 }
 
 __global__ __launch_bounds__(256) void align_merge_kernel(ArgmaxPartials part, int n_part, int M, int N, int* __restrict__ classes) {
@@ -166,6 +231,43 @@ __global__ __launch_bounds__(256) void align_merge_kernel(ArgmaxPartials part, i
 int align_rows_padded(int M) { return (M + BM - 1) / BM * BM; }
 int align_head_parts(int N) { return 2 * ((N + BN - 1) / BN); }
 
+const char* launch_head_rows_norm(const float* x, int ldx, const int* rows, int M, const float* norm_w, float eps, int K, int planes,
+                                  uint16_t* xn, hipStream_t s) {
+  if (M <= 0) return nullptr;
+  if (!x || !rows || !norm_w || !xn) return "head rows norm: null argument";
+  if (planes != 1 && planes != 2) return "head rows norm: planes must be 1 or 2";
+  if (K % BK != 0 || K > 2048) return "head rows norm: hidden must be a multiple of 64 and at most 2048";
+  const int Mp = align_rows_padded(M);
+  hipLaunchKernelGGL(align_norm_kernel, dim3(Mp / 4), dim3(256), 0, s, x, ldx, rows, M, Mp, norm_w, eps, K, planes, xn);
+  return nullptr;
+}
+
+const char* launch_score_head(const ScoreHeadArgs& a, hipStream_t s) {
+  if (a.M <= 0) return nullptr;
+  if (!a.x || !a.rows || !a.norm_w || !a.W || !a.xn || !a.targets || !a.tgt_logit || !a.lp || !a.part.val || !a.part.sum)
+    return "score head: null argument";
+  if (a.N <= 0) return "score head: empty vocabulary";
+  const int n_part = align_head_parts(a.N);
+  if (const char* e = argmax_partials_check(a.part, n_part)) return e;
+  if (a.logits && a.ldl < (size_t)a.N) return "score head: logits row stride below the vocabulary";
+  if (const char* e = launch_head_rows_norm(a.x, a.ldx, a.rows, a.M, a.norm_w, a.eps, a.K, a.planes, a.xn, s)) return e;
+  const int Mp = align_rows_padded(a.M), m_tiles = Mp / BM;
+  const long long tiles = (long long)m_tiles * ((a.N + BN - 1) / BN);
+  if (tiles > (1ll << 30)) return "score head: too many tiles";
+  const dim3 grid((unsigned)((tiles + 7) / 8 * 8));
+#define SCORE_LAUNCH(NP, LG)                                                                                                      \
+  hipLaunchKernelGGL((score_head_kernel<NP, LG>), grid, dim3(256), 0, s, a.xn, Mp, a.M, a.W, a.N, a.K, a.part, a.logits, a.ldl, \
+                     a.targets, a.tgt_logit, m_tiles, (int)tiles)
+  if (a.planes == 1) {
+    if (a.logits) SCORE_LAUNCH(1, true); else SCORE_LAUNCH(1, false);
+  } else {
+    if (a.logits) SCORE_LAUNCH(2, true); else SCORE_LAUNCH(2, false);
+  }
+#undef SCORE_LAUNCH
+  hipLaunchKernelGGL(score_merge_kernel, dim3((a.M + 3) / 4), dim3(256), 0, s, a.part, n_part, a.M, a.N, a.tgt_logit, a.lp, a.top_id, a.top_lp);
+  return nullptr;
+}
+
 const char* launch_align_head(const AlignHeadArgs& a, hipStream_t s) {
   if (a.M <= 0) return nullptr;
   if (!a.x || !a.rows || !a.norm_w || !a.W || !a.xn || !a.classes || !a.part.val) return "align head: null argument";
@@ -176,7 +278,7 @@ const char* launch_align_head(const AlignHeadArgs& a, hipStream_t s) {
   if (const char* e = argmax_partials_check(a.part, n_part)) return e;
   if (a.logits && a.ldl < a.N) return "align head: logits row stride below classify_num";
   const int Mp = align_rows_padded(a.M);
-  hipLaunchKernelGGL(align_norm_kernel, dim3(Mp / 4), dim3(256), 0, s, a.x, a.ldx, a.rows, a.M, Mp, a.norm_w, a.eps, a.K, a.planes, a.xn);
+  if (const char* e = launch_head_rows_norm(a.x, a.ldx, a.rows, a.M, a.norm_w, a.eps, a.K, a.planes, a.xn, s)) return e;
   const dim3 grid((a.N + BN - 1) / BN, Mp / BM);
   if (a.planes == 1) {
     if (a.logits) hipLaunchKernelGGL((align_head_kernel<1, true>), grid, dim3(256), 0, s, a.xn, Mp, a.M, a.W, a.N, a.K, a.part, a.logits, a.ldl);

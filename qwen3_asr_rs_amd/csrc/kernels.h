@@ -56,6 +56,29 @@ struct AlignHeadArgs {
 int align_rows_padded(int M);
 int align_head_parts(int N);
 const char* launch_align_head(const AlignHeadArgs& a, hipStream_t s);
+// the first launch of both heads: rows[M] of x gathered, final RMSNorm, bf16 operand planes xn [planes][align_rows_padded(M)][K]
+// (rows M .. padded are zeros)
+const char* launch_head_rows_norm(const float* x, int ldx, const int* rows, int M, const float* norm_w, float eps, int K, int planes,
+                                  uint16_t* xn, hipStream_t s);
+
+// ---- scoring head (k_align.hip): log-probabilities of given tokens -------------------------------------------
+// At the M rows that predict a given transcript: final RMSNorm, lm_head W [N = vocab][K = hidden] (bf16) and, per row, the
+// log-probability of targets[m], the argmax and its log-probability.  M x N logits exist only when `logits` is set.
+struct ScoreHeadArgs {
+  const float* x; int ldx;        // residual stream after the last decoder layer, fp32 [rows][ldx]
+  const int* rows; int M;         // [M] rows of x (device)
+  const float* norm_w; float eps; // final RMSNorm
+  const uint16_t* W; int N; int K;
+  int planes;                     // as AlignHeadArgs
+  uint16_t* xn;                   // workspace [planes][align_rows_padded(M)][K]
+  ArgmaxPartials part;            // [M] rows x align_head_parts(N) partials WITH the log-sum channel
+  const int* targets;             // [M] in [0, N) (device)
+  float* tgt_logit;               // [M] workspace: the fp32 accumulator of column targets[m]
+  float* lp;                      // [M] l[target] - logsumexp(l)
+  int* top_id; float* top_lp;     // [M] argmax (first index on ties) and its log-probability; nullable
+  float* logits; size_t ldl;      // nullable: [M][ldl] fp32
+};
+const char* launch_score_head(const ScoreHeadArgs& a, hipStream_t s);
 
 // ---- GEMM (k_gemm.hip) -----------------------------------------------------------------------------
 struct GemmEpilogue {

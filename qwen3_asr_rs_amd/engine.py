@@ -282,6 +282,58 @@ class HipEngine:
         self.batch = B
         return [out[b, :int(counts[b])].tolist() for b in range(B)]
 
+    # ---- scoring a given transcript ------------------------------------------------------------------
+    @staticmethod
+    def _score_targets(targets: Sequence[Sequence[int]], stride: Optional[int] = None):
+        tl = np.array([len(t) for t in targets], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(t, dtype=np.int64).reshape(-1) for t in targets] + [np.zeros(1, np.int64)]))
+        if len(flat) and (flat.min() < -2**31 or flat.max() >= 2**31):
+            raise Q3aError("score: target id does not fit 32 bits")
+        if stride is None:
+            stride = max(1, int(tl.max()) if len(tl) else 1)
+        return tl, flat.astype(np.int32), int(stride)
+
+    @staticmethod
+    def _score_split(tl, lp, ti, tp):
+        return [(lp[b, :int(n)].copy(), ti[b, :int(n)].copy(), tp[b, :int(n)].copy()) for b, n in enumerate(tl)]
+
+    def score(self, prompts: Sequence[Sequence[int]], targets: Sequence[Sequence[int]], want_logits: bool = False,
+              stride: Optional[int] = None):
+        """Stage form (q3a_score) after mel() + encode(): ONE prefill of prompt + targets[:-1] per utterance and the lm_head at the rows
+        that predict the targets.  Returns per utterance (lp, top_ids, top_lp): the log-probability of every target, the model's own
+        argmax at that position and its log-probability; with want_logits also the fp32 logits [sum of lengths][vocab]."""
+        B = len(prompts)
+        if len(targets) != B:
+            raise Q3aError(f"score: {len(targets)} target list(s) for {B} prompt(s)")
+        pl = np.array([len(p) for p in prompts], dtype=np.int32)
+        pids = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.int32) for p in prompts]))
+        tl, flat, stride = self._score_targets(targets, stride)
+        lp = np.zeros((B, max(stride, 1)), dtype=np.float32)
+        ti = np.zeros((B, max(stride, 1)), dtype=np.int32)
+        tp = np.zeros((B, max(stride, 1)), dtype=np.float32)
+        logits = np.zeros((max(int(tl.sum()), 1), self.dims.vocab_size), dtype=np.float32) if want_logits else None
+        self._chk(self._lib.q3a_score(self._h, _i32p(pids), _i32p(pl), _i32p(flat), _i32p(tl), B, _f32p(lp), _i32p(ti), _f32p(tp), stride,
+                                      _f32p(logits) if want_logits else None))
+        res = self._score_split(tl, lp, ti, tp)
+        return (res, logits[:int(tl.sum())]) if want_logits else res
+
+    def score_batch(self, clips: Sequence[np.ndarray], targets: Sequence[Sequence[int]], lang_prefix_ids: Optional[Sequence[int]] = None,
+                    stride: Optional[int] = None):
+        """Whole path (q3a_score_batch_ptrs): host PCM + the ids to score per utterance -> (lp, top_ids, top_lp) per utterance."""
+        arrs, ptrs, ns = self._ptrs(clips)
+        B = len(arrs)
+        if len(targets) != B:
+            raise Q3aError(f"score_batch: {len(targets)} target list(s) for {B} clip(s)")
+        tl, flat, stride = self._score_targets(targets, stride)
+        pre = np.asarray(lang_prefix_ids if lang_prefix_ids is not None else [], dtype=np.int32)
+        lp = np.zeros((B, max(stride, 1)), dtype=np.float32)
+        ti = np.zeros((B, max(stride, 1)), dtype=np.int32)
+        tp = np.zeros((B, max(stride, 1)), dtype=np.float32)
+        self._chk(self._lib.q3a_score_batch_ptrs(self._h, ptrs, _i64p(ns), B, _i32p(pre) if len(pre) else None, len(pre), _i32p(flat), _i32p(tl),
+                                                 _f32p(lp), _i32p(ti), _f32p(tp), stride))
+        self.batch = B
+        return self._score_split(tl, lp, ti, tp)
+
     def debug_read_raw(self, name: str) -> np.ndarray:
         """The same as bytes (records of mixed types: tools/soak_engines.py)."""
         n = C.c_uint64()
@@ -410,6 +462,17 @@ class TranscribeResult:
     avg_logprob: Optional[float] = None
 
 
+@dataclass
+class ScoreResult:
+    """AsrInference.score: the ids that were scored, the log-probability of each (natural log) and their mean (None when nothing was
+    scored), and what the model would have written at each position given the same history, with its log-probability."""
+    target_ids: List[int]
+    token_logprobs: List[float]
+    avg_logprob: Optional[float]
+    greedy_ids: List[int]
+    greedy_logprobs: List[float]
+
+
 class AsrInference:
     """Drop-in for the reference's AsrInference (src/inference.rs:19-27) backed by the HIP engine."""
 
@@ -448,6 +511,33 @@ class AsrInference:
             res.token_logprobs = [float(v) for v in lp]
             res.avg_logprob = float(np.mean(lp, dtype=np.float64)) if len(lp) else None
         return res
+
+
+    def score(self, audio, text_or_ids, language: Optional[str] = None, eos: bool = True) -> ScoreResult:
+        """How likely the model finds a given transcript of `audio`, token by token (one prefill, no decode loop).  A list of ids is
+        scored as given (the pinned contract).  A string needs `language`: the prompt carries the prefix transcribe() builds and the
+        targets are encode("<asr_text>" + text) -- what a published checkpoint writes after a forced-language prompt as
+        parse_asr_output reads it.  eos: also score <|im_end|> (151645) after the last id, i.e. "the transcript stops here"."""
+        if isinstance(audio, (str, os.PathLike)):
+            samples = load_audio(os.fspath(audio), 16000)
+        else:
+            samples = np.asarray(audio, dtype=np.float32)
+        prefix = None
+        if language is not None or isinstance(text_or_ids, str):
+            if self.tokenizer is None:
+                raise Q3aError("scoring text or forcing a language needs tokenizer.json (src/inference.rs:246-251)")
+            if language is None:
+                raise Q3aError("score: a text transcript needs `language` (the ids after a free-running prompt start with the language the model detects)")
+            prefix = self.tokenizer.encode("language " + capitalize_first(language))
+        if isinstance(text_or_ids, str):
+            ids = [int(t) for t in self.tokenizer.encode("<asr_text>" + text_or_ids)]
+        else:
+            ids = [int(t) for t in text_or_ids]
+        if eos:
+            ids = ids + [EOS_TOKEN_IDS[1]]
+        lp, top, top_lp = self.engine.score_batch([samples], [ids], prefix)[0]
+        return ScoreResult(ids, [float(v) for v in lp], float(np.mean(lp, dtype=np.float64)) if len(lp) else None,
+                           [int(t) for t in top], [float(v) for v in top_lp])
 
 
 class ForcedAligner:
