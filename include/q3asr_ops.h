@@ -56,6 +56,7 @@ int32_t q3a_op_arange(q3a_array** out, int64_t start, int64_t end, int32_t devic
 int32_t q3a_op_arange_f(q3a_array** out, double start, double end, double step, int32_t dtype, int32_t device);         /* :191 */
 int32_t q3a_op_cat(q3a_array** out, const q3a_array* const* tensors, int32_t n, int64_t dim, q3a_stream* s);            /* :199 */
 int32_t q3a_op_stack(q3a_array** out, const q3a_array* const* tensors, int32_t n, int64_t dim, q3a_stream* s);          /* :204 */
+/* embedding: every index must lie in [0, weight.shape[0]); the device does not check it (an index outside reads outside the table) */
 int32_t q3a_op_embedding(q3a_array** out, const q3a_array* weight, const q3a_array* indices, q3a_stream* s);            /* :209 */
 int32_t q3a_op_hann_window(q3a_array** out, int64_t size, int32_t device);                                               /* :215 (periodic, F32) */
 

@@ -5,6 +5,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <stdexcept>
+#include <string>
+
 #include "dev.h"
 #include "ops.h"
 
@@ -101,12 +104,16 @@ __global__ void unary_kernel(float* out, const float* in, long n, int op, float 
       case U_EXP: r = expf(x); break;
       case U_GELU: r = gelu_erf(x); break;
       case U_SILU: r = silu_f(x); break;
-      case U_CLAMP_MIN: r = (x != x) ? x : fmaxf(x, p); break;
+      case U_CLAMP_MIN: r = (x != x || p != p) ? (x + p) : fmaxf(x, p); break;  // torch.clamp_min propagates NaN from either side
       case U_ADD_S: r = x + p; break;
       case U_SUB_S: r = x - p; break;
       case U_MUL_S: r = x * p; break;
       case U_DIV_S: r = x / p; break;
-      default: r = powf(x, p); break;
+      default:  // pow with a scalar exponent: ATen's CPU kernel takes these exponents out of pow(), which decides pow(-0, 0.5) = -0 and
+                // pow(-inf, 0.5) = NaN (sqrt) where powf gives +0 and +inf
+        r = p == 2.f ? x * x : p == 3.f ? x * x * x : p == 0.5f ? sqrtf(x) : p == -0.5f ? 1.0f / sqrtf(x) : p == -1.f ? 1.0f / x
+          : p == -2.f ? 1.0f / (x * x) : powf(x, p);
+        break;
     }
     out[i] = r;
   }
@@ -129,7 +136,6 @@ struct DenseTiles {
   const float* a; const float* b; int M, N, K, tb;
   __device__ __forceinline__ float A(int m, int k) const { return (m < M && k < K) ? a[(long)m * K + k] : 0.f; }
   __device__ __forceinline__ float B(int k, int n) const { return (k < K && n < N) ? (tb ? b[(long)n * K + k] : b[(long)k * N + n]) : 0.f; }
-  __device__ __forceinline__ float init(int) const { return 0.f; }
   __device__ __forceinline__ void store(float* c, int m, int n, float v) const { if (m < M && n < N) c[(long)m * N + n] = v; }
 };
 template <class T>
@@ -138,11 +144,8 @@ __device__ __forceinline__ void mfma_tile_f32(const T& t, float* c, int K, bool 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
   const int m0 = blockIdx.x * MT, n0 = blockIdx.y * MT;  // rows on x: the long dimension (implicit-GEMM convolutions)
   f32x16_t acc;
-  {
-    const float v0 = t.init(n0 + wn * 32 + (lane & 31));  // (bias of the output column: the accumulator starts there)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = v0;
-  }
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   for (int k0 = 0; k0 < K; k0 += MK) {
 #pragma unroll
     for (int i = 0; i < MT * MK / 256; ++i) {
@@ -223,7 +226,15 @@ __global__ __launch_bounds__(256) void mean_rows_kernel(float* out, const float*
   if (threadIdx.x == 0) out[blockIdx.x] = ((red[0] + red[1]) + (red[2] + red[3])) / (float)D;
 }
 
-// row max / argmax (first index on ties, NaN treated as larger than everything like torch): one workgroup per row
+// (v, i) beats (best, bi): NaN is larger than everything (torch), the lowest index wins among NaNs and among equal values
+__device__ __forceinline__ bool arg_beats(float v, int i, float best, int bi) {
+  const bool vn = v != v, bn = best != best;
+  if (vn || bn) return vn && (!bn || i < bi);
+  return v > best || (v == best && i < bi);
+}
+// row max / argmax (first index on ties, the first NaN when there is one): one workgroup per row.  The same rule orders the
+// per-thread scan, the shuffle merge and the cross-wave merge; lanes without an element hold (-inf, INT_MAX) and lose to any
+// real element, an all -inf row included.
 __global__ __launch_bounds__(256) void argmax_rows_kernel(long long* idx_out, float* val_out, const float* in, int D) {
   __shared__ float bv[4];
   __shared__ int bi[4];
@@ -232,19 +243,19 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(long long* idx_out, fl
   int bidx = 0x7fffffff;
   for (int i = threadIdx.x; i < D; i += 256) {
     const float v = x[i];
-    if (bidx == 0x7fffffff || v > best) { best = v; bidx = i; }  // i increases: strict > keeps the first index
+    if (arg_beats(v, i, best, bidx)) { best = v; bidx = i; }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float ov = __shfl_xor(best, o, 64);
     const int oi = __shfl_xor(bidx, o, 64);
-    if (ov > best || (ov == best && oi < bidx)) { best = ov; bidx = oi; }
+    if (arg_beats(ov, oi, best, bidx)) { best = ov; bidx = oi; }
   }
   if ((threadIdx.x & 63) == 0) { bv[threadIdx.x >> 6] = best; bi[threadIdx.x >> 6] = bidx; }
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int w = 1; w < 4; ++w)
-      if (bv[w] > best || (bv[w] == best && bi[w] < bidx)) { best = bv[w]; bidx = bi[w]; }
+      if (arg_beats(bv[w], bi[w], best, bidx)) { best = bv[w]; bidx = bi[w]; }
     if (idx_out) idx_out[blockIdx.x] = bidx == 0x7fffffff ? 0 : bidx;
     if (val_out) val_out[blockIdx.x] = best;
   }
@@ -277,7 +288,8 @@ __global__ void reflect_pad_kernel(float* out, const float* in, long rows, long 
 
 // NCHW convolution, groups == 1, as an implicit GEMM on the tile body above: row m = (image, oh, ow), column = output
 // channel, k = (ci, kh, kw) ascending -- the summation order of a direct loop nest; padded taps contribute exact zeros and
-// the accumulator starts at the bias.
+// the bias is added once to the finished sum (as ATen does), so the result is the matmul of the im2col matrix, plus bias: a
+// bias carried through the K additions would pay K roundings of its own size.
 struct ConvTiles {
   const float* in; const float* w; const float* bias; ConvDims d; int M, K;
   __device__ __forceinline__ float A(int m, int k) const {
@@ -289,11 +301,10 @@ struct ConvTiles {
     return in[(((long)n * d.Ci + ci) * d.H + ih) * d.W + iw];
   }
   __device__ __forceinline__ float B(int k, int co) const { return (k < K && co < d.Co) ? w[(long)co * K + k] : 0.f; }
-  __device__ __forceinline__ float init(int co) const { return (bias && co < d.Co) ? bias[co] : 0.f; }
   __device__ __forceinline__ void store(float* out, int m, int co, float v) const {
     if (m >= M || co >= d.Co) return;
     const int ow = m % d.OW, oh = (m / d.OW) % d.OH, n = m / (d.OW * d.OH);
-    out[(((long)n * d.Co + co) * d.OH + oh) * d.OW + ow] = v;
+    out[(((long)n * d.Co + co) * d.OH + oh) * d.OW + ow] = bias ? v + bias[co] : v;
   }
 };
 __global__ __launch_bounds__(256) void conv2d_kernel(float* out, const float* in, const float* w, const float* bias, ConvDims d) {
@@ -321,6 +332,17 @@ __global__ __launch_bounds__(256) void stft_kernel(float2* out, const float* x, 
   }
 }
 
+// a configuration the runtime rejects (grid or LDS beyond the device's limits) must not pass as success with an unwritten output
+inline void launched(const char* what) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": kernel launch failed: " + hipGetErrorString(e));
+}
+inline int device_attr(hipDeviceAttribute_t a) {
+  int dev = 0, v = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, a, dev) != hipSuccess) throw std::runtime_error("cannot read the device's limits");
+  return v;
+}
+
 inline int grid_for(long n) {
   long b = (n + 255) / 256;
   return (int)(b < 1 ? 1 : (b > 16384 ? 16384 : b));
@@ -331,68 +353,91 @@ inline int grid_for(long n) {
 void k_copy_view(void* dst, int ddt, const View& dv, const void* src, int sdt, const View& sv, long n, hipStream_t s) {
   if (n <= 0) return;
   hipLaunchKernelGGL(copy_view_kernel, dim3(grid_for(n)), dim3(256), 0, s, dst, ddt, dv, src, sdt, sv, n, dtype_size(ddt));
+  launched("copy");
 }
 void k_fill(void* dst, int dt, const View& dv, long n, double val, hipStream_t s) {
   if (n <= 0) return;
   hipLaunchKernelGGL(fill_kernel, dim3(grid_for(n)), dim3(256), 0, s, dst, dt, dv, n, val);
+  launched("fill");
 }
 void k_arange(void* dst, int dt, long n, double start, double step, hipStream_t s) {
   if (n <= 0) return;
   hipLaunchKernelGGL(arange_kernel, dim3(grid_for(n)), dim3(256), 0, s, dst, dt, n, start, step);
+  launched("arange");
 }
 void k_binary(float* out, const float* a, const View& av, const float* b, const View& bv, long n, int op, hipStream_t s) {
   if (n <= 0) return;
   hipLaunchKernelGGL(binary_kernel, dim3(grid_for(n)), dim3(256), 0, s, out, a, av, b, bv, n, op);
+  launched("binary op");
 }
 void k_unary(float* out, const float* in, long n, int op, float p, hipStream_t s) {
   if (n <= 0) return;
   hipLaunchKernelGGL(unary_kernel, dim3(grid_for(n)), dim3(256), 0, s, out, in, n, op, p);
+  launched("unary op");
 }
 void k_complex_abs(float* out, const void* in, long n, hipStream_t s) {
   if (n <= 0) return;
   hipLaunchKernelGGL(complex_abs_kernel, dim3(grid_for(n)), dim3(256), 0, s, out, reinterpret_cast<const float2*>(in), n);
+  launched("abs");
 }
 void k_matmul(float* C, const float* A, const float* B, int batch, int M, int N, int K, long sa, long sb, bool b_transposed, hipStream_t s) {
   if (batch <= 0 || M <= 0 || N <= 0) return;
-  hipLaunchKernelGGL(matmul_kernel, dim3((M + MT - 1) / MT, (N + MT - 1) / MT, batch), dim3(256), 0, s, C, A, B, M, N, K, sa, sb, b_transposed ? 1 : 0);
+  // the batch rides on gridDim.z, which the device bounds (65 535 or 65 536): larger batches go in several launches
+  const int zmax = device_attr(hipDeviceAttributeMaxGridDimZ);
+  for (int b0 = 0; b0 < batch; b0 += zmax) {
+    const int nb = batch - b0 < zmax ? batch - b0 : zmax;
+    hipLaunchKernelGGL(matmul_kernel, dim3((M + MT - 1) / MT, (N + MT - 1) / MT, nb), dim3(256), 0, s, C + (long)b0 * M * N, A + (long)b0 * sa,
+                       B + (long)b0 * sb, M, N, K, sa, sb, b_transposed ? 1 : 0);
+    launched("matmul");
+  }
 }
 void k_softmax_rows(float* out, const float* in, long rows, int D, hipStream_t s) {
   if (rows <= 0) return;
   hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)rows), dim3(256), 0, s, out, in, D);
+  launched("softmax");
 }
 void k_layernorm_rows(float* out, const float* in, const float* w, const float* b, long rows, int D, float eps, hipStream_t s) {
   if (rows <= 0) return;
   hipLaunchKernelGGL(layernorm_rows_kernel, dim3((unsigned)rows), dim3(256), 0, s, out, in, w, b, D, eps);
+  launched("layer_norm");
 }
 void k_mean_rows(float* out, const float* in, long rows, int D, hipStream_t s) {
   if (rows <= 0) return;
   hipLaunchKernelGGL(mean_rows_kernel, dim3((unsigned)rows), dim3(256), 0, s, out, in, D);
+  launched("mean_dim");
 }
 void k_argmax_rows(long long* idx_out, float* val_out, const float* in, long rows, int D, hipStream_t s) {
   if (rows <= 0) return;
   hipLaunchKernelGGL(argmax_rows_kernel, dim3((unsigned)rows), dim3(256), 0, s, idx_out, val_out, in, D);
+  launched("argmax");
 }
 void k_triu(float* out, const float* in, long n, int R, int C, long diag, hipStream_t s) {
   if (n <= 0) return;
   hipLaunchKernelGGL(triu_kernel, dim3(grid_for(n)), dim3(256), 0, s, out, in, n, R, C, diag);
+  launched("triu");
 }
 void k_embedding(float* out, const float* w, const long long* idx, long n_idx, int D, hipStream_t s) {
   if (n_idx <= 0) return;
   hipLaunchKernelGGL(embedding_kernel, dim3(grid_for(n_idx * D)), dim3(256), 0, s, out, w, idx, n_idx, D);
+  launched("embedding");
 }
 void k_reflect_pad(float* out, const float* in, long rows, long n, long pl, long pr, hipStream_t s) {
   hipLaunchKernelGGL(reflect_pad_kernel, dim3(grid_for(rows * (n + pl + pr))), dim3(256), 0, s, out, in, rows, n, pl, pr);
+  launched("reflection_pad1d");
 }
 void k_conv2d(float* out, const float* in, const float* w, const float* bias, const ConvDims& d, hipStream_t s) {
   const long rows = (long)d.N * d.OH * d.OW;
   if (rows <= 0 || d.Co <= 0) return;
   hipLaunchKernelGGL(conv2d_kernel, dim3((unsigned)((rows + MT - 1) / MT), (d.Co + MT - 1) / MT), dim3(256), 0, s, out, in, w, bias, d);
+  launched("conv2d");
 }
+long k_stft_max_n_fft() { return device_attr(hipDeviceAttributeMaxSharedMemoryPerBlock) / (long)sizeof(float); }
 void k_stft(void* out, const float* x, const float* win, const float* ct, const float* st, int n_fft, int hop, int n_frames,
             int n_freq, float scale, hipStream_t s) {
   if (n_frames <= 0) return;
   hipLaunchKernelGGL(stft_kernel, dim3(n_frames), dim3(256), n_fft * sizeof(float), s, reinterpret_cast<float2*>(out), x, win, ct, st,
                      n_fft, hop, n_frames, n_freq, scale);
+  launched("stft");
 }
 
 }  // namespace ops

@@ -745,7 +745,8 @@ int32_t q3a_op_mean_dim(q3a_array** out, const q3a_array* a, const int64_t* dims
   pv->v = p;
   std::unique_ptr<A> x(pv->dtype == DT_F32 && is_contig(pv.get()) ? new A(*pv) : materialize(pv.get(), DT_F32));
   std::unique_ptr<A> r(make(oshape, DT_F32, a->device));
-  k_mean_rows(fpw(r.get()), fp(x.get()), D ? a->numel() / D : 0, (int)D, sd(a));
+  if (D == 0) k_fill(r->base(), DT_F32, r->v, r->numel(), NAN, sd(a));  // the mean of nothing is NaN (torch), not an unwritten array
+  else k_mean_rows(fpw(r.get()), fp(x.get()), a->numel() / D, (int)D, sd(a));
   ret(out, r.release());
   OPS_CATCH
 }
@@ -869,6 +870,12 @@ int32_t q3a_op_stft(q3a_array** out, const q3a_array* a, int64_t n_fft, int64_t 
   if (win_length != n_fft || !window || window->numel() != n_fft) die("stft: win_length must equal n_fft and a window is required");
   auto x = f32c(a, "stft");
   auto w = f32c(window, "stft");
+  if (n_fft < 1 || hop < 1) die("stft: n_fft and hop_length must be positive");
+  {  // the kernel keeps one windowed frame in LDS: refuse what the device cannot hold before any table is built or kernel launched
+    sd(a);
+    const long lim = k_stft_max_n_fft();
+    if (n_fft > lim) die("stft: n_fft " + std::to_string(n_fft) + " exceeds the " + std::to_string(lim) + " samples one workgroup's LDS holds on this device");
+  }
   const long L = a->v.shape[0];
   if (L < n_fft) die("stft: input shorter than n_fft");
   const int n_frames = (int)(1 + (L - n_fft) / hop), n_freq = onesided ? (int)(n_fft / 2 + 1) : (int)n_fft;
@@ -934,7 +941,8 @@ int32_t q3a_op_to_device(q3a_array** out, const q3a_array* a, int32_t device, q3
   ret(out, r.release());
   OPS_CATCH
 }
-static double element_as_double(const q3a_array* a, const int64_t* indices, int32_t n) {
+// the bytes of one element (synchronises the device's stream)
+static void element_bytes(const q3a_array* a, const int64_t* indices, int32_t n, uint8_t buf[8]) {
   if (n != a->v.nd) die("value(): one index per dimension expected");
   long off = a->v.offset;
   for (int d = 0; d < n; ++d) {
@@ -943,13 +951,16 @@ static double element_as_double(const q3a_array* a, const int64_t* indices, int3
     if (i < 0 || i >= a->v.shape[d]) die("value(): index out of range");
     off += i * a->v.stride[d];
   }
-  uint8_t buf[8] = {0};
   const int es = dtype_size(a->dtype);
   if (a->device == Q3A_CPU) memcpy(buf, (const uint8_t*)a->base() + (size_t)off * es, es);
   else {
     OHIP(hipStreamSynchronize(sd(a)));
     OHIP(hipMemcpy(buf, (const uint8_t*)a->base() + (size_t)off * es, es, hipMemcpyDeviceToHost));
   }
+}
+static double element_as_double(const q3a_array* a, const int64_t* indices, int32_t n) {
+  uint8_t buf[8] = {0};
+  element_bytes(a, indices, n, buf);
   switch (a->dtype) {
     case DT_F32: { float f; memcpy(&f, buf, 4); return f; }
     case DT_I64: { int64_t v; memcpy(&v, buf, 8); return (double)v; }
@@ -961,12 +972,12 @@ static double element_as_double(const q3a_array* a, const int64_t* indices, int3
 }
 int32_t q3a_array_int64_value(const q3a_array* a, const int64_t* indices, int32_t n, int64_t* value) {
   OPS_TRY
-  if (a->dtype == DT_I64) {  // exact for the whole int64 range
-    q3a_array* e = nullptr;
-    const double d = element_as_double(a, indices, n);
-    (void)e;
-    *value = (int64_t)d;
-    if (std::fabs(d) > 9007199254740992.0) die("int64_value: magnitude beyond 2^53 is not supported");
+  if (a->dtype == DT_I64) {  // the stored bits: exact over the whole int64 range
+    uint8_t buf[8] = {0};
+    element_bytes(a, indices, n, buf);
+    int64_t v;
+    memcpy(&v, buf, 8);
+    *value = v;
   } else {
     *value = (int64_t)element_as_double(a, indices, n);
   }

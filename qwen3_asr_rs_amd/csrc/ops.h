@@ -38,6 +38,7 @@ void k_triu(float* out, const float* in, long n, int R, int C, long diag, hipStr
 void k_embedding(float* out, const float* w, const long long* idx, long n_idx, int D, hipStream_t s);
 void k_reflect_pad(float* out, const float* in, long rows, long n, long pl, long pr, hipStream_t s);
 void k_conv2d(float* out, const float* in, const float* w, const float* bias, const ConvDims& d, hipStream_t s);
+long k_stft_max_n_fft();  // the longest frame one workgroup can hold in LDS on the current device
 void k_stft(void* out, const float* x, const float* win, const float* ct, const float* st, int n_fft, int hop, int n_frames, int n_freq,
             float scale, hipStream_t s);
 
