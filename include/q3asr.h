@@ -243,7 +243,9 @@ int32_t q3a_measure_peaks(int32_t device, int32_t reps, q3a_peaks* out);
  * *actual receives the tap size. Names: mel conv1 conv2 conv3 enc_in enc_layer0 enc_last
  * audio_embeds dec_embed dec_layer0 dec_last_hidden logits lm_head_bound ([vocab][2] fp32: approximate logit and its error bound
  * of the pruned one-sequence argmax, written next to the stored logits).  "lm_head_prune_stats" (int32[2]: 16-row blocks rescored
- * by the pruned argmax, its launches; cumulative over the engine's life) is readable without debug taps. */
+ * by the pruned argmax, its launches; cumulative over the engine's life) and "device_bytes" (uint64: bytes of device memory the
+ * workspace buffers of ALL engines of the process hold right now -- tables, activations, KV caches, the int8 lm_head copy, taps; not
+ * the weight arenas) are readable without debug taps. */
 int32_t q3a_debug_read(q3a_engine* e, const char* name, void* dst, uint64_t bytes, uint64_t* actual);
 
 /* ---- pipeline shell: host-only helpers around the hot path -------------- */

@@ -57,22 +57,29 @@ constexpr int kAudioPad = 151676, kEos0 = 151643, kEos1 = 151645;  // src/tokeni
 // sequences on the skinny path.
 constexpr int kGemvMaxSeq = 2;
 
+// bytes of device memory all DevBufs of the process hold right now (q3a_debug_read "device_bytes")
+std::atomic<uint64_t> g_device_bytes{0};
+
+// One device allocation and its owner, move-only: freed when it goes out of scope (engine members, taps, locals of the selftests)
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
   bool grew = false;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept { *this = std::move(o); }
+  DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); std::swap(grew, o.grew); return *this; }  // (o frees what this held)
+  ~DevBuf() { release(); }
   void ensure(size_t bytes) {
     if (bytes <= cap) return;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
+    release();
     size_t want = (bytes + 255) & ~size_t(255);
     HIPCHK(hipMalloc(&p, want));
     cap = want;
+    g_device_bytes += want;
     grew = true;
   }
   void release() {
-    if (p) (void)hipFree(p);
+    if (p) { (void)hipFree(p); g_device_bytes -= cap; }
     p = nullptr;
     cap = 0;
   }
@@ -91,31 +98,56 @@ struct ProfEvent {
   hipEvent_t a, b;
 };
 
+// Prompts of B utterances as setup_prompts takes them: (ids concatenated, lens[B]).  build(s, dst) returns the length of utterance
+// s's prompt and, when dst is not null, writes it there (the shape of q3a_build_prompt / q3a_build_align_prompt).
+template <class Build>
+std::pair<std::vector<int32_t>, std::vector<int32_t>> concat_prompts(int B, Build&& build) {
+  std::vector<int32_t> ids, lens(B);
+  for (int s = 0; s < B; ++s) {
+    lens[s] = build(s, nullptr);
+    const size_t o = ids.size();
+    ids.resize(o + lens[s]);
+    build(s, ids.data() + o);
+  }
+  return {std::move(ids), std::move(lens)};
+}
+
+void require_utterance_ptrs(const char* what, const float* const* ptrs, int B) {
+  for (int u = 0; u < B; ++u)
+    if (!ptrs[u]) fail(std::string(what) + ": null utterance pointer");
+}
+
 }  // namespace
 
 namespace q3a {
 void set_thread_error(const std::string& msg) { g_last_error = msg; }  // used by host_abi.cpp
 }  // namespace q3a
-// A/B knobs (kernels.h Knobs): read from the environment exactly once, atomics afterwards (q3a_debug_set writes them while
-// q3a_group_transcribe may have one host thread per GPU reading them)
+// A/B knobs (kernels.h Knobs: defaults and what each one does).  ONE table names them: q3a_debug_set looks its key up here, and
+// knobs() reads the environment names exactly once (atomics afterwards: q3a_debug_set writes them while q3a_group_transcribe may
+// have one host thread per GPU reading them).  include/q3asr.h documents the keys; tests/test_host.py compares the two.
 namespace q3a {
+struct KnobEntry { const char* key; const char* env; std::atomic<int> Knobs::*field; };  // env null: no environment name
+static const KnobEntry kKnobTable[] = {
+    {"gemm256_min_tiles", "Q3A_GEMM256_MIN_TILES", &Knobs::gemm256_min_tiles},
+    {"gemm256_persist", "Q3A_GEMM256_PERSIST", &Knobs::gemm256_persist},
+    {"gemm256_group_m", "Q3A_GEMM256_GROUP_M", &Knobs::gemm256_group_m},
+    {"dattn_batched_min_wgs", "Q3A_DATTN_BATCHED_MIN_WGS", &Knobs::dattn_batched_min_wgs},
+    {"decode_group_size", "Q3A_DECODE_GROUP", &Knobs::decode_group_size},
+    {"decode_parallel_groups", "Q3A_DECODE_PARALLEL", &Knobs::decode_parallel_groups},
+    {"fuse_qkrope", "Q3A_FUSE_QKROPE", &Knobs::fuse_qkrope},
+    {"skinny_q", "Q3A_SKINNY_Q", &Knobs::skinny_q},
+    {"eos_run_ahead", "Q3A_EOS_RUN_AHEAD", &Knobs::eos_run_ahead},
+    {"skinny_glu_hp3", "Q3A_SKINNY_GLU_HP3", &Knobs::skinny_glu_hp3},
+    {"lm_head_prune", "Q3A_LM_HEAD_PRUNE", &Knobs::lm_head_prune},
+    {"layer_taps", "Q3A_DEBUG_LAYER_TAPS", &Knobs::layer_taps},
+    {"poison_attn_partials", nullptr, &Knobs::poison_attn_partials},
+};
 Knobs& knobs() {
   static Knobs k;
   static std::once_flag once;
   std::call_once(once, [] {
-    auto env = [](const char* name, std::atomic<int>& dst) { if (const char* e = getenv(name)) dst.store(atoi(e)); };
-    env("Q3A_GEMM256_MIN_TILES", k.gemm256_min_tiles);
-    env("Q3A_GEMM256_PERSIST", k.gemm256_persist);
-    env("Q3A_GEMM256_GROUP_M", k.gemm256_group_m);
-    env("Q3A_DATTN_BATCHED_MIN_WGS", k.dattn_batched_min_wgs);
-    env("Q3A_DECODE_GROUP", k.decode_group_size);
-    env("Q3A_DECODE_PARALLEL", k.decode_parallel_groups);
-    env("Q3A_FUSE_QKROPE", k.fuse_qkrope);
-    env("Q3A_SKINNY_Q", k.skinny_q);
-    env("Q3A_EOS_RUN_AHEAD", k.eos_run_ahead);
-    env("Q3A_SKINNY_GLU_HP3", k.skinny_glu_hp3);
-    env("Q3A_LM_HEAD_PRUNE", k.lm_head_prune);
-    env("Q3A_DEBUG_LAYER_TAPS", k.layer_taps);
+    for (const KnobEntry& t : kKnobTable)
+      if (const char* e = t.env ? getenv(t.env) : nullptr) (k.*t.field).store(atoi(e));
   });
   return k;
 }
@@ -219,6 +251,9 @@ struct q3a_engine {
   // GEMM-input activations (conv maps, norm outputs, attention context, FFN hidden) are stored as bf16 in the default
   // mode -- exactly the values the MFMA consumes -- and as fp32 in the precise mode (hi+lo split inside the GEMM)
   size_t act_elem() const { return precise() ? 4 : 2; }
+  int fast_math() const { return precise() ? 0 : 1; }  // GemvArgs / SkinnyArgs::fast_math, the merge's fast exp
+  // the fp32 VALU attention (precise mode / opts.valu_attention) writes an fp32 context that is rounded afterwards
+  bool valu_attn() const { return precise() || opts.valu_attention; }
   template <typename T> const T* w(uint64_t off) const { return reinterpret_cast<const T*>(arena + off); }
   const float* wf(uint64_t off) const { return w<float>(off); }
   const uint16_t* wh(uint64_t off) const { return w<uint16_t>(off); }
@@ -272,6 +307,8 @@ struct q3a_engine {
     HIPCHK(hipEventRecord(pe.b, stream));
     prof->push_back(pe);
   }
+  // milliseconds between two of the stage events: ev[0] mel, ev[1] encoder, ev[2] prefill, ev[3] decode / head, ev[4] end
+  float stage_ms(int i, int j) { float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, ev[i], ev[j])); return ms; }
 
   // =====================================================================================
   void init_common(const std::string& model_dir, int dev, const q3a_opts* o) {
@@ -560,13 +597,11 @@ struct q3a_engine {
     conv2.ensure(nch * H2 * W2 * C * ae);
     conv3.ensure(nch * H3 * W3 * C * ae);
     const size_t Tt = (size_t)total_T;
-    // the fp32 VALU attention (precise mode / opts.valu_attention) writes an fp32 context that is rounded afterwards
-    const bool valu_attn = sp || opts.valu_attention;
     // the MFMA attention consumes q/k/v as bf16: the qkv GEMM then stores exactly those values (half the bytes)
-    const bool qkv16 = !valu_attn;
+    const bool qkv16 = !valu_attn();
     enc_x.ensure(Tt * D * 4); enc_ln.ensure(Tt * D * ae); enc_qkv.ensure(Tt * 3 * D * (qkv16 ? 2 : 4));
-    enc_ctx.ensure(Tt * D * (valu_attn ? 4 : ae));
-    if (valu_attn && !sp) enc_ctx16.ensure(Tt * D * 2);
+    enc_ctx.ensure(Tt * D * (valu_attn() ? 4 : ae));
+    if (valu_attn() && !sp) enc_ctx16.ensure(Tt * D * 2);
     enc_ffn.ensure(Tt * Fn * ae); audio_embeds.ensure(Tt * d.enc_out * 4);
 
     ChunkTable ct{d_chunk_utt.as<int>(), d_chunk_frame0.as<int>()};
@@ -602,10 +637,10 @@ struct q3a_engine {
       at.k = enc_qkv.as<uint16_t>() + D; at.v = enc_qkv.as<uint16_t>() + 2 * D;
     }
     at.o = enc_ctx.as<float>(); at.o_rs = D;
-    at.o16 = valu_attn ? nullptr : enc_ctx.as<uint16_t>();
+    at.o16 = valu_attn() ? nullptr : enc_ctx.as<uint16_t>();
     at.segs = enc_segs.as<AttnSeg>(); at.n_segs = (int)enc_segs_h.size(); at.max_len = enc_max_seg;
     at.n_kv_heads = d.enc_heads; at.scale_div = 8.0f;  // sqrt(64), layers.rs:161
-    const DevBuf& ctx_in = (valu_attn && !sp) ? enc_ctx16 : enc_ctx;  // what the out projection reads
+    const DevBuf& ctx_in = (valu_attn() && !sp) ? enc_ctx16 : enc_ctx;  // what the out projection reads
     for (int li = 0; li < d.enc_layers; ++li) {
       const EncLayerOff& e = L.enc[li];
       KCHK(launch_layernorm(enc_x.as<float>(), wf(e.ln1_w), wf(e.ln1_b), enc_ln.as<float>(), total_T, D, 1e-5f, stream, act16(enc_ln)));
@@ -614,7 +649,7 @@ struct q3a_engine {
         if (qkv16) ep.out16 = enc_qkv.as<uint16_t>(); else ep.out = enc_qkv.as<float>();
         act_gemm(enc_ln, D, wh(e.qkv_w), total_T, 3 * D, D, ep, false);
       }
-      if (valu_attn) {
+      if (valu_attn()) {
         KCHK(launch_attn_enc(at, stream));
         if (!sp) KCHK(launch_to_bf16(enc_ctx.as<float>(), enc_ctx16.as<uint16_t>(), Tt * D, stream));
       } else {
@@ -710,11 +745,10 @@ struct q3a_engine {
     upload(dec_segs, segs, stream);
     upload(d_pos, P, stream);
     const size_t Pt = (size_t)total_P, H = d.hidden;
-    const bool valu_attn = kv_f32() || opts.valu_attention;
     dec_x.ensure(Pt * H * 4); dec_ln.ensure(Pt * H * act_elem()); dec_qkv.ensure(Pt * d.qkv_dim() * 4);
-    dec_ctx.ensure(Pt * d.q_dim() * (valu_attn ? 4 : act_elem())); dec_act.ensure(Pt * d.inter * act_elem());
-    if (!valu_attn) dec_q16.ensure(Pt * d.q_dim() * 2);  // q after QK-norm + RoPE as bf16 for the MFMA prefill attention
-    if (valu_attn && !precise()) dec_ctx16.ensure(Pt * d.q_dim() * 2);
+    dec_ctx.ensure(Pt * d.q_dim() * (valu_attn() ? 4 : act_elem())); dec_act.ensure(Pt * d.inter * act_elem());
+    if (!valu_attn()) dec_q16.ensure(Pt * d.q_dim() * 2);  // q after QK-norm + RoPE as bf16 for the MFMA prefill attention
+    if (valu_attn() && !precise()) dec_ctx16.ensure(Pt * d.q_dim() * 2);
     kv_layer_elems = (size_t)b * d.n_kv * max_ctx * 128;
     kcache.ensure(kv_layer_elems * d.dec_layers * kv_elem());
     vcache.ensure(kv_layer_elems * d.dec_layers * kv_elem());
@@ -806,7 +840,7 @@ struct q3a_engine {
     const ArgmaxPartials part{part_val.as<float>(), part_idx.as<int>(), token_lp() ? part_sum.as<float>() : nullptr, part_stride};
     if (S <= kGemvMaxSeq) {
       GemvArgs g{};
-      g.fast_math = precise() ? 0 : 1;
+      g.fast_math = fast_math();
       g.x = x_dec.as<float>(); g.ldx = H; g.rms_w = wf(L.final_norm); g.eps = d.rms_eps;
       g.W = wh(L.lm_head); g.N = V; g.K = H; g.mode = 3; g.out = logits.as<float>(); g.ldo = V;
       g.part = part;
@@ -890,16 +924,14 @@ struct q3a_engine {
     at.o = dec_ctx.as<float>(); at.o_rs = QD; at.segs = dec_segs.as<AttnSeg>(); at.n_segs = B;
     at.max_len = *std::max_element(P.begin(), P.end()); at.n_kv_heads = d.n_kv;
     at.scale_div = sqrtf((float)d.head_dim);  // layers.rs:327-328
-    const bool valu_attn = kv_f32() || opts.valu_attention;
-    at.o16 = valu_attn ? nullptr : dec_ctx.as<uint16_t>();
-    if (!valu_attn) { at.q16 = dec_q16.as<uint16_t>(); at.q_rs = QD; }  // the rope kernel leaves q as bf16 [rows][QD]
-    const DevBuf& ctx_in = (valu_attn && !sp) ? dec_ctx16 : dec_ctx;  // what the o projection reads
+    at.o16 = valu_attn() ? nullptr : dec_ctx.as<uint16_t>();
+    if (!valu_attn()) { at.q16 = dec_q16.as<uint16_t>(); at.q_rs = QD; }  // the rope kernel leaves q as bf16 [rows][QD]
+    const DevBuf& ctx_in = (valu_attn() && !sp) ? dec_ctx16 : dec_ctx;  // what the o projection reads
     const bool qkv_bias = arena_flags & kFlagDecQkvBias, o_bias = arena_flags & kFlagDecOBias, mlp_bias = arena_flags & kFlagDecMlpBias;
-    const bool fuse_rope = knobs().fuse_qkrope.load() != 0 && !valu_attn && !precise() && d.head_dim == 128 && gemm256_eligible(total_P, QKV, H) && H % 64 == 0;
+    const bool fuse_rope = knobs().fuse_qkrope.load() != 0 && !valu_attn() && !precise() && d.head_dim == 128 && gemm256_eligible(total_P, QKV, H) && H % 64 == 0;
     // (debug_taps + layer_taps: raw copies of every prefill layer's intermediate buffers, for bisecting a run-to-run difference
     // to one launch -- tools/bisect_layers.py -- and for checking one launch against a reference on its own input)
     const bool layer_taps = opts.debug_taps && knobs().layer_taps.load() != 0;
-    const size_t act_b = sp ? 4 : 2;  // bytes per activation element (bf16 in the default mode)
     for (int li = 0; li < d.dec_layers; ++li) {
       const DecLayerOff& l = L.dec[li];
       auto ltap = [&](const char* what, const void* ptr, size_t bytes) {
@@ -909,13 +941,13 @@ struct q3a_engine {
         tap(name, ptr, bytes);
       };
       KCHK(launch_rmsnorm(dec_x.as<float>(), wf(l.in_ln), dec_ln.as<float>(), total_P, H, d.rms_eps, stream, act16(dec_ln)));
-      ltap("ln1", dec_ln.p, (size_t)total_P * H * act_b);
+      ltap("ln1", dec_ln.p, (size_t)total_P * H * act_elem());
       RopeKvArgs rk{};
       rk.qkv = dec_qkv.as<float>(); rk.row_seq = row_seq.as<int>(); rk.row_pos = row_pos.as<int>();
       rk.q_norm = wf(l.q_norm); rk.k_norm = wf(l.k_norm); rk.eps = d.rms_eps;
       rk.cos_t = rope_cos.as<float>(); rk.sin_t = rope_sin.as<float>();
       rk.kcache = kc_layer(li); rk.vcache = vc_layer(li); rk.n_q = d.n_q; rk.n_kv = d.n_kv; rk.max_ctx = max_ctx;
-      rk.q16 = valu_attn ? nullptr : dec_q16.as<uint16_t>();
+      rk.q16 = valu_attn() ? nullptr : dec_q16.as<uint16_t>();
       if (fuse_rope) {
         // batch-sized prefill: QK-norm, RoPE and the cache append are the epilogue of the qkv GEMM (k_gemm256.hip)
         KCHK(launch_gemm256_qkrope(dec_ln.as<uint16_t>(), H, wh(l.qkv_w), total_P, H, qkv_bias ? wf(l.qkv_b) : nullptr, rk, stream));
@@ -928,28 +960,28 @@ struct q3a_engine {
       if (fuse_rope) {
         ltap("qkvs", dec_qkv.p, std::min((size_t)1024, (size_t)total_P) * QKV * 4);  // fp32 scratch of the trailing rows (small GEMM -> separate rope kernel)
       }
-      if (!valu_attn) ltap("q", dec_q16.p, (size_t)total_P * QD * 2);  // q after QK-norm + RoPE, bf16 [rows][QD]
+      if (!valu_attn()) ltap("q", dec_q16.p, (size_t)total_P * QD * 2);  // q after QK-norm + RoPE, bf16 [rows][QD]
       ltap("k", kc_layer(li), (size_t)B * d.n_kv * max_ctx * 128 * kv_elem());
       ltap("v", vc_layer(li), (size_t)B * d.n_kv * max_ctx * 128 * kv_elem());
-      if (valu_attn) {
+      if (valu_attn()) {
         KCHK(launch_attn_prefill(at, d.n_q / d.n_kv, kv_f32(), stream));
         if (!sp) KCHK(launch_to_bf16(dec_ctx.as<float>(), dec_ctx16.as<uint16_t>(), (size_t)total_P * QD, stream));
       } else {
         KCHK(launch_fattn_prefill(at, d.n_q / d.n_kv, stream));
       }
-      ltap("attn", ctx_in.p, (size_t)total_P * QD * act_b);
+      ltap("attn", ctx_in.p, (size_t)total_P * QD * act_elem());
       {
         GemmEpilogue ep; ep.out = dec_x.as<float>(); ep.ldo = H; ep.resid = dec_x.as<float>(); ep.bias = o_bias ? wf(l.o_b) : nullptr;
         act_gemm(ctx_in, QD, wh(l.o_w), total_P, H, QD, ep, false);
       }
       ltap("o", dec_x.p, (size_t)total_P * H * 4);
       KCHK(launch_rmsnorm(dec_x.as<float>(), wf(l.post_ln), dec_ln.as<float>(), total_P, H, d.rms_eps, stream, act16(dec_ln)));
-      ltap("ln2", dec_ln.p, (size_t)total_P * H * act_b);
+      ltap("ln2", dec_ln.p, (size_t)total_P * H * act_elem());
       {
         GemmEpilogue ep; act_out(ep, dec_act); ep.ldo = I; ep.bias = mlp_bias ? wf(l.gu_b) : nullptr;
         act_gemm(dec_ln, H, wh(l.gu_w), total_P, 2 * I, H, ep, true);
       }
-      ltap("act", dec_act.p, (size_t)total_P * I * act_b);
+      ltap("act", dec_act.p, (size_t)total_P * I * act_elem());
       {
         GemmEpilogue ep; ep.out = dec_x.as<float>(); ep.ldo = H; ep.resid = dec_x.as<float>(); ep.bias = mlp_bias ? wf(l.down_b) : nullptr;
         act_gemm(dec_act, I, wh(l.down_w), total_P, H, I, ep, false);
@@ -999,18 +1031,17 @@ struct q3a_engine {
     HIPCHK(hipEventRecord(ev[4], stream));
     HIPCHK(hipStreamSynchronize(stream));
     HIPCHK(hipGetLastError());
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, ev[2], ev[4])); timings.prefill_ms = ms;
-    HIPCHK(hipEventElapsedTime(&ms, ev[3], ev[4])); head_ms = ms;
+    timings.prefill_ms = stage_ms(2, 4);
+    head_ms = stage_ms(3, 4);
     timings.decode_ms = 0.f; timings.decode_steps = 0; timings.batch = B; timings.total_audio_tokens = total_T;
     timings.total_prompt_tokens = total_P;
   }
-  // whole-path callers: mel and encoder times of the events upload_ptrs_and_mel / the caller recorded, total = mel through head
-  void head_call_front_timings() {
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1])); timings.mel_ms = ms;
-    HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2])); timings.encoder_ms = ms;
-    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[4])); timings.total_ms = ms;
+  // every whole-path call (transcription, alignment, scoring): mel and encoder times of the events upload_ptrs_and_mel / the caller
+  // recorded, total = ev[0] through ev[4]; the caller adds what its own stages between ev[2] and ev[4] are
+  void front_and_total_timings() {
+    timings.mel_ms = stage_ms(0, 1);
+    timings.encoder_ms = stage_ms(1, 2);
+    timings.total_ms = stage_ms(0, 4);
   }
   // Classes (and logits) to the host, [utterance][stride].
   void run_align(const std::vector<int>& rows, const int32_t* counts, int stride, int32_t* out_classes, float* logits_out) {
@@ -1148,7 +1179,7 @@ struct q3a_engine {
     const int S = B;  // (precise-mode lm_head only)
     if (S <= 32) {
       SkinnyArgs sk{};
-      sk.fast_math = precise() ? 0 : 1;
+      sk.fast_math = fast_math();
       sk.x = x; sk.ldx = ldx; sk.S = S; sk.W = W; sk.N = N; sk.K = K; sk.bias = bias; sk.mode = mode; sk.out = out; sk.ldo = ldo; sk.resid = resid;
       KCHK(launch_skinny(sk, precise(), stream));
     } else {
@@ -1157,13 +1188,43 @@ struct q3a_engine {
     }
   }
 
+  // The four projections of a decoder layer, stated ONCE for every path that launches them (decode_layer's GEMV and skinny forms,
+  // q3a_profile_weight_stream).  A caller starts its kernel arguments from one with gemv_args / skinny_args and sets only what its
+  // path adds: x and out pointers, the norm source, fragment flags, next-norm outputs.
+  struct Proj {
+    const uint16_t* W;  // [N][K] bf16
+    int N, K;
+    const float* bias;  // null: the checkpoint has none (arena flags)
+    int mode;           // GemvArgs / SkinnyArgs::mode: 0 plain, 1 + residual, 2 SiLU(gate) * up of interleaved rows -> N / 2 columns
+    int kclass;         // profile class of its GEMV (the skinny path books every projection as Q3A_KC_GEMM)
+    double bytes;       // weight bytes one launch streams
+  };
+  struct LayerProjs { Proj qkv, o, gu, down; };
+  LayerProjs layer_projs(int li) const {
+    const DecLayerOff& l = L.dec[li];
+    const int H = d.hidden, I = d.inter, QD = d.q_dim(), QKV = d.qkv_dim();
+    auto proj = [&](uint64_t w_off, int N, int K, uint32_t bias_flag, uint64_t b_off, int mode, int kclass) {
+      return Proj{wh(w_off), N, K, (arena_flags & bias_flag) ? wf(b_off) : nullptr, mode, kclass, 2.0 * N * K};
+    };
+    return {proj(l.qkv_w, QKV, H, kFlagDecQkvBias, l.qkv_b, 0, Q3A_KC_GEMV), proj(l.o_w, H, QD, kFlagDecOBias, l.o_b, 1, Q3A_KC_GEMV_O),
+            proj(l.gu_w, 2 * I, H, kFlagDecMlpBias, l.gu_b, 2, Q3A_KC_GEMV), proj(l.down_w, H, I, kFlagDecMlpBias, l.down_b, 1, Q3A_KC_GEMV_DOWN)};
+  }
+  template <class Args> Args proj_args(const Proj& p) const {  // the fields GemvArgs and SkinnyArgs share
+    Args a{};
+    a.fast_math = fast_math(); a.eps = d.rms_eps;  // (eps: read only where a norm source is set)
+    a.W = p.W; a.N = p.N; a.K = p.K; a.ldx = p.K; a.bias = p.bias; a.mode = p.mode; a.ldo = p.mode == 2 ? p.N / 2 : p.N;
+    return a;
+  }
+  GemvArgs gemv_args(const Proj& p) const { return proj_args<GemvArgs>(p); }
+  SkinnyArgs skinny_args(const Proj& p, int S) const { SkinnyArgs k = proj_args<SkinnyArgs>(p); k.S = S; return k; }
+
   // one decoder layer of the greedy-loop iteration (inference.rs:172-197) for sequences [s0, s0 + S) -- the whole batch on
   // the GEMV path, one group of <= 32 on the skinny MFMA path
   void decode_layer(int li, int grp, int s0, int S, hipStream_t ks) {
-    const int H = d.hidden, I = d.inter, QD = d.q_dim(), QKV = d.qkv_dim();
-    const bool qkv_bias = arena_flags & kFlagDecQkvBias, o_bias = arena_flags & kFlagDecOBias, mlp_bias = arena_flags & kFlagDecMlpBias;
+    const int H = d.hidden, QKV = d.qkv_dim();
     const bool gemv = B <= kGemvMaxSeq;
     const DecLayerOff& l = L.dec[li];
+    const LayerProjs pj = layer_projs(li);
     float* const x = x_dec.as<float>() + (size_t)s0 * H;
     float* const qkv = s_qkv.as<float>() + (size_t)s0 * QKV;
     const size_t kv_seq = (size_t)d.n_kv * max_ctx * 128 * kv_elem();  // bytes per sequence and layer
@@ -1176,80 +1237,76 @@ struct q3a_engine {
     da.q_norm = wf(l.q_norm); da.k_norm = wf(l.k_norm);
     da.kcache = (uint8_t*)kc_layer(li) + (size_t)s0 * kv_seq; da.vcache = (uint8_t*)vc_layer(li) + (size_t)s0 * kv_seq;
     if (gemv) {
-      GemvArgs g{};
-      g.fast_math = precise() ? 0 : 1;
-      g.x = x; g.ldx = H; g.rms_w = wf(l.in_ln); g.eps = d.rms_eps; g.W = wh(l.qkv_w); g.N = QKV; g.K = H;
-      g.bias = qkv_bias ? wf(l.qkv_b) : nullptr; g.mode = 0; g.out = qkv; g.ldo = QKV;
-      timed(Q3A_KC_GEMV, 2.0 * QKV * H, [&] { KCHK(launch_gemv(g, S, ks)); });
+      auto run = [&](const Proj& p, const GemvArgs& a) { timed(p.kclass, p.bytes, [&] { KCHK(launch_gemv(a, S, ks)); }); };
+      GemvArgs g = gemv_args(pj.qkv);
+      g.x = x; g.rms_w = wf(l.in_ln); g.out = qkv;
+      run(pj.qkv, g);
       timed(Q3A_KC_DECODE_ATTN, 0, [&] { KCHK(launch_decode_attn(da, S, kv_f32(), ks)); });
-      GemvArgs o{};
-      o.fast_math = precise() ? 0 : 1;
+      GemvArgs o = gemv_args(pj.o);
       if (std::min(S, 4) * d.n_q * live_nsplit_ <= GEMV_ATTN_MAX_TABLE) {  // merge the key splits inside the o_proj GEMV
         o.attn_pm = da.pm; o.attn_pl = da.pl; o.attn_po = da.po;
-        o.attn_nsplit = live_nsplit_; o.attn_heads = d.n_q; o.attn_fast_exp = precise() ? 0 : 1;
+        o.attn_nsplit = live_nsplit_; o.attn_heads = d.n_q; o.attn_fast_exp = fast_math();
       } else {  // very long contexts: separate merge launch
         timed(Q3A_KC_DECODE_ATTN, 0, [&] { KCHK(launch_attn_combine(da.pm, da.pl, da.po, live_nsplit_, S, d.n_q, s_ctx_g(grp), ks)); });
         o.x = s_ctx_g(grp);
       }
-      o.ldx = QD; o.W = wh(l.o_w); o.N = H; o.K = QD; o.bias = o_bias ? wf(l.o_b) : nullptr;
-      o.mode = 1; o.out = x; o.ldo = H; o.resid = x;
-      timed(Q3A_KC_GEMV_O, 2.0 * H * QD, [&] { KCHK(launch_gemv(o, S, ks)); });
-      GemvArgs u{};
-      u.fast_math = precise() ? 0 : 1;
-      u.x = x; u.ldx = H; u.rms_w = wf(l.post_ln); u.eps = d.rms_eps; u.W = wh(l.gu_w); u.N = 2 * I; u.K = H;
-      u.bias = mlp_bias ? wf(l.gu_b) : nullptr; u.mode = 2; u.out = s_act_g(grp); u.ldo = I;
-      timed(Q3A_KC_GEMV, 4.0 * I * H, [&] { KCHK(launch_gemv(u, S, ks)); });
-      GemvArgs dn{};
-      dn.fast_math = precise() ? 0 : 1;
-      dn.x = s_act_g(grp); dn.ldx = I; dn.W = wh(l.down_w); dn.N = H; dn.K = I; dn.bias = mlp_bias ? wf(l.down_b) : nullptr;
-      dn.mode = 1; dn.out = x; dn.ldo = H; dn.resid = x;
-      timed(Q3A_KC_GEMV_DOWN, 2.0 * H * I, [&] { KCHK(launch_gemv(dn, S, ks)); });
+      o.out = x; o.resid = x;
+      run(pj.o, o);
+      GemvArgs u = gemv_args(pj.gu);
+      u.x = x; u.rms_w = wf(l.post_ln); u.out = s_act_g(grp);
+      run(pj.gu, u);
+      GemvArgs dn = gemv_args(pj.down);
+      dn.x = s_act_g(grp); dn.out = x; dn.resid = x;
+      run(pj.down, dn);
       return;
     }
     // skinny MFMA GEMMs: the norms are fused (no norm launches), and in the default mode the two K-heavy projections read
     // bf16 activations written by their producers (attention, SwiGLU epilogue) in fragment order
     const bool b16 = !precise(), pre = prenorm_path();
-    SkinnyArgs q{};
-    q.fast_math = precise() ? 0 : 1;
-    q.x = x; q.ldx = H; q.S = S; q.eps = d.rms_eps; q.W = wh(l.qkv_w); q.N = QKV; q.K = H;
-    if (pre) { q.xw16f = nn_x_g(grp); q.ss_parts = nn_ss_g(grp); q.ss_nparts = nn_parts(); }
-    else q.rms_w = wf(l.in_ln);
-    q.bias = qkv_bias ? wf(l.qkv_b) : nullptr; q.mode = 0; q.out = qkv; q.ldo = QKV;
-    timed(Q3A_KC_GEMM, 2.0 * QKV * H, [&] { KCHK(launch_skinny(q, precise(), ks)); });
+    uint16_t* const s_ctx16 = b16 ? reinterpret_cast<uint16_t*>(s_ctx_g(grp)) : nullptr;
+    uint16_t* const s_act16 = b16 ? reinterpret_cast<uint16_t*>(s_act_g(grp)) : nullptr;
+    auto run = [&](const Proj& p, const SkinnyArgs& a) { timed(Q3A_KC_GEMM, p.bytes, [&] { KCHK(launch_skinny(a, precise(), ks)); }); };
+    // x of a projection that reads the residual stream: pre-normalised by its producer, or normalised in the GEMM by norm_w
+    auto from_residual = [&](SkinnyArgs& a, const float* norm_w) {
+      a.x = x;
+      if (pre) { a.xw16f = nn_x_g(grp); a.ss_parts = nn_ss_g(grp); a.ss_nparts = nn_parts(); }
+      else a.rms_w = norm_w;
+    };
+    // a projection that writes the residual stream: quarter workgroups where the shape allows, and the row pre-normalised by
+    // next_w for the GEMM that reads it next (null: nobody does)
+    auto to_residual = [&](SkinnyArgs& a, const float* next_w) {
+      a.out = x; a.resid = x;
+      a.qsplit = b16 && skinny_q();
+      if (pre && next_w) { a.next_w = next_w; a.next_xw16f = nn_x_g(grp); a.next_ss = nn_ss_g(grp); }
+    };
+    SkinnyArgs q = skinny_args(pj.qkv, S);
+    from_residual(q, wf(l.in_ln));
+    q.out = qkv;
+    run(pj.qkv, q);
     if (S * d.n_kv >= k_dattn_batched_min_wgs) {
       // the group alone fills the chip: one workgroup per (sequence, kv head) walks all keys and writes the context itself
-      if (b16) { da.out16 = reinterpret_cast<uint16_t*>(s_ctx_g(grp)); da.out_frag = 1; } else da.out = s_ctx_g(grp);
+      if (b16) { da.out16 = s_ctx16; da.out_frag = 1; } else da.out = s_ctx_g(grp);
       da.trim_prologue = min_P_ < 2 * 128;  // some sequence is shorter than the kernel's two prologue key tiles
       timed(Q3A_KC_DECODE_ATTN, 0, [&] { KCHK(launch_decode_attn_batched(da, S, kv_f32(), ks)); });
     } else {
       timed(Q3A_KC_DECODE_ATTN, 0, [&] { KCHK(launch_decode_attn(da, S, kv_f32(), ks)); });
-      timed(Q3A_KC_DECODE_ATTN, 0, [&] { KCHK(launch_attn_combine(da.pm, da.pl, da.po, live_nsplit_, S, d.n_q, s_ctx_g(grp), ks, b16 ? reinterpret_cast<uint16_t*>(s_ctx_g(grp)) : nullptr, b16)); });
+      timed(Q3A_KC_DECODE_ATTN, 0, [&] { KCHK(launch_attn_combine(da.pm, da.pl, da.po, live_nsplit_, S, d.n_q, s_ctx_g(grp), ks, s_ctx16, b16)); });
     }
-    SkinnyArgs o{};
-    o.fast_math = precise() ? 0 : 1;
-    o.x = s_ctx_g(grp); o.x16 = b16 ? reinterpret_cast<uint16_t*>(s_ctx_g(grp)) : nullptr; o.x16_frag = b16; o.ldx = QD; o.S = S; o.W = wh(l.o_w); o.N = H; o.K = QD;
-    o.bias = o_bias ? wf(l.o_b) : nullptr; o.mode = 1; o.out = x; o.ldo = H; o.resid = x;
-    if (pre) { o.next_w = wf(l.post_ln); o.next_xw16f = nn_x_g(grp); o.next_ss = nn_ss_g(grp); }
-    o.qsplit = b16 && skinny_q();
-    timed(Q3A_KC_GEMM, 2.0 * H * QD, [&] { KCHK(launch_skinny(o, precise(), ks)); });
-    SkinnyArgs u{};
-    u.fast_math = precise() ? 0 : 1;
-    u.x = x; u.ldx = H; u.S = S; u.eps = d.rms_eps; u.W = wh(l.gu_w); u.N = 2 * I; u.K = H;
-    if (pre) { u.xw16f = nn_x_g(grp); u.ss_parts = nn_ss_g(grp); u.ss_nparts = nn_parts(); }
-    else u.rms_w = wf(l.post_ln);
-    u.bias = mlp_bias ? wf(l.gu_b) : nullptr; u.mode = 2; u.out = s_act_g(grp); u.out16 = b16 ? reinterpret_cast<uint16_t*>(s_act_g(grp)) : nullptr; u.out16_frag = b16; u.ldo = I;
+    SkinnyArgs o = skinny_args(pj.o, S);
+    o.x = s_ctx_g(grp); o.x16 = s_ctx16; o.x16_frag = b16;
+    to_residual(o, wf(l.post_ln));
+    run(pj.o, o);
+    SkinnyArgs u = skinny_args(pj.gu, S);
+    from_residual(u, wf(l.post_ln));
+    u.out = s_act_g(grp); u.out16 = s_act16; u.out16_frag = b16;
     u.n_cu = n_cu;
     u.glu_hp3 = k_skinny_glu_hp3;
-    timed(Q3A_KC_GEMM, 4.0 * I * H, [&] { KCHK(launch_skinny(u, precise(), ks)); });
-    SkinnyArgs dn{};
-    dn.fast_math = precise() ? 0 : 1;
-    dn.x = s_act_g(grp); dn.x16 = b16 ? reinterpret_cast<uint16_t*>(s_act_g(grp)) : nullptr; dn.x16_frag = b16; dn.ldx = I; dn.S = S; dn.W = wh(l.down_w); dn.N = H; dn.K = I;
-    dn.bias = mlp_bias ? wf(l.down_b) : nullptr; dn.mode = 1; dn.out = x; dn.ldo = H; dn.resid = x;
-    dn.qsplit = b16 && skinny_q();
-    if (pre && li + 1 < d.dec_layers) {  // (the last layer feeds the final norm + lm_head, which read x_dec)
-      dn.next_w = wf(L.dec[li + 1].in_ln); dn.next_xw16f = nn_x_g(grp); dn.next_ss = nn_ss_g(grp);
-    }
-    timed(Q3A_KC_GEMM, 2.0 * H * I, [&] { KCHK(launch_skinny(dn, precise(), ks)); });
+    run(pj.gu, u);
+    SkinnyArgs dn = skinny_args(pj.down, S);
+    dn.x = s_act_g(grp); dn.x16 = s_act16; dn.x16_frag = b16;
+    // (the last layer feeds the final norm + lm_head, which read x_dec)
+    to_residual(dn, li + 1 < d.dec_layers ? wf(L.dec[li + 1].in_ln) : nullptr);
+    run(pj.down, dn);
   }
 
   // one greedy-loop iteration for all sequences (inference.rs:160-200).  Batched path: the groups of `gsize` sequences are
@@ -1311,18 +1368,13 @@ struct q3a_engine {
     const int smallest = ng == 1 ? B : std::min(gsize, B - (ng - 1) * gsize);
     return smallest * d.n_kv < k_dattn_batched_min_wgs;
   }
-  hipGraphExec_t graph_for_step() {
-    const std::string sig = make_graph_sig();
-    for (size_t i = 0; i < graph_cache.size(); ++i)
-      if (graph_cache[i].first == sig) {  // LRU: a hit moves the entry to the back, eviction takes the front
-        if (i + 1 != graph_cache.size()) std::rotate(graph_cache.begin() + i, graph_cache.begin() + i + 1, graph_cache.end());
-        return graph_cache.back().second;
-      }
+  // what fn() enqueues on `stream`, captured and instantiated; a throw inside fn ends the capture and drops the partial graph
+  template <class F> hipGraphExec_t capture_graph(F&& fn) {
     hipGraph_t g = nullptr;
     hipGraphExec_t exec = nullptr;
     HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
     try {
-      enqueue_decode_step();
+      fn();
     } catch (...) {
       hipGraph_t tmp = nullptr;
       (void)hipStreamEndCapture(stream, &tmp);
@@ -1333,6 +1385,16 @@ struct q3a_engine {
     const hipError_t ie = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
     HIPCHK(ie);
+    return exec;
+  }
+  hipGraphExec_t graph_for_step() {
+    const std::string sig = make_graph_sig();
+    for (size_t i = 0; i < graph_cache.size(); ++i)
+      if (graph_cache[i].first == sig) {  // LRU: a hit moves the entry to the back, eviction takes the front
+        if (i + 1 != graph_cache.size()) std::rotate(graph_cache.begin() + i, graph_cache.begin() + i + 1, graph_cache.end());
+        return graph_cache.back().second;
+      }
+    const hipGraphExec_t exec = capture_graph([&] { enqueue_decode_step(); });
     if (graph_cache.size() >= kGraphCacheMax) {
       // the natural-EOS loop does not synchronise between steps, so the evicted exec may still be executing: it is only
       // destroyed after the next stream synchronisation (drain_retired_graphs)
@@ -1382,16 +1444,16 @@ struct q3a_engine {
     if (B <= 0) fail("q3a_run_resident: no batch uploaded");
     if (fixed_new > 0) max_new_req = fixed_new;
     if (max_new_req <= 0) max_new_req = opts.max_new_tokens;
-    std::vector<int32_t> ids_v, lens(B);
-    for (int s = 0; s < B; ++s) {
+    const auto pr = asr_prompts(lang_ids, n_prefix);
+    setup_prompts(pr.first.data(), pr.second.data(), B, max_new_req, true);
+  }
+  // the transcription prompt of every utterance of the batch (q3a_build_prompt over T[] of set_batch)
+  std::pair<std::vector<int32_t>, std::vector<int32_t>> asr_prompts(const int32_t* lang_ids, int n_prefix) const {
+    return concat_prompts(B, [&](int s, int32_t* dst) {
       int32_t len = 0;
-      q3a_build_prompt(T[s], lang_ids, n_prefix, nullptr, &len);
-      size_t o = ids_v.size();
-      ids_v.resize(o + len);
-      q3a_build_prompt(T[s], lang_ids, n_prefix, ids_v.data() + o, &len);
-      lens[s] = len;
-    }
-    setup_prompts(ids_v.data(), lens.data(), B, max_new_req, true);
+      q3a_build_prompt(T[s], lang_ids, n_prefix, dst, &len);
+      return len;
+    });
   }
 
   // mel_enqueued: upload_ptrs_and_mel() has put the (upload-overlapped) log-mel on the stream and recorded ev[0] / ev[1].
@@ -1447,12 +1509,9 @@ struct q3a_engine {
     HIPCHK(hipEventRecord(ev[4], stream));
     HIPCHK(hipStreamSynchronize(stream));
     HIPCHK(hipGetLastError());
-    float ms;
-    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1])); timings.mel_ms = ms;
-    HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2])); timings.encoder_ms = ms;
-    HIPCHK(hipEventElapsedTime(&ms, ev[2], ev[3])); timings.prefill_ms = ms;
-    HIPCHK(hipEventElapsedTime(&ms, ev[3], ev[4])); timings.decode_ms = ms;
-    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[4])); timings.total_ms = ms;
+    front_and_total_timings();
+    timings.prefill_ms = stage_ms(2, 3);
+    timings.decode_ms = stage_ms(3, 4);
     timings.decode_steps = steps; timings.batch = B; timings.total_audio_tokens = total_T; timings.total_prompt_tokens = total_P;
   }
 
@@ -1492,21 +1551,15 @@ struct q3a_engine {
   bool fixed_mode_ = false;
   bool head_logits_ = true;  // store the logits of a batched decode step (step API, debug taps); off inside run_resident
 
+  // Graphs, streams and events go here, before the members: every DevBuf (taps included) frees itself after this body has run.
+  // So the streams, the events and an owned arena now go BEFORE the workspace buffers (they used to go after).  The device-wide wait
+  // that the first hipFree implies therefore comes from the arena's, or with a borrowed arena from the first DevBuf's, after the
+  // streams are destroyed: legal, since HIP keeps a destroyed stream's resources until its work has finished.
   ~q3a_engine() {
     drop_graphs();
     for (auto cs : chain_streams) (void)hipStreamDestroy(cs);
     for (auto ce : join_ev) (void)hipEventDestroy(ce);
     if (fork_ev) (void)hipEventDestroy(fork_ev);
-    DevBuf* bufs[] = {&dft, &filt_t, &pos_emb, &rope_cos, &rope_sin, &pcm, &d_pcm_off, &d_n_samples, &d_mel_off, &d_n_frames,
-                      &mel, &gmax, &d_chunk_utt, &d_chunk_frame0, &conv1, &conv2, &conv3, &conv3_rowmap, &convout_rowmap,
-                      &enc_x, &enc_ln, &enc_qkv, &enc_ctx, &enc_ffn, &enc_segs, &audio_embeds, &ids, &audio_rowmap, &row_seq,
-                      &row_pos, &dec_segs, &last_rows, &dec_x, &dec_ln, &dec_qkv, &dec_ctx, &dec_act, &kcache, &vcache, &x_dec,
-                      &d_pos, &next_tok, &out_ids, &step_count, &done, &s_ln, &s_qkv, &s_ctx, &s_act, &logits, &forced_tok, &part_val, &part_idx, &attn_pm, &attn_pl, &attn_po,
-                      &part_sum, &out_lp,
-                      &enc_ctx16, &dec_ctx16, &dec_q16, &zero_page, &rope_cur, &nn_x, &nn_ss, &n_done,
-                      &align_rows, &align_xn, &align_pval, &align_pidx, &align_cls, &align_logits, &score_tgt, &score_psum, &score_out};
-    for (auto* b : bufs) b->release();
-    for (auto& kv : taps) kv.second.release();
     if (own_arena && arena) (void)hipFree(arena);
     if (host_prog) (void)hipHostFree(host_prog);
     if (up_stream) { (void)hipStreamSynchronize(up_stream); (void)hipStreamDestroy(up_stream); }
@@ -1690,30 +1743,27 @@ int32_t q3a_align_batch_ptrs(q3a_engine* e, const float* const* pcm16k, const in
   e->require_aligner("q3a_align_batch");
   if (!pcm16k || !n_samples || !text_lens || B < 1 || !out_counts || stride < 0 || (stride > 0 && !out_classes))
     fail("q3a_align_batch: bad argument");
-  for (int u = 0; u < B; ++u)
-    if (!pcm16k[u]) fail("q3a_align_batch: null utterance pointer");
+  require_utterance_ptrs("q3a_align_batch", pcm16k, B);
   HIPCHK(hipSetDevice(e->device));
   e->have_prefill = false;
   e->set_batch(n_samples, B);  // geometry first: the prompts only need the lengths
-  std::vector<int32_t> ids_v, lens(B);
-  int64_t toff = 0;
+  std::vector<int64_t> toff(B, 0);  // first text id of every utterance
   for (int s = 0; s < B; ++s) {
     if (text_lens[s] < 0 || (text_lens[s] > 0 && !text_ids)) fail("q3a_align_batch: bad text");
-    int32_t len = 0;
-    q3a_build_align_prompt(e->T[s], text_ids ? text_ids + toff : nullptr, text_lens[s], nullptr, &len);
-    const size_t o = ids_v.size();
-    ids_v.resize(o + len);
-    q3a_build_align_prompt(e->T[s], text_ids ? text_ids + toff : nullptr, text_lens[s], ids_v.data() + o, &len);
-    lens[s] = len;
-    toff += text_lens[s];
+    if (s + 1 < B) toff[s + 1] = toff[s] + text_lens[s];
   }
+  const auto [ids_v, lens] = concat_prompts(B, [&](int s, int32_t* dst) {
+    int32_t len = 0;
+    q3a_build_align_prompt(e->T[s], text_ids ? text_ids + toff[s] : nullptr, text_lens[s], dst, &len);
+    return len;
+  });
   const std::vector<int> rows = e->align_marker_rows(ids_v.data(), lens.data(), B, stride, out_counts);
   e->setup_prompts(ids_v.data(), lens.data(), B, 1, true);
   e->timings = q3a_timings{};
   e->upload_ptrs_and_mel(pcm16k, n_samples, B);
   e->run_encoder();
   e->run_align(rows, out_counts, stride, out_classes, nullptr);
-  e->head_call_front_timings();
+  e->front_and_total_timings();
   Q3A_CATCH(e)
 }
 
@@ -1742,27 +1792,18 @@ int32_t q3a_score_batch_ptrs(q3a_engine* e, const float* const* pcm16k, const in
   Q3A_TRY(e)
   e->require_asr("q3a_score_batch");
   if (!pcm16k || !n_samples || !target_lens || B < 1 || stride < 0 || (stride > 0 && !out_lp) || n_prefix < 0) fail("q3a_score_batch: bad argument");
-  for (int u = 0; u < B; ++u)
-    if (!pcm16k[u]) fail("q3a_score_batch: null utterance pointer");
+  require_utterance_ptrs("q3a_score_batch", pcm16k, B);
   HIPCHK(hipSetDevice(e->device));
   e->have_prefill = false;
   e->set_batch(n_samples, B);  // geometry first: the prompts only need the lengths
-  std::vector<int32_t> pids, plens(B);
-  for (int s = 0; s < B; ++s) {
-    int32_t len = 0;
-    q3a_build_prompt(e->T[s], lang_prefix_ids, n_prefix, nullptr, &len);
-    const size_t o = pids.size();
-    pids.resize(o + len);
-    q3a_build_prompt(e->T[s], lang_prefix_ids, n_prefix, pids.data() + o, &len);
-    plens[s] = len;
-  }
+  const auto [pids, plens] = e->asr_prompts(lang_prefix_ids, n_prefix);
   const auto sp = e->score_plan("q3a_score_batch", pids.data(), plens.data(), target_ids, target_lens, B, stride);
   e->setup_prompts(sp.ids.data(), sp.lens.data(), B, 1, true);
   e->timings = q3a_timings{};
   e->upload_ptrs_and_mel(pcm16k, n_samples, B);
   e->run_encoder();
   e->run_score(sp, target_lens, stride, out_lp, out_top_ids, out_top_lp, nullptr);
-  e->head_call_front_timings();
+  e->front_and_total_timings();
   Q3A_CATCH(e)
 }
 
@@ -1898,8 +1939,7 @@ int32_t q3a_transcribe_batch_ptrs(q3a_engine* e, const float* const* pcm16k, con
   Q3A_TRY(e)
   e->require_asr("q3a_transcribe_batch");
   if (!pcm16k || !n_samples || B < 1) fail("q3a_transcribe_batch: bad argument");
-  for (int u = 0; u < B; ++u)
-    if (!pcm16k[u]) fail("q3a_transcribe_batch: null utterance pointer");
+  require_utterance_ptrs("q3a_transcribe_batch", pcm16k, B);
   const auto w0 = std::chrono::steady_clock::now();
   HIPCHK(hipSetDevice(e->device));
   e->fixed_mode_ = fixed_new_tokens > 0;
@@ -1982,38 +2022,22 @@ int32_t q3a_profile_weight_stream(q3a_engine* e, int32_t reps, float* avg_us, do
   if (e->B > kGemvMaxSeq) fail("q3a_profile_weight_stream: the GEMV path serves at most 2 sequences");
   if (reps < 1) reps = 1;
   const Dims& d = e->d;
-  const int S = e->B, H = d.hidden, I = d.inter, QKV = d.qkv_dim();
+  const int S = e->B;
   auto sweep = [&]() {
     for (int li = 0; li < d.dec_layers; ++li) {
       const DecLayerOff& l = e->L.dec[li];
-      GemvArgs g{};
-      g.fast_math = e->precise() ? 0 : 1;
-      g.x = e->x_dec.as<float>(); g.ldx = H; g.rms_w = e->wf(l.in_ln); g.eps = d.rms_eps; g.W = e->wh(l.qkv_w); g.N = QKV; g.K = H;
-      g.mode = 0; g.out = e->s_qkv.as<float>(); g.ldo = QKV;
+      const auto pj = e->layer_projs(li);
+      GemvArgs g = e->gemv_args(pj.qkv);
+      g.x = e->x_dec.as<float>(); g.rms_w = e->wf(l.in_ln); g.out = e->s_qkv.as<float>();
       KCHK(launch_gemv(g, S, e->stream));
-      GemvArgs u{};
-      u.fast_math = e->precise() ? 0 : 1;
-      u.x = e->x_dec.as<float>(); u.ldx = H; u.rms_w = e->wf(l.post_ln); u.eps = d.rms_eps; u.W = e->wh(l.gu_w); u.N = 2 * I; u.K = H;
-      u.mode = 2; u.out = e->s_act.as<float>(); u.ldo = I;
+      GemvArgs u = e->gemv_args(pj.gu);
+      u.x = e->x_dec.as<float>(); u.rms_w = e->wf(l.post_ln); u.out = e->s_act.as<float>();
       KCHK(launch_gemv(u, S, e->stream));
     }
   };
   // replayed from a hipGraph like the decode step itself: an eager host loop issues ~6 us per launch, slower than
   // these kernels run, and would time the host
-  hipGraph_t g = nullptr;
-  hipGraphExec_t ge = nullptr;
-  HIPCHK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-  try {
-    for (int r = 0; r < reps; ++r) sweep();
-  } catch (...) {
-    hipGraph_t tmp = nullptr;
-    (void)hipStreamEndCapture(e->stream, &tmp);
-    if (tmp) (void)hipGraphDestroy(tmp);
-    throw;
-  }
-  HIPCHK(hipStreamEndCapture(e->stream, &g));
-  HIPCHK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-  (void)hipGraphDestroy(g);
+  const hipGraphExec_t ge = e->capture_graph([&] { for (int r = 0; r < reps; ++r) sweep(); });
   HIPCHK(hipGraphLaunch(ge, e->stream));  // warm-up (code objects, clocks)
   HIPCHK(hipStreamSynchronize(e->stream));
   hipEvent_t a, b;
@@ -2036,7 +2060,8 @@ int32_t q3a_profile_weight_stream(q3a_engine* e, int32_t reps, float* avg_us, do
   (void)hipGraphExecDestroy(ge);
   const int n = reps * d.dec_layers * 2;
   if (avg_us) *avg_us = ms * 1000.f / (float)n;
-  if (bytes_per_launch) *bytes_per_launch = (2.0 * QKV * H + 4.0 * I * H) / 2.0;
+  const auto pj0 = e->layer_projs(0);
+  if (bytes_per_launch) *bytes_per_launch = (pj0.qkv.bytes + pj0.gu.bytes) / 2.0;
   if (launches) *launches = n;
   Q3A_CATCH(e)
 }
@@ -2045,59 +2070,35 @@ int32_t q3a_debug_read(q3a_engine* e, const char* name, void* dst, uint64_t byte
   if (!e) return 1;
   Q3A_TRY(e)
   HIPCHK(hipSetDevice(e->device));
-  if (strcmp(name, "lm_head_prune_stats") == 0) {  // counters, not a tap: readable without opts.debug_taps
-    if (actual) *actual = 8;
-    if (dst) {
-      if (bytes < 8) fail("q3a_debug_read: destination too small");
-      HIPCHK(hipStreamSynchronize(e->stream));
-      HIPCHK(hipMemcpy(dst, e->prune_stats.p, 8, hipMemcpyDeviceToHost));
-    }
-    return 0;
-  }
-  if (strcmp(name, "align_head_ms") == 0) {  // float: the aligner head's launches (norm, classifier, merge) of the last align call
-    if (actual) *actual = 4;
-    if (dst) {
-      if (bytes < 4) fail("q3a_debug_read: destination too small");
-      memcpy(dst, &e->align_head_ms, 4);
-    }
-    return 0;
-  }
-  if (strcmp(name, "score_head_ms") == 0) {  // float: the scoring head's launches (norm, lm_head with the reducing epilogue, merge) of the last score call
-    if (actual) *actual = 4;
-    if (dst) {
-      if (bytes < 4) fail("q3a_debug_read: destination too small");
-      memcpy(dst, &e->score_head_ms, 4);
-    }
-    return 0;
-  }
+  // n bytes at src (device memory: after the stream has drained) to the caller
+  auto give = [&](const void* src, size_t n, bool on_device) {
+    if (actual) *actual = n;
+    if (!dst) return;
+    if (bytes < n) fail("q3a_debug_read: destination too small");
+    if (!on_device) { memcpy(dst, src, n); return; }
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy(dst, src, n, hipMemcpyDeviceToHost));
+  };
+  // counters and times, not taps: readable without opts.debug_taps
+  const uint64_t device_bytes = g_device_bytes.load();
+  const struct { const char* name; const void* src; size_t n; bool on_device; } scalars[] = {
+      {"lm_head_prune_stats", e->prune_stats.p, 8, true},
+      {"align_head_ms", &e->align_head_ms, 4, false},  // the aligner head's launches (norm, classifier, merge) of the last align call
+      {"score_head_ms", &e->score_head_ms, 4, false},  // the scoring head's launches (norm, lm_head with the reducing epilogue, merge) of the last score call
+      {"device_bytes", &device_bytes, 8, false},       // device memory the DevBufs of the whole process hold
+  };
+  for (const auto& sc : scalars)
+    if (strcmp(name, sc.name) == 0) { give(sc.src, sc.n, sc.on_device); return 0; }
   auto it = e->taps.find(name);
   if (it == e->taps.end()) fail(std::string("q3a_debug_read: no tap named '") + name + "' (opts.debug_taps set?)");
-  size_t n = e->tap_bytes[name];
-  if (actual) *actual = n;
-  if (dst) {
-    if (bytes < n) fail("q3a_debug_read: destination too small");
-    HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(dst, it->second.p, n, hipMemcpyDeviceToHost));
-  }
+  give(it->second.p, e->tap_bytes[name], true);
   Q3A_CATCH(e)
 }
 
 int32_t q3a_debug_set(const char* key, int32_t value) {
   if (!key) return 1;
-  Knobs& kn = knobs();
-  if (strcmp(key, "gemm256_min_tiles") == 0) { kn.gemm256_min_tiles = value; return 0; }
-  if (strcmp(key, "gemm256_persist") == 0) { kn.gemm256_persist = value; return 0; }
-  if (strcmp(key, "gemm256_group_m") == 0) { kn.gemm256_group_m = value; return 0; }
-  if (strcmp(key, "dattn_batched_min_wgs") == 0) { kn.dattn_batched_min_wgs = value; return 0; }
-  if (strcmp(key, "decode_group_size") == 0) { kn.decode_group_size = value; return 0; }
-  if (strcmp(key, "decode_parallel_groups") == 0) { kn.decode_parallel_groups = value; return 0; }
-  if (strcmp(key, "fuse_qkrope") == 0) { kn.fuse_qkrope = value; return 0; }
-  if (strcmp(key, "skinny_q") == 0) { kn.skinny_q = value; return 0; }
-  if (strcmp(key, "eos_run_ahead") == 0) { kn.eos_run_ahead = value; return 0; }
-  if (strcmp(key, "skinny_glu_hp3") == 0) { kn.skinny_glu_hp3 = value; return 0; }
-  if (strcmp(key, "lm_head_prune") == 0) { kn.lm_head_prune = value; return 0; }
-  if (strcmp(key, "layer_taps") == 0) { kn.layer_taps = value; return 0; }
-  if (strcmp(key, "poison_attn_partials") == 0) { kn.poison_attn_partials = value; return 0; }
+  for (const KnobEntry& t : kKnobTable)
+    if (strcmp(key, t.key) == 0) { (knobs().*t.field).store(value); return 0; }
   g_last_error = std::string("q3a_debug_set: unknown key '") + key + "'";
   return 1;
 }
@@ -2131,7 +2132,6 @@ int32_t q3a_selftest_gemm(int32_t device, int32_t M, int32_t N, int32_t K, int32
   for (size_t i = 0; i < Y.size(); ++i) { me = std::max(me, std::fabs(Y[i] - R[i])); rm = std::max(rm, std::fabs(R[i])); }
   if (max_abs_err) *max_abs_err = me;
   if (ref_abs_max) *ref_abs_max = rm;
-  dX.release(); dW.release(); dY.release(); dR.release();
   Q3A_CATCH(e)
 }
 
@@ -2227,7 +2227,6 @@ int32_t q3a_selftest_gemm16(int32_t device, int32_t M, int32_t N, int32_t K, int
             fail("selftest_gemm16: SwiGLU epilogue is off");
         }
     }
-    dB.release(); dA.release(); dS.release(); dM.release(); dY2.release(); dY16.release();
   }
   if (max_abs_err) *max_abs_err = me;
   if (ref_abs_max) *ref_abs_max = rm;
@@ -2251,7 +2250,6 @@ int32_t q3a_selftest_gemm16(int32_t device, int32_t M, int32_t N, int32_t K, int
     (void)hipEventDestroy(a);
     (void)hipEventDestroy(b);
   }
-  dX.release(); dX16.release(); dW.release(); dY.release(); dR.release();
   Q3A_CATCH(e)
 }
 

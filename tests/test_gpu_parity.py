@@ -161,6 +161,31 @@ def test_batch_above_gemv_path(tiny_dir):
     _stage_check(tiny_dir, clips, True, steps=3)
 
 
+def test_engine_destroy_returns_every_device_buffer(tiny_dir):
+    """Every device buffer of the workspace is owned by a DevBuf that frees itself, and the bytes all of them hold are counted
+    (q3a_debug_read "device_bytes", process-wide).  Engines that ran the GEMV path (one clip: the pruned-head buffers) and the skinny
+    path (three clips) with debug taps populated leave the count exactly where it was once they are closed; while one is alive the
+    count is higher by at least the int8 lm_head copy (vocabulary x 1024 bytes even at the tiny checkpoint's hidden size), the
+    buffer that was never released before."""
+    def device_bytes(e):
+        return int(e.debug_read_raw("device_bytes").view(np.uint64)[0])
+    clips = [synthetic.synthetic_clip(40 + i, 1.5) for i in range(3)]
+    a = HipEngine(tiny_dir, 0, max_new_tokens=16)
+    a.transcribe_batch(clips[:1], None, max_new=4, fixed_new_tokens=4)
+    x0 = device_bytes(a)
+    alive = []
+    for _ in range(3):
+        b = HipEngine(tiny_dir, 0, max_new_tokens=16, debug_taps=True)
+        b.transcribe_batch(clips[:1], None, max_new=4, fixed_new_tokens=4)
+        b.transcribe_batch(clips, None, max_new=4, fixed_new_tokens=4)
+        assert b.debug_read("logits").size == 3 * b.dims.vocab_size  # (taps populated)
+        alive.append(device_bytes(a))
+        b.close()
+        assert device_bytes(a) == x0
+    assert min(alive) >= x0 + a.dims.vocab_size * 1024, (alive, x0)
+    a.close()
+
+
 def test_key_splits_follow_the_context_not_the_capacity(tiny_dir):
     """The one-sequence decode attention launches as many 128-key splits as the caches HOLD keys for (longest prompt + steps
     so far), whatever max_new_tokens reserves: a 40-token prompt generating 230 tokens crosses the 128- and 256-key marks, so

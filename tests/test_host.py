@@ -30,9 +30,10 @@ def test_exports_match_header(lib):
 def test_debug_keys_are_documented_and_reject_unknown(lib):
     """Every key q3a_debug_set accepts is described in include/q3asr.h (and vice versa); unknown keys are an error, no GPU needed."""
     src = open(os.path.join(ROOT, "qwen3_asr_rs_amd", "csrc", "engine.cpp")).read()
-    body = src[src.index("int32_t q3a_debug_set("):]
-    body = body[:body.index("\n}\n")]
-    accepted = set(re.findall(r'strcmp\(key, "([a-z0-9_]+)"\)', body))
+    assert "kKnobTable" in _cpp_function_body(src, "int32_t q3a_debug_set(")  # the keys it accepts are the table's
+    table = src[src.index("KnobEntry kKnobTable[] = {"):]
+    table = table[:table.index("\n};\n")]
+    accepted = set(re.findall(r'\{\s*"([a-z0-9_]+)"\s*,', table))
     hdr = open(os.path.join(ROOT, "include", "q3asr.h")).read()
     doc = hdr[:hdr.index("int32_t q3a_debug_set(")]
     doc = doc[doc.rindex("/*"):]
@@ -466,7 +467,7 @@ def test_step_buffers_cover_the_captured_step():
     assert listed <= members and len(listed) >= 20
     step_functions = ["void decode_layer(", "void run_head(", "void enqueue_decode_step(", "void* kc_layer(", "void* vc_layer(",
                       "NextNormOut first_layer_norm_out(", "uint16_t* nn_x_g(", "float* nn_ss_g(", "float* s_ctx_g(", "float* s_act_g(",
-                      "void batched_proj("]
+                      "void batched_proj(", "LayerProjs layer_projs("]
     used = set()
     for f in step_functions:
         body = _cpp_function_body(src, f)
