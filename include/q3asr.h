@@ -356,6 +356,61 @@ int32_t q3a_score_batch_ptrs(q3a_engine* e, const float* const* pcm16k, const in
                              const int32_t* lang_prefix_ids, int32_t n_prefix, const int32_t* target_ids, const int32_t* target_lens,
                              float* out_lp, int32_t* out_top_ids, float* out_top_lp, int32_t stride);
 
+/* ---- beam search: n-best hypotheses with scores, selected on the device ------------------------------------------------------------
+ * U utterances of W slots each (1 <= W <= 8, U * W <= 32): sequence u * W + j of the engine's batch is slot j of utterance u, and the
+ * whole-path call uploads each clip once per slot (mel, encoder and prefill run W times per utterance; sharing them is out of scope).
+ * A hypothesis has ids (EOS excluded, as q3a_fetch_ids), an fp32 score = the sum of the natural-log probabilities of its tokens (the
+ * EOS's included when it finished; one fp32 add per round, score_parent + lp) and a finished flag.  The log-probability of token v on a
+ * sequence's row of fp32 logits l is lp = (l[v] - m) - log sum exp(l - m), m the row maximum, the sum in fp32 in a fixed order (the
+ * formula of q3a_score); results are bit-identical from run to run.
+ *   Round 0 works on the prefill's logits: only slot 0 of every utterance is live (score 0), the other slots are empty (score -inf) and
+ *   produce no candidates.  In a round every live unfinished slot s contributes its W best tokens (larger logit, then smaller id; -inf
+ *   is a legal logit and ranks last; NaN is outside the contract) as (score_s + lp, s, token) and every finished slot itself as
+ *   (score, s, none).  Candidates are ordered by larger score, then smaller parent slot, then smaller token id ("none" first); the first W
+ *   survive.  In rank order a survivor takes its parent's slot if that is still free; the remaining survivors, in rank order, take the
+ *   free slots in ascending order -- only these have their history (generated KV rows) copied.  A survivor whose token is 151643 or
+ *   151645 becomes finished; the token is not appended to its ids.  The search ends when all W slots of every utterance are finished, or
+ *   after max_new rounds (rounds 0 .. max_new - 1; max_new <= 0 means, and larger values are capped by, opts.max_new_tokens); unfinished
+ *   hypotheses are returned with finished = 0 and max_new ids.  Output per utterance: the W hypotheses by larger score, then smaller slot;
+ *   empty slots (length 0, score -inf) last.  With W = 1 the ids and lengths are those of the greedy natural-EOS run, bit for bit.
+ * The step's state never leaves the device inside the loop: top-W selection, the round's bookkeeping and the KV reorder are launches of
+ * the (captured and replayed) step, and the stop word is read from pinned host memory as in the greedy loop.
+ * Refused (q3a_last_error): width < 1 or > 8; U * width > 32 sequences; a batch not divisible by width, or prompts of one utterance
+ * that differ in length (q3a_beam_begin); stride < max_new; an aligner engine; q3a_beam_step / q3a_beam_fetch without q3a_beam_begin.
+ * Afterwards the engine holds no decode state (as after q3a_score): q3a_decode_step, q3a_set_next_tokens and q3a_fetch_ids fail until the
+ * next prefill.  q3a_stage_timings reports mel, encoder, prefill and decode with decode_steps = rounds - 1.  q3a_debug_read (no debug
+ * taps needed) reflects the last round: "beam_topk_ids" (int32 [S][W]) / "beam_topk_lp" (fp32 [S][W]); "beam_parent" (int32 [S]: the
+ * SEQUENCE u * W + slot the hypothesis now in this slot continued), "beam_token" (int32 [S]: the survivor's token, an EOS id when it
+ * finished in this round, -1 for a hypothesis that was finished before), "beam_score" (fp32 [S]), "beam_finished" (uint8 [S]);
+ * "beam_stats" (int32 [4]: rounds run, survivors that needed a copy, KV rows copied, hypotheses finished; cumulative over the call).
+ * Out of scope: q3a_group_* (search each rank's slice on q3a_group_engine's handle), sharing the encoder or the prompt's KV rows
+ * across slots, length penalties inside the search (re-rank the returned list on the host), sampling, log-probabilities of
+ * alternatives that did not survive, U * W > 32. */
+
+/* Whole path, host PCM in (as q3a_transcribe_batch_ptrs).  out_ids [U][width][stride], out_lens / out_scores / out_finished [U][width],
+ * out_lp nullable [U][width][stride + 1]: per token, then the EOS's when finished. */
+int32_t q3a_beam_search_batch_ptrs(q3a_engine* e, const float* const* pcm16k, const int64_t* n_samples, int32_t U,
+                                   const int32_t* lang_prefix_ids, int32_t n_prefix, int32_t width, int32_t max_new, int32_t* out_ids,
+                                   int32_t stride, int32_t* out_lens, float* out_scores, uint8_t* out_finished, float* out_lp);
+/* Stage form, directly after q3a_mel / q3a_encode / q3a_prefill of U * width sequences in which each utterance appears `width` times in a
+ * row.  q3a_beam_begin: round 0 on the prefill's logits.  q3a_beam_step: one decode step and its round; logits_out (nullable): host
+ * fp32 [S][vocab], the rows this round selected from; fails once max_new_tokens rounds have run.  q3a_beam_fetch: as the whole path's
+ * outputs, for the rounds run so far. */
+int32_t q3a_beam_begin(q3a_engine* e, int32_t width);
+int32_t q3a_beam_step(q3a_engine* e, uint8_t* all_finished, float* logits_out);
+int32_t q3a_beam_fetch(q3a_engine* e, int32_t* out_ids, int32_t stride, int32_t* out_lens, float* out_scores, uint8_t* out_finished,
+                       float* out_lp);
+/* The three kernels on their own (no model; host arrays in, host arrays out).  top-W: logits [S][V] -> out_ids / out_lp [S][W].
+ * advance: one round of U x W slots on the given tables and state (score -inf and not finished = an empty slot); parent_out holds
+ * sequence indices, token_out -1 for "none".  kv reorder: cache = the K cache followed by the V cache, each
+ * [layers][S][n_kv][max_ctx][128] elements of elem_bytes (2 or 4); for every sequence j with parent[j] != j rows lo[j] .. hi[j] of both
+ * become a copy of sequence parent[j]'s (which must share lo and hi). */
+int32_t q3a_selftest_beam_topk(int32_t device, const float* logits, int32_t S, int32_t V, int32_t W, int32_t* out_ids, float* out_lp);
+int32_t q3a_selftest_beam_advance(int32_t device, int32_t U, int32_t W, const int32_t* topk_ids, const float* topk_lp, const float* score_in,
+                                  const uint8_t* finished_in, int32_t* parent_out, int32_t* token_out, float* score_out, uint8_t* finished_out);
+int32_t q3a_selftest_kv_reorder(int32_t device, void* cache, int32_t elem_bytes, int32_t layers, int32_t S, int32_t n_kv, int32_t max_ctx,
+                                const int32_t* lo, const int32_t* hi, const int32_t* parent);
+
 /* A/B knobs for kernel experiments (process-wide atomics, read from the environment once; not part of the reference
  * interface).  The knobs that shape the decode step are latched per batch at the next prefill and are part of the captured
  * graph's signature, so changing one on a live engine re-captures instead of replaying a stale graph.  Keys:

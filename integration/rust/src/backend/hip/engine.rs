@@ -67,6 +67,20 @@ extern "C" {
     pub fn q3a_score_batch_ptrs(e: *mut q3a_engine, pcm16k: *const *const f32, n_samples: *const i64, b: i32, lang_prefix_ids: *const i32,
                                 n_prefix: i32, target_ids: *const i32, target_lens: *const i32, out_lp: *mut f32, out_top_ids: *mut i32,
                                 out_top_lp: *mut f32, stride: i32) -> i32;
+    // beam search: n-best hypotheses with scores, selected on the device (include/q3asr.h "beam search")
+    pub fn q3a_beam_search_batch_ptrs(e: *mut q3a_engine, pcm16k: *const *const f32, n_samples: *const i64, u: i32,
+                                      lang_prefix_ids: *const i32, n_prefix: i32, width: i32, max_new: i32, out_ids: *mut i32, stride: i32,
+                                      out_lens: *mut i32, out_scores: *mut f32, out_finished: *mut u8, out_lp: *mut f32) -> i32;
+    pub fn q3a_beam_begin(e: *mut q3a_engine, width: i32) -> i32;
+    pub fn q3a_beam_step(e: *mut q3a_engine, all_finished: *mut u8, logits_out: *mut f32) -> i32;
+    pub fn q3a_beam_fetch(e: *mut q3a_engine, out_ids: *mut i32, stride: i32, out_lens: *mut i32, out_scores: *mut f32,
+                          out_finished: *mut u8, out_lp: *mut f32) -> i32;
+    pub fn q3a_selftest_beam_topk(device: i32, logits: *const f32, s: i32, v: i32, w: i32, out_ids: *mut i32, out_lp: *mut f32) -> i32;
+    pub fn q3a_selftest_beam_advance(device: i32, u: i32, w: i32, topk_ids: *const i32, topk_lp: *const f32, score_in: *const f32,
+                                     finished_in: *const u8, parent_out: *mut i32, token_out: *mut i32, score_out: *mut f32,
+                                     finished_out: *mut u8) -> i32;
+    pub fn q3a_selftest_kv_reorder(device: i32, cache: *mut std::ffi::c_void, elem_bytes: i32, layers: i32, s: i32, n_kv: i32, max_ctx: i32,
+                                   lo: *const i32, hi: *const i32, parent: *const i32) -> i32;
 }
 
 /// src/main.rs:51-65 for the `hip` feature: HIP devices visible to this process (0: none -- there is no CPU path).

@@ -22,6 +22,8 @@ SYMBOLS = [
     "q3a_group_engine", "q3a_group_partition", "q3a_group_transcribe", "q3a_group_transcribe_ptrs", "q3a_group_startup_seconds",
     "q3a_aligner_info", "q3a_build_align_prompt", "q3a_align", "q3a_align_batch_ptrs", "q3a_split_words_for_alignment",
     "q3a_align_text_ids", "q3a_fix_timestamps", "q3a_score", "q3a_score_batch_ptrs",
+    "q3a_beam_search_batch_ptrs", "q3a_beam_begin", "q3a_beam_step", "q3a_beam_fetch", "q3a_selftest_beam_topk", "q3a_selftest_beam_advance",
+    "q3a_selftest_kv_reorder",
 ]
 
 
@@ -140,6 +142,13 @@ def load() -> C.CDLL:
         "q3a_fix_timestamps": (i32, [f32p, i32, f32p]),
         "q3a_score": (i32, [P, i32p, i32p, i32p, i32p, i32, f32p, i32p, f32p, i32, f32p]),
         "q3a_score_batch_ptrs": (i32, [P, C.POINTER(P), i64p, i32, i32p, i32, i32p, i32p, f32p, i32p, f32p, i32]),
+        "q3a_beam_search_batch_ptrs": (i32, [P, C.POINTER(P), i64p, i32, i32p, i32, i32, i32, i32p, i32, i32p, f32p, u8p, f32p]),
+        "q3a_beam_begin": (i32, [P, i32]),
+        "q3a_beam_step": (i32, [P, u8p, f32p]),
+        "q3a_beam_fetch": (i32, [P, i32p, i32, i32p, f32p, u8p, f32p]),
+        "q3a_selftest_beam_topk": (i32, [i32, f32p, i32, i32, i32, i32p, f32p]),
+        "q3a_selftest_beam_advance": (i32, [i32, i32, i32, i32p, f32p, f32p, u8p, i32p, i32p, f32p, u8p]),
+        "q3a_selftest_kv_reorder": (i32, [i32, P, i32, i32, i32, i32, i32, i32p, i32p, i32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -10,6 +10,8 @@
 // ids of "<asr_text>" + text + <|im_end|>, the language prefix in the prompt) after the lines above and adds "Score: avg_logprob <mean
 // token log-probability> min_token_prob <smallest token probability> tokens <n> disagree <rows whose argmax is another id>"; without it
 // nothing changes.
+// Q3A_BEAM=<W> runs a beam search of width W (q3a_beam_search_batch_ptrs; 1..8) over the same audio and prompt after "Text:" (and
+// "Confidence:") and adds one stdout line per hypothesis, best first: "Hyp <k>: <score> <text>"; without it nothing changes.
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -120,6 +122,33 @@ static int print_score(q3a_engine* eng, q3a_tokenizer* tok, const float* pcm, in
   return 0;
 }
 
+// Q3A_BEAM=<W>: a beam search of width W over the same audio and prompt; one `Hyp k: <score> <text>` line per hypothesis, best first
+// (score = the sum of the tokens' natural-log probabilities, the EOS's included when the hypothesis finished).
+static int print_beam(q3a_engine* eng, q3a_tokenizer* tok, const float* pcm, int64_t n, const std::vector<int32_t>& prefix, int width,
+                      int32_t max_new, bool language_forced) {
+  if (width < 1) return die("Beam search failed: Q3A_BEAM must be a width of 1..8");  // (the engine refuses more than 8 itself)
+  std::vector<int32_t> ids((size_t)width * max_new), lens((size_t)width);
+  std::vector<float> scores((size_t)width);
+  std::vector<uint8_t> fin((size_t)width);
+  const float* ptrs[1] = {pcm};
+  if (q3a_beam_search_batch_ptrs(eng, ptrs, &n, 1, prefix.empty() ? nullptr : prefix.data(), (int32_t)prefix.size(), width, max_new, ids.data(),
+                                 max_new, lens.data(), scores.data(), fin.data(), nullptr) != 0)
+    return die(std::string("Beam search failed: ") + q3a_last_error(eng));
+  for (int k = 0; k < width; ++k) {
+    if (std::isinf(scores[k]) && lens[k] == 0) continue;  // an empty slot
+    const int32_t* hyp = ids.data() + (size_t)k * max_new;
+    int32_t need = 0;
+    q3a_tokenizer_decode(tok, hyp, lens[k], 1, nullptr, 0, &need);
+    std::string raw((size_t)need + 1, '\0');
+    q3a_tokenizer_decode(tok, hyp, lens[k], 1, &raw[0], need + 1, &need);
+    raw.resize((size_t)need);
+    std::vector<char> lang(256), text(raw.size() + 16);
+    q3a_parse_asr_output(raw.c_str(), language_forced, lang.data(), (int32_t)lang.size(), text.data(), (int32_t)text.size());
+    printf("Hyp %d: %.6f %s\n", k, scores[k], text.data());
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (const char* rl = getenv("RUST_LOG")) {
     if (strstr(rl, "debug") || strstr(rl, "trace")) g_level = 2;
@@ -224,8 +253,10 @@ int main(int argc, char** argv) {
     printf("Confidence: avg_logprob %.6f min_token_prob %.6f\n", avg, lps.empty() ? NAN : std::exp((double)mn));
   }
   int rc = 0;
+  const char* beam_env = getenv("Q3A_BEAM");
+  if (beam_env && *beam_env) rc = print_beam(eng, tok, pcm, n, prefix, atoi(beam_env), max_new, language != nullptr);
   const char* score_path = getenv("Q3A_SCORE_TEXT");
-  if (score_path && *score_path && language) rc = print_score(eng, tok, pcm, n, prefix, score_path);
+  if (rc == 0 && score_path && *score_path && language) rc = print_score(eng, tok, pcm, n, prefix, score_path);
   const char* aligner_dir = getenv("Q3A_ALIGNER");
   if (rc == 0 && aligner_dir && *aligner_dir) rc = print_word_times(aligner_dir, pcm, n, text.data(), language);
   q3a_free(pcm);

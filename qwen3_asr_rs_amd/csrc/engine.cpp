@@ -699,6 +699,7 @@ struct q3a_engine {
     if (!have_enc && !before_encoder) fail("q3a_prefill: no encoder output (call q3a_encode first)");
     if (b != B) fail("q3a_prefill: batch size differs from the encoded batch");
     P.assign(lens, lens + b);
+    beam_w_ = 0;  // (a beam search begins after the prefill: q3a_beam_begin)
     seq_off.resize(b);
     std::vector<int> rowseq, rowpos, amap((size_t)total_T, -1), last(b);
     int off = 0, maxP = 0;
@@ -812,7 +813,9 @@ struct q3a_engine {
   // source for DevBuf members and fails when one is missing here.
   std::vector<DevBuf*> step_bufs() {
     return {&kcache, &vcache, &x_dec, &d_pos, &next_tok, &out_ids, &step_count, &done, &s_ln, &s_qkv, &s_ctx, &s_act, &logits,
-            &part_val, &part_idx, &part_sum, &out_lp, &blk_lo, &blk_hi, &prune_stats, &attn_pm, &attn_pl, &attn_po, &nn_x, &nn_ss, &rope_cur, &rope_cos, &rope_sin, &n_done, &forced_tok};
+            &part_val, &part_idx, &part_sum, &out_lp, &blk_lo, &blk_hi, &prune_stats, &attn_pm, &attn_pl, &attn_po, &nn_x, &nn_ss, &rope_cur, &rope_cos, &rope_sin, &n_done, &forced_tok,
+            &beam_cand_val, &beam_cand_idx, &beam_part_max, &beam_part_sum, &beam_topk_ids, &beam_topk_lp, &beam_score, &beam_finished, &beam_parent, &beam_token,
+            &beam_feed, &beam_hist_parent, &beam_hist_token, &beam_hist_lp, &beam_state, &beam_lo};
   }
   std::vector<const DevBuf*> step_bufs() const {
     auto v = const_cast<q3a_engine*>(this)->step_bufs();
@@ -1355,8 +1358,8 @@ struct q3a_engine {
     }
     char buf[256];
     // (one field per latched knob, as latched: packing several into one integer let distinct settings collide -- ADVICE r5)
-    snprintf(buf, sizeof(buf), "%d.%d.%d.%d.%d.%d.%d.%d.%d.%d/%d/%d/%d/%p/%016llx", B, gsize, k_parallel_groups, k_skinny_q,
-             k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, (int)(min_P_ < 256), (int)head_logits_, (int)token_lp(), live_nsplit_,
+    snprintf(buf, sizeof(buf), "%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.b%d/%d/%d/%d/%p/%016llx", B, gsize, k_parallel_groups, k_skinny_q,
+             k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, (int)(min_P_ < 256), (int)head_logits_, (int)token_lp(), beam_w_, live_nsplit_,
              max_ctx, max_new, (const void*)arena, (unsigned long long)h);
     return buf;
   }
@@ -1394,7 +1397,7 @@ struct q3a_engine {
         if (i + 1 != graph_cache.size()) std::rotate(graph_cache.begin() + i, graph_cache.begin() + i + 1, graph_cache.end());
         return graph_cache.back().second;
       }
-    const hipGraphExec_t exec = capture_graph([&] { enqueue_decode_step(); });
+    const hipGraphExec_t exec = capture_graph([&] { enqueue_step(); });
     if (graph_cache.size() >= kGraphCacheMax) {
       // the natural-EOS loop does not synchronise between steps, so the evicted exec may still be executing: it is only
       // destroyed after the next stream synchronisation (drain_retired_graphs)
@@ -1430,7 +1433,7 @@ struct q3a_engine {
     for (int i = 0; i < n; ++i) {
       // this step feeds the token at position <= pos_hi_ and attends keys 0 .. pos_hi_
       live_nsplit_ = uses_key_splits() ? std::min(attn_nsplit, pos_hi_ / kps + 1) : attn_nsplit;
-      if (eager) enqueue_decode_step();
+      if (eager) enqueue_step();
       else HIPCHK(hipGraphLaunch(graph_for_step(), stream));
       ++pos_hi_;
     }
@@ -1516,7 +1519,7 @@ struct q3a_engine {
   }
 
   void fetch_ids(int32_t* out, int stride, int32_t* out_lens) {
-    if (!have_prefill) fail("q3a_fetch_ids: nothing generated");
+    if (!have_prefill || beam_w_ > 0) fail("q3a_fetch_ids: nothing generated");
     std::vector<int> all((size_t)B * max_new);
     HIPCHK(hipMemcpy(all.data(), out_ids.p, all.size() * 4, hipMemcpyDeviceToHost));
     generated_lens(all, out_lens);
@@ -1550,6 +1553,160 @@ struct q3a_engine {
   }
   bool fixed_mode_ = false;
   bool head_logits_ = true;  // store the logits of a batched decode step (step API, debug taps); off inside run_resident
+
+  // =====================================================================================
+  // beam search (include/q3asr.h "beam search"; k_beam.hip).  The B sequences of the batch are U = B / W
+  // utterances of W slots.  A round selects on the stored logits: top-W per sequence -> advance (candidates, rank, slots, state,
+  // history, stop word) -> KV reorder -> the survivors' tokens through the set_tokens path.  Round 0 runs on the prefill's
+  // logits; every later round is the tail of a decode step and is captured / replayed with it.  Nothing comes back to the host
+  // inside the loop: the history is back-pointers [round][sequence] that beam_fetch follows afterwards.
+  int beam_w_ = 0;                       // > 0: beam mode, slots per utterance (part of the graph signature)
+  int beam_dbg_S_ = 0, beam_dbg_W_ = 0;  // shape of the last search's tables (q3a_debug_read "beam_*")
+  DevBuf beam_cand_val, beam_cand_idx, beam_part_max, beam_part_sum, beam_topk_ids, beam_topk_lp, beam_score, beam_finished, beam_parent, beam_token;
+  DevBuf beam_feed, beam_hist_parent, beam_hist_token, beam_hist_lp, beam_state, beam_lo;
+  int* beam_prog() const { return host_prog + 2; }  // pinned: [0] advance launches completed, [1] every slot finished
+
+  void enqueue_step() {
+    enqueue_decode_step();
+    if (beam_w_ > 0) enqueue_beam_round();
+  }
+  void enqueue_beam_round() {
+    const int W = beam_w_, S = B, U = B / W;
+    BeamTopkArgs t{};
+    t.logits = logits.as<float>(); t.S = S; t.V = d.vocab; t.W = W;
+    t.cand_val = beam_cand_val.as<float>(); t.cand_idx = beam_cand_idx.as<int>();
+    t.part_max = beam_part_max.as<float>(); t.part_sum = beam_part_sum.as<float>();
+    t.out_ids = beam_topk_ids.as<int>(); t.out_lp = beam_topk_lp.as<float>();
+    timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_beam_topk(t, stream)); });
+    BeamAdvanceArgs a{};
+    a.U = U; a.W = W; a.topk_ids = t.out_ids; a.topk_lp = t.out_lp;
+    a.score = beam_score.as<float>(); a.finished = beam_finished.as<uint8_t>();
+    a.parent = beam_parent.as<int>(); a.token = beam_token.as<int>(); a.feed = beam_feed.as<int>();
+    a.hist_parent = beam_hist_parent.as<int>(); a.hist_token = beam_hist_token.as<int>(); a.hist_lp = beam_hist_lp.as<float>();
+    a.hist_cap = max_new; a.state = beam_state.as<int>();
+    // rows a copy moves: the generated suffix, first row = the prompt length, last = the row the step just appended (pos was advanced)
+    a.pos = d_pos.as<int>(); a.lo = beam_lo.as<int>(); a.hi_bias = -1;
+    a.host_progress = host_prog_dev + 2; a.eos0 = kEos0; a.eos1 = kEos1;
+    timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_beam_advance(a, stream)); });
+    KvReorderArgs r{};
+    r.kcache = kcache.p; r.vcache = vcache.p; r.elem_bytes = (int)kv_elem(); r.layers = d.dec_layers; r.S = S; r.n_kv = d.n_kv; r.max_ctx = max_ctx;
+    r.parent = a.parent; r.lo = a.lo; r.hi = a.pos; r.hi_bias = -1; r.all_done = a.state + BEAM_ST_ALL_DONE;
+    timed(Q3A_KC_OTHER, 0, [&] { KCHK(launch_kv_reorder(r, stream)); });
+    timed(Q3A_KC_OTHER, 0, [&] {
+      KCHK(launch_set_tokens(a.feed, S, wh(L.embed), d.hidden, x_dec.as<float>(), next_tok.as<int>(), stream, first_layer_norm_out()));
+    });
+  }
+  // refusals of q3a_beam_begin / q3a_beam_search_batch_ptrs that need the batch (prompt lengths P of B sequences)
+  void beam_check(const char* what, int W) const {
+    if (W < 1 || W > BEAM_MAX_W) fail(std::string(what) + ": width must be 1..8");
+    if (B % W != 0) fail(std::string(what) + ": the batch of " + std::to_string(B) + " sequences is not divisible by width " + std::to_string(W));
+    if (B > 32) fail(std::string(what) + ": utterances x width = " + std::to_string(B) + " exceeds 32 sequences");
+    for (int s = 0; s < B; ++s)
+      if (P[s] != P[s / W * W]) fail(std::string(what) + ": the prompts of utterance " + std::to_string(s / W) + " differ in length (its " + std::to_string(W) + " slots must hold the same prompt)");
+    if (d.vocab < W) fail(std::string(what) + ": vocabulary smaller than the width");
+  }
+  // state for a search over the prefilled batch, then round 0 on the prefill's logits (enqueued; nothing waited for)
+  void beam_begin(const char* what, int W) {
+    if (!have_prefill) fail(std::string(what) + ": no prefill state (call q3a_prefill first)");
+    beam_check(what, W);
+    if (!head_logits_ || pos_hi_ != *std::max_element(P.begin(), P.end()))
+      fail(std::string(what) + ": needs the logits of q3a_prefill (call it directly after the prefill)");
+    const int S = B, nc = beam_topk_chunks(d.vocab);
+    beam_cand_val.ensure((size_t)S * nc * W * 4); beam_cand_idx.ensure((size_t)S * nc * W * 4);
+    beam_part_max.ensure((size_t)S * nc * 4); beam_part_sum.ensure((size_t)S * nc * 4);
+    beam_topk_ids.ensure((size_t)S * W * 4); beam_topk_lp.ensure((size_t)S * W * 4);
+    beam_parent.ensure((size_t)S * 4); beam_token.ensure((size_t)S * 4); beam_feed.ensure((size_t)S * 4);
+    beam_hist_parent.ensure((size_t)max_new * S * 4); beam_hist_token.ensure((size_t)max_new * S * 4); beam_hist_lp.ensure((size_t)max_new * S * 4);
+    std::vector<float> sc((size_t)S, -INFINITY);
+    for (int s = 0; s < S; s += W) sc[s] = 0.f;  // only slot 0 of every utterance is live
+    std::vector<uint8_t> fin((size_t)S, 0);
+    std::vector<int> st(BEAM_ST_COUNT, 0);
+    upload(beam_score, sc, stream); upload(beam_finished, fin, stream); upload(beam_state, st, stream); upload(beam_lo, P, stream);
+    HIPCHK(hipStreamSynchronize(stream));  // (host vectors above; and no earlier launch still writes the progress words)
+    __atomic_store_n(&beam_prog()[0], 0, __ATOMIC_RELAXED);
+    __atomic_store_n(&beam_prog()[1], 0, __ATOMIC_RELAXED);
+    beam_w_ = W; beam_dbg_S_ = S; beam_dbg_W_ = W;
+    enqueue_beam_round();
+    HIPCHK(hipGetLastError());
+  }
+  // The rounds after round 0, as run_resident's natural-EOS loop: `ahead` steps stay enqueued, the stop word is read from pinned
+  // memory without synchronising.  Returns the decode steps enqueued (at most `ahead` of them after the last round).
+  int beam_loop() {
+    const int ahead = std::max(1, knobs().eos_run_ahead.load());
+    const int limit = max_new - 1;
+    int steps = 0;
+    unsigned spins = 0;
+    while (steps < limit) {
+      if (__atomic_load_n(&beam_prog()[1], __ATOMIC_RELAXED)) break;
+      const int fin = __atomic_load_n(&beam_prog()[0], __ATOMIC_RELAXED);  // advance launches completed (round 0 = 1)
+      if (steps - std::max(fin - 1, 0) < ahead) {
+        decode_steps(1);
+        ++steps;
+        spins = 0;
+      } else if (++spins > 64) {
+        sched_yield();
+        if ((spins & 0xffff) == 0) {  // a device fault must end the wait: the progress words would never move again
+          const hipError_t q = hipStreamQuery(stream);
+          if (q != hipSuccess && q != hipErrorNotReady) HIPCHK(q);
+          if (q == hipSuccess && steps - std::max(__atomic_load_n(&beam_prog()[0], __ATOMIC_RELAXED) - 1, 0) >= ahead)
+            fail("beam loop: the stream drained but the device-side progress counter did not advance");
+        }
+      }
+    }
+    return steps;
+  }
+  std::vector<int> beam_state_host() {
+    std::vector<int> st(BEAM_ST_COUNT);
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipMemcpy(st.data(), beam_state.p, st.size() * 4, hipMemcpyDeviceToHost));
+    return st;
+  }
+  // hypotheses of every utterance, best first: out_ids [U][W][stride], out_lens / out_scores / out_finished [U][W], out_lp nullable
+  // [U][W][stride + 1] (per token, then the EOS's when finished)
+  void beam_fetch(int32_t* out, int stride, int32_t* out_lens, float* out_scores, uint8_t* out_fin, float* out_lp) {
+    if (beam_w_ <= 0) fail("q3a_beam_fetch: no beam search (call q3a_beam_begin first)");
+    const int W = beam_w_, S = B, U = B / W;
+    const int R = std::min(beam_state_host()[BEAM_ST_ROUNDS], max_new);
+    std::vector<int> hp((size_t)R * S), ht((size_t)R * S);
+    std::vector<float> hl((size_t)R * S), sc(S);
+    std::vector<uint8_t> fin(S);
+    if (R > 0) {
+      HIPCHK(hipMemcpy(hp.data(), beam_hist_parent.p, hp.size() * 4, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(ht.data(), beam_hist_token.p, ht.size() * 4, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(hl.data(), beam_hist_lp.p, hl.size() * 4, hipMemcpyDeviceToHost));
+    }
+    HIPCHK(hipMemcpy(sc.data(), beam_score.p, (size_t)S * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(fin.data(), beam_finished.p, (size_t)S, hipMemcpyDeviceToHost));
+    std::vector<int> toks;
+    std::vector<float> lps;
+    for (int u = 0; u < U; ++u) {
+      std::vector<int> order(W);
+      for (int j = 0; j < W; ++j) order[j] = j;
+      std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return sc[u * W + x] > sc[u * W + y]; });  // larger score, then smaller slot
+      for (int k = 0; k < W; ++k) {
+        const int q = u * W + order[k];
+        toks.clear(); lps.clear();
+        for (int r = R - 1, cur = q; r >= 0; --r) {  // back-pointers: round r put (token, lp) into slot `cur`, continuing slot parent
+          const size_t h = (size_t)r * S + cur;
+          if (ht[h] >= 0) { toks.push_back(ht[h]); lps.push_back(hl[h]); }
+          cur = hp[h];
+        }
+        std::reverse(toks.begin(), toks.end());
+        std::reverse(lps.begin(), lps.end());
+        const int n_lp = (int)toks.size();
+        if (fin[q] && !toks.empty()) toks.pop_back();  // the ids exclude the EOS; its log-probability stays
+        const int n = (int)toks.size();
+        if (n > stride) fail("q3a_beam_fetch: a hypothesis has " + std::to_string(n) + " ids, more than stride " + std::to_string(stride));
+        const size_t o = (size_t)u * W + k;
+        for (int i = 0; i < n; ++i) out[o * stride + i] = toks[i];
+        out_lens[o] = n;
+        if (out_scores) out_scores[o] = sc[q];
+        if (out_fin) out_fin[o] = fin[q];
+        if (out_lp)
+          for (int i = 0; i < n_lp && i < stride + 1; ++i) out_lp[o * (stride + 1) + i] = lps[i];
+      }
+    }
+  }
 
   // Graphs, streams and events go here, before the members: every DevBuf (taps included) frees itself after this body has run.
   // So the streams, the events and an owned arena now go BEFORE the workspace buffers (they used to go after).  The device-wide wait
@@ -1807,6 +1964,176 @@ int32_t q3a_score_batch_ptrs(q3a_engine* e, const float* const* pcm16k, const in
   Q3A_CATCH(e)
 }
 
+// ---- beam search ----------------------------------------------------------------------------------------------------------
+int32_t q3a_beam_begin(q3a_engine* e, int32_t width) {
+  if (!e) return 1;
+  Q3A_TRY(e)
+  e->require_asr("q3a_beam_begin");
+  HIPCHK(hipSetDevice(e->device));
+  e->beam_begin("q3a_beam_begin", width);
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipGetLastError());
+  Q3A_CATCH(e)
+}
+
+int32_t q3a_beam_step(q3a_engine* e, uint8_t* all_finished, float* logits_out) {
+  if (!e) return 1;
+  Q3A_TRY(e)
+  e->require_asr("q3a_beam_step");
+  HIPCHK(hipSetDevice(e->device));
+  if (e->beam_w_ <= 0 || !e->have_prefill) fail("q3a_beam_step: no beam search (call q3a_beam_begin first)");
+  if (e->beam_state_host()[BEAM_ST_ROUNDS] >= e->max_new) fail("q3a_beam_step: the round limit (max_new_tokens) is reached");
+  e->head_logits_ = true;
+  e->decode_steps(1);
+  const std::vector<int> st = e->beam_state_host();
+  HIPCHK(hipGetLastError());
+  if (all_finished) *all_finished = st[BEAM_ST_ALL_DONE] ? 1 : 0;
+  if (logits_out) HIPCHK(hipMemcpy(logits_out, e->logits.p, (size_t)e->B * e->d.vocab * 4, hipMemcpyDeviceToHost));
+  Q3A_CATCH(e)
+}
+
+int32_t q3a_beam_fetch(q3a_engine* e, int32_t* out_ids, int32_t stride, int32_t* out_lens, float* out_scores, uint8_t* out_finished,
+                       float* out_lp) {
+  if (!e) return 1;
+  Q3A_TRY(e)
+  e->require_asr("q3a_beam_fetch");
+  if (e->beam_w_ <= 0) fail("q3a_beam_fetch: no beam search (call q3a_beam_begin first)");
+  if (!out_lens || stride < 0 || (stride > 0 && !out_ids)) fail("q3a_beam_fetch: bad argument");
+  HIPCHK(hipSetDevice(e->device));
+  e->beam_fetch(out_ids, stride, out_lens, out_scores, out_finished, out_lp);
+  Q3A_CATCH(e)
+}
+
+int32_t q3a_beam_search_batch_ptrs(q3a_engine* e, const float* const* pcm16k, const int64_t* n_samples, int32_t U,
+                                   const int32_t* lang_prefix_ids, int32_t n_prefix, int32_t width, int32_t max_new, int32_t* out_ids,
+                                   int32_t stride, int32_t* out_lens, float* out_scores, uint8_t* out_finished, float* out_lp) {
+  if (!e) return 1;
+  Q3A_TRY(e)
+  e->require_asr("q3a_beam_search_batch");
+  if (!pcm16k || !n_samples || U < 1 || !out_lens || stride < 0 || (stride > 0 && !out_ids) || n_prefix < 0) fail("q3a_beam_search_batch: bad argument");
+  if (width < 1 || width > BEAM_MAX_W) fail("q3a_beam_search_batch: width must be 1..8");
+  if ((int64_t)U * width > 32) fail("q3a_beam_search_batch: utterances x width = " + std::to_string((int64_t)U * width) + " exceeds 32 sequences");
+  const int cap = e->opts.max_new_tokens, want = max_new <= 0 ? cap : std::min(max_new, cap);
+  if (stride < want) fail("q3a_beam_search_batch: stride " + std::to_string(stride) + " is below max_new " + std::to_string(want));
+  require_utterance_ptrs("q3a_beam_search_batch", pcm16k, U);
+  HIPCHK(hipSetDevice(e->device));
+  // the W slots of an utterance are W ordinary sequences of the batch: the clip is uploaded once per slot
+  const int S = U * width;
+  std::vector<const float*> ptrs((size_t)S);
+  std::vector<int64_t> ns((size_t)S);
+  for (int s = 0; s < S; ++s) { ptrs[s] = pcm16k[s / width]; ns[s] = n_samples[s / width]; }
+  e->fixed_mode_ = false;
+  e->head_logits_ = true;  // every round selects on the stored logits
+  e->have_prefill = false;
+  e->set_batch(ns.data(), S);
+  e->prepare_prompts(lang_prefix_ids, n_prefix, want, 0);
+  e->timings = q3a_timings{};
+  e->upload_ptrs_and_mel(ptrs.data(), ns.data(), S);
+  e->run_encoder();
+  HIPCHK(hipEventRecord(e->ev[2], e->stream));
+  e->run_prefill();
+  HIPCHK(hipEventRecord(e->ev[3], e->stream));
+  e->beam_begin("q3a_beam_search_batch", width);
+  e->beam_loop();
+  HIPCHK(hipEventRecord(e->ev[4], e->stream));
+  const std::vector<int> st = e->beam_state_host();
+  HIPCHK(hipGetLastError());
+  e->front_and_total_timings();
+  e->timings.prefill_ms = e->stage_ms(2, 3);
+  e->timings.decode_ms = e->stage_ms(3, 4);
+  e->timings.decode_steps = std::max(st[BEAM_ST_ROUNDS] - 1, 0); e->timings.batch = e->B; e->timings.total_audio_tokens = e->total_T;
+  e->timings.total_prompt_tokens = e->total_P;
+  e->beam_fetch(out_ids, stride, out_lens, out_scores, out_finished, out_lp);
+  // as after q3a_score: no decode state until the next prefill
+  e->beam_w_ = 0;
+  e->have_prefill = false;
+  Q3A_CATCH(e)
+}
+
+// ---- beam kernels on their own (no model): host arrays in, host arrays out, the product launches in between -------------------------
+int32_t q3a_selftest_beam_topk(int32_t device, const float* logits, int32_t S, int32_t V, int32_t W, int32_t* out_ids, float* out_lp) {
+  q3a_engine* e = nullptr;
+  Q3A_TRY(e)
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) fail("no HIP device available");
+  if (!logits || !out_ids || !out_lp || S < 1 || V < 1) fail("q3a_selftest_beam_topk: bad argument");
+  HIPCHK(hipSetDevice(device));
+  const int nc = beam_topk_chunks(V);
+  DevBuf dLg, dCv, dCi, dPm, dPs, dOi, dOl;
+  dLg.ensure((size_t)S * V * 4); dCv.ensure((size_t)S * nc * BEAM_MAX_W * 4); dCi.ensure((size_t)S * nc * BEAM_MAX_W * 4);
+  dPm.ensure((size_t)S * nc * 4); dPs.ensure((size_t)S * nc * 4); dOi.ensure((size_t)S * BEAM_MAX_W * 4); dOl.ensure((size_t)S * BEAM_MAX_W * 4);
+  HIPCHK(hipMemcpy(dLg.p, logits, (size_t)S * V * 4, hipMemcpyHostToDevice));
+  BeamTopkArgs t{dLg.as<float>(), S, V, W, dCv.as<float>(), dCi.as<int>(), dPm.as<float>(), dPs.as<float>(), dOi.as<int>(), dOl.as<float>()};
+  KCHK(launch_beam_topk(t, nullptr));
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(out_ids, dOi.p, (size_t)S * W * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out_lp, dOl.p, (size_t)S * W * 4, hipMemcpyDeviceToHost));
+  Q3A_CATCH(e)
+}
+
+int32_t q3a_selftest_beam_advance(int32_t device, int32_t U, int32_t W, const int32_t* topk_ids, const float* topk_lp, const float* score_in,
+                                  const uint8_t* finished_in, int32_t* parent_out, int32_t* token_out, float* score_out, uint8_t* finished_out) {
+  q3a_engine* e = nullptr;
+  Q3A_TRY(e)
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) fail("no HIP device available");
+  if (!topk_ids || !topk_lp || !score_in || !finished_in || !parent_out || !token_out || !score_out || !finished_out || U < 1 || W < 1 || W > BEAM_MAX_W || U * W > 32)
+    fail("q3a_selftest_beam_advance: bad argument");
+  HIPCHK(hipSetDevice(device));
+  const size_t S = (size_t)U * W;
+  DevBuf dTi, dTl, dSc, dFi, dPa, dTo, dSt;
+  dTi.ensure(S * W * 4); dTl.ensure(S * W * 4); dSc.ensure(S * 4); dFi.ensure(S); dPa.ensure(S * 4); dTo.ensure(S * 4); dSt.ensure(BEAM_ST_COUNT * 4);
+  HIPCHK(hipMemcpy(dTi.p, topk_ids, S * W * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dTl.p, topk_lp, S * W * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dSc.p, score_in, S * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dFi.p, finished_in, S, hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(dSt.p, 0, BEAM_ST_COUNT * 4));
+  BeamAdvanceArgs a{};
+  a.U = U; a.W = W; a.topk_ids = dTi.as<int>(); a.topk_lp = dTl.as<float>(); a.score = dSc.as<float>(); a.finished = dFi.as<uint8_t>();
+  a.parent = dPa.as<int>(); a.token = dTo.as<int>(); a.state = dSt.as<int>(); a.eos0 = kEos0; a.eos1 = kEos1;
+  KCHK(launch_beam_advance(a, nullptr));
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(parent_out, dPa.p, S * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(token_out, dTo.p, S * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(score_out, dSc.p, S * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(finished_out, dFi.p, S, hipMemcpyDeviceToHost));
+  Q3A_CATCH(e)
+}
+
+int32_t q3a_selftest_kv_reorder(int32_t device, void* cache, int32_t elem_bytes, int32_t layers, int32_t S, int32_t n_kv, int32_t max_ctx,
+                                const int32_t* lo, const int32_t* hi, const int32_t* parent) {
+  q3a_engine* e = nullptr;
+  Q3A_TRY(e)
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) fail("no HIP device available");
+  if (!cache || !lo || !hi || !parent || layers < 1 || S < 1 || S > 32 || n_kv < 1 || max_ctx < 1 || (elem_bytes != 2 && elem_bytes != 4))
+    fail("q3a_selftest_kv_reorder: bad argument");
+  for (int s = 0; s < S; ++s) {  // bounds before anything runs: a copy stays inside the cache and inside one utterance's rows
+    const int p = parent[s];
+    if (p < 0 || p >= S) fail("q3a_selftest_kv_reorder: parent out of range");
+    if (lo[s] < 0 || hi[s] >= max_ctx) fail("q3a_selftest_kv_reorder: rows outside the cache");
+    if (p != s && (lo[p] != lo[s] || hi[p] != hi[s])) fail("q3a_selftest_kv_reorder: a parent must share its child's row range (a slot of the same utterance)");
+  }
+  HIPCHK(hipSetDevice(device));
+  const size_t half = (size_t)layers * S * n_kv * max_ctx * 128 * elem_bytes;  // K, then V
+  DevBuf dC, dLo, dHi, dPar;
+  dC.ensure(2 * half); dLo.ensure((size_t)S * 4); dHi.ensure((size_t)S * 4); dPar.ensure((size_t)S * 4);
+  HIPCHK(hipMemcpy(dC.p, cache, 2 * half, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dLo.p, lo, (size_t)S * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dHi.p, hi, (size_t)S * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dPar.p, parent, (size_t)S * 4, hipMemcpyHostToDevice));
+  KvReorderArgs r{};
+  r.kcache = dC.p; r.vcache = (uint8_t*)dC.p + half; r.elem_bytes = elem_bytes; r.layers = layers; r.S = S; r.n_kv = n_kv; r.max_ctx = max_ctx;
+  r.parent = dPar.as<int>(); r.lo = dLo.as<int>(); r.hi = dHi.as<int>();
+  KCHK(launch_kv_reorder(r, nullptr));
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(cache, dC.p, 2 * half, hipMemcpyDeviceToHost));
+  Q3A_CATCH(e)
+}
+
 int32_t q3a_upload_pcm(q3a_engine* e, const float* pcm16k, const int64_t* n_samples, int32_t B) {
   if (!e) return 1;
   Q3A_TRY(e)
@@ -1869,6 +2196,7 @@ int32_t q3a_decode_step(q3a_engine* e, int32_t* next_ids, uint8_t* done, float* 
   if (!e) return 1;
   Q3A_TRY(e)
   e->require_asr("q3a_decode_step");
+  if (e->beam_w_ > 0) fail("q3a_decode_step: a beam search owns the decode state (q3a_beam_step; a new q3a_prefill returns to the greedy step)");
   HIPCHK(hipSetDevice(e->device));
   {
     // capacity guard: position of the token being fed must stay inside the cache
@@ -1891,7 +2219,7 @@ int32_t q3a_set_next_tokens(q3a_engine* e, const int32_t* ids, int32_t B) {
   if (!e) return 1;
   Q3A_TRY(e)
   HIPCHK(hipSetDevice(e->device));
-  if (!e->have_prefill || B != e->B) fail("q3a_set_next_tokens: no decode state / batch mismatch");
+  if (!e->have_prefill || B != e->B || e->beam_w_ > 0) fail("q3a_set_next_tokens: no decode state / batch mismatch");
   for (int s = 0; s < B; ++s)
     if (ids[s] < 0 || ids[s] >= e->d.vocab) fail("q3a_set_next_tokens: token id out of range");
   HIPCHK(hipMemcpy(e->forced_tok.p, ids, (size_t)B * 4, hipMemcpyHostToDevice));
@@ -2089,6 +2417,19 @@ int32_t q3a_debug_read(q3a_engine* e, const char* name, void* dst, uint64_t byte
   };
   for (const auto& sc : scalars)
     if (strcmp(name, sc.name) == 0) { give(sc.src, sc.n, sc.on_device); return 0; }
+  // the last round of the last beam search (tables of beam_dbg_S_ sequences x beam_dbg_W_)
+  const size_t bS = (size_t)e->beam_dbg_S_, bW = (size_t)e->beam_dbg_W_;
+  const struct { const char* name; const DevBuf* buf; size_t n; } beams[] = {
+      {"beam_topk_ids", &e->beam_topk_ids, bS * bW * 4}, {"beam_topk_lp", &e->beam_topk_lp, bS * bW * 4},
+      {"beam_parent", &e->beam_parent, bS * 4}, {"beam_token", &e->beam_token, bS * 4}, {"beam_score", &e->beam_score, bS * 4},
+      {"beam_finished", &e->beam_finished, bS}, {"beam_stats", &e->beam_state, 16},
+  };
+  for (const auto& bm : beams)
+    if (strcmp(name, bm.name) == 0) {
+      if (bS == 0) fail(std::string("q3a_debug_read: '") + name + "' before any beam search");
+      give(bm.buf->p, bm.n, true);
+      return 0;
+    }
   auto it = e->taps.find(name);
   if (it == e->taps.end()) fail(std::string("q3a_debug_read: no tap named '") + name + "' (opts.debug_taps set?)");
   give(it->second.p, e->tap_bytes[name], true);

@@ -391,4 +391,49 @@ const char* launch_argmax_finalize(const FinalizeArgs& a, int S, hipStream_t s);
 const char* launch_set_tokens(const int* tok, int S, const uint16_t* embed, int H, float* x_next, int* next_tok, hipStream_t s,
                               const NextNormOut& nn = NextNormOut{});
 
+// ---- beam search (k_beam.hip) --------------------------------------------------------------------------------
+constexpr int BEAM_MAX_W = 8;       // slots per utterance
+constexpr int BEAM_CHUNK = 2048;    // logits one workgroup of the top-W selection reads (8 per thread)
+constexpr int KV_REORDER_SLICES = 8;  // workgroups that share the rows of one (layer, K / V, kv head): a fixed grid, capturable
+inline int beam_topk_chunks(int V) { return (V + BEAM_CHUNK - 1) / BEAM_CHUNK; }
+// Per row of logits [S][V] (fp32, row stride V): the W best ids (larger logit, then smaller id; -inf is a legal logit and ranks
+// last) and lp = (l - m) - log sum exp(l - m) of each, m the row maximum, the sum in fp32 in a fixed order.  Any V >= W.
+struct BeamTopkArgs {
+  const float* logits; int S; int V; int W;
+  float* cand_val; int* cand_idx;    // workspace [S][beam_topk_chunks(V)][W]
+  float* part_max; float* part_sum;  // workspace [S][beam_topk_chunks(V)]
+  int* out_ids; float* out_lp;       // [S][W], best first
+};
+const char* launch_beam_topk(const BeamTopkArgs& a, hipStream_t s);
+// state words of a search (device ints, BeamAdvanceArgs::state); the first four are q3a_debug_read "beam_stats"
+enum { BEAM_ST_ROUNDS = 0, BEAM_ST_COPIES = 1, BEAM_ST_KV_ROWS = 2, BEAM_ST_FINISHED = 3, BEAM_ST_ALL_DONE = 4, BEAM_ST_LAUNCHES = 5, BEAM_ST_COUNT = 8 };
+// One round of U utterances x W slots (sequence u * W + j = slot j of utterance u), include/q3asr.h "beam search".  score / finished
+// are the state before the round and are overwritten with the state after it.  A launch that finds BEAM_ST_ALL_DONE set changes
+// nothing but BEAM_ST_LAUNCHES and host_progress[0].
+struct BeamAdvanceArgs {
+  int U, W;
+  const int* topk_ids; const float* topk_lp;  // [U * W][W] of launch_beam_topk
+  float* score; uint8_t* finished;            // [U * W]
+  int* parent;                                // [U * W] sequence the slot's new hypothesis continues (itself: no copy)
+  int* token;                                 // [U * W] the survivor's token: an EOS id when it finishes now, -1 for a hypothesis that was finished (or an empty slot)
+  int* feed;                                  // nullable [U * W]: the id the next step feeds (0 for a finished slot)
+  int* hist_parent; int* hist_token; float* hist_lp; int hist_cap;  // nullable [hist_cap][U * W]: row BEAM_ST_ROUNDS receives parent / token / lp
+  int* state;                                 // [BEAM_ST_COUNT]
+  const int* pos; const int* lo; int hi_bias; // nullable: rows lo[s] .. pos[s] + hi_bias are what a copy moves (BEAM_ST_KV_ROWS)
+  int* host_progress;                         // nullable pinned host words: [0] = BEAM_ST_LAUNCHES, [1] = 1 once every slot is finished
+  int eos0, eos1;
+};
+const char* launch_beam_advance(const BeamAdvanceArgs& a, hipStream_t s);
+// For every sequence j with parent[j] != j: rows lo[j] .. hi[j] + hi_bias of K and V, every layer and kv head, become a copy of the
+// same rows of sequence parent[j] as they were before the launch (parent[j] must share j's lo and hi: a slot of the same utterance).
+// Any permutation with cycles and fan-out; nothing outside those rows is read or written.
+struct KvReorderArgs {
+  void* kcache; void* vcache;  // [layers][S][n_kv][max_ctx][128] elements each
+  int elem_bytes;              // 2 (bf16) or 4 (fp32)
+  int layers, S, n_kv, max_ctx;
+  const int* parent; const int* lo; const int* hi; int hi_bias;
+  const int* all_done;         // nullable device word: non-zero = do nothing
+};
+const char* launch_kv_reorder(const KvReorderArgs& a, hipStream_t s);
+
 }  // namespace q3a

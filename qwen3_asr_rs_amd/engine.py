@@ -56,6 +56,7 @@ class HipEngine:
         opts.valu_attention = int(valu_attention)
         opts.token_logprobs = int(token_logprobs)
         self.token_logprobs = bool(token_logprobs)
+        self.max_new_tokens = int(max_new_tokens) if int(max_new_tokens) > 0 else 4096
         md = os.fsencode(model_dir)
         if device_arena is None:
             rc = self._lib.q3a_engine_create(md, device, C.byref(opts), C.byref(self._h))
@@ -334,6 +335,74 @@ class HipEngine:
         self.batch = B
         return self._score_split(tl, lp, ti, tp)
 
+    # ---- beam search ----------------------------------------------------------------------------------
+    def _beam_unpack(self, U, W, stride, ids, lens, scores, fin, lp) -> "List[List[BeamHypothesis]]":
+        res = []
+        for u in range(U):
+            hyps = []
+            for k in range(W):
+                n, f = int(lens[u, k]), bool(fin[u, k])
+                hyps.append(BeamHypothesis(ids[u, k, :n].tolist(), float(scores[u, k]), f, lp[u, k, :n + (1 if f else 0)].copy()))
+            res.append(hyps)
+        return res
+
+    def beam_search_batch(self, clips: Sequence[np.ndarray], width: int, lang_prefix_ids: Optional[Sequence[int]] = None,
+                          max_new: int = 0) -> "List[List[BeamHypothesis]]":
+        """Whole path (q3a_beam_search_batch_ptrs): per clip its `width` hypotheses, best first (larger score, then smaller slot).
+        max_new <= 0: the engine's max_new_tokens."""
+        arrs, ptrs, ns = self._ptrs(clips)
+        U, W = len(arrs), int(width)
+        stride = max(1, min(int(max_new), self.max_new_tokens) if max_new > 0 else self.max_new_tokens)
+        shape = (max(U, 1), max(W, 1))
+        ids = np.zeros(shape + (stride,), dtype=np.int32)
+        lens = np.zeros(shape, dtype=np.int32)
+        scores = np.zeros(shape, dtype=np.float32)
+        fin = np.zeros(shape, dtype=np.uint8)
+        lp = np.zeros(shape + (stride + 1,), dtype=np.float32)
+        pre = np.asarray(lang_prefix_ids if lang_prefix_ids is not None else [], dtype=np.int32)
+        self._chk(self._lib.q3a_beam_search_batch_ptrs(self._h, ptrs, _i64p(ns), U, _i32p(pre) if len(pre) else None, len(pre), W, int(max_new),
+                                                       _i32p(ids), stride, _i32p(lens), _f32p(scores), fin.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                       _f32p(lp)))
+        self.batch = U * W
+        return self._beam_unpack(U, W, stride, ids, lens, scores, fin, lp)
+
+    def beam_begin(self, width: int):
+        """Stage form (q3a_beam_begin), directly after prefill() of U * width sequences in which each utterance appears `width` times
+        in a row: round 0 on the prefill's logits."""
+        self._chk(self._lib.q3a_beam_begin(self._h, int(width)))
+        self._beam_width = int(width)
+
+    def beam_step(self, want_logits: bool = False):
+        """One decode step and its round (q3a_beam_step).  Returns (all_finished, logits [S][vocab] the round selected from or None)."""
+        done = C.c_uint8()
+        logits = np.zeros((self.batch, self.dims.vocab_size), dtype=np.float32) if want_logits else None
+        self._chk(self._lib.q3a_beam_step(self._h, C.byref(done), _f32p(logits) if want_logits else None))
+        return bool(done.value), logits
+
+    def beam_fetch(self, stride: Optional[int] = None) -> "List[List[BeamHypothesis]]":
+        """The hypotheses after the rounds run so far (q3a_beam_fetch), per utterance best first."""
+        W = int(getattr(self, "_beam_width", 0))
+        if W <= 0:
+            self._chk(self._lib.q3a_beam_fetch(self._h, None, 0, None, None, None, None))  # (the engine's own refusal)
+        U = self.batch // W
+        stride = int(stride) if stride is not None else self.max_new_tokens
+        ids = np.zeros((U, W, stride), dtype=np.int32)
+        lens = np.zeros((U, W), dtype=np.int32)
+        scores = np.zeros((U, W), dtype=np.float32)
+        fin = np.zeros((U, W), dtype=np.uint8)
+        lp = np.zeros((U, W, stride + 1), dtype=np.float32)
+        self._chk(self._lib.q3a_beam_fetch(self._h, _i32p(ids), stride, _i32p(lens), _f32p(scores), fin.ctypes.data_as(C.POINTER(C.c_uint8)), _f32p(lp)))
+        return self._beam_unpack(U, W, stride, ids, lens, scores, fin, lp)
+
+    def beam_debug(self) -> dict:
+        """The last round of the last beam search (q3a_debug_read "beam_*"): topk_ids / topk_lp [S][W], parent / token / score /
+        finished [S], stats int32 [4] (rounds run, survivors that needed a copy, KV rows copied, hypotheses finished)."""
+        raw = {n: self.debug_read_raw("beam_" + n) for n in ("topk_ids", "topk_lp", "parent", "token", "score", "finished", "stats")}
+        S = len(raw["finished"])
+        return {"topk_ids": raw["topk_ids"].view(np.int32).reshape(S, -1), "topk_lp": raw["topk_lp"].view(np.float32).reshape(S, -1),
+                "parent": raw["parent"].view(np.int32), "token": raw["token"].view(np.int32), "score": raw["score"].view(np.float32),
+                "finished": raw["finished"].copy(), "stats": raw["stats"].view(np.int32)}
+
     def debug_read_raw(self, name: str) -> np.ndarray:
         """The same as bytes (records of mixed types: tools/soak_engines.py)."""
         n = C.c_uint64()
@@ -451,6 +520,24 @@ from .audio import AsrTokenizer, capitalize_first, fix_timestamps, load_audio, p
 
 
 @dataclass
+class BeamHypothesis:
+    """One hypothesis of a beam search: ids (EOS excluded), score = the sum of its tokens' natural-log probabilities (the EOS's included
+    when it finished), finished, and the log-probability of every id followed by the EOS's when finished (float32)."""
+    ids: List[int]
+    score: float
+    finished: bool
+    token_logprobs: np.ndarray
+
+
+@dataclass
+class Alternative:
+    """An entry of TranscribeResult.alternatives: decoded text, the search's score (before any length penalty) and the ids."""
+    text: str
+    score: float
+    ids: List[int]
+
+
+@dataclass
 class TranscribeResult:
     """src/inference.rs:269-274 (+ the raw ids, which is where parity is pinned).  With an engine created with token_logprobs=True
     also the log-probability of every id and their mean (Whisper's avg_logprob; None when no token was generated)."""
@@ -460,6 +547,7 @@ class TranscribeResult:
     ids: List[int]
     token_logprobs: Optional[List[float]] = None
     avg_logprob: Optional[float] = None
+    alternatives: Optional[List[Alternative]] = None  # beam_size > 1: the n-best list, best first (this result is its first entry)
 
 
 @dataclass
@@ -491,8 +579,11 @@ class AsrInference:
             tok = AsrTokenizer(tj)
         return cls(eng, tok)
 
-    def transcribe(self, audio, language: Optional[str] = None, max_new_tokens: int = 4096) -> TranscribeResult:
-        """src/inference.rs:89-213.  `audio`: path to a WAV file or a 16 kHz float32 array."""
+    def transcribe(self, audio, language: Optional[str] = None, max_new_tokens: int = 4096, beam_size: int = 1,
+                   length_penalty: float = 0.0) -> TranscribeResult:
+        """src/inference.rs:89-213.  `audio`: path to a WAV file or a 16 kHz float32 array.  beam_size > 1: a beam search of that
+        width instead of the greedy loop; `alternatives` holds its hypotheses ordered by score / max(len, 1) ** length_penalty
+        (float64 on the host; 0: the search's own order) and the result is the first of them."""
         if isinstance(audio, (str, os.PathLike)):
             samples = load_audio(os.fspath(audio), 16000)
         else:
@@ -502,6 +593,20 @@ class AsrInference:
             if self.tokenizer is None:
                 raise Q3aError("forcing a language needs tokenizer.json (src/inference.rs:246-251)")
             prefix = self.tokenizer.encode("language " + capitalize_first(language))
+        if beam_size > 1:
+            hyps = self.engine.beam_search_batch([samples], beam_size, prefix, min(max_new_tokens, self.engine.max_new_tokens))[0]
+            hyps = [h for h in hyps if h.score > -np.inf]
+            if length_penalty != 0.0:  # (stable: equal keys keep the search's order)
+                hyps = sorted(hyps, key=lambda h: -(float(h.score) / float(max(len(h.ids) + int(h.finished), 1)) ** float(length_penalty)))
+            alts = []
+            for h in hyps:
+                raw = self.tokenizer.decode(h.ids, True) if self.tokenizer is not None else ""
+                alts.append((Alternative(parse_asr_output(raw, language is not None)[1], h.score, h.ids), raw, h))
+            alt, raw, best = alts[0]
+            lang = parse_asr_output(raw, language is not None)[0]
+            lps = best.token_logprobs[:len(best.ids)]
+            return TranscribeResult(alt.text, lang, raw, best.ids, [float(v) for v in lps],
+                                    float(np.mean(lps, dtype=np.float64)) if len(lps) else None, [a for a, _, _ in alts])
         ids = self.engine.transcribe_batch([samples], prefix, max_new_tokens)[0]
         raw = self.tokenizer.decode(ids, True) if self.tokenizer is not None else ""
         lang, text = parse_asr_output(raw, language is not None)
