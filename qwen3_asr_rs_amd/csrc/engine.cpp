@@ -16,8 +16,6 @@
 
 #include <sched.h>
 
-#include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -25,13 +23,9 @@
 #include <map>
 #include <memory>
 #include <mutex>
-#include <string>
 #include <thread>
-#include <vector>
 
-#include "../../include/q3asr.h"
-#include "kernels.h"
-#include "model.h"
+#include "engine_internal.h"
 
 using namespace q3a;
 
@@ -39,52 +33,10 @@ namespace {
 
 thread_local std::string g_last_error;
 
-#define HIPCHK(expr)                                                                                    \
-  do {                                                                                                  \
-    hipError_t _e = (expr);                                                                             \
-    if (_e != hipSuccess)                                                                               \
-      fail(std::string("HIP error: ") + hipGetErrorString(_e) + " at " + __FILE__ + ":" + std::to_string(__LINE__) + " (" #expr ")"); \
-  } while (0)
-#define KCHK(expr)                                  \
-  do {                                              \
-    const char* _m = (expr);                        \
-    if (_m) fail(std::string("kernel launch: ") + _m); \
-  } while (0)
-
-constexpr int kAudioPad = 151676, kEos0 = 151643, kEos1 = 151645;  // src/tokenizer.rs:52-59
 // Decode-step projections: fp32-x GEMV kernels up to this many sequences, the skinny MFMA GEMM above.  Measured
 // (0.6B, 100 tokens): 2 sequences 96.6 ms on the GEMV path; 4 sequences 141 ms on it against 111 ms for FIVE
 // sequences on the skinny path.
 constexpr int kGemvMaxSeq = 2;
-
-// bytes of device memory all DevBufs of the process hold right now (q3a_debug_read "device_bytes")
-std::atomic<uint64_t> g_device_bytes{0};
-
-// One device allocation and its owner, move-only: freed when it goes out of scope (engine members, taps, locals of the selftests)
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  bool grew = false;
-  DevBuf() = default;
-  DevBuf(DevBuf&& o) noexcept { *this = std::move(o); }
-  DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); std::swap(grew, o.grew); return *this; }  // (o frees what this held)
-  ~DevBuf() { release(); }
-  void ensure(size_t bytes) {
-    if (bytes <= cap) return;
-    release();
-    size_t want = (bytes + 255) & ~size_t(255);
-    HIPCHK(hipMalloc(&p, want));
-    cap = want;
-    g_device_bytes += want;
-    grew = true;
-  }
-  void release() {
-    if (p) { (void)hipFree(p); g_device_bytes -= cap; }
-    p = nullptr;
-    cap = 0;
-  }
-  template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
-};
 
 template <typename T>
 void upload(DevBuf& b, const std::vector<T>& v, hipStream_t s) {
@@ -119,9 +71,6 @@ void require_utterance_ptrs(const char* what, const float* const* ptrs, int B) {
 
 }  // namespace
 
-namespace q3a {
-void set_thread_error(const std::string& msg) { g_last_error = msg; }  // used by host_abi.cpp
-}  // namespace q3a
 // A/B knobs (kernels.h Knobs: defaults and what each one does).  ONE table names them: q3a_debug_set looks its key up here, and
 // knobs() reads the environment names exactly once (atomics afterwards: q3a_debug_set writes them while q3a_group_transcribe may
 // have one host thread per GPU reading them).  include/q3asr.h documents the keys; tests/test_host.py compares the two.
@@ -153,6 +102,389 @@ Knobs& knobs() {
 }
 }  // namespace q3a
 
+namespace {
+
+// Debug taps, device copies by name for q3a_debug_read.  opts.debug_taps: 1 = every tap; 2 = only the small ones a soak run compares
+struct Taps {
+  std::map<std::string, DevBuf> bufs;  std::map<std::string, size_t> bytes;  // by name: the copy, and the bytes of it that are valid
+  DevBuf& reserve(const char* name, size_t n) { DevBuf& t = bufs[name]; t.ensure(n); bytes[name] = n; return t; }
+  static bool light(const char* name) { return strcmp(name, "dec_last_hidden") == 0 || strcmp(name, "head_in") == 0; }
+  void copy(int level, hipStream_t s, const char* name, const void* ptr, size_t n) {
+    if (!level || n == 0 || (level == 2 && !light(name))) return;
+    HIPCHK(hipMemcpyAsync(reserve(name, n).p, ptr, n, hipMemcpyDeviceToDevice, s));
+  }
+};
+
+// All the captured decode step sees of its owner: configuration, streams and the per-batch scalars, every one a read-only
+// reference to the owner's own word (so nothing is copied and nothing can go stale), and the rules that follow from them alone.
+struct StepView {
+  const Dims& d; const ArenaLayout& L; const q3a_opts& opts;
+  uint8_t* const& arena; const uint32_t& arena_flags; const hipStream_t& stream;
+  const std::vector<hipStream_t>& chain_streams;  // one per sequence group after the first, made by the owner before a step forks
+  const std::vector<hipEvent_t>& join_ev; const hipEvent_t& fork_ev; const int& n_cu; int* const& host_prog_dev;  // (pinned progress words, device view)
+  std::vector<ProfEvent>* const& prof; Taps& taps;  // prof not null: every launch between a pair of events
+  const int8_t* const& lm_q; const float* const& lm_qs; const int& lm_q_cols;  // int8 lm_head copy: set once at init, never moved
+  const int &B, &max_ctx, &max_new, &gsize, &live_nsplit_, &attn_nsplit, &min_P_, &part_stride, &beam_w_;
+  const size_t& kv_layer_elems; const bool& head_logits_;
+  const int &k_parallel_groups, &k_skinny_q, &k_dattn_batched_min_wgs, &k_skinny_glu_hp3, &k_lm_head_prune;  // knobs as latched per batch
+
+  bool precise() const { return opts.precise != 0; }
+  bool token_lp() const { return opts.token_logprobs != 0; }
+  bool kv_f32() const { return opts.precise != 0; }
+  size_t kv_elem() const { return kv_f32() ? 4 : 2; }
+  int fast_math() const { return precise() ? 0 : 1; }  // GemvArgs / SkinnyArgs::fast_math, the merge's fast exp
+  template <typename T> const T* w(uint64_t off) const { return reinterpret_cast<const T*>(arena + off); }
+  const float* wf(uint64_t off) const { return w<float>(off); }
+  const uint16_t* wh(uint64_t off) const { return w<uint16_t>(off); }
+};
+
+// The captured decode step as one unit: every DevBuf a launch of the step reads or writes, and every function that enqueues
+// such a launch or computes its arguments from buffers.  The rest of the engine is reachable through StepView only, so a step
+// function cannot name a buffer that the two guards against a stale graph do not cover: the reallocation sweep of setup_prompts
+// and the address hash of make_graph_sig both walk each_buf().  Sizing stays with the owner (setup_prompts, beam_begin, ensure_rope).
+struct DecodeStep : StepView {
+  DevBuf kcache, vcache, x_dec, d_pos, next_tok, out_ids, step_count, done, s_ln, s_qkv, s_ctx, s_act, logits, part_val, part_idx;
+  DevBuf part_sum, out_lp;  // opts.token_logprobs: log-sum channel of the argmax partials, [B][max_new] log-probabilities next to out_ids
+  DevBuf blk_lo, blk_hi;  // pruned lm_head argmax: per 16-row block bounds (pass 1 -> pass 2)
+  DevBuf prune_stats;     // [2] candidate blocks rescored, pass-2 launches (q3a_debug_read "lm_head_prune_stats"; never read by the step)
+  DevBuf attn_pm, attn_pl, attn_po, nn_x, nn_ss;  // nn_*: pre-normalised residual row for the next skinny GEMM: [32 * hidden] bf16 fragment order, [hidden/16][32] f32
+  // rope_cur: [B][128] cos|sin row of each sequence's current position (kept by argmax_finalize for decode attention); the tables: ensure_rope
+  DevBuf rope_cur, rope_cos, rope_sin;
+  DevBuf n_done, forced_tok;  // n_done: device counter of sequences that have produced their EOS (argmax_finalize)
+  DevBuf beam_cand_val, beam_cand_idx, beam_part_max, beam_part_sum, beam_topk_ids, beam_topk_lp, beam_score, beam_finished, beam_parent, beam_token;
+  DevBuf beam_feed, beam_hist_parent, beam_hist_token, beam_hist_lp, beam_state, beam_lo;
+  // f(buffer) for every DevBuf declared above, in declaration order (s: a DecodeStep, const or not).  The declarations of this
+  // struct ARE the guarded set: tests/test_host.py::test_step_buffers_cover_the_captured_step compares this list with them.
+  template <class Self, class F> static void each_buf(Self& s, F&& f) {
+    for (auto* b : {&s.kcache, &s.vcache, &s.x_dec, &s.d_pos, &s.next_tok, &s.out_ids, &s.step_count, &s.done, &s.s_ln, &s.s_qkv, &s.s_ctx, &s.s_act, &s.logits,
+                    &s.part_val, &s.part_idx, &s.part_sum, &s.out_lp, &s.blk_lo, &s.blk_hi, &s.prune_stats, &s.attn_pm, &s.attn_pl, &s.attn_po, &s.nn_x, &s.nn_ss,
+                    &s.rope_cur, &s.rope_cos, &s.rope_sin, &s.n_done, &s.forced_tok,
+                    &s.beam_cand_val, &s.beam_cand_idx, &s.beam_part_max, &s.beam_part_sum, &s.beam_topk_ids, &s.beam_topk_lp, &s.beam_score, &s.beam_finished,
+                    &s.beam_parent, &s.beam_token, &s.beam_feed, &s.beam_hist_parent, &s.beam_hist_token, &s.beam_hist_lp, &s.beam_state, &s.beam_lo})
+      f(*b);
+  }
+
+  void tap(const char* name, const void* ptr, size_t bytes) { taps.copy(opts.debug_taps, stream, name, ptr, bytes); }
+  // run fn() (which enqueues exactly one kernel class) optionally bracketed by events
+  template <class F> void timed(int kclass, double bytes, F&& fn) {
+    if (!prof) return fn();
+    ProfEvent pe{kclass, bytes, nullptr, nullptr};
+    HIPCHK(hipEventCreate(&pe.a));
+    HIPCHK(hipEventCreate(&pe.b));
+    HIPCHK(hipEventRecord(pe.a, stream));
+    fn();
+    HIPCHK(hipEventRecord(pe.b, stream));
+    prof->push_back(pe);
+  }
+
+  void* kc_layer(int l) { return (uint8_t*)kcache.p + (size_t)l * kv_layer_elems * kv_elem(); }
+  void* vc_layer(int l) { return (uint8_t*)vcache.p + (size_t)l * kv_layer_elems * kv_elem(); }
+
+  LmHeadPruneArgs prune_args(const GemvArgs& g) {
+    LmHeadPruneArgs pa{};
+    pa.g = g; pa.Wq = lm_q; pa.qcols = lm_q_cols; pa.qs = lm_qs;
+    pa.blk_lo = blk_lo.as<float>(); pa.blk_hi = blk_hi.as<float>(); pa.stats = prune_stats.as<int>();
+    return pa;
+  }
+
+  // final norm + lm_head on x_dec -> logits (+ block argmax partials), then argmax/finalize
+  void run_head(int advance) {
+    const int S = B, H = d.hidden, V = d.vocab;
+    tap("head_in", x_dec.p, (size_t)S * H * 4);  // (debug taps) last-layer residual rows the final norm + lm_head read
+    const double wbytes = 2.0 * V * H;
+    int n_part = 0;
+    // the argmax partials every producer below writes and argmax_finalize merges; with token log-probabilities also their log-sum
+    // channel (null: off, the kernels without it)
+    const ArgmaxPartials part{part_val.as<float>(), part_idx.as<int>(), token_lp() ? part_sum.as<float>() : nullptr, part_stride};
+    if (S <= kGemvMaxSeq) {
+      GemvArgs g{};
+      g.fast_math = fast_math();
+      g.x = x_dec.as<float>(); g.ldx = H; g.rms_w = wf(L.final_norm); g.eps = d.rms_eps;
+      g.W = wh(L.lm_head); g.N = V; g.K = H; g.mode = 3; g.out = logits.as<float>(); g.ldo = V;
+      g.part = part;
+      // (with the log-sum channel lm_head_prune_check refuses: the pruned argmax never computes most logits, the full GEMV runs)
+      LmHeadPruneArgs pa{};
+      const bool prunable = S == 1 && !precise() && lm_q_cols > 0 && (pa = prune_args(g), !lm_head_prune_check(pa));
+      if (prunable && opts.debug_taps == 1) {  // (debug taps) approximate logits and their bounds next to the stored logits
+        // a debug buffer outside each_buf(): reached only with debug_taps == 1, and V * 8 bytes whatever the batch, so it is
+        // allocated once per engine and no captured launch can outlive its address
+        DevBuf& t = taps.reserve("lm_head_bound", (size_t)V * 8);
+        LmHeadPruneArgs pd = pa;
+        pd.dbg = t.as<float>(); pd.stats = nullptr;
+        KCHK(launch_lm_head_approx(pd, stream));
+      }
+      if (prunable && k_lm_head_prune && !head_logits_) {
+        // nobody reads the logits: the exact argmax from the int8 pre-pass + a bf16 rescore of the candidate blocks
+        g.out = nullptr; pa.g.out = nullptr;
+        n_part = lm_head_rescore_groups(g, n_cu);
+        timed(Q3A_KC_GEMV_LM_HEAD, (double)V * lm_q_cols, [&] { KCHK(launch_lm_head_approx(pa, stream)); });
+        timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_lm_head_rescore(pa, n_part, stream)); });
+      } else {
+        n_part = gemv_blocks(g);
+        timed(Q3A_KC_GEMV_LM_HEAD, wbytes, [&] { KCHK(launch_gemv(g, S, stream)); });
+      }
+    } else if (!precise()) {
+      // default mode: bf16 normed rows, then the LDS-DMA GEMM at M = S (32-row tiles) -- the vocabulary matrix is
+      // streamed once through double-buffered LDS; the skinny kernel re-reads x per 16 vocabulary rows (3x slower here)
+      timed(Q3A_KC_NORM, 0, [&] { KCHK(launch_rmsnorm(x_dec.as<float>(), wf(L.final_norm), s_ln.as<float>(), S, H, d.rms_eps, stream, s_ln.as<uint16_t>())); });
+      GemmEpilogue ep; ep.out = logits.as<float>(); ep.ldo = V;
+      if (S <= 32 && V % 4 == 0 && H % 64 == 0 && part_stride >= (V + 63) / 64) {
+        // the argmax partials are the GEMM's epilogue (one per 64-column tile and row), and inside q3a_transcribe_batch /
+        // q3a_run_resident nobody reads the logits: they are not stored (19 MB per step at 32 sequences)
+        ep.part = part;
+        if (!head_logits_) ep.out = nullptr;
+        n_part = (V + 63) / 64;
+        timed(Q3A_KC_GEMM, wbytes, [&] { KCHK(launch_gemm16(s_ln.as<uint16_t>(), H, wh(L.lm_head), S, V, H, ep, false, stream)); });
+      } else {
+        timed(Q3A_KC_GEMM, wbytes, [&] { KCHK(launch_gemm16(s_ln.as<uint16_t>(), H, wh(L.lm_head), S, V, H, ep, false, stream)); });
+        n_part = 128;
+        timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_partials(logits.as<float>(), V, S, part, n_part, stream)); });
+      }
+    } else {
+      timed(Q3A_KC_NORM, 0, [&] { KCHK(launch_rmsnorm(x_dec.as<float>(), wf(L.final_norm), s_ln.as<float>(), S, H, d.rms_eps, stream)); });
+      timed(Q3A_KC_GEMM, wbytes, [&] { batched_proj(s_ln.as<float>(), H, wh(L.lm_head), V, H, nullptr, 0, logits.as<float>(), V, nullptr); });
+      n_part = 128;
+      timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_partials(logits.as<float>(), V, S, part, n_part, stream)); });
+    }
+    FinalizeArgs f{};
+    f.part = part; f.n_part = n_part; f.out_lp = part.sum ? out_lp.as<float>() : nullptr;
+    f.V = V; f.next_tok = next_tok.as<int>(); f.out_ids = out_ids.as<int>();
+    f.out_stride = max_new; f.step_count = step_count.as<int>(); f.pos = d_pos.as<int>(); f.advance = advance;
+    f.done = done.as<uint8_t>(); f.n_done = n_done.as<int>(); f.n_seq = S; f.host_progress = host_prog_dev; f.embed = wh(L.embed); f.H = H; f.x_next = x_dec.as<float>(); f.eos0 = kEos0; f.eos1 = kEos1;
+    f.cos_t = rope_cos.as<float>(); f.sin_t = rope_sin.as<float>(); f.rope_cur = rope_cur.as<float>();
+    f.nn = first_layer_norm_out();
+    timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_finalize(f, S, stream)); });
+  }
+
+  // Skinny decode path in the default mode: every kernel that writes a row of the residual stream (token embedding,
+  // o / down projection) also leaves it pre-normalised for the GEMM that reads it next -- bf16(x * w_norm) in MFMA
+  // fragment order in nn_x plus partial sums of x^2 in nn_ss (kernels.h NextNormOut / SkinnyArgs::xw16f).
+  bool prenorm_path() const { return B > kGemvMaxSeq && !precise(); }
+  // o / down projections of the batched decode step as 8-row x 16-sequence workgroups (k_skinny.hip QS; Q3A_SKINNY_Q=0: off)
+  bool skinny_q() const {
+    auto whole = [](int K) { const int st = K / 32, per = (st + 7) / 8, unr = per <= 2 ? 2 : per <= 4 ? 4 : per <= 8 ? 8 : 12; return K % 256 == 0 && per % unr == 0; };
+    return k_skinny_q != 0 && !precise() && d.hidden % 64 == 0 && whole(d.q_dim()) && whole(d.inter);
+  }
+  int nn_parts() const { return d.hidden / (skinny_q() ? 8 : 16); }  // one partial per 16- (8-) column block of a hidden-wide GEMM output
+  // Batched decode (more than kGemvMaxSeq sequences) runs in groups of <= 32 sequences: the skinny MFMA GEMM holds 32
+  // sequences per weight sweep, and the second group's sweep of a 4-13 MB matrix is served by the L2 / Infinity Cache.
+  int n_groups(int b) const { return b <= kGemvMaxSeq ? 1 : (b + gsize - 1) / gsize; }
+  size_t nn_x_stride() const { return (size_t)32 * d.hidden; }         // elements per group
+  size_t nn_ss_stride() const { return (size_t)nn_parts() * 32; }
+  uint16_t* nn_x_g(int g) const { return nn_x.as<uint16_t>() + (size_t)g * nn_x_stride(); }
+  float* nn_ss_g(int g) const { return nn_ss.as<float>() + (size_t)g * nn_ss_stride(); }
+  float* s_ctx_g(int g) const { return s_ctx.as<float>() + (size_t)g * 32 * d.q_dim(); }   // fp32 [S][QD] or bf16 fragment order
+  float* s_act_g(int g) const { return s_act.as<float>() + (size_t)g * 32 * d.inter; }
+  NextNormOut first_layer_norm_out() const {
+    NextNormOut nn{};
+    if (prenorm_path()) {
+      nn.next_w = wf(L.dec[0].in_ln); nn.next_xw16f = nn_x.as<uint16_t>(); nn.next_ss = nn_ss.as<float>(); nn.nparts = nn_parts();
+      nn.group_stride_x = (long)nn_x_stride(); nn.group_stride_ss = (long)nn_ss_stride(); nn.group_size = gsize;
+    }
+    return nn;
+  }
+
+  // decode-step projection for more than 4 sequences: skinny MFMA GEMM up to 32, generic tiles above
+  void batched_proj(const float* x, int ldx, const uint16_t* W, int N, int K, const float* bias, int mode, float* out,
+                    int ldo, const float* resid) {
+    const int S = B;  // (precise-mode lm_head only)
+    if (S <= 32) {
+      SkinnyArgs sk{};
+      sk.fast_math = fast_math();
+      sk.x = x; sk.ldx = ldx; sk.S = S; sk.W = W; sk.N = N; sk.K = K; sk.bias = bias; sk.mode = mode; sk.out = out; sk.ldo = ldo; sk.resid = resid;
+      KCHK(launch_skinny(sk, precise(), stream));
+    } else {
+      GemmEpilogue ep; ep.out = out; ep.ldo = ldo; ep.bias = bias; ep.resid = (mode == 1) ? resid : nullptr;
+      KCHK(launch_gemm(x, ldx, W, S, N, K, ep, mode == 2, precise(), stream));
+    }
+  }
+
+  // The four projections of a decoder layer, stated ONCE for every path that launches them (decode_layer's GEMV and skinny forms,
+  // q3a_profile_weight_stream).  A caller starts its kernel arguments from one with gemv_args / skinny_args and sets only what its
+  // path adds: x and out pointers, the norm source, fragment flags, next-norm outputs.
+  struct Proj {
+    const uint16_t* W;  // [N][K] bf16
+    int N, K;
+    const float* bias;  // null: the checkpoint has none (arena flags)
+    int mode;           // GemvArgs / SkinnyArgs::mode: 0 plain, 1 + residual, 2 SiLU(gate) * up of interleaved rows -> N / 2 columns
+    int kclass;         // profile class of its GEMV (the skinny path books every projection as Q3A_KC_GEMM)
+    double bytes;       // weight bytes one launch streams
+  };
+  struct LayerProjs { Proj qkv, o, gu, down; };
+  LayerProjs layer_projs(int li) const {
+    const DecLayerOff& l = L.dec[li];
+    const int H = d.hidden, I = d.inter, QD = d.q_dim(), QKV = d.qkv_dim();
+    auto proj = [&](uint64_t w_off, int N, int K, uint32_t bias_flag, uint64_t b_off, int mode, int kclass) {
+      return Proj{wh(w_off), N, K, (arena_flags & bias_flag) ? wf(b_off) : nullptr, mode, kclass, 2.0 * N * K};
+    };
+    return {proj(l.qkv_w, QKV, H, kFlagDecQkvBias, l.qkv_b, 0, Q3A_KC_GEMV), proj(l.o_w, H, QD, kFlagDecOBias, l.o_b, 1, Q3A_KC_GEMV_O),
+            proj(l.gu_w, 2 * I, H, kFlagDecMlpBias, l.gu_b, 2, Q3A_KC_GEMV), proj(l.down_w, H, I, kFlagDecMlpBias, l.down_b, 1, Q3A_KC_GEMV_DOWN)};
+  }
+  template <class Args> Args proj_args(const Proj& p) const {  // the fields GemvArgs and SkinnyArgs share
+    Args a{};
+    a.fast_math = fast_math(); a.eps = d.rms_eps;  // (eps: read only where a norm source is set)
+    a.W = p.W; a.N = p.N; a.K = p.K; a.ldx = p.K; a.bias = p.bias; a.mode = p.mode; a.ldo = p.mode == 2 ? p.N / 2 : p.N;
+    return a;
+  }
+  GemvArgs gemv_args(const Proj& p) const { return proj_args<GemvArgs>(p); }
+  SkinnyArgs skinny_args(const Proj& p, int S) const { SkinnyArgs k = proj_args<SkinnyArgs>(p); k.S = S; return k; }
+
+  // one decoder layer of the greedy-loop iteration (inference.rs:172-197) for sequences [s0, s0 + S) -- the whole batch on
+  // the GEMV path, one group of <= 32 on the skinny MFMA path
+  void decode_layer(int li, int grp, int s0, int S, hipStream_t ks) {
+    const int H = d.hidden, QKV = d.qkv_dim();
+    const bool gemv = B <= kGemvMaxSeq;
+    const DecLayerOff& l = L.dec[li];
+    const LayerProjs pj = layer_projs(li);
+    float* const x = x_dec.as<float>() + (size_t)s0 * H;
+    float* const qkv = s_qkv.as<float>() + (size_t)s0 * QKV;
+    const size_t kv_seq = (size_t)d.n_kv * max_ctx * 128 * kv_elem();  // bytes per sequence and layer
+    DecodeAttnArgs da{};
+    da.qkv = qkv; da.pos = d_pos.as<int>() + s0; da.eps = d.rms_eps;
+    da.rope_cur = rope_cur.as<float>() + (size_t)s0 * 128;
+    da.pm = attn_pm.as<float>() + (size_t)s0 * d.n_q * attn_nsplit; da.pl = attn_pl.as<float>() + (size_t)s0 * d.n_q * attn_nsplit;
+    da.po = attn_po.as<float>() + (size_t)s0 * d.n_q * attn_nsplit * 128; da.nsplit = live_nsplit_;  // (buffers sized for attn_nsplit)
+    da.n_q = d.n_q; da.n_kv = d.n_kv; da.max_ctx = max_ctx; da.scale_div = sqrtf((float)d.head_dim);
+    da.q_norm = wf(l.q_norm); da.k_norm = wf(l.k_norm);
+    da.kcache = (uint8_t*)kc_layer(li) + (size_t)s0 * kv_seq; da.vcache = (uint8_t*)vc_layer(li) + (size_t)s0 * kv_seq;
+    if (gemv) {
+      auto run = [&](const Proj& p, const GemvArgs& a) { timed(p.kclass, p.bytes, [&] { KCHK(launch_gemv(a, S, ks)); }); };
+      GemvArgs g = gemv_args(pj.qkv);
+      g.x = x; g.rms_w = wf(l.in_ln); g.out = qkv;
+      run(pj.qkv, g);
+      timed(Q3A_KC_DECODE_ATTN, 0, [&] { KCHK(launch_decode_attn(da, S, kv_f32(), ks)); });
+      GemvArgs o = gemv_args(pj.o);
+      if (std::min(S, 4) * d.n_q * live_nsplit_ <= GEMV_ATTN_MAX_TABLE) {  // merge the key splits inside the o_proj GEMV
+        o.attn_pm = da.pm; o.attn_pl = da.pl; o.attn_po = da.po;
+        o.attn_nsplit = live_nsplit_; o.attn_heads = d.n_q; o.attn_fast_exp = fast_math();
+      } else {  // very long contexts: separate merge launch
+        timed(Q3A_KC_DECODE_ATTN, 0, [&] { KCHK(launch_attn_combine(da.pm, da.pl, da.po, live_nsplit_, S, d.n_q, s_ctx_g(grp), ks)); });
+        o.x = s_ctx_g(grp);
+      }
+      o.out = x; o.resid = x;
+      run(pj.o, o);
+      GemvArgs u = gemv_args(pj.gu);
+      u.x = x; u.rms_w = wf(l.post_ln); u.out = s_act_g(grp);
+      run(pj.gu, u);
+      GemvArgs dn = gemv_args(pj.down);
+      dn.x = s_act_g(grp); dn.out = x; dn.resid = x;
+      run(pj.down, dn);
+      return;
+    }
+    // skinny MFMA GEMMs: the norms are fused (no norm launches), and in the default mode the two K-heavy projections read
+    // bf16 activations written by their producers (attention, SwiGLU epilogue) in fragment order
+    const bool b16 = !precise(), pre = prenorm_path();
+    uint16_t* const s_ctx16 = b16 ? reinterpret_cast<uint16_t*>(s_ctx_g(grp)) : nullptr;
+    uint16_t* const s_act16 = b16 ? reinterpret_cast<uint16_t*>(s_act_g(grp)) : nullptr;
+    auto run = [&](const Proj& p, const SkinnyArgs& a) { timed(Q3A_KC_GEMM, p.bytes, [&] { KCHK(launch_skinny(a, precise(), ks)); }); };
+    // x of a projection that reads the residual stream: pre-normalised by its producer, or normalised in the GEMM by norm_w
+    auto from_residual = [&](SkinnyArgs& a, const float* norm_w) {
+      a.x = x;
+      if (pre) { a.xw16f = nn_x_g(grp); a.ss_parts = nn_ss_g(grp); a.ss_nparts = nn_parts(); }
+      else a.rms_w = norm_w;
+    };
+    // a projection that writes the residual stream: quarter workgroups where the shape allows, and the row pre-normalised by
+    // next_w for the GEMM that reads it next (null: nobody does)
+    auto to_residual = [&](SkinnyArgs& a, const float* next_w) {
+      a.out = x; a.resid = x;
+      a.qsplit = b16 && skinny_q();
+      if (pre && next_w) { a.next_w = next_w; a.next_xw16f = nn_x_g(grp); a.next_ss = nn_ss_g(grp); }
+    };
+    SkinnyArgs q = skinny_args(pj.qkv, S);
+    from_residual(q, wf(l.in_ln));
+    q.out = qkv;
+    run(pj.qkv, q);
+    if (S * d.n_kv >= k_dattn_batched_min_wgs) {
+      // the group alone fills the chip: one workgroup per (sequence, kv head) walks all keys and writes the context itself
+      if (b16) { da.out16 = s_ctx16; da.out_frag = 1; } else da.out = s_ctx_g(grp);
+      da.trim_prologue = min_P_ < 2 * 128;  // some sequence is shorter than the kernel's two prologue key tiles
+      timed(Q3A_KC_DECODE_ATTN, 0, [&] { KCHK(launch_decode_attn_batched(da, S, kv_f32(), ks)); });
+    } else {
+      timed(Q3A_KC_DECODE_ATTN, 0, [&] { KCHK(launch_decode_attn(da, S, kv_f32(), ks)); });
+      timed(Q3A_KC_DECODE_ATTN, 0, [&] { KCHK(launch_attn_combine(da.pm, da.pl, da.po, live_nsplit_, S, d.n_q, s_ctx_g(grp), ks, s_ctx16, b16)); });
+    }
+    SkinnyArgs o = skinny_args(pj.o, S);
+    o.x = s_ctx_g(grp); o.x16 = s_ctx16; o.x16_frag = b16;
+    to_residual(o, wf(l.post_ln));
+    run(pj.o, o);
+    SkinnyArgs u = skinny_args(pj.gu, S);
+    from_residual(u, wf(l.post_ln));
+    u.out = s_act_g(grp); u.out16 = s_act16; u.out16_frag = b16;
+    u.n_cu = n_cu;
+    u.glu_hp3 = k_skinny_glu_hp3;
+    run(pj.gu, u);
+    SkinnyArgs dn = skinny_args(pj.down, S);
+    dn.x = s_act_g(grp); dn.x16 = s_act16; dn.x16_frag = b16;
+    // (the last layer feeds the final norm + lm_head, which read x_dec)
+    to_residual(dn, li + 1 < d.dec_layers ? wf(L.dec[li + 1].in_ln) : nullptr);
+    run(pj.down, dn);
+  }
+
+  // one greedy-loop iteration for all sequences (inference.rs:160-200).  Batched path: the groups of `gsize` sequences are
+  // independent chains of latency-bound kernels (5 per layer), so every group runs on its own stream -- forked from and
+  // joined back into the engine's stream with events, which a hipGraph capture records as parallel branches: one group's
+  // KV-streaming attention overlaps another group's weight-streaming GEMMs.  (Profiling runs keep everything on one stream.)
+  bool forks() const { return n_groups(B) > 1 && !prof && k_parallel_groups != 0; }  // (the owner makes the group streams first)
+  void enqueue_decode_step() {
+    const int ng = n_groups(B);
+    const bool chains = forks();
+    if (chains) HIPCHK(hipEventRecord(fork_ev, stream));
+    for (int g = 0; g < ng; ++g) {
+      const int s0 = ng == 1 ? 0 : g * gsize;
+      const int S = ng == 1 ? B : std::min(gsize, B - s0);
+      hipStream_t ks = (chains && g > 0) ? chain_streams[g - 1] : stream;
+      if (chains && g > 0) HIPCHK(hipStreamWaitEvent(ks, fork_ev, 0));
+      for (int li = 0; li < d.dec_layers; ++li) decode_layer(li, g, s0, S, ks);
+      if (chains && g > 0) {
+        HIPCHK(hipEventRecord(join_ev[g - 1], ks));
+        HIPCHK(hipStreamWaitEvent(stream, join_ev[g - 1], 0));
+      }
+    }
+    run_head(1);
+  }
+
+  // does any group of the batch run the key-split attention (GEMV path, or a group too small for the batched kernel)?
+  bool uses_key_splits() const {
+    if (B <= kGemvMaxSeq) return true;
+    const int ng = n_groups(B);
+    const int smallest = ng == 1 ? B : std::min(gsize, B - (ng - 1) * gsize);
+    return smallest * d.n_kv < k_dattn_batched_min_wgs;
+  }
+
+  void enqueue_step() {
+    enqueue_decode_step();
+    if (beam_w_ > 0) enqueue_beam_round();
+  }
+  void enqueue_beam_round() {
+    const int W = beam_w_, S = B, U = B / W;
+    BeamTopkArgs t{};
+    t.logits = logits.as<float>(); t.S = S; t.V = d.vocab; t.W = W;
+    t.cand_val = beam_cand_val.as<float>(); t.cand_idx = beam_cand_idx.as<int>();
+    t.part_max = beam_part_max.as<float>(); t.part_sum = beam_part_sum.as<float>();
+    t.out_ids = beam_topk_ids.as<int>(); t.out_lp = beam_topk_lp.as<float>();
+    timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_beam_topk(t, stream)); });
+    BeamAdvanceArgs a{};
+    a.U = U; a.W = W; a.topk_ids = t.out_ids; a.topk_lp = t.out_lp;
+    a.score = beam_score.as<float>(); a.finished = beam_finished.as<uint8_t>();
+    a.parent = beam_parent.as<int>(); a.token = beam_token.as<int>(); a.feed = beam_feed.as<int>();
+    a.hist_parent = beam_hist_parent.as<int>(); a.hist_token = beam_hist_token.as<int>(); a.hist_lp = beam_hist_lp.as<float>();
+    a.hist_cap = max_new; a.state = beam_state.as<int>();
+    // rows a copy moves: the generated suffix, first row = the prompt length, last = the row the step just appended (pos was advanced)
+    a.pos = d_pos.as<int>(); a.lo = beam_lo.as<int>(); a.hi_bias = -1;
+    a.host_progress = host_prog_dev + 2; a.eos0 = kEos0; a.eos1 = kEos1;
+    timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_beam_advance(a, stream)); });
+    KvReorderArgs r{};
+    r.kcache = kcache.p; r.vcache = vcache.p; r.elem_bytes = (int)kv_elem(); r.layers = d.dec_layers; r.S = S; r.n_kv = d.n_kv; r.max_ctx = max_ctx;
+    r.parent = a.parent; r.lo = a.lo; r.hi = a.pos; r.hi_bias = -1; r.all_done = a.state + BEAM_ST_ALL_DONE;
+    timed(Q3A_KC_OTHER, 0, [&] { KCHK(launch_kv_reorder(r, stream)); });
+    timed(Q3A_KC_OTHER, 0, [&] {
+      KCHK(launch_set_tokens(a.feed, S, wh(L.embed), d.hidden, x_dec.as<float>(), next_tok.as<int>(), stream, first_layer_norm_out()));
+    });
+  }
+};
+
+}  // namespace
+
 struct q3a_engine {
   Dims d;
   ArenaLayout L;
@@ -165,7 +497,7 @@ struct q3a_engine {
   std::string err;
 
   // constant tables
-  DevBuf dft, filt_t, pos_emb, rope_cos, rope_sin;
+  DevBuf dft, filt_t, pos_emb;  // (the RoPE tables are the step's: step.rope_cos / rope_sin)
   int rope_positions = 0;
 
   // ---- batch description (host) ----
@@ -184,20 +516,13 @@ struct q3a_engine {
   DevBuf conv1, conv2, conv3, conv3_rowmap, convout_rowmap;
   DevBuf enc_x, enc_ln, enc_qkv, enc_ctx, enc_ffn, enc_segs, audio_embeds;
   DevBuf ids, audio_rowmap, row_seq, row_pos, dec_segs, last_rows;
-  DevBuf dec_x, dec_ln, dec_qkv, dec_ctx, dec_act, kcache, vcache;
-  DevBuf x_dec, d_pos, next_tok, out_ids, step_count, done, s_ln, s_qkv, s_ctx, s_act, logits, forced_tok, part_val, part_idx;
-  DevBuf blk_lo, blk_hi;  // pruned lm_head argmax: per 16-row block bounds (pass 1 -> pass 2)
-  DevBuf part_sum, out_lp;  // opts.token_logprobs: log-sum channel of the argmax partials, [B][max_new] log-probabilities next to out_ids
-  DevBuf lm_q, lm_qs;     // int8 lm_head copy + per-row scale and norms (init_lm_head_q)
+  DevBuf dec_x, dec_ln, dec_qkv, dec_ctx, dec_act;
+  DevBuf lm_q_buf, lm_qs_buf;  // int8 lm_head copy + per-row scale and norms (init_lm_head_q), never reallocated: the step gets ...
+  const int8_t* lm_q = nullptr; const float* lm_qs = nullptr;  // ... these plain pointers
   int lm_q_cols = 0;      // 0: no copy
-  DevBuf prune_stats;     // [2] candidate blocks rescored, pass-2 launches (q3a_debug_read "lm_head_prune_stats"; never read by the step)
-  DevBuf attn_pm, attn_pl, attn_po;
-  DevBuf nn_x, nn_ss;  // pre-normalised residual row for the next skinny GEMM: [32 * hidden] bf16 fragment order, [hidden/16][32] f32
-  DevBuf rope_cur;  // [B][128] cos|sin row of each sequence's current position (kept by argmax_finalize for decode attention)
   DevBuf enc_ctx16, dec_ctx16;  // opts.valu_attention in the default mode: bf16 copy of the fp32 attention context
   DevBuf dec_q16;
   int n_cu = 256;
-  DevBuf n_done;    // device counter of sequences that have produced their EOS (argmax_finalize)
   int* host_prog = nullptr;      // pinned host words written by argmax_finalize (FinalizeArgs::host_progress), polled without a sync
   int* host_prog_dev = nullptr;  // the same words as the device sees them
   DevBuf zero_page;  // 256 B of zeros: padded filter taps of the bf16 implicit-GEMM convolutions read it
@@ -241,40 +566,36 @@ struct q3a_engine {
   q3a_timings timings{};
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   std::vector<ProfEvent>* prof = nullptr;
-  std::map<std::string, DevBuf> taps;
-  std::map<std::string, size_t> tap_bytes;
+  Taps taps;
 
-  bool precise() const { return opts.precise != 0; }
-  bool token_lp() const { return opts.token_logprobs != 0; }
-  bool kv_f32() const { return opts.precise != 0; }
-  size_t kv_elem() const { return kv_f32() ? 4 : 2; }
+  bool fixed_mode_ = false;
+  bool head_logits_ = true;  // store the logits of a batched decode step (step API, debug taps); off inside run_resident
+  int beam_w_ = 0;           // > 0: beam mode, slots per utterance (part of the graph signature)
+
+  // ---- the captured decode step: its buffers and launches, and all it sees of the members above ----
+  DecodeStep step{StepView{d, L, opts, arena, arena_flags, stream, chain_streams, join_ev, fork_ev, n_cu, host_prog_dev, prof, taps, lm_q, lm_qs, lm_q_cols,
+                           B, max_ctx, max_new, gsize, live_nsplit_, attn_nsplit, min_P_, part_stride, beam_w_, kv_layer_elems, head_logits_,
+                           k_parallel_groups, k_skinny_q, k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune}};
+
+  // (the mode rules are stated once, in StepView)
+  bool precise() const { return step.precise(); }
+  bool token_lp() const { return step.token_lp(); }
+  bool kv_f32() const { return step.kv_f32(); }
+  size_t kv_elem() const { return step.kv_elem(); }
   // GEMM-input activations (conv maps, norm outputs, attention context, FFN hidden) are stored as bf16 in the default
   // mode -- exactly the values the MFMA consumes -- and as fp32 in the precise mode (hi+lo split inside the GEMM)
   size_t act_elem() const { return precise() ? 4 : 2; }
-  int fast_math() const { return precise() ? 0 : 1; }  // GemvArgs / SkinnyArgs::fast_math, the merge's fast exp
   // the fp32 VALU attention (precise mode / opts.valu_attention) writes an fp32 context that is rounded afterwards
   bool valu_attn() const { return precise() || opts.valu_attention; }
-  template <typename T> const T* w(uint64_t off) const { return reinterpret_cast<const T*>(arena + off); }
-  const float* wf(uint64_t off) const { return w<float>(off); }
-  const uint16_t* wh(uint64_t off) const { return w<uint16_t>(off); }
+  const float* wf(uint64_t off) const { return step.wf(off); }
+  const uint16_t* wh(uint64_t off) const { return step.wh(off); }
 
-  // opts.debug_taps: 1 = every tap; 2 = only the small ones a soak run compares (last hidden rows, head input)
-  static bool light_tap(const char* name) { return strcmp(name, "dec_last_hidden") == 0 || strcmp(name, "head_in") == 0; }
-  void tap(const char* name, const void* ptr, size_t bytes) {
-    if (!opts.debug_taps || bytes == 0 || (opts.debug_taps == 2 && !light_tap(name))) return;
-    DevBuf& t = taps[name];
-    t.ensure(bytes);
-    tap_bytes[name] = bytes;
-    HIPCHK(hipMemcpyAsync(t.p, ptr, bytes, hipMemcpyDeviceToDevice, stream));
-  }
+  void tap(const char* name, const void* ptr, size_t bytes) { step.tap(name, ptr, bytes); }
   // tap of an activation buffer that is bf16 in the default mode and fp32 in the precise mode: always read back as fp32
   void tap_act(const char* name, const void* ptr, size_t elems) {
     if (!opts.debug_taps || elems == 0 || opts.debug_taps == 2) return;
     if (precise()) return tap(name, ptr, elems * 4);
-    DevBuf& t = taps[name];
-    t.ensure(elems * 4);
-    tap_bytes[name] = elems * 4;
-    KCHK(launch_from_bf16((const uint16_t*)ptr, t.as<float>(), elems, stream));
+    KCHK(launch_from_bf16((const uint16_t*)ptr, taps.reserve(name, elems * 4).as<float>(), elems, stream));
   }
 
   // GEMM over an activation buffer: LDS-DMA bf16 kernel (k_gemm16.hip) in the default mode, fp32 hi+lo split kernel
@@ -293,20 +614,6 @@ struct q3a_engine {
   }
   uint16_t* act16(const DevBuf& buf) const { return precise() ? nullptr : buf.as<uint16_t>(); }
 
-  // run fn() (which enqueues exactly one kernel class) optionally bracketed by events
-  template <class F> void timed(int kclass, double bytes, F&& fn) {
-    if (!prof) {
-      fn();
-      return;
-    }
-    ProfEvent pe{kclass, bytes, nullptr, nullptr};
-    HIPCHK(hipEventCreate(&pe.a));
-    HIPCHK(hipEventCreate(&pe.b));
-    HIPCHK(hipEventRecord(pe.a, stream));
-    fn();
-    HIPCHK(hipEventRecord(pe.b, stream));
-    prof->push_back(pe);
-  }
   // milliseconds between two of the stage events: ev[0] mel, ev[1] encoder, ev[2] prefill, ev[3] decode / head, ev[4] end
   float stage_ms(int i, int j) { float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, ev[i], ev[j])); return ms; }
 
@@ -331,9 +638,9 @@ struct q3a_engine {
     HIPCHK(hipHostMalloc((void**)&host_prog, 64, hipHostMallocMapped));
     memset(host_prog, 0, 64);
     HIPCHK(hipHostGetDevicePointer((void**)&host_prog_dev, host_prog, 0));
-    n_done.ensure(64);
-    prune_stats.ensure(8);
-    HIPCHK(hipMemsetAsync(prune_stats.p, 0, 8, stream));
+    step.n_done.ensure(64);
+    step.prune_stats.ensure(8);
+    HIPCHK(hipMemsetAsync(step.prune_stats.p, 0, 8, stream));
   }
 
   void init_tables() {
@@ -355,8 +662,8 @@ struct q3a_engine {
     std::vector<float> c, s;
     make_rope_tables(n, d.head_dim, d.rope_theta, c, s);
     HIPCHK(hipStreamSynchronize(stream));
-    upload(rope_cos, c, stream);
-    upload(rope_sin, s, stream);
+    upload(step.rope_cos, c, stream);
+    upload(step.rope_sin, s, stream);
     HIPCHK(hipStreamSynchronize(stream));
     rope_positions = n;
   }
@@ -366,11 +673,11 @@ struct q3a_engine {
   void init_lm_head_q() {
     const int cols = lm_head_q_cols(d.hidden);
     if (precise() || d.aligner() || cols == 0 || d.hidden % 8 != 0) return;  // (an aligner has no vocabulary lm_head)
-    lm_q.ensure((size_t)d.vocab * cols);
-    lm_qs.ensure((size_t)d.vocab * 16);
-    KCHK(launch_lm_head_quantize(wh(L.lm_head), d.vocab, d.hidden, lm_q.as<int8_t>(), lm_qs.as<float>(), stream));
+    lm_q_buf.ensure((size_t)d.vocab * cols);
+    lm_qs_buf.ensure((size_t)d.vocab * 16);
+    KCHK(launch_lm_head_quantize(wh(L.lm_head), d.vocab, d.hidden, lm_q_buf.as<int8_t>(), lm_qs_buf.as<float>(), stream));
     HIPCHK(hipStreamSynchronize(stream));
-    lm_q_cols = cols;
+    lm_q = lm_q_buf.as<int8_t>(); lm_qs = lm_qs_buf.as<float>(); lm_q_cols = cols;
   }
 
   void check_arena_header() {
@@ -744,16 +1051,16 @@ struct q3a_engine {
     upload(audio_rowmap, amap, stream);
     upload(last_rows, last, stream);
     upload(dec_segs, segs, stream);
-    upload(d_pos, P, stream);
+    upload(step.d_pos, P, stream);
     const size_t Pt = (size_t)total_P, H = d.hidden;
     dec_x.ensure(Pt * H * 4); dec_ln.ensure(Pt * H * act_elem()); dec_qkv.ensure(Pt * d.qkv_dim() * 4);
     dec_ctx.ensure(Pt * d.q_dim() * (valu_attn() ? 4 : act_elem())); dec_act.ensure(Pt * d.inter * act_elem());
     if (!valu_attn()) dec_q16.ensure(Pt * d.q_dim() * 2);  // q after QK-norm + RoPE as bf16 for the MFMA prefill attention
     if (valu_attn() && !precise()) dec_ctx16.ensure(Pt * d.q_dim() * 2);
     kv_layer_elems = (size_t)b * d.n_kv * max_ctx * 128;
-    kcache.ensure(kv_layer_elems * d.dec_layers * kv_elem());
-    vcache.ensure(kv_layer_elems * d.dec_layers * kv_elem());
-    rope_cur.ensure((size_t)b * 128 * 4);
+    step.kcache.ensure(kv_layer_elems * d.dec_layers * kv_elem());
+    step.vcache.ensure(kv_layer_elems * d.dec_layers * kv_elem());
+    step.rope_cur.ensure((size_t)b * 128 * 4);
     {
       Knobs& kn = knobs();
       const int gs = kn.decode_group_size.load();
@@ -763,36 +1070,36 @@ struct q3a_engine {
       k_skinny_glu_hp3 = kn.skinny_glu_hp3.load();
       k_lm_head_prune = kn.lm_head_prune.load();
     }
-    const size_t ng = (size_t)n_groups(b);  // groups of <= gsize sequences of the batched decode step
-    nn_x.ensure(ng * 32 * H * 2); nn_ss.ensure((size_t)ng * (H / 8) * 32 * 4);  // room for the finer (8-column) partial rows whichever shape the knob selects later
-    x_dec.ensure((size_t)b * H * 4); next_tok.ensure((size_t)b * 4); forced_tok.ensure((size_t)b * 4);
-    out_ids.ensure((size_t)b * max_new * 4); step_count.ensure((size_t)b * 4); done.ensure((size_t)b);
+    const size_t ng = (size_t)step.n_groups(b);  // groups of <= gsize sequences of the batched decode step
+    step.nn_x.ensure(ng * 32 * H * 2); step.nn_ss.ensure((size_t)ng * (H / 8) * 32 * 4);  // room for the finer (8-column) partial rows whichever shape the knob selects later
+    step.x_dec.ensure((size_t)b * H * 4); step.next_tok.ensure((size_t)b * 4); step.forced_tok.ensure((size_t)b * 4);
+    step.out_ids.ensure((size_t)b * max_new * 4); step.step_count.ensure((size_t)b * 4); step.done.ensure((size_t)b);
     // s_ctx / s_act also hold the bf16 fragment-order copies of the skinny GEMM path: always 32 sequences there
-    s_ln.ensure((size_t)b * H * 4); s_qkv.ensure((size_t)b * d.qkv_dim() * 4); s_ctx.ensure(ng * 32 * d.q_dim() * 4);
-    s_act.ensure(ng * 32 * d.inter * 4); logits.ensure((size_t)b * d.vocab * 4);
+    step.s_ln.ensure((size_t)b * H * 4); step.s_qkv.ensure((size_t)b * d.qkv_dim() * 4); step.s_ctx.ensure(ng * 32 * d.q_dim() * 4);
+    step.s_act.ensure(ng * 32 * d.inter * 4); step.logits.ensure((size_t)b * d.vocab * 4);
     part_stride = std::max(128, (d.vocab + 3) / 4);  // >= blocks of the lm_head GEMV at 1 row per wave
-    part_val.ensure((size_t)b * part_stride * 4); part_idx.ensure((size_t)b * part_stride * 4);
-    if (token_lp()) { part_sum.ensure((size_t)b * part_stride * 4); out_lp.ensure((size_t)b * max_new * 4); }
+    step.part_val.ensure((size_t)b * part_stride * 4); step.part_idx.ensure((size_t)b * part_stride * 4);
+    if (token_lp()) { step.part_sum.ensure((size_t)b * part_stride * 4); step.out_lp.ensure((size_t)b * max_new * 4); }
     {
       const size_t nblk4 = ((size_t)(d.vocab + 15) / 16 + 3) & ~size_t(3);  // lm_head_prune_blocks, rounded up for float4 reads
-      blk_lo.ensure(nblk4 * 4); blk_hi.ensure(nblk4 * 4);
+      step.blk_lo.ensure(nblk4 * 4); step.blk_hi.ensure(nblk4 * 4);
     }
     attn_nsplit = (max_ctx + dattn_keys_per_split(kv_f32()) - 1) / dattn_keys_per_split(kv_f32());
     {  // (+8 floats: the merge-first o_proj GEMV reads a head's statistics 16 bytes at a time, up to 7 entries past the last head's)
       const size_t n_stat = (size_t)b * d.n_q * attn_nsplit;
-      attn_pm.ensure((n_stat + 8) * 4); attn_pl.ensure((n_stat + 8) * 4);
-      attn_po.ensure(n_stat * 128 * 4);
+      step.attn_pm.ensure((n_stat + 8) * 4); step.attn_pl.ensure((n_stat + 8) * 4);
+      step.attn_po.ensure(n_stat * 128 * 4);
       if (knobs().poison_attn_partials.load() != 0) {  // (tests) NaN wherever no decode attention launch has written yet
-        HIPCHK(hipMemsetAsync(attn_pm.p, 0xFF, attn_pm.cap, stream));
-        HIPCHK(hipMemsetAsync(attn_pl.p, 0xFF, attn_pl.cap, stream));
-        HIPCHK(hipMemsetAsync(attn_po.p, 0xFF, attn_po.cap, stream));
+        HIPCHK(hipMemsetAsync(step.attn_pm.p, 0xFF, step.attn_pm.cap, stream));
+        HIPCHK(hipMemsetAsync(step.attn_pl.p, 0xFF, step.attn_pl.cap, stream));
+        HIPCHK(hipMemsetAsync(step.attn_po.p, 0xFF, step.attn_po.cap, stream));
       }
     }
-    HIPCHK(hipMemsetAsync(step_count.p, 0, (size_t)b * 4, stream));
-    HIPCHK(hipMemsetAsync(done.p, 0, (size_t)b, stream));
-    HIPCHK(hipMemsetAsync(n_done.p, 0, 64, stream));
-    HIPCHK(hipMemsetAsync(out_ids.p, 0, (size_t)b * max_new * 4, stream));
-    if (token_lp()) HIPCHK(hipMemsetAsync(out_lp.p, 0, (size_t)b * max_new * 4, stream));
+    HIPCHK(hipMemsetAsync(step.step_count.p, 0, (size_t)b * 4, stream));
+    HIPCHK(hipMemsetAsync(step.done.p, 0, (size_t)b, stream));
+    HIPCHK(hipMemsetAsync(step.n_done.p, 0, 64, stream));
+    HIPCHK(hipMemsetAsync(step.out_ids.p, 0, (size_t)b * max_new * 4, stream));
+    if (token_lp()) HIPCHK(hipMemsetAsync(step.out_lp.p, 0, (size_t)b * max_new * 4, stream));
     // drain the stream -- and the group streams: a run that threw mid-loop may have left run-ahead steps enqueued whose
     // argmax_finalize would still write the progress words -- BEFORE the words are reset
     HIPCHK(hipStreamSynchronize(stream));
@@ -802,103 +1109,9 @@ struct q3a_engine {
     drain_retired_graphs();
     {  // a step-visible buffer was reallocated: cached graphs may replay launches that point at the freed allocation
       bool any = false;
-      for (auto* sb : step_bufs()) { any = any || sb->grew; sb->grew = false; }
+      DecodeStep::each_buf(step, [&](DevBuf& sb) { any = any || sb.grew; sb.grew = false; });
       if (any) drop_graphs();
     }
-  }
-
-  // Every DevBuf a launch of the captured decode step reads or writes (decode_layer, run_head, enqueue_decode_step and the
-  // accessors they call).  ONE list serves both guards against a stale graph: the reallocation sweep of setup_prompts and the
-  // address hash inside make_graph_sig.  tests/test_host.py::test_step_buffers_cover_the_captured_step scans those functions'
-  // source for DevBuf members and fails when one is missing here.
-  std::vector<DevBuf*> step_bufs() {
-    return {&kcache, &vcache, &x_dec, &d_pos, &next_tok, &out_ids, &step_count, &done, &s_ln, &s_qkv, &s_ctx, &s_act, &logits,
-            &part_val, &part_idx, &part_sum, &out_lp, &blk_lo, &blk_hi, &prune_stats, &attn_pm, &attn_pl, &attn_po, &nn_x, &nn_ss, &rope_cur, &rope_cos, &rope_sin, &n_done, &forced_tok,
-            &beam_cand_val, &beam_cand_idx, &beam_part_max, &beam_part_sum, &beam_topk_ids, &beam_topk_lp, &beam_score, &beam_finished, &beam_parent, &beam_token,
-            &beam_feed, &beam_hist_parent, &beam_hist_token, &beam_hist_lp, &beam_state, &beam_lo};
-  }
-  std::vector<const DevBuf*> step_bufs() const {
-    auto v = const_cast<q3a_engine*>(this)->step_bufs();
-    return std::vector<const DevBuf*>(v.begin(), v.end());
-  }
-
-  void* kc_layer(int l) { return (uint8_t*)kcache.p + (size_t)l * kv_layer_elems * kv_elem(); }
-  void* vc_layer(int l) { return (uint8_t*)vcache.p + (size_t)l * kv_layer_elems * kv_elem(); }
-
-  LmHeadPruneArgs prune_args(const GemvArgs& g) {
-    LmHeadPruneArgs pa{};
-    pa.g = g; pa.Wq = lm_q.as<int8_t>(); pa.qcols = lm_q_cols; pa.qs = lm_qs.as<float>();
-    pa.blk_lo = blk_lo.as<float>(); pa.blk_hi = blk_hi.as<float>(); pa.stats = prune_stats.as<int>();
-    return pa;
-  }
-
-  // final norm + lm_head on x_dec -> logits (+ block argmax partials), then argmax/finalize
-  void run_head(int advance) {
-    const int S = B, H = d.hidden, V = d.vocab;
-    tap("head_in", x_dec.p, (size_t)S * H * 4);  // (debug taps) last-layer residual rows the final norm + lm_head read
-    const double wbytes = 2.0 * V * H;
-    int n_part = 0;
-    // the argmax partials every producer below writes and argmax_finalize merges; with token log-probabilities also their log-sum
-    // channel (null: off, the kernels without it)
-    const ArgmaxPartials part{part_val.as<float>(), part_idx.as<int>(), token_lp() ? part_sum.as<float>() : nullptr, part_stride};
-    if (S <= kGemvMaxSeq) {
-      GemvArgs g{};
-      g.fast_math = fast_math();
-      g.x = x_dec.as<float>(); g.ldx = H; g.rms_w = wf(L.final_norm); g.eps = d.rms_eps;
-      g.W = wh(L.lm_head); g.N = V; g.K = H; g.mode = 3; g.out = logits.as<float>(); g.ldo = V;
-      g.part = part;
-      // (with the log-sum channel lm_head_prune_check refuses: the pruned argmax never computes most logits, the full GEMV runs)
-      LmHeadPruneArgs pa{};
-      const bool prunable = S == 1 && !precise() && lm_q_cols > 0 && (pa = prune_args(g), !lm_head_prune_check(pa));
-      if (prunable && opts.debug_taps == 1) {  // (debug taps) approximate logits and their bounds next to the stored logits
-        DevBuf& t = taps["lm_head_bound"];
-        t.ensure((size_t)V * 8);
-        tap_bytes["lm_head_bound"] = (size_t)V * 8;
-        LmHeadPruneArgs pd = pa;
-        pd.dbg = t.as<float>(); pd.stats = nullptr;
-        KCHK(launch_lm_head_approx(pd, stream));
-      }
-      if (prunable && k_lm_head_prune && !head_logits_) {
-        // nobody reads the logits: the exact argmax from the int8 pre-pass + a bf16 rescore of the candidate blocks
-        g.out = nullptr; pa.g.out = nullptr;
-        n_part = lm_head_rescore_groups(g, n_cu);
-        timed(Q3A_KC_GEMV_LM_HEAD, (double)V * lm_q_cols, [&] { KCHK(launch_lm_head_approx(pa, stream)); });
-        timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_lm_head_rescore(pa, n_part, stream)); });
-      } else {
-        n_part = gemv_blocks(g);
-        timed(Q3A_KC_GEMV_LM_HEAD, wbytes, [&] { KCHK(launch_gemv(g, S, stream)); });
-      }
-    } else if (!precise()) {
-      // default mode: bf16 normed rows, then the LDS-DMA GEMM at M = S (32-row tiles) -- the vocabulary matrix is
-      // streamed once through double-buffered LDS; the skinny kernel re-reads x per 16 vocabulary rows (3x slower here)
-      timed(Q3A_KC_NORM, 0, [&] { KCHK(launch_rmsnorm(x_dec.as<float>(), wf(L.final_norm), s_ln.as<float>(), S, H, d.rms_eps, stream, s_ln.as<uint16_t>())); });
-      GemmEpilogue ep; ep.out = logits.as<float>(); ep.ldo = V;
-      if (S <= 32 && V % 4 == 0 && H % 64 == 0 && part_stride >= (V + 63) / 64) {
-        // the argmax partials are the GEMM's epilogue (one per 64-column tile and row), and inside q3a_transcribe_batch /
-        // q3a_run_resident nobody reads the logits: they are not stored (19 MB per step at 32 sequences)
-        ep.part = part;
-        if (!head_logits_) ep.out = nullptr;
-        n_part = (V + 63) / 64;
-        timed(Q3A_KC_GEMM, wbytes, [&] { KCHK(launch_gemm16(s_ln.as<uint16_t>(), H, wh(L.lm_head), S, V, H, ep, false, stream)); });
-      } else {
-        timed(Q3A_KC_GEMM, wbytes, [&] { KCHK(launch_gemm16(s_ln.as<uint16_t>(), H, wh(L.lm_head), S, V, H, ep, false, stream)); });
-        n_part = 128;
-        timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_partials(logits.as<float>(), V, S, part, n_part, stream)); });
-      }
-    } else {
-      timed(Q3A_KC_NORM, 0, [&] { KCHK(launch_rmsnorm(x_dec.as<float>(), wf(L.final_norm), s_ln.as<float>(), S, H, d.rms_eps, stream)); });
-      timed(Q3A_KC_GEMM, wbytes, [&] { batched_proj(s_ln.as<float>(), H, wh(L.lm_head), V, H, nullptr, 0, logits.as<float>(), V, nullptr); });
-      n_part = 128;
-      timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_partials(logits.as<float>(), V, S, part, n_part, stream)); });
-    }
-    FinalizeArgs f{};
-    f.part = part; f.n_part = n_part; f.out_lp = part.sum ? out_lp.as<float>() : nullptr;
-    f.V = V; f.next_tok = next_tok.as<int>(); f.out_ids = out_ids.as<int>();
-    f.out_stride = max_new; f.step_count = step_count.as<int>(); f.pos = d_pos.as<int>(); f.advance = advance;
-    f.done = done.as<uint8_t>(); f.n_done = n_done.as<int>(); f.n_seq = S; f.host_progress = host_prog_dev; f.embed = wh(L.embed); f.H = H; f.x_next = x_dec.as<float>(); f.eos0 = kEos0; f.eos1 = kEos1;
-    f.cos_t = rope_cos.as<float>(); f.sin_t = rope_sin.as<float>(); f.rope_cur = rope_cur.as<float>();
-    f.nn = first_layer_norm_out();
-    timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_finalize(f, S, stream)); });
   }
 
   void run_prefill() {
@@ -906,10 +1119,10 @@ struct q3a_engine {
     const int H = d.hidden;
     // only the last row of every sequence feeds the lm_head (the reference computes all rows and keeps
     // the last, text_decoder.rs:111-112 + inference.rs:156)
-    KCHK(launch_gather_rows(dec_x.as<float>(), last_rows.as<int>(), B, H, x_dec.as<float>(), stream));
-    tap("dec_last_hidden", x_dec.p, (size_t)B * H * 4);
-    run_head(0);
-    tap("logits", logits.p, (size_t)B * d.vocab * 4);
+    KCHK(launch_gather_rows(dec_x.as<float>(), last_rows.as<int>(), B, H, step.x_dec.as<float>(), stream));
+    tap("dec_last_hidden", step.x_dec.p, (size_t)B * H * 4);
+    step.run_head(0);
+    tap("logits", step.logits.p, (size_t)B * d.vocab * 4);
     HIPCHK(hipGetLastError());
     have_prefill = true;
   }
@@ -920,7 +1133,7 @@ struct q3a_engine {
     const bool sp = precise();
     KCHK(launch_embed(ids.as<int>(), total_P, wh(L.embed), H, kAudioPad, dec_x.as<float>(), stream));
     // audio injection (inference.rs:114-124): one row scatter instead of T full-tensor slice_scatter copies
-    scatter_audio_rows();
+    KCHK(launch_scatter_rows(audio_embeds.as<float>(), audio_rowmap.as<int>(), total_T, d.hidden, dec_x.as<float>(), stream));  // dec_x[audio_rowmap[t]] = audio_embeds[t]
     tap("dec_embed", dec_x.p, (size_t)total_P * H * 4);
     AttnArgs at{};
     at.q = dec_qkv.as<float>(); at.q_rs = QKV; at.kv_hs = (int64_t)max_ctx * 128; at.kv_rs = 128;
@@ -948,8 +1161,8 @@ struct q3a_engine {
       RopeKvArgs rk{};
       rk.qkv = dec_qkv.as<float>(); rk.row_seq = row_seq.as<int>(); rk.row_pos = row_pos.as<int>();
       rk.q_norm = wf(l.q_norm); rk.k_norm = wf(l.k_norm); rk.eps = d.rms_eps;
-      rk.cos_t = rope_cos.as<float>(); rk.sin_t = rope_sin.as<float>();
-      rk.kcache = kc_layer(li); rk.vcache = vc_layer(li); rk.n_q = d.n_q; rk.n_kv = d.n_kv; rk.max_ctx = max_ctx;
+      rk.cos_t = step.rope_cos.as<float>(); rk.sin_t = step.rope_sin.as<float>();
+      rk.kcache = step.kc_layer(li); rk.vcache = step.vc_layer(li); rk.n_q = d.n_q; rk.n_kv = d.n_kv; rk.max_ctx = max_ctx;
       rk.q16 = valu_attn() ? nullptr : dec_q16.as<uint16_t>();
       if (fuse_rope) {
         // batch-sized prefill: QK-norm, RoPE and the cache append are the epilogue of the qkv GEMM (k_gemm256.hip)
@@ -959,13 +1172,13 @@ struct q3a_engine {
         act_gemm(dec_ln, H, wh(l.qkv_w), total_P, QKV, H, ep, false);
         KCHK(launch_qknorm_rope_kv(rk, total_P, kv_f32(), stream));
       }
-      at.k = kc_layer(li); at.v = vc_layer(li);
+      at.k = step.kc_layer(li); at.v = step.vc_layer(li);
       if (fuse_rope) {
         ltap("qkvs", dec_qkv.p, std::min((size_t)1024, (size_t)total_P) * QKV * 4);  // fp32 scratch of the trailing rows (small GEMM -> separate rope kernel)
       }
       if (!valu_attn()) ltap("q", dec_q16.p, (size_t)total_P * QD * 2);  // q after QK-norm + RoPE, bf16 [rows][QD]
-      ltap("k", kc_layer(li), (size_t)B * d.n_kv * max_ctx * 128 * kv_elem());
-      ltap("v", vc_layer(li), (size_t)B * d.n_kv * max_ctx * 128 * kv_elem());
+      ltap("k", step.kc_layer(li), (size_t)B * d.n_kv * max_ctx * 128 * kv_elem());
+      ltap("v", step.vc_layer(li), (size_t)B * d.n_kv * max_ctx * 128 * kv_elem());
       if (valu_attn()) {
         KCHK(launch_attn_prefill(at, d.n_q / d.n_kv, kv_f32(), stream));
         if (!sp) KCHK(launch_to_bf16(dec_ctx.as<float>(), dec_ctx16.as<uint16_t>(), (size_t)total_P * QD, stream));
@@ -1041,6 +1254,13 @@ struct q3a_engine {
   }
   // every whole-path call (transcription, alignment, scoring): mel and encoder times of the events upload_ptrs_and_mel / the caller
   // recorded, total = ev[0] through ev[4]; the caller adds what its own stages between ev[2] and ev[4] are
+  // a call that decodes (greedy, beam): prefill = ev[2] .. ev[3], decode = ev[3] .. ev[4] over `steps` steps
+  void decode_timings(int steps) {
+    front_and_total_timings();
+    timings.prefill_ms = stage_ms(2, 3);
+    timings.decode_ms = stage_ms(3, 4);
+    timings.decode_steps = steps; timings.batch = B; timings.total_audio_tokens = total_T; timings.total_prompt_tokens = total_P;
+  }
   void front_and_total_timings() {
     timings.mel_ms = stage_ms(0, 1);
     timings.encoder_ms = stage_ms(1, 2);
@@ -1146,195 +1366,10 @@ struct q3a_engine {
   DevBuf score_tgt, score_psum, score_out;
   float score_head_ms = 0.f;  // the head's launches of the last score call (q3a_debug_read "score_head_ms")
 
-  void scatter_audio_rows();
-
-  // Skinny decode path in the default mode: every kernel that writes a row of the residual stream (token embedding,
-  // o / down projection) also leaves it pre-normalised for the GEMM that reads it next -- bf16(x * w_norm) in MFMA
-  // fragment order in nn_x plus partial sums of x^2 in nn_ss (kernels.h NextNormOut / SkinnyArgs::xw16f).
-  bool prenorm_path() const { return B > kGemvMaxSeq && !precise(); }
-  // o / down projections of the batched decode step as 8-row x 16-sequence workgroups (k_skinny.hip QS; Q3A_SKINNY_Q=0: off)
-  bool skinny_q() const {
-    auto whole = [](int K) { const int st = K / 32, per = (st + 7) / 8, unr = per <= 2 ? 2 : per <= 4 ? 4 : per <= 8 ? 8 : 12; return K % 256 == 0 && per % unr == 0; };
-    return k_skinny_q != 0 && !precise() && d.hidden % 64 == 0 && whole(d.q_dim()) && whole(d.inter);
-  }
-  int nn_parts() const { return d.hidden / (skinny_q() ? 8 : 16); }  // one partial per 16- (8-) column block of a hidden-wide GEMM output
-  // Batched decode (more than kGemvMaxSeq sequences) runs in groups of <= 32 sequences: the skinny MFMA GEMM holds 32
-  // sequences per weight sweep, and the second group's sweep of a 4-13 MB matrix is served by the L2 / Infinity Cache.
-  int n_groups(int b) const { return b <= kGemvMaxSeq ? 1 : (b + gsize - 1) / gsize; }
-  size_t nn_x_stride() const { return (size_t)32 * d.hidden; }         // elements per group
-  size_t nn_ss_stride() const { return (size_t)nn_parts() * 32; }
-  uint16_t* nn_x_g(int g) const { return nn_x.as<uint16_t>() + (size_t)g * nn_x_stride(); }
-  float* nn_ss_g(int g) const { return nn_ss.as<float>() + (size_t)g * nn_ss_stride(); }
-  float* s_ctx_g(int g) const { return s_ctx.as<float>() + (size_t)g * 32 * d.q_dim(); }   // fp32 [S][QD] or bf16 fragment order
-  float* s_act_g(int g) const { return s_act.as<float>() + (size_t)g * 32 * d.inter; }
-  NextNormOut first_layer_norm_out() const {
-    NextNormOut nn{};
-    if (prenorm_path()) {
-      nn.next_w = wf(L.dec[0].in_ln); nn.next_xw16f = nn_x.as<uint16_t>(); nn.next_ss = nn_ss.as<float>(); nn.nparts = nn_parts();
-      nn.group_stride_x = (long)nn_x_stride(); nn.group_stride_ss = (long)nn_ss_stride(); nn.group_size = gsize;
-    }
-    return nn;
-  }
-
-  // decode-step projection for more than 4 sequences: skinny MFMA GEMM up to 32, generic tiles above
-  void batched_proj(const float* x, int ldx, const uint16_t* W, int N, int K, const float* bias, int mode, float* out,
-                    int ldo, const float* resid) {
-    const int S = B;  // (precise-mode lm_head only)
-    if (S <= 32) {
-      SkinnyArgs sk{};
-      sk.fast_math = fast_math();
-      sk.x = x; sk.ldx = ldx; sk.S = S; sk.W = W; sk.N = N; sk.K = K; sk.bias = bias; sk.mode = mode; sk.out = out; sk.ldo = ldo; sk.resid = resid;
-      KCHK(launch_skinny(sk, precise(), stream));
-    } else {
-      GemmEpilogue ep; ep.out = out; ep.ldo = ldo; ep.bias = bias; ep.resid = (mode == 1) ? resid : nullptr;
-      KCHK(launch_gemm(x, ldx, W, S, N, K, ep, mode == 2, precise(), stream));
-    }
-  }
-
-  // The four projections of a decoder layer, stated ONCE for every path that launches them (decode_layer's GEMV and skinny forms,
-  // q3a_profile_weight_stream).  A caller starts its kernel arguments from one with gemv_args / skinny_args and sets only what its
-  // path adds: x and out pointers, the norm source, fragment flags, next-norm outputs.
-  struct Proj {
-    const uint16_t* W;  // [N][K] bf16
-    int N, K;
-    const float* bias;  // null: the checkpoint has none (arena flags)
-    int mode;           // GemvArgs / SkinnyArgs::mode: 0 plain, 1 + residual, 2 SiLU(gate) * up of interleaved rows -> N / 2 columns
-    int kclass;         // profile class of its GEMV (the skinny path books every projection as Q3A_KC_GEMM)
-    double bytes;       // weight bytes one launch streams
-  };
-  struct LayerProjs { Proj qkv, o, gu, down; };
-  LayerProjs layer_projs(int li) const {
-    const DecLayerOff& l = L.dec[li];
-    const int H = d.hidden, I = d.inter, QD = d.q_dim(), QKV = d.qkv_dim();
-    auto proj = [&](uint64_t w_off, int N, int K, uint32_t bias_flag, uint64_t b_off, int mode, int kclass) {
-      return Proj{wh(w_off), N, K, (arena_flags & bias_flag) ? wf(b_off) : nullptr, mode, kclass, 2.0 * N * K};
-    };
-    return {proj(l.qkv_w, QKV, H, kFlagDecQkvBias, l.qkv_b, 0, Q3A_KC_GEMV), proj(l.o_w, H, QD, kFlagDecOBias, l.o_b, 1, Q3A_KC_GEMV_O),
-            proj(l.gu_w, 2 * I, H, kFlagDecMlpBias, l.gu_b, 2, Q3A_KC_GEMV), proj(l.down_w, H, I, kFlagDecMlpBias, l.down_b, 1, Q3A_KC_GEMV_DOWN)};
-  }
-  template <class Args> Args proj_args(const Proj& p) const {  // the fields GemvArgs and SkinnyArgs share
-    Args a{};
-    a.fast_math = fast_math(); a.eps = d.rms_eps;  // (eps: read only where a norm source is set)
-    a.W = p.W; a.N = p.N; a.K = p.K; a.ldx = p.K; a.bias = p.bias; a.mode = p.mode; a.ldo = p.mode == 2 ? p.N / 2 : p.N;
-    return a;
-  }
-  GemvArgs gemv_args(const Proj& p) const { return proj_args<GemvArgs>(p); }
-  SkinnyArgs skinny_args(const Proj& p, int S) const { SkinnyArgs k = proj_args<SkinnyArgs>(p); k.S = S; return k; }
-
-  // one decoder layer of the greedy-loop iteration (inference.rs:172-197) for sequences [s0, s0 + S) -- the whole batch on
-  // the GEMV path, one group of <= 32 on the skinny MFMA path
-  void decode_layer(int li, int grp, int s0, int S, hipStream_t ks) {
-    const int H = d.hidden, QKV = d.qkv_dim();
-    const bool gemv = B <= kGemvMaxSeq;
-    const DecLayerOff& l = L.dec[li];
-    const LayerProjs pj = layer_projs(li);
-    float* const x = x_dec.as<float>() + (size_t)s0 * H;
-    float* const qkv = s_qkv.as<float>() + (size_t)s0 * QKV;
-    const size_t kv_seq = (size_t)d.n_kv * max_ctx * 128 * kv_elem();  // bytes per sequence and layer
-    DecodeAttnArgs da{};
-    da.qkv = qkv; da.pos = d_pos.as<int>() + s0; da.eps = d.rms_eps;
-    da.rope_cur = rope_cur.as<float>() + (size_t)s0 * 128;
-    da.pm = attn_pm.as<float>() + (size_t)s0 * d.n_q * attn_nsplit; da.pl = attn_pl.as<float>() + (size_t)s0 * d.n_q * attn_nsplit;
-    da.po = attn_po.as<float>() + (size_t)s0 * d.n_q * attn_nsplit * 128; da.nsplit = live_nsplit_;  // (buffers sized for attn_nsplit)
-    da.n_q = d.n_q; da.n_kv = d.n_kv; da.max_ctx = max_ctx; da.scale_div = sqrtf((float)d.head_dim);
-    da.q_norm = wf(l.q_norm); da.k_norm = wf(l.k_norm);
-    da.kcache = (uint8_t*)kc_layer(li) + (size_t)s0 * kv_seq; da.vcache = (uint8_t*)vc_layer(li) + (size_t)s0 * kv_seq;
-    if (gemv) {
-      auto run = [&](const Proj& p, const GemvArgs& a) { timed(p.kclass, p.bytes, [&] { KCHK(launch_gemv(a, S, ks)); }); };
-      GemvArgs g = gemv_args(pj.qkv);
-      g.x = x; g.rms_w = wf(l.in_ln); g.out = qkv;
-      run(pj.qkv, g);
-      timed(Q3A_KC_DECODE_ATTN, 0, [&] { KCHK(launch_decode_attn(da, S, kv_f32(), ks)); });
-      GemvArgs o = gemv_args(pj.o);
-      if (std::min(S, 4) * d.n_q * live_nsplit_ <= GEMV_ATTN_MAX_TABLE) {  // merge the key splits inside the o_proj GEMV
-        o.attn_pm = da.pm; o.attn_pl = da.pl; o.attn_po = da.po;
-        o.attn_nsplit = live_nsplit_; o.attn_heads = d.n_q; o.attn_fast_exp = fast_math();
-      } else {  // very long contexts: separate merge launch
-        timed(Q3A_KC_DECODE_ATTN, 0, [&] { KCHK(launch_attn_combine(da.pm, da.pl, da.po, live_nsplit_, S, d.n_q, s_ctx_g(grp), ks)); });
-        o.x = s_ctx_g(grp);
-      }
-      o.out = x; o.resid = x;
-      run(pj.o, o);
-      GemvArgs u = gemv_args(pj.gu);
-      u.x = x; u.rms_w = wf(l.post_ln); u.out = s_act_g(grp);
-      run(pj.gu, u);
-      GemvArgs dn = gemv_args(pj.down);
-      dn.x = s_act_g(grp); dn.out = x; dn.resid = x;
-      run(pj.down, dn);
-      return;
-    }
-    // skinny MFMA GEMMs: the norms are fused (no norm launches), and in the default mode the two K-heavy projections read
-    // bf16 activations written by their producers (attention, SwiGLU epilogue) in fragment order
-    const bool b16 = !precise(), pre = prenorm_path();
-    uint16_t* const s_ctx16 = b16 ? reinterpret_cast<uint16_t*>(s_ctx_g(grp)) : nullptr;
-    uint16_t* const s_act16 = b16 ? reinterpret_cast<uint16_t*>(s_act_g(grp)) : nullptr;
-    auto run = [&](const Proj& p, const SkinnyArgs& a) { timed(Q3A_KC_GEMM, p.bytes, [&] { KCHK(launch_skinny(a, precise(), ks)); }); };
-    // x of a projection that reads the residual stream: pre-normalised by its producer, or normalised in the GEMM by norm_w
-    auto from_residual = [&](SkinnyArgs& a, const float* norm_w) {
-      a.x = x;
-      if (pre) { a.xw16f = nn_x_g(grp); a.ss_parts = nn_ss_g(grp); a.ss_nparts = nn_parts(); }
-      else a.rms_w = norm_w;
-    };
-    // a projection that writes the residual stream: quarter workgroups where the shape allows, and the row pre-normalised by
-    // next_w for the GEMM that reads it next (null: nobody does)
-    auto to_residual = [&](SkinnyArgs& a, const float* next_w) {
-      a.out = x; a.resid = x;
-      a.qsplit = b16 && skinny_q();
-      if (pre && next_w) { a.next_w = next_w; a.next_xw16f = nn_x_g(grp); a.next_ss = nn_ss_g(grp); }
-    };
-    SkinnyArgs q = skinny_args(pj.qkv, S);
-    from_residual(q, wf(l.in_ln));
-    q.out = qkv;
-    run(pj.qkv, q);
-    if (S * d.n_kv >= k_dattn_batched_min_wgs) {
-      // the group alone fills the chip: one workgroup per (sequence, kv head) walks all keys and writes the context itself
-      if (b16) { da.out16 = s_ctx16; da.out_frag = 1; } else da.out = s_ctx_g(grp);
-      da.trim_prologue = min_P_ < 2 * 128;  // some sequence is shorter than the kernel's two prologue key tiles
-      timed(Q3A_KC_DECODE_ATTN, 0, [&] { KCHK(launch_decode_attn_batched(da, S, kv_f32(), ks)); });
-    } else {
-      timed(Q3A_KC_DECODE_ATTN, 0, [&] { KCHK(launch_decode_attn(da, S, kv_f32(), ks)); });
-      timed(Q3A_KC_DECODE_ATTN, 0, [&] { KCHK(launch_attn_combine(da.pm, da.pl, da.po, live_nsplit_, S, d.n_q, s_ctx_g(grp), ks, s_ctx16, b16)); });
-    }
-    SkinnyArgs o = skinny_args(pj.o, S);
-    o.x = s_ctx_g(grp); o.x16 = s_ctx16; o.x16_frag = b16;
-    to_residual(o, wf(l.post_ln));
-    run(pj.o, o);
-    SkinnyArgs u = skinny_args(pj.gu, S);
-    from_residual(u, wf(l.post_ln));
-    u.out = s_act_g(grp); u.out16 = s_act16; u.out16_frag = b16;
-    u.n_cu = n_cu;
-    u.glu_hp3 = k_skinny_glu_hp3;
-    run(pj.gu, u);
-    SkinnyArgs dn = skinny_args(pj.down, S);
-    dn.x = s_act_g(grp); dn.x16 = s_act16; dn.x16_frag = b16;
-    // (the last layer feeds the final norm + lm_head, which read x_dec)
-    to_residual(dn, li + 1 < d.dec_layers ? wf(L.dec[li + 1].in_ln) : nullptr);
-    run(pj.down, dn);
-  }
-
-  // one greedy-loop iteration for all sequences (inference.rs:160-200).  Batched path: the groups of `gsize` sequences are
-  // independent chains of latency-bound kernels (5 per layer), so every group runs on its own stream -- forked from and
-  // joined back into the engine's stream with events, which a hipGraph capture records as parallel branches: one group's
-  // KV-streaming attention overlaps another group's weight-streaming GEMMs.  (Profiling runs keep everything on one stream.)
-  void enqueue_decode_step() {
-    const int ng = n_groups(B);
-    const bool chains = ng > 1 && !prof && k_parallel_groups != 0;
-    if (chains) {
-      ensure_chain_streams(ng - 1);
-      HIPCHK(hipEventRecord(fork_ev, stream));
-    }
-    for (int g = 0; g < ng; ++g) {
-      const int s0 = ng == 1 ? 0 : g * gsize;
-      const int S = ng == 1 ? B : std::min(gsize, B - s0);
-      hipStream_t ks = (chains && g > 0) ? chain_streams[g - 1] : stream;
-      if (chains && g > 0) HIPCHK(hipStreamWaitEvent(ks, fork_ev, 0));
-      for (int li = 0; li < d.dec_layers; ++li) decode_layer(li, g, s0, S, ks);
-      if (chains && g > 0) {
-        HIPCHK(hipEventRecord(join_ev[g - 1], ks));
-        HIPCHK(hipStreamWaitEvent(stream, join_ev[g - 1], 0));
-      }
-    }
-    run_head(1);
+  // the captured step, through the unit (which cannot create the streams its groups fork onto)
+  void enqueue_step() {
+    if (step.forks()) ensure_chain_streams(step.n_groups(B) - 1);
+    step.enqueue_step();
   }
   void ensure_chain_streams(int n) {
     while ((int)chain_streams.size() < n) {
@@ -1350,12 +1385,12 @@ struct q3a_engine {
 
   std::string make_graph_sig() const {
     // everything the captured step's launches depend on: geometry, latched knobs and the address of EVERY step-visible buffer
-    // (FNV-1a over step_bufs(): the same list the reallocation sweep of setup_prompts walks)
+    // (FNV-1a over DecodeStep::each_buf: the same walk as the reallocation sweep of setup_prompts)
     uint64_t h = 1469598103934665603ull;
-    for (const DevBuf* sb : step_bufs()) {
-      uint64_t v = (uint64_t)(uintptr_t)sb->p;
+    DecodeStep::each_buf(step, [&](const DevBuf& sb) {
+      uint64_t v = (uint64_t)(uintptr_t)sb.p;
       for (int i = 0; i < 8; ++i) { h ^= (v >> (8 * i)) & 0xff; h *= 1099511628211ull; }
-    }
+    });
     char buf[256];
     // (one field per latched knob, as latched: packing several into one integer let distinct settings collide -- ADVICE r5)
     snprintf(buf, sizeof(buf), "%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.b%d/%d/%d/%d/%p/%016llx", B, gsize, k_parallel_groups, k_skinny_q,
@@ -1364,13 +1399,6 @@ struct q3a_engine {
     return buf;
   }
 
-  // does any group of the batch run the key-split attention (GEMV path, or a group too small for the batched kernel)?
-  bool uses_key_splits() const {
-    if (B <= kGemvMaxSeq) return true;
-    const int ng = n_groups(B);
-    const int smallest = ng == 1 ? B : std::min(gsize, B - (ng - 1) * gsize);
-    return smallest * d.n_kv < k_dattn_batched_min_wgs;
-  }
   // what fn() enqueues on `stream`, captured and instantiated; a throw inside fn ends the capture and drops the partial graph
   template <class F> hipGraphExec_t capture_graph(F&& fn) {
     hipGraph_t g = nullptr;
@@ -1432,7 +1460,7 @@ struct q3a_engine {
     // 03b3a8b, profiles/r6_ab_decode_steps_per_graph.txt.)
     for (int i = 0; i < n; ++i) {
       // this step feeds the token at position <= pos_hi_ and attends keys 0 .. pos_hi_
-      live_nsplit_ = uses_key_splits() ? std::min(attn_nsplit, pos_hi_ / kps + 1) : attn_nsplit;
+      live_nsplit_ = step.uses_key_splits() ? std::min(attn_nsplit, pos_hi_ / kps + 1) : attn_nsplit;
       if (eager) enqueue_step();
       else HIPCHK(hipGraphLaunch(graph_for_step(), stream));
       ++pos_hi_;
@@ -1440,16 +1468,8 @@ struct q3a_engine {
     if (eager) HIPCHK(hipGetLastError());
   }
 
-  // steps 2-8 on the resident batch
-  // prompts of the resident batch (inference.rs:104-137, 215-257) and every table / buffer of the prefill + decode: host integers
-  // only (T[] of set_batch), so this runs before the batch's first kernel is enqueued
-  void prepare_prompts(const int32_t* lang_ids, int n_prefix, int max_new_req, int fixed_new) {
-    if (B <= 0) fail("q3a_run_resident: no batch uploaded");
-    if (fixed_new > 0) max_new_req = fixed_new;
-    if (max_new_req <= 0) max_new_req = opts.max_new_tokens;
-    const auto pr = asr_prompts(lang_ids, n_prefix);
-    setup_prompts(pr.first.data(), pr.second.data(), B, max_new_req, true);
-  }
+  // what a transcription asks setup_prompts for: the fixed length, else the caller's limit, else the engine's
+  int max_new_request(int max_new_req, int fixed_new) const { return fixed_new > 0 ? fixed_new : max_new_req > 0 ? max_new_req : opts.max_new_tokens; }
   // the transcription prompt of every utterance of the batch (q3a_build_prompt over T[] of set_batch)
   std::pair<std::vector<int32_t>, std::vector<int32_t>> asr_prompts(const int32_t* lang_ids, int n_prefix) const {
     return concat_prompts(B, [&](int s, int32_t* dst) {
@@ -1459,16 +1479,37 @@ struct q3a_engine {
     });
   }
 
-  // mel_enqueued: upload_ptrs_and_mel() has put the (upload-overlapped) log-mel on the stream and recorded ev[0] / ev[1].
-  // The caller has run prepare_prompts() for this batch.
-  void run_resident(int fixed_new, bool mel_enqueued = false) {
+  // The front of every whole-path entry point (`what`: its name in error texts), stated once because its ORDER matters: checks,
+  // geometry, then the prompts -- prompts() returns (ids, lens) built from T[] alone -- and with them every table and buffer of the
+  // prefill and the decode, so that the drain inside setup_prompts meets an idle stream; only then the batch's first launches
+  // (upload + log-mel, encoder).  width > 1 (beam search): a clip is uploaded once per slot, `width` sequences of the batch.
+  template <class Prompts>
+  void whole_path_front(const char* what, const float* const* pcm16k, const int64_t* ns_in, int n, int width, int max_new_req, Prompts&& prompts) {
+    if (!pcm16k || !ns_in || n < 1) fail(std::string(what) + ": bad argument");
+    require_utterance_ptrs(what, pcm16k, n);
+    HIPCHK(hipSetDevice(device));
+    const int b = n * width;
+    std::vector<const float*> ptrs((size_t)b);
+    std::vector<int64_t> ns((size_t)b);
+    for (int s = 0; s < b; ++s) { ptrs[s] = pcm16k[s / width]; ns[s] = ns_in[s / width]; }
+    have_prefill = false;
+    set_batch(ns.data(), b);
+    auto&& [ids_v, lens_v] = prompts();
+    setup_prompts(ids_v.data(), lens_v.data(), b, max_new_req, true);
+    timings = q3a_timings{};
+    upload_ptrs_and_mel(ptrs.data(), ns.data(), b);
+    run_encoder();
+  }
+
+  // front_done: whole_path_front() has enqueued the log-mel and the encoder (ev[0] / ev[1] recorded); else the prompts are set up
+  void run_resident(int fixed_new, bool front_done = false) {
     if (B <= 0) fail("q3a_run_resident: no batch uploaded");
-    if (!mel_enqueued) {
+    if (!front_done) {
       HIPCHK(hipEventRecord(ev[0], stream));
       run_mel();
       HIPCHK(hipEventRecord(ev[1], stream));
+      run_encoder();
     }
-    run_encoder();
     HIPCHK(hipEventRecord(ev[2], stream));
     run_prefill();
     HIPCHK(hipEventRecord(ev[3], stream));
@@ -1488,40 +1529,18 @@ struct q3a_engine {
       // D2H copy inside the loop, so the device never idles between steps.  Steps enqueued past a sequence's EOS only
       // append ids that fetch_ids cuts off (each utterance ends at ITS first EOS); at most `ahead` whole-batch steps are
       // wasted after the last sequence finishes.
-      const int ahead = std::max(1, knobs().eos_run_ahead.load());
-      const int limit = max_new - 1;
-      unsigned spins = 0;
-      while (steps < limit) {
-        if (__atomic_load_n(&host_prog[1], __ATOMIC_RELAXED)) break;
-        const int fin = __atomic_load_n(&host_prog[0], __ATOMIC_RELAXED);  // finalize launches completed (prefill = 1)
-        if (steps - std::max(fin - 1, 0) < ahead) {
-          decode_steps(1);
-          ++steps;
-          spins = 0;
-        } else if (++spins > 64) {
-          sched_yield();
-          if ((spins & 0xffff) == 0) {  // a device fault must end the wait: the progress words would never move again
-            const hipError_t q = hipStreamQuery(stream);
-            if (q != hipSuccess && q != hipErrorNotReady) HIPCHK(q);
-            if (q == hipSuccess && steps - std::max(__atomic_load_n(&host_prog[0], __ATOMIC_RELAXED) - 1, 0) >= ahead)
-              fail("greedy loop: the stream drained but the device-side progress counter did not advance");
-          }
-        }
-      }
+      steps = run_ahead(host_prog, max_new - 1, "greedy");
     }
     HIPCHK(hipEventRecord(ev[4], stream));
     HIPCHK(hipStreamSynchronize(stream));
     HIPCHK(hipGetLastError());
-    front_and_total_timings();
-    timings.prefill_ms = stage_ms(2, 3);
-    timings.decode_ms = stage_ms(3, 4);
-    timings.decode_steps = steps; timings.batch = B; timings.total_audio_tokens = total_T; timings.total_prompt_tokens = total_P;
+    decode_timings(steps);
   }
 
   void fetch_ids(int32_t* out, int stride, int32_t* out_lens) {
     if (!have_prefill || beam_w_ > 0) fail("q3a_fetch_ids: nothing generated");
     std::vector<int> all((size_t)B * max_new);
-    HIPCHK(hipMemcpy(all.data(), out_ids.p, all.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(all.data(), step.out_ids.p, all.size() * 4, hipMemcpyDeviceToHost));
     generated_lens(all, out_lens);
     for (int s = 0; s < B; ++s)
       for (int i = 0; i < std::min(out_lens[s], stride); ++i) out[(size_t)s * stride + i] = all[(size_t)s * max_new + i];
@@ -1529,7 +1548,7 @@ struct q3a_engine {
   // lengths of the generated ids per sequence (all = out_ids on the host)
   void generated_lens(const std::vector<int>& all, int32_t* out_lens) {
     std::vector<int> sc(B);
-    HIPCHK(hipMemcpy(sc.data(), step_count.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(sc.data(), step.step_count.p, (size_t)B * 4, hipMemcpyDeviceToHost));
     for (int s = 0; s < B; ++s) {
       int n = std::min(sc[s], max_new), len = 0;
       for (; len < n; ++len) {
@@ -1545,14 +1564,12 @@ struct q3a_engine {
     if (!have_prefill) fail("q3a_fetch_logprobs: nothing generated");
     std::vector<int> all((size_t)B * max_new);
     std::vector<float> lp((size_t)B * max_new);
-    HIPCHK(hipMemcpy(all.data(), out_ids.p, all.size() * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(lp.data(), out_lp.p, lp.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(all.data(), step.out_ids.p, all.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(lp.data(), step.out_lp.p, lp.size() * 4, hipMemcpyDeviceToHost));
     generated_lens(all, out_lens);
     for (int s = 0; s < B; ++s)
       for (int i = 0; i < std::min(out_lens[s], stride); ++i) out[(size_t)s * stride + i] = lp[(size_t)s * max_new + i];
   }
-  bool fixed_mode_ = false;
-  bool head_logits_ = true;  // store the logits of a batched decode step (step API, debug taps); off inside run_resident
 
   // =====================================================================================
   // beam search (include/q3asr.h "beam search"; k_beam.hip).  The B sequences of the batch are U = B / W
@@ -1560,42 +1577,9 @@ struct q3a_engine {
   // history, stop word) -> KV reorder -> the survivors' tokens through the set_tokens path.  Round 0 runs on the prefill's
   // logits; every later round is the tail of a decode step and is captured / replayed with it.  Nothing comes back to the host
   // inside the loop: the history is back-pointers [round][sequence] that beam_fetch follows afterwards.
-  int beam_w_ = 0;                       // > 0: beam mode, slots per utterance (part of the graph signature)
   int beam_dbg_S_ = 0, beam_dbg_W_ = 0;  // shape of the last search's tables (q3a_debug_read "beam_*")
-  DevBuf beam_cand_val, beam_cand_idx, beam_part_max, beam_part_sum, beam_topk_ids, beam_topk_lp, beam_score, beam_finished, beam_parent, beam_token;
-  DevBuf beam_feed, beam_hist_parent, beam_hist_token, beam_hist_lp, beam_state, beam_lo;
   int* beam_prog() const { return host_prog + 2; }  // pinned: [0] advance launches completed, [1] every slot finished
 
-  void enqueue_step() {
-    enqueue_decode_step();
-    if (beam_w_ > 0) enqueue_beam_round();
-  }
-  void enqueue_beam_round() {
-    const int W = beam_w_, S = B, U = B / W;
-    BeamTopkArgs t{};
-    t.logits = logits.as<float>(); t.S = S; t.V = d.vocab; t.W = W;
-    t.cand_val = beam_cand_val.as<float>(); t.cand_idx = beam_cand_idx.as<int>();
-    t.part_max = beam_part_max.as<float>(); t.part_sum = beam_part_sum.as<float>();
-    t.out_ids = beam_topk_ids.as<int>(); t.out_lp = beam_topk_lp.as<float>();
-    timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_beam_topk(t, stream)); });
-    BeamAdvanceArgs a{};
-    a.U = U; a.W = W; a.topk_ids = t.out_ids; a.topk_lp = t.out_lp;
-    a.score = beam_score.as<float>(); a.finished = beam_finished.as<uint8_t>();
-    a.parent = beam_parent.as<int>(); a.token = beam_token.as<int>(); a.feed = beam_feed.as<int>();
-    a.hist_parent = beam_hist_parent.as<int>(); a.hist_token = beam_hist_token.as<int>(); a.hist_lp = beam_hist_lp.as<float>();
-    a.hist_cap = max_new; a.state = beam_state.as<int>();
-    // rows a copy moves: the generated suffix, first row = the prompt length, last = the row the step just appended (pos was advanced)
-    a.pos = d_pos.as<int>(); a.lo = beam_lo.as<int>(); a.hi_bias = -1;
-    a.host_progress = host_prog_dev + 2; a.eos0 = kEos0; a.eos1 = kEos1;
-    timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_beam_advance(a, stream)); });
-    KvReorderArgs r{};
-    r.kcache = kcache.p; r.vcache = vcache.p; r.elem_bytes = (int)kv_elem(); r.layers = d.dec_layers; r.S = S; r.n_kv = d.n_kv; r.max_ctx = max_ctx;
-    r.parent = a.parent; r.lo = a.lo; r.hi = a.pos; r.hi_bias = -1; r.all_done = a.state + BEAM_ST_ALL_DONE;
-    timed(Q3A_KC_OTHER, 0, [&] { KCHK(launch_kv_reorder(r, stream)); });
-    timed(Q3A_KC_OTHER, 0, [&] {
-      KCHK(launch_set_tokens(a.feed, S, wh(L.embed), d.hidden, x_dec.as<float>(), next_tok.as<int>(), stream, first_layer_norm_out()));
-    });
-  }
   // refusals of q3a_beam_begin / q3a_beam_search_batch_ptrs that need the batch (prompt lengths P of B sequences)
   void beam_check(const char* what, int W) const {
     if (W < 1 || W > BEAM_MAX_W) fail(std::string(what) + ": width must be 1..8");
@@ -1612,33 +1596,33 @@ struct q3a_engine {
     if (!head_logits_ || pos_hi_ != *std::max_element(P.begin(), P.end()))
       fail(std::string(what) + ": needs the logits of q3a_prefill (call it directly after the prefill)");
     const int S = B, nc = beam_topk_chunks(d.vocab);
-    beam_cand_val.ensure((size_t)S * nc * W * 4); beam_cand_idx.ensure((size_t)S * nc * W * 4);
-    beam_part_max.ensure((size_t)S * nc * 4); beam_part_sum.ensure((size_t)S * nc * 4);
-    beam_topk_ids.ensure((size_t)S * W * 4); beam_topk_lp.ensure((size_t)S * W * 4);
-    beam_parent.ensure((size_t)S * 4); beam_token.ensure((size_t)S * 4); beam_feed.ensure((size_t)S * 4);
-    beam_hist_parent.ensure((size_t)max_new * S * 4); beam_hist_token.ensure((size_t)max_new * S * 4); beam_hist_lp.ensure((size_t)max_new * S * 4);
+    step.beam_cand_val.ensure((size_t)S * nc * W * 4); step.beam_cand_idx.ensure((size_t)S * nc * W * 4);
+    step.beam_part_max.ensure((size_t)S * nc * 4); step.beam_part_sum.ensure((size_t)S * nc * 4);
+    step.beam_topk_ids.ensure((size_t)S * W * 4); step.beam_topk_lp.ensure((size_t)S * W * 4);
+    step.beam_parent.ensure((size_t)S * 4); step.beam_token.ensure((size_t)S * 4); step.beam_feed.ensure((size_t)S * 4);
+    step.beam_hist_parent.ensure((size_t)max_new * S * 4); step.beam_hist_token.ensure((size_t)max_new * S * 4); step.beam_hist_lp.ensure((size_t)max_new * S * 4);
     std::vector<float> sc((size_t)S, -INFINITY);
     for (int s = 0; s < S; s += W) sc[s] = 0.f;  // only slot 0 of every utterance is live
     std::vector<uint8_t> fin((size_t)S, 0);
     std::vector<int> st(BEAM_ST_COUNT, 0);
-    upload(beam_score, sc, stream); upload(beam_finished, fin, stream); upload(beam_state, st, stream); upload(beam_lo, P, stream);
+    upload(step.beam_score, sc, stream); upload(step.beam_finished, fin, stream); upload(step.beam_state, st, stream); upload(step.beam_lo, P, stream);
     HIPCHK(hipStreamSynchronize(stream));  // (host vectors above; and no earlier launch still writes the progress words)
     __atomic_store_n(&beam_prog()[0], 0, __ATOMIC_RELAXED);
     __atomic_store_n(&beam_prog()[1], 0, __ATOMIC_RELAXED);
     beam_w_ = W; beam_dbg_S_ = S; beam_dbg_W_ = W;
-    enqueue_beam_round();
+    step.enqueue_beam_round();
     HIPCHK(hipGetLastError());
   }
-  // The rounds after round 0, as run_resident's natural-EOS loop: `ahead` steps stay enqueued, the stop word is read from pinned
-  // memory without synchronising.  Returns the decode steps enqueued (at most `ahead` of them after the last round).
-  int beam_loop() {
+  // The natural-EOS loop of the greedy search and of the beam rounds after round 0: `ahead` decode steps stay enqueued in front of
+  // the device, and the two pinned words prog[0] (launches of the step's last kernel completed; the prefill / round 0 counts 1) and
+  // prog[1] (stop) are read without synchronising.  Returns the decode steps enqueued, at most `limit`.
+  int run_ahead(const int* prog, int limit, const char* label) {
     const int ahead = std::max(1, knobs().eos_run_ahead.load());
-    const int limit = max_new - 1;
     int steps = 0;
     unsigned spins = 0;
     while (steps < limit) {
-      if (__atomic_load_n(&beam_prog()[1], __ATOMIC_RELAXED)) break;
-      const int fin = __atomic_load_n(&beam_prog()[0], __ATOMIC_RELAXED);  // advance launches completed (round 0 = 1)
+      if (__atomic_load_n(&prog[1], __ATOMIC_RELAXED)) break;
+      const int fin = __atomic_load_n(&prog[0], __ATOMIC_RELAXED);
       if (steps - std::max(fin - 1, 0) < ahead) {
         decode_steps(1);
         ++steps;
@@ -1648,8 +1632,8 @@ struct q3a_engine {
         if ((spins & 0xffff) == 0) {  // a device fault must end the wait: the progress words would never move again
           const hipError_t q = hipStreamQuery(stream);
           if (q != hipSuccess && q != hipErrorNotReady) HIPCHK(q);
-          if (q == hipSuccess && steps - std::max(__atomic_load_n(&beam_prog()[0], __ATOMIC_RELAXED) - 1, 0) >= ahead)
-            fail("beam loop: the stream drained but the device-side progress counter did not advance");
+          if (q == hipSuccess && steps - std::max(__atomic_load_n(&prog[0], __ATOMIC_RELAXED) - 1, 0) >= ahead)
+            fail(std::string(label) + " loop: the stream drained but the device-side progress counter did not advance");
         }
       }
     }
@@ -1658,7 +1642,7 @@ struct q3a_engine {
   std::vector<int> beam_state_host() {
     std::vector<int> st(BEAM_ST_COUNT);
     HIPCHK(hipStreamSynchronize(stream));
-    HIPCHK(hipMemcpy(st.data(), beam_state.p, st.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(st.data(), step.beam_state.p, st.size() * 4, hipMemcpyDeviceToHost));
     return st;
   }
   // hypotheses of every utterance, best first: out_ids [U][W][stride], out_lens / out_scores / out_finished [U][W], out_lp nullable
@@ -1671,12 +1655,12 @@ struct q3a_engine {
     std::vector<float> hl((size_t)R * S), sc(S);
     std::vector<uint8_t> fin(S);
     if (R > 0) {
-      HIPCHK(hipMemcpy(hp.data(), beam_hist_parent.p, hp.size() * 4, hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(ht.data(), beam_hist_token.p, ht.size() * 4, hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(hl.data(), beam_hist_lp.p, hl.size() * 4, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(hp.data(), step.beam_hist_parent.p, hp.size() * 4, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(ht.data(), step.beam_hist_token.p, ht.size() * 4, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(hl.data(), step.beam_hist_lp.p, hl.size() * 4, hipMemcpyDeviceToHost));
     }
-    HIPCHK(hipMemcpy(sc.data(), beam_score.p, (size_t)S * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(fin.data(), beam_finished.p, (size_t)S, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(sc.data(), step.beam_score.p, (size_t)S * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(fin.data(), step.beam_finished.p, (size_t)S, hipMemcpyDeviceToHost));
     std::vector<int> toks;
     std::vector<float> lps;
     for (int u = 0; u < U; ++u) {
@@ -1730,28 +1714,17 @@ struct q3a_engine {
   }
 };
 
-// audio rows: dec_x[audio_rowmap[t]] = audio_embeds[t]
-void q3a_engine::scatter_audio_rows() {
-  KCHK(launch_scatter_rows(audio_embeds.as<float>(), audio_rowmap.as<int>(), total_T, d.hidden, dec_x.as<float>(), stream));
-}
-
 // =========================================================================================
 // C ABI
 // =========================================================================================
-#define Q3A_TRY(e) try {
-#define Q3A_CATCH(e)                                 \
-  }                                                  \
-  catch (const std::exception& ex) {                 \
-    if (e) (e)->err = ex.what();                     \
-    g_last_error = ex.what();                        \
-    return 1;                                        \
-  }                                                  \
-  catch (...) {                                      \
-    if (e) (e)->err = "unknown error";               \
-    g_last_error = "unknown error";                  \
-    return 1;                                        \
-  }                                                  \
-  return 0;
+
+namespace q3a {
+void set_thread_error(const std::string& msg) { g_last_error = msg; }  // used by host_abi.cpp
+void set_error(q3a_engine* e, const char* msg) {
+  if (e) e->err = msg;
+  g_last_error = msg;
+}
+}  // namespace q3a
 
 extern "C" {
 
@@ -1898,27 +1871,22 @@ int32_t q3a_align_batch_ptrs(q3a_engine* e, const float* const* pcm16k, const in
   if (!e) return 1;
   Q3A_TRY(e)
   e->require_aligner("q3a_align_batch");
-  if (!pcm16k || !n_samples || !text_lens || B < 1 || !out_counts || stride < 0 || (stride > 0 && !out_classes))
-    fail("q3a_align_batch: bad argument");
-  require_utterance_ptrs("q3a_align_batch", pcm16k, B);
-  HIPCHK(hipSetDevice(e->device));
-  e->have_prefill = false;
-  e->set_batch(n_samples, B);  // geometry first: the prompts only need the lengths
-  std::vector<int64_t> toff(B, 0);  // first text id of every utterance
-  for (int s = 0; s < B; ++s) {
-    if (text_lens[s] < 0 || (text_lens[s] > 0 && !text_ids)) fail("q3a_align_batch: bad text");
-    if (s + 1 < B) toff[s + 1] = toff[s] + text_lens[s];
-  }
-  const auto [ids_v, lens] = concat_prompts(B, [&](int s, int32_t* dst) {
-    int32_t len = 0;
-    q3a_build_align_prompt(e->T[s], text_ids ? text_ids + toff[s] : nullptr, text_lens[s], dst, &len);
-    return len;
+  if (!text_lens || !out_counts || stride < 0 || (stride > 0 && !out_classes)) fail("q3a_align_batch: bad argument");
+  std::vector<int> rows;
+  e->whole_path_front("q3a_align_batch", pcm16k, n_samples, B, 1, 1, [&] {
+    std::vector<int64_t> toff(B, 0);  // first text id of every utterance
+    for (int s = 0; s < B; ++s) {
+      if (text_lens[s] < 0 || (text_lens[s] > 0 && !text_ids)) fail("q3a_align_batch: bad text");
+      if (s + 1 < B) toff[s + 1] = toff[s] + text_lens[s];
+    }
+    auto pr = concat_prompts(B, [&](int s, int32_t* dst) {
+      int32_t len = 0;
+      q3a_build_align_prompt(e->T[s], text_ids ? text_ids + toff[s] : nullptr, text_lens[s], dst, &len);
+      return len;
+    });
+    rows = e->align_marker_rows(pr.first.data(), pr.second.data(), B, stride, out_counts);
+    return pr;
   });
-  const std::vector<int> rows = e->align_marker_rows(ids_v.data(), lens.data(), B, stride, out_counts);
-  e->setup_prompts(ids_v.data(), lens.data(), B, 1, true);
-  e->timings = q3a_timings{};
-  e->upload_ptrs_and_mel(pcm16k, n_samples, B);
-  e->run_encoder();
   e->run_align(rows, out_counts, stride, out_classes, nullptr);
   e->front_and_total_timings();
   Q3A_CATCH(e)
@@ -1948,17 +1916,13 @@ int32_t q3a_score_batch_ptrs(q3a_engine* e, const float* const* pcm16k, const in
   if (!e) return 1;
   Q3A_TRY(e)
   e->require_asr("q3a_score_batch");
-  if (!pcm16k || !n_samples || !target_lens || B < 1 || stride < 0 || (stride > 0 && !out_lp) || n_prefix < 0) fail("q3a_score_batch: bad argument");
-  require_utterance_ptrs("q3a_score_batch", pcm16k, B);
-  HIPCHK(hipSetDevice(e->device));
-  e->have_prefill = false;
-  e->set_batch(n_samples, B);  // geometry first: the prompts only need the lengths
-  const auto [pids, plens] = e->asr_prompts(lang_prefix_ids, n_prefix);
-  const auto sp = e->score_plan("q3a_score_batch", pids.data(), plens.data(), target_ids, target_lens, B, stride);
-  e->setup_prompts(sp.ids.data(), sp.lens.data(), B, 1, true);
-  e->timings = q3a_timings{};
-  e->upload_ptrs_and_mel(pcm16k, n_samples, B);
-  e->run_encoder();
+  if (!target_lens || stride < 0 || (stride > 0 && !out_lp) || n_prefix < 0) fail("q3a_score_batch: bad argument");
+  q3a_engine::ScorePlan sp;
+  e->whole_path_front("q3a_score_batch", pcm16k, n_samples, B, 1, 1, [&] {
+    const auto pr = e->asr_prompts(lang_prefix_ids, n_prefix);
+    sp = e->score_plan("q3a_score_batch", pr.first.data(), pr.second.data(), target_ids, target_lens, B, stride);
+    return std::tie(sp.ids, sp.lens);
+  });
   e->run_score(sp, target_lens, stride, out_lp, out_top_ids, out_top_lp, nullptr);
   e->front_and_total_timings();
   Q3A_CATCH(e)
@@ -1988,7 +1952,7 @@ int32_t q3a_beam_step(q3a_engine* e, uint8_t* all_finished, float* logits_out) {
   const std::vector<int> st = e->beam_state_host();
   HIPCHK(hipGetLastError());
   if (all_finished) *all_finished = st[BEAM_ST_ALL_DONE] ? 1 : 0;
-  if (logits_out) HIPCHK(hipMemcpy(logits_out, e->logits.p, (size_t)e->B * e->d.vocab * 4, hipMemcpyDeviceToHost));
+  if (logits_out) HIPCHK(hipMemcpy(logits_out, e->step.logits.p, (size_t)e->B * e->d.vocab * 4, hipMemcpyDeviceToHost));
   Q3A_CATCH(e)
 }
 
@@ -2010,127 +1974,27 @@ int32_t q3a_beam_search_batch_ptrs(q3a_engine* e, const float* const* pcm16k, co
   if (!e) return 1;
   Q3A_TRY(e)
   e->require_asr("q3a_beam_search_batch");
-  if (!pcm16k || !n_samples || U < 1 || !out_lens || stride < 0 || (stride > 0 && !out_ids) || n_prefix < 0) fail("q3a_beam_search_batch: bad argument");
+  if (U < 1 || !out_lens || stride < 0 || (stride > 0 && !out_ids) || n_prefix < 0) fail("q3a_beam_search_batch: bad argument");
   if (width < 1 || width > BEAM_MAX_W) fail("q3a_beam_search_batch: width must be 1..8");
   if ((int64_t)U * width > 32) fail("q3a_beam_search_batch: utterances x width = " + std::to_string((int64_t)U * width) + " exceeds 32 sequences");
   const int cap = e->opts.max_new_tokens, want = max_new <= 0 ? cap : std::min(max_new, cap);
   if (stride < want) fail("q3a_beam_search_batch: stride " + std::to_string(stride) + " is below max_new " + std::to_string(want));
-  require_utterance_ptrs("q3a_beam_search_batch", pcm16k, U);
-  HIPCHK(hipSetDevice(e->device));
-  // the W slots of an utterance are W ordinary sequences of the batch: the clip is uploaded once per slot
-  const int S = U * width;
-  std::vector<const float*> ptrs((size_t)S);
-  std::vector<int64_t> ns((size_t)S);
-  for (int s = 0; s < S; ++s) { ptrs[s] = pcm16k[s / width]; ns[s] = n_samples[s / width]; }
   e->fixed_mode_ = false;
   e->head_logits_ = true;  // every round selects on the stored logits
-  e->have_prefill = false;
-  e->set_batch(ns.data(), S);
-  e->prepare_prompts(lang_prefix_ids, n_prefix, want, 0);
-  e->timings = q3a_timings{};
-  e->upload_ptrs_and_mel(ptrs.data(), ns.data(), S);
-  e->run_encoder();
+  // the W slots of an utterance are W ordinary sequences of the batch
+  e->whole_path_front("q3a_beam_search_batch", pcm16k, n_samples, U, width, want, [&] { return e->asr_prompts(lang_prefix_ids, n_prefix); });
   HIPCHK(hipEventRecord(e->ev[2], e->stream));
   e->run_prefill();
   HIPCHK(hipEventRecord(e->ev[3], e->stream));
   e->beam_begin("q3a_beam_search_batch", width);
-  e->beam_loop();
+  e->run_ahead(e->beam_prog(), e->max_new - 1, "beam");
   HIPCHK(hipEventRecord(e->ev[4], e->stream));
   const std::vector<int> st = e->beam_state_host();
   HIPCHK(hipGetLastError());
-  e->front_and_total_timings();
-  e->timings.prefill_ms = e->stage_ms(2, 3);
-  e->timings.decode_ms = e->stage_ms(3, 4);
-  e->timings.decode_steps = std::max(st[BEAM_ST_ROUNDS] - 1, 0); e->timings.batch = e->B; e->timings.total_audio_tokens = e->total_T;
-  e->timings.total_prompt_tokens = e->total_P;
+  e->decode_timings(std::max(st[BEAM_ST_ROUNDS] - 1, 0));
   e->beam_fetch(out_ids, stride, out_lens, out_scores, out_finished, out_lp);
   // as after q3a_score: no decode state until the next prefill
-  e->beam_w_ = 0;
-  e->have_prefill = false;
-  Q3A_CATCH(e)
-}
-
-// ---- beam kernels on their own (no model): host arrays in, host arrays out, the product launches in between -------------------------
-int32_t q3a_selftest_beam_topk(int32_t device, const float* logits, int32_t S, int32_t V, int32_t W, int32_t* out_ids, float* out_lp) {
-  q3a_engine* e = nullptr;
-  Q3A_TRY(e)
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) fail("no HIP device available");
-  if (!logits || !out_ids || !out_lp || S < 1 || V < 1) fail("q3a_selftest_beam_topk: bad argument");
-  HIPCHK(hipSetDevice(device));
-  const int nc = beam_topk_chunks(V);
-  DevBuf dLg, dCv, dCi, dPm, dPs, dOi, dOl;
-  dLg.ensure((size_t)S * V * 4); dCv.ensure((size_t)S * nc * BEAM_MAX_W * 4); dCi.ensure((size_t)S * nc * BEAM_MAX_W * 4);
-  dPm.ensure((size_t)S * nc * 4); dPs.ensure((size_t)S * nc * 4); dOi.ensure((size_t)S * BEAM_MAX_W * 4); dOl.ensure((size_t)S * BEAM_MAX_W * 4);
-  HIPCHK(hipMemcpy(dLg.p, logits, (size_t)S * V * 4, hipMemcpyHostToDevice));
-  BeamTopkArgs t{dLg.as<float>(), S, V, W, dCv.as<float>(), dCi.as<int>(), dPm.as<float>(), dPs.as<float>(), dOi.as<int>(), dOl.as<float>()};
-  KCHK(launch_beam_topk(t, nullptr));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpy(out_ids, dOi.p, (size_t)S * W * 4, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(out_lp, dOl.p, (size_t)S * W * 4, hipMemcpyDeviceToHost));
-  Q3A_CATCH(e)
-}
-
-int32_t q3a_selftest_beam_advance(int32_t device, int32_t U, int32_t W, const int32_t* topk_ids, const float* topk_lp, const float* score_in,
-                                  const uint8_t* finished_in, int32_t* parent_out, int32_t* token_out, float* score_out, uint8_t* finished_out) {
-  q3a_engine* e = nullptr;
-  Q3A_TRY(e)
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) fail("no HIP device available");
-  if (!topk_ids || !topk_lp || !score_in || !finished_in || !parent_out || !token_out || !score_out || !finished_out || U < 1 || W < 1 || W > BEAM_MAX_W || U * W > 32)
-    fail("q3a_selftest_beam_advance: bad argument");
-  HIPCHK(hipSetDevice(device));
-  const size_t S = (size_t)U * W;
-  DevBuf dTi, dTl, dSc, dFi, dPa, dTo, dSt;
-  dTi.ensure(S * W * 4); dTl.ensure(S * W * 4); dSc.ensure(S * 4); dFi.ensure(S); dPa.ensure(S * 4); dTo.ensure(S * 4); dSt.ensure(BEAM_ST_COUNT * 4);
-  HIPCHK(hipMemcpy(dTi.p, topk_ids, S * W * 4, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dTl.p, topk_lp, S * W * 4, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dSc.p, score_in, S * 4, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dFi.p, finished_in, S, hipMemcpyHostToDevice));
-  HIPCHK(hipMemset(dSt.p, 0, BEAM_ST_COUNT * 4));
-  BeamAdvanceArgs a{};
-  a.U = U; a.W = W; a.topk_ids = dTi.as<int>(); a.topk_lp = dTl.as<float>(); a.score = dSc.as<float>(); a.finished = dFi.as<uint8_t>();
-  a.parent = dPa.as<int>(); a.token = dTo.as<int>(); a.state = dSt.as<int>(); a.eos0 = kEos0; a.eos1 = kEos1;
-  KCHK(launch_beam_advance(a, nullptr));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpy(parent_out, dPa.p, S * 4, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(token_out, dTo.p, S * 4, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(score_out, dSc.p, S * 4, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(finished_out, dFi.p, S, hipMemcpyDeviceToHost));
-  Q3A_CATCH(e)
-}
-
-int32_t q3a_selftest_kv_reorder(int32_t device, void* cache, int32_t elem_bytes, int32_t layers, int32_t S, int32_t n_kv, int32_t max_ctx,
-                                const int32_t* lo, const int32_t* hi, const int32_t* parent) {
-  q3a_engine* e = nullptr;
-  Q3A_TRY(e)
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) fail("no HIP device available");
-  if (!cache || !lo || !hi || !parent || layers < 1 || S < 1 || S > 32 || n_kv < 1 || max_ctx < 1 || (elem_bytes != 2 && elem_bytes != 4))
-    fail("q3a_selftest_kv_reorder: bad argument");
-  for (int s = 0; s < S; ++s) {  // bounds before anything runs: a copy stays inside the cache and inside one utterance's rows
-    const int p = parent[s];
-    if (p < 0 || p >= S) fail("q3a_selftest_kv_reorder: parent out of range");
-    if (lo[s] < 0 || hi[s] >= max_ctx) fail("q3a_selftest_kv_reorder: rows outside the cache");
-    if (p != s && (lo[p] != lo[s] || hi[p] != hi[s])) fail("q3a_selftest_kv_reorder: a parent must share its child's row range (a slot of the same utterance)");
-  }
-  HIPCHK(hipSetDevice(device));
-  const size_t half = (size_t)layers * S * n_kv * max_ctx * 128 * elem_bytes;  // K, then V
-  DevBuf dC, dLo, dHi, dPar;
-  dC.ensure(2 * half); dLo.ensure((size_t)S * 4); dHi.ensure((size_t)S * 4); dPar.ensure((size_t)S * 4);
-  HIPCHK(hipMemcpy(dC.p, cache, 2 * half, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dLo.p, lo, (size_t)S * 4, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dHi.p, hi, (size_t)S * 4, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dPar.p, parent, (size_t)S * 4, hipMemcpyHostToDevice));
-  KvReorderArgs r{};
-  r.kcache = dC.p; r.vcache = (uint8_t*)dC.p + half; r.elem_bytes = elem_bytes; r.layers = layers; r.S = S; r.n_kv = n_kv; r.max_ctx = max_ctx;
-  r.parent = dPar.as<int>(); r.lo = dLo.as<int>(); r.hi = dHi.as<int>();
-  KCHK(launch_kv_reorder(r, nullptr));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpy(cache, dC.p, 2 * half, hipMemcpyDeviceToHost));
+  e->beam_w_ = 0; e->have_prefill = false;
   Q3A_CATCH(e)
 }
 
@@ -2187,8 +2051,8 @@ int32_t q3a_prefill(q3a_engine* e, const int32_t* ids, const int32_t* lens, int3
   e->run_prefill();
   HIPCHK(hipStreamSynchronize(e->stream));
   HIPCHK(hipGetLastError());
-  if (last_logits_out) HIPCHK(hipMemcpy(last_logits_out, e->logits.p, (size_t)B * e->d.vocab * 4, hipMemcpyDeviceToHost));
-  if (next_ids) HIPCHK(hipMemcpy(next_ids, e->next_tok.p, (size_t)B * 4, hipMemcpyDeviceToHost));
+  if (last_logits_out) HIPCHK(hipMemcpy(last_logits_out, e->step.logits.p, (size_t)B * e->d.vocab * 4, hipMemcpyDeviceToHost));
+  if (next_ids) HIPCHK(hipMemcpy(next_ids, e->step.next_tok.p, (size_t)B * 4, hipMemcpyDeviceToHost));
   Q3A_CATCH(e)
 }
 
@@ -2201,7 +2065,7 @@ int32_t q3a_decode_step(q3a_engine* e, int32_t* next_ids, uint8_t* done, float* 
   {
     // capacity guard: position of the token being fed must stay inside the cache
     std::vector<int> pos(e->B);
-    HIPCHK(hipMemcpy(pos.data(), e->d_pos.p, (size_t)e->B * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(pos.data(), e->step.d_pos.p, (size_t)e->B * 4, hipMemcpyDeviceToHost));
     for (int s = 0; s < e->B; ++s)
       if (pos[s] + 1 > e->max_ctx) fail("q3a_decode_step: KV cache capacity exhausted (max_new_tokens reached)");
   }
@@ -2209,9 +2073,9 @@ int32_t q3a_decode_step(q3a_engine* e, int32_t* next_ids, uint8_t* done, float* 
   e->decode_steps(1);
   HIPCHK(hipStreamSynchronize(e->stream));
   HIPCHK(hipGetLastError());
-  if (next_ids) HIPCHK(hipMemcpy(next_ids, e->next_tok.p, (size_t)e->B * 4, hipMemcpyDeviceToHost));
-  if (done) HIPCHK(hipMemcpy(done, e->done.p, (size_t)e->B, hipMemcpyDeviceToHost));
-  if (logits_out) HIPCHK(hipMemcpy(logits_out, e->logits.p, (size_t)e->B * e->d.vocab * 4, hipMemcpyDeviceToHost));
+  if (next_ids) HIPCHK(hipMemcpy(next_ids, e->step.next_tok.p, (size_t)e->B * 4, hipMemcpyDeviceToHost));
+  if (done) HIPCHK(hipMemcpy(done, e->step.done.p, (size_t)e->B, hipMemcpyDeviceToHost));
+  if (logits_out) HIPCHK(hipMemcpy(logits_out, e->step.logits.p, (size_t)e->B * e->d.vocab * 4, hipMemcpyDeviceToHost));
   Q3A_CATCH(e)
 }
 
@@ -2222,9 +2086,9 @@ int32_t q3a_set_next_tokens(q3a_engine* e, const int32_t* ids, int32_t B) {
   if (!e->have_prefill || B != e->B || e->beam_w_ > 0) fail("q3a_set_next_tokens: no decode state / batch mismatch");
   for (int s = 0; s < B; ++s)
     if (ids[s] < 0 || ids[s] >= e->d.vocab) fail("q3a_set_next_tokens: token id out of range");
-  HIPCHK(hipMemcpy(e->forced_tok.p, ids, (size_t)B * 4, hipMemcpyHostToDevice));
-  KCHK(launch_set_tokens(e->forced_tok.as<int>(), B, e->wh(e->L.embed), e->d.hidden, e->x_dec.as<float>(),
-                         e->next_tok.as<int>(), e->stream, e->first_layer_norm_out()));
+  HIPCHK(hipMemcpy(e->step.forced_tok.p, ids, (size_t)B * 4, hipMemcpyHostToDevice));
+  KCHK(launch_set_tokens(e->step.forced_tok.as<int>(), B, e->wh(e->L.embed), e->d.hidden, e->step.x_dec.as<float>(),
+                         e->step.next_tok.as<int>(), e->stream, e->step.first_layer_norm_out()));
   HIPCHK(hipStreamSynchronize(e->stream));
   Q3A_CATCH(e)
 }
@@ -2238,7 +2102,10 @@ int32_t q3a_run_resident(q3a_engine* e, const int32_t* lang_prefix_ids, int32_t 
   e->fixed_mode_ = fixed_new_tokens > 0;
   e->head_logits_ = e->opts.debug_taps != 0;
   e->have_mel = e->have_enc = e->have_prefill = false;
-  e->prepare_prompts(lang_prefix_ids, n_prefix, max_new, fixed_new_tokens);
+  if (e->B <= 0) fail("q3a_run_resident: no batch uploaded");
+  // prompts and every table / buffer of the prefill + decode: host integers only (T[] of set_batch), before the batch's first kernel
+  const auto pr = e->asr_prompts(lang_prefix_ids, n_prefix);
+  e->setup_prompts(pr.first.data(), pr.second.data(), e->B, e->max_new_request(max_new, fixed_new_tokens), true);
   e->run_resident(fixed_new_tokens);
   Q3A_CATCH(e)
 }
@@ -2266,15 +2133,11 @@ int32_t q3a_transcribe_batch_ptrs(q3a_engine* e, const float* const* pcm16k, con
   if (!e) return 1;
   Q3A_TRY(e)
   e->require_asr("q3a_transcribe_batch");
-  if (!pcm16k || !n_samples || B < 1) fail("q3a_transcribe_batch: bad argument");
-  require_utterance_ptrs("q3a_transcribe_batch", pcm16k, B);
   const auto w0 = std::chrono::steady_clock::now();
-  HIPCHK(hipSetDevice(e->device));
   e->fixed_mode_ = fixed_new_tokens > 0;
   e->head_logits_ = e->opts.debug_taps != 0;
-  e->set_batch(n_samples, B);  // geometry first: the prompts only need the lengths, and their set-up synchronises an idle stream
-  e->prepare_prompts(lang_prefix_ids, n_prefix, max_new, fixed_new_tokens);
-  e->upload_ptrs_and_mel(pcm16k, n_samples, B);
+  e->whole_path_front("q3a_transcribe_batch", pcm16k, n_samples, B, 1, e->max_new_request(max_new, fixed_new_tokens),
+                      [&] { return e->asr_prompts(lang_prefix_ids, n_prefix); });
   e->run_resident(fixed_new_tokens, true);
   e->fetch_ids(out_ids, stride, out_lens);
   if (e->io.mode != 0) {
@@ -2291,11 +2154,7 @@ int32_t q3a_transcribe_batch(q3a_engine* e, const float* pcm16k, const int64_t* 
                              const int32_t* lang_prefix_ids, int32_t n_prefix, int32_t max_new, int32_t fixed_new_tokens,
                              int32_t* out_ids, int32_t stride, int32_t* out_lens) {
   if (!e) return 1;
-  if (e->d.aligner()) {
-    e->err = g_last_error = "q3a_transcribe_batch: this engine holds a forced aligner (classify_num in config.json); use q3a_align*";
-    return 1;
-  }
-  if (!pcm16k || !n_samples || B < 1) { e->err = "q3a_transcribe_batch: bad argument"; return 1; }
+  if (!pcm16k || !n_samples || B < 1) { e->err = "q3a_transcribe_batch: bad argument"; return 1; }  // (the rest: the _ptrs form's checks)
   std::vector<const float*> ptrs((size_t)B);
   int64_t off = 0;
   for (int u = 0; u < B; ++u) { ptrs[u] = pcm16k + off; off += n_samples[u]; }
@@ -2354,12 +2213,12 @@ int32_t q3a_profile_weight_stream(q3a_engine* e, int32_t reps, float* avg_us, do
   auto sweep = [&]() {
     for (int li = 0; li < d.dec_layers; ++li) {
       const DecLayerOff& l = e->L.dec[li];
-      const auto pj = e->layer_projs(li);
-      GemvArgs g = e->gemv_args(pj.qkv);
-      g.x = e->x_dec.as<float>(); g.rms_w = e->wf(l.in_ln); g.out = e->s_qkv.as<float>();
+      const auto pj = e->step.layer_projs(li);
+      GemvArgs g = e->step.gemv_args(pj.qkv);
+      g.x = e->step.x_dec.as<float>(); g.rms_w = e->wf(l.in_ln); g.out = e->step.s_qkv.as<float>();
       KCHK(launch_gemv(g, S, e->stream));
-      GemvArgs u = e->gemv_args(pj.gu);
-      u.x = e->x_dec.as<float>(); u.rms_w = e->wf(l.post_ln); u.out = e->s_act.as<float>();
+      GemvArgs u = e->step.gemv_args(pj.gu);
+      u.x = e->step.x_dec.as<float>(); u.rms_w = e->wf(l.post_ln); u.out = e->step.s_act.as<float>();
       KCHK(launch_gemv(u, S, e->stream));
     }
   };
@@ -2388,7 +2247,7 @@ int32_t q3a_profile_weight_stream(q3a_engine* e, int32_t reps, float* avg_us, do
   (void)hipGraphExecDestroy(ge);
   const int n = reps * d.dec_layers * 2;
   if (avg_us) *avg_us = ms * 1000.f / (float)n;
-  const auto pj0 = e->layer_projs(0);
+  const auto pj0 = e->step.layer_projs(0);
   if (bytes_per_launch) *bytes_per_launch = (pj0.qkv.bytes + pj0.gu.bytes) / 2.0;
   if (launches) *launches = n;
   Q3A_CATCH(e)
@@ -2410,7 +2269,7 @@ int32_t q3a_debug_read(q3a_engine* e, const char* name, void* dst, uint64_t byte
   // counters and times, not taps: readable without opts.debug_taps
   const uint64_t device_bytes = g_device_bytes.load();
   const struct { const char* name; const void* src; size_t n; bool on_device; } scalars[] = {
-      {"lm_head_prune_stats", e->prune_stats.p, 8, true},
+      {"lm_head_prune_stats", e->step.prune_stats.p, 8, true},
       {"align_head_ms", &e->align_head_ms, 4, false},  // the aligner head's launches (norm, classifier, merge) of the last align call
       {"score_head_ms", &e->score_head_ms, 4, false},  // the scoring head's launches (norm, lm_head with the reducing epilogue, merge) of the last score call
       {"device_bytes", &device_bytes, 8, false},       // device memory the DevBufs of the whole process hold
@@ -2420,9 +2279,9 @@ int32_t q3a_debug_read(q3a_engine* e, const char* name, void* dst, uint64_t byte
   // the last round of the last beam search (tables of beam_dbg_S_ sequences x beam_dbg_W_)
   const size_t bS = (size_t)e->beam_dbg_S_, bW = (size_t)e->beam_dbg_W_;
   const struct { const char* name; const DevBuf* buf; size_t n; } beams[] = {
-      {"beam_topk_ids", &e->beam_topk_ids, bS * bW * 4}, {"beam_topk_lp", &e->beam_topk_lp, bS * bW * 4},
-      {"beam_parent", &e->beam_parent, bS * 4}, {"beam_token", &e->beam_token, bS * 4}, {"beam_score", &e->beam_score, bS * 4},
-      {"beam_finished", &e->beam_finished, bS}, {"beam_stats", &e->beam_state, 16},
+      {"beam_topk_ids", &e->step.beam_topk_ids, bS * bW * 4}, {"beam_topk_lp", &e->step.beam_topk_lp, bS * bW * 4},
+      {"beam_parent", &e->step.beam_parent, bS * 4}, {"beam_token", &e->step.beam_token, bS * 4}, {"beam_score", &e->step.beam_score, bS * 4},
+      {"beam_finished", &e->step.beam_finished, bS}, {"beam_stats", &e->step.beam_state, 16},
   };
   for (const auto& bm : beams)
     if (strcmp(name, bm.name) == 0) {
@@ -2430,9 +2289,9 @@ int32_t q3a_debug_read(q3a_engine* e, const char* name, void* dst, uint64_t byte
       give(bm.buf->p, bm.n, true);
       return 0;
     }
-  auto it = e->taps.find(name);
-  if (it == e->taps.end()) fail(std::string("q3a_debug_read: no tap named '") + name + "' (opts.debug_taps set?)");
-  give(it->second.p, e->tap_bytes[name], true);
+  auto it = e->taps.bufs.find(name);
+  if (it == e->taps.bufs.end()) fail(std::string("q3a_debug_read: no tap named '") + name + "' (opts.debug_taps set?)");
+  give(it->second.p, e->taps.bytes[name], true);
   Q3A_CATCH(e)
 }
 
@@ -2442,156 +2301,6 @@ int32_t q3a_debug_set(const char* key, int32_t value) {
     if (strcmp(key, t.key) == 0) { (knobs().*t.field).store(value); return 0; }
   g_last_error = std::string("q3a_debug_set: unknown key '") + key + "'";
   return 1;
-}
-
-int32_t q3a_selftest_gemm(int32_t device, int32_t M, int32_t N, int32_t K, int32_t split, float* max_abs_err,
-                          float* ref_abs_max) {
-  q3a_engine* e = nullptr;
-  Q3A_TRY(e)
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) fail("no HIP device available");
-  HIPCHK(hipSetDevice(device));
-  std::vector<float> X((size_t)M * K);
-  std::vector<uint16_t> W((size_t)N * K);
-  uint32_t st = 12345u;
-  auto rnd = [&]() { st = st * 1664525u + 1013904223u; return ((st >> 8) & 0xffff) / 65536.0f - 0.5f; };
-  for (auto& v : X) v = rnd();
-  for (auto& v : W) { float f = rnd(); uint32_t u; memcpy(&u, &f, 4); v = (uint16_t)(u >> 16); }  // truncation is fine for a test
-  DevBuf dX, dW, dY, dR;
-  dX.ensure(X.size() * 4); dW.ensure(W.size() * 2); dY.ensure((size_t)M * N * 4); dR.ensure((size_t)M * N * 4);
-  HIPCHK(hipMemcpy(dX.p, X.data(), X.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dW.p, W.data(), W.size() * 2, hipMemcpyHostToDevice));
-  GemmEpilogue ep; ep.out = dY.as<float>(); ep.ldo = N;
-  KCHK(launch_gemm(dX.as<float>(), K, dW.as<uint16_t>(), M, N, K, ep, false, split != 0, nullptr));
-  launch_gemm_ref(dX.as<float>(), dW.as<uint16_t>(), dR.as<float>(), M, N, K, nullptr);
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipGetLastError());
-  std::vector<float> Y((size_t)M * N), R((size_t)M * N);
-  HIPCHK(hipMemcpy(Y.data(), dY.p, Y.size() * 4, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(R.data(), dR.p, R.size() * 4, hipMemcpyDeviceToHost));
-  float me = 0.f, rm = 0.f;
-  for (size_t i = 0; i < Y.size(); ++i) { me = std::max(me, std::fabs(Y[i] - R[i])); rm = std::max(rm, std::fabs(R[i])); }
-  if (max_abs_err) *max_abs_err = me;
-  if (ref_abs_max) *ref_abs_max = rm;
-  Q3A_CATCH(e)
-}
-
-int32_t q3a_selftest_gemm16(int32_t device, int32_t M, int32_t N, int32_t K, int32_t reps, float* max_abs_err,
-                            float* ref_abs_max, float* avg_us_bf16, float* avg_us_f32) {
-  q3a_engine* e = nullptr;
-  Q3A_TRY(e)
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) fail("no HIP device available");
-  HIPCHK(hipSetDevice(device));
-  std::vector<float> X((size_t)M * K);
-  std::vector<uint16_t> W((size_t)N * K);
-  uint32_t st = 777u;
-  auto rnd = [&]() { st = st * 1664525u + 1013904223u; return ((st >> 8) & 0xffff) / 65536.0f - 0.5f; };
-  auto trunc16 = [](float f) { uint32_t u; memcpy(&u, &f, 4); u &= 0xffff0000u; memcpy(&f, &u, 4); return f; };
-  for (auto& v : X) v = trunc16(rnd());  // bf16-representable activations: the bf16 copy is exact
-  for (auto& v : W) { float f = rnd(); uint32_t u; memcpy(&u, &f, 4); v = (uint16_t)(u >> 16); }
-  DevBuf dX, dX16, dW, dY, dR;
-  dX.ensure(X.size() * 4); dX16.ensure(X.size() * 2); dW.ensure(W.size() * 2); dY.ensure((size_t)M * N * 4); dR.ensure((size_t)M * N * 4);
-  HIPCHK(hipMemcpy(dX.p, X.data(), X.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dW.p, W.data(), W.size() * 2, hipMemcpyHostToDevice));
-  KCHK(launch_to_bf16(dX.as<float>(), dX16.as<uint16_t>(), X.size(), nullptr));
-  GemmEpilogue ep; ep.out = dY.as<float>(); ep.ldo = N;
-  KCHK(launch_gemm16(dX16.as<uint16_t>(), K, dW.as<uint16_t>(), M, N, K, ep, false, nullptr));
-  launch_gemm_ref(dX.as<float>(), dW.as<uint16_t>(), dR.as<float>(), M, N, K, nullptr);
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipGetLastError());
-  std::vector<float> Y((size_t)M * N), R((size_t)M * N);
-  HIPCHK(hipMemcpy(Y.data(), dY.p, Y.size() * 4, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(R.data(), dR.p, R.size() * 4, hipMemcpyDeviceToHost));
-  float me = 0.f, rm = 0.f;
-  for (size_t i = 0; i < Y.size(); ++i) { me = std::max(me, std::fabs(Y[i] - R[i])); rm = std::max(rm, std::fabs(R[i])); }
-  // ---- the epilogue variants, against the reference product R ----
-  {
-    const int P = 7;  // addend period
-    std::vector<float> bias(N), addend((size_t)P * N), resid((size_t)M * N);
-    std::vector<int> rowmap(M);
-    for (auto& v : bias) v = rnd();
-    for (auto& v : addend) v = rnd();
-    for (auto& v : resid) v = rnd();
-    for (int m = 0; m < M; ++m) rowmap[m] = (m % 11 == 5) ? -1 : M - 1 - m;  // reversed rows, some dropped
-    DevBuf dB, dA, dS, dM, dY2, dY16;
-    dB.ensure(bias.size() * 4); dA.ensure(addend.size() * 4); dS.ensure(resid.size() * 4); dM.ensure(rowmap.size() * 4);
-    dY2.ensure((size_t)M * N * 4); dY16.ensure((size_t)M * N * 2);
-    HIPCHK(hipMemcpy(dB.p, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dA.p, addend.data(), addend.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dS.p, resid.data(), resid.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dM.p, rowmap.data(), rowmap.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(dY2.p, 0, (size_t)M * N * 4));
-    // (a) fp32 out: bias + periodic addend + row map + residual
-    GemmEpilogue e2; e2.out = dY2.as<float>(); e2.ldo = N; e2.bias = dB.as<float>(); e2.addend = dA.as<float>(); e2.addend_period = P;
-    e2.rowmap = dM.as<int>(); e2.resid = dS.as<float>();
-    KCHK(launch_gemm16(dX16.as<uint16_t>(), K, dW.as<uint16_t>(), M, N, K, e2, false, nullptr));
-    HIPCHK(hipDeviceSynchronize());
-    std::vector<float> Y2((size_t)M * N);
-    HIPCHK(hipMemcpy(Y2.data(), dY2.p, Y2.size() * 4, hipMemcpyDeviceToHost));
-    std::vector<char> hit(M, 0);
-    for (int m = 0; m < M; ++m) {
-      const int o = rowmap[m];
-      if (o < 0) continue;
-      hit[o] = 1;
-      for (int n = 0; n < N; ++n) {
-        const float want = R[(size_t)m * N + n] + bias[n] + addend[(size_t)(m % P) * N + n] + resid[(size_t)o * N + n];
-        me = std::max(me, std::fabs(Y2[(size_t)o * N + n] - want));
-      }
-    }
-    for (int o = 0; o < M; ++o)
-      if (!hit[o])
-        for (int n = 0; n < N; ++n)
-          if (Y2[(size_t)o * N + n] != 0.f) fail("selftest_gemm16: a row dropped by the row map was written");
-    // (b) bf16 out: bias only; one bf16 ulp
-    auto bf = [](uint16_t h) { uint32_t u = (uint32_t)h << 16; float f; memcpy(&f, &u, 4); return f; };
-    GemmEpilogue e3; e3.out16 = dY16.as<uint16_t>(); e3.ldo = N; e3.bias = dB.as<float>();
-    KCHK(launch_gemm16(dX16.as<uint16_t>(), K, dW.as<uint16_t>(), M, N, K, e3, false, nullptr));
-    HIPCHK(hipDeviceSynchronize());
-    std::vector<uint16_t> Y16((size_t)M * N);
-    HIPCHK(hipMemcpy(Y16.data(), dY16.p, Y16.size() * 2, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < Y16.size(); ++i) {
-      const float want = R[i] + bias[i % N];
-      if (std::fabs(bf(Y16[i]) - want) > std::fabs(want) / 128.f + 1e-4f * std::max(rm, 1.f)) fail("selftest_gemm16: bf16 output with bias is off by more than an ulp");
-    }
-    // (c) SwiGLU pairs ([16 gate | 16 up] row blocks of W), bf16 out
-    if (N % 32 == 0) {
-      GemmEpilogue e4; e4.out16 = dY16.as<uint16_t>(); e4.ldo = N / 2;
-      KCHK(launch_gemm16(dX16.as<uint16_t>(), K, dW.as<uint16_t>(), M, N, K, e4, true, nullptr));
-      HIPCHK(hipDeviceSynchronize());
-      HIPCHK(hipMemcpy(Y16.data(), dY16.p, (size_t)M * (N / 2) * 2, hipMemcpyDeviceToHost));
-      for (int m = 0; m < M; ++m)
-        for (int c = 0; c < N / 2; ++c) {
-          const float g = R[(size_t)m * N + (c / 16) * 32 + c % 16], u = R[(size_t)m * N + (c / 16) * 32 + 16 + c % 16];
-          const float want = g / (1.f + std::exp(-g)) * u;
-          if (std::fabs(bf(Y16[(size_t)m * (N / 2) + c]) - want) > std::fabs(want) / 64.f + 1e-3f * std::max(rm * rm, 1.f))
-            fail("selftest_gemm16: SwiGLU epilogue is off");
-        }
-    }
-  }
-  if (max_abs_err) *max_abs_err = me;
-  if (ref_abs_max) *ref_abs_max = rm;
-  if (reps > 0) {
-    hipEvent_t a, b;
-    HIPCHK(hipEventCreate(&a));
-    HIPCHK(hipEventCreate(&b));
-    float ms = 0.f;
-    HIPCHK(hipEventRecord(a, nullptr));
-    for (int r = 0; r < reps; ++r) KCHK(launch_gemm16(dX16.as<uint16_t>(), K, dW.as<uint16_t>(), M, N, K, ep, false, nullptr));
-    HIPCHK(hipEventRecord(b, nullptr));
-    HIPCHK(hipEventSynchronize(b));
-    HIPCHK(hipEventElapsedTime(&ms, a, b));
-    if (avg_us_bf16) *avg_us_bf16 = ms * 1000.f / reps;
-    HIPCHK(hipEventRecord(a, nullptr));
-    for (int r = 0; r < reps; ++r) KCHK(launch_gemm(dX.as<float>(), K, dW.as<uint16_t>(), M, N, K, ep, false, false, nullptr));
-    HIPCHK(hipEventRecord(b, nullptr));
-    HIPCHK(hipEventSynchronize(b));
-    HIPCHK(hipEventElapsedTime(&ms, a, b));
-    if (avg_us_f32) *avg_us_f32 = ms * 1000.f / reps;
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
-  }
-  Q3A_CATCH(e)
 }
 
 }  // extern "C"

@@ -1,0 +1,68 @@
+// What engine.cpp and selftest.cpp share and nobody outside the library sees: the error macros, the owner of a device allocation
+// and the try / catch frame of a C-ABI entry point.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/q3asr.h"
+#include "kernels.h"
+#include "model.h"
+
+#define HIPCHK(expr) q3a::hip_check((expr), __FILE__, __LINE__, #expr)
+#define KCHK(expr) q3a::kernel_check(expr)  // (a launch_* wrapper returns its refusal, or null)
+
+namespace q3a {
+
+inline void hip_check(hipError_t e, const char* file, int line, const char* expr) {
+  if (e != hipSuccess) fail(std::string("HIP error: ") + hipGetErrorString(e) + " at " + file + ":" + std::to_string(line) + " (" + expr + ")");
+}
+inline void kernel_check(const char* msg) { if (msg) fail(std::string("kernel launch: ") + msg); }
+
+constexpr int kAudioPad = 151676, kEos0 = 151643, kEos1 = 151645;  // src/tokenizer.rs:52-59
+
+// bytes of device memory all DevBufs of the process hold right now (q3a_debug_read "device_bytes")
+inline std::atomic<uint64_t> g_device_bytes{0};
+
+// One device allocation and its owner, move-only: freed when it goes out of scope (engine members, taps, locals of the selftests)
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  bool grew = false;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept { *this = std::move(o); }
+  DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); std::swap(grew, o.grew); return *this; }  // (o frees what this held)
+  ~DevBuf() { release(); }
+  void ensure(size_t bytes) {
+    if (bytes <= cap) return;
+    release();
+    size_t want = (bytes + 255) & ~size_t(255);
+    HIPCHK(hipMalloc(&p, want));
+    cap = want;
+    g_device_bytes += want;
+    grew = true;
+  }
+  void release() {
+    if (p) { (void)hipFree(p); g_device_bytes -= cap; }
+    p = nullptr;
+    cap = 0;
+  }
+  template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+// e->err (e null: an entry point without an engine) and the calling thread's q3a_last_error(NULL); engine.cpp
+void set_error(q3a_engine* e, const char* msg);
+
+}  // namespace q3a
+
+// frame of a C-ABI entry point: 0, or 1 with the message recorded
+#define Q3A_TRY(e) try {
+#define Q3A_CATCH(e)                                                                  \
+  }                                                                                   \
+  catch (const std::exception& ex) { q3a::set_error(e, ex.what()); return 1; }        \
+  catch (...) { q3a::set_error(e, "unknown error"); return 1; }                       \
+  return 0;

@@ -1,0 +1,221 @@
+// q3a_selftest_*: product kernels on their own (no model) -- host arrays in, the product launches, host arrays or error figures out.
+#include <cmath>
+#include <cstring>
+
+#include "engine_internal.h"
+
+using namespace q3a;
+
+namespace {
+
+// ---- staging: every selftest runs on the null stream with blocking copies ----
+void use_device(int device) {
+  if (int n_dev = 0; hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) fail("no HIP device available");
+  HIPCHK(hipSetDevice(device));
+}
+DevBuf room(size_t bytes) { DevBuf b; b.ensure(bytes); return b; }
+template <class T> DevBuf to_device(const T* src, size_t n) {
+  DevBuf b = room(n * sizeof(T));
+  HIPCHK(hipMemcpy(b.p, src, n * sizeof(T), hipMemcpyHostToDevice));
+  return b;
+}
+template <class T> DevBuf to_device(const std::vector<T>& v) { return to_device(v.data(), v.size()); }
+template <class T> void to_host(T* dst, const DevBuf& b, size_t n) { HIPCHK(hipMemcpy(dst, b.p, n * sizeof(T), hipMemcpyDeviceToHost)); }
+template <class T> std::vector<T> to_host(const DevBuf& b, size_t n) { std::vector<T> v(n); to_host(v.data(), b, n); return v; }
+void finish() { HIPCHK(hipDeviceSynchronize()); HIPCHK(hipGetLastError()); }
+
+// ---- test data ----
+struct Lcg {  // uniform in [-0.5, 0.5)
+  uint32_t st;
+  float operator()() { st = st * 1664525u + 1013904223u; return ((st >> 8) & 0xffff) / 65536.0f - 0.5f; }
+};
+uint16_t bf16_trunc(float f) { uint32_t u; memcpy(&u, &f, 4); return (uint16_t)(u >> 16); }  // truncation is fine for a test
+float bf16_value(uint16_t h) { uint32_t u = (uint32_t)h << 16; float f; memcpy(&f, &u, 4); return f; }
+
+// x [M][K] fp32 (bf16-representable when exact16) and w [N][K] bf16 from one generator, with room for a product Y and the reference R
+struct GemmCase {
+  std::vector<float> X, R;
+  std::vector<uint16_t> W;
+  const size_t MN;  DevBuf dX, dW, dY, dR;
+  GemmCase(Lcg& rnd, int M, int N, int K, bool exact16) : X((size_t)M * K), W((size_t)N * K), MN((size_t)M * N) {
+    for (auto& v : X) { v = rnd(); if (exact16) v = bf16_value(bf16_trunc(v)); }
+    for (auto& v : W) v = bf16_trunc(rnd());
+    dX = to_device(X); dW = to_device(W); dY = room(MN * 4); dR = room(MN * 4);
+  }
+  // after the launch under test wrote dY: the reference product, then max |Y - R| and max |R|
+  void check(int M, int N, int K, float& me, float& rm) {
+    launch_gemm_ref(dX.as<float>(), dW.as<uint16_t>(), dR.as<float>(), M, N, K, nullptr);
+    finish();
+    R = to_host<float>(dR, MN);
+    const std::vector<float> Y = to_host<float>(dY, MN);
+    for (size_t i = 0; i < MN; ++i) { me = std::max(me, std::fabs(Y[i] - R[i])); rm = std::max(rm, std::fabs(R[i])); }
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+int32_t q3a_selftest_beam_topk(int32_t device, const float* logits, int32_t S, int32_t V, int32_t W, int32_t* out_ids, float* out_lp) {
+  Q3A_TRY(nullptr)
+  use_device(device);
+  if (!logits || !out_ids || !out_lp || S < 1 || V < 1) fail("q3a_selftest_beam_topk: bad argument");
+  const size_t nc = beam_topk_chunks(V), Sz = S;
+  const DevBuf dLg = to_device(logits, Sz * V), dCv = room(Sz * nc * BEAM_MAX_W * 4), dCi = room(Sz * nc * BEAM_MAX_W * 4);
+  const DevBuf dPm = room(Sz * nc * 4), dPs = room(Sz * nc * 4), dOi = room(Sz * BEAM_MAX_W * 4), dOl = room(Sz * BEAM_MAX_W * 4);
+  BeamTopkArgs t{dLg.as<float>(), S, V, W, dCv.as<float>(), dCi.as<int>(), dPm.as<float>(), dPs.as<float>(), dOi.as<int>(), dOl.as<float>()};
+  KCHK(launch_beam_topk(t, nullptr));
+  finish();
+  to_host(out_ids, dOi, Sz * W); to_host(out_lp, dOl, Sz * W);
+  Q3A_CATCH(nullptr)
+}
+
+int32_t q3a_selftest_beam_advance(int32_t device, int32_t U, int32_t W, const int32_t* topk_ids, const float* topk_lp, const float* score_in,
+                                  const uint8_t* finished_in, int32_t* parent_out, int32_t* token_out, float* score_out, uint8_t* finished_out) {
+  Q3A_TRY(nullptr)
+  use_device(device);
+  if (!topk_ids || !topk_lp || !score_in || !finished_in || !parent_out || !token_out || !score_out || !finished_out || U < 1 || W < 1 || W > BEAM_MAX_W || U * W > 32)
+    fail("q3a_selftest_beam_advance: bad argument");
+  const size_t S = (size_t)U * W;
+  const DevBuf dTi = to_device(topk_ids, S * W), dTl = to_device(topk_lp, S * W), dSc = to_device(score_in, S), dFi = to_device(finished_in, S);
+  const DevBuf dPa = room(S * 4), dTo = room(S * 4), dSt = to_device(std::vector<int>(BEAM_ST_COUNT, 0));
+  BeamAdvanceArgs a{};
+  a.U = U; a.W = W; a.topk_ids = dTi.as<int>(); a.topk_lp = dTl.as<float>(); a.score = dSc.as<float>(); a.finished = dFi.as<uint8_t>();
+  a.parent = dPa.as<int>(); a.token = dTo.as<int>(); a.state = dSt.as<int>(); a.eos0 = kEos0; a.eos1 = kEos1;
+  KCHK(launch_beam_advance(a, nullptr));
+  finish();
+  to_host(parent_out, dPa, S); to_host(token_out, dTo, S); to_host(score_out, dSc, S); to_host(finished_out, dFi, S);
+  Q3A_CATCH(nullptr)
+}
+
+int32_t q3a_selftest_kv_reorder(int32_t device, void* cache, int32_t elem_bytes, int32_t layers, int32_t S, int32_t n_kv, int32_t max_ctx,
+                                const int32_t* lo, const int32_t* hi, const int32_t* parent) {
+  Q3A_TRY(nullptr)
+  use_device(device);
+  if (!cache || !lo || !hi || !parent || layers < 1 || S < 1 || S > 32 || n_kv < 1 || max_ctx < 1 || (elem_bytes != 2 && elem_bytes != 4))
+    fail("q3a_selftest_kv_reorder: bad argument");
+  for (int s = 0; s < S; ++s) {  // bounds before anything runs: a copy stays inside the cache and inside one utterance's rows
+    const int p = parent[s];
+    if (p < 0 || p >= S) fail("q3a_selftest_kv_reorder: parent out of range");
+    if (lo[s] < 0 || hi[s] >= max_ctx) fail("q3a_selftest_kv_reorder: rows outside the cache");
+    if (p != s && (lo[p] != lo[s] || hi[p] != hi[s])) fail("q3a_selftest_kv_reorder: a parent must share its child's row range (a slot of the same utterance)");
+  }
+  const size_t half = (size_t)layers * S * n_kv * max_ctx * 128 * elem_bytes;  // K, then V
+  const DevBuf dC = to_device((const uint8_t*)cache, 2 * half), dLo = to_device(lo, S), dHi = to_device(hi, S), dPar = to_device(parent, S);
+  KvReorderArgs r{};
+  r.kcache = dC.p; r.vcache = (uint8_t*)dC.p + half; r.elem_bytes = elem_bytes; r.layers = layers; r.S = S; r.n_kv = n_kv; r.max_ctx = max_ctx;
+  r.parent = dPar.as<int>(); r.lo = dLo.as<int>(); r.hi = dHi.as<int>();
+  KCHK(launch_kv_reorder(r, nullptr));
+  finish();
+  to_host((uint8_t*)cache, dC, 2 * half);
+  Q3A_CATCH(nullptr)
+}
+
+int32_t q3a_selftest_gemm(int32_t device, int32_t M, int32_t N, int32_t K, int32_t split, float* max_abs_err,
+                          float* ref_abs_max) {
+  Q3A_TRY(nullptr)
+  use_device(device);
+  Lcg rnd{12345u};
+  GemmCase c(rnd, M, N, K, false);
+  GemmEpilogue ep; ep.out = c.dY.as<float>(); ep.ldo = N;
+  KCHK(launch_gemm(c.dX.as<float>(), K, c.dW.as<uint16_t>(), M, N, K, ep, false, split != 0, nullptr));
+  float me = 0.f, rm = 0.f;
+  c.check(M, N, K, me, rm);
+  if (max_abs_err) *max_abs_err = me;  if (ref_abs_max) *ref_abs_max = rm;
+  Q3A_CATCH(nullptr)
+}
+
+int32_t q3a_selftest_gemm16(int32_t device, int32_t M, int32_t N, int32_t K, int32_t reps, float* max_abs_err,
+                            float* ref_abs_max, float* avg_us_bf16, float* avg_us_f32) {
+  Q3A_TRY(nullptr)
+  use_device(device);
+  Lcg rnd{777u};
+  GemmCase c(rnd, M, N, K, true);  // bf16-representable activations: the bf16 copy is exact
+  const size_t MN = c.MN;
+  const DevBuf &dX = c.dX, &dW = c.dW, dX16 = room(c.X.size() * 2);
+  KCHK(launch_to_bf16(dX.as<float>(), dX16.as<uint16_t>(), c.X.size(), nullptr));
+  GemmEpilogue ep; ep.out = c.dY.as<float>(); ep.ldo = N;
+  KCHK(launch_gemm16(dX16.as<uint16_t>(), K, dW.as<uint16_t>(), M, N, K, ep, false, nullptr));
+  float me = 0.f, rm = 0.f;
+  c.check(M, N, K, me, rm);
+  const std::vector<float>& R = c.R;
+  // ---- the epilogue variants, against the reference product R ----
+  {
+    const int P = 7;  // addend period
+    std::vector<float> bias(N), addend((size_t)P * N), resid(MN);
+    std::vector<int> rowmap(M);
+    for (auto& v : bias) v = rnd();
+    for (auto& v : addend) v = rnd();
+    for (auto& v : resid) v = rnd();
+    for (int m = 0; m < M; ++m) rowmap[m] = (m % 11 == 5) ? -1 : M - 1 - m;  // reversed rows, some dropped
+    const DevBuf dB = to_device(bias), dA = to_device(addend), dS = to_device(resid), dM = to_device(rowmap);
+    const DevBuf dY2 = to_device(std::vector<float>(MN, 0.f)), dY16 = room(MN * 2);
+    // (a) fp32 out: bias + periodic addend + row map + residual
+    GemmEpilogue e2; e2.out = dY2.as<float>(); e2.ldo = N; e2.bias = dB.as<float>(); e2.addend = dA.as<float>(); e2.addend_period = P;
+    e2.rowmap = dM.as<int>(); e2.resid = dS.as<float>();
+    KCHK(launch_gemm16(dX16.as<uint16_t>(), K, dW.as<uint16_t>(), M, N, K, e2, false, nullptr));
+    finish();
+    const std::vector<float> Y2 = to_host<float>(dY2, MN);
+    std::vector<char> hit(M, 0);
+    for (int m = 0; m < M; ++m) {
+      const int o = rowmap[m];
+      if (o < 0) continue;
+      hit[o] = 1;
+      for (int n = 0; n < N; ++n) {
+        const float want = R[(size_t)m * N + n] + bias[n] + addend[(size_t)(m % P) * N + n] + resid[(size_t)o * N + n];
+        me = std::max(me, std::fabs(Y2[(size_t)o * N + n] - want));
+      }
+    }
+    for (int o = 0; o < M; ++o)
+      if (!hit[o])
+        for (int n = 0; n < N; ++n)
+          if (Y2[(size_t)o * N + n] != 0.f) fail("selftest_gemm16: a row dropped by the row map was written");
+    // (b) bf16 out: bias only; one bf16 ulp
+    GemmEpilogue e3; e3.out16 = dY16.as<uint16_t>(); e3.ldo = N; e3.bias = dB.as<float>();
+    KCHK(launch_gemm16(dX16.as<uint16_t>(), K, dW.as<uint16_t>(), M, N, K, e3, false, nullptr));
+    finish();
+    std::vector<uint16_t> Y16 = to_host<uint16_t>(dY16, MN);
+    for (size_t i = 0; i < Y16.size(); ++i) {
+      const float want = R[i] + bias[i % N];
+      if (std::fabs(bf16_value(Y16[i]) - want) > std::fabs(want) / 128.f + 1e-4f * std::max(rm, 1.f)) fail("selftest_gemm16: bf16 output with bias is off by more than an ulp");
+    }
+    // (c) SwiGLU pairs ([16 gate | 16 up] row blocks of W), bf16 out
+    if (N % 32 == 0) {
+      GemmEpilogue e4; e4.out16 = dY16.as<uint16_t>(); e4.ldo = N / 2;
+      KCHK(launch_gemm16(dX16.as<uint16_t>(), K, dW.as<uint16_t>(), M, N, K, e4, true, nullptr));
+      finish();
+      to_host(Y16.data(), dY16, MN / 2);
+      for (int m = 0; m < M; ++m)
+        for (int c2 = 0; c2 < N / 2; ++c2) {
+          const float g = R[(size_t)m * N + (c2 / 16) * 32 + c2 % 16], u = R[(size_t)m * N + (c2 / 16) * 32 + 16 + c2 % 16];
+          const float want = g / (1.f + std::exp(-g)) * u;
+          if (std::fabs(bf16_value(Y16[(size_t)m * (N / 2) + c2]) - want) > std::fabs(want) / 64.f + 1e-3f * std::max(rm * rm, 1.f))
+            fail("selftest_gemm16: SwiGLU epilogue is off");
+        }
+    }
+  }
+  if (max_abs_err) *max_abs_err = me;  if (ref_abs_max) *ref_abs_max = rm;
+  if (reps > 0) {
+    hipEvent_t a, b;
+    HIPCHK(hipEventCreate(&a));
+    HIPCHK(hipEventCreate(&b));
+    auto avg_us = [&](auto&& launch) {  // `reps` back-to-back launches between two events
+      float ms = 0.f;
+      HIPCHK(hipEventRecord(a, nullptr));
+      for (int r = 0; r < reps; ++r) KCHK(launch());
+      HIPCHK(hipEventRecord(b, nullptr));
+      HIPCHK(hipEventSynchronize(b));
+      HIPCHK(hipEventElapsedTime(&ms, a, b));
+      return ms * 1000.f / reps;
+    };
+    const float us16 = avg_us([&] { return launch_gemm16(dX16.as<uint16_t>(), K, dW.as<uint16_t>(), M, N, K, ep, false, nullptr); });
+    const float us32 = avg_us([&] { return launch_gemm(dX.as<float>(), K, dW.as<uint16_t>(), M, N, K, ep, false, false, nullptr); });
+    if (avg_us_bf16) *avg_us_bf16 = us16;
+    if (avg_us_f32) *avg_us_f32 = us32;
+    (void)hipEventDestroy(a);
+    (void)hipEventDestroy(b);
+  }
+  Q3A_CATCH(nullptr)
+}
+
+}  // extern "C"

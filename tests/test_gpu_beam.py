@@ -343,6 +343,28 @@ def test_graph_replay_equals_eager(beam_planted):
     assert all(h.finished for h in hyps[0]) and all(not h.finished and len(h.ids) == 5 for hs in hyps[1:] for h in hs)
 
 
+def test_no_stale_beam_graph_across_shapes(tiny_dir):
+    """One graph engine searches shape A (1 clip x width 2, 6 rounds), then B (2 clips x width 4, 12 rounds, longer clips), then A
+    again; every search equals an eager engine's, bit for bit.  B regrows the beam tables (history, candidates) inside beam_begin,
+    after setup_prompts has already swept for reallocations, so a graph captured for A must not replay on the freed addresses
+    (the greedy twin: tests/test_gpu_logprobs.py::test_no_stale_graph_across_batch_shapes)."""
+    shapes = {"A": ([synthetic.synthetic_clip(410, 1.25)], 2, 6), "B": ([synthetic.synthetic_clip(420 + i, 2.0) for i in range(2)], 4, 12)}
+    eager = HipEngine(tiny_dir, 0, max_new_tokens=12, use_graph=False)
+    want = {name: eager.beam_search_batch(clips, W, max_new=k) for name, (clips, W, k) in shapes.items()}
+    eager.close()
+    eng = HipEngine(tiny_dir, 0, max_new_tokens=12, use_graph=True)
+    for name in ("A", "B", "A"):
+        clips, W, k = shapes[name]
+        got = eng.beam_search_batch(clips, W, max_new=k)
+        assert [len(hs) for hs in got] == [W] * len(clips), name
+        for hs, ws in zip(got, want[name]):
+            for h, w in zip(hs, ws):
+                assert h.ids == w.ids and len(h.ids) == len(w.ids) and h.finished == w.finished, name
+                assert np.float32(h.score).view(np.uint32) == np.float32(w.score).view(np.uint32), name
+                assert np.array_equal(np.asarray(h.token_logprobs, np.float32).view(np.uint32), np.asarray(w.token_logprobs, np.float32).view(np.uint32)), name
+    eng.close()
+
+
 # ---- 9. refusals and state ---------------------------------------------------------------------------------------------
 def test_refusals_and_state(lib, tiny_dir):
     from align_ref import tiny_aligner_dir

@@ -455,29 +455,39 @@ def _cpp_function_body(src: str, signature_start: str) -> str:
 
 def test_step_buffers_cover_the_captured_step():
     """A cached decode-step graph holds raw device addresses.  Two guards keep a stale one from replaying -- the reallocation
-    sweep of setup_prompts and the address hash in make_graph_sig -- and both walk q3a_engine::step_bufs().  This test scans
-    the source of every function that enqueues a launch of the captured step for DevBuf members and fails when one is not
-    in that list ("one forgotten DevBuf re-opens the stale-graph bug")."""
+    sweep of setup_prompts and the address hash in make_graph_sig -- and both walk DecodeStep::each_buf.  The captured step is one
+    struct, DecodeStep: it declares every DevBuf a launch of the step touches, contains every function that enqueues such a launch,
+    and sees the rest of the engine through StepView only, so the compiler refuses a step function that names any other buffer
+    ("one forgotten DevBuf re-opens the stale-graph bug").  This test holds what the compiler does not: each_buf is
+    exactly the DevBufs the struct declares, neither struct has a way back to the engine, and both guards use the walk."""
     src = open(os.path.join(ROOT, "qwen3_asr_rs_amd", "csrc", "engine.cpp")).read()
-    members = set()
-    for decl in re.findall(r"^  DevBuf ([^;]+);", src, flags=re.M):
-        members.update(n.strip() for n in decl.split(","))
-    assert {"kcache", "x_dec", "logits", "nn_ss"} <= members
-    listed = set(re.findall(r"&(\w+)", _cpp_function_body(src, "std::vector<DevBuf*> step_bufs()")))
-    assert listed <= members and len(listed) >= 20
-    step_functions = ["void decode_layer(", "void run_head(", "void enqueue_decode_step(", "void* kc_layer(", "void* vc_layer(",
-                      "NextNormOut first_layer_norm_out(", "uint16_t* nn_x_g(", "float* nn_ss_g(", "float* s_ctx_g(", "float* s_act_g(",
-                      "void batched_proj(", "LayerProjs layer_projs("]
-    used = set()
-    for f in step_functions:
-        body = _cpp_function_body(src, f)
-        used.update(m for m in members if re.search(r"\b" + re.escape(m) + r"\b", body))
-    debug_only = {n for n in used if n.startswith("dbg_")}
-    missing = used - listed - debug_only
-    assert not missing, f"DevBuf members used by the captured decode step but absent from step_bufs(): {sorted(missing)}"
-    # both guards really use the list
-    assert "step_bufs()" in _cpp_function_body(src, "std::string make_graph_sig() const")
-    assert "step_bufs()" in _cpp_function_body(src, "void setup_prompts(")
+    view = _cpp_function_body(src, "struct StepView ")
+    unit = _cpp_function_body(src, "struct DecodeStep : StepView ")
+    engine = _cpp_function_body(src, "struct q3a_engine ")
+
+    def devbufs(text):
+        names = []
+        for decl in re.findall(r"^  DevBuf ([^;]+);", text, flags=re.M):
+            names += [n.strip() for n in decl.split(",")]
+        return names
+
+    declared = devbufs(unit)
+    assert {"kcache", "x_dec", "logits", "nn_ss"} <= set(declared) and len(declared) >= 20
+    # the guarded set IS the declarations: every one listed and the other way round, once each, in declaration order
+    listed = re.findall(r"&s\.(\w+)", _cpp_function_body(unit, "static void each_buf("))
+    assert listed == declared and len(set(listed)) == len(listed), (sorted(set(declared) - set(listed)), sorted(set(listed) - set(declared)))
+    # the engine keeps no buffer of the same name, and holds the unit by value
+    assert not set(devbufs(engine)) & set(declared)
+    assert re.search(r"^  DecodeStep step\{StepView\{", engine, flags=re.M)
+    # no way from the unit to any other buffer: the view hands over no DevBuf, and neither struct can name the engine
+    assert "DevBuf" not in view
+    for text in (view, unit):
+        assert not re.search(r"\bq3a_engine\b", text) and "e->" not in text
+    # (the one debug-only buffer outside the guard: the lm_head_bound tap, see the comment next to it)
+    assert re.findall(r"taps\.reserve\(([^,]+),", unit) == ['"lm_head_bound"']
+    # both guards really use the walk
+    assert "DecodeStep::each_buf(step," in _cpp_function_body(src, "std::string make_graph_sig() const")
+    assert "DecodeStep::each_buf(step," in _cpp_function_body(src, "void setup_prompts(")
 
 
 def test_mfma_table_shapes_and_launch_matching():
