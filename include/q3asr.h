@@ -411,6 +411,46 @@ int32_t q3a_selftest_beam_advance(int32_t device, int32_t U, int32_t W, const in
 int32_t q3a_selftest_kv_reorder(int32_t device, void* cache, int32_t elem_bytes, int32_t layers, int32_t S, int32_t n_kv, int32_t max_ctx,
                                 const int32_t* lo, const int32_t* hi, const int32_t* parent);
 
+/* ---- constrained decoding: a per-token logit bias inside every lm_head form ------------------------------------------------------
+ * An engine holds one dense fp32 vector b[vocab]; every entry is finite or -inf.  While a bias is set, every head of the GENERATION
+ * paths works on l' = l + b instead of the fp32 logits l.  The sum is one fp32 operation that a kernel may fuse with the multiply
+ * that forms l (acc * rstd + b), so it is specified to a tolerance, not bitwise: |l' - (l + b)| <= 2^-22 (|l| + |b|) (one rounding of
+ * l, one of the sum); exact for b = 0, and l' = -inf exactly where b = -inf.  Everything downstream is defined on l' with the rules
+ * it has without a bias:
+ *   the greedy id is argmax l' (larger value, then smaller id);
+ *   token log-probabilities (q3a_fetch_logprobs) are l'[id] - logsumexp(l'): the renormalised distribution, suppressed tokens
+ *     contribute 0 to the sum, never NaN;
+ *   beam search selects its top-W and computes lp on l';
+ *   logits_out of q3a_prefill / q3a_decode_step / q3a_beam_step and the "logits" tap hold l'; the "lm_head_bound" tap holds the
+ *     approximate BIASED logit and its bound ((-inf, 0) for a suppressed row).
+ * The one-sequence pruned argmax ("lm_head_prune") keeps running under a bias: its int8 pre-pass adds b and widens the bound by the
+ * two sums' roundings, rows with b = -inf are never candidates, and a 16-row block with every row suppressed is never rescored (an
+ * allow-list makes the second pass cheaper).
+ * Applies to: q3a_prefill (next_ids, last_logits_out), q3a_decode_step, q3a_run_resident, q3a_transcribe_batch[_ptrs],
+ * q3a_fetch_logprobs, q3a_beam_*.  Group runs: set it on each q3a_group_engine handle; there is no group-level call.
+ * Does NOT apply to q3a_score* and q3a_align*: they score and classify the unconstrained model, and their results are bit-identical
+ * with and without a bias.
+ * State: the bias persists across calls until cleared.  q3a_set_logit_bias drops the decode state as q3a_score does --
+ * q3a_decode_step, q3a_set_next_tokens and q3a_fetch_ids fail until the next prefill -- so a bias never changes under a live sequence
+ * or a captured step.  The vector is uploaded inside the call; no decode loop returns to the host for it.
+ * Refused (q3a_last_error): an id < 0 or >= vocab; a duplicate id; a NaN or +inf entry; a default_bias other than 0 / -inf; a vector
+ * with no finite entry; an aligner engine; q3a_beam_begin / q3a_beam_search_batch_ptrs with width larger than the number of finite
+ * entries.
+ * Readable without debug taps: q3a_debug_read(e, "logit_bias", ..) (fp32 [vocab] as the device holds it, zeros when off) and
+ * "logit_bias_stats" (int32 [2]: active 0 / 1, finite entries).
+ * Out of scope: per-utterance biases inside one batch (a [S][vocab] operand: 19 MB per step at 32 sequences); history-dependent
+ * processors (no-repeat n-gram, repetition penalty); multi-token phrase constraints; sampling; a bias inside q3a_score*. */
+
+/* b = default_bias everywhere (0 or -INFINITY only), then b[ids[i]] = bias[i].  n = 0 with default_bias = 0 clears the bias: the
+ * engine is back on the launches, ids and log-probabilities of an engine that never had one, bit for bit.  An allow-list is
+ * default_bias = -INFINITY with the allowed ids at 0 (the caller lists 151643 / 151645 if generation should be able to stop). */
+int32_t q3a_set_logit_bias(q3a_engine* e, const int32_t* ids, const float* bias, int32_t n, float default_bias);
+/* Host helper, no engine: parse "id bias" lines ('#' comments, blank lines, "-inf" accepted, "lo-hi bias" ranges with both ends
+ * included) and a comma list "id,lo-hi,..." of ids to suppress (bias -inf) into (ids, bias); either may be null or empty.
+ * *n = entries needed, at most cap written.  Refused (q3a_last_error(NULL)): a malformed line or item, a NaN / +inf bias, an id
+ * named twice. */
+int32_t q3a_parse_logit_bias(const char* text, const char* suppress_list, int32_t* ids, float* bias, int32_t cap, int32_t* n);
+
 /* A/B knobs for kernel experiments (process-wide atomics, read from the environment once; not part of the reference
  * interface).  The knobs that shape the decode step are latched per batch at the next prefill and are part of the captured
  * graph's signature, so changing one on a live engine re-captures instead of replaying a stale graph.  Keys:

@@ -23,7 +23,7 @@ SYMBOLS = [
     "q3a_aligner_info", "q3a_build_align_prompt", "q3a_align", "q3a_align_batch_ptrs", "q3a_split_words_for_alignment",
     "q3a_align_text_ids", "q3a_fix_timestamps", "q3a_score", "q3a_score_batch_ptrs",
     "q3a_beam_search_batch_ptrs", "q3a_beam_begin", "q3a_beam_step", "q3a_beam_fetch", "q3a_selftest_beam_topk", "q3a_selftest_beam_advance",
-    "q3a_selftest_kv_reorder",
+    "q3a_selftest_kv_reorder", "q3a_set_logit_bias", "q3a_parse_logit_bias",
 ]
 
 
@@ -149,6 +149,8 @@ def load() -> C.CDLL:
         "q3a_selftest_beam_topk": (i32, [i32, f32p, i32, i32, i32, i32p, f32p]),
         "q3a_selftest_beam_advance": (i32, [i32, i32, i32, i32p, f32p, f32p, u8p, i32p, i32p, f32p, u8p]),
         "q3a_selftest_kv_reorder": (i32, [i32, P, i32, i32, i32, i32, i32, i32p, i32p, i32p]),
+        "q3a_set_logit_bias": (i32, [P, i32p, f32p, i32, C.c_float]),
+        "q3a_parse_logit_bias": (i32, [C.c_char_p, C.c_char_p, i32p, f32p, i32, i32p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -12,6 +12,9 @@
 // nothing changes.
 // Q3A_BEAM=<W> runs a beam search of width W (q3a_beam_search_batch_ptrs; 1..8) over the same audio and prompt after "Text:" (and
 // "Confidence:") and adds one stdout line per hypothesis, best first: "Hyp <k>: <score> <text>"; without it nothing changes.
+// Q3A_SUPPRESS_TOKENS=<id,lo-hi,...> and Q3A_LOGIT_BIAS=<path of a file of "id bias" / "lo-hi bias" lines> constrain the decoding
+// (q3a_parse_logit_bias + q3a_set_logit_bias, default bias 0): the transcription and a Q3A_BEAM search run under the bias, a
+// Q3A_SCORE_TEXT score does not; without them nothing changes.
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -33,6 +36,29 @@ static void logf(int level, const char* fmt, const std::string& a = "") {
 }
 static bool exists(const char* p) { struct stat st; return stat(p, &st) == 0; }
 static int die(const std::string& msg) { fprintf(stderr, "Error: %s\n", msg.c_str()); return 1; }
+
+// Q3A_SUPPRESS_TOKENS / Q3A_LOGIT_BIAS: the engine's logit bias, set before anything is generated
+static int set_logit_bias_from_env(q3a_engine* eng) {
+  const char* list = getenv("Q3A_SUPPRESS_TOKENS");
+  const char* path = getenv("Q3A_LOGIT_BIAS");
+  if ((!list || !*list) && (!path || !*path)) return 0;
+  std::string text;
+  if (path && *path) {
+    FILE* f = fopen(path, "rb");
+    if (!f) return die(std::string("Logit bias failed: cannot read ") + path);
+    char buf[4096];
+    for (size_t k; (k = fread(buf, 1, sizeof(buf), f)) > 0;) text.append(buf, k);
+    fclose(f);
+  }
+  int32_t n = 0;
+  if (q3a_parse_logit_bias(text.c_str(), list, nullptr, nullptr, 0, &n) != 0) return die(std::string("Logit bias failed: ") + q3a_last_error(nullptr));
+  std::vector<int32_t> ids((size_t)n + 1);
+  std::vector<float> bias((size_t)n + 1);
+  if (q3a_parse_logit_bias(text.c_str(), list, ids.data(), bias.data(), n, &n) != 0) return die(std::string("Logit bias failed: ") + q3a_last_error(nullptr));
+  if (q3a_set_logit_bias(eng, ids.data(), bias.data(), n, 0.f) != 0) return die(std::string("Logit bias failed: ") + q3a_last_error(eng));
+  logf(1, "Logit bias: %s entries", std::to_string(n));
+  return 0;
+}
 
 // Q3A_ALIGNER: word times of `text` in the audio (the forced aligner's word split, prompt, head and monotonicity fix-up)
 static int print_word_times(const char* aligner_dir, const float* pcm, int64_t n, const char* text, const char* language) {
@@ -185,6 +211,7 @@ int main(int argc, char** argv) {
   if (q3a_engine_create(model_path, 0, &opts, &eng) != 0) return die(std::string("Failed to load model: ") + q3a_last_error(nullptr));
   if (q3a_weights_rounded(eng))
     logf(0, "warning: the checkpoint stores F16/F32 matrices; the HIP backend keeps matrices as bf16 (rounded to nearest-even)");
+  if (set_logit_bias_from_env(eng) != 0) return 1;
   logf(1, "Loading tokenizer...");
   q3a_tokenizer* tok = nullptr;
   const std::string tj = std::string(model_path) + "/tokenizer.json";

@@ -127,6 +127,7 @@ struct StepView {
   const int &B, &max_ctx, &max_new, &gsize, &live_nsplit_, &attn_nsplit, &min_P_, &part_stride, &beam_w_;
   const size_t& kv_layer_elems; const bool& head_logits_;
   const int &k_parallel_groups, &k_skinny_q, &k_dattn_batched_min_wgs, &k_skinny_glu_hp3, &k_lm_head_prune;  // knobs as latched per batch
+  const bool& logit_bias_on_;  // q3a_set_logit_bias: a bias is set (changes only while the engine holds no decode state)
 
   bool precise() const { return opts.precise != 0; }
   bool token_lp() const { return opts.token_logprobs != 0; }
@@ -153,6 +154,7 @@ struct DecodeStep : StepView {
   DevBuf n_done, forced_tok;  // n_done: device counter of sequences that have produced their EOS (argmax_finalize)
   DevBuf beam_cand_val, beam_cand_idx, beam_part_max, beam_part_sum, beam_topk_ids, beam_topk_lp, beam_score, beam_finished, beam_parent, beam_token;
   DevBuf beam_feed, beam_hist_parent, beam_hist_token, beam_hist_lp, beam_state, beam_lo;
+  DevBuf logit_bias;  // [vocab] fp32, every entry finite or -inf (q3a_set_logit_bias; zeros while off): every head form adds it to its logits
   // f(buffer) for every DevBuf declared above, in declaration order (s: a DecodeStep, const or not).  The declarations of this
   // struct ARE the guarded set: tests/test_host.py::test_step_buffers_cover_the_captured_step compares this list with them.
   template <class Self, class F> static void each_buf(Self& s, F&& f) {
@@ -160,7 +162,8 @@ struct DecodeStep : StepView {
                     &s.part_val, &s.part_idx, &s.part_sum, &s.out_lp, &s.blk_lo, &s.blk_hi, &s.prune_stats, &s.attn_pm, &s.attn_pl, &s.attn_po, &s.nn_x, &s.nn_ss,
                     &s.rope_cur, &s.rope_cos, &s.rope_sin, &s.n_done, &s.forced_tok,
                     &s.beam_cand_val, &s.beam_cand_idx, &s.beam_part_max, &s.beam_part_sum, &s.beam_topk_ids, &s.beam_topk_lp, &s.beam_score, &s.beam_finished,
-                    &s.beam_parent, &s.beam_token, &s.beam_feed, &s.beam_hist_parent, &s.beam_hist_token, &s.beam_hist_lp, &s.beam_state, &s.beam_lo})
+                    &s.beam_parent, &s.beam_token, &s.beam_feed, &s.beam_hist_parent, &s.beam_hist_token, &s.beam_hist_lp, &s.beam_state, &s.beam_lo,
+                    &s.logit_bias})
       f(*b);
   }
 
@@ -184,12 +187,19 @@ struct DecodeStep : StepView {
     LmHeadPruneArgs pa{};
     pa.g = g; pa.Wq = lm_q; pa.qcols = lm_q_cols; pa.qs = lm_qs;
     pa.blk_lo = blk_lo.as<float>(); pa.blk_hi = blk_hi.as<float>(); pa.stats = prune_stats.as<int>();
+    pa.logit_bias = g.bias != nullptr;  // (the one bias run_head puts there)
     return pa;
   }
 
-  // final norm + lm_head on x_dec -> logits (+ block argmax partials), then argmax/finalize
+  // the logit bias for whichever head form runs; null: none set, every launch is the one of an engine that never had one
+  const float* head_bias() const { return logit_bias_on_ ? logit_bias.as<float>() : nullptr; }
+
+  // final norm + lm_head on x_dec -> logits (+ block argmax partials), then argmax/finalize.  With a logit bias every form below
+  // works on l' = l + b: the GEMV heads and both passes of the pruned argmax through GemvArgs::bias, the gemm16 forms through
+  // GemmEpilogue::bias (in front of the argmax epilogue and of the stored logits), the precise batched form through batched_proj.
   void run_head(int advance) {
     const int S = B, H = d.hidden, V = d.vocab;
+    const float* const hb = head_bias();
     tap("head_in", x_dec.p, (size_t)S * H * 4);  // (debug taps) last-layer residual rows the final norm + lm_head read
     const double wbytes = 2.0 * V * H;
     int n_part = 0;
@@ -201,7 +211,7 @@ struct DecodeStep : StepView {
       g.fast_math = fast_math();
       g.x = x_dec.as<float>(); g.ldx = H; g.rms_w = wf(L.final_norm); g.eps = d.rms_eps;
       g.W = wh(L.lm_head); g.N = V; g.K = H; g.mode = 3; g.out = logits.as<float>(); g.ldo = V;
-      g.part = part;
+      g.part = part; g.bias = hb;
       // (with the log-sum channel lm_head_prune_check refuses: the pruned argmax never computes most logits, the full GEMV runs)
       LmHeadPruneArgs pa{};
       const bool prunable = S == 1 && !precise() && lm_q_cols > 0 && (pa = prune_args(g), !lm_head_prune_check(pa));
@@ -227,7 +237,7 @@ struct DecodeStep : StepView {
       // default mode: bf16 normed rows, then the LDS-DMA GEMM at M = S (32-row tiles) -- the vocabulary matrix is
       // streamed once through double-buffered LDS; the skinny kernel re-reads x per 16 vocabulary rows (3x slower here)
       timed(Q3A_KC_NORM, 0, [&] { KCHK(launch_rmsnorm(x_dec.as<float>(), wf(L.final_norm), s_ln.as<float>(), S, H, d.rms_eps, stream, s_ln.as<uint16_t>())); });
-      GemmEpilogue ep; ep.out = logits.as<float>(); ep.ldo = V;
+      GemmEpilogue ep; ep.out = logits.as<float>(); ep.ldo = V; ep.bias = hb;
       if (S <= 32 && V % 4 == 0 && H % 64 == 0 && part_stride >= (V + 63) / 64) {
         // the argmax partials are the GEMM's epilogue (one per 64-column tile and row), and inside q3a_transcribe_batch /
         // q3a_run_resident nobody reads the logits: they are not stored (19 MB per step at 32 sequences)
@@ -242,7 +252,7 @@ struct DecodeStep : StepView {
       }
     } else {
       timed(Q3A_KC_NORM, 0, [&] { KCHK(launch_rmsnorm(x_dec.as<float>(), wf(L.final_norm), s_ln.as<float>(), S, H, d.rms_eps, stream)); });
-      timed(Q3A_KC_GEMM, wbytes, [&] { batched_proj(s_ln.as<float>(), H, wh(L.lm_head), V, H, nullptr, 0, logits.as<float>(), V, nullptr); });
+      timed(Q3A_KC_GEMM, wbytes, [&] { batched_proj(s_ln.as<float>(), H, wh(L.lm_head), V, H, hb, 0, logits.as<float>(), V, nullptr); });
       n_part = 128;
       timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_partials(logits.as<float>(), V, S, part, n_part, stream)); });
     }
@@ -571,11 +581,13 @@ struct q3a_engine {
   bool fixed_mode_ = false;
   bool head_logits_ = true;  // store the logits of a batched decode step (step API, debug taps); off inside run_resident
   int beam_w_ = 0;           // > 0: beam mode, slots per utterance (part of the graph signature)
+  bool logit_bias_on_ = false;  // q3a_set_logit_bias: step.logit_bias is applied by every head of the generation paths (graph signature)
+  int logit_bias_finite_ = 0;   // its finite entries (the vocabulary while off): what a beam width is checked against
 
   // ---- the captured decode step: its buffers and launches, and all it sees of the members above ----
   DecodeStep step{StepView{d, L, opts, arena, arena_flags, stream, chain_streams, join_ev, fork_ev, n_cu, host_prog_dev, prof, taps, lm_q, lm_qs, lm_q_cols,
                            B, max_ctx, max_new, gsize, live_nsplit_, attn_nsplit, min_P_, part_stride, beam_w_, kv_layer_elems, head_logits_,
-                           k_parallel_groups, k_skinny_q, k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune}};
+                           k_parallel_groups, k_skinny_q, k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, logit_bias_on_}};
 
   // (the mode rules are stated once, in StepView)
   bool precise() const { return step.precise(); }
@@ -641,6 +653,11 @@ struct q3a_engine {
     step.n_done.ensure(64);
     step.prune_stats.ensure(8);
     HIPCHK(hipMemsetAsync(step.prune_stats.p, 0, 8, stream));
+    if (!d.aligner()) {  // the logit bias vector: allocated once, zeros while no bias is set
+      step.logit_bias.ensure((size_t)d.vocab * 4);
+      HIPCHK(hipMemsetAsync(step.logit_bias.p, 0, (size_t)d.vocab * 4, stream));
+      logit_bias_finite_ = d.vocab;
+    }
   }
 
   void init_tables() {
@@ -1393,8 +1410,8 @@ struct q3a_engine {
     });
     char buf[256];
     // (one field per latched knob, as latched: packing several into one integer let distinct settings collide -- ADVICE r5)
-    snprintf(buf, sizeof(buf), "%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.b%d/%d/%d/%d/%p/%016llx", B, gsize, k_parallel_groups, k_skinny_q,
-             k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, (int)(min_P_ < 256), (int)head_logits_, (int)token_lp(), beam_w_, live_nsplit_,
+    snprintf(buf, sizeof(buf), "%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.b%d.lb%d/%d/%d/%d/%p/%016llx", B, gsize, k_parallel_groups, k_skinny_q,
+             k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, (int)(min_P_ < 256), (int)head_logits_, (int)token_lp(), beam_w_, (int)logit_bias_on_, live_nsplit_,
              max_ctx, max_new, (const void*)arena, (unsigned long long)h);
     return buf;
   }
@@ -1589,10 +1606,46 @@ struct q3a_engine {
       if (P[s] != P[s / W * W]) fail(std::string(what) + ": the prompts of utterance " + std::to_string(s / W) + " differ in length (its " + std::to_string(W) + " slots must hold the same prompt)");
     if (d.vocab < W) fail(std::string(what) + ": vocabulary smaller than the width");
   }
+  // Logit bias (q3asr.h q3a_set_logit_bias).  The dense vector is composed on the host and copied on the engine's stream; the call
+  // waits for the copy (the host vector is the call's own), nothing in a decode loop ever does.  The engine holds no decode state
+  // afterwards, so the vector never changes under a live sequence, and "on / off" is part of the graph signature.
+  void set_logit_bias(const int32_t* ids, const float* bias, int n, float default_bias) {
+    const char* what = "q3a_set_logit_bias";
+    require_asr(what);
+    const int V = d.vocab;
+    if (n < 0 || (n > 0 && (!ids || !bias))) fail(std::string(what) + ": bad argument");
+    if (!(default_bias == 0.f || default_bias == -INFINITY)) fail(std::string(what) + ": default_bias must be 0 or -inf");
+    std::vector<float> b((size_t)V, default_bias);
+    std::vector<uint8_t> seen((size_t)V, 0);
+    for (int i = 0; i < n; ++i) {
+      const int id = ids[i];
+      if (id < 0 || id >= V) fail(std::string(what) + ": id " + std::to_string(id) + " is outside the vocabulary (" + std::to_string(V) + ")");
+      if (seen[id]) fail(std::string(what) + ": duplicate id " + std::to_string(id));
+      seen[id] = 1;
+      const float v = bias[i];
+      if (std::isnan(v) || v == INFINITY) fail(std::string(what) + ": the bias of id " + std::to_string(id) + " is NaN or +inf (finite or -inf only)");
+      b[id] = v;
+    }
+    int finite = 0;
+    for (int r = 0; r < V; ++r) finite += b[r] != -INFINITY;
+    if (finite == 0) fail(std::string(what) + ": the bias has no finite entry (every token would be suppressed)");
+    const bool on = !(n == 0 && default_bias == 0.f);
+    have_prefill = false; beam_w_ = 0;  // no decode state until the next prefill, as after q3a_score
+    HIPCHK(hipMemcpyAsync(step.logit_bias.p, b.data(), (size_t)V * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    logit_bias_on_ = on;
+    logit_bias_finite_ = finite;
+  }
+  void beam_bias_check(const char* what, int W) const {
+    if (logit_bias_on_ && W > logit_bias_finite_)
+      fail(std::string(what) + ": width " + std::to_string(W) + " exceeds the " + std::to_string(logit_bias_finite_) + " tokens the logit bias leaves finite");
+  }
+
   // state for a search over the prefilled batch, then round 0 on the prefill's logits (enqueued; nothing waited for)
   void beam_begin(const char* what, int W) {
     if (!have_prefill) fail(std::string(what) + ": no prefill state (call q3a_prefill first)");
     beam_check(what, W);
+    beam_bias_check(what, W);
     if (!head_logits_ || pos_hi_ != *std::max_element(P.begin(), P.end()))
       fail(std::string(what) + ": needs the logits of q3a_prefill (call it directly after the prefill)");
     const int S = B, nc = beam_topk_chunks(d.vocab);
@@ -1979,6 +2032,7 @@ int32_t q3a_beam_search_batch_ptrs(q3a_engine* e, const float* const* pcm16k, co
   if ((int64_t)U * width > 32) fail("q3a_beam_search_batch: utterances x width = " + std::to_string((int64_t)U * width) + " exceeds 32 sequences");
   const int cap = e->opts.max_new_tokens, want = max_new <= 0 ? cap : std::min(max_new, cap);
   if (stride < want) fail("q3a_beam_search_batch: stride " + std::to_string(stride) + " is below max_new " + std::to_string(want));
+  e->beam_bias_check("q3a_beam_search_batch", width);
   e->fixed_mode_ = false;
   e->head_logits_ = true;  // every round selects on the stored logits
   // the W slots of an utterance are W ordinary sequences of the batch
@@ -1995,6 +2049,14 @@ int32_t q3a_beam_search_batch_ptrs(q3a_engine* e, const float* const* pcm16k, co
   e->beam_fetch(out_ids, stride, out_lens, out_scores, out_finished, out_lp);
   // as after q3a_score: no decode state until the next prefill
   e->beam_w_ = 0; e->have_prefill = false;
+  Q3A_CATCH(e)
+}
+
+int32_t q3a_set_logit_bias(q3a_engine* e, const int32_t* ids, const float* bias, int32_t n, float default_bias) {
+  if (!e) return 1;
+  Q3A_TRY(e)
+  HIPCHK(hipSetDevice(e->device));
+  e->set_logit_bias(ids, bias, n, default_bias);
   Q3A_CATCH(e)
 }
 
@@ -2276,6 +2338,18 @@ int32_t q3a_debug_read(q3a_engine* e, const char* name, void* dst, uint64_t byte
   };
   for (const auto& sc : scalars)
     if (strcmp(name, sc.name) == 0) { give(sc.src, sc.n, sc.on_device); return 0; }
+  // the logit bias as the device holds it (zeros while off) and {active, finite entries}
+  if (strcmp(name, "logit_bias") == 0) {
+    e->require_asr("q3a_debug_read: logit_bias");
+    give(e->step.logit_bias.p, (size_t)e->d.vocab * 4, true);
+    return 0;
+  }
+  if (strcmp(name, "logit_bias_stats") == 0) {
+    e->require_asr("q3a_debug_read: logit_bias");
+    const int32_t st[2] = {e->logit_bias_on_ ? 1 : 0, e->logit_bias_finite_};
+    give(st, 8, false);
+    return 0;
+  }
   // the last round of the last beam search (tables of beam_dbg_S_ sequences x beam_dbg_W_)
   const size_t bS = (size_t)e->beam_dbg_S_, bW = (size_t)e->beam_dbg_W_;
   const struct { const char* name; const DevBuf* buf; size_t n; } beams[] = {

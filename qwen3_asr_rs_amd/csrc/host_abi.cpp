@@ -1,6 +1,9 @@
 // C ABI of the host-only pipeline-shell helpers (include/q3asr.h, "pipeline shell" section).
+#include <cctype>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -47,7 +50,88 @@ static int32_t put_str(const std::string& s, char* out, int32_t cap) {
   return (int32_t)n;
 }
 
+// ---- logit bias lists (q3a_parse_logit_bias) ----
+namespace {
+constexpr long kBiasRangeMax = 1L << 24;  // ids one "lo-hi" item may name (far beyond any vocabulary: a typo, not a list)
+
+std::string trimmed(const std::string& s) {
+  size_t a = 0, b = s.size();
+  while (a < b && isspace((unsigned char)s[a])) ++a;
+  while (b > a && isspace((unsigned char)s[b - 1])) --b;
+  return s.substr(a, b - a);
+}
+// "id" or "lo-hi" (decimal, lo <= hi, both ends included)
+void parse_id_range(const std::string& item, const std::string& where, long& lo, long& hi) {
+  auto number = [&](const std::string& t) {
+    if (t.empty() || t.size() > 10 || t.find_first_not_of("0123456789") != std::string::npos) fail(where + ": '" + item + "' is not an id or a lo-hi range");
+    return strtol(t.c_str(), nullptr, 10);
+  };
+  const size_t dash = item.find('-');
+  if (dash == std::string::npos) { lo = hi = number(item); }
+  else { lo = number(trimmed(item.substr(0, dash))); hi = number(trimmed(item.substr(dash + 1))); }
+  if (lo > hi) fail(where + ": range '" + item + "' runs backwards");
+  if (hi > 0x7fffffffL || hi - lo >= kBiasRangeMax) fail(where + ": range '" + item + "' is too large");
+}
+float parse_bias_value(const std::string& t, const std::string& where) {
+  std::string l;
+  for (char c : t) l += (char)tolower((unsigned char)c);
+  if (l == "-inf" || l == "-infinity") return -INFINITY;
+  char* end = nullptr;
+  const float v = strtof(t.c_str(), &end);  // (an overflow comes back as +-inf and is refused; an underflow is a tiny bias or 0)
+  if (t.empty() || *end || std::isnan(v) || std::isinf(v)) fail(where + ": '" + t + "' is not a finite bias or -inf");
+  return v;
+}
+}  // namespace
+
 extern "C" {
+
+int32_t q3a_parse_logit_bias(const char* text, const char* suppress_list, int32_t* ids, float* bias, int32_t cap, int32_t* n) {
+  HOST_TRY
+  if (!n || cap < 0 || (cap > 0 && (!ids || !bias))) fail("q3a_parse_logit_bias: bad argument");
+  std::set<int32_t> seen;
+  int64_t count = 0;
+  auto add = [&](long lo, long hi, float v, const std::string& where) {
+    for (long id = lo; id <= hi; ++id) {
+      if (!seen.insert((int32_t)id).second) fail(where + ": duplicate id " + std::to_string(id));
+      if (count < cap) { ids[count] = (int32_t)id; bias[count] = v; }
+      ++count;
+    }
+  };
+  const std::string t = text ? text : "";
+  int line_no = 0;
+  for (size_t pos = 0; pos <= t.size();) {
+    size_t nl = t.find('\n', pos);
+    if (nl == std::string::npos) nl = t.size();
+    std::string line = t.substr(pos, nl - pos);
+    pos = nl + 1;
+    ++line_no;
+    const size_t hash = line.find('#');
+    if (hash != std::string::npos) line.resize(hash);
+    line = trimmed(line);
+    if (line.empty()) continue;
+    const std::string where = "q3a_parse_logit_bias: line " + std::to_string(line_no);
+    const size_t sp = line.find_last_of(" \t");  // "<id or lo-hi> <bias>": the bias is the last field
+    if (sp == std::string::npos) fail(where + ": expected '<id> <bias>' or '<lo>-<hi> <bias>'");
+    long lo = 0, hi = 0;
+    parse_id_range(trimmed(line.substr(0, sp)), where, lo, hi);
+    add(lo, hi, parse_bias_value(line.substr(sp + 1), where), where);
+  }
+  const std::string sl = suppress_list ? suppress_list : "";
+  for (size_t pos = 0; !trimmed(sl).empty() && pos <= sl.size();) {
+    size_t c = sl.find(',', pos);
+    if (c == std::string::npos) c = sl.size();
+    const std::string item = trimmed(sl.substr(pos, c - pos));
+    pos = c + 1;
+    const std::string where = "q3a_parse_logit_bias: suppress list";
+    if (item.empty()) fail(where + ": empty item");
+    long lo = 0, hi = 0;
+    parse_id_range(item, where, lo, hi);
+    add(lo, hi, -INFINITY, where);
+  }
+  if (count > 0x7fffffff) fail("q3a_parse_logit_bias: too many entries");
+  *n = (int32_t)count;
+  HOST_CATCH
+}
 
 int32_t q3a_load_audio(const char* path, int32_t target_sr, float** samples_out, int64_t* n_out) {
   HOST_TRY

@@ -590,6 +590,26 @@ __global__ __launch_bounds__(256) void gemv1_head_kernel(GemvArgs a) {
 // error <= γ/2 + u) and of e_r itself (< 8 u) are covered by the relative margin 2^-10; 2^-20 |a_r| covers the final roundings,
 // and 1e-30 the absolute error of products that underflow.  dn, wn, qn are rounded up by the packer.
 // NaN or infinite bounds make the block a candidate (hi = +inf): such rows are rescored, never skipped.
+//
+// With a logit bias (q3asr.h q3a_set_logit_bias: b_r finite or -inf, g.bias) the argmax is taken over l'_r = l_r + b_r, and both passes
+// add b_r: pass 2 is gemv1_head_block, whose `acc * rstd + bv` is l'_r = fl(λ + b_r) with λ = fl(Ĝ rstd) or, where the compiler fuses
+// the multiply and the add, λ = Ĝ rstd exactly; pass 1 forms a'_r = fl(α + b_r) with α = a_r or its unrounded product in the same way.
+// e_r bounds |α - λ| in all four combinations: the derivation above bounds the distance of the exact products and then ADDS one
+// term per rounding, so leaving a rounding out only loosens it.  Each of the two sums is rounded once:
+//   |a'_r - (α + b_r)| <= u |α + b_r| <= u (|a_r| (1 + u) + |b_r|),   |l'_r - (λ + b_r)| <= u |λ + b_r| <= u (|a_r| (1 + u) + e_r + |b_r|)
+//   => |a'_r - l'_r| <= e_r + u e_r + 2 u (1 + u) |a_r| + 2 u |b_r| <= e'_r = (e_r + 2^-22 (|a_r| + |b_r|)) (1 + 2^-20):
+// 2 u = 2^-23 is half of the coefficient used (the other half covers the u^2 term), and the factor 1 + 2^-20 covers u e_r and the
+// four roundings of e'_r's own evaluation (<= 4 u e'_r).  b_r = 0 gives a'_r = a_r and e'_r >= e_r: still a bound, a little wider.
+// A suppressed row (b_r = -inf) has a'_r = l'_r = -inf exactly: lo = hi = -inf, never a candidate and NOT the "no bound" case above,
+// so a block with every row suppressed is skipped by pass 2 (hi_b = -inf < T: the engine refuses a bias without a finite entry, so
+// T is finite or the NaN / overflow case) and an allow-list makes pass 2 cheaper.  This holds for finite activations, the only ones
+// the bound is stated for: with a NaN or inf in x the exact l'_r of a suppressed row is NaN, not -inf, and the row is still dropped
+// here while the full GEMV would carry the NaN; x is shared by every row, so every unsuppressed row then takes the "no bound" case
+// and is rescored to NaN as well: the two paths differ only inside a step that is poisoned in both.  The bias entry is requested with the row's qs
+// entry, in the same batch as the weights: 4 bytes per row next to cols bytes.
+// Without a bias the kernel that runs is the one without the code (template parameter BIAS of lm_head_approx_body: false in
+// lm_head_approx_kernel, the launch of an engine that never set a bias, true in lm_head_approx_bias_kernel); pass 2 keeps
+// gemv1_head_block's uniform null check on a.bias.
 struct LmHeadArgsDev {
   GemvArgs g;
   const int8_t* Wq; const float* qs; int qcols;
@@ -643,8 +663,8 @@ __global__ __launch_bounds__(256) void lm_head_quantize_kernel(const uint16_t* W
 }
 
 // Pass 1: one wave per 16-row block, 16 rows x cols/64 bytes per lane in flight (the bf16 launch: 4 rows x 2 x cols/64); no barrier
-template <int KI>
-__global__ __launch_bounds__(256) void lm_head_approx_kernel(LmHeadArgsDev p) {
+template <int KI, bool BIAS>
+__device__ __forceinline__ void lm_head_approx_body(const LmHeadArgsDev& p) {
   constexpr int R = 16, NQ = KI / 2;  // rows per wave; 16-byte pieces of an int8 row per lane
   const GemvArgs& a = p.g;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -676,6 +696,8 @@ __global__ __launch_bounds__(256) void lm_head_approx_kernel(LmHeadArgsDev p) {
   const int my_r = blk * R + lane;  // lanes 0..15 finish one row each
   const bool my_valid = lane < R && my_r < a.N;
   const float4 q = reinterpret_cast<const float4*>(p.qs)[my_valid ? my_r : 0];  // {s, dn, wn, qn}
+  float bq = 0.f;  // BIAS: the row's logit bias, same request batch
+  if constexpr (BIAS) bq = a.bias[my_valid ? my_r : 0];
   __builtin_amdgcn_sched_barrier(0);  // every request is issued before anything is waited for
   float x[KI][8];
   float ss = 0.f, yy = 0.f;
@@ -713,7 +735,20 @@ __global__ __launch_bounds__(256) void lm_head_approx_kernel(LmHeadArgsDev p) {
   const float av = (mine * q.x) * rstd;
   const float ev = (rstd * ny) * (q.y + p.gamma * (q.z + q.w)) * (1.0f + 0x1p-10f) + fabsf(av) * 0x1p-20f + 1e-30f;
   float lo = -INFINITY, hi = -INFINITY;
-  if (my_valid) {
+  if constexpr (BIAS) {
+    if (my_valid) {
+      const float ab = av + bq;                                                     // a'_r
+      const float eb = (ev + 0x1p-22f * (fabsf(av) + fabsf(bq))) * (1.0f + 0x1p-20f);  // e'_r (the comment above LmHeadArgsDev)
+      if (bq == -INFINITY) {  // suppressed: l'_r = -inf exactly, never a candidate (lo = hi = -inf stay)
+        if (p.dbg) { p.dbg[(size_t)my_r * 2] = -INFINITY; p.dbg[(size_t)my_r * 2 + 1] = 0.f; }
+      } else {
+        lo = ab - eb;
+        hi = ab + eb;
+        if (!(lo <= hi) || hi == INFINITY) { lo = -INFINITY; hi = INFINITY; }  // NaN / overflow: always rescored
+        if (p.dbg) { p.dbg[(size_t)my_r * 2] = ab; p.dbg[(size_t)my_r * 2 + 1] = eb; }
+      }
+    }
+  } else if (my_valid) {
     lo = av - ev;
     hi = av + ev;
     if (!(lo <= hi) || hi == INFINITY) { lo = -INFINITY; hi = INFINITY; }  // NaN / overflow: always rescored
@@ -723,6 +758,11 @@ __global__ __launch_bounds__(256) void lm_head_approx_kernel(LmHeadArgsDev p) {
   hi = wave_max(hi);
   if (lane == 0) { p.blk_lo[blk] = lo; p.blk_hi[blk] = hi; }
 }
+
+template <int KI>
+__global__ __launch_bounds__(256) void lm_head_approx_kernel(LmHeadArgsDev p) { lm_head_approx_body<KI, false>(p); }
+template <int KI>
+__global__ __launch_bounds__(256) void lm_head_approx_bias_kernel(LmHeadArgsDev p) { lm_head_approx_body<KI, true>(p); }  // with the logit bias
 
 // Pass 2: T over every block, then this workgroup's blocks blockIdx.x + j * gridDim.x (at most 256) that pass hi_b >= T,
 // rescored in ascending order; one (value, row) partial per workgroup.  No workgroup waits for another.
@@ -931,7 +971,8 @@ const char* launch_lm_head_quantize(const uint16_t* W, int N, int K, int8_t* Q, 
 }
 const char* lm_head_prune_check(const LmHeadPruneArgs& a) {
   const GemvArgs& g = a.g;
-  if (g.mode != 3 || !g.rms_w || !g.x || g.attn_po || g.bias) return "lm_head_prune: needs the plain mode-3 GEMV with a fused norm";
+  if (g.mode != 3 || !g.rms_w || !g.x || g.attn_po) return "lm_head_prune: needs the plain mode-3 GEMV with a fused norm";
+  if (g.bias && !a.logit_bias) return "lm_head_prune: the only bias the bound covers is the logit bias (finite or -inf entries)";
   if (g.part.sum) return "lm_head_prune: token log-probabilities need every logit (the full GEMV)";
   if (gemv_rows_per_wave(g) != 4 || gemv_blocks(g) != lm_head_prune_blocks(g)) return "lm_head_prune: the GEMV does not run 16-row blocks here";
   if (g.K % 8 != 0 || a.qcols != lm_head_q_cols(g.K)) return "lm_head_prune: int8 row width does not match the hidden size";
@@ -943,8 +984,13 @@ const char* launch_lm_head_approx(const LmHeadPruneArgs& a, hipStream_t s) {
   if (const char* e = lm_head_prune_check(a)) return e;
   const LmHeadArgsDev p = lm_head_dev_args(a);
   const dim3 grid((p.n_blk + 3) / 4), block(256);
-  if (a.qcols == 1024) hipLaunchKernelGGL(lm_head_approx_kernel<2>, grid, block, 0, s, p);
-  else hipLaunchKernelGGL(lm_head_approx_kernel<4>, grid, block, 0, s, p);
+  if (a.g.bias) {
+    if (a.qcols == 1024) hipLaunchKernelGGL(lm_head_approx_bias_kernel<2>, grid, block, 0, s, p);
+    else hipLaunchKernelGGL(lm_head_approx_bias_kernel<4>, grid, block, 0, s, p);
+  } else {
+    if (a.qcols == 1024) hipLaunchKernelGGL(lm_head_approx_kernel<2>, grid, block, 0, s, p);
+    else hipLaunchKernelGGL(lm_head_approx_kernel<4>, grid, block, 0, s, p);
+  }
   return nullptr;
 }
 int lm_head_rescore_groups(const GemvArgs& g, int n_cu) {

@@ -264,6 +264,8 @@ struct LmHeadPruneArgs {
   float* blk_lo; float* blk_hi; // [lm_head_prune_blocks(g)] (pass 1 -> pass 2; blk_lo readable as float4: round up to 4)
   float* dbg;                   // nullable: [N][2] (approximate logit, bound) per row (pass 1)
   int* stats;                   // nullable: [2] += candidate blocks, += 1 per pass 2 (debug; the step never reads it)
+  int logit_bias;               // 1: g.bias is the logit bias (every entry finite or -inf): both passes add it and the bound is the
+                                // extended one (k_gemv.hip, above LmHeadArgsDev); 0 with g.bias set: refused
 };
 // columns of one int8 lm_head row (a multiple of 1024: 16 (32) bytes per lane of a wave), 0 = hidden size beyond the GEMV
 inline int lm_head_q_cols(int hidden) { return hidden <= 1024 ? 1024 : hidden <= 2048 ? 2048 : 0; }

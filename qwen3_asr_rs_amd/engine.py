@@ -14,7 +14,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from typing import Iterable, List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -37,6 +37,58 @@ def _i32p(a: np.ndarray):
 
 def _i64p(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def compose_logit_bias(vocab: int, suppress_tokens: Optional[Iterable[int]] = None, logit_bias: Optional[Mapping[int, float]] = None,
+                       allowed_tokens: Optional[Iterable[int]] = None, keep_eos: bool = True):
+    """The (ids, bias, default) q3a_set_logit_bias takes, from the three ways callers state a constraint (pure host function).
+
+    suppress_tokens: ids that must never be written (bias -inf; Whisper's suppress_tokens, HF bad_words_ids of length 1).
+    logit_bias: id -> finite bias or -inf (OpenAI-style logit_bias, HF sequence_bias of length 1).
+    allowed_tokens: an allow-list -- default -inf, the listed ids at 0 (or at their logit_bias entry); with keep_eos both EOS ids
+    (151643, 151645) are allowed as well, so that generation can stop.  A logit_bias entry for an id outside the allow-list is dropped.
+    Suppression wins: an id in suppress_tokens is -inf whatever logit_bias or allowed_tokens say.
+    Returns ids (int32, ascending, unique), bias (float32) and the default (0.0 or -inf); ids whose bias equals the default are left out."""
+    def checked(ids, what):
+        out = []
+        for t in ids:
+            if int(t) != t or not 0 <= int(t) < vocab:
+                raise ValueError(f"{what}: id {t!r} is outside the vocabulary ({vocab})")
+            out.append(int(t))
+        return out
+    table = {}
+    for t, v in (logit_bias or {}).items():
+        t = checked([t], "logit_bias")[0]
+        v = float(v)
+        if np.isnan(v) or v == np.inf:
+            raise ValueError(f"logit_bias: the bias of id {t} is NaN or +inf (finite or -inf only)")
+        table[t] = v
+    default = 0.0
+    if allowed_tokens is not None:
+        default = -np.inf
+        allowed = set(checked(allowed_tokens, "allowed_tokens"))
+        if keep_eos:
+            allowed |= {t for t in EOS_TOKEN_IDS if t < vocab}
+        table = {t: table.get(t, 0.0) for t in allowed}
+    for t in checked(suppress_tokens or [], "suppress_tokens"):
+        table[t] = -np.inf
+    ids = sorted(t for t, v in table.items() if v != default)
+    return np.asarray(ids, dtype=np.int32), np.asarray([table[t] for t in ids], dtype=np.float32), float(default)
+
+
+def parse_logit_bias(text: Optional[str] = None, suppress_list: Optional[str] = None):
+    """q3a_parse_logit_bias: "id bias" / "lo-hi bias" lines ('#' comments, "-inf") and a comma list "id,lo-hi,..." of ids to
+    suppress -> (ids int32, bias float32).  Host only."""
+    lib = _lib.load()
+    t = text.encode() if text is not None else None
+    sl = suppress_list.encode() if suppress_list is not None else None
+    n = C.c_int32()
+    if lib.q3a_parse_logit_bias(t, sl, None, None, 0, C.byref(n)) != 0:
+        raise Q3aError((lib.q3a_last_error(None) or b"").decode())
+    ids, bias = np.zeros(max(n.value, 1), dtype=np.int32), np.zeros(max(n.value, 1), dtype=np.float32)
+    if lib.q3a_parse_logit_bias(t, sl, _i32p(ids), _f32p(bias), n.value, C.byref(n)) != 0:
+        raise Q3aError((lib.q3a_last_error(None) or b"").decode())
+    return ids[:n.value], bias[:n.value]
 
 
 class HipEngine:
@@ -72,6 +124,7 @@ class HipEngine:
         self.batch = 0
         self._n_frames: List[int] = []
         self._T: List[int] = []
+        self.logit_bias_state: Tuple[Optional[dict], float] = (None, 0.0)  # what set_logit_bias was last given
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -335,6 +388,26 @@ class HipEngine:
         self.batch = B
         return self._score_split(tl, lp, ti, tp)
 
+    # ---- constrained decoding ----------------------------------------------------------------------------
+    def set_logit_bias(self, bias: Optional[Mapping[int, float]] = None, default: float = 0.0):
+        """q3a_set_logit_bias: b = `default` (0.0 or -inf) everywhere, then b[id] = bias[id]; every head of the generation paths works
+        on logits + b until it is cleared (None / {} with default 0.0).  Drops the decode state: prefill again before a stage-API
+        step.  compose_logit_bias() builds the arguments from suppress / bias / allow lists."""
+        items = sorted((int(t), float(v)) for t, v in (bias or {}).items())
+        ids = np.asarray([t for t, _ in items], dtype=np.int32)
+        vals = np.asarray([v for _, v in items], dtype=np.float32)
+        self._chk(self._lib.q3a_set_logit_bias(self._h, _i32p(ids) if len(ids) else None, _f32p(vals) if len(ids) else None, len(ids),
+                                               C.c_float(default)))
+        self.logit_bias_state = (dict(items) if items else None, float(default))
+
+    def logit_bias_vector(self) -> np.ndarray:
+        """The dense fp32 [vocab] bias as the device holds it (zeros when off)."""
+        return self.debug_read("logit_bias")
+
+    def logit_bias_stats(self) -> dict:
+        st = self.debug_read_raw("logit_bias_stats").view(np.int32)
+        return {"active": bool(st[0]), "finite": int(st[1])}
+
     # ---- beam search ----------------------------------------------------------------------------------
     def _beam_unpack(self, U, W, stride, ids, lens, scores, fin, lp) -> "List[List[BeamHypothesis]]":
         res = []
@@ -580,10 +653,24 @@ class AsrInference:
         return cls(eng, tok)
 
     def transcribe(self, audio, language: Optional[str] = None, max_new_tokens: int = 4096, beam_size: int = 1,
-                   length_penalty: float = 0.0) -> TranscribeResult:
+                   length_penalty: float = 0.0, suppress_tokens: Optional[Iterable[int]] = None,
+                   logit_bias: Optional[Mapping[int, float]] = None, allowed_tokens: Optional[Iterable[int]] = None) -> TranscribeResult:
         """src/inference.rs:89-213.  `audio`: path to a WAV file or a 16 kHz float32 array.  beam_size > 1: a beam search of that
         width instead of the greedy loop; `alternatives` holds its hypotheses ordered by score / max(len, 1) ** length_penalty
-        (float64 on the host; 0: the search's own order) and the result is the first of them."""
+        (float64 on the host; 0: the search's own order) and the result is the first of them.
+        suppress_tokens / logit_bias / allowed_tokens (compose_logit_bias): constrain this call -- the engine's logit bias is set for
+        it and whatever was set before is restored afterwards; composes with beam_size."""
+        if suppress_tokens is None and logit_bias is None and allowed_tokens is None:
+            return self._transcribe(audio, language, max_new_tokens, beam_size, length_penalty)
+        ids, bias, default = compose_logit_bias(self.engine.dims.vocab_size, suppress_tokens, logit_bias, allowed_tokens)
+        before = self.engine.logit_bias_state
+        self.engine.set_logit_bias(dict(zip(ids.tolist(), bias.tolist())), default)
+        try:
+            return self._transcribe(audio, language, max_new_tokens, beam_size, length_penalty)
+        finally:
+            self.engine.set_logit_bias(*before)
+
+    def _transcribe(self, audio, language, max_new_tokens, beam_size, length_penalty) -> TranscribeResult:
         if isinstance(audio, (str, os.PathLike)):
             samples = load_audio(os.fspath(audio), 16000)
         else:
