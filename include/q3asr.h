@@ -499,6 +499,33 @@ int32_t q3a_selftest_gemm(int32_t device, int32_t M, int32_t N, int32_t K, int32
 int32_t q3a_selftest_gemm16(int32_t device, int32_t M, int32_t N, int32_t K, int32_t reps, float* max_abs_err,
                             float* ref_abs_max, float* avg_us_bf16, float* avg_us_f32);
 
+/* ONE launch of the GEMM family on the caller's data (no model, no reference arithmetic in the library: tests/gemm_ref.py compares in
+ * float64).  Every output buffer is the caller's: pre-filled with a sentinel, uploaded, written by the launch, returned whole -- so rows a
+ * row map drops, columns N..ldo, rows past M and cache rows no token names are visible.  On the device each output sits between guard
+ * zones; a changed guard byte fails the call.  Arguments the launch could index out of bounds with are refused before anything runs.
+ *   launcher  0 launch_gemm, 1 launch_gemm16 (with its dispatch to gemm256), 2 launch_gemm16_small, 3 launch_conv3x3s2_gemm,
+ *             4 launch_conv3x3s2_gemm16 (with its dispatch); 0 / 3 take fp32 x, the others bf16 bit patterns
+ *   flags     1 split (hi + lo activations; launchers 0 / 3), 2 GLU ([16 gate | 16 up] row blocks of w, N / 2 output columns),
+ *             4 out is bf16 [out_rows][ldo] instead of fp32, 8 the residual IS the output buffer (resid null; fp32 output)
+ *   x         dense [M][lda]; convolution NHWC [imgs][H][Wd][C], M = imgs * OH * OW, K = 9 * C ordered (kh, kw, c), N = Cout
+ *   w         bf16 [N][K];  bias [N], addend [addend_period][ldo], resid [out_rows][ldo], rowmap [M] (negative: dropped) -- each nullable
+ *   act       0 none, 1 GELU */
+int32_t q3a_selftest_gemm_launch(int32_t device, int32_t launcher, int32_t flags, const void* x, const uint16_t* w, int32_t M, int32_t N, int32_t K,
+                                 int32_t lda, int32_t ldo, int32_t imgs, int32_t H, int32_t Wd, int32_t C, const float* bias, const float* addend,
+                                 int32_t addend_period, const float* resid, const int32_t* rowmap, int32_t act, void* out, int32_t out_rows);
+/* The same for per-head QK-norm + RoPE + KV-cache append.  fused = 1: launch_gemm256_qkrope on bf16 x [M][lda], w [(n_q + 2 n_kv) * 128][K]
+ * and a nullable bias; q16 and a bf16 cache required; qkv nullable fp32 [M][N] scratch (with it the launch may split off its trailing
+ * rows, see q3a_gemm256_split_rows).  fused = 0: launch_qknorm_rope_kv on fp32 qkv [M][N] (x, w, bias null); q is written to q16 when
+ * given, else in place; kv_f32 selects an fp32 cache.  row_seq / row_pos [M], q_norm / k_norm [128], cos_t / sin_t [max_pos][64],
+ * kcache / vcache [n_seq][n_kv][max_ctx][128].  Outputs (qkv, q16, kcache, vcache) as above: sentinel in, whole buffer out. */
+int32_t q3a_selftest_qkrope_launch(int32_t device, int32_t fused, int32_t kv_f32, const uint16_t* x, int32_t lda, const uint16_t* w, int32_t M, int32_t K,
+                                   const float* bias, float* qkv, const int32_t* row_seq, const int32_t* row_pos, const float* q_norm,
+                                   const float* k_norm, float eps, const float* cos_t, const float* sin_t, int32_t max_pos, int32_t n_q, int32_t n_kv,
+                                   int32_t n_seq, int32_t max_ctx, uint16_t* q16, void* kcache, void* vcache);
+/* Rows [0, M1) of an M x N bf16 GEMM that launch_gemm256 gives to the 256 x 256 kernel when it hands the trailing rows to the small
+ * tiles (wave quantisation; 0: no split).  Host arithmetic, no device needed. */
+int32_t q3a_gemm256_split_rows(int32_t M, int32_t N);
+
 #ifdef __cplusplus
 }
 #endif

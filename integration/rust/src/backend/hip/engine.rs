@@ -85,6 +85,16 @@ extern "C" {
                                      finished_out: *mut u8) -> i32;
     pub fn q3a_selftest_kv_reorder(device: i32, cache: *mut std::ffi::c_void, elem_bytes: i32, layers: i32, s: i32, n_kv: i32, max_ctx: i32,
                                    lo: *const i32, hi: *const i32, parent: *const i32) -> i32;
+    // one launch of the GEMM family / of QK-norm + RoPE + cache append on the caller's data (include/q3asr.h; tests/gemm_ref.py)
+    pub fn q3a_selftest_gemm_launch(device: i32, launcher: i32, flags: i32, x: *const std::ffi::c_void, w: *const u16, m: i32, n: i32, k: i32,
+                                    lda: i32, ldo: i32, imgs: i32, h: i32, wd: i32, c: i32, bias: *const f32, addend: *const f32,
+                                    addend_period: i32, resid: *const f32, rowmap: *const i32, act: i32, out: *mut std::ffi::c_void,
+                                    out_rows: i32) -> i32;
+    pub fn q3a_selftest_qkrope_launch(device: i32, fused: i32, kv_f32: i32, x: *const u16, lda: i32, w: *const u16, m: i32, k: i32,
+                                      bias: *const f32, qkv: *mut f32, row_seq: *const i32, row_pos: *const i32, q_norm: *const f32,
+                                      k_norm: *const f32, eps: f32, cos_t: *const f32, sin_t: *const f32, max_pos: i32, n_q: i32, n_kv: i32,
+                                      n_seq: i32, max_ctx: i32, q16: *mut u16, kcache: *mut std::ffi::c_void, vcache: *mut std::ffi::c_void) -> i32;
+    pub fn q3a_gemm256_split_rows(m: i32, n: i32) -> i32;
 }
 
 /// src/main.rs:51-65 for the `hip` feature: HIP devices visible to this process (0: none -- there is no CPU path).

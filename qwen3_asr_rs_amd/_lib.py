@@ -24,6 +24,7 @@ SYMBOLS = [
     "q3a_align_text_ids", "q3a_fix_timestamps", "q3a_score", "q3a_score_batch_ptrs",
     "q3a_beam_search_batch_ptrs", "q3a_beam_begin", "q3a_beam_step", "q3a_beam_fetch", "q3a_selftest_beam_topk", "q3a_selftest_beam_advance",
     "q3a_selftest_kv_reorder", "q3a_set_logit_bias", "q3a_parse_logit_bias",
+    "q3a_selftest_gemm_launch", "q3a_selftest_qkrope_launch", "q3a_gemm256_split_rows",
 ]
 
 
@@ -151,6 +152,9 @@ def load() -> C.CDLL:
         "q3a_selftest_kv_reorder": (i32, [i32, P, i32, i32, i32, i32, i32, i32p, i32p, i32p]),
         "q3a_set_logit_bias": (i32, [P, i32p, f32p, i32, C.c_float]),
         "q3a_parse_logit_bias": (i32, [C.c_char_p, C.c_char_p, i32p, f32p, i32, i32p]),
+        "q3a_selftest_gemm_launch": (i32, [i32, i32, i32, P, P, i32, i32, i32, i32, i32, i32, i32, i32, i32, P, P, i32, P, P, i32, P, i32]),
+        "q3a_selftest_qkrope_launch": (i32, [i32, i32, i32, P, i32, P, i32, i32, P, P, P, P, P, P, C.c_float, P, P, i32, i32, i32, i32, i32, P, P, P]),
+        "q3a_gemm256_split_rows": (i32, [i32, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

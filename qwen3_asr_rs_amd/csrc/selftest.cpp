@@ -52,9 +52,130 @@ struct GemmCase {
   }
 };
 
+// An output buffer between two guard zones.  The caller's bytes (pre-filled with its sentinel) go up, the launch under test writes what
+// it writes, and the bytes come back whole; a guard byte that changed is a write outside the buffer and fails the call.
+struct Guarded {
+  static constexpr size_t ZONE = 4096;
+  static constexpr uint8_t FILL = 0xA5;
+  DevBuf b;
+  size_t bytes = 0;
+  Guarded() = default;
+  Guarded(const void* host, size_t n) : bytes(n) {
+    std::vector<uint8_t> img(n + 2 * ZONE, FILL);
+    memcpy(img.data() + ZONE, host, n);
+    b = to_device(img);
+  }
+  template <class T> T* as() const { return b.p ? reinterpret_cast<T*>(static_cast<uint8_t*>(b.p) + ZONE) : nullptr; }
+  void fetch(void* host, const char* what) const {
+    const std::vector<uint8_t> img = to_host<uint8_t>(b, bytes + 2 * ZONE);
+    for (size_t i = 0; i < ZONE; ++i)
+      if (img[i] != FILL || img[ZONE + bytes + i] != FILL) fail(std::string("selftest: a byte outside the ") + what + " buffer was written");
+    memcpy(host, img.data() + ZONE, bytes);
+  }
+};
+
 }  // namespace
 
 extern "C" {
+
+int32_t q3a_gemm256_split_rows(int32_t M, int32_t N) { return gemm256_split_rows(M, N); }
+
+int32_t q3a_selftest_gemm_launch(int32_t device, int32_t launcher, int32_t flags, const void* x, const uint16_t* w, int32_t M, int32_t N, int32_t K,
+                                 int32_t lda, int32_t ldo, int32_t imgs, int32_t H, int32_t Wd, int32_t C, const float* bias, const float* addend,
+                                 int32_t addend_period, const float* resid, const int32_t* rowmap, int32_t act, void* out, int32_t out_rows) {
+  Q3A_TRY(nullptr)
+  use_device(device);
+  const bool split = flags & 1, glu = flags & 2, o16 = flags & 4, alias = flags & 8;
+  const bool conv = launcher == 3 || launcher == 4, x16 = launcher == 1 || launcher == 2 || launcher == 4;
+  // every index the launch will form is checked here: a refusal, never an access outside a buffer
+  if (launcher < 0 || launcher > 4 || (flags & ~15) || !x || !w || !out || M < 1 || N < 1 || K < 1 || out_rows < 1 || (act != 0 && act != 1))
+    fail("q3a_selftest_gemm_launch: bad argument");
+  if (conv) {
+    if (imgs < 1 || H < 1 || Wd < 1 || C < 1 || C % 32 != 0 || K != 9 * C || glu) fail("q3a_selftest_gemm_launch: bad convolution geometry");
+    if ((long)M != (long)imgs * ((H - 1) / 2 + 1) * ((Wd - 1) / 2 + 1)) fail("q3a_selftest_gemm_launch: M is not imgs * OH * OW");
+  } else if (lda < K) fail("q3a_selftest_gemm_launch: lda < K");
+  if (glu && N % 32 != 0) fail("q3a_selftest_gemm_launch: GLU needs N % 32 == 0");
+  if (ldo < (glu ? N / 2 : N)) fail("q3a_selftest_gemm_launch: ldo smaller than the output row");
+  if (o16 && !x16) fail("q3a_selftest_gemm_launch: the fp32-activation kernels have no bf16 output");
+  if (split && x16) fail("q3a_selftest_gemm_launch: split belongs to the fp32-activation kernels");
+  if (alias && (resid || o16)) fail("q3a_selftest_gemm_launch: an aliased residual is the fp32 output buffer itself");
+  if (addend && addend_period < 1) fail("q3a_selftest_gemm_launch: addend period");
+  if (rowmap) {
+    for (int m = 0; m < M; ++m)
+      if (rowmap[m] >= out_rows) fail("q3a_selftest_gemm_launch: row map points past the output");
+  } else if (out_rows < M) fail("q3a_selftest_gemm_launch: output has fewer rows than the product");
+  const size_t n_out = (size_t)out_rows * ldo, n_x = conv ? (size_t)imgs * H * Wd * C : (size_t)M * lda;
+  const DevBuf dX = to_device((const uint8_t*)x, n_x * (x16 ? 2 : 4)), dW = to_device(w, (size_t)N * K);
+  const DevBuf dZero = to_device(std::vector<uint16_t>(128, 0));
+  DevBuf dB, dA, dS, dM;
+  if (bias) dB = to_device(bias, (size_t)N);
+  if (addend) dA = to_device(addend, (size_t)addend_period * ldo);
+  if (resid) dS = to_device(resid, n_out);
+  if (rowmap) dM = to_device(rowmap, (size_t)M);
+  const Guarded dO(out, n_out * (o16 ? 2 : 4));
+  GemmEpilogue ep;
+  if (o16) ep.out16 = dO.as<uint16_t>(); else ep.out = dO.as<float>();
+  ep.ldo = ldo; ep.bias = dB.as<float>(); ep.act = act; ep.rowmap = dM.as<int>();
+  ep.resid = alias ? dO.as<float>() : dS.as<float>();
+  ep.addend = dA.as<float>(); ep.addend_period = addend ? addend_period : 1;
+  switch (launcher) {
+    case 0: KCHK(launch_gemm(dX.as<float>(), lda, dW.as<uint16_t>(), M, N, K, ep, glu, split, nullptr)); break;
+    case 1: KCHK(launch_gemm16(dX.as<uint16_t>(), lda, dW.as<uint16_t>(), M, N, K, ep, glu, nullptr)); break;
+    case 2: KCHK(launch_gemm16_small(dX.as<uint16_t>(), lda, dW.as<uint16_t>(), M, N, K, ep, glu, nullptr)); break;
+    case 3: KCHK(launch_conv3x3s2_gemm(dX.as<float>(), imgs, H, Wd, C, dW.as<uint16_t>(), N, ep, split, nullptr)); break;
+    default: KCHK(launch_conv3x3s2_gemm16(dX.as<uint16_t>(), dZero.as<uint16_t>(), imgs, H, Wd, C, dW.as<uint16_t>(), N, ep, nullptr)); break;
+  }
+  finish();
+  dO.fetch(out, "output");
+  Q3A_CATCH(nullptr)
+}
+
+int32_t q3a_selftest_qkrope_launch(int32_t device, int32_t fused, int32_t kv_f32, const uint16_t* x, int32_t lda, const uint16_t* w, int32_t M, int32_t K,
+                                   const float* bias, float* qkv, const int32_t* row_seq, const int32_t* row_pos, const float* q_norm,
+                                   const float* k_norm, float eps, const float* cos_t, const float* sin_t, int32_t max_pos, int32_t n_q, int32_t n_kv,
+                                   int32_t n_seq, int32_t max_ctx, uint16_t* q16, void* kcache, void* vcache) {
+  Q3A_TRY(nullptr)
+  use_device(device);
+  if (!row_seq || !row_pos || !q_norm || !k_norm || !cos_t || !sin_t || !kcache || !vcache || M < 1 || n_q < 1 || n_kv < 1 || n_seq < 1 || max_ctx < 1 ||
+      max_pos < 1)
+    fail("q3a_selftest_qkrope_launch: bad argument");
+  const int N = (n_q + 2 * n_kv) * 128;
+  if (fused) {
+    if (!x || !w || !q16 || kv_f32 || K < 128 || K % 64 != 0 || lda < K || lda % 8 != 0)
+      fail("q3a_selftest_qkrope_launch: the fused form needs bf16 x / W, K % 64 == 0, K >= 128, a bf16 q and a bf16 cache");
+  } else if (x || w || bias || !qkv) fail("q3a_selftest_qkrope_launch: the separate kernel takes the fp32 qkv matrix alone");
+  {  // every cache row a token names exists and is named once (two rows on one cache row would race)
+    std::vector<char> seen((size_t)n_seq * max_ctx, 0);
+    for (int m = 0; m < M; ++m) {
+      if (row_seq[m] < 0 || row_seq[m] >= n_seq || row_pos[m] < 0 || row_pos[m] >= max_ctx || row_pos[m] >= max_pos)
+        fail("q3a_selftest_qkrope_launch: a row's sequence or position is outside the cache or the RoPE table");
+      char& s = seen[(size_t)row_seq[m] * max_ctx + row_pos[m]];
+      if (s) fail("q3a_selftest_qkrope_launch: two rows name one cache row");
+      s = 1;
+    }
+  }
+  const size_t n_cache = (size_t)n_seq * n_kv * max_ctx * 128, kv_bytes = n_cache * (kv_f32 ? 4 : 2), n_q16 = (size_t)M * n_q * 128;
+  DevBuf dX, dW, dB;
+  if (fused) { dX = to_device(x, (size_t)M * lda); dW = to_device(w, (size_t)N * K); }
+  if (bias) dB = to_device(bias, (size_t)N);
+  const DevBuf dSeq = to_device(row_seq, (size_t)M), dPos = to_device(row_pos, (size_t)M), dQn = to_device(q_norm, 128), dKn = to_device(k_norm, 128);
+  const DevBuf dCos = to_device(cos_t, (size_t)max_pos * 64), dSin = to_device(sin_t, (size_t)max_pos * 64);
+  Guarded gQkv, gQ16;
+  if (qkv) gQkv = Guarded(qkv, (size_t)M * N * 4);
+  if (q16) gQ16 = Guarded(q16, n_q16 * 2);
+  const Guarded gK(kcache, kv_bytes), gV(vcache, kv_bytes);
+  RopeKvArgs rk{};
+  rk.qkv = gQkv.as<float>(); rk.row_seq = dSeq.as<int>(); rk.row_pos = dPos.as<int>(); rk.q_norm = dQn.as<float>(); rk.k_norm = dKn.as<float>();
+  rk.eps = eps; rk.cos_t = dCos.as<float>(); rk.sin_t = dSin.as<float>(); rk.kcache = gK.as<void>(); rk.vcache = gV.as<void>();
+  rk.n_q = n_q; rk.n_kv = n_kv; rk.max_ctx = max_ctx; rk.q16 = gQ16.as<uint16_t>();
+  if (fused) KCHK(launch_gemm256_qkrope(dX.as<uint16_t>(), lda, dW.as<uint16_t>(), M, K, dB.as<float>(), rk, nullptr));
+  else KCHK(launch_qknorm_rope_kv(rk, M, kv_f32 != 0, nullptr));
+  finish();
+  if (qkv) gQkv.fetch(qkv, "qkv");
+  if (q16) gQ16.fetch(q16, "q");
+  gK.fetch(kcache, "K cache"); gV.fetch(vcache, "V cache");
+  Q3A_CATCH(nullptr)
+}
 
 int32_t q3a_selftest_beam_topk(int32_t device, const float* logits, int32_t S, int32_t V, int32_t W, int32_t* out_ids, float* out_lp) {
   Q3A_TRY(nullptr)
