@@ -439,7 +439,7 @@ int32_t q3a_selftest_kv_reorder(int32_t device, void* cache, int32_t elem_bytes,
  * Readable without debug taps: q3a_debug_read(e, "logit_bias", ..) (fp32 [vocab] as the device holds it, zeros when off) and
  * "logit_bias_stats" (int32 [2]: active 0 / 1, finite entries).
  * Out of scope: per-utterance biases inside one batch (a [S][vocab] operand: 19 MB per step at 32 sequences); history-dependent
- * processors (no-repeat n-gram, repetition penalty); multi-token phrase constraints; sampling; a bias inside q3a_score*. */
+ * processors (no-repeat n-gram, repetition penalty); multi-token phrase constraints; a bias inside q3a_score*.  (Sampling: its own section below.) */
 
 /* b = default_bias everywhere (0 or -INFINITY only), then b[ids[i]] = bias[i].  n = 0 with default_bias = 0 clears the bias: the
  * engine is back on the launches, ids and log-probabilities of an engine that never had one, bit for bit.  An allow-list is
@@ -450,6 +450,42 @@ int32_t q3a_set_logit_bias(q3a_engine* e, const int32_t* ids, const float* bias,
  * *n = entries needed, at most cap written.  Refused (q3a_last_error(NULL)): a malformed line or item, a NaN / +inf bias, an id
  * named twice. */
 int32_t q3a_parse_logit_bias(const char* text, const char* suppress_list, int32_t* ids, float* bias, int32_t cap, int32_t* n);
+
+/* ---- sampling: the next id drawn from softmax(l' / T) inside the decode step ---------------------------------------------------------
+ * With temperature T > 0 every step of the GENERATION paths draws its id instead of taking the argmax, on the device, with no logits
+ * going to the host.  l' are the (biased) fp32 logits of sequence s at step t; s is the sequence's index in the call and t the number
+ * of ids the sequence has generated so far (the device's own step counter: 0 for the id the prefill produces).
+ *   Kept set.  K = { j : l'_j >= m + T ln(min_p) }, m = max_j l'_j, the threshold evaluated in fp32.  min_p = 0 keeps every finite
+ *     logit; -inf logits are never kept; the maximum always is.  (The "min-p" rule stated on logits: p_j >= min_p p_max at temperature T.)
+ *   Noise.  x_j = word 0 of Philox4x32-10 with counter (j, t, s, 0) and key (seed low word, seed high word) = q3a_sample_word(seed, s,
+ *     t, j); u_j = ((x_j >> 8) + 0.5) 2^-24, a real number strictly between 0 and 1 (an fp32 number while x_j < 2^31; above, 1 - u_j is
+ *     one, and the kernel takes -log u_j from it); g_j = -log(-log u_j).
+ *   Choice.  id = argmax over K of z_j = l'_j + T g_j (larger value, then smaller id): Gumbel-max, so id is distributed as softmax(l' / T)
+ *     restricted to K.  No division by T; T -> 0 runs continuously into the greedy id.  z_j is evaluated in fp32 (logf, log1pf, one
+ *     fma), so an id is specified up to the fp32 error of z: it is the exact arithmetic's best, or, when the exact best two lie closer
+ *     than that error, one of those two (DESIGN.md section 3.11 has the measured figure).
+ *   Everything downstream is the greedy step's: EOS, done flags, lengths, q3a_fetch_ids, natural EOS, q3a_decode_step, the logit bias.
+ *   Log-probabilities (opts.token_logprobs): log_softmax(l')[id], the biased and UNTEMPERED distribution.
+ * The noise of a token depends on (seed, s, t, j) alone: a run is reproducible from its seed, graph replay and the stage API draw the
+ * same ids, and a reference can reproduce any single entry.  Because s is the index in the call, a clip sampled alone and the same
+ * clip inside a batch draw different noise.
+ * temperature == 0 turns sampling off: the engine is back on the launches, graphs and ids of one that never sampled.
+ * State: the setting persists until changed.  q3a_set_sampling drops the decode state as q3a_set_logit_bias does, so it never changes
+ * under a live sequence.  On / off is part of the captured step's signature; temperature, min_p and seed live in a device buffer
+ * the kernels read, so changing them replays the same graph.
+ * Applies to: q3a_prefill (next_ids), q3a_decode_step, q3a_run_resident, q3a_transcribe_batch[_ptrs], q3a_fetch_logprobs.  While it
+ * is on, every lm_head form stores its logits and the one-sequence pruned argmax is not taken.
+ * Refused (q3a_last_error): a negative, NaN or infinite temperature; min_p outside [0, 1]; an aligner engine; q3a_beam_begin /
+ * q3a_beam_search_batch_ptrs while sampling is on.  q3a_score* and q3a_align* never see it.
+ * Readable: q3a_debug_read(e, "sampling", ..) (uint32 [5]: on 0 / 1, temperature and min_p as fp32 bits, seed low, seed high).
+ * Out of scope: top-k / top-p; sampling inside beam search; a group-level call (set it on each q3a_group_engine handle). */
+int32_t q3a_set_sampling(q3a_engine* e, float temperature, float min_p, uint64_t seed);
+/* Host function, no engine and no device: the random word of token j of sequence s at step t, by the code the kernel runs. */
+uint32_t q3a_sample_word(uint64_t seed, uint32_t s, uint32_t t, uint32_t j);
+/* The sampler's kernels on their own (no model): logits [S][V] host fp32, every sequence at step `step` -> out_ids [S], out_lp [S]
+ * (log_softmax(l)[id]) and out_z [S] (the winning noisy score z_id); any may be null.  temperature > 0. */
+int32_t q3a_selftest_sample(int32_t device, const float* logits, int32_t S, int32_t V, float temperature, float min_p,
+                            uint64_t seed, int32_t step, int32_t* out_ids, float* out_lp, float* out_z);
 
 /* A/B knobs for kernel experiments (process-wide atomics, read from the environment once; not part of the reference
  * interface).  The knobs that shape the decode step are latched per batch at the next prefill and are part of the captured

@@ -71,6 +71,8 @@ extern "C" {
     // decoding"); q3a_score* / q3a_align* never see it
     pub fn q3a_set_logit_bias(e: *mut q3a_engine, ids: *const i32, bias: *const f32, n: i32, default_bias: f32) -> i32;
     pub fn q3a_parse_logit_bias(text: *const c_char, suppress_list: *const c_char, ids: *mut i32, bias: *mut f32, cap: i32, n: *mut i32) -> i32;
+    pub fn q3a_set_sampling(e: *mut q3a_engine, temperature: f32, min_p: f32, seed: u64) -> i32;
+    pub fn q3a_sample_word(seed: u64, s: u32, t: u32, j: u32) -> u32;
     // beam search: n-best hypotheses with scores, selected on the device (include/q3asr.h "beam search")
     pub fn q3a_beam_search_batch_ptrs(e: *mut q3a_engine, pcm16k: *const *const f32, n_samples: *const i64, u: i32,
                                       lang_prefix_ids: *const i32, n_prefix: i32, width: i32, max_new: i32, out_ids: *mut i32, stride: i32,

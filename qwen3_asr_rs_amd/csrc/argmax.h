@@ -47,4 +47,11 @@ struct ArgmaxAcc {
   }
 };
 
+// one lane's scan of stored logits in ascending id order, online: the (max, first id, sum exp) of what it has seen (the beam
+// top-W selection and the sampler's row statistics, k_beam.hip / k_sample.hip)
+__device__ __forceinline__ void lse_visit(ArgmaxAcc<true>& m, float v, int id) {
+  if (v > m.v) { m.s = lse_term(m.s, m.v, v) + 1.f; m.v = v; m.i = id; }
+  else m.s += lse_term(1.f, v, m.v);
+}
+
 }  // namespace q3a

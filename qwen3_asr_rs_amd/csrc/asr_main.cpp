@@ -15,6 +15,8 @@
 // Q3A_SUPPRESS_TOKENS=<id,lo-hi,...> and Q3A_LOGIT_BIAS=<path of a file of "id bias" / "lo-hi bias" lines> constrain the decoding
 // (q3a_parse_logit_bias + q3a_set_logit_bias, default bias 0): the transcription and a Q3A_BEAM search run under the bias, a
 // Q3A_SCORE_TEXT score does not; without them nothing changes.
+// Q3A_TEMPERATURE=<T> [Q3A_MIN_P=<p>] [Q3A_SEED=<n>] samples the transcription at ONE temperature (q3a_set_sampling; min_p 0 and seed
+// 0 when absent); a Q3A_BEAM search is then refused by the engine.  There is no temperature fallback here (no zlib).
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -57,6 +59,29 @@ static int set_logit_bias_from_env(q3a_engine* eng) {
   if (q3a_parse_logit_bias(text.c_str(), list, ids.data(), bias.data(), n, &n) != 0) return die(std::string("Logit bias failed: ") + q3a_last_error(nullptr));
   if (q3a_set_logit_bias(eng, ids.data(), bias.data(), n, 0.f) != 0) return die(std::string("Logit bias failed: ") + q3a_last_error(eng));
   logf(1, "Logit bias: %s entries", std::to_string(n));
+  return 0;
+}
+
+// Q3A_TEMPERATURE / Q3A_MIN_P / Q3A_SEED: the engine's sampling setting, set before anything is generated
+static int set_sampling_from_env(q3a_engine* eng) {
+  const char* t = getenv("Q3A_TEMPERATURE");
+  if (!t || !*t) return 0;
+  const char *p = getenv("Q3A_MIN_P"), *sd = getenv("Q3A_SEED");
+  char* end = nullptr;
+  const float temperature = strtof(t, &end);
+  if (end == t || *end) return die(std::string("Sampling failed: Q3A_TEMPERATURE is not a number: ") + t);
+  float min_p = 0.f;
+  if (p && *p) {
+    min_p = strtof(p, &end);
+    if (end == p || *end) return die(std::string("Sampling failed: Q3A_MIN_P is not a number: ") + p);
+  }
+  unsigned long long seed = 0;
+  if (sd && *sd) {
+    seed = strtoull(sd, &end, 10);
+    if (end == sd || *end || *sd == '-') return die(std::string("Sampling failed: Q3A_SEED is not an unsigned integer: ") + sd);
+  }
+  if (q3a_set_sampling(eng, temperature, min_p, (uint64_t)seed) != 0) return die(std::string("Sampling failed: ") + q3a_last_error(eng));
+  logf(1, "Sampling: temperature %s", t);
   return 0;
 }
 
@@ -212,6 +237,7 @@ int main(int argc, char** argv) {
   if (q3a_weights_rounded(eng))
     logf(0, "warning: the checkpoint stores F16/F32 matrices; the HIP backend keeps matrices as bf16 (rounded to nearest-even)");
   if (set_logit_bias_from_env(eng) != 0) return 1;
+  if (set_sampling_from_env(eng) != 0) return 1;
   logf(1, "Loading tokenizer...");
   q3a_tokenizer* tok = nullptr;
   const std::string tj = std::string(model_path) + "/tokenizer.json";

@@ -128,6 +128,7 @@ struct StepView {
   const size_t& kv_layer_elems; const bool& head_logits_;
   const int &k_parallel_groups, &k_skinny_q, &k_dattn_batched_min_wgs, &k_skinny_glu_hp3, &k_lm_head_prune;  // knobs as latched per batch
   const bool& logit_bias_on_;  // q3a_set_logit_bias: a bias is set (changes only while the engine holds no decode state)
+  const bool& sampling_on_;    // q3a_set_sampling: temperature > 0 (likewise)
 
   bool precise() const { return opts.precise != 0; }
   bool token_lp() const { return opts.token_logprobs != 0; }
@@ -155,6 +156,9 @@ struct DecodeStep : StepView {
   DevBuf beam_cand_val, beam_cand_idx, beam_part_max, beam_part_sum, beam_topk_ids, beam_topk_lp, beam_score, beam_finished, beam_parent, beam_token;
   DevBuf beam_feed, beam_hist_parent, beam_hist_token, beam_hist_lp, beam_state, beam_lo;
   DevBuf logit_bias;  // [vocab] fp32, every entry finite or -inf (q3a_set_logit_bias; zeros while off): every head form adds it to its logits
+  // q3a_set_sampling: {temperature, min_p, seed low, seed high} as the sampler's kernels read them (a new setting needs no new graph),
+  // and the clean (max, sum exp) pair of every 2048-logit chunk of every row [B][sample_chunks(vocab)]
+  DevBuf samp_params, samp_max, samp_sum;
   // f(buffer) for every DevBuf declared above, in declaration order (s: a DecodeStep, const or not).  The declarations of this
   // struct ARE the guarded set: tests/test_host.py::test_step_buffers_cover_the_captured_step compares this list with them.
   template <class Self, class F> static void each_buf(Self& s, F&& f) {
@@ -163,7 +167,7 @@ struct DecodeStep : StepView {
                     &s.rope_cur, &s.rope_cos, &s.rope_sin, &s.n_done, &s.forced_tok,
                     &s.beam_cand_val, &s.beam_cand_idx, &s.beam_part_max, &s.beam_part_sum, &s.beam_topk_ids, &s.beam_topk_lp, &s.beam_score, &s.beam_finished,
                     &s.beam_parent, &s.beam_token, &s.beam_feed, &s.beam_hist_parent, &s.beam_hist_token, &s.beam_hist_lp, &s.beam_state, &s.beam_lo,
-                    &s.logit_bias})
+                    &s.logit_bias, &s.samp_params, &s.samp_max, &s.samp_sum})
       f(*b);
   }
 
@@ -194,12 +198,15 @@ struct DecodeStep : StepView {
   // the logit bias for whichever head form runs; null: none set, every launch is the one of an engine that never had one
   const float* head_bias() const { return logit_bias_on_ ? logit_bias.as<float>() : nullptr; }
 
-  // final norm + lm_head on x_dec -> logits (+ block argmax partials), then argmax/finalize.  With a logit bias every form below
+  // final norm + lm_head on x_dec -> logits (+ block argmax partials), then argmax/finalize.  While sampling is on every form
+  // stores its logits (as with head_logits_), the sampler (k_sample.hip) replaces the head's partials with its own noisy ones, and
+  // finalize runs on those unchanged.  With a logit bias every form below
   // works on l' = l + b: the GEMV heads and both passes of the pruned argmax through GemvArgs::bias, the gemm16 forms through
   // GemmEpilogue::bias (in front of the argmax epilogue and of the stored logits), the precise batched form through batched_proj.
   void run_head(int advance) {
     const int S = B, H = d.hidden, V = d.vocab;
     const float* const hb = head_bias();
+    const bool sample = sampling_on_, store = head_logits_ || sample;
     tap("head_in", x_dec.p, (size_t)S * H * 4);  // (debug taps) last-layer residual rows the final norm + lm_head read
     const double wbytes = 2.0 * V * H;
     int n_part = 0;
@@ -223,7 +230,7 @@ struct DecodeStep : StepView {
         pd.dbg = t.as<float>(); pd.stats = nullptr;
         KCHK(launch_lm_head_approx(pd, stream));
       }
-      if (prunable && k_lm_head_prune && !head_logits_) {
+      if (prunable && k_lm_head_prune && !store) {
         // nobody reads the logits: the exact argmax from the int8 pre-pass + a bf16 rescore of the candidate blocks
         g.out = nullptr; pa.g.out = nullptr;
         n_part = lm_head_rescore_groups(g, n_cu);
@@ -242,7 +249,7 @@ struct DecodeStep : StepView {
         // the argmax partials are the GEMM's epilogue (one per 64-column tile and row), and inside q3a_transcribe_batch /
         // q3a_run_resident nobody reads the logits: they are not stored (19 MB per step at 32 sequences)
         ep.part = part;
-        if (!head_logits_) ep.out = nullptr;
+        if (!store) ep.out = nullptr;
         n_part = (V + 63) / 64;
         timed(Q3A_KC_GEMM, wbytes, [&] { KCHK(launch_gemm16(s_ln.as<uint16_t>(), H, wh(L.lm_head), S, V, H, ep, false, stream)); });
       } else {
@@ -263,7 +270,26 @@ struct DecodeStep : StepView {
     f.done = done.as<uint8_t>(); f.n_done = n_done.as<int>(); f.n_seq = S; f.host_progress = host_prog_dev; f.embed = wh(L.embed); f.H = H; f.x_next = x_dec.as<float>(); f.eos0 = kEos0; f.eos1 = kEos1;
     f.cos_t = rope_cos.as<float>(); f.sin_t = rope_sin.as<float>(); f.rope_cur = rope_cur.as<float>();
     f.nn = first_layer_norm_out();
+    if (sample) enqueue_sampler(f);
     timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_finalize(f, S, stream)); });
+    if (sample && token_lp()) enqueue_sample_logprob();
+  }
+  // Sampling (k_sample.hip), around the finalize of run_head.  The head's partials are done with: the sampler writes its own noisy
+  // ones into the same buffers -- no log-sum channel, the drawn id is not the maximum -- and finalize merges those instead.
+  void enqueue_sampler(FinalizeArgs& f) {
+    SampleArgs sa{};
+    sa.logits = logits.as<float>(); sa.S = B; sa.V = d.vocab; sa.params = samp_params.as<uint32_t>(); sa.step_count = step_count.as<int>();
+    sa.chunk_max = samp_max.as<float>(); sa.chunk_sum = samp_sum.as<float>();
+    f.part.sum = nullptr; f.out_lp = nullptr; f.n_part = sample_chunks(d.vocab);
+    sa.part = f.part;
+    timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_sample(sa, stream)); });
+  }
+  // log_softmax(l')[id] of the drawn id, where the greedy step's log-probability would stand
+  void enqueue_sample_logprob() {
+    SampleLogprobArgs sl{};
+    sl.logits = logits.as<float>(); sl.S = B; sl.V = d.vocab; sl.chunk_max = samp_max.as<float>(); sl.chunk_sum = samp_sum.as<float>();
+    sl.next_tok = next_tok.as<int>(); sl.step_count = step_count.as<int>(); sl.out_lp = out_lp.as<float>(); sl.out_stride = max_new;
+    timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_sample_logprob(sl, stream)); });
   }
 
   // Skinny decode path in the default mode: every kernel that writes a row of the residual stream (token embedding,
@@ -583,11 +609,13 @@ struct q3a_engine {
   int beam_w_ = 0;           // > 0: beam mode, slots per utterance (part of the graph signature)
   bool logit_bias_on_ = false;  // q3a_set_logit_bias: step.logit_bias is applied by every head of the generation paths (graph signature)
   int logit_bias_finite_ = 0;   // its finite entries (the vocabulary while off): what a beam width is checked against
+  bool sampling_on_ = false;    // q3a_set_sampling: temperature > 0, the step draws its ids (k_sample.hip; graph signature)
+  uint32_t samp_words_[4] = {0, 0, 0, 0};  // what step.samp_params holds: temperature and min_p (fp32 bits), seed low / high
 
   // ---- the captured decode step: its buffers and launches, and all it sees of the members above ----
   DecodeStep step{StepView{d, L, opts, arena, arena_flags, stream, chain_streams, join_ev, fork_ev, n_cu, host_prog_dev, prof, taps, lm_q, lm_qs, lm_q_cols,
                            B, max_ctx, max_new, gsize, live_nsplit_, attn_nsplit, min_P_, part_stride, beam_w_, kv_layer_elems, head_logits_,
-                           k_parallel_groups, k_skinny_q, k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, logit_bias_on_}};
+                           k_parallel_groups, k_skinny_q, k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, logit_bias_on_, sampling_on_}};
 
   // (the mode rules are stated once, in StepView)
   bool precise() const { return step.precise(); }
@@ -657,6 +685,7 @@ struct q3a_engine {
       step.logit_bias.ensure((size_t)d.vocab * 4);
       HIPCHK(hipMemsetAsync(step.logit_bias.p, 0, (size_t)d.vocab * 4, stream));
       logit_bias_finite_ = d.vocab;
+      step.samp_params.ensure(16);  // (written by q3a_set_sampling, read only while sampling is on: engine set-up launches nothing for it)
     }
   }
 
@@ -1097,6 +1126,7 @@ struct q3a_engine {
     part_stride = std::max(128, (d.vocab + 3) / 4);  // >= blocks of the lm_head GEMV at 1 row per wave
     step.part_val.ensure((size_t)b * part_stride * 4); step.part_idx.ensure((size_t)b * part_stride * 4);
     if (token_lp()) { step.part_sum.ensure((size_t)b * part_stride * 4); step.out_lp.ensure((size_t)b * max_new * 4); }
+    if (sampling_on_) { step.samp_max.ensure((size_t)b * sample_chunks(d.vocab) * 4); step.samp_sum.ensure((size_t)b * sample_chunks(d.vocab) * 4); }
     {
       const size_t nblk4 = ((size_t)(d.vocab + 15) / 16 + 3) & ~size_t(3);  // lm_head_prune_blocks, rounded up for float4 reads
       step.blk_lo.ensure(nblk4 * 4); step.blk_hi.ensure(nblk4 * 4);
@@ -1410,8 +1440,8 @@ struct q3a_engine {
     });
     char buf[256];
     // (one field per latched knob, as latched: packing several into one integer let distinct settings collide -- ADVICE r5)
-    snprintf(buf, sizeof(buf), "%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.b%d.lb%d/%d/%d/%d/%p/%016llx", B, gsize, k_parallel_groups, k_skinny_q,
-             k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, (int)(min_P_ < 256), (int)head_logits_, (int)token_lp(), beam_w_, (int)logit_bias_on_, live_nsplit_,
+    snprintf(buf, sizeof(buf), "%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.b%d.lb%d.sm%d/%d/%d/%d/%p/%016llx", B, gsize, k_parallel_groups, k_skinny_q,
+             k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, (int)(min_P_ < 256), (int)head_logits_, (int)token_lp(), beam_w_, (int)logit_bias_on_, (int)sampling_on_, live_nsplit_,
              max_ctx, max_new, (const void*)arena, (unsigned long long)h);
     return buf;
   }
@@ -1636,6 +1666,25 @@ struct q3a_engine {
     logit_bias_on_ = on;
     logit_bias_finite_ = finite;
   }
+  // Sampling (q3asr.h q3a_set_sampling).  The setting lives in a device buffer the kernels read, so a new temperature, min_p or seed
+  // replays the same graph; on / off is part of the graph signature.  No decode state afterwards, as after q3a_set_logit_bias.
+  void set_sampling(float temperature, float min_p, uint64_t seed) {
+    const char* what = "q3a_set_sampling";
+    require_asr(what);
+    if (!(temperature >= 0.f) || !std::isfinite(temperature)) fail(std::string(what) + ": temperature must be finite and >= 0 (0 turns sampling off)");
+    if (!(min_p >= 0.f && min_p <= 1.f)) fail(std::string(what) + ": min_p must lie in [0, 1]");
+    uint32_t w[4];
+    memcpy(&w[0], &temperature, 4); memcpy(&w[1], &min_p, 4);
+    w[2] = (uint32_t)seed; w[3] = (uint32_t)(seed >> 32);
+    have_prefill = false; beam_w_ = 0;
+    HIPCHK(hipMemcpyAsync(step.samp_params.p, w, 16, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    memcpy(samp_words_, w, 16);
+    sampling_on_ = temperature > 0.f;
+  }
+  void beam_sampling_check(const char* what) const {
+    if (sampling_on_) fail(std::string(what) + ": sampling is on (q3a_set_sampling with temperature > 0); beam search selects deterministically -- turn it off first");
+  }
   void beam_bias_check(const char* what, int W) const {
     if (logit_bias_on_ && W > logit_bias_finite_)
       fail(std::string(what) + ": width " + std::to_string(W) + " exceeds the " + std::to_string(logit_bias_finite_) + " tokens the logit bias leaves finite");
@@ -1645,6 +1694,7 @@ struct q3a_engine {
   void beam_begin(const char* what, int W) {
     if (!have_prefill) fail(std::string(what) + ": no prefill state (call q3a_prefill first)");
     beam_check(what, W);
+    beam_sampling_check(what);
     beam_bias_check(what, W);
     if (!head_logits_ || pos_hi_ != *std::max_element(P.begin(), P.end()))
       fail(std::string(what) + ": needs the logits of q3a_prefill (call it directly after the prefill)");
@@ -2032,6 +2082,7 @@ int32_t q3a_beam_search_batch_ptrs(q3a_engine* e, const float* const* pcm16k, co
   if ((int64_t)U * width > 32) fail("q3a_beam_search_batch: utterances x width = " + std::to_string((int64_t)U * width) + " exceeds 32 sequences");
   const int cap = e->opts.max_new_tokens, want = max_new <= 0 ? cap : std::min(max_new, cap);
   if (stride < want) fail("q3a_beam_search_batch: stride " + std::to_string(stride) + " is below max_new " + std::to_string(want));
+  e->beam_sampling_check("q3a_beam_search_batch");
   e->beam_bias_check("q3a_beam_search_batch", width);
   e->fixed_mode_ = false;
   e->head_logits_ = true;  // every round selects on the stored logits
@@ -2057,6 +2108,14 @@ int32_t q3a_set_logit_bias(q3a_engine* e, const int32_t* ids, const float* bias,
   Q3A_TRY(e)
   HIPCHK(hipSetDevice(e->device));
   e->set_logit_bias(ids, bias, n, default_bias);
+  Q3A_CATCH(e)
+}
+
+int32_t q3a_set_sampling(q3a_engine* e, float temperature, float min_p, uint64_t seed) {
+  if (!e) return 1;
+  Q3A_TRY(e)
+  HIPCHK(hipSetDevice(e->device));
+  e->set_sampling(temperature, min_p, seed);
   Q3A_CATCH(e)
 }
 
@@ -2342,6 +2401,12 @@ int32_t q3a_debug_read(q3a_engine* e, const char* name, void* dst, uint64_t byte
   if (strcmp(name, "logit_bias") == 0) {
     e->require_asr("q3a_debug_read: logit_bias");
     give(e->step.logit_bias.p, (size_t)e->d.vocab * 4, true);
+    return 0;
+  }
+  if (strcmp(name, "sampling") == 0) {  // {on, temperature bits, min_p bits, seed low, seed high} as last set
+    e->require_asr("q3a_debug_read: sampling");
+    const uint32_t st[5] = {e->sampling_on_ ? 1u : 0u, e->samp_words_[0], e->samp_words_[1], e->samp_words_[2], e->samp_words_[3]};
+    give(st, 20, false);
     return 0;
   }
   if (strcmp(name, "logit_bias_stats") == 0) {

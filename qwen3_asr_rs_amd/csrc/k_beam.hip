@@ -58,11 +58,6 @@ __device__ __forceinline__ void wave_best(float& bv, int& bi) {
   }
 }
 
-__device__ __forceinline__ void lse_visit(ArgmaxAcc<true>& m, float v, int id) {
-  if (v > m.v) { m.s = lse_term(m.s, m.v, v) + 1.f; m.v = v; m.i = id; }
-  else m.s += lse_term(1.f, v, m.v);
-}
-
 template <int W, bool VEC>
 __global__ __launch_bounds__(256) void beam_topk_chunk_kernel(const float* __restrict__ logits, int V, int n_chunk,
                                                               float* __restrict__ cand_val, int* __restrict__ cand_idx,

@@ -438,4 +438,30 @@ struct KvReorderArgs {
 };
 const char* launch_kv_reorder(const KvReorderArgs& a, hipStream_t s);
 
+// ---- temperature sampling (k_sample.hip) -----------------------------------------------------------------------
+constexpr int SAMPLE_CHUNK = 2048;  // logits one workgroup of the sampler reads (8 per thread)
+inline int sample_chunks(int V) { return (V + SAMPLE_CHUNK - 1) / SAMPLE_CHUNK; }
+// Per row s of logits [S][V] (fp32, row stride V): with m the row maximum, the kept set { j : l_j >= m + T ln(min_p), l_j != -inf }
+// and z_j = l_j + T g_j, g_j the Gumbel noise of sample_word(seed, s, step_count[s], j) (sample_rng.h), ONE argmax partial per
+// 2048-logit chunk: the chunk's largest z and its id.  launch_argmax_finalize with n_part = sample_chunks(V) picks the row's id.
+// Two launches: the clean (max, sum exp) pair of every chunk, then the noisy partials.
+struct SampleArgs {
+  const float* logits; int S; int V;
+  const uint32_t* params;              // device [4]: temperature and min_p (fp32 bits), seed low and high word
+  const int* step_count;               // [S] the step t of each sequence (tokens it has generated so far)
+  float* chunk_max; float* chunk_sum;  // [S][sample_chunks(V)] (written)
+  ArgmaxPartials part;                 // (written) [S] rows x sample_chunks(V) partials, no log-sum channel
+};
+const char* launch_sample(const SampleArgs& a, hipStream_t s);
+// After launch_argmax_finalize: lp = (l_id - m) - log sum exp(l - m) of the id it chose (next_tok[s]), the sum merged in a fixed
+// order, written to out_lp[s][step_count[s] - 1] -- the entry finalize filled for this step; out_z[s] = the winning noisy score.
+struct SampleLogprobArgs {
+  const float* logits; int S; int V;
+  const float* chunk_max; const float* chunk_sum;  // of launch_sample
+  const int* next_tok; const int* step_count;      // [S] as finalize left them
+  float* out_lp; int out_stride;                   // nullable [S][out_stride]
+  ArgmaxPartials part; float* out_z;               // nullable [S] (selftest), with the partials of launch_sample
+};
+const char* launch_sample_logprob(const SampleLogprobArgs& a, hipStream_t s);
+
 }  // namespace q3a

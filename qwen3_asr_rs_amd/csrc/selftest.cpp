@@ -3,6 +3,7 @@
 #include <cstring>
 
 #include "engine_internal.h"
+#include "sample_rng.h"
 
 using namespace q3a;
 
@@ -229,6 +230,51 @@ int32_t q3a_selftest_kv_reorder(int32_t device, void* cache, int32_t elem_bytes,
   KCHK(launch_kv_reorder(r, nullptr));
   finish();
   to_host((uint8_t*)cache, dC, 2 * half);
+  Q3A_CATCH(nullptr)
+}
+
+uint32_t q3a_sample_word(uint64_t seed, uint32_t s, uint32_t t, uint32_t j) { return sample_word((uint32_t)seed, (uint32_t)(seed >> 32), s, t, j); }
+
+// the sampled step's tail as the engine enqueues it: launch_sample, argmax_finalize on its partials, launch_sample_logprob
+int32_t q3a_selftest_sample(int32_t device, const float* logits, int32_t S, int32_t V, float temperature, float min_p, uint64_t seed,
+                            int32_t step, int32_t* out_ids, float* out_lp, float* out_z) {
+  Q3A_TRY(nullptr)
+  if (!logits || S < 1 || V < 1 || step < 0 || step > (1 << 20)) fail("q3a_selftest_sample: bad argument");
+  if (!(temperature > 0.f) || !std::isfinite(temperature)) fail("q3a_selftest_sample: temperature must be finite and > 0");
+  if (!(min_p >= 0.f && min_p <= 1.f)) fail("q3a_selftest_sample: min_p must lie in [0, 1]");
+  use_device(device);
+  const size_t Sz = S, nc = sample_chunks(V), stride = (size_t)step + 1;
+  constexpr int H = 4;  // finalize embeds the chosen id: a token table of zeros, four columns wide
+  uint32_t w[4];
+  memcpy(&w[0], &temperature, 4); memcpy(&w[1], &min_p, 4);
+  w[2] = (uint32_t)seed; w[3] = (uint32_t)(seed >> 32);
+  const DevBuf dLg = to_device(logits, Sz * V), dPar = to_device(w, 4), dSc = to_device(std::vector<int>(Sz, step));
+  const DevBuf dCm = room(Sz * nc * 4), dCs = room(Sz * nc * 4), dPv = room(Sz * nc * 4), dPi = room(Sz * nc * 4);
+  const DevBuf dEmb = to_device(std::vector<uint16_t>((size_t)V * H, 0)), dX = room(Sz * H * 4), dTok = room(Sz * 4);
+  const DevBuf dIds = to_device(std::vector<int>(Sz * stride, -1)), dLp = to_device(std::vector<float>(Sz * stride, 0.f));
+  const DevBuf dPos = to_device(std::vector<int>(Sz, 0)), dDone = to_device(std::vector<uint8_t>(Sz, 0)), dZ = room(Sz * 4);
+  SampleArgs sa{};
+  sa.logits = dLg.as<float>(); sa.S = S; sa.V = V; sa.params = dPar.as<uint32_t>(); sa.step_count = dSc.as<int>();
+  sa.chunk_max = dCm.as<float>(); sa.chunk_sum = dCs.as<float>();
+  sa.part = ArgmaxPartials{dPv.as<float>(), dPi.as<int>(), nullptr, (int)nc};
+  KCHK(launch_sample(sa, nullptr));
+  FinalizeArgs f{};
+  f.part = sa.part; f.n_part = (int)nc; f.V = V; f.next_tok = dTok.as<int>(); f.out_ids = dIds.as<int>(); f.out_stride = (int)stride;
+  f.step_count = dSc.as<int>(); f.pos = dPos.as<int>(); f.advance = 1; f.done = dDone.as<uint8_t>(); f.n_seq = S;
+  f.embed = dEmb.as<uint16_t>(); f.H = H; f.x_next = dX.as<float>(); f.eos0 = kEos0; f.eos1 = kEos1;
+  KCHK(launch_argmax_finalize(f, S, nullptr));
+  SampleLogprobArgs sl{};
+  sl.logits = sa.logits; sl.S = S; sl.V = V; sl.chunk_max = sa.chunk_max; sl.chunk_sum = sa.chunk_sum; sl.next_tok = f.next_tok;
+  sl.step_count = f.step_count; sl.out_lp = dLp.as<float>(); sl.out_stride = (int)stride; sl.part = sa.part; sl.out_z = dZ.as<float>();
+  KCHK(launch_sample_logprob(sl, nullptr));
+  finish();
+  const std::vector<int> ids = to_host<int>(dIds, Sz * stride);
+  const std::vector<float> lp = to_host<float>(dLp, Sz * stride);
+  for (size_t s = 0; s < Sz; ++s) {
+    if (out_ids) out_ids[s] = ids[s * stride + step];
+    if (out_lp) out_lp[s] = lp[s * stride + step];
+  }
+  if (out_z) to_host(out_z, dZ, Sz);
   Q3A_CATCH(nullptr)
 }
 

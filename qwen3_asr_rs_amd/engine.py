@@ -12,7 +12,9 @@ This module holds no arithmetic: every number is produced by the HIP kernels beh
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
+import zlib
 from dataclasses import dataclass
 from typing import Iterable, List, Mapping, Optional, Sequence, Tuple
 
@@ -76,6 +78,53 @@ def compose_logit_bias(vocab: int, suppress_tokens: Optional[Iterable[int]] = No
     return np.asarray(ids, dtype=np.int32), np.asarray([table[t] for t in ids], dtype=np.float32), float(default)
 
 
+def check_sampling_args(temperature: float, min_p: float = 0.0, seed: int = 0) -> Tuple[float, float, int]:
+    """The refusals of q3a_set_sampling that need no engine (pure host function): temperature finite and >= 0 (0 = off), min_p in
+    [0, 1], seed an unsigned 64-bit integer.  Returns the three as the C call takes them."""
+    try:
+        t, p = float(temperature), float(min_p)
+    except (TypeError, ValueError):
+        raise Q3aError("set_sampling: temperature and min_p must be numbers")
+    if not (math.isfinite(t) and t >= 0.0):
+        raise Q3aError(f"set_sampling: temperature must be finite and >= 0 (0 turns sampling off), got {temperature!r}")
+    if not (0.0 <= p <= 1.0):
+        raise Q3aError(f"set_sampling: min_p must lie in [0, 1], got {min_p!r}")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not (0 <= int(seed) < 1 << 64):
+        raise Q3aError(f"set_sampling: seed must be an integer in [0, 2^64), got {seed!r}")
+    return t, p, int(seed)
+
+
+def compression_ratio(text: str) -> float:
+    """len(utf8) / len(zlib.compress(utf8)): Whisper's measure of a repetition loop (a looping transcript compresses well)."""
+    raw = text.encode("utf-8")
+    return len(raw) / len(zlib.compress(raw))
+
+
+def attempt_acceptable(text: str, avg_logprob: Optional[float], logprob_threshold: float = -1.0,
+                       compression_ratio_threshold: float = 2.4) -> bool:
+    """The fallback's acceptance rule: avg_logprob >= logprob_threshold (an attempt without tokens has none and passes this half) and
+    compression_ratio(text) <= compression_ratio_threshold."""
+    if avg_logprob is not None and not (avg_logprob >= logprob_threshold):
+        return False
+    return compression_ratio(text) <= compression_ratio_threshold
+
+
+def temperature_fallback(attempt, temperatures: Sequence[float], seed: int = 0, logprob_threshold: float = -1.0,
+                         compression_ratio_threshold: float = 2.4):
+    """Whisper's temperature fallback as a pure function: attempt(temperature, seed + k) for k = 0, 1, ... must return an object with
+    .text and .avg_logprob; the first acceptable attempt (attempt_acceptable) is returned, the last one when none is.  Returns
+    (result, temperature used, number of attempts made)."""
+    temps = [float(t) for t in temperatures]
+    if not temps:
+        raise Q3aError("temperature_fallback: no temperature given")
+    res = None
+    for k, t in enumerate(temps):
+        res = attempt(t, int(seed) + k)
+        if attempt_acceptable(res.text, res.avg_logprob, logprob_threshold, compression_ratio_threshold):
+            return res, t, k + 1
+    return res, temps[-1], len(temps)
+
+
 def parse_logit_bias(text: Optional[str] = None, suppress_list: Optional[str] = None):
     """q3a_parse_logit_bias: "id bias" / "lo-hi bias" lines ('#' comments, "-inf") and a comma list "id,lo-hi,..." of ids to
     suppress -> (ids int32, bias float32).  Host only."""
@@ -125,6 +174,7 @@ class HipEngine:
         self._n_frames: List[int] = []
         self._T: List[int] = []
         self.logit_bias_state: Tuple[Optional[dict], float] = (None, 0.0)  # what set_logit_bias was last given
+        self.sampling_state: Tuple[float, float, int] = (0.0, 0.0, 0)  # what set_sampling was last given
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -408,6 +458,20 @@ class HipEngine:
         st = self.debug_read_raw("logit_bias_stats").view(np.int32)
         return {"active": bool(st[0]), "finite": int(st[1])}
 
+    # ---- sampling ---------------------------------------------------------------------------------------
+    def set_sampling(self, temperature: float, min_p: float = 0.0, seed: int = 0):
+        """q3a_set_sampling: with temperature > 0 every generation step draws its id from softmax(logits / temperature) restricted to
+        the min-p kept set, on the device, reproducibly from `seed`; 0 turns it off.  Drops the decode state: prefill again before a
+        stage-API step.  The noise depends on a sequence's index in the call, so a clip alone and inside a batch draw differently."""
+        t, p, sd = check_sampling_args(temperature, min_p, seed)
+        self._chk(self._lib.q3a_set_sampling(self._h, C.c_float(t), C.c_float(p), C.c_uint64(sd)))
+        self.sampling_state = (t, p, sd)
+
+    def sampling_stats(self) -> dict:
+        st = self.debug_read_raw("sampling").view(np.uint32)
+        return {"active": bool(st[0]), "temperature": float(st[1:2].view(np.float32)[0]), "min_p": float(st[2:3].view(np.float32)[0]),
+                "seed": int(st[3]) | (int(st[4]) << 32)}
+
     # ---- beam search ----------------------------------------------------------------------------------
     def _beam_unpack(self, U, W, stride, ids, lens, scores, fin, lp) -> "List[List[BeamHypothesis]]":
         res = []
@@ -621,6 +685,7 @@ class TranscribeResult:
     token_logprobs: Optional[List[float]] = None
     avg_logprob: Optional[float] = None
     alternatives: Optional[List[Alternative]] = None  # beam_size > 1: the n-best list, best first (this result is its first entry)
+    temperature: Optional[float] = None  # transcribe(temperature=...): the temperature of the attempt that was kept (0.0 = greedy)
 
 
 @dataclass
@@ -654,19 +719,50 @@ class AsrInference:
 
     def transcribe(self, audio, language: Optional[str] = None, max_new_tokens: int = 4096, beam_size: int = 1,
                    length_penalty: float = 0.0, suppress_tokens: Optional[Iterable[int]] = None,
-                   logit_bias: Optional[Mapping[int, float]] = None, allowed_tokens: Optional[Iterable[int]] = None) -> TranscribeResult:
+                   logit_bias: Optional[Mapping[int, float]] = None, allowed_tokens: Optional[Iterable[int]] = None,
+                   temperature=0.0, min_p: float = 0.0, seed: int = 0, logprob_threshold: float = -1.0,
+                   compression_ratio_threshold: float = 2.4) -> TranscribeResult:
         """src/inference.rs:89-213.  `audio`: path to a WAV file or a 16 kHz float32 array.  beam_size > 1: a beam search of that
         width instead of the greedy loop; `alternatives` holds its hypotheses ordered by score / max(len, 1) ** length_penalty
         (float64 on the host; 0: the search's own order) and the result is the first of them.
         suppress_tokens / logit_bias / allowed_tokens (compose_logit_bias): constrain this call -- the engine's logit bias is set for
-        it and whatever was set before is restored afterwards; composes with beam_size."""
+        it and whatever was set before is restored afterwards; composes with beam_size.
+        temperature: a number > 0 samples this call at that temperature (HipEngine.set_sampling with min_p and seed; the engine's
+        own setting is restored afterwards); the default 0.0 leaves the engine as it is.  A tuple such as (0.0, 0.2, 0.4, 0.6, 0.8,
+        1.0) is Whisper's fallback (temperature_fallback): attempt k runs at temperatures[k] with seed + k, the first attempt with
+        avg_logprob >= logprob_threshold and compression ratio <= compression_ratio_threshold is kept, else the last; it needs an
+        engine created with token_logprobs=True.  The result's `temperature` is the one that was used.  Not with beam_size > 1."""
+        fallback = isinstance(temperature, (tuple, list))
+        temps = [float(t) for t in temperature] if fallback else [float(temperature)]
+        for t in temps:
+            check_sampling_args(t, min_p, seed)
+        if fallback and not self.engine.token_logprobs:
+            raise Q3aError("transcribe: a tuple of temperatures (fallback) decides on avg_logprob: create the engine with token_logprobs=True")
+        if beam_size > 1 and any(t > 0.0 for t in temps):
+            raise Q3aError("transcribe: beam search does not sample (beam_size > 1 with a temperature > 0)")
+        run = lambda: self._transcribe(audio, language, max_new_tokens, beam_size, length_penalty)
+        if fallback or temps[0] > 0.0:
+            plain, eng = run, self.engine
+
+            def attempt(t, sd):
+                eng.set_sampling(t, min_p, sd)
+                res = plain()
+                res.temperature = t
+                return res
+
+            def run():
+                before = eng.sampling_state
+                try:
+                    return temperature_fallback(attempt, temps, seed, logprob_threshold, compression_ratio_threshold)[0]
+                finally:
+                    eng.set_sampling(*before)
         if suppress_tokens is None and logit_bias is None and allowed_tokens is None:
-            return self._transcribe(audio, language, max_new_tokens, beam_size, length_penalty)
+            return run()
         ids, bias, default = compose_logit_bias(self.engine.dims.vocab_size, suppress_tokens, logit_bias, allowed_tokens)
         before = self.engine.logit_bias_state
         self.engine.set_logit_bias(dict(zip(ids.tolist(), bias.tolist())), default)
         try:
-            return self._transcribe(audio, language, max_new_tokens, beam_size, length_penalty)
+            return run()
         finally:
             self.engine.set_logit_bias(*before)
 
