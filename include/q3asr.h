@@ -245,7 +245,8 @@ int32_t q3a_measure_peaks(int32_t device, int32_t reps, q3a_peaks* out);
  * of the pruned one-sequence argmax, written next to the stored logits).  "lm_head_prune_stats" (int32[2]: 16-row blocks rescored
  * by the pruned argmax, its launches; cumulative over the engine's life) and "device_bytes" (uint64: bytes of device memory the
  * workspace buffers of ALL engines of the process hold right now -- tables, activations, KV caches, the int8 lm_head copy, taps; not
- * the weight arenas) are readable without debug taps. */
+ * the weight arenas) and "graph_captures" (int32: decode-step graphs captured over the engine's life; a replay adds none) are readable
+ * without debug taps; so are the settings "logit_bias", "logit_bias_stats", "sampling" and "repetition" (their own sections below). */
 int32_t q3a_debug_read(q3a_engine* e, const char* name, void* dst, uint64_t bytes, uint64_t* actual);
 
 /* ---- pipeline shell: host-only helpers around the hot path -------------- */
@@ -438,8 +439,9 @@ int32_t q3a_selftest_kv_reorder(int32_t device, void* cache, int32_t elem_bytes,
  * entries.
  * Readable without debug taps: q3a_debug_read(e, "logit_bias", ..) (fp32 [vocab] as the device holds it, zeros when off) and
  * "logit_bias_stats" (int32 [2]: active 0 / 1, finite entries).
- * Out of scope: per-utterance biases inside one batch (a [S][vocab] operand: 19 MB per step at 32 sequences); history-dependent
- * processors (no-repeat n-gram, repetition penalty); multi-token phrase constraints; a bias inside q3a_score*.  (Sampling: its own section below.) */
+ * Out of scope: per-utterance biases inside one batch (a [S][vocab] operand: 19 MB per step at 32 sequences); multi-token phrase
+ * constraints; a bias inside q3a_score*.  (Sampling, and the history-dependent processors -- repetition penalty, no-repeat n-gram:
+ * their own sections below.) */
 
 /* b = default_bias everywhere (0 or -INFINITY only), then b[ids[i]] = bias[i].  n = 0 with default_bias = 0 clears the bias: the
  * engine is back on the launches, ids and log-probabilities of an engine that never had one, bit for bit.  An allow-list is
@@ -486,6 +488,46 @@ uint32_t q3a_sample_word(uint64_t seed, uint32_t s, uint32_t t, uint32_t j);
  * (log_softmax(l)[id]) and out_z [S] (the winning noisy score z_id); any may be null.  temperature > 0. */
 int32_t q3a_selftest_sample(int32_t device, const float* logits, int32_t S, int32_t V, float temperature, float min_p,
                             uint64_t seed, int32_t step, int32_t* out_ids, float* out_lp, float* out_z);
+
+/* ---- repetition: a repetition penalty and a no-repeat n-gram ban inside the decode step ------------------------------------------------
+ * The two history-dependent logits processors every generate() user reaches for, applied on the device to the stored logits of every
+ * step of the GENERATION paths, between the lm_head and the choice of the id.  l' are the (biased) fp32 logits of sequence s at a step.
+ *   History.  t = min(step_count[s], max_new), h = out_ids[s][0 .. t): exactly the ids q3a_fetch_ids would return so far, a stored EOS
+ *     included when fixed_new_tokens runs past it.  The prompt (audio pads and a chat template) is not history.  A token forced with
+ *     q3a_set_next_tokens is not history either: it replaces the next step's input, not out_ids.
+ *   Penalty p.  For every distinct id j in h: l''_j = l'_j / p if l'_j > 0, else l'_j * p -- one correctly rounded fp32 operation.  An id
+ *     that occurred k times is penalised once; -inf stays -inf and 0 stays 0.
+ *   No-repeat n-gram n >= 1.  Only when t >= n - 1: for every i in [0, t - n + 1) with h[i + k] == h[t - n + 1 + k] for all k in
+ *     [0, n - 1), l''_{h[i + n - 1]} = -inf.  n = 1 bans every id already emitted.  The ban is applied after the penalty and wins.
+ *   Pinned meaning: bit for bit what HuggingFace's RepetitionPenaltyLogitsProcessor followed by NoRepeatNGramLogitsProcessor compute on
+ *     input_ids = h.
+ *   Everything downstream is defined on l'' by the rules it already has: the greedy id is argmax l'' (larger value, then smaller id);
+ *     sampling draws from l'' (kept set, noise and Gumbel-max unchanged); token log-probabilities are log_softmax(l'')[id]; logits_out
+ *     of q3a_prefill / q3a_decode_step and the "logits" tap hold l''.  At t = 0 (the id the prefill produces) both are the identity.
+ * repetition_penalty == 1 and no_repeat_ngram_size == 0 is off: the engine is back on the launches, graphs, ids, log-probabilities
+ * and pruned-pass counts of one that never had the setting.
+ * State: the setting persists until changed.  q3a_set_repetition drops the decode state as q3a_set_sampling does.  On / off is part of
+ * the captured step's signature; p and n live in a 16-byte device buffer the kernel reads, so another setting replays the same graph.
+ * Applies to: q3a_prefill (next_ids, last_logits_out), q3a_decode_step, q3a_run_resident, q3a_transcribe_batch[_ptrs],
+ * q3a_fetch_logprobs.  While it is on, every lm_head form stores its logits and the one-sequence pruned argmax is not taken.
+ * Group runs: set it on each q3a_group_engine handle.  q3a_score* and q3a_align* never see it: bit-identical with it on and off.
+ * Refused (q3a_last_error): a repetition_penalty that is not finite or <= 0; no_repeat_ngram_size < 0 or > 32; an aligner engine;
+ * q3a_beam_begin / q3a_beam_search_batch_ptrs while it is on (beam slots reorder their histories); a vocabulary above the 262144 ids
+ * the kernel's bitmap holds (151936 fits); no_repeat_ngram_size > 0 together with a logit bias that leaves both EOS ids at -inf and no
+ * more finite entries than max_new_tokens -- the only way a row could run out of finite logits -- refused by whichever of
+ * q3a_set_repetition / q3a_set_logit_bias comes second.  (Not refused: with fixed_new_tokens running past a stored EOS the EOS id is
+ * history like any other, so an n-gram ban over a small allow-list with an EOS id open can still empty a row AFTER the sequence's EOS;
+ * the ids and log-probabilities (NaN) of a sequence behind its EOS are unspecified in that combination, those up to it are not touched.)
+ * Readable: q3a_debug_read(e, "repetition", ..) (uint32 [3]: on 0 / 1, repetition_penalty as fp32 bits, no_repeat_ngram_size).
+ * Out of scope: penalties over the prompt; frequency / presence penalties; a history window; repetition control inside beam search;
+ * keeping the one-sequence pruned argmax under it (exact only for p >= 1, and it would need a device-side branch when the pruned
+ * winner is a seen id). */
+int32_t q3a_set_repetition(q3a_engine* e, float repetition_penalty, int32_t no_repeat_ngram_size);
+/* The kernel on its own (no model), followed by the argmax partials and their merge as the engine enqueues them: logits [S][V] host
+ * fp32, hist [S][stride] with lens [S] ids of history each (0 <= lens[s] <= stride, every id inside the vocabulary) -> out_logits
+ * [S][V] (l''), out_ids [S] (argmax l'') and out_lp [S] (log_softmax(l'')[id]); any of the three may be null. */
+int32_t q3a_selftest_repeat(int32_t device, const float* logits, int32_t S, int32_t V, const int32_t* hist, int32_t stride,
+                            const int32_t* lens, float p, int32_t n, float* out_logits, int32_t* out_ids, float* out_lp);
 
 /* A/B knobs for kernel experiments (process-wide atomics, read from the environment once; not part of the reference
  * interface).  The knobs that shape the decode step are latched per batch at the next prefill and are part of the captured

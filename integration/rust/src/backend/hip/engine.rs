@@ -73,6 +73,10 @@ extern "C" {
     pub fn q3a_parse_logit_bias(text: *const c_char, suppress_list: *const c_char, ids: *mut i32, bias: *mut f32, cap: i32, n: *mut i32) -> i32;
     pub fn q3a_set_sampling(e: *mut q3a_engine, temperature: f32, min_p: f32, seed: u64) -> i32;
     pub fn q3a_sample_word(seed: u64, s: u32, t: u32, j: u32) -> u32;
+    // repetition penalty and no-repeat n-grams on the sequence's own generated ids (include/q3asr.h "repetition")
+    pub fn q3a_set_repetition(e: *mut q3a_engine, repetition_penalty: f32, no_repeat_ngram_size: i32) -> i32;
+    pub fn q3a_selftest_repeat(device: i32, logits: *const f32, s: i32, v: i32, hist: *const i32, stride: i32, lens: *const i32, p: f32, n: i32,
+                               out_logits: *mut f32, out_ids: *mut i32, out_lp: *mut f32) -> i32;
     // beam search: n-best hypotheses with scores, selected on the device (include/q3asr.h "beam search")
     pub fn q3a_beam_search_batch_ptrs(e: *mut q3a_engine, pcm16k: *const *const f32, n_samples: *const i64, u: i32,
                                       lang_prefix_ids: *const i32, n_prefix: i32, width: i32, max_new: i32, out_ids: *mut i32, stride: i32,
@@ -140,6 +144,14 @@ impl HipEngine {
         };
         if rc != 0 { bail!("{}", msg(unsafe { q3a_last_error(self.raw) })); }
         Ok((0..b).map(|i| ids[i * max_new..i * max_new + lens[i] as usize].iter().map(|&x| x as i64).collect()).collect())
+    }
+
+    /// Repetition control for every later generation call: `repetition_penalty` (1.0: none) over the ids a sequence has generated,
+    /// then a ban on every id that would repeat an n-gram of `no_repeat_ngram_size` ids (0: none).  (1.0, 0) turns it off.
+    pub fn set_repetition(&self, repetition_penalty: f32, no_repeat_ngram_size: usize) -> Result<()> {
+        let rc = unsafe { q3a_set_repetition(self.raw, repetition_penalty, no_repeat_ngram_size as i32) };
+        if rc != 0 { bail!("{}", msg(unsafe { q3a_last_error(self.raw) })); }
+        Ok(())
     }
 }
 

@@ -25,6 +25,7 @@ SYMBOLS = [
     "q3a_beam_search_batch_ptrs", "q3a_beam_begin", "q3a_beam_step", "q3a_beam_fetch", "q3a_selftest_beam_topk", "q3a_selftest_beam_advance",
     "q3a_selftest_kv_reorder", "q3a_set_logit_bias", "q3a_parse_logit_bias",
     "q3a_set_sampling", "q3a_sample_word", "q3a_selftest_sample",
+    "q3a_set_repetition", "q3a_selftest_repeat",
     "q3a_selftest_gemm_launch", "q3a_selftest_qkrope_launch", "q3a_gemm256_split_rows",
 ]
 
@@ -156,6 +157,8 @@ def load() -> C.CDLL:
         "q3a_set_sampling": (i32, [P, C.c_float, C.c_float, u64]),
         "q3a_sample_word": (C.c_uint32, [u64, C.c_uint32, C.c_uint32, C.c_uint32]),
         "q3a_selftest_sample": (i32, [i32, f32p, i32, i32, C.c_float, C.c_float, u64, i32, i32p, f32p, f32p]),
+        "q3a_set_repetition": (i32, [P, C.c_float, i32]),
+        "q3a_selftest_repeat": (i32, [i32, f32p, i32, i32, i32p, i32, i32p, C.c_float, i32, f32p, i32p, f32p]),
         "q3a_selftest_gemm_launch": (i32, [i32, i32, i32, P, P, i32, i32, i32, i32, i32, i32, i32, i32, i32, P, P, i32, P, P, i32, P, i32]),
         "q3a_selftest_qkrope_launch": (i32, [i32, i32, i32, P, i32, P, i32, i32, P, P, P, P, P, P, C.c_float, P, P, i32, i32, i32, i32, i32, P, P, P]),
         "q3a_gemm256_split_rows": (i32, [i32, i32]),

@@ -17,6 +17,8 @@
 // Q3A_SCORE_TEXT score does not; without them nothing changes.
 // Q3A_TEMPERATURE=<T> [Q3A_MIN_P=<p>] [Q3A_SEED=<n>] samples the transcription at ONE temperature (q3a_set_sampling; min_p 0 and seed
 // 0 when absent); a Q3A_BEAM search is then refused by the engine.  There is no temperature fallback here (no zlib).
+// Q3A_REPETITION_PENALTY=<p> and / or Q3A_NO_REPEAT_NGRAM=<n> run the transcription under q3a_set_repetition (1 and 0 when absent); a
+// Q3A_BEAM search is then refused by the engine, a Q3A_SCORE_TEXT score never sees it.
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -82,6 +84,28 @@ static int set_sampling_from_env(q3a_engine* eng) {
   }
   if (q3a_set_sampling(eng, temperature, min_p, (uint64_t)seed) != 0) return die(std::string("Sampling failed: ") + q3a_last_error(eng));
   logf(1, "Sampling: temperature %s", t);
+  return 0;
+}
+
+// Q3A_REPETITION_PENALTY / Q3A_NO_REPEAT_NGRAM: the engine's repetition setting, set before anything is generated
+static int set_repetition_from_env(q3a_engine* eng) {
+  const char *p = getenv("Q3A_REPETITION_PENALTY"), *n = getenv("Q3A_NO_REPEAT_NGRAM");
+  const bool have_p = p && *p, have_n = n && *n;
+  if (!have_p && !have_n) return 0;
+  char* end = nullptr;
+  float penalty = 1.f;
+  if (have_p) {
+    penalty = strtof(p, &end);
+    if (end == p || *end) return die(std::string("Repetition control failed: Q3A_REPETITION_PENALTY is not a number: ") + p);
+  }
+  long ngram = 0;
+  if (have_n) {
+    ngram = strtol(n, &end, 10);
+    if (end == n || *end || ngram < -1000 || ngram > 1000) return die(std::string("Repetition control failed: Q3A_NO_REPEAT_NGRAM is not an integer: ") + n);
+  }
+  if (q3a_set_repetition(eng, penalty, (int32_t)ngram) != 0) return die(std::string("Repetition control failed: ") + q3a_last_error(eng));
+  logf(1, "Repetition control: penalty %s", have_p ? p : "1");
+  logf(1, "Repetition control: no-repeat n-gram %s", have_n ? n : "0");
   return 0;
 }
 
@@ -238,6 +262,7 @@ int main(int argc, char** argv) {
     logf(0, "warning: the checkpoint stores F16/F32 matrices; the HIP backend keeps matrices as bf16 (rounded to nearest-even)");
   if (set_logit_bias_from_env(eng) != 0) return 1;
   if (set_sampling_from_env(eng) != 0) return 1;
+  if (set_repetition_from_env(eng) != 0) return 1;
   logf(1, "Loading tokenizer...");
   q3a_tokenizer* tok = nullptr;
   const std::string tj = std::string(model_path) + "/tokenizer.json";

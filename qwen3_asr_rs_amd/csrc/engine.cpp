@@ -129,6 +129,7 @@ struct StepView {
   const int &k_parallel_groups, &k_skinny_q, &k_dattn_batched_min_wgs, &k_skinny_glu_hp3, &k_lm_head_prune;  // knobs as latched per batch
   const bool& logit_bias_on_;  // q3a_set_logit_bias: a bias is set (changes only while the engine holds no decode state)
   const bool& sampling_on_;    // q3a_set_sampling: temperature > 0 (likewise)
+  const bool& repetition_on_;  // q3a_set_repetition: a penalty != 1 or an n-gram size > 0 (likewise)
 
   bool precise() const { return opts.precise != 0; }
   bool token_lp() const { return opts.token_logprobs != 0; }
@@ -159,6 +160,7 @@ struct DecodeStep : StepView {
   // q3a_set_sampling: {temperature, min_p, seed low, seed high} as the sampler's kernels read them (a new setting needs no new graph),
   // and the clean (max, sum exp) pair of every 2048-logit chunk of every row [B][sample_chunks(vocab)]
   DevBuf samp_params, samp_max, samp_sum;
+  DevBuf rep_params;  // q3a_set_repetition: {penalty (fp32 bits), n-gram size, 0, 0} as repeat_apply_kernel reads them (a new setting needs no new graph)
   // f(buffer) for every DevBuf declared above, in declaration order (s: a DecodeStep, const or not).  The declarations of this
   // struct ARE the guarded set: tests/test_host.py::test_step_buffers_cover_the_captured_step compares this list with them.
   template <class Self, class F> static void each_buf(Self& s, F&& f) {
@@ -167,7 +169,7 @@ struct DecodeStep : StepView {
                     &s.rope_cur, &s.rope_cos, &s.rope_sin, &s.n_done, &s.forced_tok,
                     &s.beam_cand_val, &s.beam_cand_idx, &s.beam_part_max, &s.beam_part_sum, &s.beam_topk_ids, &s.beam_topk_lp, &s.beam_score, &s.beam_finished,
                     &s.beam_parent, &s.beam_token, &s.beam_feed, &s.beam_hist_parent, &s.beam_hist_token, &s.beam_hist_lp, &s.beam_state, &s.beam_lo,
-                    &s.logit_bias, &s.samp_params, &s.samp_max, &s.samp_sum})
+                    &s.logit_bias, &s.samp_params, &s.samp_max, &s.samp_sum, &s.rep_params})
       f(*b);
   }
 
@@ -200,13 +202,15 @@ struct DecodeStep : StepView {
 
   // final norm + lm_head on x_dec -> logits (+ block argmax partials), then argmax/finalize.  While sampling is on every form
   // stores its logits (as with head_logits_), the sampler (k_sample.hip) replaces the head's partials with its own noisy ones, and
-  // finalize runs on those unchanged.  With a logit bias every form below
+  // finalize runs on those unchanged.  While q3a_set_repetition is on every form stores its logits too, repeat_apply_kernel
+  // (k_repeat.hip) rewrites the stored rows in place (l' -> l''), and fresh partials over l'' (or the sampler) replace the head's.
+  // With a logit bias every form below
   // works on l' = l + b: the GEMV heads and both passes of the pruned argmax through GemvArgs::bias, the gemm16 forms through
   // GemmEpilogue::bias (in front of the argmax epilogue and of the stored logits), the precise batched form through batched_proj.
   void run_head(int advance) {
     const int S = B, H = d.hidden, V = d.vocab;
     const float* const hb = head_bias();
-    const bool sample = sampling_on_, store = head_logits_ || sample;
+    const bool sample = sampling_on_, repeat = repetition_on_, store = head_logits_ || sample || repeat;
     tap("head_in", x_dec.p, (size_t)S * H * 4);  // (debug taps) last-layer residual rows the final norm + lm_head read
     const double wbytes = 2.0 * V * H;
     int n_part = 0;
@@ -255,14 +259,15 @@ struct DecodeStep : StepView {
       } else {
         timed(Q3A_KC_GEMM, wbytes, [&] { KCHK(launch_gemm16(s_ln.as<uint16_t>(), H, wh(L.lm_head), S, V, H, ep, false, stream)); });
         n_part = 128;
-        timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_partials(logits.as<float>(), V, S, part, n_part, stream)); });
+        if (!repeat) timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_partials(logits.as<float>(), V, S, part, n_part, stream)); });
       }
     } else {
       timed(Q3A_KC_NORM, 0, [&] { KCHK(launch_rmsnorm(x_dec.as<float>(), wf(L.final_norm), s_ln.as<float>(), S, H, d.rms_eps, stream)); });
       timed(Q3A_KC_GEMM, wbytes, [&] { batched_proj(s_ln.as<float>(), H, wh(L.lm_head), V, H, hb, 0, logits.as<float>(), V, nullptr); });
       n_part = 128;
-      timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_partials(logits.as<float>(), V, S, part, n_part, stream)); });
+      if (!repeat) timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_partials(logits.as<float>(), V, S, part, n_part, stream)); });
     }
+    if (repeat) n_part = enqueue_repetition(part, !sample);
     FinalizeArgs f{};
     f.part = part; f.n_part = n_part; f.out_lp = part.sum ? out_lp.as<float>() : nullptr;
     f.V = V; f.next_tok = next_tok.as<int>(); f.out_ids = out_ids.as<int>();
@@ -273,6 +278,18 @@ struct DecodeStep : StepView {
     if (sample) enqueue_sampler(f);
     timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_finalize(f, S, stream)); });
     if (sample && token_lp()) enqueue_sample_logprob();
+  }
+  // Repetition penalty and no-repeat n-grams (k_repeat.hip): the stored rows, in place, from each sequence's own out_ids
+  // (l' -> l'').  The head's partials, where it wrote any, are those of l': with `partials` the rewritten rows' own, log-sum channel
+  // included, take their place (the sampler writes its own instead).  Returns the partials per row finalize then merges.
+  int enqueue_repetition(const ArgmaxPartials& part, bool partials) {
+    RepeatArgs ra{};
+    ra.logits = logits.as<float>(); ra.S = B; ra.V = d.vocab; ra.params = rep_params.as<uint32_t>();
+    ra.out_ids = out_ids.as<int>(); ra.out_stride = max_new; ra.step_count = step_count.as<int>();
+    timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_repeat_apply(ra, stream)); });
+    constexpr int kRepeatParts = 128;
+    if (partials) timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_partials(ra.logits, ra.V, ra.S, part, kRepeatParts, stream)); });
+    return kRepeatParts;
   }
   // Sampling (k_sample.hip), around the finalize of run_head.  The head's partials are done with: the sampler writes its own noisy
   // ones into the same buffers -- no log-sum channel, the drawn id is not the maximum -- and finalize merges those instead.
@@ -611,11 +628,15 @@ struct q3a_engine {
   int logit_bias_finite_ = 0;   // its finite entries (the vocabulary while off): what a beam width is checked against
   bool sampling_on_ = false;    // q3a_set_sampling: temperature > 0, the step draws its ids (k_sample.hip; graph signature)
   uint32_t samp_words_[4] = {0, 0, 0, 0};  // what step.samp_params holds: temperature and min_p (fp32 bits), seed low / high
+  bool logit_bias_eos_open_ = true;  // the logit bias leaves an EOS id finite (true while off): a sequence can always stop
+  bool repetition_on_ = false;       // q3a_set_repetition: penalty != 1 or n-gram size > 0 (k_repeat.hip; graph signature)
+  float rep_penalty_ = 1.f;          // what step.rep_params holds
+  int rep_ngram_ = 0;
 
   // ---- the captured decode step: its buffers and launches, and all it sees of the members above ----
   DecodeStep step{StepView{d, L, opts, arena, arena_flags, stream, chain_streams, join_ev, fork_ev, n_cu, host_prog_dev, prof, taps, lm_q, lm_qs, lm_q_cols,
                            B, max_ctx, max_new, gsize, live_nsplit_, attn_nsplit, min_P_, part_stride, beam_w_, kv_layer_elems, head_logits_,
-                           k_parallel_groups, k_skinny_q, k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, logit_bias_on_, sampling_on_}};
+                           k_parallel_groups, k_skinny_q, k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, logit_bias_on_, sampling_on_, repetition_on_}};
 
   // (the mode rules are stated once, in StepView)
   bool precise() const { return step.precise(); }
@@ -686,6 +707,7 @@ struct q3a_engine {
       HIPCHK(hipMemsetAsync(step.logit_bias.p, 0, (size_t)d.vocab * 4, stream));
       logit_bias_finite_ = d.vocab;
       step.samp_params.ensure(16);  // (written by q3a_set_sampling, read only while sampling is on: engine set-up launches nothing for it)
+      step.rep_params.ensure(16);   // (likewise: q3a_set_repetition)
     }
   }
 
@@ -1440,8 +1462,8 @@ struct q3a_engine {
     });
     char buf[256];
     // (one field per latched knob, as latched: packing several into one integer let distinct settings collide -- ADVICE r5)
-    snprintf(buf, sizeof(buf), "%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.b%d.lb%d.sm%d/%d/%d/%d/%p/%016llx", B, gsize, k_parallel_groups, k_skinny_q,
-             k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, (int)(min_P_ < 256), (int)head_logits_, (int)token_lp(), beam_w_, (int)logit_bias_on_, (int)sampling_on_, live_nsplit_,
+    snprintf(buf, sizeof(buf), "%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.b%d.lb%d.sm%d.rp%d/%d/%d/%d/%p/%016llx", B, gsize, k_parallel_groups, k_skinny_q,
+             k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, (int)(min_P_ < 256), (int)head_logits_, (int)token_lp(), beam_w_, (int)logit_bias_on_, (int)sampling_on_, (int)repetition_on_, live_nsplit_,
              max_ctx, max_new, (const void*)arena, (unsigned long long)h);
     return buf;
   }
@@ -1473,6 +1495,7 @@ struct q3a_engine {
         return graph_cache.back().second;
       }
     const hipGraphExec_t exec = capture_graph([&] { enqueue_step(); });
+    ++graph_captures_;
     if (graph_cache.size() >= kGraphCacheMax) {
       // the natural-EOS loop does not synchronise between steps, so the evicted exec may still be executing: it is only
       // destroyed after the next stream synchronisation (drain_retired_graphs)
@@ -1483,6 +1506,7 @@ struct q3a_engine {
     return exec;
   }
   std::vector<hipGraphExec_t> retired_graphs;
+  int32_t graph_captures_ = 0;  // decode-step graphs captured over the engine's life (q3a_debug_read "graph_captures")
   // call only when the stream is known to be idle
   void drain_retired_graphs() {
     for (auto ge : retired_graphs) (void)hipGraphExecDestroy(ge);
@@ -1660,11 +1684,43 @@ struct q3a_engine {
     for (int r = 0; r < V; ++r) finite += b[r] != -INFINITY;
     if (finite == 0) fail(std::string(what) + ": the bias has no finite entry (every token would be suppressed)");
     const bool on = !(n == 0 && default_bias == 0.f);
+    const bool eos_open = (kEos0 < V && b[kEos0] != -INFINITY) || (kEos1 < V && b[kEos1] != -INFINITY);
+    repetition_bias_check(what, rep_ngram_, eos_open, finite);
     have_prefill = false; beam_w_ = 0;  // no decode state until the next prefill, as after q3a_score
     HIPCHK(hipMemcpyAsync(step.logit_bias.p, b.data(), (size_t)V * 4, hipMemcpyHostToDevice, stream));
     HIPCHK(hipStreamSynchronize(stream));
     logit_bias_on_ = on;
     logit_bias_finite_ = finite;
+    logit_bias_eos_open_ = eos_open;
+  }
+  // Repetition penalty and no-repeat n-grams (q3asr.h q3a_set_repetition).  Penalty and n-gram size live in a device buffer the kernel
+  // reads, so a new setting replays the same graph; on / off is part of the graph signature.  No decode state afterwards.
+  void set_repetition(float penalty, int ngram) {
+    const char* what = "q3a_set_repetition";
+    require_asr(what);
+    if (!std::isfinite(penalty) || !(penalty > 0.f)) fail(std::string(what) + ": repetition_penalty must be finite and > 0 (1 turns the penalty off)");
+    if (ngram < 0 || ngram > 32) fail(std::string(what) + ": no_repeat_ngram_size must lie in [0, 32] (0 turns the ban off)");
+    const bool on = !(penalty == 1.f && ngram == 0);
+    if (on && d.vocab > REPEAT_MAX_VOCAB)
+      fail(std::string(what) + ": the vocabulary (" + std::to_string(d.vocab) + ") exceeds the " + std::to_string(REPEAT_MAX_VOCAB) + " ids the kernel's bitmap holds");
+    repetition_bias_check(what, ngram, logit_bias_eos_open_, logit_bias_finite_);
+    uint32_t w[4] = {0, (uint32_t)ngram, 0, 0};
+    memcpy(&w[0], &penalty, 4);
+    have_prefill = false; beam_w_ = 0;
+    HIPCHK(hipMemcpyAsync(step.rep_params.p, w, 16, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    rep_penalty_ = penalty; rep_ngram_ = ngram;
+    repetition_on_ = on;
+  }
+  // the one way a row could run out of finite logits: an n-gram ban over a bias that forbids every EOS and leaves no more tokens
+  // finite than a sequence may generate (asked by whichever of the two setters comes second)
+  void repetition_bias_check(const char* what, int ngram, bool eos_open, int finite) const {
+    if (ngram > 0 && !eos_open && finite <= opts.max_new_tokens)
+      fail(std::string(what) + ": no_repeat_ngram_size " + std::to_string(ngram) + " over a logit bias that forbids both EOS ids and leaves " + std::to_string(finite) +
+           " tokens finite, no more than max_new_tokens (" + std::to_string(opts.max_new_tokens) + "): a row could run out of finite logits");
+  }
+  void beam_repetition_check(const char* what) const {
+    if (repetition_on_) fail(std::string(what) + ": repetition control is on (q3a_set_repetition); beam slots reorder their histories -- turn it off first");
   }
   // Sampling (q3asr.h q3a_set_sampling).  The setting lives in a device buffer the kernels read, so a new temperature, min_p or seed
   // replays the same graph; on / off is part of the graph signature.  No decode state afterwards, as after q3a_set_logit_bias.
@@ -1695,6 +1751,7 @@ struct q3a_engine {
     if (!have_prefill) fail(std::string(what) + ": no prefill state (call q3a_prefill first)");
     beam_check(what, W);
     beam_sampling_check(what);
+    beam_repetition_check(what);
     beam_bias_check(what, W);
     if (!head_logits_ || pos_hi_ != *std::max_element(P.begin(), P.end()))
       fail(std::string(what) + ": needs the logits of q3a_prefill (call it directly after the prefill)");
@@ -2083,6 +2140,7 @@ int32_t q3a_beam_search_batch_ptrs(q3a_engine* e, const float* const* pcm16k, co
   const int cap = e->opts.max_new_tokens, want = max_new <= 0 ? cap : std::min(max_new, cap);
   if (stride < want) fail("q3a_beam_search_batch: stride " + std::to_string(stride) + " is below max_new " + std::to_string(want));
   e->beam_sampling_check("q3a_beam_search_batch");
+  e->beam_repetition_check("q3a_beam_search_batch");
   e->beam_bias_check("q3a_beam_search_batch", width);
   e->fixed_mode_ = false;
   e->head_logits_ = true;  // every round selects on the stored logits
@@ -2116,6 +2174,14 @@ int32_t q3a_set_sampling(q3a_engine* e, float temperature, float min_p, uint64_t
   Q3A_TRY(e)
   HIPCHK(hipSetDevice(e->device));
   e->set_sampling(temperature, min_p, seed);
+  Q3A_CATCH(e)
+}
+
+int32_t q3a_set_repetition(q3a_engine* e, float repetition_penalty, int32_t no_repeat_ngram_size) {
+  if (!e) return 1;
+  Q3A_TRY(e)
+  HIPCHK(hipSetDevice(e->device));
+  e->set_repetition(repetition_penalty, no_repeat_ngram_size);
   Q3A_CATCH(e)
 }
 
@@ -2394,6 +2460,7 @@ int32_t q3a_debug_read(q3a_engine* e, const char* name, void* dst, uint64_t byte
       {"align_head_ms", &e->align_head_ms, 4, false},  // the aligner head's launches (norm, classifier, merge) of the last align call
       {"score_head_ms", &e->score_head_ms, 4, false},  // the scoring head's launches (norm, lm_head with the reducing epilogue, merge) of the last score call
       {"device_bytes", &device_bytes, 8, false},       // device memory the DevBufs of the whole process hold
+      {"graph_captures", &e->graph_captures_, 4, false},  // decode-step graphs captured so far: a setting that lives in a device buffer adds none
   };
   for (const auto& sc : scalars)
     if (strcmp(name, sc.name) == 0) { give(sc.src, sc.n, sc.on_device); return 0; }
@@ -2407,6 +2474,13 @@ int32_t q3a_debug_read(q3a_engine* e, const char* name, void* dst, uint64_t byte
     e->require_asr("q3a_debug_read: sampling");
     const uint32_t st[5] = {e->sampling_on_ ? 1u : 0u, e->samp_words_[0], e->samp_words_[1], e->samp_words_[2], e->samp_words_[3]};
     give(st, 20, false);
+    return 0;
+  }
+  if (strcmp(name, "repetition") == 0) {  // {on, penalty bits, n-gram size} as last set
+    e->require_asr("q3a_debug_read: repetition");
+    uint32_t st[3] = {e->repetition_on_ ? 1u : 0u, 0u, (uint32_t)e->rep_ngram_};
+    memcpy(&st[1], &e->rep_penalty_, 4);
+    give(st, 12, false);
     return 0;
   }
   if (strcmp(name, "logit_bias_stats") == 0) {

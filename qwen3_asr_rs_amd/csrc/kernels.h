@@ -464,4 +464,19 @@ struct SampleLogprobArgs {
 };
 const char* launch_sample_logprob(const SampleLogprobArgs& a, hipStream_t s);
 
+// ---- repetition penalty and no-repeat n-grams (k_repeat.hip) -----------------------------------------------------
+constexpr int REPEAT_MAX_VOCAB = 1 << 18;  // ids the kernel's LDS bitmap holds (8192 words, 32 KB)
+constexpr int REPEAT_HIST_LDS = 4096;      // ids of a history kept in LDS (16 KB); a longer history is read in place beyond them
+// Per row s of logits [S][V] (fp32, row stride V), rewritten IN PLACE: with h = out_ids[s][0 .. t), t = min(step_count[s], out_stride),
+// every distinct id j of h gets l_j / p where l_j > 0 and l_j * p elsewhere (once, however often it occurred), then every id that
+// would complete an n-gram already in h gets -inf (n >= 1, t >= n - 1).  t = 0 leaves the row as it is.  One launch, one workgroup
+// per row; it runs before launch_argmax_partials / launch_sample, which then see l''.
+struct RepeatArgs {
+  float* logits; int S; int V;
+  const uint32_t* params;              // device [4]: p (fp32 bits), n, 0, 0 -- as validated by the setter: p finite and > 0, 0 <= n <= 32
+  const int* out_ids; int out_stride;  // [S][out_stride] the ids generated so far
+  const int* step_count;               // [S]
+};
+const char* launch_repeat_apply(const RepeatArgs& a, hipStream_t s);
+
 }  // namespace q3a

@@ -278,6 +278,55 @@ int32_t q3a_selftest_sample(int32_t device, const float* logits, int32_t S, int3
   Q3A_CATCH(nullptr)
 }
 
+// a step's tail with q3a_set_repetition on, as the engine enqueues it without sampling: launch_repeat_apply on the stored rows, fresh
+// argmax partials (with the log-sum channel) over the rewritten rows, argmax_finalize on those
+int32_t q3a_selftest_repeat(int32_t device, const float* logits, int32_t S, int32_t V, const int32_t* hist, int32_t stride,
+                            const int32_t* lens, float p, int32_t n, float* out_logits, int32_t* out_ids, float* out_lp) {
+  Q3A_TRY(nullptr)
+  if (!logits || !lens || S < 1 || V < 1 || stride < 0 || stride > (1 << 20) || (stride > 0 && !hist)) fail("q3a_selftest_repeat: bad argument");
+  if (!std::isfinite(p) || !(p > 0.f)) fail("q3a_selftest_repeat: repetition_penalty must be finite and > 0");
+  if (n < 0 || n > 32) fail("q3a_selftest_repeat: no_repeat_ngram_size must lie in [0, 32]");
+  if (V > REPEAT_MAX_VOCAB) fail("q3a_selftest_repeat: the vocabulary exceeds the kernel's bitmap");
+  const size_t Sz = S, pitch = (size_t)stride + 1;  // (one more column than any history: finalize writes the chosen id behind it)
+  std::vector<int> ids(Sz * pitch, -1);
+  for (size_t s = 0; s < Sz; ++s) {
+    if (lens[s] < 0 || lens[s] > stride) fail("q3a_selftest_repeat: a history length outside [0, stride]");
+    for (int i = 0; i < lens[s]; ++i) {
+      const int id = hist[s * stride + i];
+      if (id < 0 || id >= V) fail("q3a_selftest_repeat: a history id outside the vocabulary");
+      ids[s * pitch + i] = id;
+    }
+  }
+  use_device(device);
+  constexpr int H = 4, NP = 128;  // finalize embeds the chosen id: a token table of zeros, four columns wide
+  uint32_t w[4] = {0, (uint32_t)n, 0, 0};
+  memcpy(&w[0], &p, 4);
+  const DevBuf dLg = to_device(logits, Sz * V), dPar = to_device(w, 4), dSc = to_device(lens, Sz), dIds = to_device(ids);
+  const DevBuf dPv = room(Sz * NP * 4), dPi = room(Sz * NP * 4), dPs = room(Sz * NP * 4);
+  const DevBuf dEmb = to_device(std::vector<uint16_t>((size_t)V * H, 0)), dX = room(Sz * H * 4), dTok = room(Sz * 4);
+  const DevBuf dLp = to_device(std::vector<float>(Sz * pitch, 0.f));
+  const DevBuf dPos = to_device(std::vector<int>(Sz, 0)), dDone = to_device(std::vector<uint8_t>(Sz, 0));
+  RepeatArgs ra{};
+  ra.logits = dLg.as<float>(); ra.S = S; ra.V = V; ra.params = dPar.as<uint32_t>();
+  ra.out_ids = dIds.as<int>(); ra.out_stride = (int)pitch; ra.step_count = dSc.as<int>();
+  KCHK(launch_repeat_apply(ra, nullptr));
+  const ArgmaxPartials part{dPv.as<float>(), dPi.as<int>(), dPs.as<float>(), NP};
+  KCHK(launch_argmax_partials(ra.logits, V, S, part, NP, nullptr));
+  FinalizeArgs f{};
+  f.part = part; f.n_part = NP; f.out_lp = dLp.as<float>(); f.V = V; f.next_tok = dTok.as<int>(); f.out_ids = dIds.as<int>();
+  f.out_stride = (int)pitch; f.step_count = dSc.as<int>(); f.pos = dPos.as<int>(); f.advance = 1; f.done = dDone.as<uint8_t>(); f.n_seq = S;
+  f.embed = dEmb.as<uint16_t>(); f.H = H; f.x_next = dX.as<float>(); f.eos0 = kEos0; f.eos1 = kEos1;
+  KCHK(launch_argmax_finalize(f, S, nullptr));
+  finish();
+  if (out_logits) to_host(out_logits, dLg, Sz * V);
+  if (out_ids) to_host(out_ids, dTok, Sz);
+  if (out_lp) {
+    const std::vector<float> lp = to_host<float>(dLp, Sz * pitch);
+    for (size_t s = 0; s < Sz; ++s) out_lp[s] = lp[s * pitch + lens[s]];
+  }
+  Q3A_CATCH(nullptr)
+}
+
 int32_t q3a_selftest_gemm(int32_t device, int32_t M, int32_t N, int32_t K, int32_t split, float* max_abs_err,
                           float* ref_abs_max) {
   Q3A_TRY(nullptr)

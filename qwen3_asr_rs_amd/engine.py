@@ -94,6 +94,21 @@ def check_sampling_args(temperature: float, min_p: float = 0.0, seed: int = 0) -
     return t, p, int(seed)
 
 
+def check_repetition_args(repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0) -> Tuple[float, int]:
+    """The refusals of q3a_set_repetition that need no engine (pure host function): repetition_penalty finite and > 0 (1 = no
+    penalty), no_repeat_ngram_size an integer in [0, 32] (0 = no ban).  Returns the two as the C call takes them."""
+    try:
+        p = float(repetition_penalty)
+    except (TypeError, ValueError):
+        raise Q3aError("set_repetition: repetition_penalty must be a number")
+    if not (math.isfinite(p) and p > 0.0):
+        raise Q3aError(f"set_repetition: repetition_penalty must be finite and > 0 (1 turns the penalty off), got {repetition_penalty!r}")
+    n = no_repeat_ngram_size
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not (0 <= int(n) <= 32):
+        raise Q3aError(f"set_repetition: no_repeat_ngram_size must be an integer in [0, 32] (0 turns the ban off), got {no_repeat_ngram_size!r}")
+    return p, int(n)
+
+
 def compression_ratio(text: str) -> float:
     """len(utf8) / len(zlib.compress(utf8)): Whisper's measure of a repetition loop (a looping transcript compresses well)."""
     raw = text.encode("utf-8")
@@ -175,6 +190,7 @@ class HipEngine:
         self._T: List[int] = []
         self.logit_bias_state: Tuple[Optional[dict], float] = (None, 0.0)  # what set_logit_bias was last given
         self.sampling_state: Tuple[float, float, int] = (0.0, 0.0, 0)  # what set_sampling was last given
+        self.repetition_state: Tuple[float, int] = (1.0, 0)  # what set_repetition was last given
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -472,6 +488,20 @@ class HipEngine:
         return {"active": bool(st[0]), "temperature": float(st[1:2].view(np.float32)[0]), "min_p": float(st[2:3].view(np.float32)[0]),
                 "seed": int(st[3]) | (int(st[4]) << 32)}
 
+    # ---- repetition penalty / no-repeat n-grams ------------------------------------------------------------
+    def set_repetition(self, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0):
+        """q3a_set_repetition: every generation step divides the positive (multiplies the other) logits of the ids the sequence has
+        generated so far by repetition_penalty, once per distinct id, then bans (-inf) every id that would complete an n-gram of
+        no_repeat_ngram_size ids already generated -- on the device, on the sequence's own out_ids, bit for bit HuggingFace's two
+        processors.  (1.0, 0) turns it off.  Drops the decode state: prefill again before a stage-API step."""
+        p, n = check_repetition_args(repetition_penalty, no_repeat_ngram_size)
+        self._chk(self._lib.q3a_set_repetition(self._h, C.c_float(p), n))
+        self.repetition_state = (p, n)
+
+    def repetition_stats(self) -> dict:
+        st = self.debug_read_raw("repetition").view(np.uint32)
+        return {"active": bool(st[0]), "repetition_penalty": float(st[1:2].view(np.float32)[0]), "no_repeat_ngram_size": int(st[2])}
+
     # ---- beam search ----------------------------------------------------------------------------------
     def _beam_unpack(self, U, W, stride, ids, lens, scores, fin, lp) -> "List[List[BeamHypothesis]]":
         res = []
@@ -721,7 +751,8 @@ class AsrInference:
                    length_penalty: float = 0.0, suppress_tokens: Optional[Iterable[int]] = None,
                    logit_bias: Optional[Mapping[int, float]] = None, allowed_tokens: Optional[Iterable[int]] = None,
                    temperature=0.0, min_p: float = 0.0, seed: int = 0, logprob_threshold: float = -1.0,
-                   compression_ratio_threshold: float = 2.4) -> TranscribeResult:
+                   compression_ratio_threshold: float = 2.4, repetition_penalty: float = 1.0,
+                   no_repeat_ngram_size: int = 0) -> TranscribeResult:
         """src/inference.rs:89-213.  `audio`: path to a WAV file or a 16 kHz float32 array.  beam_size > 1: a beam search of that
         width instead of the greedy loop; `alternatives` holds its hypotheses ordered by score / max(len, 1) ** length_penalty
         (float64 on the host; 0: the search's own order) and the result is the first of them.
@@ -731,7 +762,12 @@ class AsrInference:
         own setting is restored afterwards); the default 0.0 leaves the engine as it is.  A tuple such as (0.0, 0.2, 0.4, 0.6, 0.8,
         1.0) is Whisper's fallback (temperature_fallback): attempt k runs at temperatures[k] with seed + k, the first attempt with
         avg_logprob >= logprob_threshold and compression ratio <= compression_ratio_threshold is kept, else the last; it needs an
-        engine created with token_logprobs=True.  The result's `temperature` is the one that was used.  Not with beam_size > 1."""
+        engine created with token_logprobs=True.  The result's `temperature` is the one that was used.  Not with beam_size > 1.
+        repetition_penalty / no_repeat_ngram_size: anything but (1.0, 0) sets HipEngine.set_repetition for this call and restores the
+        engine's own setting afterwards; every attempt of a temperature fallback runs under the same setting.  Not with beam_size > 1."""
+        rep_args = check_repetition_args(repetition_penalty, no_repeat_ngram_size)
+        if beam_size > 1 and rep_args != (1.0, 0):
+            raise Q3aError("transcribe: beam search has no repetition control (beam_size > 1 with repetition_penalty / no_repeat_ngram_size)")
         fallback = isinstance(temperature, (tuple, list))
         temps = [float(t) for t in temperature] if fallback else [float(temperature)]
         for t in temps:
@@ -756,6 +792,16 @@ class AsrInference:
                     return temperature_fallback(attempt, temps, seed, logprob_threshold, compression_ratio_threshold)[0]
                 finally:
                     eng.set_sampling(*before)
+        if rep_args != (1.0, 0):
+            inner, reng = run, self.engine
+
+            def run():
+                before = reng.repetition_state
+                reng.set_repetition(*rep_args)
+                try:
+                    return inner()
+                finally:
+                    reng.set_repetition(*before)
         if suppress_tokens is None and logit_bias is None and allowed_tokens is None:
             return run()
         ids, bias, default = compose_logit_bias(self.engine.dims.vocab_size, suppress_tokens, logit_bias, allowed_tokens)
