@@ -246,7 +246,8 @@ int32_t q3a_measure_peaks(int32_t device, int32_t reps, q3a_peaks* out);
  * by the pruned argmax, its launches; cumulative over the engine's life) and "device_bytes" (uint64: bytes of device memory the
  * workspace buffers of ALL engines of the process hold right now -- tables, activations, KV caches, the int8 lm_head copy, taps; not
  * the weight arenas) and "graph_captures" (int32: decode-step graphs captured over the engine's life; a replay adds none) are readable
- * without debug taps; so are the settings "logit_bias", "logit_bias_stats", "sampling" and "repetition" (their own sections below). */
+ * without debug taps; so are the settings "logit_bias", "logit_bias_stats", "sampling" and "repetition" and the counters "draft_stats"
+ * (their own sections below). */
 int32_t q3a_debug_read(q3a_engine* e, const char* name, void* dst, uint64_t bytes, uint64_t* actual);
 
 /* ---- pipeline shell: host-only helpers around the hot path -------------- */
@@ -343,7 +344,7 @@ int32_t q3a_fix_timestamps(const float* ms, int32_t n, float* out);
  * 0 and total_prompt_tokens = the rows prefilled; q3a_debug_read(e, "score_head_ms", ..) is the head's own time (a float).
  * Results are bit-identical from run to run on the same engine and inputs.
  * Out of scope: q3a_group_* (score each rank's slice on q3a_group_engine's handle, as for log-probabilities), several hypotheses
- * sharing one encoder pass, continuing generation after a forced prefix. */
+ * sharing one encoder pass.  (Continuing generation after a given prefix: "draft-verified decoding" below.) */
 
 /* Stage form, after q3a_mel + q3a_encode of the same B utterances.  prompt_ids / target_ids are concatenated over the batch;
  * outputs are host [B][stride], entries past target_lens[b] untouched; out_top_ids / out_top_lp nullable.  logits_out (nullable;
@@ -356,6 +357,68 @@ int32_t q3a_score(q3a_engine* e, const int32_t* prompt_ids, const int32_t* promp
 int32_t q3a_score_batch_ptrs(q3a_engine* e, const float* const* pcm16k, const int64_t* n_samples, int32_t B,
                              const int32_t* lang_prefix_ids, int32_t n_prefix, const int32_t* target_ids, const int32_t* target_lens,
                              float* out_lp, int32_t* out_top_ids, float* out_top_lp, int32_t stride);
+
+/* ---- draft-verified decoding: verify a transcript in one prefill, decode on ---------------------------------------------------------
+ * The caller hands in a DRAFT transcript per utterance (the previous partial transcript of a stream, a smaller model's output, a cached
+ * or human transcript that is "mostly right").  One prefill decides, on the device, the longest prefix of the draft the greedy loop would
+ * have written itself, and the captured decode step continues from exactly there: the result IS the greedy transcript; a good draft
+ * makes it cheap, a bad one costs one longer prefill.  (Exact as far as a greedy id is: the verified rows come from the prefill kernels,
+ * the loop's from the decode kernels, and the two agree to the mode's rounding noise on a logit -- 1e-5 precise, bf16 noise by default.
+ * A step whose top-1 / top-2 margin lies inside that noise may resolve differently on the two paths, exactly as between graph replay and
+ * the oracle; DESIGN.md section 3.13 has the measured figures.)
+ * For utterance s with prompt P_s (length p) and draft d_0 .. d_{n-1} (n >= 0) the engine prefills P_s ++ d_0 .. d_{n-1} ONCE (every
+ * draft id is fed, unlike scoring) and runs the lm_head at the n + 1 rows p - 1 .. p - 1 + n.  With t_i the argmax of row p - 1 + i
+ * (larger value, then smaller id):
+ *   k_s   = min{ i < n : t_i != d_i }, n if there is none -- the FIRST mismatch, not the number of matches;
+ *   tok_s = t_{k_s}.
+ * Afterwards the engine is in exactly the state the greedy loop has after producing the k_s + 1 tokens d_0 .. d_{k_s - 1}, tok_s: the
+ * out_ids rows hold them, step_count = k_s + 1, pos = p + k_s, next_tok = tok_s, the RoPE row of pos, the embedding of tok_s and its
+ * pre-normalised copy for the batched path are set; done, n_done and both pinned progress words are what argmax_finalize would have
+ * left (the prefill counts as one finalize; an EOS as tok_s finishes the sequence with k_s ids); the out_stride guard applies when
+ * k_s >= max_new; cache rows >= p + k_s are stale and are overwritten by the steps that follow.  With opts.token_logprobs the
+ * log-probabilities 0 .. k_s are the head's top_lp at those rows (the target's lp bit for bit where the target is the argmax, as in
+ * scoring).  Decoding continues with the unchanged captured step (natural EOS, run-ahead loop).
+ * A logit bias composes: the verify head is a head of the GENERATION paths and works on l' = l + b (b added to the fp32 accumulator in
+ * front of the max, log-sum and target channels; -inf stays -inf and never yields NaN), under the tolerance rule of that section.
+ * q3a_score* stays unbiased and bit-identical.
+ * Refused (q3a_last_error; the engine stays usable): a draft id < 0 or >= vocabulary; a draft id equal to <|audio_pad|> (151676) or to
+ * either EOS id (151643, 151645: a draft ends where its ids end); n > max_new (the engine's max_new_tokens in the stage form); an aligner
+ * engine; sampling or repetition control set (their choices are not an argmax of the row alone); a live beam search.
+ * q3a_debug_read(e, "draft_stats", ..) (int32 [1 + rounds]: rounds run by the last draft call, then the rows prefilled in each).
+ * q3a_stage_timings reports the prefill (every round, head and accept included) and the decode steps actually run.
+ * Out of scope: appending rows to an existing KV cache (the prefill attention keeps q_len = kv_len: every round is a full prefill);
+ * drafts under sampling or repetition control; per-slot drafts in beam search; q3a_group_*; a sliding window for endless streams. */
+
+/* Stage form, after q3a_mel + q3a_encode of the same B utterances.  prompt_ids / draft_ids are concatenated over the batch.
+ * accepted_out [B] = k_s, next_ids_out [B] = tok_s (both nullable).  logits_out (nullable; a test aid): host fp32
+ * [sum of (n + 1)][vocab], the verified rows of all utterances in order (l' under a bias).  Afterwards q3a_decode_step,
+ * q3a_set_next_tokens, q3a_fetch_ids and q3a_fetch_logprobs work as after q3a_prefill. */
+int32_t q3a_prefill_draft(q3a_engine* e, const int32_t* prompt_ids, const int32_t* prompt_lens, const int32_t* draft_ids,
+                          const int32_t* draft_lens, int32_t B, int32_t* accepted_out, int32_t* next_ids_out, float* logits_out);
+/* Whole path, host PCM in (the overlapped upload of q3a_transcribe_batch_ptrs; natural EOS only; max_new as there).  Outputs as
+ * q3a_transcribe_batch_ptrs, plus accepted_out [B] (nullable) = k_s of the last round.
+ * Rounds: after a round with first mismatch k_s the rest of the draft is often still right (a substitution).  A further round runs
+ * while round + 1 < max_rounds and the longest rejected tail max_s (n_s - k_s - 1) is at least max(min_tail, 1); it prefills the
+ * drafts q3a_draft_next_round gives (cut to max_new ids).  Mel and encoder run once.  Exactness never depends on the rule, only cost. */
+int32_t q3a_transcribe_draft_batch_ptrs(q3a_engine* e, const float* const* pcm16k, const int64_t* n_samples, int32_t B,
+                                        const int32_t* lang_prefix_ids, int32_t n_prefix, const int32_t* draft_ids, const int32_t* draft_lens,
+                                        int32_t max_new, int32_t max_rounds, int32_t min_tail, int32_t* out_ids, int32_t stride,
+                                        int32_t* out_lens, int32_t* accepted_out);
+/* Host helper, no engine: the draft of the next round, d[:k] ++ [tok] ++ d[k+1:], or d[:k] when tok is an EOS id (0 <= k <= n).
+ * *n_out = ids needed, at most cap written. */
+int32_t q3a_draft_next_round(const int32_t* draft, int32_t n, int32_t k, int32_t tok, int32_t* out, int32_t cap, int32_t* n_out);
+/* The accept kernel on its own (no model; host arrays in and out).  Sequence s owns draft_ids[draft_off[s] .. draft_off[s + 1]) and
+ * the head rows top_ids / top_lp [draft_off[s] + s ..] (n + 1 of them); top_lp / out_lp nullable.  embed: bf16 [V][H], H % 64 == 0;
+ * norm_w (nullable [H]): also the pre-normalised copy, nn_x [groups][32 * H] bf16 in fragment order and nn_ss [groups][H / 16][32]
+ * with groups of group_size sequences; cos_t / sin_t [max_pos][64].  Output buffers arrive pre-filled with the caller's sentinel and
+ * come back whole (a write outside one fails the call): accepted [2 S] (k, then tok), out_ids / out_lp [S][out_stride],
+ * state = next_tok [S] | step_count [S] | pos [S] | done [S] | n_done | progress word 0 | progress word 1, x_next [S][H],
+ * rope_cur [S][128]. */
+int32_t q3a_selftest_draft_accept(int32_t device, int32_t S, const int32_t* draft_ids, const int32_t* draft_off, const int32_t* prompt_lens,
+                                  const int32_t* top_ids, const float* top_lp, int32_t out_stride, const uint16_t* embed, int32_t V, int32_t H,
+                                  const float* norm_w, int32_t group_size, const float* cos_t, const float* sin_t, int32_t max_pos,
+                                  int32_t* accepted, int32_t* out_ids, float* out_lp, int32_t* state, float* x_next, float* rope_cur,
+                                  uint16_t* nn_x, float* nn_ss);
 
 /* ---- beam search: n-best hypotheses with scores, selected on the device ------------------------------------------------------------
  * U utterances of W slots each (1 <= W <= 8, U * W <= 32): sequence u * W + j of the engine's batch is slot j of utterance u, and the

@@ -19,6 +19,11 @@
 // 0 when absent); a Q3A_BEAM search is then refused by the engine.  There is no temperature fallback here (no zlib).
 // Q3A_REPETITION_PENALTY=<p> and / or Q3A_NO_REPEAT_NGRAM=<n> run the transcription under q3a_set_repetition (1 and 0 when absent); a
 // Q3A_BEAM search is then refused by the engine, a Q3A_SCORE_TEXT score never sees it.
+// Q3A_DRAFT_TEXT=<path of a UTF-8 file> with a `language` argument transcribes with that text as a draft (q3a_transcribe_draft_batch_ptrs:
+// the ids of "<asr_text>" + text, as Q3A_SCORE_TEXT reads a transcript): the same "Language:" / "Text:" lines as without it, then
+// "Accepted: <k> / <n>" -- the leading draft ids the greedy loop would have written itself, of the n the draft has.  Q3A_DRAFT_ROUNDS=<r>
+// (default 1) allows further verification rounds.  The engine refuses it together with Q3A_TEMPERATURE / Q3A_REPETITION_PENALTY /
+// Q3A_NO_REPEAT_NGRAM.
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -167,10 +172,10 @@ static int print_word_times(const char* aligner_dir, const float* pcm, int64_t n
   return rc;
 }
 
-// Q3A_SCORE_TEXT: the log-probability the model gives the transcript in `path`, token by token, in one prefill
-static int print_score(q3a_engine* eng, q3a_tokenizer* tok, const float* pcm, int64_t n, const std::vector<int32_t>& prefix, const char* path) {
+// the ids of "<asr_text>" + the text in `path` (trailing line ends dropped): how Q3A_SCORE_TEXT and Q3A_DRAFT_TEXT read a transcript
+static int transcript_ids(q3a_tokenizer* tok, const char* path, const char* what, std::vector<int32_t>& ids) {
   FILE* f = fopen(path, "rb");
-  if (!f) return die(std::string("Scoring failed: cannot read ") + path);
+  if (!f) return die(std::string(what) + " failed: cannot read " + path);
   std::string text;
   char buf[4096];
   for (size_t got; (got = fread(buf, 1, sizeof(buf), f)) > 0;) text.append(buf, got);
@@ -178,12 +183,19 @@ static int print_score(q3a_engine* eng, q3a_tokenizer* tok, const float* pcm, in
   while (!text.empty() && (text.back() == '\n' || text.back() == '\r')) text.pop_back();
   const std::string full = "<asr_text>" + text;
   int32_t nt = 0;
-  std::vector<int32_t> ids(full.size() + 8);
+  ids.assign(full.size() + 8, 0);
   if (q3a_tokenizer_encode(tok, full.c_str(), ids.data(), (int32_t)ids.size(), &nt) != 0)
-    return die(std::string("Scoring failed: ") + q3a_last_error(nullptr));
+    return die(std::string(what) + " failed: " + q3a_last_error(nullptr));
   ids.resize((size_t)nt);
+  return 0;
+}
+
+// Q3A_SCORE_TEXT: the log-probability the model gives the transcript in `path`, token by token, in one prefill
+static int print_score(q3a_engine* eng, q3a_tokenizer* tok, const float* pcm, int64_t n, const std::vector<int32_t>& prefix, const char* path) {
+  std::vector<int32_t> ids;
+  if (transcript_ids(tok, path, "Scoring", ids) != 0) return 1;
   ids.push_back(151645);  // <|im_end|>: "the transcript stops here" is scored too
-  nt = (int32_t)ids.size();
+  int32_t nt = (int32_t)ids.size();
   std::vector<float> lp((size_t)nt), top_lp((size_t)nt);
   std::vector<int32_t> top((size_t)nt);
   const float* ptrs[1] = {pcm};
@@ -293,8 +305,23 @@ int main(int argc, char** argv) {
   const int32_t max_new = 4096;  // inference.rs:153
   std::vector<int32_t> ids((size_t)max_new);
   int32_t len = 0;
-  if (q3a_transcribe_batch(eng, pcm, &n, 1, prefix.empty() ? nullptr : prefix.data(), (int32_t)prefix.size(), max_new, 0,
-                           ids.data(), max_new, &len) != 0)
+  const char* draft_path = getenv("Q3A_DRAFT_TEXT");
+  const bool with_draft = draft_path && *draft_path;
+  int32_t accepted = 0, n_draft = 0;
+  if (with_draft) {
+    if (!language) return die("Draft failed: Q3A_DRAFT_TEXT needs the language argument (the ids after a free-running prompt start with the language the model detects)");
+    std::vector<int32_t> draft;
+    if (transcript_ids(tok, draft_path, "Draft", draft) != 0) return 1;
+    n_draft = (int32_t)draft.size();
+    const char* rounds_env = getenv("Q3A_DRAFT_ROUNDS");
+    const int rounds = rounds_env && atoi(rounds_env) > 0 ? atoi(rounds_env) : 1;
+    const float* ptrs[1] = {pcm};
+    draft.push_back(0);  // (never read: a valid pointer for an empty draft)
+    if (q3a_transcribe_draft_batch_ptrs(eng, ptrs, &n, 1, prefix.data(), (int32_t)prefix.size(), draft.data(), &n_draft, max_new, rounds, 5 /* the one-clip break-even, DESIGN.md section 3.13 */,
+                                        ids.data(), max_new, &len, &accepted) != 0)
+      return die(std::string("Draft failed: ") + q3a_last_error(eng));
+  } else if (q3a_transcribe_batch(eng, pcm, &n, 1, prefix.empty() ? nullptr : prefix.data(), (int32_t)prefix.size(), max_new, 0,
+                                  ids.data(), max_new, &len) != 0)
     return die(std::string("Transcription failed: ") + q3a_last_error(eng));
   std::vector<float> lps;
   if (want_lp) {
@@ -330,6 +357,7 @@ int main(int argc, char** argv) {
     const double avg = lps.empty() ? NAN : sum / (double)lps.size();
     printf("Confidence: avg_logprob %.6f min_token_prob %.6f\n", avg, lps.empty() ? NAN : std::exp((double)mn));
   }
+  if (with_draft) printf("Accepted: %d / %d\n", accepted, n_draft);
   int rc = 0;
   const char* beam_env = getenv("Q3A_BEAM");
   if (beam_env && *beam_env) rc = print_beam(eng, tok, pcm, n, prefix, atoi(beam_env), max_new, language != nullptr);

@@ -161,6 +161,7 @@ struct DecodeStep : StepView {
   // and the clean (max, sum exp) pair of every 2048-logit chunk of every row [B][sample_chunks(vocab)]
   DevBuf samp_params, samp_max, samp_sum;
   DevBuf rep_params;  // q3a_set_repetition: {penalty (fp32 bits), n-gram size, 0, 0} as repeat_apply_kernel reads them (a new setting needs no new graph)
+  DevBuf draft_accepted;  // draft verification (k_draft.hip): [2 B] first mismatch k per sequence, then its token -- one small D2H copy per prefill
   // f(buffer) for every DevBuf declared above, in declaration order (s: a DecodeStep, const or not).  The declarations of this
   // struct ARE the guarded set: tests/test_host.py::test_step_buffers_cover_the_captured_step compares this list with them.
   template <class Self, class F> static void each_buf(Self& s, F&& f) {
@@ -169,7 +170,7 @@ struct DecodeStep : StepView {
                     &s.rope_cur, &s.rope_cos, &s.rope_sin, &s.n_done, &s.forced_tok,
                     &s.beam_cand_val, &s.beam_cand_idx, &s.beam_part_max, &s.beam_part_sum, &s.beam_topk_ids, &s.beam_topk_lp, &s.beam_score, &s.beam_finished,
                     &s.beam_parent, &s.beam_token, &s.beam_feed, &s.beam_hist_parent, &s.beam_hist_token, &s.beam_hist_lp, &s.beam_state, &s.beam_lo,
-                    &s.logit_bias, &s.samp_params, &s.samp_max, &s.samp_sum, &s.rep_params})
+                    &s.logit_bias, &s.samp_params, &s.samp_max, &s.samp_sum, &s.rep_params, &s.draft_accepted})
       f(*b);
   }
 
@@ -278,6 +279,19 @@ struct DecodeStep : StepView {
     if (sample) enqueue_sampler(f);
     timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_finalize(f, S, stream)); });
     if (sample && token_lp()) enqueue_sample_logprob();
+  }
+  // Draft verification (k_draft.hip), in the place of the prefill's run_head(0): from the verify head's argmax per row to the state the
+  // greedy loop has after the accepted tokens.  It writes the step's buffers, so it is enqueued here; `a` arrives with the call's own
+  // inputs (draft, offsets, prompt lengths, the head's top_id / top_lp: buffers of one prefill that no captured launch ever sees).
+  void enqueue_draft_accept(DraftAcceptArgs a) {
+    a.n_seq = B; a.accepted = draft_accepted.as<int>();
+    a.next_tok = next_tok.as<int>(); a.out_ids = out_ids.as<int>(); a.out_stride = max_new; a.step_count = step_count.as<int>(); a.pos = d_pos.as<int>();
+    a.out_lp = token_lp() ? out_lp.as<float>() : nullptr;
+    a.done = done.as<uint8_t>(); a.n_done = n_done.as<int>(); a.host_progress = host_prog_dev;
+    a.embed = wh(L.embed); a.H = d.hidden; a.x_next = x_dec.as<float>(); a.eos0 = kEos0; a.eos1 = kEos1;
+    a.cos_t = rope_cos.as<float>(); a.sin_t = rope_sin.as<float>(); a.rope_cur = rope_cur.as<float>();
+    a.nn = first_layer_norm_out();
+    timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_draft_accept(a, stream)); });
   }
   // Repetition penalty and no-repeat n-grams (k_repeat.hip): the stored rows, in place, from each sequence's own out_ids
   // (l' -> l'').  The head's partials, where it wrote any, are those of l': with `partials` the rewritten rows' own, log-sum channel
@@ -1140,7 +1154,7 @@ struct q3a_engine {
     }
     const size_t ng = (size_t)step.n_groups(b);  // groups of <= gsize sequences of the batched decode step
     step.nn_x.ensure(ng * 32 * H * 2); step.nn_ss.ensure((size_t)ng * (H / 8) * 32 * 4);  // room for the finer (8-column) partial rows whichever shape the knob selects later
-    step.x_dec.ensure((size_t)b * H * 4); step.next_tok.ensure((size_t)b * 4); step.forced_tok.ensure((size_t)b * 4);
+    step.x_dec.ensure((size_t)b * H * 4); step.next_tok.ensure((size_t)b * 4); step.forced_tok.ensure((size_t)b * 4); step.draft_accepted.ensure((size_t)b * 8);
     step.out_ids.ensure((size_t)b * max_new * 4); step.step_count.ensure((size_t)b * 4); step.done.ensure((size_t)b);
     // s_ctx / s_act also hold the bf16 fragment-order copies of the skinny GEMM path: always 32 sequences there
     step.s_ln.ensure((size_t)b * H * 4); step.s_qkv.ensure((size_t)b * d.qkv_dim() * 4); step.s_ctx.ensure(ng * 32 * d.q_dim() * 4);
@@ -1434,6 +1448,105 @@ struct q3a_engine {
   }
   DevBuf score_tgt, score_psum, score_out;
   float score_head_ms = 0.f;  // the head's launches of the last score call (q3a_debug_read "score_head_ms")
+
+  // =====================================================================================
+  // draft-verified decoding (q3a_prefill_draft / q3a_transcribe_draft_batch_ptrs): ONE causal prefill over
+  // prompt ++ draft, the scoring head at the n + 1 rows p - 1 .. p - 1 + n (under the logit bias, if one is set), then
+  // DecodeStep::enqueue_draft_accept -- and the engine stands where the greedy loop stands after its first k + 1 tokens.
+  struct DraftPlan {
+    std::vector<int32_t> ids, lens;  // what is prefilled: per utterance prompt ++ draft (every draft id is fed, unlike scoring)
+    std::vector<int> rows, targets;  // per head row: row of the residual stream, and the draft id it is compared with (the last row of an utterance has none: id 0)
+    std::vector<int> words;          // the accept kernel's inputs: draft_off [B + 1] | prompt_len [B] | draft ids
+    std::vector<int> plen, dlen;
+  };
+  // what no draft call runs under (the header's list; the per-id refusals are draft_plan's)
+  void draft_check(const char* what) const {
+    require_asr(what);
+    if (sampling_on_) fail(std::string(what) + ": sampling is on (q3a_set_sampling with temperature > 0): a sampled id is not the argmax of its row -- turn it off first");
+    if (repetition_on_) fail(std::string(what) + ": repetition control is on (q3a_set_repetition): its choice depends on the history, not on the row alone -- turn it off first");
+    if (beam_w_ > 0) fail(std::string(what) + ": a beam search owns the decode state (a new q3a_prefill returns to the greedy step)");
+  }
+  DraftPlan draft_plan(const char* what, const int32_t* prompt_ids, const int32_t* prompt_lens, const int32_t* draft_ids, const int32_t* draft_lens,
+                       int b, int max_new_eff) const {
+    DraftPlan dp;
+    dp.lens.resize(b); dp.plen.resize(b); dp.dlen.resize(b);
+    dp.words.assign((size_t)2 * b + 1, 0);
+    size_t po = 0, to = 0;
+    for (int s = 0; s < b; ++s) {
+      const int p = prompt_lens[s], n = draft_lens[s];
+      if (p <= 0) fail(std::string(what) + ": empty prompt");
+      if (n < 0 || (n > 0 && !draft_ids)) fail(std::string(what) + ": bad draft length");
+      if (n > max_new_eff)
+        fail(std::string(what) + ": utterance " + std::to_string(s) + " has a draft of " + std::to_string(n) + " ids, more than max_new " + std::to_string(max_new_eff));
+      const int row0 = (int)dp.ids.size() + p - 1;
+      dp.ids.insert(dp.ids.end(), prompt_ids + po, prompt_ids + po + p);
+      for (int i = 0; i < n; ++i) {
+        const int32_t y = draft_ids[to + i];
+        if (y < 0 || y >= d.vocab) fail(std::string(what) + ": draft id " + std::to_string(y) + " out of range (vocabulary " + std::to_string(d.vocab) + ")");
+        if (y == kAudioPad) fail(std::string(what) + ": <|audio_pad|> (" + std::to_string(kAudioPad) + ") cannot be a draft id: the engine finds audio rows by this id");
+        if (y == kEos0 || y == kEos1) fail(std::string(what) + ": an EOS id (" + std::to_string(y) + ") cannot be a draft id: a draft ends where its ids end");
+        dp.ids.push_back(y);
+        dp.words.push_back(y);
+        dp.rows.push_back(row0 + i);
+        dp.targets.push_back(y);
+      }
+      dp.rows.push_back(row0 + n);
+      dp.targets.push_back(0);
+      dp.lens[s] = p + n; dp.plen[s] = p; dp.dlen[s] = n;
+      dp.words[s + 1] = dp.words[s] + n;
+      dp.words[(size_t)b + 1 + s] = p;
+      po += p; to += n;
+    }
+    return dp;
+  }
+  // prompts of dp already set up (setup_prompts over dp.ids / dp.lens).  acc [2 B]: k per utterance, then its token.  logits_out
+  // (nullable): the head's rows [sum (n + 1)][vocab].  The stream is idle on return and the engine holds decode state.
+  void run_prefill_draft(const DraftPlan& dp, std::vector<int>& acc, float* logits_out) {
+    const int M = (int)dp.rows.size(), V = d.vocab, H = d.hidden;
+    have_prefill = false;
+    run_prefill_layers();
+    const int planes = precise() ? 2 : 1, n_part = align_head_parts(V);
+    upload(align_rows, dp.rows, stream);
+    upload(score_tgt, dp.targets, stream);
+    upload(draft_in, dp.words, stream);
+    align_xn.ensure((size_t)planes * align_rows_padded(M) * H * 2);
+    align_pval.ensure((size_t)M * n_part * 4); align_pidx.ensure((size_t)M * n_part * 4); score_psum.ensure((size_t)M * n_part * 4);
+    score_out.ensure((size_t)M * 4 * 4);  // tgt_logit | lp | top_id | top_lp
+    if (logits_out) align_logits.ensure((size_t)M * V * 4);
+    ScoreHeadArgs a{};
+    a.x = dec_x.as<float>(); a.ldx = H; a.rows = align_rows.as<int>(); a.M = M;
+    a.norm_w = wf(L.final_norm); a.eps = d.rms_eps; a.W = wh(L.lm_head); a.N = V; a.K = H;
+    a.planes = planes; a.xn = align_xn.as<uint16_t>();
+    a.part = ArgmaxPartials{align_pval.as<float>(), align_pidx.as<int>(), score_psum.as<float>(), n_part};
+    a.targets = score_tgt.as<int>();
+    a.tgt_logit = score_out.as<float>(); a.lp = score_out.as<float>() + M;
+    a.top_id = score_out.as<int>() + 2 * (size_t)M; a.top_lp = score_out.as<float>() + 3 * (size_t)M;
+    a.logits = logits_out ? align_logits.as<float>() : nullptr; a.ldl = (size_t)V;
+    a.bias = step.head_bias();  // a logit bias composes: the verify head is a head of the generation paths
+    KCHK(launch_score_head(a, stream));
+    DraftAcceptArgs da{};
+    da.draft_off = draft_in.as<int>(); da.prompt_len = da.draft_off + B + 1; da.draft = da.prompt_len + B;
+    da.top_id = a.top_id; da.top_lp = a.top_lp;
+    step.enqueue_draft_accept(da);
+    HIPCHK(hipStreamSynchronize(stream));
+    HIPCHK(hipGetLastError());
+    acc.resize((size_t)2 * B);
+    HIPCHK(hipMemcpy(acc.data(), step.draft_accepted.p, acc.size() * 4, hipMemcpyDeviceToHost));
+    if (logits_out) HIPCHK(hipMemcpy(logits_out, align_logits.p, (size_t)M * V * 4, hipMemcpyDeviceToHost));
+    // the host-side bounds of the decode loop, from what was accepted: pos_hi_ an upper bound of every position (decode_steps derives
+    // live_nsplit_ from it), min_P_ a lower bound of the live lengths (trim_prologue; both are in the graph signature)
+    pos_hi_ = 0; min_P_ = 0x7fffffff;
+    for (int s = 0; s < B; ++s) {
+      if (acc[s] < 0 || acc[s] > dp.dlen[s]) fail("draft accept: the device returned a first mismatch outside the draft");
+      pos_hi_ = std::max(pos_hi_, dp.plen[s] + acc[s]);
+      min_P_ = std::min(min_P_, dp.plen[s] + acc[s]);
+    }
+    draft_stats_[0] += 1;
+    draft_stats_.push_back(total_P);
+    have_prefill = true;
+  }
+  DevBuf draft_in;
+  std::vector<int32_t> draft_stats_{0};  // of the last draft call: rounds run, then the rows prefilled in each (q3a_debug_read "draft_stats")
 
   // the captured step, through the unit (which cannot create the streams its groups fork onto)
   void enqueue_step() {
@@ -1776,14 +1889,15 @@ struct q3a_engine {
   // The natural-EOS loop of the greedy search and of the beam rounds after round 0: `ahead` decode steps stay enqueued in front of
   // the device, and the two pinned words prog[0] (launches of the step's last kernel completed; the prefill / round 0 counts 1) and
   // prog[1] (stop) are read without synchronising.  Returns the decode steps enqueued, at most `limit`.
-  int run_ahead(const int* prog, int limit, const char* label) {
+  // `base`: what prog[0] stood at before the first step of this loop, less one (a draft-verified prefill leaves it at k + 1).
+  int run_ahead(const int* prog, int limit, const char* label, int base = 0) {
     const int ahead = std::max(1, knobs().eos_run_ahead.load());
     int steps = 0;
     unsigned spins = 0;
     while (steps < limit) {
       if (__atomic_load_n(&prog[1], __ATOMIC_RELAXED)) break;
       const int fin = __atomic_load_n(&prog[0], __ATOMIC_RELAXED);
-      if (steps - std::max(fin - 1, 0) < ahead) {
+      if (steps - std::max(fin - 1 - base, 0) < ahead) {
         decode_steps(1);
         ++steps;
         spins = 0;
@@ -1792,7 +1906,7 @@ struct q3a_engine {
         if ((spins & 0xffff) == 0) {  // a device fault must end the wait: the progress words would never move again
           const hipError_t q = hipStreamQuery(stream);
           if (q != hipSuccess && q != hipErrorNotReady) HIPCHK(q);
-          if (q == hipSuccess && steps - std::max(__atomic_load_n(&prog[0], __ATOMIC_RELAXED) - 1, 0) >= ahead)
+          if (q == hipSuccess && steps - std::max(__atomic_load_n(&prog[0], __ATOMIC_RELAXED) - 1 - base, 0) >= ahead)
             fail(std::string(label) + " loop: the stream drained but the device-side progress counter did not advance");
         }
       }
@@ -2348,6 +2462,100 @@ int32_t q3a_transcribe_batch(q3a_engine* e, const float* pcm16k, const int64_t* 
   return q3a_transcribe_batch_ptrs(e, ptrs.data(), n_samples, B, lang_prefix_ids, n_prefix, max_new, fixed_new_tokens, out_ids, stride, out_lens);
 }
 
+// ---- draft-verified decoding ----------------------------------------------------------------------------------------------
+int32_t q3a_prefill_draft(q3a_engine* e, const int32_t* prompt_ids, const int32_t* prompt_lens, const int32_t* draft_ids, const int32_t* draft_lens,
+                          int32_t B, int32_t* accepted_out, int32_t* next_ids_out, float* logits_out) {
+  if (!e) return 1;
+  Q3A_TRY(e)
+  const char* what = "q3a_prefill_draft";
+  e->draft_check(what);
+  if (!prompt_ids || !prompt_lens || !draft_lens || B < 1) fail(std::string(what) + ": bad argument");
+  HIPCHK(hipSetDevice(e->device));
+  if (!e->have_enc) fail(std::string(what) + ": no encoder output (call q3a_encode first)");
+  if (B != e->B) fail(std::string(what) + ": batch size differs from the encoded batch");
+  const auto dp = e->draft_plan(what, prompt_ids, prompt_lens, draft_ids, draft_lens, B, e->opts.max_new_tokens);
+  e->fixed_mode_ = false;
+  e->head_logits_ = true;
+  e->have_prefill = false;
+  e->setup_prompts(dp.ids.data(), dp.lens.data(), B, e->opts.max_new_tokens);
+  e->timings = q3a_timings{};
+  e->draft_stats_.assign(1, 0);
+  std::vector<int> acc;
+  e->run_prefill_draft(dp, acc, logits_out);
+  for (int s = 0; s < B; ++s) {
+    if (accepted_out) accepted_out[s] = acc[s];
+    if (next_ids_out) next_ids_out[s] = acc[(size_t)B + s];
+  }
+  Q3A_CATCH(e)
+}
+
+int32_t q3a_transcribe_draft_batch_ptrs(q3a_engine* e, const float* const* pcm16k, const int64_t* n_samples, int32_t B,
+                                        const int32_t* lang_prefix_ids, int32_t n_prefix, const int32_t* draft_ids, const int32_t* draft_lens,
+                                        int32_t max_new, int32_t max_rounds, int32_t min_tail, int32_t* out_ids, int32_t stride,
+                                        int32_t* out_lens, int32_t* accepted_out) {
+  if (!e) return 1;
+  Q3A_TRY(e)
+  const char* what = "q3a_transcribe_draft_batch";
+  e->draft_check(what);
+  if (!draft_lens || !out_lens || stride < 0 || (stride > 0 && !out_ids) || n_prefix < 0 || B < 1) fail(std::string(what) + ": bad argument");
+  const auto w0 = std::chrono::steady_clock::now();
+  e->fixed_mode_ = false;
+  e->head_logits_ = e->opts.debug_taps != 0;
+  const int mn = e->max_new_request(max_new, 0), mn_eff = std::min(std::max(mn, 1), e->opts.max_new_tokens);
+  std::pair<std::vector<int32_t>, std::vector<int32_t>> pr;  // the prompts without a draft: the same in every round
+  q3a_engine::DraftPlan dp;
+  e->whole_path_front(what, pcm16k, n_samples, B, 1, mn, [&] {
+    pr = e->asr_prompts(lang_prefix_ids, n_prefix);
+    dp = e->draft_plan(what, pr.first.data(), pr.second.data(), draft_ids, draft_lens, B, mn_eff);
+    return std::tie(dp.ids, dp.lens);
+  });
+  e->draft_stats_.assign(1, 0);
+  HIPCHK(hipEventRecord(e->ev[2], e->stream));
+  std::vector<int> acc;
+  std::vector<int32_t> cur, cur_lens(B), nxt;
+  {
+    size_t total = 0;
+    for (int s = 0; s < B; ++s) { cur_lens[s] = draft_lens[s]; total += draft_lens[s]; }
+    if (total) cur.assign(draft_ids, draft_ids + total);
+  }
+  for (int round = 0;; ++round) {
+    e->run_prefill_draft(dp, acc, nullptr);
+    // another round pays while the longest rejected tail is worth a prefill (mel and encoder are not run again)
+    int tail = 0;
+    for (int s = 0; s < B; ++s) tail = std::max(tail, cur_lens[s] - acc[s] - 1);
+    if (round + 1 >= max_rounds || tail < std::max(min_tail, 1)) break;
+    nxt.clear();
+    size_t off = 0;
+    for (int s = 0; s < B; ++s) {
+      int32_t need = 0;
+      const size_t o = nxt.size();
+      nxt.resize(o + (size_t)cur_lens[s] + 1);
+      if (q3a_draft_next_round(cur.data() + off, cur_lens[s], acc[s], acc[(size_t)B + s], nxt.data() + o, cur_lens[s] + 1, &need) != 0)
+        fail(std::string(what) + ": " + q3a_last_error(nullptr));
+      off += cur_lens[s];
+      cur_lens[s] = std::min(need, mn_eff);  // (an accepted draft of max_new ids plus the head's next id: the id has no slot)
+      nxt.resize(o + cur_lens[s]);
+    }
+    cur.swap(nxt);
+    dp = e->draft_plan(what, pr.first.data(), pr.second.data(), cur.data(), cur_lens.data(), B, mn_eff);
+    e->setup_prompts(dp.ids.data(), dp.lens.data(), B, mn);
+  }
+  HIPCHK(hipEventRecord(e->ev[3], e->stream));
+  int min_k = e->max_new;
+  for (int s = 0; s < B; ++s) min_k = std::min(min_k, acc[s]);
+  // every sequence has k + 1 tokens: the one that has the fewest bounds the steps the loop may still run
+  const int steps = e->run_ahead(e->host_prog, e->max_new - 1 - min_k, "draft", acc[0]);
+  HIPCHK(hipEventRecord(e->ev[4], e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  HIPCHK(hipGetLastError());
+  e->decode_timings(steps);
+  e->fetch_ids(out_ids, stride, out_lens);
+  if (accepted_out)
+    for (int s = 0; s < B; ++s) accepted_out[s] = acc[s];
+  e->io.wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - w0).count();
+  Q3A_CATCH(e)
+}
+
 int32_t q3a_io_timings_last(const q3a_engine* e, q3a_io_timings* out) {
   if (!e || !out) return 1;
   *out = e->io;
@@ -2468,6 +2676,10 @@ int32_t q3a_debug_read(q3a_engine* e, const char* name, void* dst, uint64_t byte
   if (strcmp(name, "logit_bias") == 0) {
     e->require_asr("q3a_debug_read: logit_bias");
     give(e->step.logit_bias.p, (size_t)e->d.vocab * 4, true);
+    return 0;
+  }
+  if (strcmp(name, "draft_stats") == 0) {  // the last draft call: rounds run, then the rows prefilled in each round
+    give(e->draft_stats_.data(), e->draft_stats_.size() * 4, false);
     return 0;
   }
   if (strcmp(name, "sampling") == 0) {  // {on, temperature bits, min_p bits, seed low, seed high} as last set

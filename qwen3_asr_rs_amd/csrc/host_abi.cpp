@@ -133,6 +133,22 @@ int32_t q3a_parse_logit_bias(const char* text, const char* suppress_list, int32_
   HOST_CATCH
 }
 
+// ---- draft-verified decoding: the draft of the next round (q3asr.h) ----
+int32_t q3a_draft_next_round(const int32_t* draft, int32_t n, int32_t k, int32_t tok, int32_t* out, int32_t cap, int32_t* n_out) {
+  HOST_TRY
+  if (!n_out || n < 0 || k < 0 || k > n || cap < 0 || (n > 0 && !draft) || (cap > 0 && !out)) fail("q3a_draft_next_round: bad argument");
+  const bool eos = tok == 151643 || tok == 151645;  // the model stops at k: what stood behind it in the draft is dropped
+  int64_t count = 0;
+  auto put = [&](int32_t id) { if (count < cap) out[count] = id; ++count; };
+  for (int i = 0; i < k; ++i) put(draft[i]);
+  if (!eos) {
+    put(tok);
+    for (int i = k + 1; i < n; ++i) put(draft[i]);
+  }
+  *n_out = (int32_t)count;
+  HOST_CATCH
+}
+
 int32_t q3a_load_audio(const char* path, int32_t target_sr, float** samples_out, int64_t* n_out) {
   HOST_TRY
   if (!path || !samples_out || !n_out) fail("null argument");

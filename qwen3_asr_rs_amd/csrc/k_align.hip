@@ -69,11 +69,15 @@ __global__ __launch_bounds__(256) void align_norm_kernel(const float* __restrict
 }
 
 // One 64 x 128 output tile at (m0, n0 = 128 tile_n).  LP (scoring head): the partials carry the log-sum channel and the lane that
-// holds column targets[m] stores its accumulator to tgt_logit[m].
-template <int NP, bool LOGITS, bool LP>
+// holds column targets[m] stores its accumulator to tgt_logit[m].  BIAS (draft verification under a logit bias, LP only): bias[n], finite
+// or -inf, is added to the fp32 accumulator in front of every channel and of the stored logits; a -inf logit stays exactly -inf,
+// contributes 0 to the log-sum and never yields NaN (a lane whose columns are all suppressed keeps (max -inf, sum 0), which
+// ArgmaxAcc::merge drops).  A new instantiation: the others compile to what they were.
+template <int NP, bool LOGITS, bool LP, bool BIAS = false>
 __device__ __forceinline__ void head_tile(const uint16_t* __restrict__ xn, int Mp, int M, const uint16_t* __restrict__ W, int N, int K,
                                           const ArgmaxPartials& part, float* __restrict__ logits, size_t ldl, int m0, int tile_n,
-                                          const int* __restrict__ targets, float* __restrict__ tgt_logit) {
+                                          const int* __restrict__ targets, float* __restrict__ tgt_logit,
+                                          const float* __restrict__ bias = nullptr) {
   __shared__ __attribute__((aligned(16))) uint16_t As[NP][BM * LDSK];
   __shared__ __attribute__((aligned(16))) uint16_t Bs[BN * LDSK];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave >> 1, wn = wave & 1;
@@ -155,6 +159,9 @@ __device__ __forceinline__ void head_tile(const uint16_t* __restrict__ xn, int M
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
         const int n = n0 + 64 * wn + 16 * ni + (lane & 15);
+        if constexpr (BIAS) {
+          if (n < N) acc[mi][ni][r] += bias[n];
+        }
         const float v = acc[mi][ni][r];
         if (n < N && v > best.v) { best.v = v; best.i = n; }
         if (LOGITS && n < N && m < M) logits[(size_t)m * ldl + n] = v;
@@ -166,7 +173,11 @@ __device__ __forceinline__ void head_tile(const uint16_t* __restrict__ xn, int M
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) {
           const int n = n0 + 64 * wn + 16 * ni + (lane & 15);
-          if (n < N) best.s += __expf(acc[mi][ni][r] - best.v);
+          if constexpr (BIAS) {
+            if (n < N && acc[mi][ni][r] != -INFINITY) best.s += __expf(acc[mi][ni][r] - best.v);
+          } else {
+            if (n < N) best.s += __expf(acc[mi][ni][r] - best.v);
+          }
         }
       }
 #pragma unroll
@@ -193,6 +204,18 @@ __global__ __launch_bounds__(256) void score_head_kernel(const uint16_t* __restr
   const int id = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
   if (id >= tiles) return;  // (the whole workgroup)
   head_tile<NP, LOGITS, true>(xn, Mp, M, W, N, K, part, logits, ldl, (id % m_tiles) * BM, id / m_tiles, targets, tgt_logit);
+}
+
+// the scoring head's walk on l' = l + b (draft verification while a logit bias is set)
+template <int NP, bool LOGITS>
+__global__ __launch_bounds__(256) void draft_head_kernel(const uint16_t* __restrict__ xn, int Mp, int M, const uint16_t* __restrict__ W,
+                                                         int N, int K, ArgmaxPartials part, float* __restrict__ logits, size_t ldl,
+                                                         const int* __restrict__ targets, float* __restrict__ tgt_logit, int m_tiles,
+                                                         int tiles, const float* __restrict__ bias) {
+  const int chunk = gridDim.x >> 3;
+  const int id = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+  if (id >= tiles) return;  // (the whole workgroup)
+  head_tile<NP, LOGITS, true, true>(xn, Mp, M, W, N, K, part, logits, ldl, (id % m_tiles) * BM, id / m_tiles, targets, tgt_logit, bias);
 }
 
 __global__ __launch_bounds__(256) void score_merge_kernel(ArgmaxPartials part, int n_part, int M, int N, const float* __restrict__ tgt_logit,
@@ -258,11 +281,21 @@ const char* launch_score_head(const ScoreHeadArgs& a, hipStream_t s) {
 #define SCORE_LAUNCH(NP, LG)                                                                                                      \
   hipLaunchKernelGGL((score_head_kernel<NP, LG>), grid, dim3(256), 0, s, a.xn, Mp, a.M, a.W, a.N, a.K, a.part, a.logits, a.ldl, \
                      a.targets, a.tgt_logit, m_tiles, (int)tiles)
-  if (a.planes == 1) {
+#define DRAFT_LAUNCH(NP, LG)                                                                                                      \
+  hipLaunchKernelGGL((draft_head_kernel<NP, LG>), grid, dim3(256), 0, s, a.xn, Mp, a.M, a.W, a.N, a.K, a.part, a.logits, a.ldl, \
+                     a.targets, a.tgt_logit, m_tiles, (int)tiles, a.bias)
+  if (a.bias) {
+    if (a.planes == 1) {
+      if (a.logits) DRAFT_LAUNCH(1, true); else DRAFT_LAUNCH(1, false);
+    } else {
+      if (a.logits) DRAFT_LAUNCH(2, true); else DRAFT_LAUNCH(2, false);
+    }
+  } else if (a.planes == 1) {
     if (a.logits) SCORE_LAUNCH(1, true); else SCORE_LAUNCH(1, false);
   } else {
     if (a.logits) SCORE_LAUNCH(2, true); else SCORE_LAUNCH(2, false);
   }
+#undef DRAFT_LAUNCH
 #undef SCORE_LAUNCH
   hipLaunchKernelGGL(score_merge_kernel, dim3((a.M + 3) / 4), dim3(256), 0, s, a.part, n_part, a.M, a.N, a.tgt_logit, a.lp, a.top_id, a.top_lp);
   return nullptr;

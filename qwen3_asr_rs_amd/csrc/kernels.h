@@ -77,6 +77,9 @@ struct ScoreHeadArgs {
   float* lp;                      // [M] l[target] - logsumexp(l)
   int* top_id; float* top_lp;     // [M] argmax (first index on ties) and its log-probability; nullable
   float* logits; size_t ldl;      // nullable: [M][ldl] fp32
+  // draft verification only (nullable; q3a_score* never sets it): a logit bias [N], every entry finite or -inf, added to the fp32
+  // accumulator in front of the max, log-sum and target channels and of the stored logits -- the BIAS instantiation of the same tile
+  const float* bias;
 };
 const char* launch_score_head(const ScoreHeadArgs& a, hipStream_t s);
 
@@ -392,6 +395,26 @@ const char* launch_argmax_finalize(const FinalizeArgs& a, int S, hipStream_t s);
 // x_next[s] = embed[tok[s]]; next_tok[s] = tok[s]  (teacher forcing)
 const char* launch_set_tokens(const int* tok, int S, const uint16_t* embed, int H, float* x_next, int* next_tok, hipStream_t s,
                               const NextNormOut& nn = NextNormOut{});
+
+// ---- draft verification (k_draft.hip) ------------------------------------------------------------------------
+// After ONE prefill of prompt ++ draft and the scoring head at the n + 1 rows p - 1 .. p - 1 + n of every sequence (top_id / top_lp of
+// ScoreHeadArgs): the first position k at which the head's argmax differs from the draft (n if none), and the state the greedy loop
+// has after producing the k + 1 tokens d_0 .. d_{k-1}, top_id[k] -- everything launch_argmax_finalize would have left behind.
+// One workgroup per sequence.  Sequence s owns draft[draft_off[s] .. draft_off[s + 1]) and head rows draft_off[s] + s + i.
+struct DraftAcceptArgs {
+  int n_seq;
+  const int* draft; const int* draft_off;  // [draft_off[n_seq]] ids, [n_seq + 1] offsets
+  const int* prompt_len;                   // [n_seq] p: the prompt without the draft
+  const int* top_id; const float* top_lp;  // [draft_off[n_seq] + n_seq] of the verify head; top_lp read only with out_lp
+  int* accepted;                           // [2 n_seq] (written): k per sequence, then the token top_id[k] per sequence
+  int* next_tok; int* out_ids; int out_stride; int* step_count; int* pos;  // as FinalizeArgs (all written: step_count = k + 1, pos = p + k)
+  float* out_lp;                           // nullable [n_seq][out_stride]: top_lp of rows 0 .. k
+  uint8_t* done; int* n_done; int* host_progress;  // as FinalizeArgs; host_progress[0] = step_count of sequence 0
+  const uint16_t* embed; int H; float* x_next; int eos0, eos1;
+  const float* cos_t; const float* sin_t; float* rope_cur;  // RoPE row of pos, as FinalizeArgs
+  NextNormOut nn;
+};
+const char* launch_draft_accept(const DraftAcceptArgs& a, hipStream_t s);
 
 // ---- beam search (k_beam.hip) --------------------------------------------------------------------------------
 constexpr int BEAM_MAX_W = 8;       // slots per utterance

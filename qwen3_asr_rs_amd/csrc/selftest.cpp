@@ -327,6 +327,77 @@ int32_t q3a_selftest_repeat(int32_t device, const float* logits, int32_t S, int3
   Q3A_CATCH(nullptr)
 }
 
+int32_t q3a_selftest_draft_accept(int32_t device, int32_t S, const int32_t* draft_ids, const int32_t* draft_off, const int32_t* prompt_lens,
+                                  const int32_t* top_ids, const float* top_lp, int32_t out_stride, const uint16_t* embed, int32_t V, int32_t H,
+                                  const float* norm_w, int32_t group_size, const float* cos_t, const float* sin_t, int32_t max_pos,
+                                  int32_t* accepted, int32_t* out_ids, float* out_lp, int32_t* state, float* x_next, float* rope_cur,
+                                  uint16_t* nn_x, float* nn_ss) {
+  Q3A_TRY(nullptr)
+  const char* what = "q3a_selftest_draft_accept";
+  if (S < 1 || !draft_off || !prompt_lens || !top_ids || !embed || !cos_t || !sin_t || !accepted || !out_ids || !state || !x_next || !rope_cur)
+    fail(std::string(what) + ": bad argument");
+  if (out_stride < 1 || V < 1 || H < 64 || H % 64 != 0 || max_pos < 1) fail(std::string(what) + ": bad shape");
+  if (group_size < 1 || group_size > 32) fail(std::string(what) + ": group_size must lie in [1, 32]");
+  if (norm_w && (!nn_x || !nn_ss)) fail(std::string(what) + ": norm_w needs nn_x and nn_ss");
+  if (draft_off[0] != 0) fail(std::string(what) + ": draft_off[0] must be 0");
+  const size_t Sz = S;
+  for (size_t s = 0; s < Sz; ++s) {
+    const int n = draft_off[s + 1] - draft_off[s];
+    if (n < 0 || (n > 0 && !draft_ids)) fail(std::string(what) + ": bad draft offsets");
+    if (prompt_lens[s] < 1 || prompt_lens[s] + n >= max_pos) fail(std::string(what) + ": a position outside the RoPE tables");
+  }
+  const size_t nd = draft_off[S], M = nd + Sz;
+  for (size_t r = 0; r < M; ++r)
+    if (top_ids[r] < 0 || top_ids[r] >= V) fail(std::string(what) + ": a head id outside the embedding table");
+  use_device(device);
+  const int groups = (S + group_size - 1) / group_size, nparts = H / 16;
+  const size_t nnx = (size_t)groups * 32 * H, nns = (size_t)groups * nparts * 32;
+  std::vector<int> dr(draft_ids, draft_ids + nd);
+  dr.resize(nd + 4, 0);
+  const DevBuf dDr = to_device(dr), dOff = to_device(draft_off, Sz + 1), dPl = to_device(prompt_lens, Sz), dTop = to_device(top_ids, M);
+  DevBuf dTlp;
+  if (top_lp) dTlp = to_device(top_lp, M);
+  const DevBuf dAcc = room(Sz * 8), dTok = room(Sz * 4), dSc = to_device(std::vector<int>(Sz, -7)), dPos = to_device(std::vector<int>(Sz, -7));
+  const Guarded gIds(out_ids, Sz * out_stride * 4);
+  Guarded gLp;
+  if (top_lp && out_lp) gLp = Guarded(out_lp, Sz * out_stride * 4);
+  const DevBuf dDone = to_device(std::vector<uint8_t>(Sz, 0)), dNd = to_device(std::vector<int>(16, 0)), dProg = to_device(std::vector<int>(16, 0));
+  const DevBuf dEmb = to_device(embed, (size_t)V * H), dCos = to_device(cos_t, (size_t)max_pos * 64), dSin = to_device(sin_t, (size_t)max_pos * 64);
+  const Guarded gX(x_next, Sz * H * 4), gRope(rope_cur, Sz * 128 * 4);
+  DevBuf dW;
+  Guarded gNx, gNs;
+  if (norm_w) { dW = to_device(norm_w, (size_t)H); gNx = Guarded(nn_x, nnx * 2); gNs = Guarded(nn_ss, nns * 4); }
+  DraftAcceptArgs a{};
+  a.n_seq = S; a.draft = dDr.as<int>(); a.draft_off = dOff.as<int>(); a.prompt_len = dPl.as<int>();
+  a.top_id = dTop.as<int>(); a.top_lp = top_lp ? dTlp.as<float>() : nullptr; a.accepted = dAcc.as<int>();
+  a.next_tok = dTok.as<int>(); a.out_ids = gIds.as<int>(); a.out_stride = out_stride; a.step_count = dSc.as<int>(); a.pos = dPos.as<int>();
+  a.out_lp = gLp.b.p ? gLp.as<float>() : nullptr;
+  a.done = dDone.as<uint8_t>(); a.n_done = dNd.as<int>(); a.host_progress = dProg.as<int>();
+  a.embed = dEmb.as<uint16_t>(); a.H = H; a.x_next = gX.as<float>(); a.eos0 = kEos0; a.eos1 = kEos1;
+  a.cos_t = dCos.as<float>(); a.sin_t = dSin.as<float>(); a.rope_cur = gRope.as<float>();
+  if (norm_w) {
+    a.nn.next_w = dW.as<float>(); a.nn.next_xw16f = gNx.as<uint16_t>(); a.nn.next_ss = gNs.as<float>(); a.nn.nparts = nparts;
+    a.nn.group_stride_x = (long)32 * H; a.nn.group_stride_ss = (long)nparts * 32; a.nn.group_size = group_size;
+  }
+  KCHK(launch_draft_accept(a, nullptr));
+  finish();
+  to_host(accepted, dAcc, Sz * 2);
+  gIds.fetch(out_ids, "out_ids");
+  if (gLp.b.p) gLp.fetch(out_lp, "out_lp");
+  gX.fetch(x_next, "x_next");
+  gRope.fetch(rope_cur, "rope_cur");
+  if (norm_w) { gNx.fetch(nn_x, "nn_x"); gNs.fetch(nn_ss, "nn_ss"); }
+  // state: next_tok [S] | step_count [S] | pos [S] | done [S] | n_done | progress[0] | progress[1]
+  to_host(state, dTok, Sz);
+  to_host(state + Sz, dSc, Sz);
+  to_host(state + 2 * Sz, dPos, Sz);
+  const std::vector<uint8_t> dn = to_host<uint8_t>(dDone, Sz);
+  for (size_t s = 0; s < Sz; ++s) state[3 * Sz + s] = dn[s];
+  to_host(state + 4 * Sz, dNd, 1);
+  to_host(state + 4 * Sz + 1, dProg, 2);
+  Q3A_CATCH(nullptr)
+}
+
 int32_t q3a_selftest_gemm(int32_t device, int32_t M, int32_t N, int32_t K, int32_t split, float* max_abs_err,
                           float* ref_abs_max) {
   Q3A_TRY(nullptr)

@@ -25,6 +25,13 @@ from . import _lib
 EOS_TOKEN_IDS = (151643, 151645)  # src/inference.rs:154, src/tokenizer.rs:54-55
 
 
+AUDIO_PAD_ID = 151676  # <|audio_pad|>: the engine finds audio rows by this id
+# transcribe_draft_batch: a further verification round runs while the longest rejected tail of a draft has at least this many ids.
+# The break-even is (prefill + head + accept time) / (time of one decode step) at one clip, rounded up: measured 2.614 ms / 585.8 us =
+# 4.46 (tools/draft_cost.py, 0.6b preset, one 30 s clip, 100 ids).  At 32 clips it is 16.7: pass min_tail there.
+DRAFT_MIN_TAIL = 5
+
+
 class Q3aError(RuntimeError):
     pass
 
@@ -107,6 +114,50 @@ def check_repetition_args(repetition_penalty: float = 1.0, no_repeat_ngram_size:
     if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not (0 <= int(n) <= 32):
         raise Q3aError(f"set_repetition: no_repeat_ngram_size must be an integer in [0, 32] (0 turns the ban off), got {no_repeat_ngram_size!r}")
     return p, int(n)
+
+
+def check_draft_ids(draft, vocab: int, max_new: int) -> List[int]:
+    """The refusals of q3a_prefill_draft / q3a_transcribe_draft_batch_ptrs that need no engine (pure host function): every id an
+    integer inside the vocabulary, none of them <|audio_pad|> or an EOS id, at most max_new of them.  Returns the ids as a list."""
+    out = []
+    for t in draft:
+        if isinstance(t, bool) or not isinstance(t, (int, np.integer)):
+            raise Q3aError(f"draft: id {t!r} is not an integer")
+        t = int(t)
+        if not 0 <= t < vocab:
+            raise Q3aError(f"draft: id {t} is outside the vocabulary ({vocab})")
+        if t == AUDIO_PAD_ID:
+            raise Q3aError(f"draft: <|audio_pad|> ({AUDIO_PAD_ID}) cannot be a draft id")
+        if t in EOS_TOKEN_IDS:
+            raise Q3aError(f"draft: an EOS id ({t}) cannot be a draft id: a draft ends where its ids end")
+        out.append(t)
+    if len(out) > max_new:
+        raise Q3aError(f"draft: {len(out)} ids, more than max_new {max_new}")
+    return out
+
+
+def check_draft_compat(beam_size: int = 1, temperatures: Sequence[float] = (0.0,), repetition: Tuple[float, int] = (1.0, 0)):
+    """What a draft does not combine with (pure host function): beam search, sampling, repetition control -- their choices are not the
+    argmax of a row alone, so one prefill cannot verify them."""
+    if beam_size > 1:
+        raise Q3aError("transcribe: a draft verifies the greedy loop, not a beam search (draft with beam_size > 1)")
+    if any(float(t) > 0.0 for t in temperatures):
+        raise Q3aError("transcribe: a draft cannot be verified under sampling (draft with a temperature > 0)")
+    if tuple(repetition) != (1.0, 0):
+        raise Q3aError("transcribe: a draft cannot be verified under repetition control (draft with repetition_penalty / no_repeat_ngram_size)")
+
+
+def draft_next_round(draft: Sequence[int], k: int, tok: int, cap: Optional[int] = None) -> Tuple[List[int], int]:
+    """q3a_draft_next_round (host only): the draft of the next verification round, d[:k] + [tok] + d[k+1:], or d[:k] when tok is an EOS
+    id.  Returns (the ids, at most cap of them; the number of ids the full answer has)."""
+    lib = _lib.load()
+    d = np.asarray(list(draft), dtype=np.int32)
+    cap = len(d) + 1 if cap is None else int(cap)
+    out = np.zeros(max(cap, 1), dtype=np.int32)
+    n = C.c_int32()
+    if lib.q3a_draft_next_round(_i32p(d) if len(d) else None, len(d), int(k), int(tok), _i32p(out) if cap > 0 else None, cap, C.byref(n)) != 0:
+        raise Q3aError((lib.q3a_last_error(None) or b"").decode())
+    return out[:min(n.value, cap)].tolist(), int(n.value)
 
 
 def compression_ratio(text: str) -> float:
@@ -326,6 +377,60 @@ class HipEngine:
                                                       fixed_new_tokens, _i32p(out), stride, _i32p(lens)))
         self.batch = B
         return [out[b, :min(int(lens[b]), stride)].tolist() for b in range(B)]
+
+    # ---- draft-verified decoding ----------------------------------------------------------------------
+    @staticmethod
+    def _flat_drafts(drafts: Sequence[Sequence[int]]):
+        dl = np.array([len(t) for t in drafts], dtype=np.int32)
+        flat = np.concatenate([np.asarray(t, dtype=np.int64).reshape(-1) for t in drafts] + [np.zeros(1, np.int64)])
+        if flat.min() < -2**31 or flat.max() >= 2**31:
+            raise Q3aError("draft: id does not fit 32 bits")
+        return dl, np.ascontiguousarray(flat.astype(np.int32))
+
+    def prefill_draft(self, prompts: Sequence[Sequence[int]], drafts: Sequence[Sequence[int]], want_logits: bool = False):
+        """Stage form (q3a_prefill_draft) after mel() + encode(): ONE prefill of prompt + draft per utterance, the lm_head at the n + 1
+        rows that predict the draft ids and the id behind them, and the engine stands where the greedy loop stands after the accepted
+        ids: decode_step / set_next_tokens / fetch_ids / fetch_logprobs continue from there.  Returns (accepted k per utterance, the
+        token at k per utterance[, the verified rows' logits [sum of (n + 1)][vocab]])."""
+        B = len(prompts)
+        if len(drafts) != B:
+            raise Q3aError(f"prefill_draft: {len(drafts)} draft(s) for {B} prompt(s)")
+        pl = np.array([len(p) for p in prompts], dtype=np.int32)
+        pids = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.int32) for p in prompts]))
+        dl, flat = self._flat_drafts(drafts)
+        acc, nxt = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        logits = np.zeros((int(dl.sum()) + B, self.dims.vocab_size), dtype=np.float32) if want_logits else None
+        self._chk(self._lib.q3a_prefill_draft(self._h, _i32p(pids), _i32p(pl), _i32p(flat), _i32p(dl), B, _i32p(acc), _i32p(nxt),
+                                              _f32p(logits) if want_logits else None))
+        self.batch = B
+        return (acc, nxt, logits) if want_logits else (acc, nxt)
+
+    def transcribe_draft_batch(self, clips: Sequence[np.ndarray], drafts: Sequence[Sequence[int]], lang_prefix_ids: Optional[Sequence[int]] = None,
+                               max_new: int = 0, max_rounds: int = 1, min_tail: int = DRAFT_MIN_TAIL) -> Tuple[List[List[int]], List[int]]:
+        """Whole path (q3a_transcribe_draft_batch_ptrs): the greedy natural-EOS transcript of every clip, exactly what transcribe_batch
+        returns, with the longest prefix of each draft that the greedy loop would have written itself verified in one prefill instead
+        of decoded step by step.  max_new <= 0: the engine's max_new_tokens.  max_rounds > 1: a rejected id is replaced by the model's
+        and the rest of the draft verified again while its tail has at least min_tail ids.  Returns (ids per clip, accepted ids per
+        clip in the last round)."""
+        arrs, ptrs, ns = self._ptrs(clips)
+        B = len(arrs)
+        if len(drafts) != B:
+            raise Q3aError(f"transcribe_draft_batch: {len(drafts)} draft(s) for {B} clip(s)")
+        stride = max(1, min(int(max_new), self.max_new_tokens) if max_new > 0 else self.max_new_tokens)
+        dl, flat = self._flat_drafts(drafts)
+        out = np.zeros((B, stride), dtype=np.int32)
+        lens, acc = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        pre = np.asarray(lang_prefix_ids if lang_prefix_ids is not None else [], dtype=np.int32)
+        self._chk(self._lib.q3a_transcribe_draft_batch_ptrs(self._h, ptrs, _i64p(ns), B, _i32p(pre) if len(pre) else None, len(pre), _i32p(flat),
+                                                            _i32p(dl), int(max_new), int(max_rounds), int(min_tail), _i32p(out), stride, _i32p(lens),
+                                                            _i32p(acc)))
+        self.batch = B
+        return [out[b, :min(int(lens[b]), stride)].tolist() for b in range(B)], [int(k) for k in acc]
+
+    def draft_stats(self) -> dict:
+        """The last draft call (q3a_debug_read "draft_stats"): rounds run and the rows prefilled in each."""
+        st = self.debug_read_raw("draft_stats").view(np.int32)
+        return {"rounds": int(st[0]), "rows": [int(v) for v in st[1:]]}
 
     def io_timings(self) -> dict:
         """Input side of the last transcribe_batch (q3a_io_timings_last)."""
@@ -716,6 +821,7 @@ class TranscribeResult:
     avg_logprob: Optional[float] = None
     alternatives: Optional[List[Alternative]] = None  # beam_size > 1: the n-best list, best first (this result is its first entry)
     temperature: Optional[float] = None  # transcribe(temperature=...): the temperature of the attempt that was kept (0.0 = greedy)
+    accepted_draft_tokens: Optional[int] = None  # transcribe(draft=...): leading ids of the draft the greedy loop would have written itself
 
 
 @dataclass
@@ -752,7 +858,7 @@ class AsrInference:
                    logit_bias: Optional[Mapping[int, float]] = None, allowed_tokens: Optional[Iterable[int]] = None,
                    temperature=0.0, min_p: float = 0.0, seed: int = 0, logprob_threshold: float = -1.0,
                    compression_ratio_threshold: float = 2.4, repetition_penalty: float = 1.0,
-                   no_repeat_ngram_size: int = 0) -> TranscribeResult:
+                   no_repeat_ngram_size: int = 0, draft=None) -> TranscribeResult:
         """src/inference.rs:89-213.  `audio`: path to a WAV file or a 16 kHz float32 array.  beam_size > 1: a beam search of that
         width instead of the greedy loop; `alternatives` holds its hypotheses ordered by score / max(len, 1) ** length_penalty
         (float64 on the host; 0: the search's own order) and the result is the first of them.
@@ -764,7 +870,12 @@ class AsrInference:
         avg_logprob >= logprob_threshold and compression ratio <= compression_ratio_threshold is kept, else the last; it needs an
         engine created with token_logprobs=True.  The result's `temperature` is the one that was used.  Not with beam_size > 1.
         repetition_penalty / no_repeat_ngram_size: anything but (1.0, 0) sets HipEngine.set_repetition for this call and restores the
-        engine's own setting afterwards; every attempt of a temperature fallback runs under the same setting.  Not with beam_size > 1."""
+        engine's own setting afterwards; every attempt of a temperature fallback runs under the same setting.  Not with beam_size > 1.
+        draft: a transcript that is probably mostly right -- a list of ids, an earlier TranscribeResult (its ids) or a string (score()'s
+        text convention: it needs `language`, and the ids are encode("<asr_text>" + text)).  The result is the greedy result; the ids of
+        the draft the greedy loop would have written itself are verified in one prefill instead of decoded one by one, and
+        `accepted_draft_tokens` says how many that were.  Composes with suppress_tokens / logit_bias / allowed_tokens; raises Q3aError
+        with beam_size > 1, a temperature > 0 or repetition control."""
         rep_args = check_repetition_args(repetition_penalty, no_repeat_ngram_size)
         if beam_size > 1 and rep_args != (1.0, 0):
             raise Q3aError("transcribe: beam search has no repetition control (beam_size > 1 with repetition_penalty / no_repeat_ngram_size)")
@@ -776,7 +887,11 @@ class AsrInference:
             raise Q3aError("transcribe: a tuple of temperatures (fallback) decides on avg_logprob: create the engine with token_logprobs=True")
         if beam_size > 1 and any(t > 0.0 for t in temps):
             raise Q3aError("transcribe: beam search does not sample (beam_size > 1 with a temperature > 0)")
-        run = lambda: self._transcribe(audio, language, max_new_tokens, beam_size, length_penalty)
+        draft_ids = None
+        if draft is not None:
+            check_draft_compat(beam_size, temps, rep_args)
+            draft_ids = self._draft_ids(draft, language, max_new_tokens)
+        run = lambda: self._transcribe(audio, language, max_new_tokens, beam_size, length_penalty, draft_ids)
         if fallback or temps[0] > 0.0:
             plain, eng = run, self.engine
 
@@ -812,7 +927,18 @@ class AsrInference:
         finally:
             self.engine.set_logit_bias(*before)
 
-    def _transcribe(self, audio, language, max_new_tokens, beam_size, length_penalty) -> TranscribeResult:
+    def _draft_ids(self, draft, language, max_new_tokens) -> List[int]:
+        if isinstance(draft, TranscribeResult):
+            draft = draft.ids
+        if isinstance(draft, str):
+            if self.tokenizer is None:
+                raise Q3aError("a text draft needs tokenizer.json (src/inference.rs:246-251)")
+            if language is None:
+                raise Q3aError("transcribe: a text draft needs `language` (the ids after a free-running prompt start with the language the model detects)")
+            draft = self.tokenizer.encode("<asr_text>" + draft)
+        return check_draft_ids(draft, self.engine.dims.vocab_size, min(int(max_new_tokens), self.engine.max_new_tokens))
+
+    def _transcribe(self, audio, language, max_new_tokens, beam_size, length_penalty, draft_ids=None) -> TranscribeResult:
         if isinstance(audio, (str, os.PathLike)):
             samples = load_audio(os.fspath(audio), 16000)
         else:
@@ -836,10 +962,15 @@ class AsrInference:
             lps = best.token_logprobs[:len(best.ids)]
             return TranscribeResult(alt.text, lang, raw, best.ids, [float(v) for v in lps],
                                     float(np.mean(lps, dtype=np.float64)) if len(lps) else None, [a for a, _, _ in alts])
-        ids = self.engine.transcribe_batch([samples], prefix, max_new_tokens)[0]
+        accepted = None
+        if draft_ids is not None:
+            got, acc = self.engine.transcribe_draft_batch([samples], [draft_ids], prefix, min(max_new_tokens, self.engine.max_new_tokens))
+            ids, accepted = got[0], acc[0]
+        else:
+            ids = self.engine.transcribe_batch([samples], prefix, max_new_tokens)[0]
         raw = self.tokenizer.decode(ids, True) if self.tokenizer is not None else ""
         lang, text = parse_asr_output(raw, language is not None)
-        res = TranscribeResult(text, lang, raw, ids)
+        res = TranscribeResult(text, lang, raw, ids, accepted_draft_tokens=accepted)
         if self.engine.token_logprobs:
             lp = self.engine.fetch_logprobs()[0]
             res.token_logprobs = [float(v) for v in lp]
@@ -872,6 +1003,55 @@ class AsrInference:
         lp, top, top_lp = self.engine.score_batch([samples], [ids], prefix)[0]
         return ScoreResult(ids, [float(v) for v in lp], float(np.mean(lp, dtype=np.float64)) if len(lp) else None,
                            [int(t) for t in top], [float(v) for v in top_lp])
+
+
+@dataclass
+class StreamingUpdate:
+    """One push of a StreamingTranscriber: the transcript of all audio so far, how many leading ids of the previous transcript stayed
+    (0 on the first push), and the seconds of audio it covers."""
+    result: TranscribeResult
+    accepted: int
+    audio_seconds: float
+
+
+class StreamingTranscriber:
+    """Incremental transcription on top of AsrInference.transcribe(draft=...): every push() transcribes ALL audio received so far with
+    the previous transcript's ids as the draft, so what the new audio did not change is verified in one prefill instead of decoded
+    again, and `accepted` -- the ids that stayed -- is read off the result instead of guessed with a roll-back heuristic.
+    Each push re-runs the log-mel, the encoder and the prefill over the whole audio: the cost per update grows with the stream, and
+    a bounded window for endless streams is out of scope.  transcribe_kwargs go to every transcribe call (max_new_tokens,
+    suppress_tokens, ...); anything a draft does not combine with raises Q3aError at the first push."""
+
+    def __init__(self, asr, language: Optional[str] = None, **transcribe_kwargs):
+        if "draft" in transcribe_kwargs or "audio" in transcribe_kwargs:
+            raise Q3aError("StreamingTranscriber: the draft and the audio are its own")
+        self.asr, self.language, self.kwargs = asr, language, dict(transcribe_kwargs)
+        self.reset()
+
+    def reset(self):
+        """Forget the audio and the previous transcript: the next push starts a new stream."""
+        self._audio = np.zeros(0, dtype=np.float32)
+        self._ids: List[int] = []
+        self.last: Optional[StreamingUpdate] = None
+
+    def push(self, samples) -> StreamingUpdate:
+        """Append 16 kHz float32 samples and transcribe the audio so far."""
+        self._audio = np.concatenate([self._audio, np.asarray(samples, dtype=np.float32).reshape(-1)])
+        draft = []
+        for t in self._ids:  # (an id a draft may not hold -- a model that wrote <|audio_pad|> -- ends it)
+            if t == AUDIO_PAD_ID or t in EOS_TOKEN_IDS:
+                break
+            draft.append(t)
+        res = self.asr.transcribe(self._audio, language=self.language, draft=draft, **self.kwargs)
+        self._ids = [int(t) for t in res.ids]
+        self.last = StreamingUpdate(res, int(res.accepted_draft_tokens or 0), len(self._audio) / 16000.0)
+        return self.last
+
+    def finish(self) -> Optional[StreamingUpdate]:
+        """The last update (None when nothing was pushed); the stream is reset."""
+        last = self.last
+        self.reset()
+        return last
 
 
 class ForcedAligner:
