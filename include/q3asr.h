@@ -663,6 +663,23 @@ int32_t q3a_selftest_qkrope_launch(int32_t device, int32_t fused, int32_t kv_f32
                                    const float* bias, float* qkv, const int32_t* row_seq, const int32_t* row_pos, const float* q_norm,
                                    const float* k_norm, float eps, const float* cos_t, const float* sin_t, int32_t max_pos, int32_t n_q, int32_t n_kv,
                                    int32_t n_seq, int32_t max_ctx, uint16_t* q16, void* kcache, void* vcache);
+/* ONE launch of the one-sequence GEMV family on the caller's data, in the precise arithmetic (fast_math = 0, attn_fast_exp = 0), as
+ * q3a_selftest_gemm_launch: tests/decode_kernels_ref.py compares in float64.  w bf16 [N][K]; x [K] fp32, or -- x and rms_w null -- the
+ * flash-decoding partials attn_pm / attn_pl [heads][nsplit] and attn_po [heads][nsplit][128] with K = heads * 128, merged on the fly.
+ * rms_w [K] (nullable) fuses the RMSNorm with eps; bias [N] nullable; mode 0 store, 1 out = resid + y (resid [N]), 2 GLU (N / 2 outputs),
+ * 3 the lm_head: launch_gemv (pruned = 0) or the int8 pre-pass + rescore pair (pruned = 1, out null), then argmax_finalize at step 2 of a
+ * 4-step sequence at position 5: out_state = {next token, out_ids[2], step count, position} after it.  out (sentinel in, whole buffer
+ * out, guard zones on the device) is [N] ([N / 2] in mode 2), nullable in mode 3. */
+int32_t q3a_selftest_gemv_launch(int32_t device, int32_t pruned, const uint16_t* w, int32_t N, int32_t K, const float* x, const float* rms_w, float eps,
+                                 const float* bias, int32_t mode, const float* resid, const float* attn_pm, const float* attn_pl, const float* attn_po,
+                                 int32_t attn_nsplit, int32_t attn_heads, float* out, int32_t* out_state);
+/* The same for launch_decode_attn at one sequence: qkv [(n_q + 2 n_kv) * 128] raw projections of the token at position pos, q_norm / k_norm
+ * [128], rope_cur [128] = cos (64) | sin (64) of pos, kcache / vcache [n_kv][max_ctx][128] (bf16 bits, or fp32 with kv_f32: the precise
+ * exponential) holding rows 0 .. pos - 1.  Outputs, each sentinel in / whole buffer out: the caches (row pos appended), pm / pl
+ * [n_q][nsplit], po [n_q][nsplit][128]. */
+int32_t q3a_selftest_decode_attn_launch(int32_t device, int32_t kv_f32, const float* qkv, int32_t pos, const float* q_norm, const float* k_norm, float eps,
+                                        const float* rope_cur, void* kcache, void* vcache, int32_t n_q, int32_t n_kv, int32_t max_ctx, int32_t nsplit,
+                                        float scale_div, float* pm, float* pl, float* po);
 /* Rows [0, M1) of an M x N bf16 GEMM that launch_gemm256 gives to the 256 x 256 kernel when it hands the trailing rows to the small
  * tiles (wave quantisation; 0: no split).  Host arithmetic, no device needed. */
 int32_t q3a_gemm256_split_rows(int32_t M, int32_t N);

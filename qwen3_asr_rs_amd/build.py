@@ -35,6 +35,13 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vector
 # .hip sources only: keeps the device assembly (<stem>-hip-amdgcn-amd-amdhsa-gfx950.s) next to the object for scan_isa().  Part
 # of the stamp (hashed below with FLAGS), and an object whose assembly is gone counts as stale.
 HIP_FLAGS = ["-x", "hip", "-save-temps=obj"]
+# Kernel-argument preload (gfx950): the command processor writes the first dwords of the kernarg segment into user SGPRs when it
+# launches a wave (14 is what fits next to the kernarg pointer), so a kernel whose leading parameters are flat -- pointers and
+# ints, not a struct by value -- starts with them in registers instead of behind a scalar load that always misses (csrc/dev.h).
+# hipcc puts a compatibility header in front of every such kernel (the same dwords by s_load) for firmware that does not preload.
+# An LLVM option may appear only once on a command line, so an A/B variant cannot override it by appending: a variant whose
+# defines contain -DQ3A_NO_KERNARG_PRELOAD is built without it.
+KERNARG_PRELOAD_FLAGS = ["-mllvm", "-amdgpu-kernarg-preload-count=14"]
 
 # A/B builds for kernel experiments: Q3A_BUILD_VARIANT=name Q3A_BUILD_DEFINES="-DX=1 ..." builds
 # lib/libq3asr_hip_<name>.so next to the product library (load it with Q3A_LIB=<path>, see _lib.py).
@@ -44,6 +51,8 @@ if _VARIANT:
     OBJ_DIR = OBJ_DIR + "_" + _VARIANT
     LIB_PATH = os.path.join(LIB_DIR, f"libq3asr_hip_{_VARIANT}.so")
     CLI_PATH = os.path.join(BIN_DIR, f"asr_{_VARIANT}")
+if "-DQ3A_NO_KERNARG_PRELOAD" not in FLAGS:
+    HIP_FLAGS = HIP_FLAGS + KERNARG_PRELOAD_FLAGS
 
 
 def _hash(paths) -> str:

@@ -5,19 +5,34 @@
 
 // Phase stamps for tools/phase_probe.hip (probe builds define Q3A_STAMP; the product library never does): thread 0 of a
 // workgroup records the 100 MHz wall clock at up to 8 phase boundaries of the kernel.
+// The clock is read BEFORE the stamp pointer is looked at, and kernels whose pointer rides in an argument tail (below) take their
+// entry stamp into a register (Q3A_STAMP_ENTRY) and store it with the next one (Q3A_STAMP_PUT): waiting for the pointer at entry
+// would put the scalar round trip back that the preloaded head removes, in the probe build only.
 #ifdef Q3A_STAMP
 #define Q3A_STAMP_FIELD unsigned long long* stamp = nullptr;  /* [workgroup][8], null = off */
-#define Q3A_STAMP_AT(ptr, wg, slot) do { if ((ptr) && threadIdx.x == 0) (ptr)[(size_t)(wg) * 8 + (slot)] = wall_clock64(); } while (0)
+#define Q3A_STAMP_PUT(ptr, wg, slot, val) do { if ((ptr) && threadIdx.x == 0) (ptr)[(size_t)(wg) * 8 + (slot)] = (val); } while (0)
+#define Q3A_STAMP_AT(ptr, wg, slot) do { const unsigned long long q3a_t_ = wall_clock64(); Q3A_STAMP_PUT(ptr, wg, slot, q3a_t_); } while (0)
+#define Q3A_STAMP_ENTRY(var) const unsigned long long var = wall_clock64()
 #else
 #define Q3A_STAMP_FIELD
+#define Q3A_STAMP_PUT(ptr, wg, slot, val) do { } while (0)
 #define Q3A_STAMP_AT(ptr, wg, slot) do { } while (0)
+#define Q3A_STAMP_ENTRY(var) do { } while (0)
 #endif
 
 // hipcc loads kernel arguments lazily -- a scalar load right in front of each first use -- and on this chip a scalar load
 // that misses (the kernarg segment of a fresh dispatch always does) is a 0.3-0.5 us round trip: the stamped timelines of
 // tools/phase_probe.hip showed 1.4-2.2 us between a kernel's entry and its last load request, most of it three or four
 // such round trips in series.  Q3A_ARG(x) makes x (a kernel-argument expression) resident in SGPRs at that point; a
-// block of them at the top of a kernel turns the series into ONE clause that overlaps the address arithmetic.
+// block of them turns the series into ONE clause.
+// The kernels of the one-sequence decode chain (k_gemv.hip gemv1_kernel / gemv1_head_kernel / lm_head_*, k_dattn.hip
+// decode_attn_kernel, k_decode.hip argmax_finalize_kernel) go one step further and do not wait for that clause in front of their
+// first memory request either: their leading parameters are flat -- pointers first, then ints, at most 14 dwords -- and the
+// command processor preloads those into SGPRs when it launches a wave (build.py KERNARG_PRELOAD_FLAGS; a struct by value is a
+// byref argument and is never preloaded).  The head holds what the first requests are addressed with; everything else is a tail
+// struct behind it, which holds no head field.  What the clause still carries there is the tail: a Q3A_ARG block BEHIND the
+// requests fetches it in one round trip that overlaps the loads in flight.  Firmware that does not preload runs the compiler's
+// compatibility header (the same dwords by s_load, one wait), which costs what the old first clause cost.
 #define Q3A_ARG(x) asm volatile("" ::"s"(x))
 
 namespace q3a {

@@ -71,14 +71,15 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& a, const 
   __shared__ float cm[DA_WAVES][GROUP], cl[DA_WAVES][GROUP];
   __shared__ float co[DA_WAVES][GROUP][128];
   // pos in front of the Q3A_ARG block: behind it (asm volatile) hipcc no longer proves the location clobber-free and turns
-  // the scalar load into a vector load that it waits for at once
+  // the scalar load into a vector load that it waits for at once.  a.pos is a preloaded head argument (decode_attn_kernel), so this
+  // is ONE scalar round trip from the wave's first instruction, not two in series.
   const int pos = a.pos[s];
-  // every argument in one scalar-load clause (dev.h Q3A_ARG) instead of three scalar round trips in series
-  Q3A_ARG(a.qkv); Q3A_ARG(a.pos); Q3A_ARG(a.q_norm); Q3A_ARG(a.k_norm); Q3A_ARG(a.eps); Q3A_ARG(a.rope_cur); Q3A_ARG(a.kcache); Q3A_ARG(a.vcache);
-  Q3A_ARG(a.pm); Q3A_ARG(a.pl); Q3A_ARG(a.po); Q3A_ARG(a.nsplit); Q3A_ARG(a.n_q); Q3A_ARG(a.n_kv); Q3A_ARG(a.max_ctx); Q3A_ARG(a.scale_div);
+  // the tail in one scalar-load clause (dev.h Q3A_ARG) next to it, ONE wait for both (without the last entry hipcc sinks the load of
+  // pos below the first requests, behind a wait of its own); the head arguments are in SGPRs already
+  Q3A_ARG(a.q_norm); Q3A_ARG(a.k_norm); Q3A_ARG(a.eps); Q3A_ARG(a.pm); Q3A_ARG(a.pl); Q3A_ARG(a.po); Q3A_ARG(a.scale_div); Q3A_ARG(pos);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int stamp_wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-  Q3A_STAMP_AT(a.stamp, stamp_wg, 0);  // entry
+  Q3A_STAMP_ENTRY(t_entry);  // (behind the clause above, where the entry stamp has always been)
   const int sub = lane % LPK, kq = lane / LPK;
   const int key_lo = sp * KEYS_PER_SPLIT;
   const size_t pbase = ((size_t)s * a.n_q + (size_t)kvh * GROUP) * a.nsplit + sp;  // + g * nsplit
@@ -124,6 +125,7 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& a, const 
   }
   __builtin_amdgcn_sched_barrier(0);
   Q3A_STAMP_AT(a.stamp, stamp_wg, 1);  // every load requested
+  Q3A_STAMP_PUT(a.stamp, stamp_wg, 0, t_entry);  // entry
   if (key_lo > pos) {  // this split holds no key yet: statistics of an empty set, zeroed output
     if (tid < GROUP) { a.pm[pbase + (size_t)tid * a.nsplit] = -INFINITY; a.pl[pbase + (size_t)tid * a.nsplit] = 0.f; }
     if (tid < GROUP * 128) a.po[(pbase + (size_t)(tid >> 7) * a.nsplit) * 128 + (tid & 127)] = 0.f;
@@ -258,8 +260,26 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& a, const 
   Q3A_STAMP_AT(a.stamp, stamp_wg, 5);
 }
 
+// Kernel arguments: a flat head of 14 dwords that the command processor preloads into SGPRs at wave launch (build.py
+// KERNARG_PRELOAD_FLAGS; k_gemv.hip has the scheme) -- the cache and row pointers and the dimensions every request address is made
+// of, and pos -- then the tail, which holds no head field.
+struct DecodeAttnTail {
+  const float* q_norm; const float* k_norm; float eps;
+  float* pm; float* pl; float* po;
+  float scale_div;
+  Q3A_STAMP_FIELD
+};
 template <int GROUP, typename KVT>
-__global__ __launch_bounds__(DA_WAVES * 64) void decode_attn_kernel(DecodeAttnArgs a) {
+__global__ __launch_bounds__(DA_WAVES * 64) void decode_attn_kernel(void* kcache, void* vcache, const int* pos, const float* qkv,
+                                                                    const float* rope_cur, int nsplit, int n_q, int n_kv, int max_ctx,
+                                                                    DecodeAttnTail t) {
+  DecodeAttnArgs a{};
+  a.kcache = kcache; a.vcache = vcache; a.pos = pos; a.qkv = qkv; a.rope_cur = rope_cur; a.nsplit = nsplit; a.n_q = n_q; a.n_kv = n_kv;
+  a.max_ctx = max_ctx;
+  a.q_norm = t.q_norm; a.k_norm = t.k_norm; a.eps = t.eps; a.pm = t.pm; a.pl = t.pl; a.po = t.po; a.scale_div = t.scale_div;
+#ifdef Q3A_STAMP
+  a.stamp = t.stamp;
+#endif
   decode_attn_body<GROUP, KVT>(a, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
@@ -621,16 +641,23 @@ const char* launch_decode_attn(const DecodeAttnArgs& a, int S, bool kv_f32, hipS
   // layer's K / V rows into the XCD-local L2s: -1.4 % per step on one box, +1.2 % on another, every partial form slower; removed,
   // docs/HISTORY.md 3.2, commit 3ac6499 has the code.)
   dim3 grid(a.n_kv, S, a.nsplit), block(DA_WAVES * 64);
+  DecodeAttnTail t{};
+  t.q_norm = a.q_norm; t.k_norm = a.k_norm; t.eps = a.eps; t.pm = a.pm; t.pl = a.pl; t.po = a.po; t.scale_div = a.scale_div;
+#ifdef Q3A_STAMP
+  t.stamp = a.stamp;
+#endif
+#define Q3A_DA_ARGS a.kcache, a.vcache, a.pos, a.qkv, a.rope_cur, a.nsplit, a.n_q, a.n_kv, a.max_ctx, t
 #define Q3A_DA(G)                                                                                   \
   do {                                                                                              \
-    if (kv_f32) hipLaunchKernelGGL((decode_attn_kernel<G, float>), grid, block, 0, s, a);          \
-    else hipLaunchKernelGGL((decode_attn_kernel<G, uint16_t>), grid, block, 0, s, a);              \
+    if (kv_f32) hipLaunchKernelGGL((decode_attn_kernel<G, float>), grid, block, 0, s, Q3A_DA_ARGS); \
+    else hipLaunchKernelGGL((decode_attn_kernel<G, uint16_t>), grid, block, 0, s, Q3A_DA_ARGS);     \
   } while (0)
   if (group == 1) Q3A_DA(1);
   else if (group == 2) Q3A_DA(2);
   else if (group == 4) Q3A_DA(4);
   else return "decode_attn: GQA group must be 1, 2 or 4";
 #undef Q3A_DA
+#undef Q3A_DA_ARGS
   return nullptr;
 }
 

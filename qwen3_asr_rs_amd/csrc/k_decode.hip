@@ -103,8 +103,26 @@ __global__ __launch_bounds__(256) void argmax_partial_kernel(const float* __rest
 
 // argmax, stage 2 + bookkeeping of the greedy loop.  LP (token log-probabilities): the chosen id's logit IS the global maximum M, so
 // lp = -log sum_p part.sum[p] e^(part.val[p] - M), the merged sum (<= 0: the partial that holds M contributes at least e^0 = 1).
+// Kernel arguments: a flat head of 14 dwords preloaded into SGPRs at wave launch (build.py KERNARG_PRELOAD_FLAGS; k_gemv.hip has the
+// scheme) -- what the first batch of requests is addressed with -- then the tail, which holds no head field.
+struct FinalizeTail {
+  float* part_sum;
+  int V; int out_stride; int advance;
+  uint8_t* done; int* n_done; int n_seq; int* host_progress;
+  const uint16_t* embed; int H; float* x_next; int eos0, eos1;
+  const float* cos_t; const float* sin_t; float* rope_cur;
+  NextNormOut nn;
+  float* out_lp;
+};
 template <bool LP>
-__global__ __launch_bounds__(1024) void argmax_finalize_kernel(FinalizeArgs a) {
+__global__ __launch_bounds__(1024) void argmax_finalize_kernel(float* part_val, int* part_idx, int* next_tok, int* out_ids, int* step_count,
+                                                               int* pos, int n_part, int part_stride, FinalizeTail t) {
+  FinalizeArgs a{};
+  a.part.val = part_val; a.part.idx = part_idx; a.next_tok = next_tok; a.out_ids = out_ids; a.step_count = step_count; a.pos = pos;
+  a.n_part = n_part; a.part.stride = part_stride;
+  a.part.sum = t.part_sum; a.V = t.V; a.out_stride = t.out_stride; a.advance = t.advance; a.done = t.done;
+  a.n_done = t.n_done; a.n_seq = t.n_seq; a.host_progress = t.host_progress; a.embed = t.embed; a.H = t.H; a.x_next = t.x_next;
+  a.eos0 = t.eos0; a.eos1 = t.eos1; a.cos_t = t.cos_t; a.sin_t = t.sin_t; a.rope_cur = t.rope_cur; a.nn = t.nn; a.out_lp = t.out_lp;
   __shared__ float bv[16], bs[LP ? 16 : 1];
   __shared__ int bi[16];
   __shared__ int tok_s;
@@ -114,15 +132,20 @@ __global__ __launch_bounds__(1024) void argmax_finalize_kernel(FinalizeArgs a) {
   // two loads and a vmcnt(0) per iteration, ten dependent L2 round trips for the 9496 partials of the one-sequence lm_head) and,
   // behind `pos`, the RoPE row of the next position.
   constexpr int FIN_PRE = 10;  // 10 240 partials (vocabulary 151 936 in 16-row blocks: 9496); more are folded by the loop below
-  const int np = a.pos[s] + a.advance;
+  const int pos0 = a.pos[s];
   const int sc = a.step_count[s];
-  const int was_done = a.done[s];
   ArgmaxAcc<LP> pre[FIN_PRE];
 #pragma unroll
   for (int j = 0; j < FIN_PRE; ++j) {
     const int i = tid + j * 1024;
     pre[j] = ArgmaxAcc<LP>::load(a.part, s, i < a.n_part ? i : a.n_part - 1);  // all three channels in the same batch
   }
+  // what is addressed through the tail comes behind the partials, which need the preloaded head only: the tail in one scalar-load
+  // clause (dev.h Q3A_ARG) while they are in flight, instead of one round trip in front of each first use
+  Q3A_ARG(a.advance); Q3A_ARG(a.done); Q3A_ARG(a.V); Q3A_ARG(a.out_stride); Q3A_ARG(a.n_done); Q3A_ARG(a.n_seq); Q3A_ARG(a.host_progress);
+  Q3A_ARG(a.embed); Q3A_ARG(a.H); Q3A_ARG(a.x_next); Q3A_ARG(a.eos0); Q3A_ARG(a.eos1); Q3A_ARG(a.cos_t); Q3A_ARG(a.sin_t); Q3A_ARG(a.rope_cur);
+  const int np = pos0 + a.advance;
+  const int was_done = a.done[s];
   float rope_v = 0.f;
   if (a.rope_cur && tid < 128) rope_v = tid < 64 ? a.cos_t[(size_t)np * 64 + tid] : a.sin_t[(size_t)np * 64 + tid - 64];
   ArgmaxAcc<LP> m;
@@ -207,8 +230,14 @@ const char* launch_argmax_finalize(const FinalizeArgs& a, int S, hipStream_t s) 
   if (!a.part.val) return "argmax_finalize: partial buffer missing";
   if (const char* e = argmax_partials_check(a.part, a.n_part)) return e;
   if (!a.part.sum != !a.out_lp) return "argmax_finalize: part.sum and out_lp go together";
-  if (a.part.sum) hipLaunchKernelGGL(argmax_finalize_kernel<true>, dim3(S), dim3(1024), 0, s, a);
-  else hipLaunchKernelGGL(argmax_finalize_kernel<false>, dim3(S), dim3(1024), 0, s, a);
+  FinalizeTail t{};
+  t.part_sum = a.part.sum; t.V = a.V; t.out_stride = a.out_stride; t.advance = a.advance; t.done = a.done;
+  t.n_done = a.n_done; t.n_seq = a.n_seq; t.host_progress = a.host_progress; t.embed = a.embed; t.H = a.H; t.x_next = a.x_next;
+  t.eos0 = a.eos0; t.eos1 = a.eos1; t.cos_t = a.cos_t; t.sin_t = a.sin_t; t.rope_cur = a.rope_cur; t.nn = a.nn; t.out_lp = a.out_lp;
+#define Q3A_FIN_ARGS a.part.val, a.part.idx, a.next_tok, a.out_ids, a.step_count, a.pos, a.n_part, a.part.stride, t
+  if (a.part.sum) hipLaunchKernelGGL(argmax_finalize_kernel<true>, dim3(S), dim3(1024), 0, s, Q3A_FIN_ARGS);
+  else hipLaunchKernelGGL(argmax_finalize_kernel<false>, dim3(S), dim3(1024), 0, s, Q3A_FIN_ARGS);
+#undef Q3A_FIN_ARGS
   return nullptr;
 }
 

@@ -18,6 +18,7 @@
 //   4. wavefront reduction on DPP (no LDS crossbar), fused epilogue.
 // x can also be assembled on the fly from the flash-decoding partials of k_dattn.hip (o_proj input).
 #include <algorithm>
+#include <type_traits>
 
 #include "argmax.h"
 
@@ -153,11 +154,6 @@ __device__ __forceinline__ void attn_merge8_ch(const GemvArgs& a, int b, int k, 
 #pragma unroll
   for (int e = 0; e < 8; ++e) x[e] *= inv;
 }
-template <bool FAST>
-__device__ __forceinline__ void attn_merge8(const GemvArgs& a, int b, int k, float (&x)[8]) {
-  if (a.attn_nsplit <= 4) attn_merge8_ch<FAST, 4>(a, b, k, x);  // kernel-argument condition: uniform
-  else attn_merge8_ch<FAST, 8>(a, b, k, x);
-}
 
 template <int PR>
 __device__ __forceinline__ void gemv_rows(const GemvArgs& a, int g, int (&prow)[PR]) {
@@ -269,13 +265,13 @@ __device__ __forceinline__ void gemv_epilogue(const GemvArgs& a, int g, const in
 // 2 KI (4 KI with the norm weight) -- and handed to the four waves through LDS: every wave needs the whole vector, and in the
 // register form each of them pulls it through the CU's texture-address path again (two thirds of a qkv workgroup's load
 // instructions were x and norm-weight re-reads).  Same values, same arithmetic.
-template <int PR, int KI, bool RMS, bool ATTN, int MF = 0, bool XL = false>
-__global__ __launch_bounds__(256) void gemv1_kernel(GemvArgs a) {
+template <int PR, int KI, bool RMS, bool ATTN, int MF, bool XL>
+__device__ __forceinline__ void gemv1_body(const GemvArgs& a) {
   static_assert(!XL || !ATTN, "the merged attention vector already goes through LDS");
   __shared__ __attribute__((aligned(16))) float xl_x[XL ? KI * 512 : 4], xl_w[(XL && RMS) ? KI * 512 : 4];
   __shared__ __attribute__((aligned(16))) float x_s[ATTN ? KI * 512 : 4];  // only the attention merge goes through LDS
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  Q3A_STAMP_AT(a.stamp, blockIdx.x, 0);  // entry
+  Q3A_STAMP_ENTRY(t_entry);
   const int K = a.K;
   // (an XCD-contiguous block -> row remap, so that each output line is dirtied in one L2 only, measured 0.6 % slower)
   const int g = blockIdx.x * 4 + wave;
@@ -356,6 +352,9 @@ __global__ __launch_bounds__(256) void gemv1_kernel(GemvArgs a) {
     __builtin_amdgcn_sched_barrier(0);  // the partials' requests stay in front of the weight stream
   }
   if (RMS || XL) { request_x(); request_w(); } else { request_w(); request_x(); }
+  // MF forms: the bias below is addressed through the tail, whose scalar loads hipcc issues behind the fence above; without this
+  // one it also puts their wait in front of the weight requests
+  if constexpr (ATTN && MF > 0) __builtin_amdgcn_sched_barrier(0);
   // epilogue operands (bias, residual) ride behind the stream instead of costing an L2 round trip at the very end
   float bv[PR], rv[PR];
 #pragma unroll
@@ -366,6 +365,10 @@ __global__ __launch_bounds__(256) void gemv1_kernel(GemvArgs a) {
   }
   __builtin_amdgcn_sched_barrier(0);  // every request is issued before anything is waited for
   Q3A_STAMP_AT(a.stamp, blockIdx.x, 1);  // every load requested
+  Q3A_STAMP_PUT(a.stamp, blockIdx.x, 0, t_entry);  // entry
+  // what is left of the tail, in one scalar clause under the loads in flight (dev.h Q3A_ARG)
+  Q3A_ARG(a.out); Q3A_ARG(a.fast_math);
+  if (ATTN) Q3A_ARG(a.attn_fast_exp);
   if constexpr (ATTN && MF > 0) {  // merge from the registers requested up front (same arithmetic as attn_merge8_ch<FAST, MF>, one chunk)
     if (mg_on) {
       const bool fast = a.attn_fast_exp != 0;
@@ -395,14 +398,25 @@ __global__ __launch_bounds__(256) void gemv1_kernel(GemvArgs a) {
       xr[it][1] = *reinterpret_cast<const float4*>(x_s + kk[it] + 4);
     }
   } else if (ATTN) {  // each wave merges a quarter of the vector, once per block
+    // The two kernel-argument choices (exponential, chunk size) are made OUTSIDE the loop over the wave's pieces: with both inside,
+    // every iteration carried four copies of the merge and the K = 6144 form no longer unrolled (kin / kk went to scratch).
+    auto merge_pieces = [&](auto fast_c, auto ch_c) {
 #pragma unroll
-    for (int it = 0; it < KI; ++it) {
-      if ((it & 3) == wave && kin[it]) {
-        float v[8];
-        if (a.attn_fast_exp) attn_merge8<true>(a, 0, kk[it], v); else attn_merge8<false>(a, 0, kk[it], v);
-        *reinterpret_cast<float4*>(x_s + kk[it]) = make_float4(v[0], v[1], v[2], v[3]);
-        *reinterpret_cast<float4*>(x_s + kk[it] + 4) = make_float4(v[4], v[5], v[6], v[7]);
+      for (int it = 0; it < KI; ++it) {
+        if ((it & 3) == wave && kin[it]) {
+          float v[8];
+          attn_merge8_ch<decltype(fast_c)::value, decltype(ch_c)::value>(a, 0, kk[it], v);
+          *reinterpret_cast<float4*>(x_s + kk[it]) = make_float4(v[0], v[1], v[2], v[3]);
+          *reinterpret_cast<float4*>(x_s + kk[it] + 4) = make_float4(v[4], v[5], v[6], v[7]);
+        }
       }
+    };
+    typedef std::integral_constant<int, 4> Ch4;
+    typedef std::integral_constant<int, 8> Ch8;
+    if (a.attn_fast_exp) {
+      if (a.attn_nsplit <= 4) merge_pieces(std::true_type{}, Ch4{}); else merge_pieces(std::true_type{}, Ch8{});
+    } else {
+      if (a.attn_nsplit <= 4) merge_pieces(std::false_type{}, Ch4{}); else merge_pieces(std::false_type{}, Ch8{});
     }
     __syncthreads();
 #pragma unroll
@@ -472,6 +486,49 @@ __global__ __launch_bounds__(256) void gemv1_kernel(GemvArgs a) {
       if (prow[i] >= 0) a.out[g * (PR / 2) + (i >> 1)] = silu_sel(acc[i][0], a.fast_math != 0) * acc[i + 1][0];
   }
   Q3A_STAMP_AT(a.stamp, blockIdx.x, 4);  // reduced and stored
+}
+
+// Kernel arguments of the one-sequence chain: a flat head, then a tail struct.  The head -- pointers first, at most 14 dwords -- is what
+// stands in front of the kernel's first memory request; the command processor preloads it into SGPRs at wave launch (build.py
+// KERNARG_PRELOAD_FLAGS), so the weight stream is requested without waiting for a scalar load of the kernarg segment.  A struct by
+// value is never preloaded: the tail (what the kernel needs only behind its requests) is fetched by ordinary scalar loads that
+// overlap them.  The tails hold NO head field, so no stale copy of one can be read; the kernels rebuild the launcher's GemvArgs
+// from head and tail in registers and run the one body.
+struct GemvTail {  // plain and norm-fused forms
+  float* out; int fast_math;
+  Q3A_STAMP_FIELD
+};
+struct GemvAttnTail {  // ATTN forms (o_proj: x = merged attention partials)
+  float* out; const float* bias; int attn_heads; int attn_fast_exp; int fast_math;
+  Q3A_STAMP_FIELD
+};
+#ifdef Q3A_STAMP
+#define Q3A_STAMP_COPY(dst, src) (dst).stamp = (src).stamp
+#else
+#define Q3A_STAMP_COPY(dst, src) do { } while (0)
+#endif
+template <int PR, int KI, bool RMS, bool ATTN, int MF = 0, bool XL = false>
+__global__ __launch_bounds__(256) void gemv1_kernel(const uint16_t* W, const float* x, const float* rms_w, const float* bias,
+                                                    const float* resid, int N, int K, int mode, float eps, GemvTail t) {
+  static_assert(!ATTN, "the ATTN forms take the partials in their head");
+  GemvArgs a{};
+  a.W = W; a.x = x; a.rms_w = rms_w; a.bias = bias; a.resid = resid; a.N = N; a.K = K; a.mode = mode; a.eps = eps;
+  a.out = t.out; a.fast_math = t.fast_math;
+  Q3A_STAMP_COPY(a, t);
+  gemv1_body<PR, KI, RMS, ATTN, MF, XL>(a);
+}
+// (The split count and the mode stand in front of the first partial / weight address.  out is first needed by the final store, and
+// the bias -- no o_proj of the models has one -- is requested behind the weight stream: both ride in the tail.)
+template <int PR, int KI, bool RMS, bool ATTN, int MF = 0, bool XL = false>
+__global__ __launch_bounds__(256) void gemv1_kernel(const float* attn_pm, const float* attn_pl, const float* attn_po, const uint16_t* W,
+                                                    const float* resid, int N, int K, int attn_nsplit, int mode, GemvAttnTail t) {
+  static_assert(ATTN && !RMS, "the plain forms take x and the norm weight in their head");
+  GemvArgs a{};
+  a.attn_pm = attn_pm; a.attn_pl = attn_pl; a.attn_po = attn_po; a.W = W; a.resid = resid; a.N = N; a.K = K; a.attn_nsplit = attn_nsplit;
+  a.mode = mode;
+  a.out = t.out; a.bias = t.bias; a.attn_heads = t.attn_heads; a.attn_fast_exp = t.attn_fast_exp; a.fast_math = t.fast_math;
+  Q3A_STAMP_COPY(a, t);
+  gemv1_body<PR, KI, RMS, ATTN, MF, XL>(a);
 }
 
 // ---- lm_head (mode 3, one sequence, fused final RMSNorm) -------------------------------------------------
@@ -560,14 +617,18 @@ __device__ __forceinline__ void gemv1_head_block(const GemvArgs& a, int blk, flo
   }
 }
 
+// (head / tail as gemv1_kernel: the tail is the partial descriptor, first needed by the block's final store)
 template <int PR, int KI, bool LP = false>
-__global__ __launch_bounds__(256) void gemv1_head_kernel(GemvArgs a) {
+__global__ __launch_bounds__(256) void gemv1_head_kernel(const uint16_t* W, const float* x, const float* rms_w, const float* bias, float* out,
+                                                         int N, int K, float eps, int fast_math, ArgmaxPartials part) {
   __shared__ float am_v[4][1];
   __shared__ int am_i[4][1];
   __shared__ float am_s[LP ? 4 : 1];
+  GemvArgs a{};
+  a.W = W; a.x = x; a.rms_w = rms_w; a.bias = bias; a.out = out; a.N = N; a.K = K; a.eps = eps; a.fast_math = fast_math; a.mode = 3;
   ArgmaxAcc<LP> r;
   gemv1_head_block<PR, KI, LP>(a, blockIdx.x, am_v, am_i, am_s, r);
-  if (threadIdx.x == 0) r.store(a.part, 0, blockIdx.x);
+  if (threadIdx.x == 0) r.store(part, 0, blockIdx.x);
 }
 
 // ---- pruned argmax of the one-sequence lm_head ------------------------------------------------------------
@@ -610,7 +671,7 @@ __global__ __launch_bounds__(256) void gemv1_head_kernel(GemvArgs a) {
 // Without a bias the kernel that runs is the one without the code (template parameter BIAS of lm_head_approx_body: false in
 // lm_head_approx_kernel, the launch of an engine that never set a bias, true in lm_head_approx_bias_kernel); pass 2 keeps
 // gemv1_head_block's uniform null check on a.bias.
-struct LmHeadArgsDev {
+struct LmHeadArgsDev {  // what both passes read; no kernel parameter: the kernels assemble it from their flat head and their tail
   GemvArgs g;
   const int8_t* Wq; const float* qs; int qcols;
   float gamma;
@@ -759,15 +820,43 @@ __device__ __forceinline__ void lm_head_approx_body(const LmHeadArgsDev& p) {
   if (lane == 0) { p.blk_lo[blk] = lo; p.blk_hi[blk] = hi; }
 }
 
+// kernel arguments as gemv1_kernel: what stands in front of the int8 stream is the head, the rest the tail
+struct LmHeadApproxTail {
+  float eps; int fast_math; float gamma;
+  float* blk_lo; float* blk_hi; float* dbg;
+};
+__device__ __forceinline__ LmHeadArgsDev lm_head_approx_args(const int8_t* Wq, const float* x, const float* rms_w, const float* qs, const float* bias,
+                                                             int N, int K, int qcols, int n_blk, const LmHeadApproxTail& t) {
+  LmHeadArgsDev p{};
+  p.Wq = Wq; p.g.x = x; p.g.rms_w = rms_w; p.qs = qs; p.g.bias = bias; p.g.N = N; p.g.K = K; p.qcols = qcols; p.n_blk = n_blk;
+  p.g.eps = t.eps; p.g.fast_math = t.fast_math; p.gamma = t.gamma; p.blk_lo = t.blk_lo; p.blk_hi = t.blk_hi; p.dbg = t.dbg;
+  return p;
+}
 template <int KI>
-__global__ __launch_bounds__(256) void lm_head_approx_kernel(LmHeadArgsDev p) { lm_head_approx_body<KI, false>(p); }
+__global__ __launch_bounds__(256) void lm_head_approx_kernel(const int8_t* Wq, const float* x, const float* rms_w, const float* qs, const float* bias,
+                                                             int N, int K, int qcols, int n_blk, LmHeadApproxTail t) {
+  lm_head_approx_body<KI, false>(lm_head_approx_args(Wq, x, rms_w, qs, bias, N, K, qcols, n_blk, t));
+}
 template <int KI>
-__global__ __launch_bounds__(256) void lm_head_approx_bias_kernel(LmHeadArgsDev p) { lm_head_approx_body<KI, true>(p); }  // with the logit bias
+__global__ __launch_bounds__(256) void lm_head_approx_bias_kernel(const int8_t* Wq, const float* x, const float* rms_w, const float* qs,
+                                                                  const float* bias, int N, int K, int qcols, int n_blk, LmHeadApproxTail t) {
+  lm_head_approx_body<KI, true>(lm_head_approx_args(Wq, x, rms_w, qs, bias, N, K, qcols, n_blk, t));  // with the logit bias
+}
 
 // Pass 2: T over every block, then this workgroup's blocks blockIdx.x + j * gridDim.x (at most 256) that pass hi_b >= T,
 // rescored in ascending order; one (value, row) partial per workgroup.  No workgroup waits for another.
+struct LmHeadRescoreTail {
+  const float* bias; float* out; int fast_math;
+  ArgmaxPartials part;
+  int* stats;
+};
 template <int PR, int KI>
-__global__ __launch_bounds__(256) void lm_head_rescore_kernel(LmHeadArgsDev p) {
+__global__ __launch_bounds__(256) void lm_head_rescore_kernel(const float* blk_lo, const float* blk_hi, const uint16_t* W, const float* x,
+                                                              const float* rms_w, int n_blk, int N, int K, float eps, LmHeadRescoreTail tl) {
+  LmHeadArgsDev p{};
+  p.blk_lo = const_cast<float*>(blk_lo); p.blk_hi = const_cast<float*>(blk_hi); p.g.W = W; p.g.x = x; p.g.rms_w = rms_w; p.n_blk = n_blk;
+  p.g.N = N; p.g.K = K; p.g.eps = eps;
+  p.g.bias = tl.bias; p.g.out = tl.out; p.g.fast_math = tl.fast_math; p.g.part = tl.part; p.stats = tl.stats; p.g.mode = 3;
   __shared__ float am_v[4][1];
   __shared__ int am_i[4][1];
   __shared__ float red[4];
@@ -910,6 +999,23 @@ __global__ __launch_bounds__(256) void gemvn_kernel(GemvArgs a) {
   gemv_epilogue<NB, PR, LP>(a, g, prow, acc, am_v, am_i, am_s);
 }
 
+// the kernels' flat heads and tails, in the order of their signatures
+#define GEMV_PLAIN_ARGS(a) (a).W, (a).x, (a).rms_w, (a).bias, (a).resid, (a).N, (a).K, (a).mode, (a).eps, gemv_tail(a)
+#define GEMV_ATTN_ARGS(a) (a).attn_pm, (a).attn_pl, (a).attn_po, (a).W, (a).resid, (a).N, (a).K, (a).attn_nsplit, (a).mode, gemv_attn_tail(a)
+#define GEMV_HEAD_ARGS(a) (a).W, (a).x, (a).rms_w, (a).bias, (a).out, (a).N, (a).K, (a).eps, (a).fast_math, (a).part
+GemvTail gemv_tail(const GemvArgs& a) {
+  GemvTail t{};
+  t.out = a.out; t.fast_math = a.fast_math;
+  Q3A_STAMP_COPY(t, a);
+  return t;
+}
+GemvAttnTail gemv_attn_tail(const GemvArgs& a) {
+  GemvAttnTail t{};
+  t.out = a.out; t.bias = a.bias; t.attn_heads = a.attn_heads; t.attn_fast_exp = a.attn_fast_exp; t.fast_math = a.fast_math;
+  Q3A_STAMP_COPY(t, a);
+  return t;
+}
+
 template <int PR, int KI>
 void launch1k(const GemvArgs& a, hipStream_t s) {
   const dim3 grid(gemv_blocks(a)), block(256);
@@ -917,24 +1023,24 @@ void launch1k(const GemvArgs& a, hipStream_t s) {
   // 0.6B x 1 and x 2, neutral at 1.7B; profiles/r6_ab_merge_first.txt); beyond, the chunked merge behind it
   if (a.attn_po) {
     if constexpr (KI <= 4) {  // (not instantiated beyond: never launched)
-      if (a.attn_nsplit <= 4) { hipLaunchKernelGGL((gemv1_kernel<PR, KI, false, true, 4>), grid, block, 0, s, a); return; }
-      if (a.attn_nsplit <= 8) { hipLaunchKernelGGL((gemv1_kernel<PR, KI, false, true, 8>), grid, block, 0, s, a); return; }
+      if (a.attn_nsplit <= 4) { hipLaunchKernelGGL((gemv1_kernel<PR, KI, false, true, 4>), grid, block, 0, s, GEMV_ATTN_ARGS(a)); return; }
+      if (a.attn_nsplit <= 8) { hipLaunchKernelGGL((gemv1_kernel<PR, KI, false, true, 8>), grid, block, 0, s, GEMV_ATTN_ARGS(a)); return; }
     }
-    hipLaunchKernelGGL((gemv1_kernel<PR, KI, false, true>), grid, block, 0, s, a);
+    hipLaunchKernelGGL((gemv1_kernel<PR, KI, false, true>), grid, block, 0, s, GEMV_ATTN_ARGS(a));
   } else if (a.rms_w) {
     // Norm-fused projections at K <= 1024 (qkv, gate / up at hidden 1024): x and the norm weight once per workgroup through LDS
     // (round 6: 609.7 -> 595.1 us per step at 0.6B, ids identical; profiles/r6_ab_gemv_x_lds.txt).  Not where it was measured to
     // lose: K = 2048 (+18 %: 32 KiB of LDS per workgroup halves the residency of the 1536-workgroup gate / up launch), the down
     // projection (+4 %: x in front of the weights delays them), the lm_head (+1.3 %: a barrier in each of 9496 workgroups).
     if (a.mode == 3) {
-      if (a.part.sum) hipLaunchKernelGGL((gemv1_head_kernel<PR, KI, true>), grid, block, 0, s, a);
-      else hipLaunchKernelGGL((gemv1_head_kernel<PR, KI>), grid, block, 0, s, a);
+      if (a.part.sum) hipLaunchKernelGGL((gemv1_head_kernel<PR, KI, true>), grid, block, 0, s, GEMV_HEAD_ARGS(a));
+      else hipLaunchKernelGGL((gemv1_head_kernel<PR, KI>), grid, block, 0, s, GEMV_HEAD_ARGS(a));
       return;
     }
-    if constexpr (KI == 2) { hipLaunchKernelGGL((gemv1_kernel<PR, KI, true, false, 0, true>), grid, block, 0, s, a); return; }
-    hipLaunchKernelGGL((gemv1_kernel<PR, KI, true, false>), grid, block, 0, s, a);
+    if constexpr (KI == 2) { hipLaunchKernelGGL((gemv1_kernel<PR, KI, true, false, 0, true>), grid, block, 0, s, GEMV_PLAIN_ARGS(a)); return; }
+    hipLaunchKernelGGL((gemv1_kernel<PR, KI, true, false>), grid, block, 0, s, GEMV_PLAIN_ARGS(a));
   } else {
-    hipLaunchKernelGGL((gemv1_kernel<PR, KI, false, false>), grid, block, 0, s, a);
+    hipLaunchKernelGGL((gemv1_kernel<PR, KI, false, false>), grid, block, 0, s, GEMV_PLAIN_ARGS(a));
   }
 }
 template <int PR>
@@ -984,13 +1090,16 @@ const char* launch_lm_head_approx(const LmHeadPruneArgs& a, hipStream_t s) {
   if (const char* e = lm_head_prune_check(a)) return e;
   const LmHeadArgsDev p = lm_head_dev_args(a);
   const dim3 grid((p.n_blk + 3) / 4), block(256);
+  const LmHeadApproxTail t{p.g.eps, p.g.fast_math, p.gamma, p.blk_lo, p.blk_hi, p.dbg};
+#define LM_HEAD_APPROX_ARGS p.Wq, p.g.x, p.g.rms_w, p.qs, p.g.bias, p.g.N, p.g.K, p.qcols, p.n_blk, t
   if (a.g.bias) {
-    if (a.qcols == 1024) hipLaunchKernelGGL(lm_head_approx_bias_kernel<2>, grid, block, 0, s, p);
-    else hipLaunchKernelGGL(lm_head_approx_bias_kernel<4>, grid, block, 0, s, p);
+    if (a.qcols == 1024) hipLaunchKernelGGL(lm_head_approx_bias_kernel<2>, grid, block, 0, s, LM_HEAD_APPROX_ARGS);
+    else hipLaunchKernelGGL(lm_head_approx_bias_kernel<4>, grid, block, 0, s, LM_HEAD_APPROX_ARGS);
   } else {
-    if (a.qcols == 1024) hipLaunchKernelGGL(lm_head_approx_kernel<2>, grid, block, 0, s, p);
-    else hipLaunchKernelGGL(lm_head_approx_kernel<4>, grid, block, 0, s, p);
+    if (a.qcols == 1024) hipLaunchKernelGGL(lm_head_approx_kernel<2>, grid, block, 0, s, LM_HEAD_APPROX_ARGS);
+    else hipLaunchKernelGGL(lm_head_approx_kernel<4>, grid, block, 0, s, LM_HEAD_APPROX_ARGS);
   }
+#undef LM_HEAD_APPROX_ARGS
   return nullptr;
 }
 int lm_head_rescore_groups(const GemvArgs& g, int n_cu) {
@@ -1001,8 +1110,11 @@ const char* launch_lm_head_rescore(const LmHeadPruneArgs& a, int groups, hipStre
   if (const char* e = lm_head_prune_check(a)) return e;
   const LmHeadArgsDev p = lm_head_dev_args(a);
   if (groups < 1 || groups > a.g.part.stride || (p.n_blk + groups - 1) / groups > 256) return "lm_head_prune: bad rescore grid";
-  if (a.qcols == 1024) hipLaunchKernelGGL((lm_head_rescore_kernel<4, 2>), dim3(groups), dim3(256), 0, s, p);
-  else hipLaunchKernelGGL((lm_head_rescore_kernel<4, 4>), dim3(groups), dim3(256), 0, s, p);
+  const LmHeadRescoreTail t{p.g.bias, p.g.out, p.g.fast_math, p.g.part, p.stats};
+#define LM_HEAD_RESCORE_ARGS p.blk_lo, p.blk_hi, p.g.W, p.g.x, p.g.rms_w, p.n_blk, p.g.N, p.g.K, p.g.eps, t
+  if (a.qcols == 1024) hipLaunchKernelGGL((lm_head_rescore_kernel<4, 2>), dim3(groups), dim3(256), 0, s, LM_HEAD_RESCORE_ARGS);
+  else hipLaunchKernelGGL((lm_head_rescore_kernel<4, 4>), dim3(groups), dim3(256), 0, s, LM_HEAD_RESCORE_ARGS);
+#undef LM_HEAD_RESCORE_ARGS
   return nullptr;
 }
 

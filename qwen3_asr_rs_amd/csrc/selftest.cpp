@@ -327,6 +327,109 @@ int32_t q3a_selftest_repeat(int32_t device, const float* logits, int32_t S, int3
   Q3A_CATCH(nullptr)
 }
 
+int32_t q3a_selftest_gemv_launch(int32_t device, int32_t pruned, const uint16_t* w, int32_t N, int32_t K, const float* x, const float* rms_w, float eps,
+                                 const float* bias, int32_t mode, const float* resid, const float* attn_pm, const float* attn_pl, const float* attn_po,
+                                 int32_t attn_nsplit, int32_t attn_heads, float* out, int32_t* out_state) {
+  Q3A_TRY(nullptr)
+  const char* what = "q3a_selftest_gemv_launch";
+  // every index the launches will form is checked here: a refusal, never an access outside a buffer
+  if (!w || N < 1 || K < 8 || K % 8 != 0 || K > 6144 || mode < 0 || mode > 3 || (pruned != 0 && pruned != 1)) fail(std::string(what) + ": bad argument");
+  const bool attn = attn_po != nullptr;
+  if (attn ? (x || rms_w || !attn_pm || !attn_pl || attn_nsplit < 1 || attn_heads < 1 || K != attn_heads * 128 ||
+              (long)attn_heads * attn_nsplit > GEMV_ATTN_MAX_TABLE) : (!x || attn_pm || attn_pl))
+    fail(std::string(what) + ": x alone, or the three partial arrays with K = heads * 128 alone");
+  if (mode == 2 && N % 32 != 0) fail(std::string(what) + ": GLU needs N % 32 == 0");
+  if ((mode == 1) != (resid != nullptr)) fail(std::string(what) + ": the residual goes with mode 1");
+  if (mode == 3 ? (!rms_w || !out_state) : (!out || pruned)) fail(std::string(what) + ": mode 3 needs the norm weight and out_state, the other modes out");
+  if (pruned && out) fail(std::string(what) + ": the pruned argmax stores no logits");
+  use_device(device);
+  const size_t n_out = mode == 2 ? (size_t)N / 2 : (size_t)N;
+  const DevBuf dW = to_device(w, (size_t)N * K);
+  DevBuf dX, dG, dB, dR, dPm, dPl, dPo;
+  if (x) dX = to_device(x, (size_t)K);
+  if (rms_w) dG = to_device(rms_w, (size_t)K);
+  if (bias) dB = to_device(bias, (size_t)N);
+  if (resid) dR = to_device(resid, (size_t)N);
+  if (attn) {
+    // the kernels read a head's statistics 16 bytes at a time, past the last head's own into the allocation's padding: NaN there
+    const size_t ns = (size_t)attn_heads * attn_nsplit;
+    std::vector<float> pm(ns + 8, NAN), pl(ns + 8, NAN);
+    memcpy(pm.data(), attn_pm, ns * 4); memcpy(pl.data(), attn_pl, ns * 4);
+    dPm = to_device(pm); dPl = to_device(pl); dPo = to_device(attn_po, ns * 128);
+  }
+  Guarded dO;
+  if (out) dO = Guarded(out, n_out * 4);
+  GemvArgs g{};
+  g.x = dX.as<float>(); g.ldx = K; g.rms_w = dG.as<float>(); g.eps = eps; g.W = dW.as<uint16_t>(); g.N = N; g.K = K; g.bias = dB.as<float>();
+  g.mode = mode; g.out = dO.as<float>(); g.ldo = (int)n_out; g.resid = dR.as<float>();
+  g.attn_pm = dPm.as<float>(); g.attn_pl = dPl.as<float>(); g.attn_po = dPo.as<float>(); g.attn_nsplit = attn_nsplit; g.attn_heads = attn_heads;
+  g.attn_fast_exp = 0; g.fast_math = 0;  // the precise arithmetic: only fp32 rounding enters
+  if (mode != 3) {
+    KCHK(launch_gemv(g, 1, nullptr));
+    finish();
+    dO.fetch(out, "output");
+  } else {
+    int n_part = gemv_blocks(g);
+    const DevBuf dPv = room((size_t)n_part * 4), dPi = room((size_t)n_part * 4);
+    g.part = ArgmaxPartials{dPv.as<float>(), dPi.as<int>(), nullptr, n_part};
+    DevBuf dQ, dQs, dLo, dHi;
+    if (pruned) {
+      LmHeadPruneArgs pa{};
+      pa.g = g; pa.qcols = lm_head_q_cols(K); pa.logit_bias = bias ? 1 : 0;
+      if (pa.qcols == 0) fail(std::string(what) + ": hidden size beyond the pruned argmax");
+      const size_t nb4 = ((size_t)lm_head_prune_blocks(g) + 3) / 4 * 4;
+      dQ = room((size_t)N * pa.qcols); dQs = room((size_t)N * 16); dLo = room(nb4 * 4); dHi = room(nb4 * 4);
+      pa.Wq = dQ.as<int8_t>(); pa.qs = dQs.as<float>(); pa.blk_lo = dLo.as<float>(); pa.blk_hi = dHi.as<float>();
+      KCHK(lm_head_prune_check(pa));
+      KCHK(launch_lm_head_quantize(g.W, N, K, dQ.as<int8_t>(), dQs.as<float>(), nullptr));
+      n_part = lm_head_rescore_groups(g, 0);
+      KCHK(launch_lm_head_approx(pa, nullptr));
+      KCHK(launch_lm_head_rescore(pa, n_part, nullptr));
+    } else {
+      KCHK(launch_gemv(g, 1, nullptr));
+    }
+    // finalize as the greedy loop runs it, from a state in which every counter it touches is visible: step 2 of 4, position 5
+    constexpr int STRIDE = 4, STEP = 2, POS = 5;
+    const DevBuf dTok = to_device(std::vector<int>(1, -1)), dIds = to_device(std::vector<int>(STRIDE, -1)), dSc = to_device(std::vector<int>(1, STEP));
+    const DevBuf dPos = to_device(std::vector<int>(1, POS)), dDone = to_device(std::vector<uint8_t>(1, 0)), dXn = room((size_t)K * 4);
+    FinalizeArgs f{};
+    f.part = g.part; f.n_part = n_part; f.V = N; f.next_tok = dTok.as<int>(); f.out_ids = dIds.as<int>(); f.out_stride = STRIDE;
+    f.step_count = dSc.as<int>(); f.pos = dPos.as<int>(); f.advance = 1; f.done = dDone.as<uint8_t>(); f.n_seq = 1;
+    f.embed = g.W; f.H = K; f.x_next = dXn.as<float>(); f.eos0 = -1; f.eos1 = -1;  // (the embedding row of the chosen id: a row of w)
+    KCHK(launch_argmax_finalize(f, 1, nullptr));
+    finish();
+    if (out) dO.fetch(out, "output");
+    const std::vector<int> ids = to_host<int>(dIds, STRIDE);
+    out_state[0] = to_host<int>(dTok, 1)[0]; out_state[1] = ids[STEP]; out_state[2] = to_host<int>(dSc, 1)[0]; out_state[3] = to_host<int>(dPos, 1)[0];
+  }
+  Q3A_CATCH(nullptr)
+}
+
+int32_t q3a_selftest_decode_attn_launch(int32_t device, int32_t kv_f32, const float* qkv, int32_t pos, const float* q_norm, const float* k_norm, float eps,
+                                        const float* rope_cur, void* kcache, void* vcache, int32_t n_q, int32_t n_kv, int32_t max_ctx, int32_t nsplit,
+                                        float scale_div, float* pm, float* pl, float* po) {
+  Q3A_TRY(nullptr)
+  const char* what = "q3a_selftest_decode_attn_launch";
+  if (!qkv || !q_norm || !k_norm || !rope_cur || !kcache || !vcache || !pm || !pl || !po || n_q < 1 || n_kv < 1 || n_q % n_kv != 0 || max_ctx < 1 ||
+      nsplit < 1 || !(scale_div > 0.f))
+    fail(std::string(what) + ": bad argument");
+  const int keys = dattn_keys_per_split(kv_f32 != 0);
+  if (pos < 0 || pos >= max_ctx || pos >= nsplit * keys) fail(std::string(what) + ": pos outside the cache or beyond the last split");
+  use_device(device);
+  const size_t eb = kv_f32 ? 4 : 2, n_cache = (size_t)n_kv * max_ctx * 128, ns = (size_t)n_q * nsplit;
+  const DevBuf dQkv = to_device(qkv, (size_t)(n_q + 2 * n_kv) * 128), dQn = to_device(q_norm, 128), dKn = to_device(k_norm, 128);
+  const DevBuf dRope = to_device(rope_cur, 128), dPos = to_device(std::vector<int>(1, pos));
+  const Guarded dK(kcache, n_cache * eb), dV(vcache, n_cache * eb), dPm(pm, ns * 4), dPl(pl, ns * 4), dPo(po, ns * 128 * 4);
+  DecodeAttnArgs a{};
+  a.qkv = dQkv.as<float>(); a.pos = dPos.as<int>(); a.q_norm = dQn.as<float>(); a.k_norm = dKn.as<float>(); a.eps = eps; a.rope_cur = dRope.as<float>();
+  a.kcache = dK.as<void>(); a.vcache = dV.as<void>(); a.pm = dPm.as<float>(); a.pl = dPl.as<float>(); a.po = dPo.as<float>();
+  a.nsplit = nsplit; a.n_q = n_q; a.n_kv = n_kv; a.max_ctx = max_ctx; a.scale_div = scale_div;
+  KCHK(launch_decode_attn(a, 1, kv_f32 != 0, nullptr));
+  finish();
+  dK.fetch(kcache, "key cache"); dV.fetch(vcache, "value cache"); dPm.fetch(pm, "split maxima"); dPl.fetch(pl, "split sums"); dPo.fetch(po, "split outputs");
+  Q3A_CATCH(nullptr)
+}
+
 int32_t q3a_selftest_draft_accept(int32_t device, int32_t S, const int32_t* draft_ids, const int32_t* draft_off, const int32_t* prompt_lens,
                                   const int32_t* top_ids, const float* top_lp, int32_t out_stride, const uint16_t* embed, int32_t V, int32_t H,
                                   const float* norm_w, int32_t group_size, const float* cos_t, const float* sin_t, int32_t max_pos,
