@@ -270,28 +270,36 @@ struct DecodeStep : StepView {
     }
     if (repeat) n_part = enqueue_repetition(part, !sample);
     FinalizeArgs f{};
-    f.part = part; f.n_part = n_part; f.out_lp = part.sum ? out_lp.as<float>() : nullptr;
-    f.V = V; f.next_tok = next_tok.as<int>(); f.out_ids = out_ids.as<int>();
-    f.out_stride = max_new; f.step_count = step_count.as<int>(); f.pos = d_pos.as<int>(); f.advance = advance;
-    f.done = done.as<uint8_t>(); f.n_done = n_done.as<int>(); f.n_seq = S; f.host_progress = host_prog_dev; f.embed = wh(L.embed); f.H = H; f.x_next = x_dec.as<float>(); f.eos0 = kEos0; f.eos1 = kEos1;
-    f.cos_t = rope_cos.as<float>(); f.sin_t = rope_sin.as<float>(); f.rope_cur = rope_cur.as<float>();
-    f.nn = first_layer_norm_out();
+    f.part = part; f.n_part = n_part; f.V = V; f.advance = advance; f.c = commit();
     if (sample) enqueue_sampler(f);
     timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_finalize(f, S, stream)); });
     if (sample && token_lp()) enqueue_sample_logprob();
+  }
+  // What a committed token leaves behind (kernels.h StepCommit), in the live buffers: the ONE place that names them for that purpose,
+  // whichever launch commits (finalize, draft accept, a fed token).
+  StepCommit commit() const {
+    StepCommit c{};
+    c.next_tok = next_tok.as<int>(); c.out_ids = out_ids.as<int>(); c.out_stride = max_new; c.out_lp = token_lp() ? out_lp.as<float>() : nullptr;
+    c.step_count = step_count.as<int>(); c.pos = d_pos.as<int>();
+    c.done = done.as<uint8_t>(); c.n_done = n_done.as<int>(); c.n_seq = B; c.host_progress = host_prog_dev;
+    c.embed = wh(L.embed); c.H = d.hidden; c.x_next = x_dec.as<float>(); c.eos0 = kEos0; c.eos1 = kEos1;
+    c.cos_t = rope_cos.as<float>(); c.sin_t = rope_sin.as<float>(); c.rope_cur = rope_cur.as<float>();
+    c.nn = first_layer_norm_out();
+    return c;
   }
   // Draft verification (k_draft.hip), in the place of the prefill's run_head(0): from the verify head's argmax per row to the state the
   // greedy loop has after the accepted tokens.  It writes the step's buffers, so it is enqueued here; `a` arrives with the call's own
   // inputs (draft, offsets, prompt lengths, the head's top_id / top_lp: buffers of one prefill that no captured launch ever sees).
   void enqueue_draft_accept(DraftAcceptArgs a) {
-    a.n_seq = B; a.accepted = draft_accepted.as<int>();
-    a.next_tok = next_tok.as<int>(); a.out_ids = out_ids.as<int>(); a.out_stride = max_new; a.step_count = step_count.as<int>(); a.pos = d_pos.as<int>();
-    a.out_lp = token_lp() ? out_lp.as<float>() : nullptr;
-    a.done = done.as<uint8_t>(); a.n_done = n_done.as<int>(); a.host_progress = host_prog_dev;
-    a.embed = wh(L.embed); a.H = d.hidden; a.x_next = x_dec.as<float>(); a.eos0 = kEos0; a.eos1 = kEos1;
-    a.cos_t = rope_cos.as<float>(); a.sin_t = rope_sin.as<float>(); a.rope_cur = rope_cur.as<float>();
-    a.nn = first_layer_norm_out();
+    a.n_seq = B; a.accepted = draft_accepted.as<int>(); a.c = commit();
     timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_draft_accept(a, stream)); });
+  }
+  // teacher forcing and the beam round: tok [B] (device) is what the next step feeds
+  void enqueue_set_tokens(const int* tok) { KCHK(launch_set_tokens(tok, B, commit(), stream)); }
+  // the same from host ids (q3a_set_next_tokens), through the step's own staging buffer
+  void enqueue_forced_tokens(const int32_t* ids) {
+    HIPCHK(hipMemcpy(forced_tok.p, ids, (size_t)B * 4, hipMemcpyHostToDevice));
+    enqueue_set_tokens(forced_tok.as<int>());
   }
   // Repetition penalty and no-repeat n-grams (k_repeat.hip): the stored rows, in place, from each sequence's own out_ids
   // (l' -> l'').  The head's partials, where it wrote any, are those of l': with `partials` the rewritten rows' own, log-sum channel
@@ -311,7 +319,7 @@ struct DecodeStep : StepView {
     SampleArgs sa{};
     sa.logits = logits.as<float>(); sa.S = B; sa.V = d.vocab; sa.params = samp_params.as<uint32_t>(); sa.step_count = step_count.as<int>();
     sa.chunk_max = samp_max.as<float>(); sa.chunk_sum = samp_sum.as<float>();
-    f.part.sum = nullptr; f.out_lp = nullptr; f.n_part = sample_chunks(d.vocab);
+    f.part.sum = nullptr; f.c.out_lp = nullptr; f.n_part = sample_chunks(d.vocab);
     sa.part = f.part;
     timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_sample(sa, stream)); });
   }
@@ -544,9 +552,7 @@ struct DecodeStep : StepView {
     r.kcache = kcache.p; r.vcache = vcache.p; r.elem_bytes = (int)kv_elem(); r.layers = d.dec_layers; r.S = S; r.n_kv = d.n_kv; r.max_ctx = max_ctx;
     r.parent = a.parent; r.lo = a.lo; r.hi = a.pos; r.hi_bias = -1; r.all_done = a.state + BEAM_ST_ALL_DONE;
     timed(Q3A_KC_OTHER, 0, [&] { KCHK(launch_kv_reorder(r, stream)); });
-    timed(Q3A_KC_OTHER, 0, [&] {
-      KCHK(launch_set_tokens(a.feed, S, wh(L.embed), d.hidden, x_dec.as<float>(), next_tok.as<int>(), stream, first_layer_norm_out()));
-    });
+    timed(Q3A_KC_OTHER, 0, [&] { enqueue_set_tokens(a.feed); });
   }
 };
 
@@ -1349,22 +1355,41 @@ struct q3a_engine {
     timings.encoder_ms = stage_ms(1, 2);
     timings.total_ms = stage_ms(0, 4);
   }
+  // What both row heads share (kernels.h RowHeadArgs), workspace sized: the M rows align_rows names of the last prefill's residual
+  // stream, the final norm, W = lm_head [N][hidden] (the aligner's classifier sits there); log_sum: partials with that channel;
+  // want_logits: the only M x N buffer, and only on request.
+  void fill_row_head(RowHeadArgs& a, int M, int N, bool log_sum, bool want_logits) {
+    const int H = d.hidden, planes = precise() ? 2 : 1, n_part = align_head_parts(N);
+    align_xn.ensure((size_t)planes * align_rows_padded(M) * H * 2);
+    align_pval.ensure((size_t)M * n_part * 4); align_pidx.ensure((size_t)M * n_part * 4);
+    if (log_sum) score_psum.ensure((size_t)M * n_part * 4);
+    if (want_logits) align_logits.ensure((size_t)M * N * 4);
+    a.x = dec_x.as<float>(); a.ldx = H; a.rows = align_rows.as<int>(); a.M = M;
+    a.norm_w = wf(L.final_norm); a.eps = d.rms_eps; a.W = wh(L.lm_head); a.N = N; a.K = H;
+    a.planes = planes; a.xn = align_xn.as<uint16_t>();
+    a.part = ArgmaxPartials{align_pval.as<float>(), align_pidx.as<int>(), log_sum ? score_psum.as<float>() : nullptr, n_part};
+    a.logits = want_logits ? align_logits.as<float>() : nullptr; a.ldl = (size_t)N;
+  }
+  // The scoring head over the vocabulary at those rows against `targets` [M] (q3a_score*, draft verification): results in score_out
+  // as tgt_logit | lp | top_id | top_lp, M words each.
+  ScoreHeadArgs score_head_args(int M, const std::vector<int>& targets, bool want_logits) {
+    ScoreHeadArgs a{};
+    fill_row_head(a, M, d.vocab, true, want_logits);
+    upload(score_tgt, targets, stream);
+    score_out.ensure((size_t)M * 4 * 4);
+    a.targets = score_tgt.as<int>();
+    a.tgt_logit = score_out.as<float>(); a.lp = score_out.as<float>() + M;
+    a.top_id = score_out.as<int>() + 2 * (size_t)M; a.top_lp = score_out.as<float>() + 3 * (size_t)M;
+    return a;
+  }
   // Classes (and logits) to the host, [utterance][stride].
   void run_align(const std::vector<int>& rows, const int32_t* counts, int stride, int32_t* out_classes, float* logits_out) {
-    const int M = (int)rows.size(), N = d.classify_num, H = d.hidden;
+    const int M = (int)rows.size(), N = d.classify_num;
     run_prefill_then_head(rows, align_head_ms, [&] {
-      const int planes = precise() ? 2 : 1, n_part = align_head_parts(N);
-      align_xn.ensure((size_t)planes * align_rows_padded(M) * H * 2);
-      align_pval.ensure((size_t)M * n_part * 4); align_pidx.ensure((size_t)M * n_part * 4);
-      align_cls.ensure((size_t)M * 4);
-      if (logits_out) align_logits.ensure((size_t)M * N * 4);
       AlignHeadArgs a{};
-      a.x = dec_x.as<float>(); a.ldx = H; a.rows = align_rows.as<int>(); a.M = M;
-      a.norm_w = wf(L.final_norm); a.eps = d.rms_eps; a.W = wh(L.lm_head); a.N = N; a.K = H;
-      a.planes = planes; a.xn = align_xn.as<uint16_t>();
-      a.part = ArgmaxPartials{align_pval.as<float>(), align_pidx.as<int>(), nullptr, n_part};
+      fill_row_head(a, M, N, false, logits_out != nullptr);
+      align_cls.ensure((size_t)M * 4);
       a.classes = align_cls.as<int>();
-      a.logits = logits_out ? align_logits.as<float>() : nullptr; a.ldl = N;
       KCHK(launch_align_head(a, stream));
     });
     std::vector<int> cls((size_t)M);
@@ -1383,6 +1408,13 @@ struct q3a_engine {
     std::vector<int32_t> ids, lens;  // what is prefilled: per utterance prompt ++ targets[0 .. n-2]
     std::vector<int> rows, targets;  // per scored position: row of the residual stream that predicts it, and its id
   };
+  // what no id a caller hands in to be fed behind the prompt may be; noun: "target" (q3a_score*) or "draft" (draft calls).  The texts
+  // say "target id 7 out of range" / "cannot be a target" and "draft id 7 out of range" / "cannot be a draft id".
+  void check_given_id(const char* what, const std::string& noun, int32_t y) const {
+    if (y < 0 || y >= d.vocab) fail(std::string(what) + ": " + noun + " id " + std::to_string(y) + " out of range (vocabulary " + std::to_string(d.vocab) + ")");
+    if (y == kAudioPad)
+      fail(std::string(what) + ": <|audio_pad|> (" + std::to_string(kAudioPad) + ") cannot be a " + (noun == "target" ? noun : noun + " id") + ": the engine finds audio rows by this id");
+  }
   // prompt_ids / target_ids concatenated over the batch; refuses what the header lists
   ScorePlan score_plan(const char* what, const int32_t* prompt_ids, const int32_t* prompt_lens, const int32_t* target_ids,
                        const int32_t* target_lens, int b, int stride) const {
@@ -1399,8 +1431,7 @@ struct q3a_engine {
       sp.ids.insert(sp.ids.end(), prompt_ids + po, prompt_ids + po + p);
       for (int i = 0; i < n; ++i) {
         const int32_t y = target_ids[to + i];
-        if (y < 0 || y >= d.vocab) fail(std::string(what) + ": target id " + std::to_string(y) + " out of range (vocabulary " + std::to_string(d.vocab) + ")");
-        if (y == kAudioPad) fail(std::string(what) + ": <|audio_pad|> (" + std::to_string(kAudioPad) + ") cannot be a target: the engine finds audio rows by this id");
+        check_given_id(what, "target", y);
         if (i + 1 < n) sp.ids.push_back(y);  // the last target is never fed
         sp.rows.push_back(row0 + i);
         sp.targets.push_back(y);
@@ -1413,25 +1444,8 @@ struct q3a_engine {
   // prompts of sp already set up.  Results to the host [utterance][stride]; logits_out (nullable): [rows][vocab].
   void run_score(const ScorePlan& sp, const int32_t* target_lens, int stride, float* out_lp, int32_t* out_top_ids, float* out_top_lp,
                  float* logits_out) {
-    const int M = (int)sp.rows.size(), V = d.vocab, H = d.hidden;
-    run_prefill_then_head(sp.rows, score_head_ms, [&] {
-      const int planes = precise() ? 2 : 1, n_part = align_head_parts(V);
-      upload(score_tgt, sp.targets, stream);
-      align_xn.ensure((size_t)planes * align_rows_padded(M) * H * 2);
-      align_pval.ensure((size_t)M * n_part * 4); align_pidx.ensure((size_t)M * n_part * 4); score_psum.ensure((size_t)M * n_part * 4);
-      score_out.ensure((size_t)M * 4 * 4);  // tgt_logit | lp | top_id | top_lp
-      if (logits_out) align_logits.ensure((size_t)M * V * 4);  // the only M x vocab buffer, and only on request
-      ScoreHeadArgs a{};
-      a.x = dec_x.as<float>(); a.ldx = H; a.rows = align_rows.as<int>(); a.M = M;
-      a.norm_w = wf(L.final_norm); a.eps = d.rms_eps; a.W = wh(L.lm_head); a.N = V; a.K = H;
-      a.planes = planes; a.xn = align_xn.as<uint16_t>();
-      a.part = ArgmaxPartials{align_pval.as<float>(), align_pidx.as<int>(), score_psum.as<float>(), n_part};
-      a.targets = score_tgt.as<int>();
-      a.tgt_logit = score_out.as<float>(); a.lp = score_out.as<float>() + M;
-      a.top_id = score_out.as<int>() + 2 * (size_t)M; a.top_lp = score_out.as<float>() + 3 * (size_t)M;
-      a.logits = logits_out ? align_logits.as<float>() : nullptr; a.ldl = (size_t)V;
-      KCHK(launch_score_head(a, stream));
-    });
+    const int M = (int)sp.rows.size(), V = d.vocab;
+    run_prefill_then_head(sp.rows, score_head_ms, [&] { KCHK(launch_score_head(score_head_args(M, sp.targets, logits_out != nullptr), stream)); });
     if (M == 0) return;
     std::vector<float> res((size_t)M * 4);
     HIPCHK(hipMemcpy(res.data(), score_out.p, res.size() * 4, hipMemcpyDeviceToHost));
@@ -1482,8 +1496,7 @@ struct q3a_engine {
       dp.ids.insert(dp.ids.end(), prompt_ids + po, prompt_ids + po + p);
       for (int i = 0; i < n; ++i) {
         const int32_t y = draft_ids[to + i];
-        if (y < 0 || y >= d.vocab) fail(std::string(what) + ": draft id " + std::to_string(y) + " out of range (vocabulary " + std::to_string(d.vocab) + ")");
-        if (y == kAudioPad) fail(std::string(what) + ": <|audio_pad|> (" + std::to_string(kAudioPad) + ") cannot be a draft id: the engine finds audio rows by this id");
+        check_given_id(what, "draft", y);
         if (y == kEos0 || y == kEos1) fail(std::string(what) + ": an EOS id (" + std::to_string(y) + ") cannot be a draft id: a draft ends where its ids end");
         dp.ids.push_back(y);
         dp.words.push_back(y);
@@ -1502,26 +1515,12 @@ struct q3a_engine {
   // prompts of dp already set up (setup_prompts over dp.ids / dp.lens).  acc [2 B]: k per utterance, then its token.  logits_out
   // (nullable): the head's rows [sum (n + 1)][vocab].  The stream is idle on return and the engine holds decode state.
   void run_prefill_draft(const DraftPlan& dp, std::vector<int>& acc, float* logits_out) {
-    const int M = (int)dp.rows.size(), V = d.vocab, H = d.hidden;
+    const int M = (int)dp.rows.size(), V = d.vocab;
     have_prefill = false;
     run_prefill_layers();
-    const int planes = precise() ? 2 : 1, n_part = align_head_parts(V);
     upload(align_rows, dp.rows, stream);
-    upload(score_tgt, dp.targets, stream);
     upload(draft_in, dp.words, stream);
-    align_xn.ensure((size_t)planes * align_rows_padded(M) * H * 2);
-    align_pval.ensure((size_t)M * n_part * 4); align_pidx.ensure((size_t)M * n_part * 4); score_psum.ensure((size_t)M * n_part * 4);
-    score_out.ensure((size_t)M * 4 * 4);  // tgt_logit | lp | top_id | top_lp
-    if (logits_out) align_logits.ensure((size_t)M * V * 4);
-    ScoreHeadArgs a{};
-    a.x = dec_x.as<float>(); a.ldx = H; a.rows = align_rows.as<int>(); a.M = M;
-    a.norm_w = wf(L.final_norm); a.eps = d.rms_eps; a.W = wh(L.lm_head); a.N = V; a.K = H;
-    a.planes = planes; a.xn = align_xn.as<uint16_t>();
-    a.part = ArgmaxPartials{align_pval.as<float>(), align_pidx.as<int>(), score_psum.as<float>(), n_part};
-    a.targets = score_tgt.as<int>();
-    a.tgt_logit = score_out.as<float>(); a.lp = score_out.as<float>() + M;
-    a.top_id = score_out.as<int>() + 2 * (size_t)M; a.top_lp = score_out.as<float>() + 3 * (size_t)M;
-    a.logits = logits_out ? align_logits.as<float>() : nullptr; a.ldl = (size_t)V;
+    ScoreHeadArgs a = score_head_args(M, dp.targets, logits_out != nullptr);
     a.bias = step.head_bias();  // a logit bias composes: the verify head is a head of the generation paths
     KCHK(launch_score_head(a, stream));
     DraftAcceptArgs da{};
@@ -2387,9 +2386,7 @@ int32_t q3a_set_next_tokens(q3a_engine* e, const int32_t* ids, int32_t B) {
   if (!e->have_prefill || B != e->B || e->beam_w_ > 0) fail("q3a_set_next_tokens: no decode state / batch mismatch");
   for (int s = 0; s < B; ++s)
     if (ids[s] < 0 || ids[s] >= e->d.vocab) fail("q3a_set_next_tokens: token id out of range");
-  HIPCHK(hipMemcpy(e->step.forced_tok.p, ids, (size_t)B * 4, hipMemcpyHostToDevice));
-  KCHK(launch_set_tokens(e->step.forced_tok.as<int>(), B, e->wh(e->L.embed), e->d.hidden, e->step.x_dec.as<float>(),
-                         e->step.next_tok.as<int>(), e->stream, e->step.first_layer_norm_out()));
+  e->step.enqueue_forced_tokens(ids);
   HIPCHK(hipStreamSynchronize(e->stream));
   Q3A_CATCH(e)
 }

@@ -17,6 +17,10 @@
 // contiguous chunk of tile ids its XCD receives, so the row tiles that share a 128-row slab of the lm_head run together on one L2.
 // score_merge_kernel: one wave per row merges the row's partials (lane l takes partials l, l + 64, ... in ascending order, then the
 // xor butterfly 32 .. 1: a fixed order) and writes lp = l[target] - logsumexp, top_id, top_lp = -log(sum).
+#include <limits.h>
+
+#include <type_traits>
+
 #include "argmax.h"
 #include "dev.h"
 #include "kernels.h"
@@ -72,7 +76,7 @@ __global__ __launch_bounds__(256) void align_norm_kernel(const float* __restrict
 // holds column targets[m] stores its accumulator to tgt_logit[m].  BIAS (draft verification under a logit bias, LP only): bias[n], finite
 // or -inf, is added to the fp32 accumulator in front of every channel and of the stored logits; a -inf logit stays exactly -inf,
 // contributes 0 to the log-sum and never yields NaN (a lane whose columns are all suppressed keeps (max -inf, sum 0), which
-// ArgmaxAcc::merge drops).  A new instantiation: the others compile to what they were.
+// ArgmaxAcc::merge drops).
 template <int NP, bool LOGITS, bool LP, bool BIAS = false>
 __device__ __forceinline__ void head_tile(const uint16_t* __restrict__ xn, int Mp, int M, const uint16_t* __restrict__ W, int N, int K,
                                           const ArgmaxPartials& part, float* __restrict__ logits, size_t ldl, int m0, int tile_n,
@@ -195,27 +199,18 @@ __global__ __launch_bounds__(256) void align_head_kernel(const uint16_t* __restr
 
 // 1-D grid of 8 * ceil(tiles / 8) workgroups: the hardware deals workgroup ids round-robin to the 8 XCDs, so workgroup w walks tile
 // (w % 8) * chunk + w / 8 -- every XCD a contiguous chunk of the tile order, in which the row tiles (m_tiles of them) are fastest
-template <int NP, bool LOGITS>
+// BIAS: the same walk on l' = l + b (draft verification while a logit bias is set).  The bias pointer is a trailing argument that
+// only the BIAS instantiations have (Bias = const float*, else empty): the others keep the kernarg segment they had without it.
+template <int NP, bool LOGITS, bool BIAS, class... Bias>
 __global__ __launch_bounds__(256) void score_head_kernel(const uint16_t* __restrict__ xn, int Mp, int M, const uint16_t* __restrict__ W,
                                                          int N, int K, ArgmaxPartials part, float* __restrict__ logits, size_t ldl,
                                                          const int* __restrict__ targets, float* __restrict__ tgt_logit, int m_tiles,
-                                                         int tiles) {
+                                                         int tiles, Bias __restrict__... bias) {
+  static_assert(sizeof...(Bias) == (BIAS ? 1 : 0), "the bias argument goes with BIAS");
   const int chunk = gridDim.x >> 3;
   const int id = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
   if (id >= tiles) return;  // (the whole workgroup)
-  head_tile<NP, LOGITS, true>(xn, Mp, M, W, N, K, part, logits, ldl, (id % m_tiles) * BM, id / m_tiles, targets, tgt_logit);
-}
-
-// the scoring head's walk on l' = l + b (draft verification while a logit bias is set)
-template <int NP, bool LOGITS>
-__global__ __launch_bounds__(256) void draft_head_kernel(const uint16_t* __restrict__ xn, int Mp, int M, const uint16_t* __restrict__ W,
-                                                         int N, int K, ArgmaxPartials part, float* __restrict__ logits, size_t ldl,
-                                                         const int* __restrict__ targets, float* __restrict__ tgt_logit, int m_tiles,
-                                                         int tiles, const float* __restrict__ bias) {
-  const int chunk = gridDim.x >> 3;
-  const int id = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
-  if (id >= tiles) return;  // (the whole workgroup)
-  head_tile<NP, LOGITS, true, true>(xn, Mp, M, W, N, K, part, logits, ldl, (id % m_tiles) * BM, id / m_tiles, targets, tgt_logit, bias);
+  head_tile<NP, LOGITS, true, BIAS>(xn, Mp, M, W, N, K, part, logits, ldl, (id % m_tiles) * BM, id / m_tiles, targets, tgt_logit, bias...);
 }
 
 __global__ __launch_bounds__(256) void score_merge_kernel(ArgmaxPartials part, int n_part, int M, int N, const float* __restrict__ tgt_logit,
@@ -254,72 +249,70 @@ __global__ __launch_bounds__(256) void align_merge_kernel(ArgmaxPartials part, i
 int align_rows_padded(int M) { return (M + BM - 1) / BM * BM; }
 int align_head_parts(int N) { return 2 * ((N + BN - 1) / BN); }
 
-const char* launch_head_rows_norm(const float* x, int ldx, const int* rows, int M, const float* norm_w, float eps, int K, int planes,
-                                  uint16_t* xn, hipStream_t s) {
-  if (M <= 0) return nullptr;
-  if (!x || !rows || !norm_w || !xn) return "head rows norm: null argument";
-  if (planes != 1 && planes != 2) return "head rows norm: planes must be 1 or 2";
-  if (K % BK != 0 || K > 2048) return "head rows norm: hidden must be a multiple of 64 and at most 2048";
-  const int Mp = align_rows_padded(M);
-  hipLaunchKernelGGL(align_norm_kernel, dim3(Mp / 4), dim3(256), 0, s, x, ldx, rows, M, Mp, norm_w, eps, K, planes, xn);
+const char* launch_head_rows_norm(const RowHeadArgs& a, hipStream_t s) {
+  if (a.M <= 0) return nullptr;
+  if (!a.x || !a.rows || !a.norm_w || !a.xn) return "head rows norm: null argument";
+  if (a.planes != 1 && a.planes != 2) return "head rows norm: planes must be 1 or 2";
+  if (a.K % BK != 0 || a.K > 2048) return "head rows norm: hidden must be a multiple of 64 and at most 2048";
+  const int Mp = align_rows_padded(a.M);
+  hipLaunchKernelGGL(align_norm_kernel, dim3(Mp / 4), dim3(256), 0, s, a.x, a.ldx, a.rows, a.M, Mp, a.norm_w, a.eps, a.K, a.planes, a.xn);
   return nullptr;
+}
+
+// What launch_head_rows_norm does not check itself: the weights, the partials (n_part per row) and the logits' row stride.
+static const char* row_head_check(const RowHeadArgs& a, int n_part) {
+  if (!a.W || !a.part.val) return "row head: null argument";
+  if (a.N <= 0) return "row head: no output columns";
+  if (const char* e = argmax_partials_check(a.part, n_part)) return e;
+  if (a.logits && a.ldl < (size_t)a.N) return "row head: logits row stride below the output columns";
+  return nullptr;
+}
+// f(planes, logits, bias) with the three as compile-time constants: the one dispatch of both heads' tile kernels
+template <class F>
+static void row_head_dispatch(int planes, bool logits, bool bias, F&& f) {
+  auto flag = [](bool v, auto&& g) { if (v) g(std::true_type{}); else g(std::false_type{}); };
+  flag(planes == 2, [&](auto p2) {
+    flag(logits, [&](auto lg) {
+      flag(bias, [&](auto bs) { f(std::integral_constant<int, decltype(p2)::value ? 2 : 1>{}, lg, bs); });
+    });
+  });
 }
 
 const char* launch_score_head(const ScoreHeadArgs& a, hipStream_t s) {
   if (a.M <= 0) return nullptr;
-  if (!a.x || !a.rows || !a.norm_w || !a.W || !a.xn || !a.targets || !a.tgt_logit || !a.lp || !a.part.val || !a.part.sum)
-    return "score head: null argument";
-  if (a.N <= 0) return "score head: empty vocabulary";
+  if (!a.targets || !a.tgt_logit || !a.lp || !a.part.sum) return "score head: null argument";
   const int n_part = align_head_parts(a.N);
-  if (const char* e = argmax_partials_check(a.part, n_part)) return e;
-  if (a.logits && a.ldl < (size_t)a.N) return "score head: logits row stride below the vocabulary";
-  if (const char* e = launch_head_rows_norm(a.x, a.ldx, a.rows, a.M, a.norm_w, a.eps, a.K, a.planes, a.xn, s)) return e;
+  if (const char* e = row_head_check(a, n_part)) return e;
   const int Mp = align_rows_padded(a.M), m_tiles = Mp / BM;
   const long long tiles = (long long)m_tiles * ((a.N + BN - 1) / BN);
   if (tiles > (1ll << 30)) return "score head: too many tiles";
+  if (const char* e = launch_head_rows_norm(a, s)) return e;
   const dim3 grid((unsigned)((tiles + 7) / 8 * 8));
-#define SCORE_LAUNCH(NP, LG)                                                                                                      \
-  hipLaunchKernelGGL((score_head_kernel<NP, LG>), grid, dim3(256), 0, s, a.xn, Mp, a.M, a.W, a.N, a.K, a.part, a.logits, a.ldl, \
-                     a.targets, a.tgt_logit, m_tiles, (int)tiles)
-#define DRAFT_LAUNCH(NP, LG)                                                                                                      \
-  hipLaunchKernelGGL((draft_head_kernel<NP, LG>), grid, dim3(256), 0, s, a.xn, Mp, a.M, a.W, a.N, a.K, a.part, a.logits, a.ldl, \
-                     a.targets, a.tgt_logit, m_tiles, (int)tiles, a.bias)
-  if (a.bias) {
-    if (a.planes == 1) {
-      if (a.logits) DRAFT_LAUNCH(1, true); else DRAFT_LAUNCH(1, false);
-    } else {
-      if (a.logits) DRAFT_LAUNCH(2, true); else DRAFT_LAUNCH(2, false);
-    }
-  } else if (a.planes == 1) {
-    if (a.logits) SCORE_LAUNCH(1, true); else SCORE_LAUNCH(1, false);
-  } else {
-    if (a.logits) SCORE_LAUNCH(2, true); else SCORE_LAUNCH(2, false);
-  }
-#undef DRAFT_LAUNCH
-#undef SCORE_LAUNCH
+  row_head_dispatch(a.planes, a.logits != nullptr, a.bias != nullptr, [&](auto np, auto lg, auto bs) {
+    auto launch = [&](auto... bias) {
+      hipLaunchKernelGGL((score_head_kernel<decltype(np)::value, decltype(lg)::value, decltype(bs)::value>), grid, dim3(256), 0, s, a.xn, Mp, a.M,
+                         a.W, a.N, a.K, a.part, a.logits, a.ldl, a.targets, a.tgt_logit, m_tiles, (int)tiles, bias...);
+    };
+    if constexpr (decltype(bs)::value) launch(a.bias); else launch();
+  });
   hipLaunchKernelGGL(score_merge_kernel, dim3((a.M + 3) / 4), dim3(256), 0, s, a.part, n_part, a.M, a.N, a.tgt_logit, a.lp, a.top_id, a.top_lp);
   return nullptr;
 }
 
 const char* launch_align_head(const AlignHeadArgs& a, hipStream_t s) {
   if (a.M <= 0) return nullptr;
-  if (!a.x || !a.rows || !a.norm_w || !a.W || !a.xn || !a.classes || !a.part.val) return "align head: null argument";
-  if (a.planes != 1 && a.planes != 2) return "align head: planes must be 1 or 2";
-  if (a.K % BK != 0 || a.K > 2048 || a.N <= 0) return "align head: hidden must be a multiple of 64 and at most 2048";
+  if (!a.classes) return "align head: null argument";
   if (a.part.sum) return "align head: no log-sum channel";
+  if (a.ldl > (size_t)INT_MAX) return "align head: logits row stride too large";
   const int n_part = align_head_parts(a.N);
-  if (const char* e = argmax_partials_check(a.part, n_part)) return e;
-  if (a.logits && a.ldl < a.N) return "align head: logits row stride below classify_num";
+  if (const char* e = row_head_check(a, n_part)) return e;
+  if (const char* e = launch_head_rows_norm(a, s)) return e;
   const int Mp = align_rows_padded(a.M);
-  if (const char* e = launch_head_rows_norm(a.x, a.ldx, a.rows, a.M, a.norm_w, a.eps, a.K, a.planes, a.xn, s)) return e;
   const dim3 grid((a.N + BN - 1) / BN, Mp / BM);
-  if (a.planes == 1) {
-    if (a.logits) hipLaunchKernelGGL((align_head_kernel<1, true>), grid, dim3(256), 0, s, a.xn, Mp, a.M, a.W, a.N, a.K, a.part, a.logits, a.ldl);
-    else hipLaunchKernelGGL((align_head_kernel<1, false>), grid, dim3(256), 0, s, a.xn, Mp, a.M, a.W, a.N, a.K, a.part, a.logits, a.ldl);
-  } else {
-    if (a.logits) hipLaunchKernelGGL((align_head_kernel<2, true>), grid, dim3(256), 0, s, a.xn, Mp, a.M, a.W, a.N, a.K, a.part, a.logits, a.ldl);
-    else hipLaunchKernelGGL((align_head_kernel<2, false>), grid, dim3(256), 0, s, a.xn, Mp, a.M, a.W, a.N, a.K, a.part, a.logits, a.ldl);
-  }
+  row_head_dispatch(a.planes, a.logits != nullptr, false, [&](auto np, auto lg, auto) {
+    hipLaunchKernelGGL((align_head_kernel<decltype(np)::value, decltype(lg)::value>), grid, dim3(256), 0, s, a.xn, Mp, a.M, a.W, a.N, a.K, a.part,
+                       a.logits, (int)a.ldl);
+  });
   hipLaunchKernelGGL(align_merge_kernel, dim3((a.M + 255) / 256), dim3(256), 0, s, a.part, n_part, a.M, a.N, a.classes);
   return nullptr;
 }

@@ -9,7 +9,7 @@
 //                           embedding of the chosen token for the next step -- no per-token D2H sync
 //                           (the reference does int64_value per token, src/inference.rs:161)
 #include "argmax.h"
-#include "embed_row.h"
+#include "step_commit.h"
 
 namespace q3a {
 
@@ -104,7 +104,9 @@ __global__ __launch_bounds__(256) void argmax_partial_kernel(const float* __rest
 // argmax, stage 2 + bookkeeping of the greedy loop.  LP (token log-probabilities): the chosen id's logit IS the global maximum M, so
 // lp = -log sum_p part.sum[p] e^(part.val[p] - M), the merged sum (<= 0: the partial that holds M contributes at least e^0 = 1).
 // Kernel arguments: a flat head of 14 dwords preloaded into SGPRs at wave launch (build.py KERNARG_PRELOAD_FLAGS; k_gemv.hip has the
-// scheme) -- what the first batch of requests is addressed with -- then the tail, which holds no head field.
+// scheme) -- what the first batch of requests is addressed with -- then the tail, which holds no head field.  The kernel puts its
+// FinalizeArgs together again from both, field by field in the order the code object was measured with (an aggregate initialiser of the
+// StepCommit gives another register allocation); the token's bookkeeping and rows are step_commit.h's.
 struct FinalizeTail {
   float* part_sum;
   int V; int out_stride; int advance;
@@ -118,11 +120,13 @@ template <bool LP>
 __global__ __launch_bounds__(1024) void argmax_finalize_kernel(float* part_val, int* part_idx, int* next_tok, int* out_ids, int* step_count,
                                                                int* pos, int n_part, int part_stride, FinalizeTail t) {
   FinalizeArgs a{};
-  a.part.val = part_val; a.part.idx = part_idx; a.next_tok = next_tok; a.out_ids = out_ids; a.step_count = step_count; a.pos = pos;
+  a.part.val = part_val; a.part.idx = part_idx; a.c.next_tok = next_tok; a.c.out_ids = out_ids; a.c.step_count = step_count; a.c.pos = pos;
   a.n_part = n_part; a.part.stride = part_stride;
-  a.part.sum = t.part_sum; a.V = t.V; a.out_stride = t.out_stride; a.advance = t.advance; a.done = t.done;
-  a.n_done = t.n_done; a.n_seq = t.n_seq; a.host_progress = t.host_progress; a.embed = t.embed; a.H = t.H; a.x_next = t.x_next;
-  a.eos0 = t.eos0; a.eos1 = t.eos1; a.cos_t = t.cos_t; a.sin_t = t.sin_t; a.rope_cur = t.rope_cur; a.nn = t.nn; a.out_lp = t.out_lp;
+  a.part.sum = t.part_sum; a.V = t.V; a.c.out_stride = t.out_stride; a.advance = t.advance; a.c.done = t.done;
+  a.c.n_done = t.n_done; a.c.n_seq = t.n_seq; a.c.host_progress = t.host_progress; a.c.embed = t.embed; a.c.H = t.H; a.c.x_next = t.x_next;
+  a.c.eos0 = t.eos0; a.c.eos1 = t.eos1; a.c.cos_t = t.cos_t; a.c.sin_t = t.sin_t; a.c.rope_cur = t.rope_cur; a.c.nn = t.nn; a.c.out_lp = t.out_lp;
+  const ArgmaxPartials& part = a.part;
+  const StepCommit& c = a.c;
   __shared__ float bv[16], bs[LP ? 16 : 1];
   __shared__ int bi[16];
   __shared__ int tok_s;
@@ -132,29 +136,28 @@ __global__ __launch_bounds__(1024) void argmax_finalize_kernel(float* part_val, 
   // two loads and a vmcnt(0) per iteration, ten dependent L2 round trips for the 9496 partials of the one-sequence lm_head) and,
   // behind `pos`, the RoPE row of the next position.
   constexpr int FIN_PRE = 10;  // 10 240 partials (vocabulary 151 936 in 16-row blocks: 9496); more are folded by the loop below
-  const int pos0 = a.pos[s];
-  const int sc = a.step_count[s];
+  const int pos0 = c.pos[s];
+  const int sc = c.step_count[s];
   ArgmaxAcc<LP> pre[FIN_PRE];
 #pragma unroll
   for (int j = 0; j < FIN_PRE; ++j) {
     const int i = tid + j * 1024;
-    pre[j] = ArgmaxAcc<LP>::load(a.part, s, i < a.n_part ? i : a.n_part - 1);  // all three channels in the same batch
+    pre[j] = ArgmaxAcc<LP>::load(part, s, i < n_part ? i : n_part - 1);  // all three channels in the same batch
   }
   // what is addressed through the tail comes behind the partials, which need the preloaded head only: the tail in one scalar-load
   // clause (dev.h Q3A_ARG) while they are in flight, instead of one round trip in front of each first use
-  Q3A_ARG(a.advance); Q3A_ARG(a.done); Q3A_ARG(a.V); Q3A_ARG(a.out_stride); Q3A_ARG(a.n_done); Q3A_ARG(a.n_seq); Q3A_ARG(a.host_progress);
-  Q3A_ARG(a.embed); Q3A_ARG(a.H); Q3A_ARG(a.x_next); Q3A_ARG(a.eos0); Q3A_ARG(a.eos1); Q3A_ARG(a.cos_t); Q3A_ARG(a.sin_t); Q3A_ARG(a.rope_cur);
-  const int np = pos0 + a.advance;
-  const int was_done = a.done[s];
-  float rope_v = 0.f;
-  if (a.rope_cur && tid < 128) rope_v = tid < 64 ? a.cos_t[(size_t)np * 64 + tid] : a.sin_t[(size_t)np * 64 + tid - 64];
+  Q3A_ARG(t.advance); Q3A_ARG(c.done); Q3A_ARG(t.V); Q3A_ARG(c.out_stride); Q3A_ARG(c.n_done); Q3A_ARG(c.n_seq); Q3A_ARG(c.host_progress);
+  Q3A_ARG(c.embed); Q3A_ARG(c.H); Q3A_ARG(c.x_next); Q3A_ARG(c.eos0); Q3A_ARG(c.eos1); Q3A_ARG(c.cos_t); Q3A_ARG(c.sin_t); Q3A_ARG(c.rope_cur);
+  const int np = pos0 + t.advance;
+  const int was_done = c.done[s];
+  const float rope_v = rope_row_elem(c, np);  // (requested here, long before store_rope_row)
   ArgmaxAcc<LP> m;
 #pragma unroll
   for (int j = 0; j < FIN_PRE; ++j) {
-    const bool in = tid + j * 1024 < a.n_part;
+    const bool in = tid + j * 1024 < n_part;
     m.merge(in ? pre[j].v : -INFINITY, pre[j].i, LP && in ? pre[j].s : 0.f);
   }
-  for (int i = tid + FIN_PRE * 1024; i < a.n_part; i += 1024) m.merge(ArgmaxAcc<LP>::load(a.part, s, i));
+  for (int i = tid + FIN_PRE * 1024; i < n_part; i += 1024) m.merge(ArgmaxAcc<LP>::load(part, s, i));
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) m.merge_lane(o);
   if (lane == 0) {
@@ -170,29 +173,13 @@ __global__ __launch_bounds__(1024) void argmax_finalize_kernel(float* part_val, 
       lp = -logf(m.s);
       if (lp > 0.f) lp = 0.f;  // (rounding; NaN passes through)
     }
-    if (idx < 0 || idx >= a.V) { idx = 0; lp = __int_as_float(0x7fc00000); }  // all-NaN guard
+    if (idx < 0 || idx >= t.V) { idx = 0; lp = __int_as_float(0x7fc00000); }  // all-NaN guard
     tok_s = idx;
-    a.next_tok[s] = idx;
-    if (sc < a.out_stride) a.out_ids[(size_t)s * a.out_stride + sc] = idx;
-    if constexpr (LP) {
-      if (sc < a.out_stride) a.out_lp[(size_t)s * a.out_stride + sc] = lp;
-    }
-    a.step_count[s] = sc + 1;
-    a.pos[s] = np;
-    if ((idx == a.eos0 || idx == a.eos1) && !was_done) {  // this sequence's first EOS (inference.rs:163-165)
-      a.done[s] = 1;
-      if (a.n_done) {
-        const int n = atomicAdd(a.n_done, 1) + 1;
-        if (n == a.n_seq && a.host_progress) __hip_atomic_store(a.host_progress + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    }
-    if (s == 0 && a.host_progress) __hip_atomic_store(a.host_progress, sc + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    commit_token(c, s, sc, idx, LP, lp, sc + 1, np, was_done);
   }
   __syncthreads();
-  // RoPE row of the position the next decode step works at, at a fixed address: the attention kernels of that step
-  // request it together with q/k/v instead of after a dependent load of pos
-  if (a.rope_cur && tid < 128) a.rope_cur[(size_t)s * 128 + tid] = rope_v;
-  embed_row(a.embed, tok_s, a.H, a.x_next, s, a.nn, bv);  // bv: its 16 floats are free again after the barrier above
+  store_rope_row(c, s, rope_v);
+  embed_row(c.embed, tok_s, c.H, c.x_next, s, c.nn, bv);  // bv: its 16 floats are free again after the barrier above
 }
 
 }  // namespace
@@ -203,10 +190,11 @@ const char* launch_embed(const int* ids, int rows, const uint16_t* embed, int H,
   hipLaunchKernelGGL(embed_kernel, dim3(rows), dim3(256), 0, s, ids, embed, H, skip_id, out);
   return nullptr;
 }
-const char* launch_set_tokens(const int* tok, int S, const uint16_t* embed, int H, float* x_next, int* next_tok,
-                              hipStream_t s, const NextNormOut& nn) {
-  if (nn.next_w && S > 32 && (nn.group_stride_x <= 0 || nn.group_stride_ss <= 0)) return "set_tokens: more than 32 sequences need group strides";
-  hipLaunchKernelGGL(set_tokens_kernel, dim3(S), dim3(256), 0, s, tok, embed, H, x_next, next_tok, nn);
+const char* launch_set_tokens(const int* tok, int S, const StepCommit& c, hipStream_t s) {
+  if (S <= 0) return nullptr;
+  if (!tok) return "set_tokens: null argument";
+  if (const char* e = step_commit_check(c, S, Q3A_STEP_COMMIT_MSGS("set_tokens"), true)) return e;
+  hipLaunchKernelGGL(set_tokens_kernel, dim3(S), dim3(256), 0, s, tok, c.embed, c.H, c.x_next, c.next_tok, c.nn);
   return nullptr;
 }
 const char* launch_qknorm_rope_kv(const RopeKvArgs& a, int rows, bool kv_f32, hipStream_t s) {
@@ -229,12 +217,12 @@ const char* launch_argmax_finalize(const FinalizeArgs& a, int S, hipStream_t s) 
   if (S <= 0) return nullptr;
   if (!a.part.val) return "argmax_finalize: partial buffer missing";
   if (const char* e = argmax_partials_check(a.part, a.n_part)) return e;
-  if (!a.part.sum != !a.out_lp) return "argmax_finalize: part.sum and out_lp go together";
-  FinalizeTail t{};
-  t.part_sum = a.part.sum; t.V = a.V; t.out_stride = a.out_stride; t.advance = a.advance; t.done = a.done;
-  t.n_done = a.n_done; t.n_seq = a.n_seq; t.host_progress = a.host_progress; t.embed = a.embed; t.H = a.H; t.x_next = a.x_next;
-  t.eos0 = a.eos0; t.eos1 = a.eos1; t.cos_t = a.cos_t; t.sin_t = a.sin_t; t.rope_cur = a.rope_cur; t.nn = a.nn; t.out_lp = a.out_lp;
-#define Q3A_FIN_ARGS a.part.val, a.part.idx, a.next_tok, a.out_ids, a.step_count, a.pos, a.n_part, a.part.stride, t
+  if (!a.part.sum != !a.c.out_lp) return "argmax_finalize: part.sum and out_lp go together";
+  const StepCommit& c = a.c;
+  if (const char* e = step_commit_check(c, S, Q3A_STEP_COMMIT_MSGS("argmax_finalize"))) return e;
+  const FinalizeTail t{a.part.sum, a.V, c.out_stride, a.advance, c.done, c.n_done, c.n_seq, c.host_progress, c.embed, c.H, c.x_next,
+                       c.eos0, c.eos1, c.cos_t, c.sin_t, c.rope_cur, c.nn, c.out_lp};
+#define Q3A_FIN_ARGS a.part.val, a.part.idx, c.next_tok, c.out_ids, c.step_count, c.pos, a.n_part, a.part.stride, t
   if (a.part.sum) hipLaunchKernelGGL(argmax_finalize_kernel<true>, dim3(S), dim3(1024), 0, s, Q3A_FIN_ARGS);
   else hipLaunchKernelGGL(argmax_finalize_kernel<false>, dim3(S), dim3(1024), 0, s, Q3A_FIN_ARGS);
 #undef Q3A_FIN_ARGS

@@ -4,13 +4,12 @@
 //   1. k = min{ i < n : t_i != d_i } (n if none): every thread scans a strided share of the draft in ascending order and keeps the
 //      first mismatch it meets, then a min over the wave (xor butterfly) and over the waves (LDS).  The FIRST mismatch: ids behind it
 //      that happen to agree again do not count.
-//   2. out_ids[0 .. k) = d, out_ids[k] = tok = t_k (and their log-probabilities: the head's top_lp at those rows, which is the
-//      target's lp bit for bit where the target is the argmax), with the out_stride guard of argmax_finalize.
-//   3. thread 0: next_tok, step_count = k + 1, pos = p + k, the done flag / n_done / pinned progress words as argmax_finalize sets
-//      them (an EOS as tok finishes the sequence with k ids); ids and positions are plain stores, the progress words system-scope
-//      atomic stores.
-//   4. the RoPE row of pos and the embedding of tok (+ the pre-normalised copy of the skinny path), as argmax_finalize.
-#include "embed_row.h"
+//   2. thread 0 commits tok = t_k at slot k (step_commit.h commit_token: step_count = k + 1, pos = p + k; an EOS as tok finishes the
+//      sequence with k ids), with the head's top_lp at that row as its log-probability -- the target's lp bit for bit where the
+//      target is the argmax.
+//   3. out_ids[0 .. k) = d and their log-probabilities, under the same out_stride guard.
+//   4. the RoPE row of pos (store_rope_row) and the embedding of tok (embed_row).
+#include "step_commit.h"
 
 namespace q3a {
 
@@ -22,6 +21,7 @@ __global__ __launch_bounds__(DRAFT_THREADS) void draft_accept_kernel(DraftAccept
   __shared__ int wk[DRAFT_THREADS / 64];
   __shared__ float red[16];
   __shared__ int k_s, tok_s;
+  const StepCommit& c = a.c;
   const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int d0 = a.draft_off[s], n = a.draft_off[s + 1] - d0;
   const int r0 = d0 + s;  // first head row of the sequence (every sequence in front has one row more than draft ids)
@@ -40,44 +40,28 @@ __global__ __launch_bounds__(DRAFT_THREADS) void draft_accept_kernel(DraftAccept
     k_s = k; tok_s = tok;
     a.accepted[s] = k;
     a.accepted[a.n_seq + s] = tok;
-    a.next_tok[s] = tok;
-    if (k < a.out_stride) {
-      a.out_ids[(size_t)s * a.out_stride + k] = tok;
-      if (a.out_lp) a.out_lp[(size_t)s * a.out_stride + k] = a.top_lp[r0 + k];
-    }
-    a.step_count[s] = k + 1;
-    a.pos[s] = p + k;
-    if (tok == a.eos0 || tok == a.eos1) {  // the sequence's first EOS: no draft id is one (refused on the host)
-      a.done[s] = 1;
-      if (a.n_done) {
-        const int nd = atomicAdd(a.n_done, 1) + 1;
-        if (nd == a.n_seq && a.host_progress) __hip_atomic_store(a.host_progress + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    }
-    if (s == 0 && a.host_progress) __hip_atomic_store(a.host_progress, k + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    const bool with_lp = c.out_lp != nullptr;
+    // (was_done = 0: a prefill begins with the flags clear, and no draft id is an EOS -- refused on the host)
+    commit_token(c, s, k, tok, with_lp, with_lp && k < c.out_stride ? a.top_lp[r0 + k] : 0.f, k + 1, p + k, 0);
   }
   __syncthreads();
   k = k_s;
-  const int kw = min(k, a.out_stride);  // accepted draft ids that have a slot
+  const int kw = min(k, c.out_stride);  // accepted draft ids that have a slot
   for (int i = tid; i < kw; i += DRAFT_THREADS) {
-    a.out_ids[(size_t)s * a.out_stride + i] = a.draft[d0 + i];
-    if (a.out_lp) a.out_lp[(size_t)s * a.out_stride + i] = a.top_lp[r0 + i];
+    c.out_ids[(size_t)s * c.out_stride + i] = a.draft[d0 + i];
+    if (c.out_lp) c.out_lp[(size_t)s * c.out_stride + i] = a.top_lp[r0 + i];
   }
-  const int np = p + k;
-  if (a.rope_cur && tid < 128) a.rope_cur[(size_t)s * 128 + tid] = tid < 64 ? a.cos_t[(size_t)np * 64 + tid] : a.sin_t[(size_t)np * 64 + tid - 64];
-  embed_row(a.embed, tok_s, a.H, a.x_next, s, a.nn, red);
+  store_rope_row(c, s, rope_row_elem(c, p + k));
+  embed_row(c.embed, tok_s, c.H, c.x_next, s, c.nn, red);
 }
 
 }  // namespace
 
 const char* launch_draft_accept(const DraftAcceptArgs& a, hipStream_t s) {
   if (a.n_seq <= 0) return nullptr;
-  if (!a.draft_off || !a.prompt_len || !a.top_id || !a.accepted || !a.next_tok || !a.out_ids || !a.step_count || !a.pos || !a.done || !a.embed || !a.x_next)
-    return "draft accept: null argument";
-  if (a.out_lp && !a.top_lp) return "draft accept: out_lp needs top_lp";
-  if (a.out_stride < 1 || a.H < 4 || a.H % 4 != 0) return "draft accept: bad shape";
-  if (a.rope_cur && (!a.cos_t || !a.sin_t)) return "draft accept: rope_cur needs the tables";
-  if (a.nn.next_w && a.n_seq > 32 && (a.nn.group_stride_x <= 0 || a.nn.group_stride_ss <= 0)) return "draft accept: more than 32 sequences need group strides";
+  if (!a.draft_off || !a.prompt_len || !a.top_id || !a.accepted) return "draft accept: null argument";
+  if (a.c.out_lp && !a.top_lp) return "draft accept: out_lp needs top_lp";
+  if (const char* e = step_commit_check(a.c, a.n_seq, Q3A_STEP_COMMIT_MSGS("draft accept"))) return e;
   hipLaunchKernelGGL(draft_accept_kernel, dim3(a.n_seq), dim3(DRAFT_THREADS), 0, s, a);
   return nullptr;
 }

@@ -39,44 +39,38 @@ inline const char* argmax_partials_check(const ArgmaxPartials& p, int n_part) {
   return nullptr;
 }
 
-// ---- forced-aligner head (k_align.hip) -----------------------------------------------------------------
-// At the M marker rows of an aligner prefill: final RMSNorm, classifier W [N = classify_num][K = hidden] (bf16) and the argmax
-// over the N time classes.  The logits are written only when `logits` is set.
-struct AlignHeadArgs {
-  const float* x; int ldx;        // residual stream after the last decoder layer, fp32 [rows][ldx]
-  const int* rows; int M;         // [M] marker rows of x (device)
-  const float* norm_w; float eps; // final RMSNorm
-  const uint16_t* W; int N; int K;
-  int planes;                     // 1: bf16 operand (default mode); 2: hi + lo bf16 split of the fp32 normed rows (precise mode)
-  uint16_t* xn;                   // workspace [planes][align_rows_padded(M)][K]
-  ArgmaxPartials part;            // [M] rows x align_head_parts(N) partials, no log-sum channel
-  int* classes;                   // [M] argmax (first index on ties)
-  float* logits; int ldl;         // nullable: [M][ldl] fp32
-};
-int align_rows_padded(int M);
-int align_head_parts(int N);
-const char* launch_align_head(const AlignHeadArgs& a, hipStream_t s);
-// the first launch of both heads: rows[M] of x gathered, final RMSNorm, bf16 operand planes xn [planes][align_rows_padded(M)][K]
-// (rows M .. padded are zeros)
-const char* launch_head_rows_norm(const float* x, int ldx, const int* rows, int M, const float* norm_w, float eps, int K, int planes,
-                                  uint16_t* xn, hipStream_t s);
-
-// ---- scoring head (k_align.hip): log-probabilities of given tokens -------------------------------------------
-// At the M rows that predict a given transcript: final RMSNorm, lm_head W [N = vocab][K = hidden] (bf16) and, per row, the
-// log-probability of targets[m], the argmax and its log-probability.  M x N logits exist only when `logits` is set.
-struct ScoreHeadArgs {
+// ---- heads at a list of rows of a prefill's residual stream (k_align.hip) -----------------------------------------
+// What both heads share: at the M rows `rows` of x the final RMSNorm, then W [N][K] (bf16) on 64 x 128 tiles with one argmax
+// partial per row and 64-column strip.  The logits are written only when `logits` is set.
+struct RowHeadArgs {
   const float* x; int ldx;        // residual stream after the last decoder layer, fp32 [rows][ldx]
   const int* rows; int M;         // [M] rows of x (device)
   const float* norm_w; float eps; // final RMSNorm
   const uint16_t* W; int N; int K;
-  int planes;                     // as AlignHeadArgs
+  int planes;                     // 1: bf16 operand (default mode); 2: hi + lo bf16 split of the fp32 normed rows (precise mode)
   uint16_t* xn;                   // workspace [planes][align_rows_padded(M)][K]
-  ArgmaxPartials part;            // [M] rows x align_head_parts(N) partials WITH the log-sum channel
+  ArgmaxPartials part;            // [M] rows x align_head_parts(N) partials
+  float* logits; size_t ldl;      // nullable: [M][ldl] fp32
+};
+// the first launch of both heads: rows[M] of x gathered, final RMSNorm, bf16 operand planes xn [planes][align_rows_padded(M)][K]
+// (rows M .. padded are zeros); it reads x .. xn of the arguments
+int align_rows_padded(int M);
+const char* launch_head_rows_norm(const RowHeadArgs& a, hipStream_t s);
+// Forced-aligner head: the rows are the marker rows of an aligner prefill, W the classifier [N = classify_num][K = hidden], and the
+// result the argmax over the N time classes.  part has no log-sum channel.
+struct AlignHeadArgs : RowHeadArgs {
+  int* classes;                   // [M] argmax (first index on ties)
+};
+int align_head_parts(int N);
+const char* launch_align_head(const AlignHeadArgs& a, hipStream_t s);
+// Scoring head: log-probabilities of given tokens.  The rows are those that predict a given transcript, W the lm_head
+// [N = vocab][K = hidden]; per row the log-probability of targets[m], the argmax and its log-probability.  part carries the log-sum
+// channel.
+struct ScoreHeadArgs : RowHeadArgs {
   const int* targets;             // [M] in [0, N) (device)
   float* tgt_logit;               // [M] workspace: the fp32 accumulator of column targets[m]
   float* lp;                      // [M] l[target] - logsumexp(l)
   int* top_id; float* top_lp;     // [M] argmax (first index on ties) and its log-probability; nullable
-  float* logits; size_t ldl;      // nullable: [M][ldl] fp32
   // draft verification only (nullable; q3a_score* never sets it): a logit bias [N], every entry finite or -inf, added to the fp32
   // accumulator in front of the max, log-sum and target channels and of the stored logits -- the BIAS instantiation of the same tile
   const float* bias;
@@ -363,21 +357,22 @@ const char* launch_attn_combine(const float* pm, const float* pl, const float* p
                                 hipStream_t s, uint16_t* out16 = nullptr, bool frag = false);
 // out16 != null: bf16 there instead of out; frag: in skinny_frag_index order (S <= 32)
 
-struct FinalizeArgs {
-  ArgmaxPartials part;     // [S] rows of n_part partials
-  int n_part;
-  int V;
+// The state a committed token leaves behind, whichever kernel commits it (argmax_finalize, draft_accept; set_tokens writes the
+// part a fed token has: next_tok, x_next, nn).  The device side is step_commit.h.
+struct StepCommit {
   int* next_tok;           // [S] token to feed next (written)
-  int* out_ids;            // [S][out_stride] generated ids (written at step_count[s])
+  int* out_ids;            // [S][out_stride] generated ids (written at the token's slot: the step_count[s] it was chosen at)
   int out_stride;
-  int* step_count;         // [S]
-  int* pos;                // [S] += advance
-  int advance;
-  uint8_t* done;           // [S] sticky: set when the argmax is EOS
+  // token log-probabilities (nullable): [S][out_stride] logit[id] - logsumexp(logits) of the chosen id next to out_ids (NaN where
+  // the all-NaN guard fires)
+  float* out_lp;
+  int* step_count;         // [S] ids generated so far
+  int* pos;                // [S] position of the token to feed next
+  uint8_t* done;           // [S] sticky: set when the token is EOS
   int* n_done;             // device counter of sequences whose done flag is set (nullable); n_seq = sequences in the batch
   int n_seq;
   int* host_progress;      // pinned host words the greedy loop's host side polls WITHOUT synchronising the stream (nullable):
-                           // [0] = finalize launches completed for sequence 0 (prefill counts as 1), [1] = 1 once every
+                           // [0] = step_count of sequence 0 (prefill counts as 1), [1] = 1 once every
                            // sequence has produced its EOS (src/inference.rs:163-165 evaluated for the whole batch on the device)
   const uint16_t* embed; int H;
   float* x_next;           // [S][H] embedding of the chosen token
@@ -385,16 +380,35 @@ struct FinalizeArgs {
   const float* cos_t; const float* sin_t;  // RoPE tables [max_pos][64]
   float* rope_cur;         // [S][128] (written): cos | sin row of the updated pos[s] (DecodeAttnArgs::rope_cur); nullable
   NextNormOut nn;          // pre-normalised copy of x_next for the first layer's qkv GEMM (skinny path)
-  // token log-probabilities (with part.sum, else null): [S][out_stride] logit[id] - logsumexp(logits) of the chosen id next to
-  // out_ids (NaN where the all-NaN guard fires)
-  float* out_lp;
+};
+// The one host check of a StepCommit for S sequences, in the words of the launcher that calls it: required pointers, H >= 4 and
+// H % 4 == 0, out_stride >= 1, rope_cur needs the tables, more than 32 sequences with nn.next_w need group strides.  fed_only:
+// only what launch_set_tokens reads (next_tok, embed, H, x_next, nn).
+struct StepCommitMsgs { const char *null_arg, *shape, *rope, *groups; };
+#define Q3A_STEP_COMMIT_MSGS(who) \
+  q3a::StepCommitMsgs { who ": null argument", who ": bad shape", who ": rope_cur needs the tables", who ": more than 32 sequences need group strides" }
+inline const char* step_commit_check(const StepCommit& c, int S, const StepCommitMsgs& m, bool fed_only = false) {
+  if (!c.next_tok || !c.embed || !c.x_next) return m.null_arg;
+  if (c.H < 4 || c.H % 4 != 0) return m.shape;
+  if (c.nn.next_w && S > 32 && (c.nn.group_stride_x <= 0 || c.nn.group_stride_ss <= 0)) return m.groups;
+  if (fed_only) return nullptr;
+  if (!c.out_ids || !c.step_count || !c.pos || !c.done) return m.null_arg;
+  if (c.out_stride < 1) return m.shape;
+  if (c.rope_cur && (!c.cos_t || !c.sin_t)) return m.rope;
+  return nullptr;
+}
+struct FinalizeArgs {
+  ArgmaxPartials part;     // [S] rows of n_part partials; with part.sum (and c.out_lp) the token log-probabilities
+  int n_part;
+  int V;
+  int advance;             // c.pos[s] += advance
+  StepCommit c;
 };
 // nblk block partials per row of logits [S][V] (GEMM decode path; the GEMV lm_head produces its own)
 const char* launch_argmax_partials(const float* logits, int V, int S, const ArgmaxPartials& p, int nblk, hipStream_t s);
 const char* launch_argmax_finalize(const FinalizeArgs& a, int S, hipStream_t s);
-// x_next[s] = embed[tok[s]]; next_tok[s] = tok[s]  (teacher forcing)
-const char* launch_set_tokens(const int* tok, int S, const uint16_t* embed, int H, float* x_next, int* next_tok, hipStream_t s,
-                              const NextNormOut& nn = NextNormOut{});
+// c.x_next[s] = embed[tok[s]] (+ c.nn); c.next_tok[s] = tok[s]  (teacher forcing)
+const char* launch_set_tokens(const int* tok, int S, const StepCommit& c, hipStream_t s);
 
 // ---- draft verification (k_draft.hip) ------------------------------------------------------------------------
 // After ONE prefill of prompt ++ draft and the scoring head at the n + 1 rows p - 1 .. p - 1 + n of every sequence (top_id / top_lp of
@@ -405,14 +419,9 @@ struct DraftAcceptArgs {
   int n_seq;
   const int* draft; const int* draft_off;  // [draft_off[n_seq]] ids, [n_seq + 1] offsets
   const int* prompt_len;                   // [n_seq] p: the prompt without the draft
-  const int* top_id; const float* top_lp;  // [draft_off[n_seq] + n_seq] of the verify head; top_lp read only with out_lp
+  const int* top_id; const float* top_lp;  // [draft_off[n_seq] + n_seq] of the verify head; top_lp read only with c.out_lp
   int* accepted;                           // [2 n_seq] (written): k per sequence, then the token top_id[k] per sequence
-  int* next_tok; int* out_ids; int out_stride; int* step_count; int* pos;  // as FinalizeArgs (all written: step_count = k + 1, pos = p + k)
-  float* out_lp;                           // nullable [n_seq][out_stride]: top_lp of rows 0 .. k
-  uint8_t* done; int* n_done; int* host_progress;  // as FinalizeArgs; host_progress[0] = step_count of sequence 0
-  const uint16_t* embed; int H; float* x_next; int eos0, eos1;
-  const float* cos_t; const float* sin_t; float* rope_cur;  // RoPE row of pos, as FinalizeArgs
-  NextNormOut nn;
+  StepCommit c;                            // all written: step_count = k + 1, pos = p + k, out_ids / out_lp at slots 0 .. k
 };
 const char* launch_draft_accept(const DraftAcceptArgs& a, hipStream_t s);
 

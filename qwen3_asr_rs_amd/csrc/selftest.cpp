@@ -75,6 +75,17 @@ struct Guarded {
   }
 };
 
+// A StepCommit over a test's own buffers: the counters and rows every commit writes.  The caller adds what its launch also keeps
+// (n_done and the progress words, the RoPE row, the pre-normalised copy); left out, they are off.
+StepCommit bare_commit(int S, const DevBuf& tok, int* out_ids, int out_stride, float* out_lp, const DevBuf& step_count, const DevBuf& pos,
+                       const DevBuf& done, const uint16_t* embed, int H, float* x_next, int eos0, int eos1) {
+  StepCommit c{};
+  c.next_tok = tok.as<int>(); c.out_ids = out_ids; c.out_stride = out_stride; c.out_lp = out_lp;
+  c.step_count = step_count.as<int>(); c.pos = pos.as<int>(); c.done = done.as<uint8_t>(); c.n_seq = S;
+  c.embed = embed; c.H = H; c.x_next = x_next; c.eos0 = eos0; c.eos1 = eos1;
+  return c;
+}
+
 }  // namespace
 
 extern "C" {
@@ -259,13 +270,12 @@ int32_t q3a_selftest_sample(int32_t device, const float* logits, int32_t S, int3
   sa.part = ArgmaxPartials{dPv.as<float>(), dPi.as<int>(), nullptr, (int)nc};
   KCHK(launch_sample(sa, nullptr));
   FinalizeArgs f{};
-  f.part = sa.part; f.n_part = (int)nc; f.V = V; f.next_tok = dTok.as<int>(); f.out_ids = dIds.as<int>(); f.out_stride = (int)stride;
-  f.step_count = dSc.as<int>(); f.pos = dPos.as<int>(); f.advance = 1; f.done = dDone.as<uint8_t>(); f.n_seq = S;
-  f.embed = dEmb.as<uint16_t>(); f.H = H; f.x_next = dX.as<float>(); f.eos0 = kEos0; f.eos1 = kEos1;
+  f.part = sa.part; f.n_part = (int)nc; f.V = V; f.advance = 1;
+  f.c = bare_commit(S, dTok, dIds.as<int>(), (int)stride, nullptr, dSc, dPos, dDone, dEmb.as<uint16_t>(), H, dX.as<float>(), kEos0, kEos1);
   KCHK(launch_argmax_finalize(f, S, nullptr));
   SampleLogprobArgs sl{};
-  sl.logits = sa.logits; sl.S = S; sl.V = V; sl.chunk_max = sa.chunk_max; sl.chunk_sum = sa.chunk_sum; sl.next_tok = f.next_tok;
-  sl.step_count = f.step_count; sl.out_lp = dLp.as<float>(); sl.out_stride = (int)stride; sl.part = sa.part; sl.out_z = dZ.as<float>();
+  sl.logits = sa.logits; sl.S = S; sl.V = V; sl.chunk_max = sa.chunk_max; sl.chunk_sum = sa.chunk_sum; sl.next_tok = f.c.next_tok;
+  sl.step_count = f.c.step_count; sl.out_lp = dLp.as<float>(); sl.out_stride = (int)stride; sl.part = sa.part; sl.out_z = dZ.as<float>();
   KCHK(launch_sample_logprob(sl, nullptr));
   finish();
   const std::vector<int> ids = to_host<int>(dIds, Sz * stride);
@@ -313,9 +323,8 @@ int32_t q3a_selftest_repeat(int32_t device, const float* logits, int32_t S, int3
   const ArgmaxPartials part{dPv.as<float>(), dPi.as<int>(), dPs.as<float>(), NP};
   KCHK(launch_argmax_partials(ra.logits, V, S, part, NP, nullptr));
   FinalizeArgs f{};
-  f.part = part; f.n_part = NP; f.out_lp = dLp.as<float>(); f.V = V; f.next_tok = dTok.as<int>(); f.out_ids = dIds.as<int>();
-  f.out_stride = (int)pitch; f.step_count = dSc.as<int>(); f.pos = dPos.as<int>(); f.advance = 1; f.done = dDone.as<uint8_t>(); f.n_seq = S;
-  f.embed = dEmb.as<uint16_t>(); f.H = H; f.x_next = dX.as<float>(); f.eos0 = kEos0; f.eos1 = kEos1;
+  f.part = part; f.n_part = NP; f.V = V; f.advance = 1;
+  f.c = bare_commit(S, dTok, dIds.as<int>(), (int)pitch, dLp.as<float>(), dSc, dPos, dDone, dEmb.as<uint16_t>(), H, dX.as<float>(), kEos0, kEos1);
   KCHK(launch_argmax_finalize(f, S, nullptr));
   finish();
   if (out_logits) to_host(out_logits, dLg, Sz * V);
@@ -393,9 +402,8 @@ int32_t q3a_selftest_gemv_launch(int32_t device, int32_t pruned, const uint16_t*
     const DevBuf dTok = to_device(std::vector<int>(1, -1)), dIds = to_device(std::vector<int>(STRIDE, -1)), dSc = to_device(std::vector<int>(1, STEP));
     const DevBuf dPos = to_device(std::vector<int>(1, POS)), dDone = to_device(std::vector<uint8_t>(1, 0)), dXn = room((size_t)K * 4);
     FinalizeArgs f{};
-    f.part = g.part; f.n_part = n_part; f.V = N; f.next_tok = dTok.as<int>(); f.out_ids = dIds.as<int>(); f.out_stride = STRIDE;
-    f.step_count = dSc.as<int>(); f.pos = dPos.as<int>(); f.advance = 1; f.done = dDone.as<uint8_t>(); f.n_seq = 1;
-    f.embed = g.W; f.H = K; f.x_next = dXn.as<float>(); f.eos0 = -1; f.eos1 = -1;  // (the embedding row of the chosen id: a row of w)
+    f.part = g.part; f.n_part = n_part; f.V = N; f.advance = 1;
+    f.c = bare_commit(1, dTok, dIds.as<int>(), STRIDE, nullptr, dSc, dPos, dDone, g.W, K, dXn.as<float>(), -1, -1);  // (the embedding row of the chosen id: a row of w)
     KCHK(launch_argmax_finalize(f, 1, nullptr));
     finish();
     if (out) dO.fetch(out, "output");
@@ -473,14 +481,13 @@ int32_t q3a_selftest_draft_accept(int32_t device, int32_t S, const int32_t* draf
   DraftAcceptArgs a{};
   a.n_seq = S; a.draft = dDr.as<int>(); a.draft_off = dOff.as<int>(); a.prompt_len = dPl.as<int>();
   a.top_id = dTop.as<int>(); a.top_lp = top_lp ? dTlp.as<float>() : nullptr; a.accepted = dAcc.as<int>();
-  a.next_tok = dTok.as<int>(); a.out_ids = gIds.as<int>(); a.out_stride = out_stride; a.step_count = dSc.as<int>(); a.pos = dPos.as<int>();
-  a.out_lp = gLp.b.p ? gLp.as<float>() : nullptr;
-  a.done = dDone.as<uint8_t>(); a.n_done = dNd.as<int>(); a.host_progress = dProg.as<int>();
-  a.embed = dEmb.as<uint16_t>(); a.H = H; a.x_next = gX.as<float>(); a.eos0 = kEos0; a.eos1 = kEos1;
-  a.cos_t = dCos.as<float>(); a.sin_t = dSin.as<float>(); a.rope_cur = gRope.as<float>();
+  StepCommit& c = a.c;
+  c = bare_commit(S, dTok, gIds.as<int>(), out_stride, gLp.b.p ? gLp.as<float>() : nullptr, dSc, dPos, dDone, dEmb.as<uint16_t>(), H, gX.as<float>(), kEos0, kEos1);
+  c.n_done = dNd.as<int>(); c.host_progress = dProg.as<int>();
+  c.cos_t = dCos.as<float>(); c.sin_t = dSin.as<float>(); c.rope_cur = gRope.as<float>();
   if (norm_w) {
-    a.nn.next_w = dW.as<float>(); a.nn.next_xw16f = gNx.as<uint16_t>(); a.nn.next_ss = gNs.as<float>(); a.nn.nparts = nparts;
-    a.nn.group_stride_x = (long)32 * H; a.nn.group_stride_ss = (long)nparts * 32; a.nn.group_size = group_size;
+    c.nn.next_w = dW.as<float>(); c.nn.next_xw16f = gNx.as<uint16_t>(); c.nn.next_ss = gNs.as<float>(); c.nn.nparts = nparts;
+    c.nn.group_stride_x = (long)32 * H; c.nn.group_stride_ss = (long)nparts * 32; c.nn.group_size = group_size;
   }
   KCHK(launch_draft_accept(a, nullptr));
   finish();

@@ -195,6 +195,36 @@ def test_equals_the_greedy_loop_tiny_dims(peaked40, precise, use_graph):
     print(f"[draft] tiny precise={precise} graph={use_graph}: {compared} (utterance, draft) pairs equal to the plain call and the oracle")
 
 
+@pytest.mark.parametrize("S,precise", [(1, False), (1, True), (3, True), (33, True)])
+def test_empty_draft_leaves_the_state_of_a_plain_prefill(peaked40, S, precise):
+    """prefill_draft with empty drafts commits one token per sequence through the accept kernel, prefill through argmax_finalize:
+    both must leave the same decode state, so the two decode steps behind either are bit-equal.  S = 1 is the GEMV path (no
+    pre-normalised copy of the embedding row), S = 3 and 33 the skinny path with one and two sequence groups.  The default mode
+    from 3 sequences on is left out: the row's sum of squares is folded over 16 waves in finalize and over 4 in the accept kernel."""
+    f = peaked40
+    sel = [u for u, ok in enumerate(f["ok_bf16"]) if ok][:S]
+    assert len(sel) == S
+    eng = HipEngine(f["dir"], 0, max_new_tokens=KMAX, precise=precise)
+    eng.mel([f["clips"][u] for u in sel]); eng.encode()
+    prompts = [HipEngine.build_prompt(t) for t in eng._T]
+
+    def two_steps():
+        steps = [eng.decode_step(want_logits=True) for _ in range(2)]
+        return [lg.copy() for lg, _, _ in steps], [nx.tolist() for _, nx, _ in steps], eng.fetch_ids(KMAX)
+
+    _, nxt_plain = eng.prefill(prompts)
+    plain = two_steps()
+    acc, nxt_draft = eng.prefill_draft(prompts, [[]] * S)
+    draft = two_steps()
+    eng.close()
+    assert acc.tolist() == [0] * S
+    assert nxt_draft.tolist() == nxt_plain.tolist()
+    for a, b in zip(plain[0], draft[0]):
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    assert draft[1] == plain[1]
+    assert draft[2] == plain[2]
+
+
 def test_token_logprobs_agree_with_the_plain_call(peaked40):
     f = peaked40
     sel = [0, 1, 2, 3, 4]

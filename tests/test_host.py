@@ -490,6 +490,36 @@ def test_step_buffers_cover_the_captured_step():
     assert "DecodeStep::each_buf(step," in _cpp_function_body(src, "void setup_prompts(")
 
 
+def test_step_commit_and_score_head_are_stated_once():
+    """What a committed token leaves behind (kernels.h StepCommit) is named for a launch in ONE function of the captured step,
+    DecodeStep::commit(): finalize, the draft accept kernel and a fed token all take it from there, so a new field has one place to
+    go.  Likewise the scoring head's arguments are built in one function of the engine, and the extern "C" layer reaches the step's
+    token feed through the unit, not through its buffers."""
+    src = open(os.path.join(ROOT, "qwen3_asr_rs_amd", "csrc", "engine.cpp")).read()
+    unit = _cpp_function_body(src, "struct DecodeStep : StepView ")
+    commit = _cpp_function_body(unit, "StepCommit commit() const")
+    # every commit buffer is written into an argument struct once in the unit, and that once is inside commit()
+    for field in (r"\.rope_cur = rope_cur\.as<float>\(\);", r"\bx_next =", r"\.done = done\.as<uint8_t>\(\)", r"\.n_done = n_done\.as<int>\(\)",
+                  r"\.host_progress = host_prog_dev;", r"\.embed = wh\(L\.embed\)", r"\.nn = first_layer_norm_out\(\)"):
+        assert len(re.findall(field, unit)) == 1, field
+        assert len(re.findall(field, commit)) == 1, field
+    # its users: the three launches that commit or feed a token, and nothing else builds one
+    assert len(re.findall(r"\bcommit\(\)", unit)) == 4   # the definition, run_head, enqueue_draft_accept, enqueue_set_tokens
+    assert len(re.findall(r"\bStepCommit \w+\{", src)) == 1 and len(re.findall(r"\bStepCommit \w+\{", commit)) == 1
+    for user in ("void run_head(int advance)", "void enqueue_draft_accept(DraftAcceptArgs a)", "void enqueue_set_tokens(const int* tok)"):
+        assert "commit()" in _cpp_function_body(unit, user), user
+    assert len(re.findall(r"\blaunch_set_tokens\(", src)) == 1
+    assert "enqueue_set_tokens(a.feed)" in _cpp_function_body(unit, "void enqueue_beam_round()")
+    # one place builds the scoring head's arguments, on top of the part both row heads share
+    assert len(re.findall(r"\bScoreHeadArgs \w+\{\}", src)) == 1 and len(re.findall(r"\bScoreHeadArgs \w+ = score_head_args\(", src)) == 1
+    assert src.count("score_head_args(") == 3 and src.count("fill_row_head(") == 3   # definition + q3a_score*'s and the draft prefill's / the aligner's use
+    assert len(re.findall(r"\.xn = align_xn\.as<uint16_t>\(\)", src)) == 1
+    # the C ABI layer goes through the unit
+    abi = src[src.index('extern "C" {'):]
+    assert "step.forced_tok" not in abi and "launch_set_tokens" not in abi
+    assert "step.enqueue_forced_tokens(ids)" in _cpp_function_body(abi, "int32_t q3a_set_next_tokens(")
+
+
 def test_mfma_table_shapes_and_launch_matching():
     """tools/mfma_table.py (the counter-vs-wall-clock MFMA table of DESIGN.md section 6): its shape list reproduces the tile counts
     the committed profiles show for 32 clips (conv2 6000, conv3 1560, enc qkv 506 after the round split, fc1 686, 196-tile residual

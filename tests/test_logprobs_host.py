@@ -100,7 +100,10 @@ def test_engine_hands_one_argmax_descriptor_to_every_producer():
     # argmax_partial launches) and to the finalize, which writes out_lp with it
     assert "g.part = part;" in head and "pa = prune_args(g)" in head and "ep.part = part;" in head
     assert head.count("launch_argmax_partials(") == head.count("launch_argmax_partials(logits.as<float>(), V, S, part, n_part, stream)") == 2
-    assert "f.part = part;" in head and re.search(r"f\.out_lp = part\.sum \? out_lp\.as<float>\(\) : nullptr;", head)
+    # (out_lp is part of what a token commits, DecodeStep::commit(), under the same condition as the descriptor's sum)
+    assert "f.part = part;" in head and "f.c = commit();" in head
+    commit = src[src.index("  StepCommit commit() const {"):]
+    assert re.search(r"c\.out_lp = token_lp\(\) \? out_lp\.as<float>\(\) : nullptr;", commit[:commit.index("\n  }\n")])
     sig = src[src.index("std::string make_graph_sig() const"):]
     assert "token_lp()" in sig[:sig.index("return buf;")]
     gemv = _read("qwen3_asr_rs_amd", "csrc", "k_gemv.hip")
