@@ -556,9 +556,41 @@ struct DecodeStep : StepView {
   }
 };
 
+// How far the current batch has come.  Monotone: a stage implies every stage below it, and a call that overwrites what a stage
+// stands for rewinds first.  Decoding: the engine holds decode state (KV cache, next token, out_ids of a prefill).
+enum class Stage { None, Batch, Mel, Encoded, Decoding };
+
+// What a call requires of the engine and what it leaves behind.  The functions below are the ONLY writers of the four words, for the
+// engine and for the extern "C" layer alike (tests/test_host.py), so a new call type states its requirements and its effect in their
+// terms and cannot forget half of a rule.  The captured step reads beam_w() and head_logits() through StepView's references.
+class CallState {
+  Stage stage_ = Stage::None;
+  int beam_w_ = 0;           // > 0: a live beam search, slots per utterance (part of the graph signature); only while Decoding
+  bool fixed_mode_ = false;  // the ids of the last generating call have a fixed length (no cut at EOS)
+  bool head_logits_ = true;  // store the logits of a batched decode step (step API, debug taps); off inside the whole-path calls
+ public:
+  bool at(Stage s) const { return stage_ >= s; }
+  const int& beam_w() const { return beam_w_; }
+  bool fixed_mode() const { return fixed_mode_; }
+  const bool& head_logits() const { return head_logits_; }
+  void advance(Stage s) { if (stage_ < s) stage_ = s; }
+  void rewind(Stage s) {  // to at most s; a search does not outlive its decode state
+    if (stage_ > s) stage_ = s;
+    if (stage_ < Stage::Decoding) end_search();
+  }
+  void drop_decode_state() { rewind(Stage::Encoded); }  // no decode state until the next prefill
+  void require(Stage s, const char* text) const { if (stage_ < s) fail(text); }
+  void require(Stage s, const std::string& text) const { require(s, text.c_str()); }
+  void begin_search(int W) { beam_w_ = W; }
+  void end_search() { beam_w_ = 0; }
+  // the mode pair of a call that generates; a single step of the step API keeps the length rule of its prefill
+  void begin_call(bool fixed, bool keep_logits) { fixed_mode_ = fixed; head_logits_ = keep_logits; }
+  void begin_step_call() { head_logits_ = true; }
+};
+
 }  // namespace
 
-struct q3a_engine {
+struct q3a_engine : CallState {
   Dims d;
   ArenaLayout L;
   q3a_opts opts{};
@@ -578,7 +610,6 @@ struct q3a_engine {
   std::vector<int64_t> n_samples, pcm_off, mel_off;
   std::vector<int> n_frames, n_chunks, T, tok_off;   // per utterance; tok_off = first encoder token
   int total_chunks = 0, total_T = 0, max_frames = 0;
-  bool have_mel = false, have_enc = false, have_prefill = false;
   std::vector<int> P, seq_off;  // prompt lengths / first row
   int total_P = 0, max_ctx = 0, max_new = 0;
   std::vector<AttnSeg> enc_segs_h;
@@ -641,9 +672,6 @@ struct q3a_engine {
   std::vector<ProfEvent>* prof = nullptr;
   Taps taps;
 
-  bool fixed_mode_ = false;
-  bool head_logits_ = true;  // store the logits of a batched decode step (step API, debug taps); off inside run_resident
-  int beam_w_ = 0;           // > 0: beam mode, slots per utterance (part of the graph signature)
   bool logit_bias_on_ = false;  // q3a_set_logit_bias: step.logit_bias is applied by every head of the generation paths (graph signature)
   int logit_bias_finite_ = 0;   // its finite entries (the vocabulary while off): what a beam width is checked against
   bool sampling_on_ = false;    // q3a_set_sampling: temperature > 0, the step draws its ids (k_sample.hip; graph signature)
@@ -655,7 +683,7 @@ struct q3a_engine {
 
   // ---- the captured decode step: its buffers and launches, and all it sees of the members above ----
   DecodeStep step{StepView{d, L, opts, arena, arena_flags, stream, chain_streams, join_ev, fork_ev, n_cu, host_prog_dev, prof, taps, lm_q, lm_qs, lm_q_cols,
-                           B, max_ctx, max_new, gsize, live_nsplit_, attn_nsplit, min_P_, part_stride, beam_w_, kv_layer_elems, head_logits_,
+                           B, max_ctx, max_new, gsize, live_nsplit_, attn_nsplit, min_P_, part_stride, beam_w(), kv_layer_elems, head_logits(),
                            k_parallel_groups, k_skinny_q, k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, logit_bias_on_, sampling_on_, repetition_on_}};
 
   // (the mode rules are stated once, in StepView)
@@ -780,11 +808,11 @@ struct q3a_engine {
   // batch geometry (host integers; audio_encoder.rs:79-121, 263-279)
   void set_batch(const int64_t* ns, int b) {
     // a failure below must not leave the previous batch's device tables paired with new host geometry
-    have_mel = have_enc = have_prefill = false;
+    rewind(Stage::None);
     if (b <= 0) { B = 0; fail("batch must be >= 1"); }
     // the same lengths as the batch before (fixed-length serving windows; every repetition of a benchmark): all tables
     // below are functions of the lengths alone and are already on the device
-    if (geom_valid && b == B && (int)n_samples.size() == b && std::equal(ns, ns + b, n_samples.begin())) return;
+    if (geom_valid && b == B && (int)n_samples.size() == b && std::equal(ns, ns + b, n_samples.begin())) return advance(Stage::Batch);
     geom_valid = false;
     B = 0;
     for (int u = 0; u < b; ++u)
@@ -855,6 +883,7 @@ struct q3a_engine {
     HIPCHK(hipStreamSynchronize(stream));  // host vectors above go out of scope
     B = b;  // committed only after every table is on the device
     geom_valid = true;
+    advance(Stage::Batch);
   }
 
   void upload_pcm(const float* host, const int64_t* ns, int b) {
@@ -972,7 +1001,7 @@ struct q3a_engine {
     mel_done();
   }
   void mel_done() {
-    have_mel = true;
+    advance(Stage::Mel);
     size_t bytes = 0;
     for (int u = 0; u < B; ++u) bytes += (size_t)n_frames[u] * d.n_mels * 4;
     tap("mel", mel.p, bytes);
@@ -980,7 +1009,7 @@ struct q3a_engine {
 
   // =====================================================================================
   void run_encoder() {
-    if (!have_mel) fail("q3a_encode: no mel (call q3a_mel first)");
+    require(Stage::Mel, "q3a_encode: no mel (call q3a_mel first)");
     const int C = d.conv_ch, D = d.enc_d, Fn = d.enc_ffn;
     const int H1 = Dims::conv_len(d.n_mels), W1 = Dims::conv_len(d.chunk_frames());
     const int H2 = Dims::conv_len(H1), W2 = Dims::conv_len(W1);
@@ -1082,7 +1111,7 @@ struct q3a_engine {
     }
     tap("audio_embeds", audio_embeds.p, Tt * d.enc_out * 4);
     HIPCHK(hipGetLastError());
-    have_enc = true;
+    advance(Stage::Encoded);
   }
 
   // =====================================================================================
@@ -1091,10 +1120,9 @@ struct q3a_engine {
   // depend on T[] (host integers of set_batch), and the stream synchronisation below then meets an idle stream instead of
   // draining the encoder between its last kernel and the prefill's first
   void setup_prompts(const int32_t* ids_h, const int32_t* lens, int b, int max_new_req, bool before_encoder = false) {
-    if (!have_enc && !before_encoder) fail("q3a_prefill: no encoder output (call q3a_encode first)");
-    if (b != B) fail("q3a_prefill: batch size differs from the encoded batch");
+    if (!before_encoder) require_encoded("q3a_prefill", b);  // (else b is the batch whose geometry the caller has just set)
     P.assign(lens, lens + b);
-    beam_w_ = 0;  // (a beam search begins after the prefill: q3a_beam_begin)
+    end_search();  // (a beam search begins after the prefill: q3a_beam_begin)
     seq_off.resize(b);
     std::vector<int> rowseq, rowpos, amap((size_t)total_T, -1), last(b);
     int off = 0, maxP = 0;
@@ -1213,11 +1241,14 @@ struct q3a_engine {
     step.run_head(0);
     tap("logits", step.logits.p, (size_t)B * d.vocab * 4);
     HIPCHK(hipGetLastError());
-    have_prefill = true;
+    advance(Stage::Decoding);
   }
 
-  // embedding, audio rows and every decoder layer of the prompts: dec_x holds the last layer's residual stream afterwards
+  // embedding, audio rows and every decoder layer of the prompts: dec_x holds the last layer's residual stream afterwards.  The
+  // layers overwrite the KV cache, so whatever decode state there was ends HERE, for every caller; run_prefill and the draft
+  // prefill advance again once theirs is complete.
   void run_prefill_layers() {
+    drop_decode_state();
     const int H = d.hidden, I = d.inter, QD = d.q_dim(), QKV = d.qkv_dim();
     const bool sp = precise();
     KCHK(launch_embed(ids.as<int>(), total_P, wh(L.embed), H, kAudioPad, dec_x.as<float>(), stream));
@@ -1232,13 +1263,18 @@ struct q3a_engine {
     at.o16 = valu_attn() ? nullptr : dec_ctx.as<uint16_t>();
     if (!valu_attn()) { at.q16 = dec_q16.as<uint16_t>(); at.q_rs = QD; }  // the rope kernel leaves q as bf16 [rows][QD]
     const DevBuf& ctx_in = (valu_attn() && !sp) ? dec_ctx16 : dec_ctx;  // what the o projection reads
-    const bool qkv_bias = arena_flags & kFlagDecQkvBias, o_bias = arena_flags & kFlagDecOBias, mlp_bias = arena_flags & kFlagDecMlpBias;
+    // a projection over all prompt rows: W, N, K, bias and the GLU form from DecodeStep::layer_projs, the rest of ep from the caller
+    auto proj_gemm = [&](const DevBuf& x, const DecodeStep::Proj& p, GemmEpilogue ep) {
+      ep.bias = p.bias;
+      act_gemm(x, p.K, p.W, total_P, p.N, p.K, ep, p.mode == 2);
+    };
     const bool fuse_rope = knobs().fuse_qkrope.load() != 0 && !valu_attn() && !precise() && d.head_dim == 128 && gemm256_eligible(total_P, QKV, H) && H % 64 == 0;
     // (debug_taps + layer_taps: raw copies of every prefill layer's intermediate buffers, for bisecting a run-to-run difference
     // to one launch -- tools/bisect_layers.py -- and for checking one launch against a reference on its own input)
     const bool layer_taps = opts.debug_taps && knobs().layer_taps.load() != 0;
     for (int li = 0; li < d.dec_layers; ++li) {
       const DecLayerOff& l = L.dec[li];
+      const DecodeStep::LayerProjs pj = step.layer_projs(li);
       auto ltap = [&](const char* what, const void* ptr, size_t bytes) {
         if (!layer_taps) return;
         char name[32];
@@ -1255,10 +1291,10 @@ struct q3a_engine {
       rk.q16 = valu_attn() ? nullptr : dec_q16.as<uint16_t>();
       if (fuse_rope) {
         // batch-sized prefill: QK-norm, RoPE and the cache append are the epilogue of the qkv GEMM (k_gemm256.hip)
-        KCHK(launch_gemm256_qkrope(dec_ln.as<uint16_t>(), H, wh(l.qkv_w), total_P, H, qkv_bias ? wf(l.qkv_b) : nullptr, rk, stream));
+        KCHK(launch_gemm256_qkrope(dec_ln.as<uint16_t>(), pj.qkv.K, pj.qkv.W, total_P, pj.qkv.K, pj.qkv.bias, rk, stream));
       } else {
-        GemmEpilogue ep; ep.out = dec_qkv.as<float>(); ep.ldo = QKV; ep.bias = qkv_bias ? wf(l.qkv_b) : nullptr;
-        act_gemm(dec_ln, H, wh(l.qkv_w), total_P, QKV, H, ep, false);
+        GemmEpilogue ep; ep.out = dec_qkv.as<float>(); ep.ldo = QKV;
+        proj_gemm(dec_ln, pj.qkv, ep);
         KCHK(launch_qknorm_rope_kv(rk, total_P, kv_f32(), stream));
       }
       at.k = step.kc_layer(li); at.v = step.vc_layer(li);
@@ -1276,20 +1312,20 @@ struct q3a_engine {
       }
       ltap("attn", ctx_in.p, (size_t)total_P * QD * act_elem());
       {
-        GemmEpilogue ep; ep.out = dec_x.as<float>(); ep.ldo = H; ep.resid = dec_x.as<float>(); ep.bias = o_bias ? wf(l.o_b) : nullptr;
-        act_gemm(ctx_in, QD, wh(l.o_w), total_P, H, QD, ep, false);
+        GemmEpilogue ep; ep.out = dec_x.as<float>(); ep.ldo = H; ep.resid = dec_x.as<float>();
+        proj_gemm(ctx_in, pj.o, ep);
       }
       ltap("o", dec_x.p, (size_t)total_P * H * 4);
       KCHK(launch_rmsnorm(dec_x.as<float>(), wf(l.post_ln), dec_ln.as<float>(), total_P, H, d.rms_eps, stream, act16(dec_ln)));
       ltap("ln2", dec_ln.p, (size_t)total_P * H * act_elem());
       {
-        GemmEpilogue ep; act_out(ep, dec_act); ep.ldo = I; ep.bias = mlp_bias ? wf(l.gu_b) : nullptr;
-        act_gemm(dec_ln, H, wh(l.gu_w), total_P, 2 * I, H, ep, true);
+        GemmEpilogue ep; act_out(ep, dec_act); ep.ldo = I;
+        proj_gemm(dec_ln, pj.gu, ep);
       }
       ltap("act", dec_act.p, (size_t)total_P * I * act_elem());
       {
-        GemmEpilogue ep; ep.out = dec_x.as<float>(); ep.ldo = H; ep.resid = dec_x.as<float>(); ep.bias = mlp_bias ? wf(l.down_b) : nullptr;
-        act_gemm(dec_act, I, wh(l.down_w), total_P, H, I, ep, false);
+        GemmEpilogue ep; ep.out = dec_x.as<float>(); ep.ldo = H; ep.resid = dec_x.as<float>();
+        proj_gemm(dec_act, pj.down, ep);
       }
       ltap("x", dec_x.p, (size_t)total_P * H * 4);
       if (li == 0) tap("dec_layer0", dec_x.p, (size_t)total_P * H * 4);
@@ -1301,6 +1337,11 @@ struct q3a_engine {
   // (k_align.hip); no vocabulary lm_head, no argmax_finalize, no decode state
   void require_asr(const char* what) const {
     if (d.aligner()) fail(std::string(what) + ": this engine holds a forced aligner (classify_num in config.json); use q3a_align*");
+  }
+  // the pair every call of the step API that prefills begins with (`what`: its name in the texts)
+  void require_encoded(const char* what, int b) const {
+    require(Stage::Encoded, std::string(what) + ": no encoder output (call q3a_encode first)");
+    if (b != B) fail(std::string(what) + ": batch size differs from the encoded batch");
   }
   void require_aligner(const char* what) const {
     if (!d.aligner()) fail(std::string(what) + ": not a forced-aligner checkpoint (config.json has no thinker_config.classify_num)");
@@ -1322,22 +1363,24 @@ struct q3a_engine {
   }
   // The skeleton the aligner and the scoring call share: prefill layers, then a head at a list of rows of the last layer's residual
   // stream (uploaded to align_rows), no decode state.  Prompts already set up (setup_prompts).  Events: ev[2] before the prefill
-  // (recorded here), ev[3] after the layers, ev[4] after the head; the stream is idle on return.
+  // (recorded here), ev[3] after the layers, ev[4] after the head; the stream is idle on return.  head_ms null (the draft prefill,
+  // whose whole-path call records ev[2] / ev[3] around its rounds): no event is recorded and no timing written.
   template <class Head>
-  void run_prefill_then_head(const std::vector<int>& rows, float& head_ms, Head&& enqueue_head) {
-    have_prefill = false;
-    HIPCHK(hipEventRecord(ev[2], stream));
+  void run_prefill_then_head(const std::vector<int>& rows, float* head_ms, Head&& enqueue_head) {
+    auto mark = [&](int i) { if (head_ms) HIPCHK(hipEventRecord(ev[i], stream)); };
+    mark(2);
     run_prefill_layers();
-    HIPCHK(hipEventRecord(ev[3], stream));
+    mark(3);
     if (!rows.empty()) {
       upload(align_rows, rows, stream);
       enqueue_head();
     }
-    HIPCHK(hipEventRecord(ev[4], stream));
+    mark(4);
     HIPCHK(hipStreamSynchronize(stream));
     HIPCHK(hipGetLastError());
+    if (!head_ms) return;
     timings.prefill_ms = stage_ms(2, 4);
-    head_ms = stage_ms(3, 4);
+    *head_ms = stage_ms(3, 4);
     timings.decode_ms = 0.f; timings.decode_steps = 0; timings.batch = B; timings.total_audio_tokens = total_T;
     timings.total_prompt_tokens = total_P;
   }
@@ -1382,10 +1425,17 @@ struct q3a_engine {
     a.top_id = score_out.as<int>() + 2 * (size_t)M; a.top_lp = score_out.as<float>() + 3 * (size_t)M;
     return a;
   }
+  // Packed per-position results of a row head (utterance after utterance, n[s] positions each) to the caller's [utterance][stride];
+  // out null: not asked for.
+  template <class T> void scatter_rows(const T* packed, const int32_t* n, int stride, T* out) const {
+    if (!out) return;
+    for (int s = 0, k = 0; s < B; ++s)
+      for (int i = 0; i < n[s]; ++i) out[(size_t)s * stride + i] = packed[k++];
+  }
   // Classes (and logits) to the host, [utterance][stride].
   void run_align(const std::vector<int>& rows, const int32_t* counts, int stride, int32_t* out_classes, float* logits_out) {
     const int M = (int)rows.size(), N = d.classify_num;
-    run_prefill_then_head(rows, align_head_ms, [&] {
+    run_prefill_then_head(rows, &align_head_ms, [&] {
       AlignHeadArgs a{};
       fill_row_head(a, M, N, false, logits_out != nullptr);
       align_cls.ensure((size_t)M * 4);
@@ -1395,8 +1445,7 @@ struct q3a_engine {
     std::vector<int> cls((size_t)M);
     if (M > 0) HIPCHK(hipMemcpy(cls.data(), align_cls.p, (size_t)M * 4, hipMemcpyDeviceToHost));
     if (M > 0 && logits_out) HIPCHK(hipMemcpy(logits_out, align_logits.p, (size_t)M * N * 4, hipMemcpyDeviceToHost));
-    for (int s = 0, k = 0; s < B; ++s)
-      for (int i = 0; i < counts[s]; ++i) out_classes[(size_t)s * stride + i] = cls[k++];
+    scatter_rows(cls.data(), counts, stride, out_classes);
   }
   DevBuf align_rows, align_xn, align_pval, align_pidx, align_cls, align_logits;
   float align_head_ms = 0.f;  // the head's launches of the last align call (q3a_debug_read "align_head_ms")
@@ -1404,61 +1453,64 @@ struct q3a_engine {
   // =====================================================================================
   // scoring a given transcript (q3a_score*): ONE causal prefill over prompt + targets[:-1], then the lm_head at the rows that
   // predict the targets with a reducing epilogue (k_align.hip launch_score_head); no argmax_finalize, no decode state.
-  struct ScorePlan {
-    std::vector<int32_t> ids, lens;  // what is prefilled: per utterance prompt ++ targets[0 .. n-2]
-    std::vector<int> rows, targets;  // per scored position: row of the residual stream that predicts it, and its id
+  // Ids a caller hands in to be fed behind the prompt -- targets to score, a draft to verify -- as ONE plan of the prefill and its head rows.
+  struct GivenPlan {
+    std::vector<int32_t> ids, lens;  // what is prefilled: per utterance prompt ++ given ids (all of them, or all but the last)
+    std::vector<int> rows, targets;  // per head row: row of the residual stream, and the given id it predicts (a trailing row has none: id 0)
+    std::vector<int32_t> n;          // given ids per utterance
   };
-  // what no id a caller hands in to be fed behind the prompt may be; noun: "target" (q3a_score*) or "draft" (draft calls).  The texts
-  // say "target id 7 out of range" / "cannot be a target" and "draft id 7 out of range" / "cannot be a draft id".
-  void check_given_id(const char* what, const std::string& noun, int32_t y) const {
-    if (y < 0 || y >= d.vocab) fail(std::string(what) + ": " + noun + " id " + std::to_string(y) + " out of range (vocabulary " + std::to_string(d.vocab) + ")");
-    if (y == kAudioPad)
-      fail(std::string(what) + ": <|audio_pad|> (" + std::to_string(kAudioPad) + ") cannot be a " + (noun == "target" ? noun : noun + " id") + ": the engine finds audio rows by this id");
-  }
-  // prompt_ids / target_ids concatenated over the batch; refuses what the header lists
-  ScorePlan score_plan(const char* what, const int32_t* prompt_ids, const int32_t* prompt_lens, const int32_t* target_ids,
-                       const int32_t* target_lens, int b, int stride) const {
-    ScorePlan sp;
-    sp.lens.resize(b);
+  // The two uses differ in this much.  Scoring never feeds the last target (nothing is predicted from it); a draft feeds every id, adds
+  // the row that predicts the token after the draft, and may hold no EOS.  The rest is what their refusals name.
+  struct GivenPolicy {
+    const char* noun;          // "target id 7 out of range" / "draft id 7 out of range"
+    const char* cannot_be;     // "cannot be a target" / "cannot be a draft id"
+    bool feed_last, trailing_row, refuse_eos;
+    const char *count_pre, *count_post, *limit_noun;  // "has 9 targets, more than stride 8" / "has a draft of 9 ids, more than max_new 8"
+  };
+  static constexpr GivenPolicy kScored{"target", "target", false, false, false, "", " targets", "stride"};
+  static constexpr GivenPolicy kDrafted{"draft", "draft id", true, true, true, "a draft of ", " ids", "max_new"};
+  // prompt_ids / given_ids concatenated over the batch; refuses what the header lists for the call `what`
+  GivenPlan given_plan(const char* what, const GivenPolicy& pol, const int32_t* prompt_ids, const int32_t* prompt_lens, const int32_t* given_ids,
+                       const int32_t* given_lens, int b, int limit) const {
+    const std::string w(what);
+    GivenPlan gp;
+    gp.lens.resize(b);
+    gp.n.assign(given_lens, given_lens + b);
     size_t po = 0, to = 0;
     for (int s = 0; s < b; ++s) {
-      const int p = prompt_lens[s], n = target_lens[s];
-      if (p <= 0) fail(std::string(what) + ": empty prompt");
-      if (n < 0 || (n > 0 && !target_ids)) fail(std::string(what) + ": bad target length");
-      if (n > stride)
-        fail(std::string(what) + ": utterance " + std::to_string(s) + " has " + std::to_string(n) + " targets, more than stride " + std::to_string(stride));
-      const int row0 = (int)sp.ids.size() + p - 1;
-      sp.ids.insert(sp.ids.end(), prompt_ids + po, prompt_ids + po + p);
+      const int p = prompt_lens[s], n = given_lens[s];
+      if (p <= 0) fail(w + ": empty prompt");
+      if (n < 0 || (n > 0 && !given_ids)) fail(w + ": bad " + pol.noun + " length");
+      if (n > limit)
+        fail(w + ": utterance " + std::to_string(s) + " has " + pol.count_pre + std::to_string(n) + pol.count_post + ", more than " + pol.limit_noun + " " + std::to_string(limit));
+      const int row0 = (int)gp.ids.size() + p - 1, fed = pol.feed_last ? n : std::max(n - 1, 0);
+      gp.ids.insert(gp.ids.end(), prompt_ids + po, prompt_ids + po + p);
       for (int i = 0; i < n; ++i) {
-        const int32_t y = target_ids[to + i];
-        check_given_id(what, "target", y);
-        if (i + 1 < n) sp.ids.push_back(y);  // the last target is never fed
-        sp.rows.push_back(row0 + i);
-        sp.targets.push_back(y);
+        const int32_t y = given_ids[to + i];
+        if (y < 0 || y >= d.vocab) fail(w + ": " + pol.noun + " id " + std::to_string(y) + " out of range (vocabulary " + std::to_string(d.vocab) + ")");
+        if (y == kAudioPad) fail(w + ": <|audio_pad|> (" + std::to_string(kAudioPad) + ") cannot be a " + pol.cannot_be + ": the engine finds audio rows by this id");
+        if (pol.refuse_eos && (y == kEos0 || y == kEos1)) fail(w + ": an EOS id (" + std::to_string(y) + ") cannot be a draft id: a draft ends where its ids end");
+        if (i < fed) gp.ids.push_back(y);
+        gp.rows.push_back(row0 + i);
+        gp.targets.push_back(y);
       }
-      sp.lens[s] = p + std::max(n - 1, 0);
+      if (pol.trailing_row) { gp.rows.push_back(row0 + n); gp.targets.push_back(0); }
+      gp.lens[s] = p + fed;
       po += p; to += n;
     }
-    return sp;
+    return gp;
   }
   // prompts of sp already set up.  Results to the host [utterance][stride]; logits_out (nullable): [rows][vocab].
-  void run_score(const ScorePlan& sp, const int32_t* target_lens, int stride, float* out_lp, int32_t* out_top_ids, float* out_top_lp,
-                 float* logits_out) {
+  void run_score(const GivenPlan& sp, int stride, float* out_lp, int32_t* out_top_ids, float* out_top_lp, float* logits_out) {
     const int M = (int)sp.rows.size(), V = d.vocab;
-    run_prefill_then_head(sp.rows, score_head_ms, [&] { KCHK(launch_score_head(score_head_args(M, sp.targets, logits_out != nullptr), stream)); });
+    run_prefill_then_head(sp.rows, &score_head_ms, [&] { KCHK(launch_score_head(score_head_args(M, sp.targets, logits_out != nullptr), stream)); });
     if (M == 0) return;
-    std::vector<float> res((size_t)M * 4);
+    std::vector<float> res((size_t)M * 4);  // tgt_logit | lp | top_id | top_lp
     HIPCHK(hipMemcpy(res.data(), score_out.p, res.size() * 4, hipMemcpyDeviceToHost));
     if (logits_out) HIPCHK(hipMemcpy(logits_out, align_logits.p, (size_t)M * V * 4, hipMemcpyDeviceToHost));
-    const float* lp = res.data() + M;
-    const int32_t* ti = reinterpret_cast<const int32_t*>(res.data()) + 2 * (size_t)M;
-    const float* tl = res.data() + 3 * (size_t)M;
-    for (int s = 0, k = 0; s < B; ++s)
-      for (int i = 0; i < target_lens[s]; ++i, ++k) {
-        out_lp[(size_t)s * stride + i] = lp[k];
-        if (out_top_ids) out_top_ids[(size_t)s * stride + i] = ti[k];
-        if (out_top_lp) out_top_lp[(size_t)s * stride + i] = tl[k];
-      }
+    scatter_rows(res.data() + M, sp.n.data(), stride, out_lp);
+    scatter_rows(reinterpret_cast<const int32_t*>(res.data()) + 2 * (size_t)M, sp.n.data(), stride, out_top_ids);
+    scatter_rows(res.data() + 3 * (size_t)M, sp.n.data(), stride, out_top_lp);
   }
   DevBuf score_tgt, score_psum, score_out;
   float score_head_ms = 0.f;  // the head's launches of the last score call (q3a_debug_read "score_head_ms")
@@ -1467,68 +1519,35 @@ struct q3a_engine {
   // draft-verified decoding (q3a_prefill_draft / q3a_transcribe_draft_batch_ptrs): ONE causal prefill over
   // prompt ++ draft, the scoring head at the n + 1 rows p - 1 .. p - 1 + n (under the logit bias, if one is set), then
   // DecodeStep::enqueue_draft_accept -- and the engine stands where the greedy loop stands after its first k + 1 tokens.
-  struct DraftPlan {
-    std::vector<int32_t> ids, lens;  // what is prefilled: per utterance prompt ++ draft (every draft id is fed, unlike scoring)
-    std::vector<int> rows, targets;  // per head row: row of the residual stream, and the draft id it is compared with (the last row of an utterance has none: id 0)
-    std::vector<int> words;          // the accept kernel's inputs: draft_off [B + 1] | prompt_len [B] | draft ids
-    std::vector<int> plen, dlen;
-  };
-  // what no draft call runs under (the header's list; the per-id refusals are draft_plan's)
+  // what no draft call runs under (the header's list; the per-id refusals are given_plan's)
   void draft_check(const char* what) const {
     require_asr(what);
     if (sampling_on_) fail(std::string(what) + ": sampling is on (q3a_set_sampling with temperature > 0): a sampled id is not the argmax of its row -- turn it off first");
     if (repetition_on_) fail(std::string(what) + ": repetition control is on (q3a_set_repetition): its choice depends on the history, not on the row alone -- turn it off first");
-    if (beam_w_ > 0) fail(std::string(what) + ": a beam search owns the decode state (a new q3a_prefill returns to the greedy step)");
+    if (beam_w() > 0) fail(std::string(what) + ": a beam search owns the decode state (a new q3a_prefill returns to the greedy step)");
   }
-  DraftPlan draft_plan(const char* what, const int32_t* prompt_ids, const int32_t* prompt_lens, const int32_t* draft_ids, const int32_t* draft_lens,
-                       int b, int max_new_eff) const {
-    DraftPlan dp;
-    dp.lens.resize(b); dp.plen.resize(b); dp.dlen.resize(b);
-    dp.words.assign((size_t)2 * b + 1, 0);
-    size_t po = 0, to = 0;
-    for (int s = 0; s < b; ++s) {
-      const int p = prompt_lens[s], n = draft_lens[s];
-      if (p <= 0) fail(std::string(what) + ": empty prompt");
-      if (n < 0 || (n > 0 && !draft_ids)) fail(std::string(what) + ": bad draft length");
-      if (n > max_new_eff)
-        fail(std::string(what) + ": utterance " + std::to_string(s) + " has a draft of " + std::to_string(n) + " ids, more than max_new " + std::to_string(max_new_eff));
-      const int row0 = (int)dp.ids.size() + p - 1;
-      dp.ids.insert(dp.ids.end(), prompt_ids + po, prompt_ids + po + p);
-      for (int i = 0; i < n; ++i) {
-        const int32_t y = draft_ids[to + i];
-        check_given_id(what, "draft", y);
-        if (y == kEos0 || y == kEos1) fail(std::string(what) + ": an EOS id (" + std::to_string(y) + ") cannot be a draft id: a draft ends where its ids end");
-        dp.ids.push_back(y);
-        dp.words.push_back(y);
-        dp.rows.push_back(row0 + i);
-        dp.targets.push_back(y);
-      }
-      dp.rows.push_back(row0 + n);
-      dp.targets.push_back(0);
-      dp.lens[s] = p + n; dp.plen[s] = p; dp.dlen[s] = n;
-      dp.words[s + 1] = dp.words[s] + n;
-      dp.words[(size_t)b + 1 + s] = p;
-      po += p; to += n;
-    }
-    return dp;
-  }
-  // prompts of dp already set up (setup_prompts over dp.ids / dp.lens).  acc [2 B]: k per utterance, then its token.  logits_out
-  // (nullable): the head's rows [sum (n + 1)][vocab].  The stream is idle on return and the engine holds decode state.
-  void run_prefill_draft(const DraftPlan& dp, std::vector<int>& acc, float* logits_out) {
+  // prompts of dp (a kDrafted plan) already set up (setup_prompts over dp.ids / dp.lens).  acc [2 B]: k per utterance, then its token.
+  // logits_out (nullable): the head's rows [sum (n + 1)][vocab].  The stream is idle on return and the engine holds decode state.
+  void run_prefill_draft(const GivenPlan& dp, std::vector<int>& acc, float* logits_out) {
     const int M = (int)dp.rows.size(), V = d.vocab;
-    have_prefill = false;
-    run_prefill_layers();
-    upload(align_rows, dp.rows, stream);
-    upload(draft_in, dp.words, stream);
-    ScoreHeadArgs a = score_head_args(M, dp.targets, logits_out != nullptr);
-    a.bias = step.head_bias();  // a logit bias composes: the verify head is a head of the generation paths
-    KCHK(launch_score_head(a, stream));
-    DraftAcceptArgs da{};
-    da.draft_off = draft_in.as<int>(); da.prompt_len = da.draft_off + B + 1; da.draft = da.prompt_len + B;
-    da.top_id = a.top_id; da.top_lp = a.top_lp;
-    step.enqueue_draft_accept(da);
-    HIPCHK(hipStreamSynchronize(stream));
-    HIPCHK(hipGetLastError());
+    // the accept kernel's inputs: draft_off [B + 1] | prompt_len [B] | draft ids (what each utterance feeds behind its prompt)
+    std::vector<int> words((size_t)2 * B + 1, 0);
+    for (int s = 0, off = 0; s < B; off += dp.lens[s++]) {
+      words[s + 1] = words[s] + dp.n[s];
+      words[(size_t)B + 1 + s] = dp.lens[s] - dp.n[s];
+      words.insert(words.end(), dp.ids.begin() + off + dp.lens[s] - dp.n[s], dp.ids.begin() + off + dp.lens[s]);
+    }
+    const int* const plen = words.data() + B + 1;  // (the insertions are over)
+    run_prefill_then_head(dp.rows, nullptr, [&] {
+      upload(draft_in, words, stream);
+      ScoreHeadArgs a = score_head_args(M, dp.targets, logits_out != nullptr);
+      a.bias = step.head_bias();  // a logit bias composes: the verify head is a head of the generation paths
+      KCHK(launch_score_head(a, stream));
+      DraftAcceptArgs da{};
+      da.draft_off = draft_in.as<int>(); da.prompt_len = da.draft_off + B + 1; da.draft = da.prompt_len + B;
+      da.top_id = a.top_id; da.top_lp = a.top_lp;
+      step.enqueue_draft_accept(da);
+    });
     acc.resize((size_t)2 * B);
     HIPCHK(hipMemcpy(acc.data(), step.draft_accepted.p, acc.size() * 4, hipMemcpyDeviceToHost));
     if (logits_out) HIPCHK(hipMemcpy(logits_out, align_logits.p, (size_t)M * V * 4, hipMemcpyDeviceToHost));
@@ -1536,13 +1555,13 @@ struct q3a_engine {
     // live_nsplit_ from it), min_P_ a lower bound of the live lengths (trim_prologue; both are in the graph signature)
     pos_hi_ = 0; min_P_ = 0x7fffffff;
     for (int s = 0; s < B; ++s) {
-      if (acc[s] < 0 || acc[s] > dp.dlen[s]) fail("draft accept: the device returned a first mismatch outside the draft");
-      pos_hi_ = std::max(pos_hi_, dp.plen[s] + acc[s]);
-      min_P_ = std::min(min_P_, dp.plen[s] + acc[s]);
+      if (acc[s] < 0 || acc[s] > dp.n[s]) fail("draft accept: the device returned a first mismatch outside the draft");
+      pos_hi_ = std::max(pos_hi_, plen[s] + acc[s]);
+      min_P_ = std::min(min_P_, plen[s] + acc[s]);
     }
     draft_stats_[0] += 1;
     draft_stats_.push_back(total_P);
-    have_prefill = true;
+    advance(Stage::Decoding);
   }
   DevBuf draft_in;
   std::vector<int32_t> draft_stats_{0};  // of the last draft call: rounds run, then the rows prefilled in each (q3a_debug_read "draft_stats")
@@ -1575,7 +1594,7 @@ struct q3a_engine {
     char buf[256];
     // (one field per latched knob, as latched: packing several into one integer let distinct settings collide -- ADVICE r5)
     snprintf(buf, sizeof(buf), "%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.b%d.lb%d.sm%d.rp%d/%d/%d/%d/%p/%016llx", B, gsize, k_parallel_groups, k_skinny_q,
-             k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, (int)(min_P_ < 256), (int)head_logits_, (int)token_lp(), beam_w_, (int)logit_bias_on_, (int)sampling_on_, (int)repetition_on_, live_nsplit_,
+             k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, (int)(min_P_ < 256), (int)head_logits(), (int)token_lp(), beam_w(), (int)logit_bias_on_, (int)sampling_on_, (int)repetition_on_, live_nsplit_,
              max_ctx, max_new, (const void*)arena, (unsigned long long)h);
     return buf;
   }
@@ -1633,7 +1652,7 @@ struct q3a_engine {
   }
 
   void decode_steps(int n) {
-    if (!have_prefill) fail("decode: no prefill state");
+    require(Stage::Decoding, "decode: no prefill state");
     if (n <= 0) return;
     const bool eager = !opts.use_graph || prof;
     const int kps = dattn_keys_per_split(kv_f32());
@@ -1675,7 +1694,6 @@ struct q3a_engine {
     std::vector<const float*> ptrs((size_t)b);
     std::vector<int64_t> ns((size_t)b);
     for (int s = 0; s < b; ++s) { ptrs[s] = pcm16k[s / width]; ns[s] = ns_in[s / width]; }
-    have_prefill = false;
     set_batch(ns.data(), b);
     auto&& [ids_v, lens_v] = prompts();
     setup_prompts(ids_v.data(), lens_v.data(), b, max_new_req, true);
@@ -1686,7 +1704,6 @@ struct q3a_engine {
 
   // front_done: whole_path_front() has enqueued the log-mel and the encoder (ev[0] / ev[1] recorded); else the prompts are set up
   void run_resident(int fixed_new, bool front_done = false) {
-    if (B <= 0) fail("q3a_run_resident: no batch uploaded");
     if (!front_done) {
       HIPCHK(hipEventRecord(ev[0], stream));
       run_mel();
@@ -1721,12 +1738,25 @@ struct q3a_engine {
   }
 
   void fetch_ids(int32_t* out, int stride, int32_t* out_lens) {
-    if (!have_prefill || beam_w_ > 0) fail("q3a_fetch_ids: nothing generated");
-    std::vector<int> all((size_t)B * max_new);
-    HIPCHK(hipMemcpy(all.data(), step.out_ids.p, all.size() * 4, hipMemcpyDeviceToHost));
-    generated_lens(all, out_lens);
+    if (!at(Stage::Decoding) || beam_w() > 0) fail("q3a_fetch_ids: nothing generated");
+    fetch_generated<int32_t>(nullptr, out, stride, out_lens);
+  }
+  // opts.token_logprobs: the log-probability of every id fetch_ids returns, same order and lengths
+  void fetch_logprobs(float* out, int stride, int32_t* out_lens) {
+    if (!token_lp()) fail("q3a_fetch_logprobs: the engine was created without opts.token_logprobs = 1");
+    require(Stage::Decoding, "q3a_fetch_logprobs: nothing generated");
+    fetch_generated<float>(&step.out_lp, out, stride, out_lens);
+  }
+  // What the two share: out_ids to the host, the length rule, and every sequence's first min(length, stride) words -- of `vals`
+  // ([B][max_new] on the device, T words), or with vals null of the ids themselves.
+  template <class T> void fetch_generated(const DevBuf* vals, T* out, int stride, int32_t* out_lens) {
+    std::vector<int> ids((size_t)B * max_new);
+    std::vector<T> v(vals ? ids.size() : 0);
+    HIPCHK(hipMemcpy(ids.data(), step.out_ids.p, ids.size() * 4, hipMemcpyDeviceToHost));
+    if (vals) HIPCHK(hipMemcpy(v.data(), vals->p, v.size() * sizeof(T), hipMemcpyDeviceToHost));
+    generated_lens(ids, out_lens);
     for (int s = 0; s < B; ++s)
-      for (int i = 0; i < std::min(out_lens[s], stride); ++i) out[(size_t)s * stride + i] = all[(size_t)s * max_new + i];
+      for (int i = 0; i < std::min(out_lens[s], stride); ++i) out[(size_t)s * stride + i] = vals ? v[(size_t)s * max_new + i] : (T)ids[(size_t)s * max_new + i];
   }
   // lengths of the generated ids per sequence (all = out_ids on the host)
   void generated_lens(const std::vector<int>& all, int32_t* out_lens) {
@@ -1736,22 +1766,10 @@ struct q3a_engine {
       int n = std::min(sc[s], max_new), len = 0;
       for (; len < n; ++len) {
         int t = all[(size_t)s * max_new + len];
-        if (!fixed_mode_ && (t == kEos0 || t == kEos1)) break;  // generated_ids excludes EOS (inference.rs:163-167)
+        if (!fixed_mode() && (t == kEos0 || t == kEos1)) break;  // generated_ids excludes EOS (inference.rs:163-167)
       }
       out_lens[s] = len;
     }
-  }
-  // opts.token_logprobs: the log-probability of every id fetch_ids returns, same order and lengths
-  void fetch_logprobs(float* out, int stride, int32_t* out_lens) {
-    if (!token_lp()) fail("q3a_fetch_logprobs: the engine was created without opts.token_logprobs = 1");
-    if (!have_prefill) fail("q3a_fetch_logprobs: nothing generated");
-    std::vector<int> all((size_t)B * max_new);
-    std::vector<float> lp((size_t)B * max_new);
-    HIPCHK(hipMemcpy(all.data(), step.out_ids.p, all.size() * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(lp.data(), step.out_lp.p, lp.size() * 4, hipMemcpyDeviceToHost));
-    generated_lens(all, out_lens);
-    for (int s = 0; s < B; ++s)
-      for (int i = 0; i < std::min(out_lens[s], stride); ++i) out[(size_t)s * stride + i] = lp[(size_t)s * max_new + i];
   }
 
   // =====================================================================================
@@ -1798,7 +1816,7 @@ struct q3a_engine {
     const bool on = !(n == 0 && default_bias == 0.f);
     const bool eos_open = (kEos0 < V && b[kEos0] != -INFINITY) || (kEos1 < V && b[kEos1] != -INFINITY);
     repetition_bias_check(what, rep_ngram_, eos_open, finite);
-    have_prefill = false; beam_w_ = 0;  // no decode state until the next prefill, as after q3a_score
+    drop_decode_state();
     HIPCHK(hipMemcpyAsync(step.logit_bias.p, b.data(), (size_t)V * 4, hipMemcpyHostToDevice, stream));
     HIPCHK(hipStreamSynchronize(stream));
     logit_bias_on_ = on;
@@ -1818,7 +1836,7 @@ struct q3a_engine {
     repetition_bias_check(what, ngram, logit_bias_eos_open_, logit_bias_finite_);
     uint32_t w[4] = {0, (uint32_t)ngram, 0, 0};
     memcpy(&w[0], &penalty, 4);
-    have_prefill = false; beam_w_ = 0;
+    drop_decode_state();
     HIPCHK(hipMemcpyAsync(step.rep_params.p, w, 16, hipMemcpyHostToDevice, stream));
     HIPCHK(hipStreamSynchronize(stream));
     rep_penalty_ = penalty; rep_ngram_ = ngram;
@@ -1844,7 +1862,7 @@ struct q3a_engine {
     uint32_t w[4];
     memcpy(&w[0], &temperature, 4); memcpy(&w[1], &min_p, 4);
     w[2] = (uint32_t)seed; w[3] = (uint32_t)(seed >> 32);
-    have_prefill = false; beam_w_ = 0;
+    drop_decode_state();
     HIPCHK(hipMemcpyAsync(step.samp_params.p, w, 16, hipMemcpyHostToDevice, stream));
     HIPCHK(hipStreamSynchronize(stream));
     memcpy(samp_words_, w, 16);
@@ -1860,12 +1878,12 @@ struct q3a_engine {
 
   // state for a search over the prefilled batch, then round 0 on the prefill's logits (enqueued; nothing waited for)
   void beam_begin(const char* what, int W) {
-    if (!have_prefill) fail(std::string(what) + ": no prefill state (call q3a_prefill first)");
+    require(Stage::Decoding, std::string(what) + ": no prefill state (call q3a_prefill first)");
     beam_check(what, W);
     beam_sampling_check(what);
     beam_repetition_check(what);
     beam_bias_check(what, W);
-    if (!head_logits_ || pos_hi_ != *std::max_element(P.begin(), P.end()))
+    if (!head_logits() || pos_hi_ != *std::max_element(P.begin(), P.end()))
       fail(std::string(what) + ": needs the logits of q3a_prefill (call it directly after the prefill)");
     const int S = B, nc = beam_topk_chunks(d.vocab);
     step.beam_cand_val.ensure((size_t)S * nc * W * 4); step.beam_cand_idx.ensure((size_t)S * nc * W * 4);
@@ -1881,7 +1899,8 @@ struct q3a_engine {
     HIPCHK(hipStreamSynchronize(stream));  // (host vectors above; and no earlier launch still writes the progress words)
     __atomic_store_n(&beam_prog()[0], 0, __ATOMIC_RELAXED);
     __atomic_store_n(&beam_prog()[1], 0, __ATOMIC_RELAXED);
-    beam_w_ = W; beam_dbg_S_ = S; beam_dbg_W_ = W;
+    begin_search(W);
+    beam_dbg_S_ = S; beam_dbg_W_ = W;
     step.enqueue_beam_round();
     HIPCHK(hipGetLastError());
   }
@@ -1921,8 +1940,7 @@ struct q3a_engine {
   // hypotheses of every utterance, best first: out_ids [U][W][stride], out_lens / out_scores / out_finished [U][W], out_lp nullable
   // [U][W][stride + 1] (per token, then the EOS's when finished)
   void beam_fetch(int32_t* out, int stride, int32_t* out_lens, float* out_scores, uint8_t* out_fin, float* out_lp) {
-    if (beam_w_ <= 0) fail("q3a_beam_fetch: no beam search (call q3a_beam_begin first)");
-    const int W = beam_w_, S = B, U = B / W;
+    const int W = beam_w(), S = B, U = B / W;  // (a live search: the callers' check)
     const int R = std::min(beam_state_host()[BEAM_ST_ROUNDS], max_new);
     std::vector<int> hp((size_t)R * S), ht((size_t)R * S);
     std::vector<float> hl((size_t)R * S), sc(S);
@@ -2130,8 +2148,7 @@ int32_t q3a_align(q3a_engine* e, const int32_t* ids, const int32_t* lens, int32_
   e->require_aligner("q3a_align");
   if (!ids || !lens || B < 1 || !out_counts || stride < 0 || (stride > 0 && !out_classes)) fail("q3a_align: bad argument");
   HIPCHK(hipSetDevice(e->device));
-  if (!e->have_enc) fail("q3a_align: no encoder output (call q3a_encode first)");
-  if (B != e->B) fail("q3a_align: batch size differs from the encoded batch");
+  e->require_encoded("q3a_align", B);
   const std::vector<int> rows = e->align_marker_rows(ids, lens, B, stride, out_counts);
   e->setup_prompts(ids, lens, B, 1);
   e->timings = q3a_timings{};
@@ -2173,13 +2190,11 @@ int32_t q3a_score(q3a_engine* e, const int32_t* prompt_ids, const int32_t* promp
   e->require_asr("q3a_score");
   if (!prompt_ids || !prompt_lens || !target_lens || B < 1 || stride < 0 || (stride > 0 && !out_lp)) fail("q3a_score: bad argument");
   HIPCHK(hipSetDevice(e->device));
-  if (!e->have_enc) fail("q3a_score: no encoder output (call q3a_encode first)");
-  if (B != e->B) fail("q3a_score: batch size differs from the encoded batch");
-  const auto sp = e->score_plan("q3a_score", prompt_ids, prompt_lens, target_ids, target_lens, B, stride);
-  e->have_prefill = false;
+  e->require_encoded("q3a_score", B);
+  const auto sp = e->given_plan("q3a_score", q3a_engine::kScored, prompt_ids, prompt_lens, target_ids, target_lens, B, stride);
   e->setup_prompts(sp.ids.data(), sp.lens.data(), B, 1);
   e->timings = q3a_timings{};
-  e->run_score(sp, target_lens, stride, out_lp, out_top_ids, out_top_lp, logits_out);
+  e->run_score(sp, stride, out_lp, out_top_ids, out_top_lp, logits_out);
   Q3A_CATCH(e)
 }
 
@@ -2190,13 +2205,13 @@ int32_t q3a_score_batch_ptrs(q3a_engine* e, const float* const* pcm16k, const in
   Q3A_TRY(e)
   e->require_asr("q3a_score_batch");
   if (!target_lens || stride < 0 || (stride > 0 && !out_lp) || n_prefix < 0) fail("q3a_score_batch: bad argument");
-  q3a_engine::ScorePlan sp;
+  q3a_engine::GivenPlan sp;
   e->whole_path_front("q3a_score_batch", pcm16k, n_samples, B, 1, 1, [&] {
     const auto pr = e->asr_prompts(lang_prefix_ids, n_prefix);
-    sp = e->score_plan("q3a_score_batch", pr.first.data(), pr.second.data(), target_ids, target_lens, B, stride);
+    sp = e->given_plan("q3a_score_batch", q3a_engine::kScored, pr.first.data(), pr.second.data(), target_ids, target_lens, B, stride);
     return std::tie(sp.ids, sp.lens);
   });
-  e->run_score(sp, target_lens, stride, out_lp, out_top_ids, out_top_lp, nullptr);
+  e->run_score(sp, stride, out_lp, out_top_ids, out_top_lp, nullptr);
   e->front_and_total_timings();
   Q3A_CATCH(e)
 }
@@ -2218,9 +2233,9 @@ int32_t q3a_beam_step(q3a_engine* e, uint8_t* all_finished, float* logits_out) {
   Q3A_TRY(e)
   e->require_asr("q3a_beam_step");
   HIPCHK(hipSetDevice(e->device));
-  if (e->beam_w_ <= 0 || !e->have_prefill) fail("q3a_beam_step: no beam search (call q3a_beam_begin first)");
+  if (e->beam_w() <= 0) fail("q3a_beam_step: no beam search (call q3a_beam_begin first)");
   if (e->beam_state_host()[BEAM_ST_ROUNDS] >= e->max_new) fail("q3a_beam_step: the round limit (max_new_tokens) is reached");
-  e->head_logits_ = true;
+  e->begin_step_call();
   e->decode_steps(1);
   const std::vector<int> st = e->beam_state_host();
   HIPCHK(hipGetLastError());
@@ -2234,7 +2249,7 @@ int32_t q3a_beam_fetch(q3a_engine* e, int32_t* out_ids, int32_t stride, int32_t*
   if (!e) return 1;
   Q3A_TRY(e)
   e->require_asr("q3a_beam_fetch");
-  if (e->beam_w_ <= 0) fail("q3a_beam_fetch: no beam search (call q3a_beam_begin first)");
+  if (e->beam_w() <= 0) fail("q3a_beam_fetch: no beam search (call q3a_beam_begin first)");
   if (!out_lens || stride < 0 || (stride > 0 && !out_ids)) fail("q3a_beam_fetch: bad argument");
   HIPCHK(hipSetDevice(e->device));
   e->beam_fetch(out_ids, stride, out_lens, out_scores, out_finished, out_lp);
@@ -2255,8 +2270,7 @@ int32_t q3a_beam_search_batch_ptrs(q3a_engine* e, const float* const* pcm16k, co
   e->beam_sampling_check("q3a_beam_search_batch");
   e->beam_repetition_check("q3a_beam_search_batch");
   e->beam_bias_check("q3a_beam_search_batch", width);
-  e->fixed_mode_ = false;
-  e->head_logits_ = true;  // every round selects on the stored logits
+  e->begin_call(false, true);  // every round selects on the stored logits
   // the W slots of an utterance are W ordinary sequences of the batch
   e->whole_path_front("q3a_beam_search_batch", pcm16k, n_samples, U, width, want, [&] { return e->asr_prompts(lang_prefix_ids, n_prefix); });
   HIPCHK(hipEventRecord(e->ev[2], e->stream));
@@ -2269,8 +2283,7 @@ int32_t q3a_beam_search_batch_ptrs(q3a_engine* e, const float* const* pcm16k, co
   HIPCHK(hipGetLastError());
   e->decode_timings(std::max(st[BEAM_ST_ROUNDS] - 1, 0));
   e->beam_fetch(out_ids, stride, out_lens, out_scores, out_finished, out_lp);
-  // as after q3a_score: no decode state until the next prefill
-  e->beam_w_ = 0; e->have_prefill = false;
+  e->drop_decode_state();  // as after q3a_score
   Q3A_CATCH(e)
 }
 
@@ -2345,8 +2358,7 @@ int32_t q3a_prefill(q3a_engine* e, const int32_t* ids, const int32_t* lens, int3
   Q3A_TRY(e)
   e->require_asr("q3a_prefill");
   HIPCHK(hipSetDevice(e->device));
-  e->fixed_mode_ = false;
-  e->head_logits_ = true;
+  e->begin_call(false, true);
   e->setup_prompts(ids, lens, B, e->opts.max_new_tokens);
   e->run_prefill();
   HIPCHK(hipStreamSynchronize(e->stream));
@@ -2360,7 +2372,7 @@ int32_t q3a_decode_step(q3a_engine* e, int32_t* next_ids, uint8_t* done, float* 
   if (!e) return 1;
   Q3A_TRY(e)
   e->require_asr("q3a_decode_step");
-  if (e->beam_w_ > 0) fail("q3a_decode_step: a beam search owns the decode state (q3a_beam_step; a new q3a_prefill returns to the greedy step)");
+  if (e->beam_w() > 0) fail("q3a_decode_step: a beam search owns the decode state (q3a_beam_step; a new q3a_prefill returns to the greedy step)");
   HIPCHK(hipSetDevice(e->device));
   {
     // capacity guard: position of the token being fed must stay inside the cache
@@ -2369,7 +2381,7 @@ int32_t q3a_decode_step(q3a_engine* e, int32_t* next_ids, uint8_t* done, float* 
     for (int s = 0; s < e->B; ++s)
       if (pos[s] + 1 > e->max_ctx) fail("q3a_decode_step: KV cache capacity exhausted (max_new_tokens reached)");
   }
-  e->head_logits_ = true;
+  e->begin_step_call();
   e->decode_steps(1);
   HIPCHK(hipStreamSynchronize(e->stream));
   HIPCHK(hipGetLastError());
@@ -2383,7 +2395,7 @@ int32_t q3a_set_next_tokens(q3a_engine* e, const int32_t* ids, int32_t B) {
   if (!e) return 1;
   Q3A_TRY(e)
   HIPCHK(hipSetDevice(e->device));
-  if (!e->have_prefill || B != e->B || e->beam_w_ > 0) fail("q3a_set_next_tokens: no decode state / batch mismatch");
+  if (!e->at(Stage::Decoding) || B != e->B || e->beam_w() > 0) fail("q3a_set_next_tokens: no decode state / batch mismatch");
   for (int s = 0; s < B; ++s)
     if (ids[s] < 0 || ids[s] >= e->d.vocab) fail("q3a_set_next_tokens: token id out of range");
   e->step.enqueue_forced_tokens(ids);
@@ -2397,10 +2409,9 @@ int32_t q3a_run_resident(q3a_engine* e, const int32_t* lang_prefix_ids, int32_t 
   Q3A_TRY(e)
   e->require_asr("q3a_run_resident");
   HIPCHK(hipSetDevice(e->device));
-  e->fixed_mode_ = fixed_new_tokens > 0;
-  e->head_logits_ = e->opts.debug_taps != 0;
-  e->have_mel = e->have_enc = e->have_prefill = false;
-  if (e->B <= 0) fail("q3a_run_resident: no batch uploaded");
+  e->begin_call(fixed_new_tokens > 0, e->opts.debug_taps != 0);
+  e->rewind(Stage::Batch);  // mel and encoder run again, on the PCM that is resident
+  e->require(Stage::Batch, "q3a_run_resident: no batch uploaded");
   // prompts and every table / buffer of the prefill + decode: host integers only (T[] of set_batch), before the batch's first kernel
   const auto pr = e->asr_prompts(lang_prefix_ids, n_prefix);
   e->setup_prompts(pr.first.data(), pr.second.data(), e->B, e->max_new_request(max_new, fixed_new_tokens), true);
@@ -2432,8 +2443,7 @@ int32_t q3a_transcribe_batch_ptrs(q3a_engine* e, const float* const* pcm16k, con
   Q3A_TRY(e)
   e->require_asr("q3a_transcribe_batch");
   const auto w0 = std::chrono::steady_clock::now();
-  e->fixed_mode_ = fixed_new_tokens > 0;
-  e->head_logits_ = e->opts.debug_taps != 0;
+  e->begin_call(fixed_new_tokens > 0, e->opts.debug_taps != 0);
   e->whole_path_front("q3a_transcribe_batch", pcm16k, n_samples, B, 1, e->max_new_request(max_new, fixed_new_tokens),
                       [&] { return e->asr_prompts(lang_prefix_ids, n_prefix); });
   e->run_resident(fixed_new_tokens, true);
@@ -2468,12 +2478,9 @@ int32_t q3a_prefill_draft(q3a_engine* e, const int32_t* prompt_ids, const int32_
   e->draft_check(what);
   if (!prompt_ids || !prompt_lens || !draft_lens || B < 1) fail(std::string(what) + ": bad argument");
   HIPCHK(hipSetDevice(e->device));
-  if (!e->have_enc) fail(std::string(what) + ": no encoder output (call q3a_encode first)");
-  if (B != e->B) fail(std::string(what) + ": batch size differs from the encoded batch");
-  const auto dp = e->draft_plan(what, prompt_ids, prompt_lens, draft_ids, draft_lens, B, e->opts.max_new_tokens);
-  e->fixed_mode_ = false;
-  e->head_logits_ = true;
-  e->have_prefill = false;
+  e->require_encoded(what, B);
+  const auto dp = e->given_plan(what, q3a_engine::kDrafted, prompt_ids, prompt_lens, draft_ids, draft_lens, B, e->opts.max_new_tokens);
+  e->begin_call(false, true);
   e->setup_prompts(dp.ids.data(), dp.lens.data(), B, e->opts.max_new_tokens);
   e->timings = q3a_timings{};
   e->draft_stats_.assign(1, 0);
@@ -2496,14 +2503,13 @@ int32_t q3a_transcribe_draft_batch_ptrs(q3a_engine* e, const float* const* pcm16
   e->draft_check(what);
   if (!draft_lens || !out_lens || stride < 0 || (stride > 0 && !out_ids) || n_prefix < 0 || B < 1) fail(std::string(what) + ": bad argument");
   const auto w0 = std::chrono::steady_clock::now();
-  e->fixed_mode_ = false;
-  e->head_logits_ = e->opts.debug_taps != 0;
+  e->begin_call(false, e->opts.debug_taps != 0);
   const int mn = e->max_new_request(max_new, 0), mn_eff = std::min(std::max(mn, 1), e->opts.max_new_tokens);
   std::pair<std::vector<int32_t>, std::vector<int32_t>> pr;  // the prompts without a draft: the same in every round
-  q3a_engine::DraftPlan dp;
+  q3a_engine::GivenPlan dp;
   e->whole_path_front(what, pcm16k, n_samples, B, 1, mn, [&] {
     pr = e->asr_prompts(lang_prefix_ids, n_prefix);
-    dp = e->draft_plan(what, pr.first.data(), pr.second.data(), draft_ids, draft_lens, B, mn_eff);
+    dp = e->given_plan(what, q3a_engine::kDrafted, pr.first.data(), pr.second.data(), draft_ids, draft_lens, B, mn_eff);
     return std::tie(dp.ids, dp.lens);
   });
   e->draft_stats_.assign(1, 0);
@@ -2534,7 +2540,7 @@ int32_t q3a_transcribe_draft_batch_ptrs(q3a_engine* e, const float* const* pcm16
       nxt.resize(o + cur_lens[s]);
     }
     cur.swap(nxt);
-    dp = e->draft_plan(what, pr.first.data(), pr.second.data(), cur.data(), cur_lens.data(), B, mn_eff);
+    dp = e->given_plan(what, q3a_engine::kDrafted, pr.first.data(), pr.second.data(), cur.data(), cur_lens.data(), B, mn_eff);
     e->setup_prompts(dp.ids.data(), dp.lens.data(), B, mn);
   }
   HIPCHK(hipEventRecord(e->ev[3], e->stream));
@@ -2569,7 +2575,7 @@ int32_t q3a_profile_decode_step(q3a_engine* e, q3a_kernel_profile* out) {
   if (!e || !out) return 1;
   Q3A_TRY(e)
   HIPCHK(hipSetDevice(e->device));
-  if (!e->have_prefill) fail("q3a_profile_decode_step: no decode state");
+  e->require(Stage::Decoding, "q3a_profile_decode_step: no decode state");
   std::vector<ProfEvent> evs;
   e->prof = &evs;
   try {
@@ -2597,7 +2603,7 @@ int32_t q3a_profile_weight_stream(q3a_engine* e, int32_t reps, float* avg_us, do
   if (!e) return 1;
   Q3A_TRY(e)
   HIPCHK(hipSetDevice(e->device));
-  if (!e->have_prefill) fail("q3a_profile_weight_stream: no decode state");
+  e->require(Stage::Decoding, "q3a_profile_weight_stream: no decode state");
   if (e->B > kGemvMaxSeq) fail("q3a_profile_weight_stream: the GEMV path serves at most 2 sequences");
   if (reps < 1) reps = 1;
   const Dims& d = e->d;

@@ -520,6 +520,35 @@ def test_step_commit_and_score_head_are_stated_once():
     assert "step.enqueue_forced_tokens(ids)" in _cpp_function_body(abi, "int32_t q3a_set_next_tokens(")
 
 
+def test_call_state_has_one_writer_and_one_drop():
+    """What a call requires and leaves behind -- the stage, the width of a live beam search, the per-call mode pair -- is written by
+    the functions of CallState alone: the words are private to it, the extern "C" layer and the engine assign none of them, and
+    "no decode state until the next prefill" has ONE body, which every call that drops decode state goes through."""
+    src = open(os.path.join(ROOT, "qwen3_asr_rs_amd", "csrc", "engine.cpp")).read()
+    state = _cpp_function_body(src, "class CallState ")
+    words = r"\b(stage_|beam_w_|fixed_mode_|head_logits_)\s*(=[^=]|\+\+|--|[-+|&]=)"
+    assert state.index("stage_ = Stage::None") < state.index(" public:")  # (a class: private until then)
+    for w in ("stage_", "beam_w_", "fixed_mode_", "head_logits_"):
+        assert re.search(r"\b%s = " % w, state[:state.index(" public:")]), w
+    abi = src[src.index('extern "C" {'):]
+    assert not re.search(words, abi) and not re.search(words, src.replace(state, ""))
+    assert "have_prefill" not in src and "have_enc" not in src and "have_mel" not in src
+    assert re.search(r"^struct q3a_engine : CallState \{", src, flags=re.M)
+    # one body; the setters, the beam whole-path call and the prefill layers (scoring, alignment, draft verification) call it
+    assert len(re.findall(r"void drop_decode_state\(\)", src)) == 1 and "void drop_decode_state() { rewind(Stage::Encoded); }" in state
+    assert "end_search();" in _cpp_function_body(state, "void rewind(Stage s)")
+    engine = _cpp_function_body(src, "struct q3a_engine ")
+    for user in ("void set_logit_bias(", "void set_repetition(float penalty, int ngram)", "void set_sampling(", "void run_prefill_layers()"):
+        assert "drop_decode_state();" in _cpp_function_body(engine, user), user
+    assert "e->drop_decode_state();" in _cpp_function_body(abi, "int32_t q3a_beam_search_batch_ptrs(")
+    for user in ("void run_align(", "void run_score(", "void run_prefill_draft("):
+        assert "run_prefill_then_head(" in _cpp_function_body(engine, user), user
+    assert "run_prefill_layers();" in _cpp_function_body(engine, "void run_prefill_then_head(")
+    # the repeated pair of checks is one function, and one plan builder serves scoring and the draft
+    assert src.count("no encoder output (call q3a_encode first)") == 1 and src.count("batch size differs from the encoded batch") == 1
+    assert len(re.findall(r"\bGivenPlan given_plan\(", src)) == 1 and src.count("given_plan(") == 6
+
+
 def test_mfma_table_shapes_and_launch_matching():
     """tools/mfma_table.py (the counter-vs-wall-clock MFMA table of DESIGN.md section 6): its shape list reproduces the tile counts
     the committed profiles show for 32 clips (conv2 6000, conv3 1560, enc qkv 506 after the round split, fc1 686, 196-tile residual
