@@ -265,10 +265,18 @@ __device__ __forceinline__ void gemv_epilogue(const GemvArgs& a, int g, const in
 // 2 KI (4 KI with the norm weight) -- and handed to the four waves through LDS: every wave needs the whole vector, and in the
 // register form each of them pulls it through the CU's texture-address path again (two thirds of a qkv workgroup's load
 // instructions were x and norm-weight re-reads).  Same values, same arithmetic.
+// XH (the plain forms at K > 2048, KI = 6 / 12: the down projection): the same hand-over of x, chosen from the other flags.  One
+// row per wave at K = 3072 is 6 weight loads next to 12 loads of x per wave; with the hand-over 3.  The three x requests go IN FRONT
+// of the weights: x is back after one L2 round trip and the store / barrier / read-back run while the weights are in flight (stamped
+// timeline, profiles/gemv_down_handover_phase_probe.txt: issue 0.85 -> 0.19 us, span 2.02 -> 1.93 us).  Behind the weights the
+// hand-over starts when the last weight chunk has landed and stands exposed in front of the FMAs (span 2.21 us: it lost).
 template <int PR, int KI, bool RMS, bool ATTN, int MF, bool XL>
 __device__ __forceinline__ void gemv1_body(const GemvArgs& a) {
   static_assert(!XL || !ATTN, "the merged attention vector already goes through LDS");
-  __shared__ __attribute__((aligned(16))) float xl_x[XL ? KI * 512 : 4], xl_w[(XL && RMS) ? KI * 512 : 4];
+  constexpr bool XH = !RMS && !ATTN && KI > 4;
+  constexpr bool XLDS = XL || XH;  // x goes through LDS (xl_x; the norm weight, xl_w, only in the XL forms)
+  static_assert(!XH || KI % 2 == 0, "the hand-over stores unguarded: its rounds of 1024 columns must end at KI * 512");
+  __shared__ __attribute__((aligned(16))) float xl_x[XLDS ? KI * 512 : 4], xl_w[(XL && RMS) ? KI * 512 : 4];
   __shared__ __attribute__((aligned(16))) float x_s[ATTN ? KI * 512 : 4];  // only the attention merge goes through LDS
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   Q3A_STAMP_ENTRY(t_entry);
@@ -287,11 +295,11 @@ __device__ __forceinline__ void gemv1_body(const GemvArgs& a) {
   }
   float4 xr[KI][2], nr[RMS ? KI : 1][2];
   uint4 wq[KI][PR];
-  constexpr int XLN = (KI + 1) / 2;  // 16-byte pieces of x per lane in the XL form (256 lanes x 4 floats = 1024 columns per round)
-  float4 xl_rx[XL ? XLN : 1], xl_rw[(XL && RMS) ? XLN : 1];
+  constexpr int XLN = (KI + 1) / 2;  // 16-byte pieces of x per lane in the XL / XH forms (256 lanes x 4 floats = 1024 columns per round)
+  float4 xl_rx[XLDS ? XLN : 1], xl_rw[(XL && RMS) ? XLN : 1];
   auto request_x = [&]() {  // L2 hits
     if (ATTN) return;
-    if constexpr (XL) {
+    if constexpr (XLDS) {
 #pragma unroll
       for (int j = 0; j < XLN; ++j) {
         const int k = (tid + j * 256) * 4, kc = k < K ? k : 0;
@@ -320,7 +328,9 @@ __device__ __forceinline__ void gemv1_body(const GemvArgs& a) {
       }
   };
   // Loads return in order.  With a fused norm, x and the norm weight go first: they are back, squared and scaled long
-  // before the first weight chunk lands (-0.2 us).  Without one the weights go first (x-first measured +0.2..0.4 us).
+  // before the first weight chunk lands (-0.2 us).  So does an x that is handed over through LDS (XL, XH: few requests, and the
+  // hand-over must not wait for the stream).  A plain x in registers goes behind the weights (2 KI requests in front of them measured
+  // +0.2..0.4 us).
   constexpr int MCH = MF > 0 ? MF : 1;
   float mg_m[MCH], mg_l[MCH];
   float4 mg_o0[MCH], mg_o1[MCH];
@@ -351,7 +361,7 @@ __device__ __forceinline__ void gemv1_body(const GemvArgs& a) {
     }
     __builtin_amdgcn_sched_barrier(0);  // the partials' requests stay in front of the weight stream
   }
-  if (RMS || XL) { request_x(); request_w(); } else { request_w(); request_x(); }
+  if (RMS || XLDS) { request_x(); request_w(); } else { request_w(); request_x(); }
   // MF forms: the bias below is addressed through the tail, whose scalar loads hipcc issues behind the fence above; without this
   // one it also puts their wait in front of the weight requests
   if constexpr (ATTN && MF > 0) __builtin_amdgcn_sched_barrier(0);
@@ -425,12 +435,14 @@ __device__ __forceinline__ void gemv1_body(const GemvArgs& a) {
       xr[it][1] = *reinterpret_cast<const float4*>(x_s + kk[it] + 4);
     }
   }
-  if constexpr (XL) {  // hand the vector to the four waves (the weights are still in flight)
+  if constexpr (XLDS) {  // hand the vector to the four waves (the weights are still in flight)
 #pragma unroll
     for (int j = 0; j < XLN; ++j) {
       const int k = (tid + j * 256) * 4;
-      if (k < KI * 512) {
-        *reinterpret_cast<float4*>(xl_x + k) = xl_rx[j];
+      if (XH || k < KI * 512) {  // (XH: KI is even, the XLN rounds cover exactly KI * 512 columns)
+        // element by element: as one aggregate copy (a memcpy from the private array to LDS) hipcc kept xl_rx[XLN > 1] in scratch
+        const float4 v = xl_rx[j];
+        *reinterpret_cast<float4*>(xl_x + k) = make_float4(v.x, v.y, v.z, v.w);
         if (RMS) *reinterpret_cast<float4*>(xl_w + k) = xl_rw[j];
       }
     }
@@ -1030,8 +1042,13 @@ void launch1k(const GemvArgs& a, hipStream_t s) {
   } else if (a.rms_w) {
     // Norm-fused projections at K <= 1024 (qkv, gate / up at hidden 1024): x and the norm weight once per workgroup through LDS
     // (round 6: 609.7 -> 595.1 us per step at 0.6B, ids identical; profiles/r6_ab_gemv_x_lds.txt).  Not where it was measured to
-    // lose: K = 2048 (+18 %: 32 KiB of LDS per workgroup halves the residency of the 1536-workgroup gate / up launch), the down
-    // projection (+4 %: x in front of the weights delays them), the lm_head (+1.3 %: a barrier in each of 9496 workgroups).
+    // lose: K = 2048 (+18 %: 32 KiB of LDS per workgroup halves the residency of the 1536-workgroup gate / up launch), the lm_head
+    // (+1.3 %: a barrier in each of 9496 workgroups).
+    // The down projection (the plain form below, K > 2048) lost 4 % in that round's trial, which was put down to x standing in front
+    // of the weights without a look at its assembly.  The hand-over as it then stood, instantiated with more than one 16-byte piece
+    // per lane, compiles with the pieces in scratch (the aggregate copy into LDS; it now copies element by element), which that trial
+    // may have measured.  Rebuilt without scratch, both request orders were stamped: x in front of the weights wins, x behind them
+    // loses (gemv1_body XH; profiles/gemv_down_handover_phase_probe.txt, gemv_down_handover_headline_ab.txt).
     if (a.mode == 3) {
       if (a.part.sum) hipLaunchKernelGGL((gemv1_head_kernel<PR, KI, true>), grid, block, 0, s, GEMV_HEAD_ARGS(a));
       else hipLaunchKernelGGL((gemv1_head_kernel<PR, KI>), grid, block, 0, s, GEMV_HEAD_ARGS(a));
