@@ -27,12 +27,10 @@ namespace q3a {
 
 int gemv_rows_per_wave(const GemvArgs& a) {  // physical weight rows per wave
   const int logical = (a.mode == 2) ? a.N / 2 : a.N;
-  // tuning knobs for A/B runs (rows per wave for mid-size and small matrices); defaults are the measured best
-  static const int mid = [] { const char* e = getenv("Q3A_GEMV_PR_MID"); return e ? atoi(e) : 2; }();
-  static const int small = [] { const char* e = getenv("Q3A_GEMV_PR_SMALL"); return e ? atoi(e) : 1; }();
+  // (2 for mid-size and 1 for small matrices are the measured best: profiles/r6_gemv_rows_per_wave.txt)
   if (logical >= 32768 && a.K <= 2048) return 4;
-  if (logical >= 4096 || a.mode == 2) return (mid == 4 || mid == 2) ? mid : 2;
-  return (small == 1 || small == 2 || small == 4) ? small : 1;
+  if (logical >= 4096 || a.mode == 2) return 2;
+  return 1;
 }
 int gemv_blocks(const GemvArgs& a) {
   const int pr = gemv_rows_per_wave(a);
@@ -100,6 +98,13 @@ __device__ __forceinline__ void attn_combined8(const GemvArgs& a, int b, int k, 
 // Single-sequence form of the merge: no table, no barrier.  The 16 lanes that share a head read that head's (m, l)
 // statistics themselves (same-address loads, one request) together with the partial outputs -- every load is
 // independent, one L2 round trip -- and rescale online over chunks of 4 splits.
+// attn_partial_row8: the request of one split's partial row (8 elements at d of head row base + sp; a split past ns is clamped to the
+// last one and voided through its statistics), for this merge and for the MF forms of gemv1_body.
+__device__ __forceinline__ void attn_partial_row8(const GemvArgs& a, int base, int sp, int d, float4& o0, float4& o1) {
+  const int spc = sp < a.attn_nsplit ? sp : a.attn_nsplit - 1;
+  o0 = *reinterpret_cast<const float4*>(a.attn_po + (size_t)(base + spc) * 128 + d);
+  o1 = *reinterpret_cast<const float4*>(a.attn_po + (size_t)(base + spc) * 128 + d + 4);
+}
 // FAST: hardware exponential (default mode); the precise mode keeps expf.
 template <bool FAST, int CH>
 __device__ __forceinline__ void attn_merge8_ch(const GemvArgs& a, int b, int k, float (&x)[8]) {
@@ -122,15 +127,12 @@ __device__ __forceinline__ void attn_merge8_ch(const GemvArgs& a, int b, int k, 
       m[j] = a.attn_pm[base + spc];
       l[j] = a.attn_pl[base + spc];
       if (sp >= ns) m[j] = -INFINITY;
-      o0[j] = *reinterpret_cast<const float4*>(a.attn_po + (size_t)(base + spc) * 128 + d);
-      o1[j] = *reinterpret_cast<const float4*>(a.attn_po + (size_t)(base + spc) * 128 + d + 4);
+      attn_partial_row8(a, base, sp, d, o0[j], o1[j]);
     }
     // every request above stays above: without the fence hipcc sinks the l / o loads below the `continue` that only needs m --
     // m first, a wait, then the rest: two dependent round trips where the source has one (ISA: global_load x5, s_waitcnt
     // vmcnt(0), branch, global_load x21)
-#ifndef Q3A_NO_MERGE_FENCE  // A/B builds only
     asm volatile("" ::: "memory");
-#endif
     float Mn = M;
 #pragma unroll
     for (int j = 0; j < CH; ++j) Mn = fmaxf(Mn, m[j]);
@@ -178,8 +180,79 @@ __device__ __forceinline__ float dot8(const uint4& w, const float (&x)[8], float
   return s + (a.x + a.y);
 }
 
-// epilogue shared by both variants; acc holds the finished (rstd-scaled) dot products, valid on every lane.
-// LP (mode 3, token log-probabilities): also the log-sum channel (argmax.h); am_s as am_v.
+// ---- pieces shared by the lm_head kernels (gemv1_head_block, both passes of the pruned argmax) and gemvn_kernel ----------------
+// gemv1_body keeps the same steps written out: behind these functions hipcc allocated more registers in its shipped forms (the
+// qkv / gate-up form lost a wave per SIMD behind unpack_cols, the down projection behind a shared dot loop) and rescheduled the loads
+// of the chunked merge (profiles/gemv_family_code_objects.txt).
+// One piece of the weight stream: 16 bytes (8 columns at k) of physical row prow; a row past N (prow < 0) is clamped to the last
+// one and voided by the epilogue.  Unconditional: no exec-masked blocks, no waits between requests.
+__device__ __forceinline__ uint4 ld_w16(const GemvArgs& a, int prow, int k) {
+  const int row = prow >= 0 ? prow : a.N - 1;
+  return ld_stream16(a.W + (size_t)row * a.K + k);
+}
+// The HBM stream of a wave: all KI * PR pieces of its rows in flight at once
+template <int KI, int PR>
+__device__ __forceinline__ void request_rows(const GemvArgs& a, const int (&prow)[PR], const int (&kk)[KI], uint4 (&wq)[KI][PR]) {
+#pragma unroll
+  for (int it = 0; it < KI; ++it)
+#pragma unroll
+    for (int i = 0; i < PR; ++i) wq[it][i] = ld_w16(a, prow[i], kk[it]);
+}
+// The lane's column plan (one sequence): k-iteration `it` covers columns lane * 8 + it * 512 .. + 7.  kin: the piece lies inside K;
+// kk: its address, clamped to 0 where it does not (the unpack voids what was loaded there).
+template <int KI>
+__device__ __forceinline__ void lane_cols(int lane, int K, bool (&kin)[KI], int (&kk)[KI]) {
+#pragma unroll
+  for (int it = 0; it < KI; ++it) {
+    const int k = lane * 8 + it * 512;
+    kin[it] = k < K;
+    kk[it] = kin[it] ? k : 0;
+  }
+}
+// x and the norm weight of the lane's columns, two float4 each per k-iteration, requested in the order x, x, w, w
+template <int KI>
+__device__ __forceinline__ void fetch_cols(const GemvArgs& a, const int (&kk)[KI], float4 (&xr)[KI][2], float4 (&nr)[KI][2]) {
+#pragma unroll
+  for (int it = 0; it < KI; ++it) {
+    xr[it][0] = *reinterpret_cast<const float4*>(a.x + kk[it]);
+    xr[it][1] = *reinterpret_cast<const float4*>(a.x + kk[it] + 4);
+    nr[it][0] = *reinterpret_cast<const float4*>(a.rms_w + kk[it]);
+    nr[it][1] = *reinterpret_cast<const float4*>(a.rms_w + kk[it] + 4);
+  }
+}
+// What was fetched, as the operand of the dot products: columns beyond K contribute nothing, ss += x^2 (the RMSNorm's sum, of the
+// raw x), x becomes ŷ = x * w_norm; YY (pass 1 of the pruned argmax): *yy += ŷ^2.  The bound of the pruned argmax needs both passes
+// to form the same ŷ: they form it here.
+template <int KI, bool YY = false>
+__device__ __forceinline__ void unpack_cols(int K, const bool (&kin)[KI], const float4 (&xr)[KI][2], const float4 (&nr)[KI][2],
+                                            float (&x)[KI][8], float& ss, float* yy = nullptr) {
+#pragma unroll
+  for (int it = 0; it < KI; ++it) {
+    const float4 v0 = xr[it][0], v1 = xr[it][1];
+    const float xv[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) x[it][e] = (K == KI * 512 || kin[it]) ? xv[e] : 0.f;
+    const float4 w0 = nr[it][0], w1 = nr[it][1];
+    const float wv[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { ss += x[it][e] * x[it][e]; x[it][e] *= wv[e]; }
+    if constexpr (YY) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) *yy += x[it][e] * x[it][e];
+    }
+  }
+}
+// The four waves' argmax partials of sequence b (lane 0 of each wave wrote them; the caller's barrier lies in between), merged in
+// wave order.  LP: with the log-sum channel am_s.
+template <bool LP, int NB>
+__device__ __forceinline__ ArgmaxAcc<LP> merge_wave_partials(float (*am_v)[NB], int (*am_i)[NB], float (*am_s)[NB], int b) {
+  ArgmaxAcc<LP> r{am_v[0][b], am_i[0][b], LP ? am_s[0][b] : 0.f};
+  for (int w = 1; w < 4; ++w) r.merge(am_v[w][b], am_i[w][b], LP ? am_s[w][b] : 0.f);
+  return r;
+}
+
+// epilogue of gemvn_kernel (the one-sequence kernels finish in gemv1_body / gemv1_head_block); acc holds the finished (rstd-scaled)
+// dot products, valid on every lane.  LP (mode 3, token log-probabilities): also the log-sum channel (argmax.h); am_s as am_v.
 template <int NB, int PR, bool LP>
 __device__ __forceinline__ void gemv_epilogue(const GemvArgs& a, int g, const int (&prow)[PR], float (&acc)[PR][NB],
                                               float (*am_v)[NB], int (*am_i)[NB], float (*am_s)[NB]) {
@@ -216,11 +289,7 @@ __device__ __forceinline__ void gemv_epilogue(const GemvArgs& a, int g, const in
       }
     }
     __syncthreads();
-    if (tid < NB) {
-      ArgmaxAcc<LP> r{am_v[0][tid], am_i[0][tid], LP ? am_s[0][tid] : 0.f};
-      for (int w = 1; w < 4; ++w) r.merge(am_v[w][tid], am_i[w][tid], LP ? am_s[w][tid] : 0.f);
-      r.store(a.part, tid, g >> 2);
-    }
+    if (tid < NB) merge_wave_partials<LP, NB>(am_v, am_i, am_s, tid).store(a.part, tid, g >> 2);
     return;
   }
   if (lane != 0) return;
@@ -274,10 +343,10 @@ template <int PR, int KI, bool RMS, bool ATTN, int MF, bool XL>
 __device__ __forceinline__ void gemv1_body(const GemvArgs& a) {
   static_assert(!XL || !ATTN, "the merged attention vector already goes through LDS");
   constexpr bool XH = !RMS && !ATTN && KI > 4;
-  constexpr bool XLDS = XL || XH;  // x goes through LDS (xl_x; the norm weight, xl_w, only in the XL forms)
+  constexpr bool XLDS = XL || XH;  // x is handed over through LDS (the norm weight, xl_w, only in the XL forms)
   static_assert(!XH || KI % 2 == 0, "the hand-over stores unguarded: its rounds of 1024 columns must end at KI * 512");
-  __shared__ __attribute__((aligned(16))) float xl_x[XLDS ? KI * 512 : 4], xl_w[(XL && RMS) ? KI * 512 : 4];
-  __shared__ __attribute__((aligned(16))) float x_s[ATTN ? KI * 512 : 4];  // only the attention merge goes through LDS
+  // x through LDS: the merged attention vector (ATTN) or the hand-over (XL / XH), never both
+  __shared__ __attribute__((aligned(16))) float x_lds[(ATTN || XLDS) ? KI * 512 : 4], xl_w[(XL && RMS) ? KI * 512 : 4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   Q3A_STAMP_ENTRY(t_entry);
   const int K = a.K;
@@ -354,11 +423,7 @@ __device__ __forceinline__ void gemv1_body(const GemvArgs& a) {
       }
     }
 #pragma unroll
-    for (int j = 0; j < MCH; ++j) {
-      const int spc = j < ns ? j : ns - 1;
-      mg_o0[j] = *reinterpret_cast<const float4*>(a.attn_po + (size_t)(base + spc) * 128 + d);
-      mg_o1[j] = *reinterpret_cast<const float4*>(a.attn_po + (size_t)(base + spc) * 128 + d + 4);
-    }
+    for (int j = 0; j < MCH; ++j) attn_partial_row8(a, base, j, d, mg_o0[j], mg_o1[j]);
     __builtin_amdgcn_sched_barrier(0);  // the partials' requests stay in front of the weight stream
   }
   if (RMS || XLDS) { request_x(); request_w(); } else { request_w(); request_x(); }
@@ -398,16 +463,11 @@ __device__ __forceinline__ void gemv1_body(const GemvArgs& a) {
       const float inv = 1.0f / L;
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] *= inv;
-      *reinterpret_cast<float4*>(x_s + mg_k) = make_float4(v[0], v[1], v[2], v[3]);
-      *reinterpret_cast<float4*>(x_s + mg_k + 4) = make_float4(v[4], v[5], v[6], v[7]);
+      *reinterpret_cast<float4*>(x_lds + mg_k) = make_float4(v[0], v[1], v[2], v[3]);
+      *reinterpret_cast<float4*>(x_lds + mg_k + 4) = make_float4(v[4], v[5], v[6], v[7]);
     }
     __syncthreads();
-#pragma unroll
-    for (int it = 0; it < KI; ++it) {
-      xr[it][0] = *reinterpret_cast<const float4*>(x_s + kk[it]);
-      xr[it][1] = *reinterpret_cast<const float4*>(x_s + kk[it] + 4);
-    }
-  } else if (ATTN) {  // each wave merges a quarter of the vector, once per block
+  } else if constexpr (ATTN) {  // each wave merges a quarter of the vector, once per block
     // The two kernel-argument choices (exponential, chunk size) are made OUTSIDE the loop over the wave's pieces: with both inside,
     // every iteration carried four copies of the merge and the K = 6144 form no longer unrolled (kin / kk went to scratch).
     auto merge_pieces = [&](auto fast_c, auto ch_c) {
@@ -416,8 +476,8 @@ __device__ __forceinline__ void gemv1_body(const GemvArgs& a) {
         if ((it & 3) == wave && kin[it]) {
           float v[8];
           attn_merge8_ch<decltype(fast_c)::value, decltype(ch_c)::value>(a, 0, kk[it], v);
-          *reinterpret_cast<float4*>(x_s + kk[it]) = make_float4(v[0], v[1], v[2], v[3]);
-          *reinterpret_cast<float4*>(x_s + kk[it] + 4) = make_float4(v[4], v[5], v[6], v[7]);
+          *reinterpret_cast<float4*>(x_lds + kk[it]) = make_float4(v[0], v[1], v[2], v[3]);
+          *reinterpret_cast<float4*>(x_lds + kk[it] + 4) = make_float4(v[4], v[5], v[6], v[7]);
         }
       }
     };
@@ -429,11 +489,6 @@ __device__ __forceinline__ void gemv1_body(const GemvArgs& a) {
       if (a.attn_nsplit <= 4) merge_pieces(std::false_type{}, Ch4{}); else merge_pieces(std::false_type{}, Ch8{});
     }
     __syncthreads();
-#pragma unroll
-    for (int it = 0; it < KI; ++it) {
-      xr[it][0] = *reinterpret_cast<const float4*>(x_s + kk[it]);
-      xr[it][1] = *reinterpret_cast<const float4*>(x_s + kk[it] + 4);
-    }
   }
   if constexpr (XLDS) {  // hand the vector to the four waves (the weights are still in flight)
 #pragma unroll
@@ -442,24 +497,27 @@ __device__ __forceinline__ void gemv1_body(const GemvArgs& a) {
       if (XH || k < KI * 512) {  // (XH: KI is even, the XLN rounds cover exactly KI * 512 columns)
         // element by element: as one aggregate copy (a memcpy from the private array to LDS) hipcc kept xl_rx[XLN > 1] in scratch
         const float4 v = xl_rx[j];
-        *reinterpret_cast<float4*>(xl_x + k) = make_float4(v.x, v.y, v.z, v.w);
+        *reinterpret_cast<float4*>(x_lds + k) = make_float4(v.x, v.y, v.z, v.w);
         if (RMS) *reinterpret_cast<float4*>(xl_w + k) = xl_rw[j];
       }
     }
     __syncthreads();
+  }
+  // every wave reads the whole vector back (the norm weight with it in the XL forms), behind the barrier of whichever path filled x_lds
+  if constexpr (ATTN || XLDS) {
 #pragma unroll
     for (int it = 0; it < KI; ++it) {
-      xr[it][0] = *reinterpret_cast<const float4*>(xl_x + kk[it]);
-      xr[it][1] = *reinterpret_cast<const float4*>(xl_x + kk[it] + 4);
-      if (RMS) {
+      xr[it][0] = *reinterpret_cast<const float4*>(x_lds + kk[it]);
+      xr[it][1] = *reinterpret_cast<const float4*>(x_lds + kk[it] + 4);
+      if (XL && RMS) {
         nr[it][0] = *reinterpret_cast<const float4*>(xl_w + kk[it]);
         nr[it][1] = *reinterpret_cast<const float4*>(xl_w + kk[it] + 4);
       }
     }
   }
   Q3A_STAMP_AT(a.stamp, blockIdx.x, 2);  // (ATTN: merged vector in LDS)
-  float x[KI][8];
-  float ss = 0.f;  // (packing sum(x^2) and x * w_norm two wide measured 0.6 % slower on the whole step)
+  float x[KI][8], acc[PR];
+  float ss = 0.f;
 #pragma unroll
   for (int it = 0; it < KI; ++it) {
     const float4 v0 = xr[it][0], v1 = xr[it][1];
@@ -473,29 +531,28 @@ __device__ __forceinline__ void gemv1_body(const GemvArgs& a) {
       for (int e = 0; e < 8; ++e) { ss += x[it][e] * x[it][e]; x[it][e] *= wv[e]; }
     }
   }
-  float acc[PR][1];
 #pragma unroll
-  for (int i = 0; i < PR; ++i) acc[i][0] = 0.f;
+  for (int i = 0; i < PR; ++i) acc[i] = 0.f;
 #pragma unroll
   for (int it = 0; it < KI; ++it)
 #pragma unroll
-    for (int i = 0; i < PR; ++i) acc[i][0] = dot8(wq[it][i], x[it], acc[i][0]);
-  if (wave == 0) asm volatile("" ::"v"(acc[0][0]));  // (the stamp below sits behind the FMAs of wave 0, i.e. behind its weights)
+    for (int i = 0; i < PR; ++i) acc[i] = dot8(wq[it][i], x[it], acc[i]);
+  if (wave == 0) asm volatile("" ::"v"(acc[0]));  // (the stamp below sits behind the FMAs of wave 0, i.e. behind its weights)
   Q3A_STAMP_AT(a.stamp, blockIdx.x, 3);  // weights landed, dot products done
   float rstd = 1.0f;
   if (RMS) rstd = rstd_of(wave_sum_fast(ss) / (float)K + a.eps, a.fast_math != 0);  // a wave covers all of K
 #pragma unroll
-  for (int i = 0; i < PR; ++i) acc[i][0] = wave_sum_fast(acc[i][0]) * rstd + bv[i];
+  for (int i = 0; i < PR; ++i) acc[i] = wave_sum_fast(acc[i]) * rstd + bv[i];
   // epilogue (bias already added; acc is valid on every lane; mode 3 runs gemv1_head_kernel)
   if (lane != 0) return;
   if (a.mode != 2) {
 #pragma unroll
     for (int i = 0; i < PR; ++i)
-      if (prow[i] >= 0) a.out[prow[i]] = acc[i][0] + rv[i];
+      if (prow[i] >= 0) a.out[prow[i]] = acc[i] + rv[i];
   } else {
 #pragma unroll
     for (int i = 0; i + 1 < PR; i += 2)
-      if (prow[i] >= 0) a.out[g * (PR / 2) + (i >> 1)] = silu_sel(acc[i][0], a.fast_math != 0) * acc[i + 1][0];
+      if (prow[i] >= 0) a.out[g * (PR / 2) + (i >> 1)] = silu_sel(acc[i], a.fast_math != 0) * acc[i + 1];
   }
   Q3A_STAMP_AT(a.stamp, blockIdx.x, 4);  // reduced and stored
 }
@@ -550,62 +607,33 @@ __global__ __launch_bounds__(256) void gemv1_kernel(const float* attn_pm, const 
 // two cannot drift apart.  Ends with a barrier; the block's partial is valid in thread 0's `out`.  LP (token log-probabilities):
 // with the log-sum channel (am_s: 4 floats of LDS); the value / row arithmetic is the same either way.
 template <int PR, int KI, bool LP = false>
-__device__ __forceinline__ void gemv1_head_block(const GemvArgs& a, int blk, float (&am_v)[4][1], int (&am_i)[4][1], float* am_s,
+__device__ __forceinline__ void gemv1_head_block(const GemvArgs& a, int blk, float (&am_v)[4][1], int (&am_i)[4][1], float (*am_s)[1],
                                                  ArgmaxAcc<LP>& out) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int K = a.K;
   const int g = blk * 4 + wave;
   int prow[PR];
   gemv_rows<PR>(a, g, prow);
   bool kin[KI];
   int kk[KI];
-#pragma unroll
-  for (int it = 0; it < KI; ++it) {
-    const int k = lane * 8 + it * 512;
-    kin[it] = k < K;
-    kk[it] = kin[it] ? k : 0;
-  }
+  lane_cols<KI>(lane, a.K, kin, kk);
   float4 xr[KI][2], nr[KI][2];
   uint4 wq[KI][PR];
-#pragma unroll
-  for (int it = 0; it < KI; ++it) {  // x and the norm weight first (L2 hits), then the weight stream
-    xr[it][0] = *reinterpret_cast<const float4*>(a.x + kk[it]);
-    xr[it][1] = *reinterpret_cast<const float4*>(a.x + kk[it] + 4);
-    nr[it][0] = *reinterpret_cast<const float4*>(a.rms_w + kk[it]);
-    nr[it][1] = *reinterpret_cast<const float4*>(a.rms_w + kk[it] + 4);
-  }
-#pragma unroll
-  for (int it = 0; it < KI; ++it)
-#pragma unroll
-    for (int i = 0; i < PR; ++i) {
-      const int row = prow[i] >= 0 ? prow[i] : a.N - 1;
-      wq[it][i] = ld_stream16(a.W + (size_t)row * K + kk[it]);
-    }
+  fetch_cols<KI>(a, kk, xr, nr);  // x and the norm weight first (L2 hits), then the weight stream
+  request_rows<KI, PR>(a, prow, kk, wq);
   float bv[PR];
 #pragma unroll
   for (int i = 0; i < PR; ++i) bv[i] = a.bias ? a.bias[prow[i] >= 0 ? prow[i] : 0] : 0.f;
   __builtin_amdgcn_sched_barrier(0);  // every request is issued before anything is waited for
-  float x[KI][8];
+  float x[KI][8], acc[PR];
   float ss = 0.f;
-#pragma unroll
-  for (int it = 0; it < KI; ++it) {
-    const float4 v0 = xr[it][0], v1 = xr[it][1];
-    const float xv[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) x[it][e] = (K == KI * 512 || kin[it]) ? xv[e] : 0.f;
-    const float4 w0 = nr[it][0], w1 = nr[it][1];
-    const float wv[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { ss += x[it][e] * x[it][e]; x[it][e] *= wv[e]; }
-  }
-  float acc[PR];
+  unpack_cols<KI>(a.K, kin, xr, nr, x, ss);
 #pragma unroll
   for (int i = 0; i < PR; ++i) acc[i] = 0.f;
 #pragma unroll
   for (int it = 0; it < KI; ++it)
 #pragma unroll
     for (int i = 0; i < PR; ++i) acc[i] = dot8(wq[it][i], x[it], acc[i]);
-  const float rstd = rstd_of(wave_sum_fast(ss) / (float)K + a.eps, a.fast_math != 0);  // a wave covers all of K
+  const float rstd = rstd_of(wave_sum_fast(ss) / (float)a.K + a.eps, a.fast_math != 0);  // a wave covers all of K
 #pragma unroll
   for (int i = 0; i < PR; ++i) acc[i] = wave_sum_fast(acc[i]) * rstd + bv[i];
   ArgmaxAcc<LP> m;
@@ -620,13 +648,10 @@ __device__ __forceinline__ void gemv1_head_block(const GemvArgs& a, int blk, flo
     float ws = 0.f;
 #pragma unroll
     for (int i = 0; i < PR; ++i) ws += prow[i] < 0 ? 0.f : lse_term(1.f, acc[i], m.v);
-    if (lane == 0) am_s[wave] = ws;
+    if (lane == 0) am_s[wave][0] = ws;
   }
   __syncthreads();
-  if (tid == 0) {
-    out = {am_v[0][0], am_i[0][0], LP ? am_s[0] : 0.f};
-    for (int w = 1; w < 4; ++w) out.merge(am_v[w][0], am_i[w][0], LP ? am_s[w] : 0.f);
-  }
+  if (tid == 0) out = merge_wave_partials<LP, 1>(am_v, am_i, am_s, 0);
 }
 
 // (head / tail as gemv1_kernel: the tail is the partial descriptor, first needed by the block's final store)
@@ -635,7 +660,7 @@ __global__ __launch_bounds__(256) void gemv1_head_kernel(const uint16_t* W, cons
                                                          int N, int K, float eps, int fast_math, ArgmaxPartials part) {
   __shared__ float am_v[4][1];
   __shared__ int am_i[4][1];
-  __shared__ float am_s[LP ? 4 : 1];
+  __shared__ float am_s[LP ? 4 : 1][1];
   GemvArgs a{};
   a.W = W; a.x = x; a.rms_w = rms_w; a.bias = bias; a.out = out; a.N = N; a.K = K; a.eps = eps; a.fast_math = fast_math; a.mode = 3;
   ArgmaxAcc<LP> r;
@@ -651,7 +676,7 @@ __global__ __launch_bounds__(256) void gemv1_head_kernel(const uint16_t* W, cons
 // hi_b = max (a_r + e_r) is not below T and reduces them to one (value, row) partial per workgroup.  The ids are those of the
 // unpruned launch; the worst case (every block a candidate) is one extra full pass.
 //
-// The bound.  Let ŷ_k be the fp32 products x_k * w_k both passes form (the same lanes, the same instruction), G = sum ŷ_k W_rk and
+// The bound.  Let ŷ_k be the fp32 products x_k * w_k both passes form (unpack_cols: one function, the same lanes), G = sum ŷ_k W_rk and
 // P = sum ŷ_k Q_rk exactly, Ĝ and P̂ their fp32 evaluations, s = s_r.  Each term of either dot product passes through at most
 // K/64 + 1 roundings in its lane (the product -- none if fused -- and the chain of packed adds and FMAs over the lane's K/64
 // columns) and 6 in the 64-lane wave_sum_fast tree; whatever the order and the fusing, the classic bound (Higham, Accuracy and
@@ -683,13 +708,12 @@ __global__ __launch_bounds__(256) void gemv1_head_kernel(const uint16_t* W, cons
 // Without a bias the kernel that runs is the one without the code (template parameter BIAS of lm_head_approx_body: false in
 // lm_head_approx_kernel, the launch of an engine that never set a bias, true in lm_head_approx_bias_kernel); pass 2 keeps
 // gemv1_head_block's uniform null check on a.bias.
-struct LmHeadArgsDev {  // what both passes read; no kernel parameter: the kernels assemble it from their flat head and their tail
+struct LmHeadArgsDev {  // what pass 1 reads, device side only: its kernels assemble it from their flat head and their tail
   GemvArgs g;
   const int8_t* Wq; const float* qs; int qcols;
   float gamma;
   float* blk_lo; float* blk_hi; int n_blk;
   float* dbg;  // [N][2] (a_r, e_r), debug taps only
-  int* stats;  // [2] += candidate blocks, += 1 per step (pass 2; never read by the step)
 };
 
 __device__ __forceinline__ float dotq8(uint32_t lo, uint32_t hi, const float (&x)[8], float s) {
@@ -745,20 +769,9 @@ __device__ __forceinline__ void lm_head_approx_body(const LmHeadArgsDev& p) {
   if (blk >= p.n_blk) return;  // wave-uniform
   bool kin[KI];
   int kk[KI];
-#pragma unroll
-  for (int it = 0; it < KI; ++it) {
-    const int k = lane * 8 + it * 512;
-    kin[it] = k < K;
-    kk[it] = kin[it] ? k : 0;
-  }
+  lane_cols<KI>(lane, K, kin, kk);
   float4 xr[KI][2], nr[KI][2];
-#pragma unroll
-  for (int it = 0; it < KI; ++it) {
-    xr[it][0] = *reinterpret_cast<const float4*>(a.x + kk[it]);
-    xr[it][1] = *reinterpret_cast<const float4*>(a.x + kk[it] + 4);
-    nr[it][0] = *reinterpret_cast<const float4*>(a.rms_w + kk[it]);
-    nr[it][1] = *reinterpret_cast<const float4*>(a.rms_w + kk[it] + 4);
-  }
+  fetch_cols<KI>(a, kk, xr, nr);
   uint4 wq[R][NQ];
 #pragma unroll
   for (int i = 0; i < R; ++i) {
@@ -774,19 +787,7 @@ __device__ __forceinline__ void lm_head_approx_body(const LmHeadArgsDev& p) {
   __builtin_amdgcn_sched_barrier(0);  // every request is issued before anything is waited for
   float x[KI][8];
   float ss = 0.f, yy = 0.f;
-#pragma unroll
-  for (int it = 0; it < KI; ++it) {  // exactly gemv1_head_block's x, sum(x^2) and ŷ
-    const float4 v0 = xr[it][0], v1 = xr[it][1];
-    const float xv[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) x[it][e] = (K == KI * 512 || kin[it]) ? xv[e] : 0.f;
-    const float4 w0 = nr[it][0], w1 = nr[it][1];
-    const float wv[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { ss += x[it][e] * x[it][e]; x[it][e] *= wv[e]; }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) yy += x[it][e] * x[it][e];
-  }
+  unpack_cols<KI, true>(K, kin, xr, nr, x, ss, &yy);  // gemv1_head_block's x, sum(x^2) and ŷ: the same function
   float acc[R];
 #pragma unroll
   for (int i = 0; i < R; ++i) {
@@ -860,23 +861,22 @@ __global__ __launch_bounds__(256) void lm_head_approx_bias_kernel(const int8_t* 
 struct LmHeadRescoreTail {
   const float* bias; float* out; int fast_math;
   ArgmaxPartials part;
-  int* stats;
+  int* stats;  // [2] += candidate blocks, += 1 per step (never read by the step)
 };
 template <int PR, int KI>
 __global__ __launch_bounds__(256) void lm_head_rescore_kernel(const float* blk_lo, const float* blk_hi, const uint16_t* W, const float* x,
                                                               const float* rms_w, int n_blk, int N, int K, float eps, LmHeadRescoreTail tl) {
-  LmHeadArgsDev p{};
-  p.blk_lo = const_cast<float*>(blk_lo); p.blk_hi = const_cast<float*>(blk_hi); p.g.W = W; p.g.x = x; p.g.rms_w = rms_w; p.n_blk = n_blk;
-  p.g.N = N; p.g.K = K; p.g.eps = eps;
-  p.g.bias = tl.bias; p.g.out = tl.out; p.g.fast_math = tl.fast_math; p.g.part = tl.part; p.stats = tl.stats; p.g.mode = 3;
+  GemvArgs g{};
+  g.W = W; g.x = x; g.rms_w = rms_w; g.N = N; g.K = K; g.eps = eps;
+  g.bias = tl.bias; g.out = tl.out; g.fast_math = tl.fast_math; g.part = tl.part; g.mode = 3;
   __shared__ float am_v[4][1];
   __shared__ int am_i[4][1];
   __shared__ float red[4];
   __shared__ int cand[256];
   constexpr int PRE = 10;  // float4 of block minima per thread in the first batch (40 960 blocks); more are folded by the loop below
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nb = p.n_blk, n4 = (nb + 3) / 4, G = gridDim.x;
-  const float4* lo4 = reinterpret_cast<const float4*>(p.blk_lo);
+  const int nb = n_blk, n4 = (nb + 3) / 4, G = gridDim.x;
+  const float4* lo4 = reinterpret_cast<const float4*>(blk_lo);
   float4 lv[PRE];
 #pragma unroll
   for (int j = 0; j < PRE; ++j) {
@@ -884,7 +884,7 @@ __global__ __launch_bounds__(256) void lm_head_rescore_kernel(const float* blk_l
     lv[j] = lo4[i4 < n4 ? i4 : n4 - 1];
   }
   const int mb = blockIdx.x + tid * G;  // this thread's block
-  const float hv = p.blk_hi[mb < nb ? mb : nb - 1];
+  const float hv = blk_hi[mb < nb ? mb : nb - 1];
   float t = -INFINITY;
   auto fold = [&](const float4& v, int i4) {
     const int i = i4 * 4;
@@ -909,16 +909,16 @@ __global__ __launch_bounds__(256) void lm_head_rescore_kernel(const float* blk_l
   for (int j = 0; j < nj; ++j) {
     if (!cand[j]) continue;  // uniform
     ArgmaxAcc<false> r;
-    gemv1_head_block<PR, KI>(p.g, blockIdx.x + j * G, am_v, am_i, nullptr, r);
+    gemv1_head_block<PR, KI>(g, blockIdx.x + j * G, am_v, am_i, nullptr, r);
     if (tid == 0) best.merge(r);
     ++nc;
     __syncthreads();  // am_v / am_i are reused by the next candidate
   }
   if (tid == 0) {
-    best.store(p.g.part, 0, blockIdx.x);
-    if (p.stats) {
-      if (nc) atomicAdd(&p.stats[0], nc);
-      if (blockIdx.x == 0) atomicAdd(&p.stats[1], 1);
+    best.store(g.part, 0, blockIdx.x);
+    if (tl.stats) {
+      if (nc) atomicAdd(&tl.stats[0], nc);
+      if (blockIdx.x == 0) atomicAdd(&tl.stats[1], 1);
     }
   }
 }
@@ -936,14 +936,11 @@ __global__ __launch_bounds__(256) void gemvn_kernel(GemvArgs a) {
   const int g = blockIdx.x * 4 + wave;
   int prow[PR];
   gemv_rows<PR>(a, g, prow);
+  bool kin[PF];  // the first PF k-iterations are requested up front, on the one-sequence column plan
+  int kk[PF];
+  lane_cols<PF>(lane, K, kin, kk);
   uint4 wq[PF][PR];
-#pragma unroll
-  for (int it = 0; it < PF; ++it) {
-    const int k = lane * 8 + it * 512;
-#pragma unroll
-    for (int i = 0; i < PR; ++i)  // unconditional (clamped) loads: no exec-masked blocks, no waits between requests
-      wq[it][i] = ld_stream16(a.W + (size_t)(prow[i] >= 0 ? prow[i] : a.N - 1) * K + (k < K ? k : 0));
-  }
+  request_rows<PF, PR>(a, prow, kk, wq);
   __shared__ AttnTables f_s;
   if (a.attn_po) attn_scales(a, NB, f_s);
 #pragma unroll
@@ -990,15 +987,12 @@ __global__ __launch_bounds__(256) void gemvn_kernel(GemvArgs a) {
     }
   };
 #pragma unroll
-  for (int it = 0; it < PF; ++it) {
-    const int k = lane * 8 + it * 512;
-    if (k < K) fma_all(wq[it], k);
-  }
+  for (int it = 0; it < PF; ++it)
+    if (kin[it]) fma_all(wq[it], kk[it]);
   for (int k = lane * 8 + PF * 512; k < K; k += 512) {
     uint4 w[PR];
 #pragma unroll
-    for (int i = 0; i < PR; ++i)
-      w[i] = ld_stream16(a.W + (size_t)(prow[i] >= 0 ? prow[i] : a.N - 1) * K + k);
+    for (int i = 0; i < PR; ++i) w[i] = ld_w16(a, prow[i], k);
     fma_all(w, k);
   }
 #pragma unroll
@@ -1076,14 +1070,6 @@ void launchn(const GemvArgs& a, hipStream_t s) {
 
 }  // namespace
 
-static LmHeadArgsDev lm_head_dev_args(const LmHeadPruneArgs& a) {
-  LmHeadArgsDev p{};
-  p.g = a.g; p.Wq = a.Wq; p.qs = a.qs; p.qcols = a.qcols; p.blk_lo = a.blk_lo; p.blk_hi = a.blk_hi; p.n_blk = lm_head_prune_blocks(a.g);
-  p.dbg = a.dbg; p.stats = a.stats;
-  const double nu = (double)a.qcols * 0x1p-24;  // γ of the bound above, n = cols
-  p.gamma = (float)(nu / (1.0 - nu)) * (1.0f + 0x1p-20f);
-  return p;
-}
 int lm_head_prune_blocks(const GemvArgs& g) { return (g.N + 15) / 16; }
 const char* launch_lm_head_quantize(const uint16_t* W, int N, int K, int8_t* Q, float* qs, hipStream_t s) {
   const int cols = lm_head_q_cols(K);
@@ -1105,10 +1091,12 @@ const char* lm_head_prune_check(const LmHeadPruneArgs& a) {
 }
 const char* launch_lm_head_approx(const LmHeadPruneArgs& a, hipStream_t s) {
   if (const char* e = lm_head_prune_check(a)) return e;
-  const LmHeadArgsDev p = lm_head_dev_args(a);
-  const dim3 grid((p.n_blk + 3) / 4), block(256);
-  const LmHeadApproxTail t{p.g.eps, p.g.fast_math, p.gamma, p.blk_lo, p.blk_hi, p.dbg};
-#define LM_HEAD_APPROX_ARGS p.Wq, p.g.x, p.g.rms_w, p.qs, p.g.bias, p.g.N, p.g.K, p.qcols, p.n_blk, t
+  const GemvArgs& g = a.g;
+  const int n_blk = lm_head_prune_blocks(g);
+  const dim3 grid((n_blk + 3) / 4), block(256);
+  const double nu = (double)a.qcols * 0x1p-24;  // γ of the bound above, n = cols
+  const LmHeadApproxTail t{g.eps, g.fast_math, (float)(nu / (1.0 - nu)) * (1.0f + 0x1p-20f), a.blk_lo, a.blk_hi, a.dbg};
+#define LM_HEAD_APPROX_ARGS a.Wq, g.x, g.rms_w, a.qs, g.bias, g.N, g.K, a.qcols, n_blk, t
   if (a.g.bias) {
     if (a.qcols == 1024) hipLaunchKernelGGL(lm_head_approx_bias_kernel<2>, grid, block, 0, s, LM_HEAD_APPROX_ARGS);
     else hipLaunchKernelGGL(lm_head_approx_bias_kernel<4>, grid, block, 0, s, LM_HEAD_APPROX_ARGS);
@@ -1125,10 +1113,11 @@ int lm_head_rescore_groups(const GemvArgs& g, int n_cu) {
 }
 const char* launch_lm_head_rescore(const LmHeadPruneArgs& a, int groups, hipStream_t s) {
   if (const char* e = lm_head_prune_check(a)) return e;
-  const LmHeadArgsDev p = lm_head_dev_args(a);
-  if (groups < 1 || groups > a.g.part.stride || (p.n_blk + groups - 1) / groups > 256) return "lm_head_prune: bad rescore grid";
-  const LmHeadRescoreTail t{p.g.bias, p.g.out, p.g.fast_math, p.g.part, p.stats};
-#define LM_HEAD_RESCORE_ARGS p.blk_lo, p.blk_hi, p.g.W, p.g.x, p.g.rms_w, p.n_blk, p.g.N, p.g.K, p.g.eps, t
+  const GemvArgs& g = a.g;
+  const int n_blk = lm_head_prune_blocks(g);
+  if (groups < 1 || groups > g.part.stride || (n_blk + groups - 1) / groups > 256) return "lm_head_prune: bad rescore grid";
+  const LmHeadRescoreTail t{g.bias, g.out, g.fast_math, g.part, a.stats};
+#define LM_HEAD_RESCORE_ARGS a.blk_lo, a.blk_hi, g.W, g.x, g.rms_w, n_blk, g.N, g.K, g.eps, t
   if (a.qcols == 1024) hipLaunchKernelGGL((lm_head_rescore_kernel<4, 2>), dim3(groups), dim3(256), 0, s, LM_HEAD_RESCORE_ARGS);
   else hipLaunchKernelGGL((lm_head_rescore_kernel<4, 4>), dim3(groups), dim3(256), 0, s, LM_HEAD_RESCORE_ARGS);
 #undef LM_HEAD_RESCORE_ARGS

@@ -243,9 +243,12 @@ def excess(got, ref, bound):
 # N = 16 * 37 + 5 is the smallest shape with a partly filled last 16-row block; launch_gemv runs it one row per wave.  The pruned pair
 # (int8 pre-pass + rescore) only exists where the unpruned launch runs 16-row blocks -- 4 rows per wave, from 32768 rows on
 # (k_gemv.hip lm_head_prune_check refuses anything else) -- so the pair is checked at 32768 + 16 * 37 + 5 rows, against the unpruned
-# launch on the same data.
+# launch on the same data.  K = 2048 (the 1.7B model's hidden size) runs the other instantiation of each kernel: gemv1_head_kernel<*, 4>,
+# lm_head_approx_kernel<4>, lm_head_rescore_kernel<4, 4>.
 LM_HEAD_CASES = [dict(name="lm-head-597", K=1024, N=16 * 37 + 5, pruned=False),
-                 dict(name="lm-head-33365", K=1024, N=32768 + 16 * 37 + 5, pruned=True)]
+                 dict(name="lm-head-33365", K=1024, N=32768 + 16 * 37 + 5, pruned=True),
+                 dict(name="lm-head-597-k2048", K=2048, N=16 * 37 + 5, pruned=False),
+                 dict(name="lm-head-33365-k2048", K=2048, N=32768 + 16 * 37 + 5, pruned=True)]
 
 
 def lm_head_inputs(c):
