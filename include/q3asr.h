@@ -621,6 +621,12 @@ int32_t q3a_selftest_repeat(int32_t device, const float* logits, int32_t S, int3
  *                        over the lm_head (approximate logits with a rigorous error bound) and a bf16 rescore of the 16-row blocks
  *                        that can still hold the maximum: the ids are bit-identical to 0, the full bf16 GEMV.  Taken at the next
  *                        batch set-up.
+ *   "oproj_by_head"      1 (default): the one-sequence decode step of the default mode (hidden size <= 1024, kv heads of two q heads)
+ *                        runs o_proj per pair of kv heads -- partial vectors that the gate / up projection adds to the residual -- and
+ *                        decode attention in 32-key splits up to 512 keys of context, 64-key splits up to 1024, 128-key splits up
+ *                        to 2048; 0: the o_proj that merges the whole context and 128-key splits, which longer contexts, the
+ *                        precise mode and every other shape run anyway.  Same sums in another fp32 order.  Taken at the next
+ *                        batch set-up.
  *   "layer_taps"         (debug aid) 1: an engine created with debug taps also keeps raw copies of every encoder / decoder
  *                        prefill layer's intermediate buffers (taps "E%02d_x", "L%02d_ln1" / "_q" (default mode) / "_k" / "_v" /
  *                        "_attn" / "_o" / "_ln2" / "_act" / "_x"; the environment's Q3A_DEBUG_LAYER_TAPS=1 sets it).  Taken at the
@@ -680,6 +686,23 @@ int32_t q3a_selftest_gemv_launch(int32_t device, int32_t pruned, const uint16_t*
 int32_t q3a_selftest_decode_attn_launch(int32_t device, int32_t kv_f32, const float* qkv, int32_t pos, const float* q_norm, const float* k_norm, float eps,
                                         const float* rope_cur, void* kcache, void* vcache, int32_t n_q, int32_t n_kv, int32_t max_ctx, int32_t nsplit,
                                         float scale_div, float* pm, float* pl, float* po);
+/* The same launch with the split size given: keys_per_split 32 or 64 (bf16 cache, kv heads of at most two q heads: 4 waves per
+ * workgroup), 128, or 0 for the default; nsplit splits of that size, every one of them written. */
+int32_t q3a_selftest_decode_attn_split_launch(int32_t device, int32_t kv_f32, int32_t keys_per_split, const float* qkv, int32_t pos, const float* q_norm,
+                                              const float* k_norm, float eps, const float* rope_cur, void* kcache, void* vcache, int32_t n_q, int32_t n_kv,
+                                              int32_t max_ctx, int32_t nsplit, float scale_div, float* pm, float* pl, float* po);
+/* ONE launch of the o_proj per pair of kv heads (launch_oproj_head; the default arithmetic: hardware exponential in the merge): w bf16 [N][K],
+ * K = attn_heads * 128 = n_parts * 512, the flash-decoding partials as in q3a_selftest_gemv_launch with attn_nsplit <= 16 (more is
+ * refused with a message, nothing is launched), bias [N] nullable (added to slice 0).  y_part [n_parts][N] (sentinel in, whole buffer
+ * out): the dot products of each 512-column slice with the merged context, no residual. */
+int32_t q3a_selftest_oproj_head_launch(int32_t device, const uint16_t* w, int32_t N, int32_t K, const float* bias, const float* attn_pm, const float* attn_pl,
+                                       const float* attn_po, int32_t attn_nsplit, int32_t attn_heads, int32_t n_parts, float* y_part);
+/* ONE launch of the gate / up GEMV that adds partial vectors to its input (launch_gemv with GemvArgs::x_parts; precise arithmetic):
+ * GLU of w bf16 [N][K], K <= 1024, on the RMSNorm (rms_w [K], eps) of x + x_parts[0] + ... + x_parts[n_parts - 1] (x [K], x_parts
+ * [n_parts][K], n_parts <= 4), bias [N] nullable.  out [N / 2] and x_out [K], the summed vector as the launch stores it (sentinel in,
+ * whole buffer out). */
+int32_t q3a_selftest_gemv_parts_launch(int32_t device, const uint16_t* w, int32_t N, int32_t K, const float* x, const float* rms_w, float eps,
+                                       const float* bias, const float* x_parts, int32_t n_parts, float* out, float* x_out);
 /* Rows [0, M1) of an M x N bf16 GEMM that launch_gemm256 gives to the 256 x 256 kernel when it hands the trailing rows to the small
  * tiles (wave quantisation; 0: no split).  Host arithmetic, no device needed. */
 int32_t q3a_gemm256_split_rows(int32_t M, int32_t N);

@@ -28,6 +28,7 @@ SYMBOLS = [
     "q3a_set_repetition", "q3a_selftest_repeat",
     "q3a_selftest_gemm_launch", "q3a_selftest_qkrope_launch", "q3a_gemm256_split_rows",
     "q3a_selftest_gemv_launch", "q3a_selftest_decode_attn_launch",
+    "q3a_selftest_decode_attn_split_launch", "q3a_selftest_oproj_head_launch", "q3a_selftest_gemv_parts_launch",
     "q3a_prefill_draft", "q3a_transcribe_draft_batch_ptrs", "q3a_draft_next_round", "q3a_selftest_draft_accept",
 ]
 
@@ -165,6 +166,9 @@ def load() -> C.CDLL:
         "q3a_selftest_qkrope_launch": (i32, [i32, i32, i32, P, i32, P, i32, i32, P, P, P, P, P, P, C.c_float, P, P, i32, i32, i32, i32, i32, P, P, P]),
         "q3a_selftest_gemv_launch": (i32, [i32, i32, P, i32, i32, P, P, C.c_float, P, i32, P, P, P, P, i32, i32, P, P]),
         "q3a_selftest_decode_attn_launch": (i32, [i32, i32, P, i32, P, P, C.c_float, P, P, P, i32, i32, i32, i32, C.c_float, P, P, P]),
+        "q3a_selftest_decode_attn_split_launch": (i32, [i32, i32, i32, P, i32, P, P, C.c_float, P, P, P, i32, i32, i32, i32, C.c_float, P, P, P]),
+        "q3a_selftest_oproj_head_launch": (i32, [i32, P, i32, i32, P, P, P, P, i32, i32, i32, P]),
+        "q3a_selftest_gemv_parts_launch": (i32, [i32, P, i32, i32, P, P, C.c_float, P, P, i32, P, P]),
         "q3a_gemm256_split_rows": (i32, [i32, i32]),
         "q3a_prefill_draft": (i32, [P, i32p, i32p, i32p, i32p, i32, i32p, i32p, f32p]),
         "q3a_transcribe_draft_batch_ptrs": (i32, [P, C.POINTER(P), i64p, i32, i32p, i32, i32p, i32p, i32, i32, i32, i32p, i32, i32p, i32p]),
@@ -173,6 +177,8 @@ def load() -> C.CDLL:
                                             i32p, i32p, f32p, i32p, f32p, f32p, P, f32p]),
     }
     for name, (res, args) in sig.items():
+        if os.environ.get("Q3A_LIB") and not hasattr(lib, name):
+            continue  # an A/B build of another commit (the parent's, for a headline A/B) may predate an entry point
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

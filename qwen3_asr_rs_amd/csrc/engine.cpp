@@ -88,6 +88,7 @@ static const KnobEntry kKnobTable[] = {
     {"eos_run_ahead", "Q3A_EOS_RUN_AHEAD", &Knobs::eos_run_ahead},
     {"skinny_glu_hp3", "Q3A_SKINNY_GLU_HP3", &Knobs::skinny_glu_hp3},
     {"lm_head_prune", "Q3A_LM_HEAD_PRUNE", &Knobs::lm_head_prune},
+    {"oproj_by_head", "Q3A_OPROJ_BY_HEAD", &Knobs::oproj_by_head},
     {"layer_taps", "Q3A_DEBUG_LAYER_TAPS", &Knobs::layer_taps},
     {"poison_attn_partials", nullptr, &Knobs::poison_attn_partials},
 };
@@ -124,9 +125,9 @@ struct StepView {
   const std::vector<hipEvent_t>& join_ev; const hipEvent_t& fork_ev; const int& n_cu; int* const& host_prog_dev;  // (pinned progress words, device view)
   std::vector<ProfEvent>* const& prof; Taps& taps;  // prof not null: every launch between a pair of events
   const int8_t* const& lm_q; const float* const& lm_qs; const int& lm_q_cols;  // int8 lm_head copy: set once at init, never moved
-  const int &B, &max_ctx, &max_new, &gsize, &live_nsplit_, &attn_nsplit, &min_P_, &part_stride, &beam_w_;
+  const int &B, &max_ctx, &max_new, &gsize, &live_nsplit_, &live_kps_, &attn_nsplit, &min_P_, &part_stride, &beam_w_;
   const size_t& kv_layer_elems; const bool& head_logits_;
-  const int &k_parallel_groups, &k_skinny_q, &k_dattn_batched_min_wgs, &k_skinny_glu_hp3, &k_lm_head_prune;  // knobs as latched per batch
+  const int &k_parallel_groups, &k_skinny_q, &k_dattn_batched_min_wgs, &k_skinny_glu_hp3, &k_lm_head_prune, &k_oproj_by_head;  // knobs as latched per batch
   const bool& logit_bias_on_;  // q3a_set_logit_bias: a bias is set (changes only while the engine holds no decode state)
   const bool& sampling_on_;    // q3a_set_sampling: temperature > 0 (likewise)
   const bool& repetition_on_;  // q3a_set_repetition: a penalty != 1 or an n-gram size > 0 (likewise)
@@ -150,6 +151,7 @@ struct DecodeStep : StepView {
   DevBuf part_sum, out_lp;  // opts.token_logprobs: log-sum channel of the argmax partials, [B][max_new] log-probabilities next to out_ids
   DevBuf blk_lo, blk_hi;  // pruned lm_head argmax: per 16-row block bounds (pass 1 -> pass 2)
   DevBuf prune_stats;     // [2] candidate blocks rescored, pass-2 launches (q3a_debug_read "lm_head_prune_stats"; never read by the step)
+  DevBuf o_part, x_mid;  // one-sequence chain with o_proj per pair of kv heads: its partial vectors [n_kv / 2][hidden], and the residual after o_proj [hidden] (gate / up writes it, down reads it)
   DevBuf attn_pm, attn_pl, attn_po, nn_x, nn_ss;  // nn_*: pre-normalised residual row for the next skinny GEMM: [32 * hidden] bf16 fragment order, [hidden/16][32] f32
   // rope_cur: [B][128] cos|sin row of each sequence's current position (kept by argmax_finalize for decode attention); the tables: ensure_rope
   DevBuf rope_cur, rope_cos, rope_sin;
@@ -166,7 +168,7 @@ struct DecodeStep : StepView {
   // struct ARE the guarded set: tests/test_host.py::test_step_buffers_cover_the_captured_step compares this list with them.
   template <class Self, class F> static void each_buf(Self& s, F&& f) {
     for (auto* b : {&s.kcache, &s.vcache, &s.x_dec, &s.d_pos, &s.next_tok, &s.out_ids, &s.step_count, &s.done, &s.s_ln, &s.s_qkv, &s.s_ctx, &s.s_act, &s.logits,
-                    &s.part_val, &s.part_idx, &s.part_sum, &s.out_lp, &s.blk_lo, &s.blk_hi, &s.prune_stats, &s.attn_pm, &s.attn_pl, &s.attn_po, &s.nn_x, &s.nn_ss,
+                    &s.part_val, &s.part_idx, &s.part_sum, &s.out_lp, &s.blk_lo, &s.blk_hi, &s.prune_stats, &s.o_part, &s.x_mid, &s.attn_pm, &s.attn_pl, &s.attn_po, &s.nn_x, &s.nn_ss,
                     &s.rope_cur, &s.rope_cos, &s.rope_sin, &s.n_done, &s.forced_tok,
                     &s.beam_cand_val, &s.beam_cand_idx, &s.beam_part_max, &s.beam_part_sum, &s.beam_topk_ids, &s.beam_topk_lp, &s.beam_score, &s.beam_finished,
                     &s.beam_parent, &s.beam_token, &s.beam_feed, &s.beam_hist_parent, &s.beam_hist_token, &s.beam_hist_lp, &s.beam_state, &s.beam_lo,
@@ -419,6 +421,7 @@ struct DecodeStep : StepView {
     da.rope_cur = rope_cur.as<float>() + (size_t)s0 * 128;
     da.pm = attn_pm.as<float>() + (size_t)s0 * d.n_q * attn_nsplit; da.pl = attn_pl.as<float>() + (size_t)s0 * d.n_q * attn_nsplit;
     da.po = attn_po.as<float>() + (size_t)s0 * d.n_q * attn_nsplit * 128; da.nsplit = live_nsplit_;  // (buffers sized for attn_nsplit)
+    da.keys_per_split = live_kps_;  // (0 outside the chain with o_proj by column slice: 128)
     da.n_q = d.n_q; da.n_kv = d.n_kv; da.max_ctx = max_ctx; da.scale_div = sqrtf((float)d.head_dim);
     da.q_norm = wf(l.q_norm); da.k_norm = wf(l.k_norm);
     da.kcache = (uint8_t*)kc_layer(li) + (size_t)s0 * kv_seq; da.vcache = (uint8_t*)vc_layer(li) + (size_t)s0 * kv_seq;
@@ -428,6 +431,23 @@ struct DecodeStep : StepView {
       g.x = x; g.rms_w = wf(l.in_ln); g.out = qkv;
       run(pj.qkv, g);
       timed(Q3A_KC_DECODE_ATTN, 0, [&] { KCHK(launch_decode_attn(da, S, kv_f32(), ks)); });
+      if (live_kps_ > 0) {
+        // o_proj per pair of kv heads: n_kv / 2 partial vectors, no residual add; gate / up forms x + their sum for itself and leaves it in x_mid
+        // (x_dec is read by every workgroup of that launch: the sum cannot go back there), the down projection adds to x_mid and
+        // writes x_dec, where the next layer and the head expect the residual stream
+        OprojHeadArgs oh{};
+        oh.pm = da.pm; oh.pl = da.pl; oh.po = da.po; oh.nsplit = live_nsplit_;
+        oh.W = pj.o.W; oh.N = pj.o.N; oh.K = pj.o.K; oh.bias = pj.o.bias; oh.n_parts = d.n_kv / 2; oh.y_part = o_part.as<float>();
+        timed(pj.o.kclass, pj.o.bytes, [&] { KCHK(launch_oproj_head(oh, ks)); });
+        GemvArgs u = gemv_args(pj.gu);
+        u.x = x; u.rms_w = wf(l.post_ln); u.out = s_act_g(grp);
+        u.x_parts = oh.y_part; u.x_nparts = oh.n_parts; u.x_out = x_mid.as<float>();
+        run(pj.gu, u);
+        GemvArgs dn = gemv_args(pj.down);
+        dn.x = s_act_g(grp); dn.out = x; dn.resid = u.x_out;
+        run(pj.down, dn);
+        return;
+      }
       GemvArgs o = gemv_args(pj.o);
       if (std::min(S, 4) * d.n_q * live_nsplit_ <= GEMV_ATTN_MAX_TABLE) {  // merge the key splits inside the o_proj GEMV
         o.attn_pm = da.pm; o.attn_pl = da.pl; o.attn_po = da.po;
@@ -519,6 +539,14 @@ struct DecodeStep : StepView {
   }
 
   // does any group of the batch run the key-split attention (GEMV path, or a group too small for the batched kernel)?
+  // The one-sequence chain of the default mode with o_proj per pair of kv heads (k_gemv.hip oproj_head_kernel, the XP gate / up form)
+  // and the finer key splits it allows: where the shapes are the kernels' -- kv heads of two q heads, at most GEMV_X_PARTS_MAX pairs,
+  // a hidden size in the gate / up hand-over form (K <= 1024).  The 1.7B model (hidden 2048) keeps the merging o_proj.
+  bool oproj_by_head() const {
+    return k_oproj_by_head != 0 && B == 1 && !precise() && d.n_q == 2 * d.n_kv && d.n_kv % 2 == 0 && d.n_kv / 2 <= GEMV_X_PARTS_MAX && d.hidden <= 1024;
+  }
+  // keys per split for a step whose context is `keys` keys; 0: the chain does not run (contexts beyond dattn_fine_keys_per_split)
+  int fine_keys_per_split(int keys) const { return oproj_by_head() ? dattn_fine_keys_per_split(keys) : 0; }
   bool uses_key_splits() const {
     if (B <= kGemvMaxSeq) return true;
     const int ng = n_groups(B);
@@ -637,7 +665,7 @@ struct q3a_engine : CallState {
   int gsize = 32;  // sequences per group of the batched decode step (<= 32: one skinny-GEMM weight sweep), fixed per batch
   // knobs that shape the decode step, latched per batch in setup_prompts: producers outside the captured graph (prefill
   // finalize, set_tokens) and the captured step must agree on them, and the graph signature names them
-  int k_parallel_groups = 1, k_skinny_q = 1, k_dattn_batched_min_wgs = 128, k_skinny_glu_hp3 = 1, k_lm_head_prune = 1;
+  int k_parallel_groups = 1, k_skinny_q = 1, k_dattn_batched_min_wgs = 128, k_skinny_glu_hp3 = 1, k_lm_head_prune = 1, k_oproj_by_head = 1;
   std::vector<hipStream_t> chain_streams;
   std::vector<hipEvent_t> join_ev;
   hipEvent_t fork_ev = nullptr;
@@ -651,6 +679,7 @@ struct q3a_engine : CallState {
   // 128-key split).  Sized by what the caches HOLD, not by their capacity: pos_hi_ = longest prompt + decode steps enqueued
   // (host-side count, an upper bound of every sequence's position), so a generous max_new_tokens costs no empty splits.
   int pos_hi_ = 0, live_nsplit_ = 0;
+  int live_kps_ = 0;  // keys per split of the step being enqueued where the chain with o_proj by column slice runs (32 / 64 / 128), else 0
   int min_P_ = 0;  // shortest prompt of the batch (decides DecodeAttnArgs::trim_prologue; part of the graph signature)
 
   // ---- input upload of q3a_transcribe_batch[_ptrs] (the window is host PCM -> ids on the host) ----
@@ -683,8 +712,8 @@ struct q3a_engine : CallState {
 
   // ---- the captured decode step: its buffers and launches, and all it sees of the members above ----
   DecodeStep step{StepView{d, L, opts, arena, arena_flags, stream, chain_streams, join_ev, fork_ev, n_cu, host_prog_dev, prof, taps, lm_q, lm_qs, lm_q_cols,
-                           B, max_ctx, max_new, gsize, live_nsplit_, attn_nsplit, min_P_, part_stride, beam_w(), kv_layer_elems, head_logits(),
-                           k_parallel_groups, k_skinny_q, k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, logit_bias_on_, sampling_on_, repetition_on_}};
+                           B, max_ctx, max_new, gsize, live_nsplit_, live_kps_, attn_nsplit, min_P_, part_stride, beam_w(), kv_layer_elems, head_logits(),
+                           k_parallel_groups, k_skinny_q, k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, k_oproj_by_head, logit_bias_on_, sampling_on_, repetition_on_}};
 
   // (the mode rules are stated once, in StepView)
   bool precise() const { return step.precise(); }
@@ -1185,6 +1214,7 @@ struct q3a_engine : CallState {
       k_dattn_batched_min_wgs = kn.dattn_batched_min_wgs.load();
       k_skinny_glu_hp3 = kn.skinny_glu_hp3.load();
       k_lm_head_prune = kn.lm_head_prune.load();
+      k_oproj_by_head = kn.oproj_by_head.load();
     }
     const size_t ng = (size_t)step.n_groups(b);  // groups of <= gsize sequences of the batched decode step
     step.nn_x.ensure(ng * 32 * H * 2); step.nn_ss.ensure((size_t)ng * (H / 8) * 32 * 4);  // room for the finer (8-column) partial rows whichever shape the knob selects later
@@ -1202,6 +1232,10 @@ struct q3a_engine : CallState {
       step.blk_lo.ensure(nblk4 * 4); step.blk_hi.ensure(nblk4 * 4);
     }
     attn_nsplit = (max_ctx + dattn_keys_per_split(kv_f32()) - 1) / dattn_keys_per_split(kv_f32());
+    if (step.oproj_by_head()) {  // the finer splits: up to OPROJ_HEAD_MAX_SPLITS of them, whatever max_ctx
+      attn_nsplit = std::max(attn_nsplit, OPROJ_HEAD_MAX_SPLITS);
+      step.o_part.ensure((size_t)(d.n_kv / 2) * H * 4); step.x_mid.ensure(H * 4);
+    }
     {  // (+8 floats: the merge-first o_proj GEMV reads a head's statistics 16 bytes at a time, up to 7 entries past the last head's)
       const size_t n_stat = (size_t)b * d.n_q * attn_nsplit;
       step.attn_pm.ensure((n_stat + 8) * 4); step.attn_pl.ensure((n_stat + 8) * 4);
@@ -1593,8 +1627,8 @@ struct q3a_engine : CallState {
     });
     char buf[256];
     // (one field per latched knob, as latched: packing several into one integer let distinct settings collide -- ADVICE r5)
-    snprintf(buf, sizeof(buf), "%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.b%d.lb%d.sm%d.rp%d/%d/%d/%d/%p/%016llx", B, gsize, k_parallel_groups, k_skinny_q,
-             k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, (int)(min_P_ < 256), (int)head_logits(), (int)token_lp(), beam_w(), (int)logit_bias_on_, (int)sampling_on_, (int)repetition_on_, live_nsplit_,
+    snprintf(buf, sizeof(buf), "%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.b%d.lb%d.sm%d.rp%d/%d.%d/%d/%d/%p/%016llx", B, gsize, k_parallel_groups, k_skinny_q,
+             k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, k_oproj_by_head, (int)(min_P_ < 256), (int)head_logits(), (int)token_lp(), beam_w(), (int)logit_bias_on_, (int)sampling_on_, (int)repetition_on_, live_nsplit_, live_kps_,
              max_ctx, max_new, (const void*)arena, (unsigned long long)h);
     return buf;
   }
@@ -1662,7 +1696,9 @@ struct q3a_engine : CallState {
     // 03b3a8b, profiles/r6_ab_decode_steps_per_graph.txt.)
     for (int i = 0; i < n; ++i) {
       // this step feeds the token at position <= pos_hi_ and attends keys 0 .. pos_hi_
-      live_nsplit_ = step.uses_key_splits() ? std::min(attn_nsplit, pos_hi_ / kps + 1) : attn_nsplit;
+      live_kps_ = step.fine_keys_per_split(pos_hi_ + 1);
+      live_nsplit_ = live_kps_ > 0 ? pos_hi_ / live_kps_ + 1
+                     : step.uses_key_splits() ? std::min(attn_nsplit, pos_hi_ / kps + 1) : attn_nsplit;
       if (eager) enqueue_step();
       else HIPCHK(hipGraphLaunch(graph_for_step(), stream));
       ++pos_hi_;

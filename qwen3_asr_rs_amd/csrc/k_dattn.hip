@@ -6,7 +6,7 @@
 // softmax(q K^T / sqrt(128)) V (layers.rs:327-335; the decode-step mask of text_decoder.rs:121-131 is
 // all zeros).
 //
-// Grid = (kv head, sequence, key split of 128 keys).  One CU streams only ~25-50 GB/s, so the ~200 KB of
+// Grid = (kv head, sequence, key split of 128 keys; 32 or 64 on the one-sequence chain with o_proj by column slice).  One CU streams only ~25-50 GB/s, so the ~200 KB of
 // K+V a kv head holds at context ~400 must be spread over several CUs: measured 12.8 us with one workgroup
 // per kv head (8 or 16 waves alike) against 6.4 us with 128-key splits.  Every workgroup
 //   * first issues its cache loads (they do not depend on the new token): each wave owns 16 keys and reads
@@ -50,26 +50,29 @@ template <> struct Frag16<float> {
 #ifndef Q3A_DA_WAVES
 #define Q3A_DA_WAVES 8
 #endif
-constexpr int DA_WAVES = Q3A_DA_WAVES;  // waves per workgroup; a split is always 128 keys
+constexpr int DA_WAVES = Q3A_DA_WAVES;  // waves per workgroup of the batched kernel and of the 128-key splits
 
 // (Round 2 built a fused qkv-projection + attention launch on top of this body -- qkv_attn_kernel, handed over inside each XCD --
 // and round 5 a pair-split form of the batched kernel below; both were correct and slower, and were removed in round 6:
 // docs/HISTORY.md, last present at commit caf7a05.)
-template <int GROUP, typename KVT>
+// SPLIT_KEYS, WAVES: keys per split and waves per workgroup -- 128 keys on 8 waves, or (bf16 cache, behind launch_oproj_head, which
+// merges up to 16 partials per head) 64 or 32 keys on 4 waves: a workgroup then pulls 32 or 16 KB of K+V through its CU instead of 64,
+// and a 505-key context spreads over 128 workgroups instead of 32.  The new token's rows take GROUP + 2 waves.
+template <int GROUP, typename KVT, int SPLIT_KEYS, int WAVES>
 __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& a, const int kvh, const int s, const int sp) {
+  static_assert(WAVES >= GROUP + 2, "one wave per q head, one for k, one for v");
   constexpr int DPL = Frag16<KVT>::DPL;   // head dims per lane: 8 (bf16) / 4 (f32)
   constexpr int LPK = 128 / DPL;          // lanes per key: 16 / 32
   constexpr int KPI = 64 / LPK;           // keys per load instruction: 4 / 2
-  constexpr int SPLIT_KEYS = sizeof(KVT) == 2 ? DATTN_KEYS_PER_SPLIT_BF16 : DATTN_KEYS_PER_SPLIT_F32;
-  constexpr int NI = (SPLIT_KEYS / DA_WAVES) / KPI;  // load instructions per wave: 4 / 8 at 16 keys per wave
-  constexpr int KEYS_PER_WAVE = KPI * NI;     // 16 with 8 waves
-  constexpr int KEYS_PER_SPLIT = KEYS_PER_WAVE * DA_WAVES;  // 128
-  static_assert(KEYS_PER_SPLIT == (sizeof(KVT) == 2 ? DATTN_KEYS_PER_SPLIT_BF16 : DATTN_KEYS_PER_SPLIT_F32), "split size");
+  constexpr int NI = (SPLIT_KEYS / WAVES) / KPI;  // load instructions per wave: 4 / 8 at 16 keys per wave, 2 at 8 (bf16)
+  constexpr int KEYS_PER_WAVE = KPI * NI;     // 16 at 128 keys on 8 waves and at 64 on 4, 8 at 32 on 4
+  constexpr int KEYS_PER_SPLIT = KEYS_PER_WAVE * WAVES;
+  static_assert(NI >= 1 && KEYS_PER_SPLIT == SPLIT_KEYS, "split size");
   __shared__ float q_s[GROUP][128];
   __shared__ __attribute__((aligned(16))) KVT k_s[128];  // the new token's k / v row in cache format
   __shared__ __attribute__((aligned(16))) KVT v_s[128];
-  __shared__ float cm[DA_WAVES][GROUP], cl[DA_WAVES][GROUP];
-  __shared__ float co[DA_WAVES][GROUP][128];
+  __shared__ float cm[WAVES][GROUP], cl[WAVES][GROUP];
+  __shared__ float co[WAVES][GROUP][128];
   // pos in front of the Q3A_ARG block: behind it (asm volatile) hipcc no longer proves the location clobber-free and turns
   // the scalar load into a vector load that it waits for at once.  a.pos is a preloaded head argument (decode_attn_kernel), so this
   // is ONE scalar round trip from the wave's first instruction, not two in series.
@@ -238,15 +241,15 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& a, const 
   }
   __syncthreads();
   Q3A_STAMP_AT(a.stamp, stamp_wg, 4);  // wave partials in LDS
-  // ---- merge the 8 waves, write the split's partial ----
+  // ---- merge the waves, write the split's partial ----
   if (wave < GROUP) {
     const int g = wave;
     float M = -INFINITY;
 #pragma unroll
-    for (int w = 0; w < DA_WAVES; ++w) M = fmaxf(M, cm[w][g]);  // finite: key_lo <= pos
+    for (int w = 0; w < WAVES; ++w) M = fmaxf(M, cm[w][g]);  // finite: key_lo <= pos
     float L = 0.f, o0 = 0.f, o1 = 0.f;
 #pragma unroll
-    for (int w = 0; w < DA_WAVES; ++w) {
+    for (int w = 0; w < WAVES; ++w) {
       const float f = (cm[w][g] == -INFINITY) ? 0.f : expw(cm[w][g] - M);
       L += cl[w][g] * f;
       o0 += co[w][g][lane] * f;
@@ -280,7 +283,24 @@ __global__ __launch_bounds__(DA_WAVES * 64) void decode_attn_kernel(void* kcache
 #ifdef Q3A_STAMP
   a.stamp = t.stamp;
 #endif
-  decode_attn_body<GROUP, KVT>(a, blockIdx.x, blockIdx.y, blockIdx.z);
+  decode_attn_body<GROUP, KVT, sizeof(KVT) == 2 ? DATTN_KEYS_PER_SPLIT_BF16 : DATTN_KEYS_PER_SPLIT_F32, DA_WAVES>(a, blockIdx.x, blockIdx.y, blockIdx.z);
+}
+// The 32- and 64-key splits: 4 waves either way, so ONE kernel runs both.  The split size is a head argument (n_q is GROUP * n_kv and
+// makes room for it among the 14 preloaded dwords) and the choice between the two bodies a scalar branch on a preloaded SGPR, in front
+// of the first request; each body is the straight-line code it is on its own.
+template <int GROUP, typename KVT>
+__global__ __launch_bounds__(4 * 64) void decode_attn_fine_kernel(void* kcache, void* vcache, const int* pos, const float* qkv,
+                                                                  const float* rope_cur, int nsplit, int n_kv, int max_ctx, int keys_per_split,
+                                                                  DecodeAttnTail t) {
+  DecodeAttnArgs a{};
+  a.kcache = kcache; a.vcache = vcache; a.pos = pos; a.qkv = qkv; a.rope_cur = rope_cur; a.nsplit = nsplit; a.n_q = GROUP * n_kv; a.n_kv = n_kv;
+  a.max_ctx = max_ctx;
+  a.q_norm = t.q_norm; a.k_norm = t.k_norm; a.eps = t.eps; a.pm = t.pm; a.pl = t.pl; a.po = t.po; a.scale_div = t.scale_div;
+#ifdef Q3A_STAMP
+  a.stamp = t.stamp;
+#endif
+  if (keys_per_split == 32) decode_attn_body<GROUP, KVT, 32, 4>(a, blockIdx.x, blockIdx.y, blockIdx.z);
+  else decode_attn_body<GROUP, KVT, 64, 4>(a, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
 
@@ -635,12 +655,15 @@ const char* launch_decode_attn(const DecodeAttnArgs& a, int S, bool kv_f32, hipS
   if (S <= 0) return nullptr;
   // the caller launches as many splits as the caches HOLD keys for (every pos < nsplit * keys per split), not as many as they
   // have room for: keys beyond the last split are never looked at
-  if (a.nsplit <= 0 || (a.nsplit - 1) * dattn_keys_per_split(kv_f32) >= a.max_ctx) return "decode_attn: 1 .. ceil(max_ctx / keys per split) key splits";
+  const int kps = a.keys_per_split ? a.keys_per_split : dattn_keys_per_split(kv_f32);
+  if (kps != 128 && (kv_f32 || (kps != 32 && kps != 64))) return "decode_attn: 32- and 64-key splits run on the bf16 cache only; otherwise 128 keys per split";
+  if (a.nsplit <= 0 || (a.nsplit - 1) * kps >= a.max_ctx) return "decode_attn: 1 .. ceil(max_ctx / keys per split) key splits";
   const int group = a.n_q / a.n_kv;
+  if (kps != 128 && group != 2) return "decode_attn: 32- and 64-key splits run for kv heads of two q heads";
   // (Round 6 measured an L2 warm-up duty here -- the CUs this launch leaves idle pulling the o_proj / down matrices and the next
   // layer's K / V rows into the XCD-local L2s: -1.4 % per step on one box, +1.2 % on another, every partial form slower; removed,
   // docs/HISTORY.md 3.2, commit 3ac6499 has the code.)
-  dim3 grid(a.n_kv, S, a.nsplit), block(DA_WAVES * 64);
+  dim3 grid(a.n_kv, S, a.nsplit), block((kps == 128 ? DA_WAVES : 4) * 64);
   DecodeAttnTail t{};
   t.q_norm = a.q_norm; t.k_norm = a.k_norm; t.eps = a.eps; t.pm = a.pm; t.pl = a.pl; t.po = a.po; t.scale_div = a.scale_div;
 #ifdef Q3A_STAMP
@@ -652,7 +675,9 @@ const char* launch_decode_attn(const DecodeAttnArgs& a, int S, bool kv_f32, hipS
     if (kv_f32) hipLaunchKernelGGL((decode_attn_kernel<G, float>), grid, block, 0, s, Q3A_DA_ARGS); \
     else hipLaunchKernelGGL((decode_attn_kernel<G, uint16_t>), grid, block, 0, s, Q3A_DA_ARGS);     \
   } while (0)
-  if (group == 1) Q3A_DA(1);
+  if (kps != 128)  // (group == 2, checked above)
+    hipLaunchKernelGGL((decode_attn_fine_kernel<2, uint16_t>), grid, block, 0, s, a.kcache, a.vcache, a.pos, a.qkv, a.rope_cur, a.nsplit, a.n_kv, a.max_ctx, kps, t);
+  else if (group == 1) Q3A_DA(1);
   else if (group == 2) Q3A_DA(2);
   else if (group == 4) Q3A_DA(4);
   else return "decode_attn: GQA group must be 1, 2 or 4";

@@ -339,9 +339,15 @@ __device__ __forceinline__ void gemv_epilogue(const GemvArgs& a, int g, const in
 // of the weights: x is back after one L2 round trip and the store / barrier / read-back run while the weights are in flight (stamped
 // timeline, profiles/gemv_down_handover_phase_probe.txt: issue 0.85 -> 0.19 us, span 2.02 -> 1.93 us).  Behind the weights the
 // hand-over starts when the last weight chunk has landed and stands exposed in front of the FMAs (span 2.21 us: it lost).
-template <int PR, int KI, bool RMS, bool ATTN, int MF, bool XL>
+// XP (an XL form: gate / up behind oproj_head_kernel): the vector handed over is x + x_parts[0] + ... + x_parts[n - 1], n <=
+// GEMV_X_PARTS_MAX = 4 -- the residual and o_proj's partial vectors, added in ascending order by the thread that hands its four columns
+// over.  All GEMV_X_PARTS_MAX + 1 requests go in one batch where the single x request stands (a vector past n is clamped to the last
+// one and not added).  Workgroup 0 also stores the sum to x_out, the residual the down projection and the next layer read: a buffer no
+// workgroup of this launch reads, so the store races with nothing.
+template <int PR, int KI, bool RMS, bool ATTN, int MF, bool XL, bool XP = false>
 __device__ __forceinline__ void gemv1_body(const GemvArgs& a) {
   static_assert(!XL || !ATTN, "the merged attention vector already goes through LDS");
+  static_assert(!XP || (XL && RMS), "the partial vectors are added in the hand-over of the norm-fused XL form");
   constexpr bool XH = !RMS && !ATTN && KI > 4;
   constexpr bool XLDS = XL || XH;  // x is handed over through LDS (the norm weight, xl_w, only in the XL forms)
   static_assert(!XH || KI % 2 == 0, "the hand-over stores unguarded: its rounds of 1024 columns must end at KI * 512");
@@ -366,6 +372,8 @@ __device__ __forceinline__ void gemv1_body(const GemvArgs& a) {
   uint4 wq[KI][PR];
   constexpr int XLN = (KI + 1) / 2;  // 16-byte pieces of x per lane in the XL / XH forms (256 lanes x 4 floats = 1024 columns per round)
   float4 xl_rx[XLDS ? XLN : 1], xl_rw[(XL && RMS) ? XLN : 1];
+  constexpr int XPN = XP ? GEMV_X_PARTS_MAX : 1;
+  float4 xp_r[XP ? XLN : 1][XPN];
   auto request_x = [&]() {  // L2 hits
     if (ATTN) return;
     if constexpr (XLDS) {
@@ -373,6 +381,11 @@ __device__ __forceinline__ void gemv1_body(const GemvArgs& a) {
       for (int j = 0; j < XLN; ++j) {
         const int k = (tid + j * 256) * 4, kc = k < K ? k : 0;
         xl_rx[j] = *reinterpret_cast<const float4*>(a.x + kc);
+        if constexpr (XP) {
+#pragma unroll
+          for (int h = 0; h < XPN; ++h)
+            xp_r[j][h] = *reinterpret_cast<const float4*>(a.x_parts + (size_t)(h < a.x_nparts ? h : a.x_nparts - 1) * K + kc);
+        }
         if (RMS) xl_rw[j] = *reinterpret_cast<const float4*>(a.rms_w + kc);
       }
       return;
@@ -496,7 +509,13 @@ __device__ __forceinline__ void gemv1_body(const GemvArgs& a) {
       const int k = (tid + j * 256) * 4;
       if (XH || k < KI * 512) {  // (XH: KI is even, the XLN rounds cover exactly KI * 512 columns)
         // element by element: as one aggregate copy (a memcpy from the private array to LDS) hipcc kept xl_rx[XLN > 1] in scratch
-        const float4 v = xl_rx[j];
+        float4 v = xl_rx[j];
+        if constexpr (XP) {
+#pragma unroll
+          for (int h = 0; h < XPN; ++h)
+            if (h < a.x_nparts) { v.x += xp_r[j][h].x; v.y += xp_r[j][h].y; v.z += xp_r[j][h].z; v.w += xp_r[j][h].w; }
+          if (blockIdx.x == 0 && k < K) *reinterpret_cast<float4*>(a.x_out + k) = v;
+        }
         *reinterpret_cast<float4*>(x_lds + k) = make_float4(v.x, v.y, v.z, v.w);
         if (RMS) *reinterpret_cast<float4*>(xl_w + k) = xl_rw[j];
       }
@@ -598,6 +617,142 @@ __global__ __launch_bounds__(256) void gemv1_kernel(const float* attn_pm, const 
   a.out = t.out; a.bias = t.bias; a.attn_heads = t.attn_heads; a.attn_fast_exp = t.attn_fast_exp; a.fast_math = t.fast_math;
   Q3A_STAMP_COPY(a, t);
   gemv1_body<PR, KI, RMS, ATTN, MF, XL>(a);
+}
+
+// The XP form (gate / up: mode 2, norm fused, K <= 1024).  Every vector the hand-over's one batch of requests is addressed with
+// stands in the head; the store of the sum (x_out) rides in the tail.
+struct GemvXpTail {
+  float* out; float* x_out; int fast_math;
+  Q3A_STAMP_FIELD
+};
+template <int PR, int KI>
+__global__ __launch_bounds__(256) void gemv1_xp_kernel(const uint16_t* W, const float* x, const float* rms_w, const float* x_parts,
+                                                       const float* bias, int N, int K, int x_nparts, float eps, GemvXpTail t) {
+  GemvArgs a{};
+  a.W = W; a.x = x; a.rms_w = rms_w; a.x_parts = x_parts; a.bias = bias; a.N = N; a.K = K; a.x_nparts = x_nparts; a.eps = eps; a.mode = 2;
+  a.out = t.out; a.x_out = t.x_out; a.fast_math = t.fast_math;
+  Q3A_STAMP_COPY(a, t);
+  gemv1_body<PR, KI, true, false, 0, true, true>(a);
+}
+
+// ---- o_proj per column slice (one sequence, default mode) ---------------------------------------------------
+// Workgroup (slice p, row block): the CW columns of slice p -- whole kv heads, CW / 128 q heads -- of RB rows of W.  Today's
+// o_proj merges the whole context in each of its 256 workgroups (nsplit x 8 KB of partials next to 16 KB of weights); here a
+// workgroup requests only its slice's partials (nsplit x CW x 4 bytes), in one batch in front of its weights, and merges them once:
+//   * thread (tg, e4) of the TG = 256 / (CW / 4) thread groups requests 4 elements (e4) of splits tg, tg + TG, ...: OPROJ_HEAD_MAX_SPLITS /
+//     TG requests per thread, a split past nsplit clamped to the last one and voided through its statistics;
+//   * the statistics (m, l) of the slice's heads go through LDS: one request per thread, then every thread reads its head's 16
+//     entries back and forms M, L and f_j = exp(m_j - M) as attn_merge8_ch does (hardware exponential; an empty split has m = -inf,
+//     f = 0, and zeroed partials);
+//   * each thread group's sum over its splits goes to LDS, and every lane adds the TG sums of the 8 columns its weights need, in
+//     ascending group order, and scales by 1 / L.
+// The weight slice of a row is CW / 8 lanes x 16 B: a wave instruction covers 64 / (CW / 8) rows.  The result is y_part[p][n], fp32:
+// no residual -- the consumer (gemv1_xp_kernel) adds the slices to it.  Slice p = blockIdx.x % n_parts.  Built and measured with CW =
+// 256 (one kv head per slice: 8 partial vectors at the models' shapes, each workgroup on the XCD whose L2 holds what decode attention
+// wrote for its kv head under round-robin placement) and CW = 512 (a pair of kv heads, 4 vectors): 512 won by 3 us per step -- gate / up
+// requests half as many vectors -- and is the only form instantiated (profiles/oproj_by_head_headline_ab.txt).
+struct OprojHeadTail {
+  const float* bias;
+  Q3A_STAMP_FIELD
+};
+template <int CW, int RB>
+__global__ __launch_bounds__(256) void oproj_head_kernel(const float* pm, const float* pl, const float* po, const uint16_t* W, float* y_part,
+                                                         int N, int K, int nsplit, int n_parts, OprojHeadTail t) {
+  constexpr int NS = OPROJ_HEAD_MAX_SPLITS;
+  constexpr int HEADS = CW / 128;  // q heads of a slice
+  constexpr int LPR = CW / 8;      // lanes per row slice
+  constexpr int RPI = 64 / LPR;    // rows per wave instruction
+  constexpr int NI = RB / 4 / RPI; // weight requests per lane
+  constexpr int E4 = CW / 4;       // 16-byte pieces of one split's slice
+  constexpr int TG = 256 / E4;     // thread groups
+  constexpr int SPT = NS / TG;     // splits per thread
+  static_assert(CW == 128 || CW == 256 || CW == 512, "a slice is 1, 2 or 4 q heads");
+  static_assert(NI >= 1 && NI * RPI * 4 == RB && SPT * TG == NS && HEADS * NS <= 256, "row block / split plan");
+  __shared__ float m_s[HEADS * NS], l_s[HEADS * NS], inv_s[HEADS];
+  __shared__ __attribute__((aligned(16))) float red[TG][CW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  Q3A_STAMP_ENTRY(t_entry);
+  const int part = blockIdx.x % n_parts, rb = blockIdx.x / n_parts;
+  const int q0 = part * HEADS;  // first q head of the slice
+  const int e4 = tid % E4, tg = tid / E4, hh = e4 >> 5, d = (e4 & 31) * 4;
+  // 1. statistics: entry (head, split) = tid of the first HEADS * NS threads; the others repeat the last entry (no branch around a load)
+  const int st = tid < HEADS * NS ? tid : HEADS * NS - 1, st_j = st % NS, st_jc = st_j < nsplit ? st_j : nsplit - 1;
+  float st_m = pm[(size_t)(q0 + st / NS) * nsplit + st_jc], st_l = pl[(size_t)(q0 + st / NS) * nsplit + st_jc];
+  // 2. this thread's pieces of the partial rows
+  float4 o[SPT];
+#pragma unroll
+  for (int i = 0; i < SPT; ++i) {
+    const int j = tg + i * TG, jc = j < nsplit ? j : nsplit - 1;
+    o[i] = *reinterpret_cast<const float4*>(po + ((size_t)(q0 + hh) * nsplit + jc) * 128 + d);
+  }
+  __builtin_amdgcn_sched_barrier(0);  // the partials' requests stay in front of the weight stream
+  // 3. the weight stream: rows past N are clamped to the last one and not stored
+  const int row0 = rb * RB + wave * (RB / 4) + lane / LPR;
+  uint4 wq[NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const int row = row0 + i * RPI, rc = row < N ? row : N - 1;
+    wq[i] = ld_stream16(W + (size_t)rc * K + part * CW + (lane % LPR) * 8);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  float bv[NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const int row = row0 + i * RPI;
+    bv[i] = (t.bias && part == 0) ? t.bias[row < N ? row : N - 1] : 0.f;
+  }
+  __builtin_amdgcn_sched_barrier(0);  // every request is issued before anything is waited for
+  Q3A_STAMP_AT(t.stamp, blockIdx.x, 1);  // every load requested
+  Q3A_STAMP_PUT(t.stamp, blockIdx.x, 0, t_entry);  // entry
+  if (st_j >= nsplit) { st_m = -INFINITY; st_l = 0.f; }  // (a stale entry past nsplit may hold anything)
+  if (tid < HEADS * NS) { m_s[tid] = st_m; l_s[tid] = st_l; }
+  __syncthreads();
+  float M = -INFINITY, L = 0.f;
+#pragma unroll
+  for (int j = 0; j < NS; ++j) M = fmaxf(M, m_s[hh * NS + j]);  // finite: split 0 always holds the current token
+#pragma unroll
+  for (int j = 0; j < NS; ++j) L += l_s[hh * NS + j] * __expf(m_s[hh * NS + j] - M);  // empty split: exp(-inf) = 0
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int i = 0; i < SPT; ++i) {
+    const float f = __expf(m_s[hh * NS + tg + i * TG] - M);
+    acc.x += o[i].x * f; acc.y += o[i].y * f; acc.z += o[i].z * f; acc.w += o[i].w * f;
+  }
+  *reinterpret_cast<float4*>(&red[tg][e4 * 4]) = acc;
+  if (tg == 0 && (e4 & 31) == 0) inv_s[hh] = 1.0f / L;
+  __syncthreads();
+  // 4. the merged context of the 8 columns this lane's weights multiply
+  const int c0 = (lane % LPR) * 8;
+  float x[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) x[e] = 0.f;
+#pragma unroll
+  for (int g = 0; g < TG; ++g) {
+    const float4 a0 = *reinterpret_cast<const float4*>(&red[g][c0]), a1 = *reinterpret_cast<const float4*>(&red[g][c0 + 4]);
+    x[0] += a0.x; x[1] += a0.y; x[2] += a0.z; x[3] += a0.w; x[4] += a1.x; x[5] += a1.y; x[6] += a1.z; x[7] += a1.w;
+  }
+  const float inv = inv_s[c0 >> 7];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) x[e] *= inv;
+  Q3A_STAMP_AT(t.stamp, blockIdx.x, 2);  // merged slice in registers
+  float y[NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    float v = row16_sum(dot8(wq[i], x, 0.f));
+    if (LPR >= 32) v = xor16_sum(v);
+    if (LPR >= 64) v = xor32_sum(v);
+    y[i] = v + bv[i];
+  }
+  if (wave == 0) asm volatile("" ::"v"(y[0]));
+  Q3A_STAMP_AT(t.stamp, blockIdx.x, 3);  // weights landed, dot products done
+  if (lane % LPR == 0) {
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      const int row = row0 + i * RPI;
+      if (row < N) y_part[(size_t)part * N + row] = y[i];
+    }
+  }
+  Q3A_STAMP_AT(t.stamp, blockIdx.x, 4);  // stored
 }
 
 // ---- lm_head (mode 3, one sequence, fused final RMSNorm) -------------------------------------------------
@@ -1048,8 +1203,20 @@ void launch1k(const GemvArgs& a, hipStream_t s) {
       else hipLaunchKernelGGL((gemv1_head_kernel<PR, KI>), grid, block, 0, s, GEMV_HEAD_ARGS(a));
       return;
     }
-    if constexpr (KI == 2) { hipLaunchKernelGGL((gemv1_kernel<PR, KI, true, false, 0, true>), grid, block, 0, s, GEMV_PLAIN_ARGS(a)); return; }
-    hipLaunchKernelGGL((gemv1_kernel<PR, KI, true, false>), grid, block, 0, s, GEMV_PLAIN_ARGS(a));
+    if constexpr (KI == 2) {
+      if constexpr (PR == 2) {  // (launch_gemv has checked: mode 2, which runs two rows per wave)
+        if (a.x_parts) {
+          GemvXpTail t{};
+          t.out = a.out; t.x_out = a.x_out; t.fast_math = a.fast_math;
+          Q3A_STAMP_COPY(t, a);
+          hipLaunchKernelGGL((gemv1_xp_kernel<PR, KI>), grid, block, 0, s, a.W, a.x, a.rms_w, a.x_parts, a.bias, a.N, a.K, a.x_nparts, a.eps, t);
+          return;
+        }
+      }
+      hipLaunchKernelGGL((gemv1_kernel<PR, KI, true, false, 0, true>), grid, block, 0, s, GEMV_PLAIN_ARGS(a));
+    } else {  // (an `else`, not a statement behind a return: there the register form was instantiated at KI = 2 as well, three kernels nothing launches)
+      hipLaunchKernelGGL((gemv1_kernel<PR, KI, true, false>), grid, block, 0, s, GEMV_PLAIN_ARGS(a));
+    }
   } else {
     hipLaunchKernelGGL((gemv1_kernel<PR, KI, false, false>), grid, block, 0, s, GEMV_PLAIN_ARGS(a));
   }
@@ -1124,6 +1291,28 @@ const char* launch_lm_head_rescore(const LmHeadPruneArgs& a, int groups, hipStre
   return nullptr;
 }
 
+const char* oproj_head_check(const OprojHeadArgs& a) {
+  if (!a.pm || !a.pl || !a.po || !a.W || !a.y_part || a.N < 1) return "oproj_head: missing buffer";
+  if (a.N > 1024) return "oproj_head: N <= 1024 (the gate / up form that adds the partial vectors exists at K <= 1024)";
+  if (a.nsplit < 1 || a.nsplit > OPROJ_HEAD_MAX_SPLITS) return "oproj_head: 1 .. 16 key splits (more: the merging o_proj of launch_gemv)";
+  if (a.n_parts < 1 || a.K != a.n_parts * 512) return "oproj_head: a slice is 512 columns (two kv heads of two q heads)";
+  return nullptr;
+}
+const char* launch_oproj_head(const OprojHeadArgs& a, hipStream_t s) {
+  if (const char* e = oproj_head_check(a)) return e;
+  OprojHeadTail t{};
+  t.bias = a.bias;
+  Q3A_STAMP_COPY(t, a);
+  // 4 slices x 16-row blocks: 256 workgroups at N = 1024, the only hidden size the chain runs at (the gate / up form behind it
+  // exists at K <= 1024)
+  constexpr int rb = 16;
+  const dim3 grid(a.n_parts * ((a.N + rb - 1) / rb)), block(256);
+#define OPROJ_HEAD_ARGS a.pm, a.pl, a.po, a.W, a.y_part, a.N, a.K, a.nsplit, a.n_parts, t
+  hipLaunchKernelGGL((oproj_head_kernel<512, rb>), grid, block, 0, s, OPROJ_HEAD_ARGS);
+#undef OPROJ_HEAD_ARGS
+  return nullptr;
+}
+
 const char* launch_gemv(const GemvArgs& a0, int NB, hipStream_t s) {
   if (a0.K % 8 != 0) return "gemv: K must be a multiple of 8";
   if (a0.K > 6144) return "gemv: K > 6144 unsupported";
@@ -1135,6 +1324,8 @@ const char* launch_gemv(const GemvArgs& a0, int NB, hipStream_t s) {
   if (a0.attn_po && (a0.K % 128 != 0 || a0.K != a0.attn_heads * 128)) return "gemv: attention-partial input needs K = heads*128";
   if (a0.attn_po && a0.rms_w) return "gemv: attention-partial input cannot be combined with a fused RMSNorm";
   if (a0.attn_po && (NB < 4 ? NB : 4) * a0.attn_heads * a0.attn_nsplit > ATTN_F_MAX) return "gemv: too many attention splits for the LDS scale table";
+  if (a0.x_parts && (NB != 1 || !a0.x || !a0.rms_w || a0.mode != 2 || a0.K > 1024 || a0.x_nparts < 1 || a0.x_nparts > GEMV_X_PARTS_MAX || !a0.x_out))
+    return "gemv: partial vectors are added in the one-sequence norm-fused GLU form at K <= 1024 only (1 .. 4 vectors, x_out set)";
   const int pr = gemv_rows_per_wave(a0);
   const int nb_cap = (int)((64 * 1024) / ((size_t)a0.K * 4));  // rows of x that fit in 64 KiB of LDS
   int done = 0;

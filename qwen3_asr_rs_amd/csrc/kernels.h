@@ -126,6 +126,7 @@ struct Knobs {
   std::atomic<int> eos_run_ahead{1};            // Q3A_EOS_RUN_AHEAD: decode steps kept enqueued ahead of the device in natural-EOS mode.  1: exactly the steps needed are executed; paired with a fixed-N run of the same engine (profiles/r5_eos_run_ahead_ab.txt, two processes): 1 costs +0.03 / +1.24 ms per 100 tokens, 2 costs +2.07 / +1.86 ms (one wasted step + the same launch latency), 3 +1.3 / +1.2, 4 +3.3 / +3.1
   std::atomic<int> skinny_glu_hp3{1};           // Q3A_SKINNY_GLU_HP3: gate/up skinny GEMM as 3 half-pair tiles per workgroup when the pair form has more workgroups than CUs (k_skinny.hip HP; 0 = off, 2 = whenever the shape allows)
   std::atomic<int> lm_head_prune{1};            // Q3A_LM_HEAD_PRUNE: one-sequence decode argmax from an int8 pre-pass + bf16 rescore of the candidate blocks (k_gemv.hip; bit-identical ids)
+  std::atomic<int> oproj_by_head{1};            // Q3A_OPROJ_BY_HEAD: one-sequence decode chain of the default mode (hidden <= 1024) with o_proj per pair of kv heads, its partial vectors added by gate / up, and 32- / 64-key attention splits up to 512 / 1024 keys; 0 = the merging o_proj and 128-key splits, which contexts beyond 2048 keys run anyway (tests compare the two; ids equal, logits differ by fp32 summation order)
   // debug aids (tests): no effect on what a run computes
   std::atomic<int> layer_taps{0};               // Q3A_DEBUG_LAYER_TAPS: with debug taps, raw copies of every encoder / decoder prefill layer's intermediate buffers
   std::atomic<int> poison_attn_partials{0};     // every batch set-up fills the decode attention's split partials (m, l, o) with NaN bytes
@@ -243,9 +244,31 @@ struct GemvArgs {
   const float* attn_pm; const float* attn_pl; const float* attn_po; int attn_nsplit; int attn_heads;
   int attn_fast_exp;            // merge weights with the hardware exponential (default mode) instead of expf
   int fast_math;                // default mode: hardware rsq / exp / rcp in the RMSNorm scale and SiLU of the epilogue (dev.h rstd_of)
+  // optional (one sequence, norm-fused, K <= 1024: the gate / up projection behind launch_oproj_head): the kernel's input is
+  // x + x_parts[0] + ... + x_parts[x_nparts - 1] (rows of K floats, added in ascending order), and workgroup 0 stores that sum to
+  // x_out [K], which must not overlap x or x_parts: every workgroup of the launch reads those
+  const float* x_parts; int x_nparts; float* x_out;
   Q3A_STAMP_FIELD
 };
+constexpr int GEMV_X_PARTS_MAX = 4;
 const char* launch_gemv(const GemvArgs& a, int NB, hipStream_t s);
+
+// o_proj of the one-sequence chain by column slice (k_gemv.hip oproj_head_kernel): the K = n_q * 128 columns are cut into n_parts
+// slices of 512 -- two kv heads of two q heads each (one kv head per slice, 8 partial vectors at the models' shapes, measured 3 us per
+// step slower: profiles/oproj_by_head_headline_ab.txt); workgroup (slice p, row block) merges the flash-decoding partials of the slice's q heads ONCE, through
+// LDS, streams its rows of the slice and stores their dot products to y_part[p][n] -- fp32, no residual (the bias, if any, rides in
+// slice 0).  The consumer adds the n_parts vectors to the residual (GemvArgs::x_parts).  Default arithmetic (hardware exponential).
+struct OprojHeadArgs {
+  const float* pm; const float* pl; const float* po; int nsplit;  // partials of launch_decode_attn: [n_q][nsplit]( [128]), one sequence
+  const uint16_t* W; int N; int K;                                // bf16 [N][K], K = n_q * 128
+  const float* bias;                                              // [N] or null
+  int n_parts;                                                    // K / n_parts = 512 columns (two kv heads of two q heads)
+  float* y_part;                                                  // [n_parts][N]
+  Q3A_STAMP_FIELD
+};
+constexpr int OPROJ_HEAD_MAX_SPLITS = 16;
+const char* oproj_head_check(const OprojHeadArgs& a);  // null when the launch can run on these arguments
+const char* launch_oproj_head(const OprojHeadArgs& a, hipStream_t s);
 constexpr int GEMV_ATTN_MAX_TABLE = 1024;  // min(NB,4) * heads * nsplit must fit (else merge with launch_attn_combine first)
 int gemv_blocks(const GemvArgs& a);        // grid size launch_gemv uses (= number of argmax partials in mode 3)
 int gemv_rows_per_wave(const GemvArgs& a);
@@ -333,7 +356,8 @@ struct DecodeAttnArgs {
   void* kcache; void* vcache;  // this layer
   float* pm; float* pl;       // [S][n_q][nsplit] partial softmax max / sum per key split
   float* po;                   // [S][n_q][nsplit][128] unnormalised partial outputs
-  int nsplit;                  // >= ceil(max_ctx / dattn_keys_per_split(kv_f32))
+  int nsplit;                  // splits launched: every pos < nsplit * keys per split
+  int keys_per_split;          // launch_decode_attn, bf16 cache, GQA group <= 2: 32 or 64 (4 waves per workgroup) or 128; 0 = dattn_keys_per_split
   int n_q, n_kv, max_ctx;
   float scale_div;
   // launch_decode_attn_batched only: when the batch alone fills the chip (S * n_kv workgroups), one workgroup walks ALL
@@ -344,11 +368,12 @@ struct DecodeAttnArgs {
   int trim_prologue;           // batched kernel: 1 = some sequence of the batch is shorter than the two prologue key tiles, trim them to the live rows too
   Q3A_STAMP_FIELD
 };
-#ifndef Q3A_DATTN_SPLIT_KEYS
-#define Q3A_DATTN_SPLIT_KEYS 128  // keys per flash-decoding split of the one-sequence path (A/B builds: 64)
-#endif
-constexpr int DATTN_KEYS_PER_SPLIT_BF16 = Q3A_DATTN_SPLIT_KEYS, DATTN_KEYS_PER_SPLIT_F32 = 128;
+constexpr int DATTN_KEYS_PER_SPLIT_BF16 = 128, DATTN_KEYS_PER_SPLIT_F32 = 128;  // (DecodeAttnArgs::keys_per_split = 0)
 inline int dattn_keys_per_split(bool kv_f32) { return kv_f32 ? DATTN_KEYS_PER_SPLIT_F32 : DATTN_KEYS_PER_SPLIT_BF16; }
+// Keys per split of the one-sequence chain whose o_proj runs per pair of kv heads (launch_oproj_head merges at most OPROJ_HEAD_MAX_SPLITS
+// partials per head): the smallest size that keeps the live splits of a context of `keys` keys (the new token's included) at 16 or
+// fewer; 0: beyond the table, the chain with launch_gemv's merging o_proj runs.
+inline int dattn_fine_keys_per_split(int keys) { return keys <= 512 ? 32 : keys <= 1024 ? 64 : keys <= 2048 ? 128 : 0; }
 const char* launch_decode_attn(const DecodeAttnArgs& a, int S, bool kv_f32, hipStream_t s);
 // one workgroup per (sequence, kv head), online softmax over 128-key tiles, final output written directly (a.out / a.out16)
 const char* launch_decode_attn_batched(const DecodeAttnArgs& a, int S, bool kv_f32, hipStream_t s);

@@ -420,15 +420,76 @@ int32_t q3a_selftest_gemv_launch(int32_t device, int32_t pruned, const uint16_t*
   Q3A_CATCH(nullptr)
 }
 
+int32_t q3a_selftest_oproj_head_launch(int32_t device, const uint16_t* w, int32_t N, int32_t K, const float* bias, const float* attn_pm, const float* attn_pl,
+                                       const float* attn_po, int32_t attn_nsplit, int32_t attn_heads, int32_t n_parts, float* y_part) {
+  Q3A_TRY(nullptr)
+  const char* what = "q3a_selftest_oproj_head_launch";
+  // every index the launch will form is checked here or by the launcher's own check, in front of any copy to the device
+  if (!w || !attn_pm || !attn_pl || !attn_po || !y_part || N < 1 || attn_heads < 1 || attn_nsplit < 1 || n_parts < 1 || K != attn_heads * 128)
+    fail(std::string(what) + ": bad argument");
+  OprojHeadArgs a{};
+  a.pm = attn_pm; a.pl = attn_pl; a.po = attn_po;  // (host pointers: only looked at for null by the check)
+  a.nsplit = attn_nsplit; a.W = w; a.N = N; a.K = K; a.n_parts = n_parts; a.y_part = y_part;
+  KCHK(oproj_head_check(a));
+  use_device(device);
+  const size_t ns = (size_t)attn_heads * attn_nsplit;
+  const DevBuf dW = to_device(w, (size_t)N * K), dPm = to_device(attn_pm, ns), dPl = to_device(attn_pl, ns), dPo = to_device(attn_po, ns * 128);
+  DevBuf dB;
+  if (bias) dB = to_device(bias, (size_t)N);
+  const Guarded dY(y_part, (size_t)n_parts * N * 4);
+  a.pm = dPm.as<float>(); a.pl = dPl.as<float>(); a.po = dPo.as<float>(); a.W = dW.as<uint16_t>(); a.bias = dB.as<float>(); a.y_part = dY.as<float>();
+  KCHK(launch_oproj_head(a, nullptr));
+  finish();
+  dY.fetch(y_part, "partial vectors");
+  Q3A_CATCH(nullptr)
+}
+
+int32_t q3a_selftest_gemv_parts_launch(int32_t device, const uint16_t* w, int32_t N, int32_t K, const float* x, const float* rms_w, float eps,
+                                       const float* bias, const float* x_parts, int32_t n_parts, float* out, float* x_out) {
+  Q3A_TRY(nullptr)
+  const char* what = "q3a_selftest_gemv_parts_launch";
+  if (!w || !x || !rms_w || !x_parts || !out || !x_out || N < 32 || N % 32 != 0 || K < 8 || K % 8 != 0 || K > 1024 || n_parts < 1 || n_parts > GEMV_X_PARTS_MAX)
+    fail(std::string(what) + ": bad argument");
+  use_device(device);
+  const DevBuf dW = to_device(w, (size_t)N * K), dP = to_device(x_parts, (size_t)n_parts * K);
+  // x and the norm weight go on past K with NaN, as in q3a_selftest_gemv_launch (the partial vectors are rows of exactly K floats: a
+  // read past the last one's end would leave the allocation, so the kernel's column clamp is what the K = 1016 case checks there)
+  auto padded = [&](const float* src) {
+    std::vector<float> v(1024 + 8, NAN);
+    memcpy(v.data(), src, (size_t)K * 4);
+    return to_device(v);
+  };
+  const DevBuf dX = padded(x), dG = padded(rms_w);
+  DevBuf dB;
+  if (bias) dB = to_device(bias, (size_t)N);
+  const Guarded dO(out, (size_t)N / 2 * 4), dXo(x_out, (size_t)K * 4);
+  GemvArgs g{};
+  g.x = dX.as<float>(); g.ldx = K; g.rms_w = dG.as<float>(); g.eps = eps; g.W = dW.as<uint16_t>(); g.N = N; g.K = K; g.bias = dB.as<float>();
+  g.mode = 2; g.out = dO.as<float>(); g.ldo = N / 2; g.fast_math = 0;
+  g.x_parts = dP.as<float>(); g.x_nparts = n_parts; g.x_out = dXo.as<float>();
+  KCHK(launch_gemv(g, 1, nullptr));
+  finish();
+  dO.fetch(out, "output"); dXo.fetch(x_out, "summed x");
+  Q3A_CATCH(nullptr)
+}
+
 int32_t q3a_selftest_decode_attn_launch(int32_t device, int32_t kv_f32, const float* qkv, int32_t pos, const float* q_norm, const float* k_norm, float eps,
                                         const float* rope_cur, void* kcache, void* vcache, int32_t n_q, int32_t n_kv, int32_t max_ctx, int32_t nsplit,
                                         float scale_div, float* pm, float* pl, float* po) {
+  return q3a_selftest_decode_attn_split_launch(device, kv_f32, 0, qkv, pos, q_norm, k_norm, eps, rope_cur, kcache, vcache, n_q, n_kv, max_ctx, nsplit,
+                                               scale_div, pm, pl, po);
+}
+
+int32_t q3a_selftest_decode_attn_split_launch(int32_t device, int32_t kv_f32, int32_t keys_per_split, const float* qkv, int32_t pos, const float* q_norm,
+                                              const float* k_norm, float eps, const float* rope_cur, void* kcache, void* vcache, int32_t n_q, int32_t n_kv,
+                                              int32_t max_ctx, int32_t nsplit, float scale_div, float* pm, float* pl, float* po) {
   Q3A_TRY(nullptr)
   const char* what = "q3a_selftest_decode_attn_launch";
   if (!qkv || !q_norm || !k_norm || !rope_cur || !kcache || !vcache || !pm || !pl || !po || n_q < 1 || n_kv < 1 || n_q % n_kv != 0 || max_ctx < 1 ||
       nsplit < 1 || !(scale_div > 0.f))
     fail(std::string(what) + ": bad argument");
-  const int keys = dattn_keys_per_split(kv_f32 != 0);
+  if (keys_per_split != 0 && keys_per_split != 32 && keys_per_split != 64 && keys_per_split != 128) fail(std::string(what) + ": 32, 64 or 128 keys per split (0: the default)");
+  const int keys = keys_per_split ? keys_per_split : dattn_keys_per_split(kv_f32 != 0);
   if (pos < 0 || pos >= max_ctx || pos >= nsplit * keys) fail(std::string(what) + ": pos outside the cache or beyond the last split");
   use_device(device);
   const size_t eb = kv_f32 ? 4 : 2, n_cache = (size_t)n_kv * max_ctx * 128, ns = (size_t)n_q * nsplit;
@@ -438,7 +499,7 @@ int32_t q3a_selftest_decode_attn_launch(int32_t device, int32_t kv_f32, const fl
   DecodeAttnArgs a{};
   a.qkv = dQkv.as<float>(); a.pos = dPos.as<int>(); a.q_norm = dQn.as<float>(); a.k_norm = dKn.as<float>(); a.eps = eps; a.rope_cur = dRope.as<float>();
   a.kcache = dK.as<void>(); a.vcache = dV.as<void>(); a.pm = dPm.as<float>(); a.pl = dPl.as<float>(); a.po = dPo.as<float>();
-  a.nsplit = nsplit; a.n_q = n_q; a.n_kv = n_kv; a.max_ctx = max_ctx; a.scale_div = scale_div;
+  a.nsplit = nsplit; a.keys_per_split = keys_per_split; a.n_q = n_q; a.n_kv = n_kv; a.max_ctx = max_ctx; a.scale_div = scale_div;
   KCHK(launch_decode_attn(a, 1, kv_f32 != 0, nullptr));
   finish();
   dK.fetch(kcache, "key cache"); dV.fetch(vcache, "value cache"); dPm.fetch(pm, "split maxima"); dPl.fetch(pl, "split sums"); dPo.fetch(po, "split outputs");
