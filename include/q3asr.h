@@ -703,6 +703,33 @@ int32_t q3a_selftest_oproj_head_launch(int32_t device, const uint16_t* w, int32_
  * whole buffer out). */
 int32_t q3a_selftest_gemv_parts_launch(int32_t device, const uint16_t* w, int32_t N, int32_t K, const float* x, const float* rms_w, float eps,
                                        const float* bias, const float* x_parts, int32_t n_parts, float* out, float* x_out);
+/* ONE launch_skinny call (the batched decode step's GEMM, 1 .. 32 sequences; skinny_init() first) on the caller's data, as
+ * q3a_selftest_gemm_launch: tests/batched_decode_ref.py compares in float64.  w bf16 [N][K], K % 32 == 0, K <= 6144.  The x source is exactly
+ * one of: x fp32 [S][ldx] with rms_w [K] (fused RMSNorm with eps) or without; x16 bf16 row-major [S][ldx] or, with x16_frag, in fragment
+ * order; xw16f (pre-normalised, fragment order) with ss_parts [ss_nparts][32].  A buffer in fragment order holds 32 sequences: the caller
+ * gives all 32 * K elements (32 * cols rounded up to whole 32-column steps for an output), so the slots of sequences >= S are its own, as
+ * are the ss_parts columns >= S.  On the device fp32 x and rms_w go on past their end with NaN.  bias [N] nullable; mode 0 store, 1 out =
+ * resid + y (resid [S][ldo]), 2 GLU (N / 2 output columns).  Outputs, each sentinel in / whole buffer out between guard zones: out fp32
+ * [32][ldo] (rows >= S stay the caller's), or in mode 2 out16 bf16 [32][ldo] / fragment order (out16_frag); with next_w [N] (mode 1) also next_xw16f (fragment order) and
+ * next_ss [N / 16 rounded up, or N / 8 with quarter workgroups][32].  flags: 1 split (hi + lo activations), 2 fast_math, 4 qsplit (quarter
+ * workgroups), 8 in place (resid null: the residual is what out holds, one device buffer for both, as the engine calls it).  glu_hp3 and
+ * n_cu as SkinnyArgs.  form [11] receives the instantiation that ran: split, TILES, SH, XMODE, UNR, WLDS, QS, PALIAS, HP, grid size, dynamic
+ * LDS bytes. */
+int32_t q3a_selftest_skinny_launch(int32_t device, const uint16_t* w, int32_t N, int32_t K, int32_t S, const float* x, int32_t ldx, const float* rms_w,
+                                   const uint16_t* x16, int32_t x16_frag, const uint16_t* xw16f, const float* ss_parts, int32_t ss_nparts, float eps,
+                                   const float* bias, int32_t mode, const float* resid, float* out, uint16_t* out16, int32_t out16_frag, int32_t ldo,
+                                   const float* next_w, uint16_t* next_xw16f, float* next_ss, int32_t flags, int32_t glu_hp3, int32_t n_cu,
+                                   int32_t* form);
+/* The decode attention of S sequences with ragged pos [S]: launch_decode_attn_batched (split_path = 0, trim_prologue given), or
+ * launch_decode_attn with nsplit splits of keys_per_split keys (0: the default) followed by launch_attn_combine (split_path = 1).  qkv
+ * [S][(n_q + 2 n_kv) * 128], rope_cur [S][128], kcache / vcache [S][n_kv][max_ctx][128] (bf16 bits, or fp32 with kv_f32).  out_form 0: out
+ * fp32 [S][n_q * 128]; 1: bf16 row-major; 2: bf16 in fragment order (32 sequences' room; more than 32 sequences are refused).  Outputs,
+ * each sentinel in / whole buffer out: the caches, out, and on the split path pm / pl [S][n_q][nsplit] and po [S][n_q][nsplit][128]
+ * (null on the batched path). */
+int32_t q3a_selftest_batched_attn_launch(int32_t device, int32_t kv_f32, int32_t split_path, int32_t S, const float* qkv, const int32_t* pos,
+                                         const float* q_norm, const float* k_norm, float eps, const float* rope_cur, void* kcache, void* vcache,
+                                         int32_t n_q, int32_t n_kv, int32_t max_ctx, float scale_div, int32_t trim_prologue, int32_t nsplit,
+                                         int32_t keys_per_split, int32_t out_form, void* out, float* pm, float* pl, float* po);
 /* Rows [0, M1) of an M x N bf16 GEMM that launch_gemm256 gives to the 256 x 256 kernel when it hands the trailing rows to the small
  * tiles (wave quantisation; 0: no split).  Host arithmetic, no device needed. */
 int32_t q3a_gemm256_split_rows(int32_t M, int32_t N);

@@ -382,9 +382,16 @@ constexpr size_t sk_dyn_lds_max(int tiles, int sh) {
   return 160 * 1024 - sizeof(float) * (SK_WAVES * tiles * sh * 16 * 17 + SK_WAVES * sh * 16) - 2048;
 }
 
+// Every launch goes through here: the instantiation that runs and the one skinny_last_form() reports are the same template arguments.
+thread_local SkinnyForm last_form{};
+template <bool SPLIT, int TILES, int SH, int XMODE, int UNR, bool WLDS, bool QS = false, bool PALIAS = false, bool HP = false>
+void launch_form(const SkinnyArgs& a, dim3 grid, size_t dyn_lds, hipStream_t s) {
+  last_form = SkinnyForm{SPLIT, TILES, SH, XMODE, UNR, WLDS, QS, PALIAS, HP, (int)grid.x, (int)dyn_lds};
+  hipLaunchKernelGGL((skinny_kernel<SPLIT, TILES, SH, XMODE, UNR, WLDS, QS, PALIAS, HP>), grid, dim3(SK_WAVES * 64), dyn_lds, s, a);
+}
+
 template <bool SPLIT, int TILES, int SH, int XMODE, int UNR>
 void launch_k(const SkinnyArgs& a, dim3 grid, hipStream_t s) {
-  const dim3 block(SK_WAVES * 64);
   // weights through LDS when the wave's slice is exactly UNR steps and the image fits next to the reduction buffer
   const int steps = a.K / 32, per = (steps + SK_WAVES - 1) / SK_WAVES;
   const size_t wbytes = (size_t)SK_WAVES * TILES * (UNR / 2) * 2048;
@@ -399,7 +406,7 @@ void launch_k(const SkinnyArgs& a, dim3 grid, hipStream_t s) {
     const bool balances = (int)grid.x > n_cu_hp && inter / 24 <= n_cu_hp;
     if (shape_ok && (a.glu_hp3 == 2 || (a.glu_hp3 == 1 && balances))) {
       const size_t wb = (size_t)SK_WAVES * 3 * 2 * 2048;  // 8 waves x 3 tiles x 2 k columns (4 steps) x 16 rows x 128 B
-      hipLaunchKernelGGL((skinny_kernel<false, 3, SH, 3, 4, true, false, true, true>), dim3(inter / 24), block, wb, s, a);
+      launch_form<false, 3, SH, 3, 4, true, false, true, true>(a, dim3(inter / 24), wb, s);
       return;
     }
   }
@@ -410,7 +417,7 @@ void launch_k(const SkinnyArgs& a, dim3 grid, hipStream_t s) {
     const int n_cu = a.n_cu > 0 ? a.n_cu : 256;
     if (wlds_on && (int)grid.x > n_cu && per == UNR && steps % per == 0) {
       const size_t wb2 = (size_t)SK_WAVES * TILES * (UNR / 4) * 2048;
-      hipLaunchKernelGGL((skinny_kernel<SPLIT, TILES, SH, XMODE, UNR / 2, true, false, true>), grid, block, wb2, s, a);
+      launch_form<SPLIT, TILES, SH, XMODE, UNR / 2, true, false, true>(a, grid, wb2, s);
       return;
     }
   }
@@ -419,11 +426,11 @@ void launch_k(const SkinnyArgs& a, dim3 grid, hipStream_t s) {
     // down projection 14.8 us for 25 MB)
     if (wlds_on && per % UNR == 0 && steps % per == 0 && wbytes <= sk_dyn_lds_max(TILES, SH)) {
       // dynamic LDS above the 64 KiB default: the attribute is set by skinny_init() (not here: this may run under capture)
-      hipLaunchKernelGGL((skinny_kernel<SPLIT, TILES, SH, XMODE, UNR, true>), grid, block, wbytes, s, a);
+      launch_form<SPLIT, TILES, SH, XMODE, UNR, true>(a, grid, wbytes, s);
       return;
     }
   }
-  hipLaunchKernelGGL((skinny_kernel<SPLIT, TILES, SH, XMODE, UNR, false>), grid, block, 0, s, a);
+  launch_form<SPLIT, TILES, SH, XMODE, UNR, false>(a, grid, 0, s);
 }
 template <bool SPLIT, int XMODE, int UNR>
 void launch_u(const SkinnyArgs& a, hipStream_t s) {
@@ -431,8 +438,7 @@ void launch_u(const SkinnyArgs& a, hipStream_t s) {
     if (a.qsplit) {  // validated by launch_skinny: mode 1, fragment-order x, N % 64 == 0, whole passes of UNR steps
       SkinnyArgs q = a;
       q.qs_halves = a.S > 16 ? 2 : 1;
-      const dim3 grid((a.N / 8) * q.qs_halves), block(SK_WAVES * 64);
-      hipLaunchKernelGGL((skinny_kernel<false, 1, 1, 2, UNR, true, true>), grid, block, (size_t)SK_WAVES * (UNR / 2) * 1024, s, q);
+      launch_form<false, 1, 1, 2, UNR, true, true>(q, dim3((a.N / 8) * q.qs_halves), (size_t)SK_WAVES * (UNR / 2) * 1024, s);
       return;
     }
   }
@@ -508,7 +514,10 @@ const char* skinny_init() {
   return e == hipSuccess ? nullptr : "skinny gemm: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed";
 }
 
+SkinnyForm skinny_last_form() { return last_form; }
+
 const char* launch_skinny(const SkinnyArgs& a, bool split, hipStream_t s) {
+  last_form = SkinnyForm{};
   if (a.S <= 0) return nullptr;
   if (a.S > 32) return "skinny gemm: at most 32 sequences";
   if (a.K % 32 != 0 || a.ldx % 8 != 0) return "skinny gemm: K must be a multiple of 32, ldx of 8";

@@ -506,6 +506,114 @@ int32_t q3a_selftest_decode_attn_split_launch(int32_t device, int32_t kv_f32, in
   Q3A_CATCH(nullptr)
 }
 
+int32_t q3a_selftest_skinny_launch(int32_t device, const uint16_t* w, int32_t N, int32_t K, int32_t S, const float* x, int32_t ldx, const float* rms_w,
+                                   const uint16_t* x16, int32_t x16_frag, const uint16_t* xw16f, const float* ss_parts, int32_t ss_nparts, float eps,
+                                   const float* bias, int32_t mode, const float* resid, float* out, uint16_t* out16, int32_t out16_frag, int32_t ldo,
+                                   const float* next_w, uint16_t* next_xw16f, float* next_ss, int32_t flags, int32_t glu_hp3, int32_t n_cu,
+                                   int32_t* form) {
+  Q3A_TRY(nullptr)
+  const char* what = "q3a_selftest_skinny_launch";
+  const bool split = flags & 1, fast = flags & 2, qsplit = flags & 4, inplace = flags & 8;
+  // every index the launch will form is checked here or by launch_skinny's own check, in front of any copy to the device
+  if (!w || !form || (flags & ~15) || N < 1 || K < 32 || K % 32 != 0 || K > 6144 || S < 1 || S > 32 || mode < 0 || mode > 2 || glu_hp3 < 0 || glu_hp3 > 2 || n_cu < 0)
+    fail(std::string(what) + ": bad argument");
+  if ((x != nullptr) + (x16 != nullptr) + (xw16f != nullptr) != 1) fail(std::string(what) + ": exactly one of x, x16 and xw16f");
+  if (rms_w && !x) fail(std::string(what) + ": the fused norm takes fp32 x");
+  if (xw16f && (!ss_parts || ss_nparts < 1 || ss_nparts > 4096)) fail(std::string(what) + ": xw16f needs ss_parts [ss_nparts][32]");
+  if ((x || (x16 && !x16_frag)) && (ldx < K || ldx % 8 != 0)) fail(std::string(what) + ": ldx below K or no multiple of 8");
+  if (mode == 2 && N % 32 != 0) fail(std::string(what) + ": GLU needs N % 32 == 0");
+  const int cols = mode == 2 ? N / 2 : N;
+  if ((out != nullptr) == (out16 != nullptr) || (out16 && mode != 2) || ldo < cols) fail(std::string(what) + ": one of out / out16 (GLU only) with ldo >= its columns");
+  if (inplace ? (mode != 1 || resid || !out) : ((mode == 1) != (resid != nullptr))) fail(std::string(what) + ": the residual goes with mode 1 (in place: it is `out`)");
+  if (next_w && (mode != 1 || !next_xw16f || !next_ss)) fail(std::string(what) + ": next_w needs mode 1, next_xw16f and next_ss");
+  if (qsplit && (split || mode != 1 || !x16 || !x16_frag || N % 64 != 0 || (K / 32) % 8 != 0)) fail(std::string(what) + ": quarter workgroups need mode 1, fragment-order x16, N % 64 == 0, K % 256 == 0");
+  use_device(device);
+  KCHK(skinny_init());
+  const size_t Sz = S, frag_x = (size_t)32 * K, frag_cols = (size_t)32 * ((cols + 31) / 32 * 32);
+  const DevBuf dW = to_device(w, (size_t)N * K);
+  // fp32 x and the norm weight go on past their end with NaN, as in q3a_selftest_gemv_launch
+  auto padded = [&](const float* src, size_t n) {
+    std::vector<float> v(n + 6144 + 8, NAN);
+    memcpy(v.data(), src, n * 4);
+    return to_device(v);
+  };
+  DevBuf dX, dG, dX16, dXw, dSs, dB, dR, dNw;
+  if (x) dX = padded(x, Sz * ldx);
+  if (rms_w) dG = padded(rms_w, (size_t)K);
+  if (x16) dX16 = to_device(x16, x16_frag ? frag_x : Sz * ldx);
+  if (xw16f) { dXw = to_device(xw16f, frag_x); dSs = to_device(ss_parts, (size_t)ss_nparts * 32); }
+  if (bias) dB = to_device(bias, (size_t)N);
+  if (resid) dR = to_device(resid, Sz * ldo);
+  if (next_w) dNw = to_device(next_w, (size_t)N);
+  Guarded gO, gO16, gNx, gNs;
+  // (row-major outputs have 32 rows whatever S is: a store to a row >= S lands in the caller's sentinel, where it is seen)
+  if (out) gO = Guarded(out, (size_t)32 * ldo * 4);
+  if (out16) gO16 = Guarded(out16, (out16_frag ? frag_cols : (size_t)32 * ldo) * 2);
+  const size_t ss_rows = qsplit ? (size_t)N / 8 : ((size_t)N + 15) / 16;
+  if (next_w) { gNx = Guarded(next_xw16f, frag_cols * 2); gNs = Guarded(next_ss, ss_rows * 32 * 4); }
+  SkinnyArgs a{};
+  a.x = dX.as<float>(); a.ldx = (x || (x16 && !x16_frag)) ? ldx : K; a.S = S; a.x16 = dX16.as<uint16_t>(); a.x16_frag = x16_frag ? 1 : 0; a.out16_frag = out16_frag ? 1 : 0;
+  a.rms_w = dG.as<float>(); a.eps = eps; a.W = dW.as<uint16_t>(); a.N = N; a.K = K; a.bias = dB.as<float>(); a.mode = mode;
+  a.out = gO.as<float>(); a.ldo = ldo; a.out16 = gO16.as<uint16_t>(); a.resid = inplace ? gO.as<float>() : dR.as<float>();
+  a.xw16f = dXw.as<uint16_t>(); a.ss_parts = dSs.as<float>(); a.ss_nparts = xw16f ? ss_nparts : 0;
+  a.next_w = dNw.as<float>(); a.next_xw16f = gNx.as<uint16_t>(); a.next_ss = gNs.as<float>();
+  a.qsplit = qsplit ? 1 : 0; a.glu_hp3 = glu_hp3; a.n_cu = n_cu; a.fast_math = fast ? 1 : 0;
+  KCHK(launch_skinny(a, split, nullptr));
+  const SkinnyForm f = skinny_last_form();
+  finish();
+  const int rep[11] = {f.split, f.tiles, f.sh, f.xmode, f.unr, f.wlds, f.qs, f.palias, f.hp, f.grid, f.dyn_lds};
+  memcpy(form, rep, sizeof rep);
+  if (out) gO.fetch(out, "output");
+  if (out16) gO16.fetch(out16, "bf16 output");
+  if (next_w) { gNx.fetch(next_xw16f, "next_xw16f"); gNs.fetch(next_ss, "next_ss"); }
+  Q3A_CATCH(nullptr)
+}
+
+int32_t q3a_selftest_batched_attn_launch(int32_t device, int32_t kv_f32, int32_t split_path, int32_t S, const float* qkv, const int32_t* pos,
+                                         const float* q_norm, const float* k_norm, float eps, const float* rope_cur, void* kcache, void* vcache,
+                                         int32_t n_q, int32_t n_kv, int32_t max_ctx, float scale_div, int32_t trim_prologue, int32_t nsplit,
+                                         int32_t keys_per_split, int32_t out_form, void* out, float* pm, float* pl, float* po) {
+  Q3A_TRY(nullptr)
+  const char* what = "q3a_selftest_batched_attn_launch";
+  if (!qkv || !pos || !q_norm || !k_norm || !rope_cur || !kcache || !vcache || !out || S < 1 || S > 64 || n_q < 1 || n_kv < 1 || n_q % n_kv != 0 ||
+      max_ctx < 1 || !(scale_div > 0.f) || out_form < 0 || out_form > 2 || (trim_prologue != 0 && trim_prologue != 1))
+    fail(std::string(what) + ": bad argument");
+  int keys = 0;
+  if (split_path) {
+    if (!pm || !pl || !po || nsplit < 1) fail(std::string(what) + ": the split path needs nsplit and the three partial arrays");
+    if (keys_per_split != 0 && keys_per_split != 32 && keys_per_split != 64 && keys_per_split != 128) fail(std::string(what) + ": 32, 64 or 128 keys per split (0: the default)");
+    keys = keys_per_split ? keys_per_split : dattn_keys_per_split(kv_f32 != 0);
+  } else if (pm || pl || po) fail(std::string(what) + ": the batched kernel writes no partials");
+  for (int s = 0; s < S; ++s)
+    if (pos[s] < 0 || pos[s] >= max_ctx || (split_path && pos[s] >= nsplit * keys)) fail(std::string(what) + ": a pos outside the cache or beyond the last split");
+  use_device(device);
+  const size_t Sz = S, eb = kv_f32 ? 4 : 2, n_cache = Sz * n_kv * max_ctx * 128, ns = Sz * n_q * (split_path ? nsplit : 0), hd = (size_t)n_q * 128;
+  // (fragment order holds 32 sequences; with more the launcher refuses before anything runs, and the buffer is sized for the row-major form)
+  const size_t n_out = out_form == 2 && S <= 32 ? 32 * hd : Sz * hd;
+  const DevBuf dQkv = to_device(qkv, Sz * (n_q + 2 * n_kv) * 128), dQn = to_device(q_norm, 128), dKn = to_device(k_norm, 128);
+  const DevBuf dRope = to_device(rope_cur, Sz * 128), dPos = to_device(pos, Sz);
+  const Guarded dK(kcache, n_cache * eb), dV(vcache, n_cache * eb), dO(out, n_out * (out_form ? 2 : 4));
+  Guarded dPm, dPl, dPo;
+  if (split_path) { dPm = Guarded(pm, ns * 4); dPl = Guarded(pl, ns * 4); dPo = Guarded(po, ns * 128 * 4); }
+  DecodeAttnArgs a{};
+  a.qkv = dQkv.as<float>(); a.pos = dPos.as<int>(); a.q_norm = dQn.as<float>(); a.k_norm = dKn.as<float>(); a.eps = eps; a.rope_cur = dRope.as<float>();
+  a.kcache = dK.as<void>(); a.vcache = dV.as<void>(); a.n_q = n_q; a.n_kv = n_kv; a.max_ctx = max_ctx; a.scale_div = scale_div;
+  if (split_path) {
+    a.pm = dPm.as<float>(); a.pl = dPl.as<float>(); a.po = dPo.as<float>(); a.nsplit = nsplit; a.keys_per_split = keys_per_split;
+    if (out_form == 2 && S > 32) fail("attn_combine: fragment order holds at most 32 sequences");  // (its launcher's own refusal, in front of the first launch)
+    KCHK(launch_decode_attn(a, S, kv_f32 != 0, nullptr));
+    KCHK(launch_attn_combine(a.pm, a.pl, a.po, nsplit, S, n_q, out_form ? nullptr : dO.as<float>(), nullptr, out_form ? dO.as<uint16_t>() : nullptr, out_form == 2));
+  } else {
+    if (out_form) { a.out16 = dO.as<uint16_t>(); a.out_frag = out_form == 2; } else a.out = dO.as<float>();
+    a.trim_prologue = trim_prologue;
+    KCHK(launch_decode_attn_batched(a, S, kv_f32 != 0, nullptr));
+  }
+  finish();
+  dK.fetch(kcache, "key cache"); dV.fetch(vcache, "value cache"); dO.fetch(out, "context");
+  if (split_path) { dPm.fetch(pm, "split maxima"); dPl.fetch(pl, "split sums"); dPo.fetch(po, "split outputs"); }
+  Q3A_CATCH(nullptr)
+}
+
 int32_t q3a_selftest_draft_accept(int32_t device, int32_t S, const int32_t* draft_ids, const int32_t* draft_off, const int32_t* prompt_lens,
                                   const int32_t* top_ids, const float* top_lp, int32_t out_stride, const uint16_t* embed, int32_t V, int32_t H,
                                   const float* norm_w, int32_t group_size, const float* cos_t, const float* sin_t, int32_t max_pos,
