@@ -247,7 +247,7 @@ int32_t q3a_measure_peaks(int32_t device, int32_t reps, q3a_peaks* out);
  * workspace buffers of ALL engines of the process hold right now -- tables, activations, KV caches, the int8 lm_head copy, taps; not
  * the weight arenas) and "graph_captures" (int32: decode-step graphs captured over the engine's life; a replay adds none) are readable
  * without debug taps; so are the settings "logit_bias", "logit_bias_stats", "sampling" and "repetition" and the counters "draft_stats"
- * (their own sections below). */
+ * (their own sections below), and the setting "sequence_bias" (its own section below). */
 int32_t q3a_debug_read(q3a_engine* e, const char* name, void* dst, uint64_t bytes, uint64_t* actual);
 
 /* ---- pipeline shell: host-only helpers around the hot path -------------- */
@@ -383,7 +383,8 @@ int32_t q3a_score_batch_ptrs(q3a_engine* e, const float* const* pcm16k, const in
  * q3a_score* stays unbiased and bit-identical.
  * Refused (q3a_last_error; the engine stays usable): a draft id < 0 or >= vocabulary; a draft id equal to <|audio_pad|> (151676) or to
  * either EOS id (151643, 151645: a draft ends where its ids end); n > max_new (the engine's max_new_tokens in the stage form); an aligner
- * engine; sampling or repetition control set (their choices are not an argmax of the row alone); a live beam search.
+ * engine; sampling or repetition control set (their choices are not an argmax of the row alone); a live beam search.  (Likewise a
+ * sequence bias: its own section below.)
  * q3a_debug_read(e, "draft_stats", ..) (int32 [1 + rounds]: rounds run by the last draft call, then the rows prefilled in each).
  * q3a_stage_timings reports the prefill (every round, head and accept included) and the decode steps actually run.
  * Out of scope: appending rows to an existing KV cache (the prefill attention keeps q_len = kv_len: every round is a full prefill);
@@ -503,7 +504,7 @@ int32_t q3a_selftest_kv_reorder(int32_t device, void* cache, int32_t elem_bytes,
  * Readable without debug taps: q3a_debug_read(e, "logit_bias", ..) (fp32 [vocab] as the device holds it, zeros when off) and
  * "logit_bias_stats" (int32 [2]: active 0 / 1, finite entries).
  * Out of scope: per-utterance biases inside one batch (a [S][vocab] operand: 19 MB per step at 32 sequences); multi-token phrase
- * constraints; a bias inside q3a_score*.  (Sampling, and the history-dependent processors -- repetition penalty, no-repeat n-gram:
+ * constraints (multi-token sequences: their own section below); a bias inside q3a_score*.  (Sampling, and the history-dependent processors -- repetition penalty, no-repeat n-gram:
  * their own sections below.) */
 
 /* b = default_bias everywhere (0 or -INFINITY only), then b[ids[i]] = bias[i].  n = 0 with default_bias = 0 clears the bias: the
@@ -591,6 +592,77 @@ int32_t q3a_set_repetition(q3a_engine* e, float repetition_penalty, int32_t no_r
  * [S][V] (l''), out_ids [S] (argmax l'') and out_lp [S] (log_softmax(l'')[id]); any of the three may be null. */
 int32_t q3a_selftest_repeat(int32_t device, const float* logits, int32_t S, int32_t V, const int32_t* hist, int32_t stride,
                             const int32_t* lens, float p, int32_t n, float* out_logits, int32_t* out_ids, float* out_lp);
+
+/* ---- sequence bias: hotword boosts and banned phrases inside the decode step -------------------------------------------------------------
+ * The multi-token constraint of generate(): a list of (token sequence, bias) pairs, the bias added to the sequence's last token
+ * whenever the ids generated so far end in the rest of the sequence -- applied on the device to the stored logits of every step of the
+ * GENERATION paths, between the lm_head and the choice of the id.  A banned phrase is an entry with a bias of -inf; a hotword boost is
+ * an entry for every prefix of the phrase (q3a_hotword_sequences).  An engine holds a list of E entries; an entry is a token sequence
+ * q_0 .. q_{L-1} with 1 <= L <= 32 and a bias that is finite or -inf.  l' are the (biased) fp32 logits of sequence s at a step.
+ *   History.  t = min(step_count[s], max_new), h = out_ids[s][0 .. t): the same words and the same exclusions as in the repetition
+ *     section.  The prompt is not history.  A token forced with q3a_set_next_tokens is not history.
+ *   Firing.  An entry of length L fires on a row iff t >= L - 1 and h[t - L + 1 .. t) equals q_0 .. q_{L-2}.  A one-token entry
+ *     always fires, also at t = 0, which is the id the prefill produces.
+ *   Sum.  For a target id v, the entries are those whose last token is v.  acc = 0.0f; the bias of the one-token entry on v is added
+ *     first, if there is one (it fires); then the bias of each longer firing entry, in the order the caller gave them; each addition is
+ *     one fp32 add.  If at least one entry fired, l''_v = l'_v + acc, one more fp32 add.  Ids that no entry fired on are not touched.
+ *     -inf stays -inf and never yields NaN: +inf and NaN biases are refused.
+ *   Pinned meaning: for every entry that fires or could fire, bit for bit what HuggingFace's
+ *     SequenceBiasLogitsProcessor(sequence_bias = the entries as a dict in the caller's order) computes on input_ids = [x] ++ h for an
+ *     arbitrary id x.  The one extra column in front removes HuggingFace's len(sequence) > context quirk, which ignores an L-token
+ *     sequence at t = L - 1; here the sequence fires.  NoBadWordsLogitsProcessor is the same processor with every bias -inf.  One
+ *     exception: a logit of -0.0 that nothing fired on stays -0.0, where HuggingFace's scores + 0 turns it into +0.0.
+ *   Order with the other processors: logit bias (inside the head), sequence bias, repetition penalty, n-gram ban, then argmax or
+ *     sampler -- HuggingFace's generate() order for finite biases; a -inf is invariant under the penalty and the ban, so the bad-words
+ *     use gives the same row wherever it stands.
+ *   Everything downstream is defined on l'' by the rules it already has: the greedy id is the larger value, then the smaller id; the
+ *     sampler's kept set and noise; q3a_fetch_logprobs = log_softmax(l'')[id]; logits_out of q3a_prefill / q3a_decode_step and the
+ *     "logits" tap hold l''.
+ * An empty list (n = 0) is off: the engine is back on the launches, graphs, ids, log-probabilities and pruned-pass counts of one that
+ * never had the setting.  While it is on, every lm_head form stores its logits and the one-sequence pruned argmax is not taken, as
+ * under repetition control.
+ * State: the list persists until changed.  q3a_set_sequence_bias drops the decode state as q3a_set_repetition does.  On / off is part
+ * of the captured step's signature; the tables and their counts live in a device buffer of fixed capacity that the kernel reads, so
+ * another list replays the same graph.  The buffer is allocated at the first non-empty set and freed with the engine: "device_bytes"
+ * is level across set / clear cycles after the first.
+ * Applies to: q3a_prefill (next_ids, last_logits_out), q3a_decode_step, q3a_run_resident, q3a_transcribe_batch[_ptrs],
+ * q3a_fetch_logprobs.  Group runs: set it on each q3a_group_engine handle.  q3a_score* and q3a_align* never see it: bit-identical
+ * with it on and off.
+ * Limits: E <= 4096; L <= 32; at most 65536 ids over all entries.
+ * Refused (q3a_last_error; the engine stays usable): an id < 0 or >= vocab; an empty sequence, or L > 32; more entries or ids than
+ * the limits; the same sequence twice; a NaN or +inf bias; an aligner engine; q3a_beam_begin / q3a_beam_search_batch_ptrs while it is
+ * on (beam slots reorder their histories); q3a_prefill_draft / q3a_transcribe_draft_batch_ptrs while it is on (the choice is not an
+ * argmax of the row alone); a -inf entry together with an allow-list logit bias (default_bias -inf) whose finite entries are no more
+ * than the distinct targets of -inf entries plus, with an n-gram ban on, max_new_tokens -- the only way a row could run out of finite
+ * logits -- refused by whichever of q3a_set_sequence_bias / q3a_set_logit_bias / q3a_set_repetition comes second.
+ * Readable: q3a_debug_read(e, "sequence_bias", ..) (int32 [4]: on 0 / 1, entries, ids over all entries, distinct targets).
+ * Out of scope: per-utterance lists inside one batch; subtracting a partial boost when a phrase is abandoned; sequence bias inside
+ * beam search or under a draft (so not in StreamingTranscriber); matching over the prompt; boost values tuned on real weights (none
+ * has been: q3a_hotword_sequences takes the boost from the caller). */
+
+/* ids: the entries' ids one after the other (sum of lens), lens [n], bias [n].  n = 0 clears the list. */
+int32_t q3a_set_sequence_bias(q3a_engine* e, const int32_t* ids, const int32_t* lens, const float* bias, int32_t n);
+/* The kernel on its own (no model), followed by the argmax partials and their merge as the engine enqueues them: logits [S][V] host
+ * fp32, hist [S][stride] with lens [S] ids of history each (0 <= lens[s] <= stride, every id inside the vocabulary), the list as
+ * q3a_set_sequence_bias takes it -> out_logits [S][V] (l''), out_ids [S] (argmax l'') and out_lp [S] (log_softmax(l'')[id]); any of
+ * the three may be null.  The arguments are validated before a device is looked for. */
+int32_t q3a_selftest_seqbias(int32_t device, const float* logits, int32_t S, int32_t V, const int32_t* hist, int32_t stride, const int32_t* lens,
+                             const int32_t* seq_ids, const int32_t* seq_lens, const float* seq_bias, int32_t n, float* out_logits,
+                             int32_t* out_ids, float* out_lp);
+/* Host helpers, no engine.  All three return a list as q3a_set_sequence_bias takes it: *n_ids / *n = ids and entries needed; ids
+ * [ids_cap], lens [cap] and bias [cap] are written only when both capacities hold the whole list (call once with 0 / 0 to size).
+ * q3a_parse_sequence_bias: lines "bias id id ..." ('#' comments, blank lines, "-inf" accepted).  Refused (q3a_last_error(NULL)): a
+ *   malformed line, a NaN / +inf bias, more than 32 ids on a line, a sequence given twice.
+ * q3a_hotword_sequences: for each phrase both tokenisations, encode(phrase) and encode(" " + phrase); for each tokenisation
+ *   p_0 .. p_{L-1} the entries (p_0 .. p_j), j = 1 .. L-1, with bias `boost`, and, when start_boost != 0, also (p_0) with start_boost
+ *   (so a phrase that is ONE token is boosted by start_boost alone).  Equal sequences are merged, keeping the larger bias.  A phrase
+ *   whose tokenisation exceeds 32 ids is refused by name; so are an empty phrase and a boost that is not finite.
+ * q3a_banned_sequences: both tokenisations of each phrase, whole, at -inf. */
+int32_t q3a_parse_sequence_bias(const char* text, int32_t* ids, int32_t ids_cap, int32_t* lens, float* bias, int32_t cap, int32_t* n_ids, int32_t* n);
+int32_t q3a_hotword_sequences(const q3a_tokenizer* t, const char* const* phrases, int32_t n_phrases, float boost, float start_boost, int32_t* ids,
+                              int32_t ids_cap, int32_t* lens, float* bias, int32_t cap, int32_t* n_ids, int32_t* n);
+int32_t q3a_banned_sequences(const q3a_tokenizer* t, const char* const* phrases, int32_t n_phrases, int32_t* ids, int32_t ids_cap, int32_t* lens,
+                             float* bias, int32_t cap, int32_t* n_ids, int32_t* n);
 
 /* A/B knobs for kernel experiments (process-wide atomics, read from the environment once; not part of the reference
  * interface).  The knobs that shape the decode step are latched per batch at the next prefill and are part of the captured

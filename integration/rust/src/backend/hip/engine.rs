@@ -77,6 +77,13 @@ extern "C" {
     pub fn q3a_set_repetition(e: *mut q3a_engine, repetition_penalty: f32, no_repeat_ngram_size: i32) -> i32;
     pub fn q3a_selftest_repeat(device: i32, logits: *const f32, s: i32, v: i32, hist: *const i32, stride: i32, lens: *const i32, p: f32, n: i32,
                                out_logits: *mut f32, out_ids: *mut i32, out_lp: *mut f32) -> i32;
+    // sequence bias: hotword boosts and banned phrases on the sequence's own generated ids (include/q3asr.h "sequence bias")
+    pub fn q3a_set_sequence_bias(e: *mut q3a_engine, ids: *const i32, lens: *const i32, bias: *const f32, n: i32) -> i32;
+    pub fn q3a_selftest_seqbias(device: i32, logits: *const f32, s: i32, v: i32, hist: *const i32, stride: i32, lens: *const i32,
+                                seq_ids: *const i32, seq_lens: *const i32, seq_bias: *const f32, n: i32, out_logits: *mut f32,
+                                out_ids: *mut i32, out_lp: *mut f32) -> i32;
+    pub fn q3a_parse_sequence_bias(text: *const c_char, ids: *mut i32, ids_cap: i32, lens: *mut i32, bias: *mut f32, cap: i32,
+                                   n_ids: *mut i32, n: *mut i32) -> i32;
     // beam search: n-best hypotheses with scores, selected on the device (include/q3asr.h "beam search")
     pub fn q3a_beam_search_batch_ptrs(e: *mut q3a_engine, pcm16k: *const *const f32, n_samples: *const i64, u: i32,
                                       lang_prefix_ids: *const i32, n_prefix: i32, width: i32, max_new: i32, out_ids: *mut i32, stride: i32,
@@ -150,6 +157,18 @@ impl HipEngine {
     /// then a ban on every id that would repeat an n-gram of `no_repeat_ngram_size` ids (0: none).  (1.0, 0) turns it off.
     pub fn set_repetition(&self, repetition_penalty: f32, no_repeat_ngram_size: usize) -> Result<()> {
         let rc = unsafe { q3a_set_repetition(self.raw, repetition_penalty, no_repeat_ngram_size as i32) };
+        if rc != 0 { bail!("{}", msg(unsafe { q3a_last_error(self.raw) })); }
+        Ok(())
+    }
+
+    /// Sequence bias for every later generation call: `entries` are (token sequence, bias) pairs; at every step the bias is added to
+    /// the logit of the sequence's last id whenever the ids generated so far end in the rest of it (HuggingFace's
+    /// SequenceBiasLogitsProcessor; a bias of f32::NEG_INFINITY bans the phrase).  An empty slice turns it off.
+    pub fn set_sequence_bias(&self, entries: &[(&[i32], f32)]) -> Result<()> {
+        let ids: Vec<i32> = entries.iter().flat_map(|(q, _)| q.iter().copied()).collect();
+        let lens: Vec<i32> = entries.iter().map(|(q, _)| q.len() as i32).collect();
+        let bias: Vec<f32> = entries.iter().map(|(_, b)| *b).collect();
+        let rc = unsafe { q3a_set_sequence_bias(self.raw, ids.as_ptr(), lens.as_ptr(), bias.as_ptr(), entries.len() as i32) };
         if rc != 0 { bail!("{}", msg(unsafe { q3a_last_error(self.raw) })); }
         Ok(())
     }

@@ -26,6 +26,7 @@ SYMBOLS = [
     "q3a_selftest_kv_reorder", "q3a_set_logit_bias", "q3a_parse_logit_bias",
     "q3a_set_sampling", "q3a_sample_word", "q3a_selftest_sample",
     "q3a_set_repetition", "q3a_selftest_repeat",
+    "q3a_set_sequence_bias", "q3a_selftest_seqbias", "q3a_parse_sequence_bias", "q3a_hotword_sequences", "q3a_banned_sequences",
     "q3a_selftest_gemm_launch", "q3a_selftest_qkrope_launch", "q3a_gemm256_split_rows",
     "q3a_selftest_gemv_launch", "q3a_selftest_decode_attn_launch",
     "q3a_selftest_decode_attn_split_launch", "q3a_selftest_oproj_head_launch", "q3a_selftest_gemv_parts_launch",
@@ -163,6 +164,11 @@ def load() -> C.CDLL:
         "q3a_selftest_sample": (i32, [i32, f32p, i32, i32, C.c_float, C.c_float, u64, i32, i32p, f32p, f32p]),
         "q3a_set_repetition": (i32, [P, C.c_float, i32]),
         "q3a_selftest_repeat": (i32, [i32, f32p, i32, i32, i32p, i32, i32p, C.c_float, i32, f32p, i32p, f32p]),
+        "q3a_set_sequence_bias": (i32, [P, i32p, i32p, f32p, i32]),
+        "q3a_selftest_seqbias": (i32, [i32, f32p, i32, i32, i32p, i32, i32p, i32p, i32p, f32p, i32, f32p, i32p, f32p]),
+        "q3a_parse_sequence_bias": (i32, [C.c_char_p, i32p, i32, i32p, f32p, i32, i32p, i32p]),
+        "q3a_hotword_sequences": (i32, [P, C.POINTER(C.c_char_p), i32, C.c_float, C.c_float, i32p, i32, i32p, f32p, i32, i32p, i32p]),
+        "q3a_banned_sequences": (i32, [P, C.POINTER(C.c_char_p), i32, i32p, i32, i32p, f32p, i32, i32p, i32p]),
         "q3a_selftest_gemm_launch": (i32, [i32, i32, i32, P, P, i32, i32, i32, i32, i32, i32, i32, i32, i32, P, P, i32, P, P, i32, P, i32]),
         "q3a_selftest_qkrope_launch": (i32, [i32, i32, i32, P, i32, P, i32, i32, P, P, P, P, P, P, C.c_float, P, P, i32, i32, i32, i32, i32, P, P, P]),
         "q3a_selftest_gemv_launch": (i32, [i32, i32, P, i32, i32, P, P, C.c_float, P, i32, P, P, P, P, i32, i32, P, P]),

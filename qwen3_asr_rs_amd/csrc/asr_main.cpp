@@ -24,6 +24,12 @@
 // "Accepted: <k> / <n>" -- the leading draft ids the greedy loop would have written itself, of the n the draft has.  Q3A_DRAFT_ROUNDS=<r>
 // (default 1) allows further verification rounds.  The engine refuses it together with Q3A_TEMPERATURE / Q3A_REPETITION_PENALTY /
 // Q3A_NO_REPEAT_NGRAM.
+// Q3A_HOTWORDS=<path of a file, one phrase per line> with Q3A_HOTWORD_BOOST=<b> (required: no value has been tuned on real weights) and
+// optionally Q3A_HOTWORD_START_BOOST=<b> boosts those phrases (q3a_hotword_sequences); Q3A_BANNED_PHRASES=<path, one phrase per line>
+// never writes them (q3a_banned_sequences); Q3A_SEQUENCE_BIAS=<path of a file of "bias id id ..." lines> gives entries as ids
+// (q3a_parse_sequence_bias).  The three are concatenated in that order (a sequence named twice keeps the larger bias) and set with
+// q3a_set_sequence_bias before anything is generated; the engine then refuses a Q3A_BEAM search and Q3A_DRAFT_TEXT, a
+// Q3A_SCORE_TEXT score never sees it.  '#' starts a comment in the phrase files too; without the variables nothing changes.
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -111,6 +117,102 @@ static int set_repetition_from_env(q3a_engine* eng) {
   if (q3a_set_repetition(eng, penalty, (int32_t)ngram) != 0) return die(std::string("Repetition control failed: ") + q3a_last_error(eng));
   logf(1, "Repetition control: penalty %s", have_p ? p : "1");
   logf(1, "Repetition control: no-repeat n-gram %s", have_n ? n : "0");
+  return 0;
+}
+
+static bool read_file(const char* path, std::string& text) {
+  FILE* f = fopen(path, "rb");
+  if (!f) return false;
+  char buf[4096];
+  for (size_t k; (k = fread(buf, 1, sizeof(buf), f)) > 0;) text.append(buf, k);
+  fclose(f);
+  return true;
+}
+
+// Q3A_HOTWORDS (+ Q3A_HOTWORD_BOOST, Q3A_HOTWORD_START_BOOST) / Q3A_BANNED_PHRASES / Q3A_SEQUENCE_BIAS: the engine's sequence bias,
+// set before anything is generated
+static int set_sequence_bias_from_env(q3a_engine* eng, q3a_tokenizer* tok) {
+  const char *hot = getenv("Q3A_HOTWORDS"), *ban = getenv("Q3A_BANNED_PHRASES"), *file = getenv("Q3A_SEQUENCE_BIAS");
+  const char *boost_s = getenv("Q3A_HOTWORD_BOOST"), *start_s = getenv("Q3A_HOTWORD_START_BOOST");
+  const bool have_hot = hot && *hot, have_ban = ban && *ban, have_file = file && *file;
+  if (!have_hot && !have_ban && !have_file) return 0;
+  const std::string what = "Sequence bias failed: ";
+  std::vector<std::vector<int32_t>> seqs;
+  std::vector<float> biases;
+  // one of the three list helpers, sized by a first call without room, appended (an equal sequence keeps the larger bias)
+  auto take = [&](auto&& call) -> int {
+    int32_t n_ids = 0, n = 0;
+    if (call(nullptr, 0, nullptr, nullptr, 0, &n_ids, &n) != 0) return die(what + q3a_last_error(nullptr));
+    std::vector<int32_t> ids((size_t)n_ids + 1), lens((size_t)n + 1);
+    std::vector<float> bias((size_t)n + 1);
+    if (call(ids.data(), n_ids, lens.data(), bias.data(), n, &n_ids, &n) != 0) return die(what + q3a_last_error(nullptr));
+    for (int32_t k = 0, o = 0; k < n; o += lens[k++]) {
+      const std::vector<int32_t> q(ids.begin() + o, ids.begin() + o + lens[k]);
+      const auto it = std::find(seqs.begin(), seqs.end(), q);
+      if (it != seqs.end()) { float& b = biases[(size_t)(it - seqs.begin())]; b = std::max(b, bias[k]); }
+      else { seqs.push_back(q); biases.push_back(bias[k]); }
+    }
+    return 0;
+  };
+  // the phrases of a file: one per line, '#' comments and blank lines dropped
+  auto phrases_of = [&](const char* path, std::vector<std::string>& out) -> int {
+    std::string text;
+    if (!read_file(path, text)) return die(what + "cannot read " + path);
+    for (size_t pos = 0; pos <= text.size();) {
+      size_t nl = text.find('\n', pos);
+      if (nl == std::string::npos) nl = text.size();
+      std::string line = text.substr(pos, nl - pos);
+      pos = nl + 1;
+      const size_t hash = line.find('#');
+      if (hash != std::string::npos) line.resize(hash);
+      while (!line.empty() && isspace((unsigned char)line.back())) line.pop_back();
+      size_t a = 0;
+      while (a < line.size() && isspace((unsigned char)line[a])) ++a;
+      if (a < line.size()) out.push_back(line.substr(a));
+    }
+    return 0;
+  };
+  auto number = [&](const char* name, const char* v, float& out) -> int {
+    char* end = nullptr;
+    out = strtof(v, &end);
+    if (end == v || *end) return die(what + name + " is not a number: " + v);
+    return 0;
+  };
+  if (have_hot) {
+    if (!boost_s || !*boost_s) return die(what + "Q3A_HOTWORDS needs Q3A_HOTWORD_BOOST (no default: no value has been tuned on real weights)");
+    float boost = 0.f, start = 0.f;
+    if (number("Q3A_HOTWORD_BOOST", boost_s, boost) != 0) return 1;
+    if (start_s && *start_s && number("Q3A_HOTWORD_START_BOOST", start_s, start) != 0) return 1;
+    std::vector<std::string> ph;
+    if (phrases_of(hot, ph) != 0) return 1;
+    std::vector<const char*> pp;
+    for (auto& x : ph) pp.push_back(x.c_str());
+    pp.push_back(nullptr);
+    const int32_t np = (int32_t)ph.size();
+    if (take([&](int32_t* ids, int32_t ic, int32_t* lens, float* bias, int32_t cap, int32_t* n_ids, int32_t* n) {
+          return q3a_hotword_sequences(tok, pp.data(), np, boost, start, ids, ic, lens, bias, cap, n_ids, n); }) != 0) return 1;
+  }
+  if (have_ban) {
+    std::vector<std::string> ph;
+    if (phrases_of(ban, ph) != 0) return 1;
+    std::vector<const char*> pp;
+    for (auto& x : ph) pp.push_back(x.c_str());
+    pp.push_back(nullptr);
+    const int32_t np = (int32_t)ph.size();
+    if (take([&](int32_t* ids, int32_t ic, int32_t* lens, float* bias, int32_t cap, int32_t* n_ids, int32_t* n) {
+          return q3a_banned_sequences(tok, pp.data(), np, ids, ic, lens, bias, cap, n_ids, n); }) != 0) return 1;
+  }
+  if (have_file) {
+    std::string text;
+    if (!read_file(file, text)) return die(what + "cannot read " + file);
+    if (take([&](int32_t* ids, int32_t ic, int32_t* lens, float* bias, int32_t cap, int32_t* n_ids, int32_t* n) {
+          return q3a_parse_sequence_bias(text.c_str(), ids, ic, lens, bias, cap, n_ids, n); }) != 0) return 1;
+  }
+  std::vector<int32_t> ids, lens;
+  for (const auto& q : seqs) { ids.insert(ids.end(), q.begin(), q.end()); lens.push_back((int32_t)q.size()); }
+  ids.push_back(0); lens.push_back(0); biases.push_back(0.f);  // (never read: valid pointers for an empty list)
+  if (q3a_set_sequence_bias(eng, ids.data(), lens.data(), biases.data(), (int32_t)seqs.size()) != 0) return die(what + q3a_last_error(eng));
+  logf(1, "Sequence bias: %s entries", std::to_string(seqs.size()));
   return 0;
 }
 
@@ -283,6 +385,7 @@ int main(int argc, char** argv) {
     q3a_engine_destroy(eng);
     return die("Failed to load tokenizer: " + m);
   }
+  if (set_sequence_bias_from_env(eng, tok) != 0) return 1;
   logf(1, "Model loaded successfully");
 
   logf(1, "Transcribing: %s", audio_file);

@@ -23,6 +23,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <set>
 #include <thread>
 
 #include "engine_internal.h"
@@ -103,6 +104,61 @@ Knobs& knobs() {
 }
 }  // namespace q3a
 
+namespace q3a {
+// The list of q3a_set_sequence_bias as the sequence-bias phase of history_apply_kernel reads it (engine_internal.h; kernels.h SeqBiasArgs).
+SeqBiasTable seqbias_layout(const char* what_c, const int32_t* ids, const int32_t* lens, const float* bias, int n, int V) {
+  const std::string what = what_c;
+  if (n < 0 || (n > 0 && (!ids || !lens || !bias))) fail(what + ": bad argument");
+  if (n > SEQBIAS_MAX_ENTRIES) fail(what + ": " + std::to_string(n) + " entries, more than " + std::to_string(SEQBIAS_MAX_ENTRIES));
+  struct Ent { int off, len, order; float bias; };
+  std::vector<Ent> ents;
+  std::set<std::vector<int32_t>> seen;
+  long total = 0;
+  for (int i = 0; i < n; ++i) {
+    const int L = lens[i];
+    if (L < 1) fail(what + ": entry " + std::to_string(i) + " is an empty sequence");
+    if (L > SEQBIAS_MAX_LEN) fail(what + ": entry " + std::to_string(i) + " has " + std::to_string(L) + " ids, more than " + std::to_string(SEQBIAS_MAX_LEN));
+    if (total + L > SEQBIAS_MAX_IDS) fail(what + ": more than " + std::to_string(SEQBIAS_MAX_IDS) + " ids over all entries");
+    for (int k = 0; k < L; ++k) {
+      const int id = ids[total + k];
+      if (id < 0 || id >= V) fail(what + ": id " + std::to_string(id) + " of entry " + std::to_string(i) + " is outside the vocabulary (" + std::to_string(V) + ")");
+    }
+    if (!seen.insert(std::vector<int32_t>(ids + total, ids + total + L)).second) fail(what + ": entry " + std::to_string(i) + " repeats the sequence of an earlier entry");
+    const float v = bias[i];
+    if (std::isnan(v) || v == INFINITY) fail(what + ": the bias of entry " + std::to_string(i) + " is NaN or +inf (finite or -inf only)");
+    ents.push_back({(int)total, L, i, v});
+    total += L;
+  }
+  // stable by target id, the one-token entry of a target (there is at most one) first, the longer ones in the caller's order
+  std::stable_sort(ents.begin(), ents.end(), [&](const Ent& a, const Ent& b) {
+    const int ta = ids[a.off + a.len - 1], tb = ids[b.off + b.len - 1];
+    return ta != tb ? ta < tb : (a.len == 1) > (b.len == 1);
+  });
+  SeqBiasTable t;
+  t.words.assign(SEQBIAS_TABLE_WORDS, 0u);
+  uint32_t* const w = t.words.data();
+  int pre = 0, last_inf_target = -1;
+  for (size_t e = 0; e < ents.size(); ++e) {
+    const Ent& x = ents[e];
+    const int target = ids[x.off + x.len - 1];
+    if (t.groups == 0 || (int)w[SEQBIAS_OFF_TARGET + t.groups - 1] != target) {
+      w[SEQBIAS_OFF_TARGET + t.groups] = (uint32_t)target;
+      w[SEQBIAS_OFF_BEGIN + t.groups] = (uint32_t)e;
+      ++t.groups;
+    }
+    memcpy(&w[SEQBIAS_OFF_BIAS + e], &x.bias, 4);
+    w[SEQBIAS_OFF_PRE_OFF + e] = (uint32_t)pre;
+    for (int k = 0; k + 1 < x.len; ++k) w[SEQBIAS_OFF_PRE_IDS + pre++] = (uint32_t)ids[x.off + k];
+    if (x.bias == -INFINITY && target != last_inf_target) { ++t.inf_targets; last_inf_target = target; }
+  }
+  w[SEQBIAS_OFF_BEGIN + t.groups] = (uint32_t)ents.size();
+  w[SEQBIAS_OFF_PRE_OFF + ents.size()] = (uint32_t)pre;
+  t.entries = (int)ents.size(); t.ids = (int)total;
+  w[0] = (uint32_t)t.groups; w[1] = (uint32_t)t.entries;
+  return t;
+}
+}  // namespace q3a
+
 namespace {
 
 // Debug taps, device copies by name for q3a_debug_read.  opts.debug_taps: 1 = every tap; 2 = only the small ones a soak run compares
@@ -131,6 +187,7 @@ struct StepView {
   const bool& logit_bias_on_;  // q3a_set_logit_bias: a bias is set (changes only while the engine holds no decode state)
   const bool& sampling_on_;    // q3a_set_sampling: temperature > 0 (likewise)
   const bool& repetition_on_;  // q3a_set_repetition: a penalty != 1 or an n-gram size > 0 (likewise)
+  const bool& sequence_bias_on_;  // q3a_set_sequence_bias: a list with at least one entry (likewise)
 
   bool precise() const { return opts.precise != 0; }
   bool token_lp() const { return opts.token_logprobs != 0; }
@@ -162,7 +219,8 @@ struct DecodeStep : StepView {
   // q3a_set_sampling: {temperature, min_p, seed low, seed high} as the sampler's kernels read them (a new setting needs no new graph),
   // and the clean (max, sum exp) pair of every 2048-logit chunk of every row [B][sample_chunks(vocab)]
   DevBuf samp_params, samp_max, samp_sum;
-  DevBuf rep_params;  // q3a_set_repetition: {penalty (fp32 bits), n-gram size, 0, 0} as repeat_apply_kernel reads them (a new setting needs no new graph)
+  DevBuf rep_params;  // q3a_set_repetition: {penalty (fp32 bits), n-gram size, 0, 0} as history_apply_kernel reads them (a new setting needs no new graph)
+  DevBuf seq_bias;  // q3a_set_sequence_bias: the list's tables and counts, SEQBIAS_TABLE_WORDS words whatever the list (a new list needs no new graph); allocated by the first non-empty set
   DevBuf draft_accepted;  // draft verification (k_draft.hip): [2 B] first mismatch k per sequence, then its token -- one small D2H copy per prefill
   // f(buffer) for every DevBuf declared above, in declaration order (s: a DecodeStep, const or not).  The declarations of this
   // struct ARE the guarded set: tests/test_host.py::test_step_buffers_cover_the_captured_step compares this list with them.
@@ -172,7 +230,7 @@ struct DecodeStep : StepView {
                     &s.rope_cur, &s.rope_cos, &s.rope_sin, &s.n_done, &s.forced_tok,
                     &s.beam_cand_val, &s.beam_cand_idx, &s.beam_part_max, &s.beam_part_sum, &s.beam_topk_ids, &s.beam_topk_lp, &s.beam_score, &s.beam_finished,
                     &s.beam_parent, &s.beam_token, &s.beam_feed, &s.beam_hist_parent, &s.beam_hist_token, &s.beam_hist_lp, &s.beam_state, &s.beam_lo,
-                    &s.logit_bias, &s.samp_params, &s.samp_max, &s.samp_sum, &s.rep_params, &s.draft_accepted})
+                    &s.logit_bias, &s.samp_params, &s.samp_max, &s.samp_sum, &s.rep_params, &s.seq_bias, &s.draft_accepted})
       f(*b);
   }
 
@@ -205,15 +263,17 @@ struct DecodeStep : StepView {
 
   // final norm + lm_head on x_dec -> logits (+ block argmax partials), then argmax/finalize.  While sampling is on every form
   // stores its logits (as with head_logits_), the sampler (k_sample.hip) replaces the head's partials with its own noisy ones, and
-  // finalize runs on those unchanged.  While q3a_set_repetition is on every form stores its logits too, repeat_apply_kernel
+  // finalize runs on those unchanged.  While q3a_set_repetition is on every form stores its logits too, history_apply_kernel
   // (k_repeat.hip) rewrites the stored rows in place (l' -> l''), and fresh partials over l'' (or the sampler) replace the head's.
+  // q3a_set_sequence_bias is the same arrangement one place earlier: the same kernel in its sequence-bias mode (k_repeat.hip) rewrites the stored rows
+  // first, repetition control then works on its result, and the fresh partials are computed once, after the last rewriting kernel.
   // With a logit bias every form below
   // works on l' = l + b: the GEMV heads and both passes of the pruned argmax through GemvArgs::bias, the gemm16 forms through
   // GemmEpilogue::bias (in front of the argmax epilogue and of the stored logits), the precise batched form through batched_proj.
   void run_head(int advance) {
     const int S = B, H = d.hidden, V = d.vocab;
     const float* const hb = head_bias();
-    const bool sample = sampling_on_, repeat = repetition_on_, store = head_logits_ || sample || repeat;
+    const bool sample = sampling_on_, repeat = repetition_on_, seqb = sequence_bias_on_, rewrite = repeat || seqb, store = head_logits_ || sample || rewrite;
     tap("head_in", x_dec.p, (size_t)S * H * 4);  // (debug taps) last-layer residual rows the final norm + lm_head read
     const double wbytes = 2.0 * V * H;
     int n_part = 0;
@@ -262,14 +322,15 @@ struct DecodeStep : StepView {
       } else {
         timed(Q3A_KC_GEMM, wbytes, [&] { KCHK(launch_gemm16(s_ln.as<uint16_t>(), H, wh(L.lm_head), S, V, H, ep, false, stream)); });
         n_part = 128;
-        if (!repeat) timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_partials(logits.as<float>(), V, S, part, n_part, stream)); });
+        if (!rewrite) timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_partials(logits.as<float>(), V, S, part, n_part, stream)); });
       }
     } else {
       timed(Q3A_KC_NORM, 0, [&] { KCHK(launch_rmsnorm(x_dec.as<float>(), wf(L.final_norm), s_ln.as<float>(), S, H, d.rms_eps, stream)); });
       timed(Q3A_KC_GEMM, wbytes, [&] { batched_proj(s_ln.as<float>(), H, wh(L.lm_head), V, H, hb, 0, logits.as<float>(), V, nullptr); });
       n_part = 128;
-      if (!repeat) timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_partials(logits.as<float>(), V, S, part, n_part, stream)); });
+      if (!rewrite) timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_partials(logits.as<float>(), V, S, part, n_part, stream)); });
     }
+    if (seqb) n_part = enqueue_sequence_bias(part, !sample && !repeat);
     if (repeat) n_part = enqueue_repetition(part, !sample);
     FinalizeArgs f{};
     f.part = part; f.n_part = n_part; f.V = V; f.advance = advance; f.c = commit();
@@ -303,6 +364,23 @@ struct DecodeStep : StepView {
     HIPCHK(hipMemcpy(forced_tok.p, ids, (size_t)B * 4, hipMemcpyHostToDevice));
     enqueue_set_tokens(forced_tok.as<int>());
   }
+  // fresh argmax partials (log-sum channel included) over rows a kernel has rewritten in place; returns their number per row
+  int enqueue_rewritten_partials(const ArgmaxPartials& part) {
+    constexpr int kRewrittenParts = 128;
+    timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_partials(logits.as<float>(), d.vocab, B, part, kRewrittenParts, stream)); });
+    return kRewrittenParts;
+  }
+  // Sequence bias (k_repeat.hip): the stored rows, in place, from each sequence's own out_ids and the list's tables in seq_bias.
+  // It runs in front of repetition control (HuggingFace's generate() order); `partials`: no rewriting kernel follows and the
+  // sampler does not either, so the rewritten rows' own partials take the place of the head's here.
+  int enqueue_sequence_bias(const ArgmaxPartials& part, bool partials) {
+    SeqBiasArgs sa{};
+    sa.logits = logits.as<float>(); sa.S = B; sa.V = d.vocab; seqbias_point(sa, seq_bias.p);
+    sa.out_ids = out_ids.as<int>(); sa.out_stride = max_new; sa.step_count = step_count.as<int>();
+    if (!seq_bias.p) fail("sequence bias: on without its tables");
+    timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_seqbias_apply(sa, stream)); });
+    return partials ? enqueue_rewritten_partials(part) : 0;
+  }
   // Repetition penalty and no-repeat n-grams (k_repeat.hip): the stored rows, in place, from each sequence's own out_ids
   // (l' -> l'').  The head's partials, where it wrote any, are those of l': with `partials` the rewritten rows' own, log-sum channel
   // included, take their place (the sampler writes its own instead).  Returns the partials per row finalize then merges.
@@ -311,9 +389,7 @@ struct DecodeStep : StepView {
     ra.logits = logits.as<float>(); ra.S = B; ra.V = d.vocab; ra.params = rep_params.as<uint32_t>();
     ra.out_ids = out_ids.as<int>(); ra.out_stride = max_new; ra.step_count = step_count.as<int>();
     timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_repeat_apply(ra, stream)); });
-    constexpr int kRepeatParts = 128;
-    if (partials) timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_partials(ra.logits, ra.V, ra.S, part, kRepeatParts, stream)); });
-    return kRepeatParts;
+    return partials ? enqueue_rewritten_partials(part) : 0;
   }
   // Sampling (k_sample.hip), around the finalize of run_head.  The head's partials are done with: the sampler writes its own noisy
   // ones into the same buffers -- no log-sum channel, the drawn id is not the maximum -- and finalize merges those instead.
@@ -709,11 +785,15 @@ struct q3a_engine : CallState {
   bool repetition_on_ = false;       // q3a_set_repetition: penalty != 1 or n-gram size > 0 (k_repeat.hip; graph signature)
   float rep_penalty_ = 1.f;          // what step.rep_params holds
   int rep_ngram_ = 0;
+  bool logit_bias_allow_list_ = false;  // the logit bias was set with default_bias = -inf (an allow-list)
+  bool sequence_bias_on_ = false;       // q3a_set_sequence_bias: a list with at least one entry (k_repeat.hip; graph signature)
+  int seq_bias_stats_[4] = {0, 0, 0, 0};  // of the list step.seq_bias holds: on, entries, ids over all entries, distinct targets
+  int seq_bias_inf_targets_ = 0;        // distinct targets of its -inf entries (0 while off)
 
   // ---- the captured decode step: its buffers and launches, and all it sees of the members above ----
   DecodeStep step{StepView{d, L, opts, arena, arena_flags, stream, chain_streams, join_ev, fork_ev, n_cu, host_prog_dev, prof, taps, lm_q, lm_qs, lm_q_cols,
                            B, max_ctx, max_new, gsize, live_nsplit_, live_kps_, attn_nsplit, min_P_, part_stride, beam_w(), kv_layer_elems, head_logits(),
-                           k_parallel_groups, k_skinny_q, k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, k_oproj_by_head, logit_bias_on_, sampling_on_, repetition_on_}};
+                           k_parallel_groups, k_skinny_q, k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, k_oproj_by_head, logit_bias_on_, sampling_on_, repetition_on_, sequence_bias_on_}};
 
   // (the mode rules are stated once, in StepView)
   bool precise() const { return step.precise(); }
@@ -1558,6 +1638,7 @@ struct q3a_engine : CallState {
     require_asr(what);
     if (sampling_on_) fail(std::string(what) + ": sampling is on (q3a_set_sampling with temperature > 0): a sampled id is not the argmax of its row -- turn it off first");
     if (repetition_on_) fail(std::string(what) + ": repetition control is on (q3a_set_repetition): its choice depends on the history, not on the row alone -- turn it off first");
+    if (sequence_bias_on_) fail(std::string(what) + ": a sequence bias is on (q3a_set_sequence_bias): its choice depends on the history, not on the row alone -- turn it off first");
     if (beam_w() > 0) fail(std::string(what) + ": a beam search owns the decode state (a new q3a_prefill returns to the greedy step)");
   }
   // prompts of dp (a kDrafted plan) already set up (setup_prompts over dp.ids / dp.lens).  acc [2 B]: k per utterance, then its token.
@@ -1627,8 +1708,8 @@ struct q3a_engine : CallState {
     });
     char buf[256];
     // (one field per latched knob, as latched: packing several into one integer let distinct settings collide -- ADVICE r5)
-    snprintf(buf, sizeof(buf), "%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.b%d.lb%d.sm%d.rp%d/%d.%d/%d/%d/%p/%016llx", B, gsize, k_parallel_groups, k_skinny_q,
-             k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, k_oproj_by_head, (int)(min_P_ < 256), (int)head_logits(), (int)token_lp(), beam_w(), (int)logit_bias_on_, (int)sampling_on_, (int)repetition_on_, live_nsplit_, live_kps_,
+    snprintf(buf, sizeof(buf), "%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.b%d.lb%d.sm%d.rp%d.sb%d/%d.%d/%d/%d/%p/%016llx", B, gsize, k_parallel_groups, k_skinny_q,
+             k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, k_oproj_by_head, (int)(min_P_ < 256), (int)head_logits(), (int)token_lp(), beam_w(), (int)logit_bias_on_, (int)sampling_on_, (int)repetition_on_, (int)sequence_bias_on_, live_nsplit_, live_kps_,
              max_ctx, max_new, (const void*)arena, (unsigned long long)h);
     return buf;
   }
@@ -1852,12 +1933,14 @@ struct q3a_engine : CallState {
     const bool on = !(n == 0 && default_bias == 0.f);
     const bool eos_open = (kEos0 < V && b[kEos0] != -INFINITY) || (kEos1 < V && b[kEos1] != -INFINITY);
     repetition_bias_check(what, rep_ngram_, eos_open, finite);
+    sequence_bias_check(what, seq_bias_inf_targets_, default_bias == -INFINITY, finite, rep_ngram_);
     drop_decode_state();
     HIPCHK(hipMemcpyAsync(step.logit_bias.p, b.data(), (size_t)V * 4, hipMemcpyHostToDevice, stream));
     HIPCHK(hipStreamSynchronize(stream));
     logit_bias_on_ = on;
     logit_bias_finite_ = finite;
     logit_bias_eos_open_ = eos_open;
+    logit_bias_allow_list_ = default_bias == -INFINITY;
   }
   // Repetition penalty and no-repeat n-grams (q3asr.h q3a_set_repetition).  Penalty and n-gram size live in a device buffer the kernel
   // reads, so a new setting replays the same graph; on / off is part of the graph signature.  No decode state afterwards.
@@ -1870,6 +1953,7 @@ struct q3a_engine : CallState {
     if (on && d.vocab > REPEAT_MAX_VOCAB)
       fail(std::string(what) + ": the vocabulary (" + std::to_string(d.vocab) + ") exceeds the " + std::to_string(REPEAT_MAX_VOCAB) + " ids the kernel's bitmap holds");
     repetition_bias_check(what, ngram, logit_bias_eos_open_, logit_bias_finite_);
+    sequence_bias_check(what, seq_bias_inf_targets_, logit_bias_allow_list_, logit_bias_finite_, ngram);
     uint32_t w[4] = {0, (uint32_t)ngram, 0, 0};
     memcpy(&w[0], &penalty, 4);
     drop_decode_state();
@@ -1884,6 +1968,36 @@ struct q3a_engine : CallState {
     if (ngram > 0 && !eos_open && finite <= opts.max_new_tokens)
       fail(std::string(what) + ": no_repeat_ngram_size " + std::to_string(ngram) + " over a logit bias that forbids both EOS ids and leaves " + std::to_string(finite) +
            " tokens finite, no more than max_new_tokens (" + std::to_string(opts.max_new_tokens) + "): a row could run out of finite logits");
+  }
+  // Sequence bias (q3asr.h q3a_set_sequence_bias).  The list is laid out on the host (seqbias_layout) and lives in ONE device buffer of
+  // fixed size the kernel reads, counts included, so another list replays the same graph; on / off is part of the graph signature.
+  // The buffer is allocated by the first non-empty list and kept until the engine goes.  No decode state afterwards.
+  void set_sequence_bias(const int32_t* ids, const int32_t* lens, const float* bias, int n) {
+    const char* what = "q3a_set_sequence_bias";
+    require_asr(what);
+    const SeqBiasTable tb = seqbias_layout(what, ids, lens, bias, n, d.vocab);
+    sequence_bias_check(what, tb.inf_targets, logit_bias_allow_list_, logit_bias_finite_, rep_ngram_);
+    drop_decode_state();
+    if (tb.entries > 0 || step.seq_bias.p) {  // (an engine that never had a list has no buffer, and clearing allocates none)
+      step.seq_bias.ensure(SEQBIAS_TABLE_WORDS * 4);
+      HIPCHK(hipMemcpyAsync(step.seq_bias.p, tb.words.data(), SEQBIAS_TABLE_WORDS * 4, hipMemcpyHostToDevice, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+    }
+    sequence_bias_on_ = tb.entries > 0;
+    seq_bias_stats_[0] = sequence_bias_on_; seq_bias_stats_[1] = tb.entries; seq_bias_stats_[2] = tb.ids; seq_bias_stats_[3] = tb.groups;
+    seq_bias_inf_targets_ = tb.inf_targets;
+  }
+  // the one way a row could run out of finite logits under a sequence bias: -inf entries over an allow-list that leaves no more
+  // tokens finite than those entries can take away, plus -- with an n-gram ban -- the tokens a sequence may generate (asked by
+  // whichever of the three setters comes second)
+  void sequence_bias_check(const char* what, int inf_targets, bool allow_list, int finite, int ngram) const {
+    const long taken = (long)inf_targets + (ngram > 0 ? opts.max_new_tokens : 0);
+    if (inf_targets > 0 && allow_list && finite <= taken)
+      fail(std::string(what) + ": -inf sequence-bias entries on " + std::to_string(inf_targets) + " target(s)" + (ngram > 0 ? ", no_repeat_ngram_size " + std::to_string(ngram) + " (max_new_tokens " + std::to_string(opts.max_new_tokens) + ")" : "") +
+           " over an allow-list logit bias that leaves " + std::to_string(finite) + " tokens finite: a row could run out of finite logits");
+  }
+  void beam_sequence_bias_check(const char* what) const {
+    if (sequence_bias_on_) fail(std::string(what) + ": a sequence bias is on (q3a_set_sequence_bias); beam slots reorder their histories -- turn it off first");
   }
   void beam_repetition_check(const char* what) const {
     if (repetition_on_) fail(std::string(what) + ": repetition control is on (q3a_set_repetition); beam slots reorder their histories -- turn it off first");
@@ -1918,6 +2032,7 @@ struct q3a_engine : CallState {
     beam_check(what, W);
     beam_sampling_check(what);
     beam_repetition_check(what);
+    beam_sequence_bias_check(what);
     beam_bias_check(what, W);
     if (!head_logits() || pos_hi_ != *std::max_element(P.begin(), P.end()))
       fail(std::string(what) + ": needs the logits of q3a_prefill (call it directly after the prefill)");
@@ -2305,6 +2420,7 @@ int32_t q3a_beam_search_batch_ptrs(q3a_engine* e, const float* const* pcm16k, co
   if (stride < want) fail("q3a_beam_search_batch: stride " + std::to_string(stride) + " is below max_new " + std::to_string(want));
   e->beam_sampling_check("q3a_beam_search_batch");
   e->beam_repetition_check("q3a_beam_search_batch");
+  e->beam_sequence_bias_check("q3a_beam_search_batch");
   e->beam_bias_check("q3a_beam_search_batch", width);
   e->begin_call(false, true);  // every round selects on the stored logits
   // the W slots of an utterance are W ordinary sequences of the batch
@@ -2344,6 +2460,14 @@ int32_t q3a_set_repetition(q3a_engine* e, float repetition_penalty, int32_t no_r
   Q3A_TRY(e)
   HIPCHK(hipSetDevice(e->device));
   e->set_repetition(repetition_penalty, no_repeat_ngram_size);
+  Q3A_CATCH(e)
+}
+
+int32_t q3a_set_sequence_bias(q3a_engine* e, const int32_t* ids, const int32_t* lens, const float* bias, int32_t n) {
+  if (!e) return 1;
+  Q3A_TRY(e)
+  HIPCHK(hipSetDevice(e->device));
+  e->set_sequence_bias(ids, lens, bias, n);
   Q3A_CATCH(e)
 }
 
@@ -2732,6 +2856,11 @@ int32_t q3a_debug_read(q3a_engine* e, const char* name, void* dst, uint64_t byte
     uint32_t st[3] = {e->repetition_on_ ? 1u : 0u, 0u, (uint32_t)e->rep_ngram_};
     memcpy(&st[1], &e->rep_penalty_, 4);
     give(st, 12, false);
+    return 0;
+  }
+  if (strcmp(name, "sequence_bias") == 0) {  // {on, entries, ids over all entries, distinct targets} of the list as last set
+    e->require_asr("q3a_debug_read: sequence_bias");
+    give(e->seq_bias_stats_, 16, false);
     return 0;
   }
   if (strcmp(name, "logit_bias_stats") == 0) {

@@ -54,6 +54,17 @@ struct DevBuf {
   template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// A sequence-bias list as the kernel reads it (kernels.h SeqBiasArgs): the block of words for the device, and what the refusals and
+// q3a_debug_read "sequence_bias" need to know of it.
+struct SeqBiasTable {
+  std::vector<uint32_t> words;  // [SEQBIAS_TABLE_WORDS]
+  int groups = 0, entries = 0, ids = 0, inf_targets = 0;  // groups: distinct targets; inf_targets: distinct targets of -inf entries
+};
+// ids: the entries' ids one after the other, lens [n], bias [n] (n >= 0).  Entries are sorted stably by target id, the one-token
+// entry of a target first.  Throws with `what` in front on every refusal of the header's list that needs no engine: an id outside
+// [0, V), an empty or too long entry, too many entries or ids, a sequence given twice, a NaN or +inf bias.  engine.cpp
+SeqBiasTable seqbias_layout(const char* what, const int32_t* ids, const int32_t* lens, const float* bias, int n, int V);
+
 // e->err (e null: an entry point without an engine) and the calling thread's q3a_last_error(NULL); engine.cpp
 void set_error(q3a_engine* e, const char* msg);
 

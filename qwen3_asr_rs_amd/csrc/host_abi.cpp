@@ -133,6 +133,125 @@ int32_t q3a_parse_logit_bias(const char* text, const char* suppress_list, int32_
   HOST_CATCH
 }
 
+// ---- sequence bias lists (q3a_parse_sequence_bias, q3a_hotword_sequences, q3a_banned_sequences) ----
+}  // extern "C"
+namespace {
+constexpr int kSeqMaxLen = 32;  // ids of one entry (q3asr.h "sequence bias")
+
+// entries in the order they first appeared; an equal sequence keeps the larger bias
+struct SeqList {
+  std::vector<std::vector<int32_t>> seqs;
+  std::vector<float> bias;
+  void add(const std::vector<int32_t>& q, float b) {
+    for (size_t i = 0; i < seqs.size(); ++i)
+      if (seqs[i] == q) { bias[i] = std::max(bias[i], b); return; }
+    seqs.push_back(q);
+    bias.push_back(b);
+  }
+  // *n_ids / *n = ids and entries needed; written only when both capacities hold everything
+  void give(const char* what, int32_t* ids, int32_t ids_cap, int32_t* lens, float* out_bias, int32_t cap, int32_t* n_ids, int32_t* n) const {
+    if (!n_ids || !n || ids_cap < 0 || cap < 0 || (ids_cap > 0 && !ids) || (cap > 0 && (!lens || !out_bias))) fail(std::string(what) + ": bad argument");
+    size_t total = 0;
+    for (const auto& q : seqs) total += q.size();
+    if (total > 0x7fffffff || seqs.size() > 0x7fffffff) fail(std::string(what) + ": too many entries");
+    *n_ids = (int32_t)total;
+    *n = (int32_t)seqs.size();
+    if (total > (size_t)ids_cap || seqs.size() > (size_t)cap) return;
+    size_t o = 0;
+    for (size_t i = 0; i < seqs.size(); ++i) {
+      lens[i] = (int32_t)seqs[i].size();
+      out_bias[i] = bias[i];
+      for (int32_t id : seqs[i]) ids[o++] = id;
+    }
+  }
+};
+
+// both tokenisations of a phrase, encode(phrase) and encode(" " + phrase): a word at the start of the text and one behind a space
+std::vector<std::vector<int32_t>> phrase_tokenisations(const char* what, const q3a_tokenizer* t, const char* phrase) {
+  const std::string p = trimmed(phrase ? phrase : "");
+  if (p.empty()) fail(std::string(what) + ": an empty phrase");
+  std::vector<std::vector<int32_t>> out;
+  for (const std::string& text : {p, " " + p}) {
+    const std::vector<int64_t> v = t->tok.encode(text);
+    if (v.empty()) fail(std::string(what) + ": phrase '" + p + "' encodes to no id");
+    if ((int)v.size() > kSeqMaxLen) fail(std::string(what) + ": phrase '" + p + "' encodes to " + std::to_string(v.size()) + " ids, more than " + std::to_string(kSeqMaxLen));
+    out.emplace_back(v.begin(), v.end());
+  }
+  return out;
+}
+}  // namespace
+extern "C" {
+
+int32_t q3a_parse_sequence_bias(const char* text, int32_t* ids, int32_t ids_cap, int32_t* lens, float* bias, int32_t cap, int32_t* n_ids, int32_t* n) {
+  HOST_TRY
+  const char* what = "q3a_parse_sequence_bias";
+  SeqList list;
+  const std::string t = text ? text : "";
+  int line_no = 0;
+  for (size_t pos = 0; pos <= t.size();) {
+    size_t nl = t.find('\n', pos);
+    if (nl == std::string::npos) nl = t.size();
+    std::string line = t.substr(pos, nl - pos);
+    pos = nl + 1;
+    ++line_no;
+    const size_t hash = line.find('#');
+    if (hash != std::string::npos) line.resize(hash);
+    line = trimmed(line);
+    if (line.empty()) continue;
+    const std::string where = std::string(what) + ": line " + std::to_string(line_no);
+    std::vector<std::string> fields;  // "<bias> <id> <id> ...": the bias is the first field
+    for (size_t a = 0; a < line.size();) {
+      while (a < line.size() && isspace((unsigned char)line[a])) ++a;
+      size_t b = a;
+      while (b < line.size() && !isspace((unsigned char)line[b])) ++b;
+      if (b > a) fields.push_back(line.substr(a, b - a));
+      a = b;
+    }
+    if (fields.size() < 2) fail(where + ": expected '<bias> <id> <id> ...'");
+    if ((int)fields.size() - 1 > kSeqMaxLen) fail(where + ": " + std::to_string(fields.size() - 1) + " ids, more than " + std::to_string(kSeqMaxLen));
+    const float v = parse_bias_value(fields[0], where);
+    std::vector<int32_t> q;
+    for (size_t i = 1; i < fields.size(); ++i) {
+      const std::string& f = fields[i];
+      if (f.size() > 10 || f.find_first_not_of("0123456789") != std::string::npos || strtol(f.c_str(), nullptr, 10) > 0x7fffffffL) fail(where + ": '" + f + "' is not an id");
+      q.push_back((int32_t)strtol(f.c_str(), nullptr, 10));
+    }
+    for (const auto& have : list.seqs)
+      if (have == q) fail(where + ": the sequence was given on an earlier line");
+    list.add(q, v);
+  }
+  list.give(what, ids, ids_cap, lens, bias, cap, n_ids, n);
+  HOST_CATCH
+}
+
+int32_t q3a_hotword_sequences(const q3a_tokenizer* t, const char* const* phrases, int32_t n_phrases, float boost, float start_boost, int32_t* ids,
+                              int32_t ids_cap, int32_t* lens, float* bias, int32_t cap, int32_t* n_ids, int32_t* n) {
+  HOST_TRY
+  const char* what = "q3a_hotword_sequences";
+  if (!t || n_phrases < 0 || (n_phrases > 0 && !phrases)) fail(std::string(what) + ": bad argument");
+  if (!std::isfinite(boost) || !std::isfinite(start_boost)) fail(std::string(what) + ": boost and start_boost must be finite");
+  SeqList list;
+  for (int i = 0; i < n_phrases; ++i)
+    for (const auto& p : phrase_tokenisations(what, t, phrases[i])) {
+      if (start_boost != 0.f) list.add({p[0]}, start_boost);
+      for (size_t j = 1; j < p.size(); ++j) list.add(std::vector<int32_t>(p.begin(), p.begin() + j + 1), boost);
+    }
+  list.give(what, ids, ids_cap, lens, bias, cap, n_ids, n);
+  HOST_CATCH
+}
+
+int32_t q3a_banned_sequences(const q3a_tokenizer* t, const char* const* phrases, int32_t n_phrases, int32_t* ids, int32_t ids_cap, int32_t* lens,
+                             float* bias, int32_t cap, int32_t* n_ids, int32_t* n) {
+  HOST_TRY
+  const char* what = "q3a_banned_sequences";
+  if (!t || n_phrases < 0 || (n_phrases > 0 && !phrases)) fail(std::string(what) + ": bad argument");
+  SeqList list;
+  for (int i = 0; i < n_phrases; ++i)
+    for (const auto& p : phrase_tokenisations(what, t, phrases[i])) list.add(p, -INFINITY);
+  list.give(what, ids, ids_cap, lens, bias, cap, n_ids, n);
+  HOST_CATCH
+}
+
 // ---- draft-verified decoding: the draft of the next round (q3asr.h) ----
 int32_t q3a_draft_next_round(const int32_t* draft, int32_t n, int32_t k, int32_t tok, int32_t* out, int32_t cap, int32_t* n_out) {
   HOST_TRY

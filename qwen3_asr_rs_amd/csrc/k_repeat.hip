@@ -1,9 +1,23 @@
-// Repetition penalty and no-repeat n-grams on the device (include/q3asr.h "repetition"): what a step with
-// q3a_set_repetition on puts between the lm_head and the argmax partials (or the sampler).  The kernel reads only the stored logits
-// l' [S][V] (fp32, bias included) and the sequence's own out_ids, so it does not care which head form wrote the row, and it keeps
-// nothing from step to step: the history IS out_ids[s][0 .. t), t = min(step_count[s], out_stride).
+// The history-dependent logits processors on the device: sequence bias (include/q3asr.h "sequence bias") and the
+// repetition penalty with the no-repeat n-gram ban (include/q3asr.h "repetition") -- what a step with
+// q3a_set_sequence_bias / q3a_set_repetition on puts between the lm_head and the argmax partials (or the sampler).  The kernel reads only
+// the stored logits l' [S][V] (fp32, bias included) and the sequence's own out_ids, so it does not care which head form wrote the row,
+// and it keeps nothing from step to step: no trie, no match state, nothing to undo.  The history IS out_ids[s][0 .. t),
+// t = min(step_count[s], out_stride).  Both processors are phases of ONE kernel (the library's kernel count is pinned by
+// tests/test_kernarg_preload.py); a launch runs the phases of one processor, the other's arguments are null.
 //
-//   repeat_apply_kernel    one workgroup of 256 threads per sequence, four phases with a barrier between them:
+//   history_apply_kernel   one workgroup of 256 threads per sequence.
+//     sequence bias (launch_seqbias_apply):
+//                          0a. the last min(t, 31) ids of the history go to LDS (an entry has at most 32 ids, so 31 lead its target);
+//                          0b. thread g, stride 256 over the G target groups (G from device memory: another list replays the same
+//                             graph), walks its group's entries in the setter's order -- the one-token entry first, then the longer
+//                             ones as the caller gave them --, compares each entry's leading ids with the LDS tail and adds the bias
+//                             of every entry that fires to acc (0.0f at the start, one fp32 add each); if one fired, the ONE
+//                             read-modify-write row[target] += acc.  A target belongs to exactly one group and a group to exactly
+//                             one thread: no atomic, no order dependence.  One-token entries fire at t = 0 too (the id the prefill
+//                             produces): nothing returns early here.  Every index formed from the tables is checked against the
+//                             table's capacity and the row's length before it is used.
+//     repetition (launch_repeat_apply), four phases with a barrier between them:
 //                          1. zero a ceil(V / 32)-word bitmap in LDS;
 //                          2. every thread reads its share of the history, keeps it in LDS and sets the id's bit (LDS atomic OR);
 //                          3. every thread walks its bitmap words and rewrites the set entries of the row in place, l / p where
@@ -20,15 +34,44 @@ namespace q3a {
 
 namespace {
 
-__global__ __launch_bounds__(256) void repeat_apply_kernel(RepeatArgs a, int words, int hist_cap) {
+__global__ __launch_bounds__(256) void history_apply_kernel(SeqBiasArgs sb, RepeatArgs a, int words, int hist_cap) {
   extern __shared__ __attribute__((aligned(16))) uint32_t repeat_lds[];
+  __shared__ int tail[SEQBIAS_MAX_LEN - 1];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  if (sb.params) {  // (uniform: a kernel argument)
+    const int V = sb.V, t = max(min(sb.step_count[s], sb.out_stride), 0);
+    const int m = min(t, SEQBIAS_MAX_LEN - 1);  // ids of the history an entry can ask about
+    const int* const h = sb.out_ids + (size_t)s * sb.out_stride;
+    float* const row = sb.logits + (size_t)s * V;
+    if (tid < m) tail[tid] = h[t - m + tid];
+    __syncthreads();
+    const int G = min(sb.params[0], SEQBIAS_MAX_ENTRIES), E = min(sb.params[1], SEQBIAS_MAX_ENTRIES);
+    for (int g = tid; g < G; g += 256) {
+      const int target = sb.grp_target[g];
+      const int e0 = max(sb.grp_begin[g], 0), e1 = min(sb.grp_begin[g + 1], E);
+      float acc = 0.f;
+      bool fired = false;
+      for (int e = e0; e < e1; ++e) {
+        const int off = sb.ent_pre_off[e], n = sb.ent_pre_off[e + 1] - off;  // the entry's L - 1 leading ids: pre_ids[off .. off + n)
+        if (n < 0 || n > m || off < 0 || off + n > SEQBIAS_MAX_IDS) continue;  // (n > m: t < L - 1, the entry cannot fire yet)
+        bool eq = true;
+        for (int k = 0; k < n; ++k) eq = eq && sb.pre_ids[off + k] == tail[m - n + k];
+        if (eq) {
+          acc += sb.ent_bias[e];
+          fired = true;
+        }
+      }
+      if (fired && (unsigned)target < (unsigned)V) row[target] = row[target] + acc;
+    }
+  }
+  if (!a.params) return;  // (uniform)
   uint32_t* const bits = repeat_lds;                                         // [words]
   int* const hist = reinterpret_cast<int*>(repeat_lds + ((words + 3) & ~3));  // [hist_cap] the first hist_cap ids of the history
-  const int s = blockIdx.x, tid = threadIdx.x, V = a.V;
+  const int V = a.V;
   const float p = __uint_as_float(a.params[0]);
   const int n = (int)a.params[1];
   const int t = min(a.step_count[s], a.out_stride);
-  if (t <= 0) return;  // (the whole workgroup: nothing generated yet, both processors are the identity)
+  if (t <= 0) return;  // (the whole workgroup: nothing generated yet, both repetition processors are the identity)
   const int* const h = a.out_ids + (size_t)s * a.out_stride;
   float* const row = a.logits + (size_t)s * V;
   // a history longer than the LDS copy is read where it lies for the rest (out_ids is L2 resident)
@@ -55,10 +98,10 @@ __global__ __launch_bounds__(256) void repeat_apply_kernel(RepeatArgs a, int wor
   }
   __syncthreads();
   if (n >= 1 && t >= n - 1) {
-    const int tail = t - n + 1;  // h[tail .. t): the n - 1 ids a banned id would complete to a seen n-gram
-    for (int i = tid; i < tail; i += 256) {
+    const int tail0 = t - n + 1;  // h[tail0 .. t): the n - 1 ids a banned id would complete to a seen n-gram
+    for (int i = tid; i < tail0; i += 256) {
       bool eq = true;
-      for (int k = 0; k < n - 1; ++k) eq = eq && at(i + k) == at(tail + k);
+      for (int k = 0; k < n - 1; ++k) eq = eq && at(i + k) == at(tail0 + k);
       if (eq) {
         const int id = at(i + n - 1);
         if ((unsigned)id < (unsigned)V) row[id] = -INFINITY;
@@ -76,7 +119,16 @@ const char* launch_repeat_apply(const RepeatArgs& a, hipStream_t s) {
   if (!a.logits || !a.params || !a.out_ids || !a.step_count || a.out_stride < 1) return "repetition: null argument";
   const int words = (a.V + 31) / 32, hist_cap = a.out_stride < REPEAT_HIST_LDS ? a.out_stride : REPEAT_HIST_LDS;
   const size_t lds = ((size_t)((words + 3) & ~3) + (size_t)hist_cap) * 4;  // <= 32 KB + 16 KB
-  hipLaunchKernelGGL(repeat_apply_kernel, dim3(a.S), dim3(256), lds, s, a, words, hist_cap);
+  hipLaunchKernelGGL(history_apply_kernel, dim3(a.S), dim3(256), lds, s, SeqBiasArgs{}, a, words, hist_cap);
+  return nullptr;
+}
+
+const char* launch_seqbias_apply(const SeqBiasArgs& a, hipStream_t s) {
+  if (a.S <= 0) return nullptr;
+  if (a.V < 1) return "sequence bias: empty vocabulary";
+  if (!a.logits || !a.params || !a.grp_target || !a.grp_begin || !a.ent_bias || !a.ent_pre_off || !a.pre_ids || !a.out_ids || !a.step_count || a.out_stride < 1)
+    return "sequence bias: null argument";
+  hipLaunchKernelGGL(history_apply_kernel, dim3(a.S), dim3(256), 0, s, a, RepeatArgs{}, 0, 0);
   return nullptr;
 }
 

@@ -540,4 +540,35 @@ struct RepeatArgs {
 };
 const char* launch_repeat_apply(const RepeatArgs& a, hipStream_t s);
 
+// ---- sequence bias (k_repeat.hip: a mode of the same kernel) -----------------------------------------------------------------------------
+constexpr int SEQBIAS_MAX_ENTRIES = 4096;  // entries of a list (and so target groups)
+constexpr int SEQBIAS_MAX_LEN = 32;        // ids of one entry
+constexpr int SEQBIAS_MAX_IDS = 65536;     // ids over all entries
+// Per row s of logits [S][V] (fp32, row stride V), rewritten IN PLACE: with h = out_ids[s][0 .. t), t = min(step_count[s], out_stride),
+// an entry q_0 .. q_{L-1} fires iff t >= L - 1 and h[t - L + 1 .. t) == q_0 .. q_{L-2}; for every target id with a firing entry,
+// l_target += acc, acc = 0.0f + the biases of its firing entries in table order (one fp32 add each).  Entries are grouped by target:
+// group g owns entries grp_begin[g] .. grp_begin[g + 1), entry e the leading ids pre_ids[ent_pre_off[e] .. ent_pre_off[e + 1]).
+// One launch, one workgroup per row; it runs before launch_repeat_apply / launch_argmax_partials / launch_sample.
+struct SeqBiasArgs {
+  float* logits; int S; int V;
+  const int* params;                       // device [4]: groups G, entries E, 0, 0 (read by the kernel: another list, the same launch)
+  const int* grp_target; const int* grp_begin;   // [SEQBIAS_MAX_ENTRIES], [SEQBIAS_MAX_ENTRIES + 1]
+  const float* ent_bias; const int* ent_pre_off; // [SEQBIAS_MAX_ENTRIES], [SEQBIAS_MAX_ENTRIES + 1]
+  const int* pre_ids;                      // [SEQBIAS_MAX_IDS]
+  const int* out_ids; int out_stride;      // [S][out_stride] the ids generated so far
+  const int* step_count;                   // [S]
+};
+const char* launch_seqbias_apply(const SeqBiasArgs& a, hipStream_t s);
+// The tables as ONE block of 32-bit words at fixed offsets (so one device buffer of fixed size holds any list), laid out on the host:
+// entries sorted stably by target id, the one-token entry of a target first.
+constexpr size_t SEQBIAS_OFF_TARGET = 4, SEQBIAS_OFF_BEGIN = SEQBIAS_OFF_TARGET + SEQBIAS_MAX_ENTRIES,
+                 SEQBIAS_OFF_BIAS = SEQBIAS_OFF_BEGIN + SEQBIAS_MAX_ENTRIES + 1, SEQBIAS_OFF_PRE_OFF = SEQBIAS_OFF_BIAS + SEQBIAS_MAX_ENTRIES,
+                 SEQBIAS_OFF_PRE_IDS = SEQBIAS_OFF_PRE_OFF + SEQBIAS_MAX_ENTRIES + 1, SEQBIAS_TABLE_WORDS = SEQBIAS_OFF_PRE_IDS + SEQBIAS_MAX_IDS;
+// the kernel's table pointers into a device copy of that block (engine_internal.h seqbias_layout writes it)
+inline void seqbias_point(SeqBiasArgs& a, const void* table_dev) {
+  const int* const w = static_cast<const int*>(table_dev);
+  a.params = w; a.grp_target = w + SEQBIAS_OFF_TARGET; a.grp_begin = w + SEQBIAS_OFF_BEGIN;
+  a.ent_bias = reinterpret_cast<const float*>(w + SEQBIAS_OFF_BIAS); a.ent_pre_off = w + SEQBIAS_OFF_PRE_OFF; a.pre_ids = w + SEQBIAS_OFF_PRE_IDS;
+}
+
 }  // namespace q3a

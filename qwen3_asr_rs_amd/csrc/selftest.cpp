@@ -336,6 +336,53 @@ int32_t q3a_selftest_repeat(int32_t device, const float* logits, int32_t S, int3
   Q3A_CATCH(nullptr)
 }
 
+// a step's tail with q3a_set_sequence_bias on, as the engine enqueues it without repetition control and without sampling: the list laid
+// out by the setter's own function, launch_seqbias_apply on the stored rows, fresh argmax partials (with the log-sum channel) over the
+// rewritten rows, argmax_finalize on those
+int32_t q3a_selftest_seqbias(int32_t device, const float* logits, int32_t S, int32_t V, const int32_t* hist, int32_t stride, const int32_t* lens,
+                             const int32_t* seq_ids, const int32_t* seq_lens, const float* seq_bias, int32_t n, float* out_logits,
+                             int32_t* out_ids, float* out_lp) {
+  Q3A_TRY(nullptr)
+  const char* what = "q3a_selftest_seqbias";
+  if (!logits || !lens || S < 1 || V < 1 || stride < 0 || stride > (1 << 20) || (stride > 0 && !hist)) fail(std::string(what) + ": bad argument");
+  const SeqBiasTable tb = seqbias_layout(what, seq_ids, seq_lens, seq_bias, n, V);
+  const size_t Sz = S, pitch = (size_t)stride + 1;  // (one more column than any history: finalize writes the chosen id behind it)
+  std::vector<int> ids(Sz * pitch, -1);
+  for (size_t s = 0; s < Sz; ++s) {
+    if (lens[s] < 0 || lens[s] > stride) fail(std::string(what) + ": a history length outside [0, stride]");
+    for (int i = 0; i < lens[s]; ++i) {
+      const int id = hist[s * stride + i];
+      if (id < 0 || id >= V) fail(std::string(what) + ": a history id outside the vocabulary");
+      ids[s * pitch + i] = id;
+    }
+  }
+  use_device(device);
+  constexpr int H = 4, NP = 128;  // finalize embeds the chosen id: a token table of zeros, four columns wide
+  const DevBuf dLg = to_device(logits, Sz * V), dTab = to_device(tb.words), dSc = to_device(lens, Sz), dIds = to_device(ids);
+  const DevBuf dPv = room(Sz * NP * 4), dPi = room(Sz * NP * 4), dPs = room(Sz * NP * 4);
+  const DevBuf dEmb = to_device(std::vector<uint16_t>((size_t)V * H, 0)), dX = room(Sz * H * 4), dTok = room(Sz * 4);
+  const DevBuf dLp = to_device(std::vector<float>(Sz * pitch, 0.f));
+  const DevBuf dPos = to_device(std::vector<int>(Sz, 0)), dDone = to_device(std::vector<uint8_t>(Sz, 0));
+  SeqBiasArgs sa{};
+  sa.logits = dLg.as<float>(); sa.S = S; sa.V = V; seqbias_point(sa, dTab.p);
+  sa.out_ids = dIds.as<int>(); sa.out_stride = (int)pitch; sa.step_count = dSc.as<int>();
+  KCHK(launch_seqbias_apply(sa, nullptr));
+  const ArgmaxPartials part{dPv.as<float>(), dPi.as<int>(), dPs.as<float>(), NP};
+  KCHK(launch_argmax_partials(sa.logits, V, S, part, NP, nullptr));
+  FinalizeArgs f{};
+  f.part = part; f.n_part = NP; f.V = V; f.advance = 1;
+  f.c = bare_commit(S, dTok, dIds.as<int>(), (int)pitch, dLp.as<float>(), dSc, dPos, dDone, dEmb.as<uint16_t>(), H, dX.as<float>(), kEos0, kEos1);
+  KCHK(launch_argmax_finalize(f, S, nullptr));
+  finish();
+  if (out_logits) to_host(out_logits, dLg, Sz * V);
+  if (out_ids) to_host(out_ids, dTok, Sz);
+  if (out_lp) {
+    const std::vector<float> lp = to_host<float>(dLp, Sz * pitch);
+    for (size_t s = 0; s < Sz; ++s) out_lp[s] = lp[s * pitch + lens[s]];
+  }
+  Q3A_CATCH(nullptr)
+}
+
 int32_t q3a_selftest_gemv_launch(int32_t device, int32_t pruned, const uint16_t* w, int32_t N, int32_t K, const float* x, const float* rms_w, float eps,
                                  const float* bias, int32_t mode, const float* resid, const float* attn_pm, const float* attn_pl, const float* attn_po,
                                  int32_t attn_nsplit, int32_t attn_heads, float* out, int32_t* out_state) {

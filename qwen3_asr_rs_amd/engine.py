@@ -116,6 +116,139 @@ def check_repetition_args(repetition_penalty: float = 1.0, no_repeat_ngram_size:
     return p, int(n)
 
 
+SEQUENCE_BIAS_MAX_ENTRIES, SEQUENCE_BIAS_MAX_LEN, SEQUENCE_BIAS_MAX_IDS = 4096, 32, 65536
+
+
+def _sequence_bias_pairs(entries) -> List[Tuple[tuple, float]]:
+    """entries as a list of (ids, bias) pairs: from a mapping {tuple of ids: bias} or an iterable of (ids, bias); None: no entry."""
+    if entries is None:
+        return []
+    items = entries.items() if isinstance(entries, Mapping) else entries
+    out = []
+    for item in items:
+        try:
+            seq, b = item
+            out.append((tuple(seq), b))
+        except (TypeError, ValueError):
+            raise Q3aError(f"sequence_bias: an entry must be (ids, bias), got {item!r}")
+    return out
+
+
+def check_sequence_bias(entries, vocab: int):
+    """The refusals of q3a_set_sequence_bias that need no engine (pure host function): every entry 1 to 32 integer ids inside the
+    vocabulary with a bias that is finite or -inf, no sequence twice, at most 4096 entries and 65536 ids.  `entries` is a mapping
+    {tuple of ids: bias} or an iterable of (ids, bias) pairs, in the order the biases are to be added.  Returns (ids int32, the
+    entries' ids one after the other; lens int32; bias float32) as the C call takes them."""
+    pairs = _sequence_bias_pairs(entries)
+    if len(pairs) > SEQUENCE_BIAS_MAX_ENTRIES:
+        raise Q3aError(f"sequence_bias: {len(pairs)} entries, more than {SEQUENCE_BIAS_MAX_ENTRIES}")
+    ids, lens, bias, seen = [], [], [], set()
+    for i, (seq, b) in enumerate(pairs):
+        if not 1 <= len(seq) <= SEQUENCE_BIAS_MAX_LEN:
+            raise Q3aError(f"sequence_bias: entry {i} has {len(seq)} ids (1 to {SEQUENCE_BIAS_MAX_LEN})")
+        for t in seq:
+            if isinstance(t, bool) or not isinstance(t, (int, np.integer)):
+                raise Q3aError(f"sequence_bias: id {t!r} of entry {i} is not an integer")
+            if not 0 <= int(t) < vocab:
+                raise Q3aError(f"sequence_bias: id {int(t)} of entry {i} is outside the vocabulary ({vocab})")
+        seq = tuple(int(t) for t in seq)
+        if seq in seen:
+            raise Q3aError(f"sequence_bias: entry {i} repeats the sequence of an earlier entry")
+        seen.add(seq)
+        try:
+            b = float(b)
+        except (TypeError, ValueError):
+            raise Q3aError(f"sequence_bias: the bias of entry {i} must be a number")
+        if math.isnan(b) or b == math.inf:
+            raise Q3aError(f"sequence_bias: the bias of entry {i} is NaN or +inf (finite or -inf only)")
+        ids += seq
+        lens.append(len(seq))
+        bias.append(b)
+    if len(ids) > SEQUENCE_BIAS_MAX_IDS:
+        raise Q3aError(f"sequence_bias: {len(ids)} ids over all entries, more than {SEQUENCE_BIAS_MAX_IDS}")
+    return np.asarray(ids, dtype=np.int32), np.asarray(lens, dtype=np.int32), np.asarray(bias, dtype=np.float32)
+
+
+def _sequence_list_call(fn, *front) -> List[Tuple[tuple, float]]:
+    """One of the C helpers that return a sequence-bias list (sized by a first call with no room)."""
+    lib = _lib.load()
+    n_ids, n = C.c_int32(), C.c_int32()
+    if fn(*front, None, 0, None, None, 0, C.byref(n_ids), C.byref(n)) != 0:
+        raise Q3aError((lib.q3a_last_error(None) or b"").decode())
+    ids, lens, bias = np.zeros(max(n_ids.value, 1), np.int32), np.zeros(max(n.value, 1), np.int32), np.zeros(max(n.value, 1), np.float32)
+    if fn(*front, _i32p(ids), n_ids.value, _i32p(lens), _f32p(bias), n.value, C.byref(n_ids), C.byref(n)) != 0:
+        raise Q3aError((lib.q3a_last_error(None) or b"").decode())
+    out, o = [], 0
+    for k in range(n.value):
+        out.append((tuple(int(t) for t in ids[o:o + lens[k]]), float(bias[k])))
+        o += int(lens[k])
+    return out
+
+
+def parse_sequence_bias(text: str) -> List[Tuple[tuple, float]]:
+    """q3a_parse_sequence_bias: lines "bias id id ..." ('#' comments, "-inf") -> [(ids, bias)].  Host only."""
+    return _sequence_list_call(_lib.load().q3a_parse_sequence_bias, text.encode())
+
+
+def _phrase_array(phrases):
+    ps = [phrases] if isinstance(phrases, str) else list(phrases)
+    return (C.c_char_p * max(len(ps), 1))(*[p.encode("utf-8") for p in ps]), ps
+
+
+def _phrase_tokenisations(tokenizer, phrase: str, what: str) -> List[List[int]]:
+    p = phrase.strip()
+    if not p:
+        raise Q3aError(f"{what}: an empty phrase")
+    out = []
+    for text in (p, " " + p):
+        ids = [int(t) for t in tokenizer.encode(text)]
+        if not ids:
+            raise Q3aError(f"{what}: phrase '{p}' encodes to no id")
+        if len(ids) > SEQUENCE_BIAS_MAX_LEN:
+            raise Q3aError(f"{what}: phrase '{p}' encodes to {len(ids)} ids, more than {SEQUENCE_BIAS_MAX_LEN}")
+        out.append(ids)
+    return out
+
+
+def _merge_sequences(pairs) -> List[Tuple[tuple, float]]:
+    table = {}
+    for seq, b in pairs:
+        table[seq] = max(table[seq], b) if seq in table else b
+    return list(table.items())
+
+
+def hotword_sequences(tokenizer, phrases, boost: float, start_boost: float = 0.0) -> List[Tuple[tuple, float]]:
+    """q3a_hotword_sequences: the sequence-bias entries that boost `phrases`.  For each phrase both tokenisations, encode(phrase) and
+    encode(" " + phrase); for each tokenisation p_0 .. p_{L-1} the entries (p_0 .. p_j), j = 1 .. L-1, with bias `boost`, and, when
+    start_boost != 0, also (p_0) with start_boost.  Equal sequences are merged, keeping the larger bias; a phrase over 32 ids is
+    refused by name.  No boost value has been tuned on real weights: `boost` has no default.  An AsrTokenizer goes through the C
+    helper; any other object with encode(text) through the same rule in Python."""
+    boost, start_boost = float(boost), float(start_boost)
+    if not (math.isfinite(boost) and math.isfinite(start_boost)):
+        raise Q3aError("hotword_sequences: boost and start_boost must be finite")
+    if isinstance(tokenizer, AsrTokenizer):
+        arr, ps = _phrase_array(phrases)
+        return _sequence_list_call(_lib.load().q3a_hotword_sequences, tokenizer._h, arr, len(ps), C.c_float(boost), C.c_float(start_boost))
+    pairs = []
+    for phrase in ([phrases] if isinstance(phrases, str) else phrases):
+        for p in _phrase_tokenisations(tokenizer, phrase, "hotword_sequences"):
+            if start_boost != 0.0:
+                pairs.append((tuple(p[:1]), start_boost))
+            pairs += [(tuple(p[:j + 1]), boost) for j in range(1, len(p))]
+    return _merge_sequences(pairs)
+
+
+def banned_sequences(tokenizer, phrases) -> List[Tuple[tuple, float]]:
+    """q3a_banned_sequences: both tokenisations of each phrase, whole, at -inf (equal sequences once)."""
+    if isinstance(tokenizer, AsrTokenizer):
+        arr, ps = _phrase_array(phrases)
+        return _sequence_list_call(_lib.load().q3a_banned_sequences, tokenizer._h, arr, len(ps))
+    pairs = []
+    for phrase in ([phrases] if isinstance(phrases, str) else phrases):
+        pairs += [(tuple(p), -math.inf) for p in _phrase_tokenisations(tokenizer, phrase, "banned_sequences")]
+    return _merge_sequences(pairs)
+
+
 def check_draft_ids(draft, vocab: int, max_new: int) -> List[int]:
     """The refusals of q3a_prefill_draft / q3a_transcribe_draft_batch_ptrs that need no engine (pure host function): every id an
     integer inside the vocabulary, none of them <|audio_pad|> or an EOS id, at most max_new of them.  Returns the ids as a list."""
@@ -242,6 +375,7 @@ class HipEngine:
         self.logit_bias_state: Tuple[Optional[dict], float] = (None, 0.0)  # what set_logit_bias was last given
         self.sampling_state: Tuple[float, float, int] = (0.0, 0.0, 0)  # what set_sampling was last given
         self.repetition_state: Tuple[float, int] = (1.0, 0)  # what set_repetition was last given
+        self.sequence_bias_state: List[Tuple[tuple, float]] = []  # what set_sequence_bias was last given, as (ids, bias) pairs
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -607,6 +741,22 @@ class HipEngine:
         st = self.debug_read_raw("repetition").view(np.uint32)
         return {"active": bool(st[0]), "repetition_penalty": float(st[1:2].view(np.float32)[0]), "no_repeat_ngram_size": int(st[2])}
 
+    # ---- sequence bias: hotword boosts and banned phrases ------------------------------------------------------
+    def set_sequence_bias(self, entries=None):
+        """q3a_set_sequence_bias: `entries` is a mapping {tuple of ids: bias} or an iterable of (ids, bias) pairs; at every generation
+        step the bias of an entry is added to the logit of its last id whenever the ids the sequence has generated so far end in the
+        rest of the entry -- on the device, on the sequence's own out_ids, bit for bit HuggingFace's SequenceBiasLogitsProcessor
+        (NoBadWordsLogitsProcessor with a bias of -inf).  None / an empty list turns it off.  hotword_sequences() and
+        banned_sequences() build entries from phrases.  Drops the decode state: prefill again before a stage-API step."""
+        ids, lens, bias = check_sequence_bias(entries, self.dims.vocab_size)
+        n = len(lens)
+        self._chk(self._lib.q3a_set_sequence_bias(self._h, _i32p(ids) if n else None, _i32p(lens) if n else None, _f32p(bias) if n else None, n))
+        self.sequence_bias_state = _sequence_bias_pairs(entries)
+
+    def sequence_bias_stats(self) -> dict:
+        st = self.debug_read_raw("sequence_bias").view(np.int32)
+        return {"active": bool(st[0]), "entries": int(st[1]), "ids": int(st[2]), "targets": int(st[3])}
+
     # ---- beam search ----------------------------------------------------------------------------------
     def _beam_unpack(self, U, W, stride, ids, lens, scores, fin, lp) -> "List[List[BeamHypothesis]]":
         res = []
@@ -858,7 +1008,9 @@ class AsrInference:
                    logit_bias: Optional[Mapping[int, float]] = None, allowed_tokens: Optional[Iterable[int]] = None,
                    temperature=0.0, min_p: float = 0.0, seed: int = 0, logprob_threshold: float = -1.0,
                    compression_ratio_threshold: float = 2.4, repetition_penalty: float = 1.0,
-                   no_repeat_ngram_size: int = 0, draft=None) -> TranscribeResult:
+                   no_repeat_ngram_size: int = 0, draft=None, hotwords: Optional[Iterable[str]] = None,
+                   hotword_boost: Optional[float] = None, hotword_start_boost: float = 0.0,
+                   banned_phrases: Optional[Iterable[str]] = None, sequence_bias=None) -> TranscribeResult:
         """src/inference.rs:89-213.  `audio`: path to a WAV file or a 16 kHz float32 array.  beam_size > 1: a beam search of that
         width instead of the greedy loop; `alternatives` holds its hypotheses ordered by score / max(len, 1) ** length_penalty
         (float64 on the host; 0: the search's own order) and the result is the first of them.
@@ -875,7 +1027,19 @@ class AsrInference:
         text convention: it needs `language`, and the ids are encode("<asr_text>" + text)).  The result is the greedy result; the ids of
         the draft the greedy loop would have written itself are verified in one prefill instead of decoded one by one, and
         `accepted_draft_tokens` says how many that were.  Composes with suppress_tokens / logit_bias / allowed_tokens; raises Q3aError
-        with beam_size > 1, a temperature > 0 or repetition control."""
+        with beam_size > 1, a temperature > 0 or repetition control.
+        hotwords / banned_phrases / sequence_bias: a sequence bias for this call (HipEngine.set_sequence_bias; the engine's own list is
+        restored afterwards).  hotwords: phrases to boost -- hotword_sequences(tokenizer, hotwords, hotword_boost,
+        hotword_start_boost); hotword_boost has NO default and is required with hotwords: no value has been tuned on real weights.
+        banned_phrases: phrases never to write -- the two tokenisations of each at -inf.  sequence_bias: entries given as ids, a
+        mapping {tuple of ids: bias} or (ids, bias) pairs.  The three are concatenated in that order; a sequence named twice keeps the
+        larger bias.  Composes with temperature, repetition_penalty, no_repeat_ngram_size and the logit-bias arguments; raises
+        Q3aError with beam_size > 1 or a draft."""
+        seq_entries = self._sequence_bias_entries(hotwords, hotword_boost, hotword_start_boost, banned_phrases, sequence_bias)
+        if seq_entries is not None and beam_size > 1:
+            raise Q3aError("transcribe: beam search has no sequence bias (beam_size > 1 with hotwords / banned_phrases / sequence_bias)")
+        if seq_entries is not None and draft is not None:
+            raise Q3aError("transcribe: a draft cannot be verified under a sequence bias (draft with hotwords / banned_phrases / sequence_bias)")
         rep_args = check_repetition_args(repetition_penalty, no_repeat_ngram_size)
         if beam_size > 1 and rep_args != (1.0, 0):
             raise Q3aError("transcribe: beam search has no repetition control (beam_size > 1 with repetition_penalty / no_repeat_ngram_size)")
@@ -917,6 +1081,16 @@ class AsrInference:
                     return inner()
                 finally:
                     reng.set_repetition(*before)
+        if seq_entries is not None:
+            inner_sb, seng = run, self.engine
+
+            def run():
+                before = seng.sequence_bias_state
+                seng.set_sequence_bias(seq_entries)
+                try:
+                    return inner_sb()
+                finally:
+                    seng.set_sequence_bias(before)
         if suppress_tokens is None and logit_bias is None and allowed_tokens is None:
             return run()
         ids, bias, default = compose_logit_bias(self.engine.dims.vocab_size, suppress_tokens, logit_bias, allowed_tokens)
@@ -926,6 +1100,30 @@ class AsrInference:
             return run()
         finally:
             self.engine.set_logit_bias(*before)
+
+    def _sequence_bias_entries(self, hotwords, hotword_boost, hotword_start_boost, banned_phrases, sequence_bias):
+        """The call's sequence-bias entries, checked; None when none of the arguments was given."""
+        if hotwords is None and banned_phrases is None and sequence_bias is None:
+            if hotword_boost is not None:
+                raise Q3aError("transcribe: hotword_boost without hotwords")
+            return None
+        pairs = []
+        if hotwords is not None:
+            if hotword_boost is None:
+                raise Q3aError("transcribe: hotwords need hotword_boost (it has no default: no value has been tuned on real weights)")
+            if self.tokenizer is None:
+                raise Q3aError("hotwords need tokenizer.json (src/inference.rs:246-251)")
+            pairs += hotword_sequences(self.tokenizer, hotwords, hotword_boost, hotword_start_boost)
+        elif hotword_boost is not None:
+            raise Q3aError("transcribe: hotword_boost without hotwords")
+        if banned_phrases is not None:
+            if self.tokenizer is None:
+                raise Q3aError("banned_phrases need tokenizer.json (src/inference.rs:246-251)")
+            pairs += banned_sequences(self.tokenizer, banned_phrases)
+        pairs += _sequence_bias_pairs(sequence_bias)
+        pairs = _merge_sequences(pairs)
+        check_sequence_bias(pairs, self.engine.dims.vocab_size)
+        return pairs
 
     def _draft_ids(self, draft, language, max_new_tokens) -> List[int]:
         if isinstance(draft, TranscribeResult):
