@@ -802,6 +802,19 @@ int32_t q3a_selftest_batched_attn_launch(int32_t device, int32_t kv_f32, int32_t
                                          const float* q_norm, const float* k_norm, float eps, const float* rope_cur, void* kcache, void* vcache,
                                          int32_t n_q, int32_t n_kv, int32_t max_ctx, float scale_div, int32_t trim_prologue, int32_t nsplit,
                                          int32_t keys_per_split, int32_t out_form, void* out, float* pm, float* pl, float* po);
+/* One launch of the segment attention (encoder windows, causal prefill) on the caller's data.  launcher 0: launch_attn_enc, 1:
+ * launch_attn_prefill(group, kv_f32), 2: launch_fattn_enc, 3: launch_fattn_prefill(group).  Segment i has seg_len[i] queries / keys, its q
+ * and output rows start at seg_q_row0[i], its keys at element seg_kv_off[i] of K / V.  q fp32 and / or q16 bf16, [q_rows][q_rs]; k and v are
+ * buffers of kv_elems elements (fp32 with kv_f32, else bf16 bits) whose element k_base / v_base is what the launch is given as K / V (the
+ * encoder's interleaved [rows][3 D] buffer: the same array three times, bases D and 2 D); head stride kv_hs, row stride kv_rs.  The output
+ * (o fp32 or o16 bf16, [o_rows][o_rs]) goes up with the caller's content between guard zones and comes back whole.  The call fails when
+ * the launcher refuses (its message is the error), when an index would leave a buffer, or when a byte of k or v changed.  form[12]: MFMA
+ * (1) or VALU (0) family, DMA kernel, HD, GROUP, CAUSAL, fp32 K/V, KSPLIT, NS, QPW, grid x, y, z of the instantiation launched. */
+int32_t q3a_selftest_seg_attn_launch(int32_t device, int32_t launcher, int32_t kv_f32, int32_t group, const int32_t* seg_q_row0, const int32_t* seg_len,
+                                     const int64_t* seg_kv_off, int32_t n_segs, int32_t max_len, const float* q, const uint16_t* q16, int32_t q_rows,
+                                     int32_t q_rs, const void* k, const void* v, int64_t kv_elems, int64_t k_base, int64_t v_base, int64_t kv_hs,
+                                     int32_t kv_rs, int32_t n_kv_heads, float scale_div, float* o, uint16_t* o16, int32_t o_rows, int32_t o_rs,
+                                     int32_t* form);
 /* Rows [0, M1) of an M x N bf16 GEMM that launch_gemm256 gives to the 256 x 256 kernel when it hands the trailing rows to the small
  * tiles (wave quantisation; 0: no split).  Host arithmetic, no device needed. */
 int32_t q3a_gemm256_split_rows(int32_t M, int32_t N);

@@ -30,7 +30,7 @@ SYMBOLS = [
     "q3a_selftest_gemm_launch", "q3a_selftest_qkrope_launch", "q3a_gemm256_split_rows",
     "q3a_selftest_gemv_launch", "q3a_selftest_decode_attn_launch",
     "q3a_selftest_decode_attn_split_launch", "q3a_selftest_oproj_head_launch", "q3a_selftest_gemv_parts_launch",
-    "q3a_selftest_skinny_launch", "q3a_selftest_batched_attn_launch",
+    "q3a_selftest_skinny_launch", "q3a_selftest_batched_attn_launch", "q3a_selftest_seg_attn_launch",
     "q3a_prefill_draft", "q3a_transcribe_draft_batch_ptrs", "q3a_draft_next_round", "q3a_selftest_draft_accept",
 ]
 
@@ -178,6 +178,8 @@ def load() -> C.CDLL:
         "q3a_selftest_gemv_parts_launch": (i32, [i32, P, i32, i32, P, P, C.c_float, P, P, i32, P, P]),
         "q3a_selftest_skinny_launch": (i32, [i32, P, i32, i32, i32, P, i32, P, P, i32, P, P, i32, C.c_float, P, i32, P, P, P, i32, i32, P, P, P, i32, i32, i32, P]),
         "q3a_selftest_batched_attn_launch": (i32, [i32, i32, i32, i32, P, P, P, P, C.c_float, P, P, P, i32, i32, i32, C.c_float, i32, i32, i32, i32, P, P, P, P]),
+        "q3a_selftest_seg_attn_launch": (i32, [i32, i32, i32, i32, P, P, P, i32, i32, P, P, i32, i32, P, P, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                               i32, i32, C.c_float, P, P, i32, i32, P]),
         "q3a_gemm256_split_rows": (i32, [i32, i32]),
         "q3a_prefill_draft": (i32, [P, i32p, i32p, i32p, i32p, i32, i32p, i32p, f32p]),
         "q3a_transcribe_draft_batch_ptrs": (i32, [P, C.POINTER(P), i64p, i32, i32p, i32, i32p, i32p, i32, i32, i32, i32p, i32, i32p, i32p]),

@@ -149,21 +149,28 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
   }
 }
 
+// Every launch goes through here: the instantiation that runs and the one attn_last_form() reports are the same template arguments.
+thread_local AttnForm last_form{};
 template <int HD, int GROUP, bool CAUSAL, typename KVT, int QPW>
 void launch_t(const AttnArgs& a, hipStream_t s) {
   dim3 grid((a.max_len + 4 * QPW - 1) / (4 * QPW), a.n_kv_heads, a.n_segs);
+  last_form = AttnForm{HD, GROUP, CAUSAL, sizeof(KVT) == 4, QPW, (int)grid.x, (int)grid.y, (int)grid.z};
   hipLaunchKernelGGL((attn_kernel<HD, GROUP, CAUSAL, KVT, QPW>), grid, dim3(256), 0, s, a);
 }
 
 }  // namespace
 
+AttnForm attn_last_form() { return last_form; }
+
 const char* launch_attn_enc(const AttnArgs& a, hipStream_t s) {
+  last_form = AttnForm{};
   if (a.n_segs <= 0) return nullptr;
   launch_t<64, 1, false, float, 8>(a, s);
   return nullptr;
 }
 
 const char* launch_attn_prefill(const AttnArgs& a, int group, bool kv_f32, hipStream_t s) {
+  last_form = AttnForm{};
   if (a.n_segs <= 0) return nullptr;
   if (group == 1) {
     if (kv_f32) launch_t<128, 1, true, float, 4>(a, s); else launch_t<128, 1, true, uint16_t, 4>(a, s);

@@ -543,6 +543,10 @@ __global__ __launch_bounds__(256, NS == 3 ? 3 : 2) void fattn_dma_kernel(AttnArg
   }
 }
 
+// Every launch goes through launch_dma / launch_f: the instantiation that runs and the one fattn_last_form() reports are the same
+// template arguments.
+thread_local FattnForm last_form{};
+
 template <int HD, int GROUP, bool CAUSAL>
 void launch_dma(const AttnArgs& a, hipStream_t s) {
   constexpr int QT = 32 * (4 / GROUP);
@@ -551,6 +555,7 @@ void launch_dma(const AttnArgs& a, hipStream_t s) {
   static const int ns = [] { const char* e = getenv("Q3A_FATTN_NS"); return e ? atoi(e) : 3; }();
   // (round 5's hand-pipelined form of this kernel -- second score register set, softmax of tile t between the QK MFMAs of tile t + 1 --
   // was bit-identical and slower, 64.2 vs 60.5 us per prefill layer; removed in round 6, docs/HISTORY.md, last present at commit caf7a05)
+  last_form = FattnForm{1, HD, GROUP, CAUSAL, 0, 1, ns == 4 ? 4 : 3, (int)grid.x, (int)grid.y, (int)grid.z};
   if (ns == 4) hipLaunchKernelGGL((fattn_dma_kernel<HD, GROUP, CAUSAL, 4>), grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL((fattn_dma_kernel<HD, GROUP, CAUSAL, 3>), grid, dim3(256), 0, s, a);
 }
@@ -573,12 +578,16 @@ template <int HD, int GROUP, bool CAUSAL, typename KVT, int KSPLIT = 1>
 void launch_f(const AttnArgs& a, hipStream_t s) {
   constexpr int QT = 32 * (4 / (GROUP * KSPLIT));
   dim3 grid((a.max_len + QT - 1) / QT, a.n_kv_heads, a.n_segs);
+  last_form = FattnForm{0, HD, GROUP, CAUSAL, sizeof(KVT) == 4, KSPLIT, 0, (int)grid.x, (int)grid.y, (int)grid.z};
   hipLaunchKernelGGL((fattn_kernel<HD, GROUP, CAUSAL, KVT, KSPLIT>), grid, dim3(256), 0, s, a);
 }
 
 }  // namespace
 
+FattnForm fattn_last_form() { return last_form; }
+
 const char* launch_fattn_enc(const AttnArgs& a, hipStream_t s) {
+  last_form = FattnForm{};
   if (a.n_segs <= 0) return nullptr;
   if (a.q_rs % 4 != 0 || a.kv_rs % 4 != 0 || a.o_rs % 4 != 0) return "fattn: row strides must be multiples of 4";
   if (a.q16) {  // bf16 q/k/v projections (k and v point into the same bf16 buffer)
@@ -592,6 +601,7 @@ const char* launch_fattn_enc(const AttnArgs& a, hipStream_t s) {
 }
 
 const char* launch_fattn_prefill(const AttnArgs& a, int group, hipStream_t s) {
+  last_form = FattnForm{};
   if (a.n_segs <= 0) return nullptr;
   if (a.q_rs % 4 != 0 || a.o_rs % 4 != 0) return "fattn: row strides must be multiples of 4";
   if (a.q16 && a.q_rs % 8 != 0) return "fattn: bf16 q row stride must be a multiple of 8";

@@ -199,6 +199,12 @@ const char* launch_attn_prefill(const AttnArgs& a, int group, bool kv_f32, hipSt
 // MFMA flash-attention versions of the two above (k_fattn.hip): bf16 operands, default mode only
 const char* launch_fattn_enc(const AttnArgs& a, hipStream_t s);                 // fp32 K/V rounded to bf16 while staging
 const char* launch_fattn_prefill(const AttnArgs& a, int group, hipStream_t s);  // bf16 KV cache
+// The instantiation the last launch_attn_* / launch_fattn_* call of this thread launched (all zero: none -- an empty batch or a refusal).
+// Tests compare it with the form they mean to run: the launchers pick by pointer alignment, strides, shape and knobs read once per process.
+struct AttnForm { int hd, group, causal, kv_f32, qpw, grid_x, grid_y, grid_z; };
+AttnForm attn_last_form();
+struct FattnForm { int dma, hd, group, causal, kv_f32, ksplit, ns, grid_x, grid_y, grid_z; };  // dma 1: fattn_dma_kernel with NS stages; 0: fattn_kernel (ns 0)
+FattnForm fattn_last_form();
 
 // ---- decoder glue (k_decode.hip) ----------------------------------------------------------------------------
 // hidden[r] = embed[ids[r]] for rows whose id is not `skip_id` (audio rows are written by the encoder tail)

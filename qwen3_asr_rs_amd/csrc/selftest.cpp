@@ -661,6 +661,76 @@ int32_t q3a_selftest_batched_attn_launch(int32_t device, int32_t kv_f32, int32_t
   Q3A_CATCH(nullptr)
 }
 
+int32_t q3a_selftest_seg_attn_launch(int32_t device, int32_t launcher, int32_t kv_f32, int32_t group, const int32_t* seg_q_row0, const int32_t* seg_len,
+                                     const int64_t* seg_kv_off, int32_t n_segs, int32_t max_len, const float* q, const uint16_t* q16, int32_t q_rows,
+                                     int32_t q_rs, const void* k, const void* v, int64_t kv_elems, int64_t k_base, int64_t v_base, int64_t kv_hs,
+                                     int32_t kv_rs, int32_t n_kv_heads, float scale_div, float* o, uint16_t* o16, int32_t o_rows, int32_t o_rs,
+                                     int32_t* form) {
+  Q3A_TRY(nullptr)
+  const char* what = "q3a_selftest_seg_attn_launch";
+  const bool mfma = launcher >= 2, enc = launcher == 0 || launcher == 2;
+  if (launcher < 0 || launcher > 3 || !seg_q_row0 || !seg_len || !seg_kv_off || !k || !v || !form || n_segs < 1 || n_segs > 4096 || max_len < 1 ||
+      q_rows < 1 || q_rs < 1 || o_rows < 1 || o_rs < 1 || kv_elems < 1 || k_base < 0 || v_base < 0 || kv_hs < 0 || kv_rs < 1 || n_kv_heads < 1 ||
+      n_kv_heads > 64 || group < 1 || group > 8 || !(scale_div > 0.f))
+    fail(std::string(what) + ": bad argument");
+  if (enc && group != 1) fail(std::string(what) + ": the encoder form has one query head per K/V head");
+  if ((o != nullptr) == (o16 != nullptr) || (!mfma && (o16 || q16 || !q)) || (!q && !q16)) fail(std::string(what) + ": one of o / o16 and q and / or q16 (bf16: the MFMA launchers only)");
+  // the K/V element type each launcher reads: fp32 windows (bf16 with q16) in the encoder, the cache's type in the prefill
+  if ((kv_f32 != 0) != (launcher == 0 || (launcher == 1 && kv_f32) || (launcher == 2 && !q16))) fail(std::string(what) + ": kv_f32 does not name what this launcher reads");
+  // every index the launch will form is checked here or by the launcher's own check: a refusal, never an access outside a buffer
+  const int HD = enc ? 64 : 128, al = kv_f32 ? 4 : 8;
+  const long cols = (long)n_kv_heads * group * HD;
+  if (cols > q_rs || cols > o_rs || HD > kv_rs) fail(std::string(what) + ": a row stride below the row");
+  if (k_base % al || v_base % al || kv_hs % al || (launcher != 2 && kv_rs % al)) fail(std::string(what) + ": K/V offsets and strides in whole 16-byte groups");
+  std::vector<AttnSeg> segs(n_segs);
+  int longest = 0;
+  for (int i = 0; i < n_segs; ++i) {
+    const int r0 = seg_q_row0[i], len = seg_len[i];
+    const int64_t off = seg_kv_off[i];
+    if (r0 < 0 || len < 1 || (long)r0 + len > q_rows || (long)r0 + len > o_rows) fail(std::string(what) + ": a segment's rows lie outside q or the output");
+    if (off < 0 || off % al || std::max(k_base, v_base) + off + (int64_t)(n_kv_heads - 1) * kv_hs + (int64_t)(len - 1) * kv_rs + HD > kv_elems)
+      fail(std::string(what) + ": a segment's keys lie outside K / V");
+    segs[i] = AttnSeg{r0, len, off};
+    longest = std::max(longest, len);
+  }
+  if (max_len < longest || max_len > (1 << 20)) fail(std::string(what) + ": max_len below the longest segment");
+  use_device(device);
+  const size_t eb = kv_f32 ? 4 : 2, n_q = (size_t)q_rows * q_rs, n_o = (size_t)o_rows * o_rs;
+  const DevBuf dK = to_device((const uint8_t*)k, (size_t)kv_elems * eb), dV = to_device((const uint8_t*)v, (size_t)kv_elems * eb), dSeg = to_device(segs);
+  DevBuf dQ, dQ16;
+  if (q) dQ = to_device(q, n_q);
+  if (q16) dQ16 = to_device(q16, n_q);
+  const Guarded dO(o ? (const void*)o : (const void*)o16, n_o * (o ? 4 : 2));
+  AttnArgs a{};
+  a.q = dQ.as<float>(); a.q_rs = q_rs; a.q16 = dQ16.as<uint16_t>();
+  a.k = static_cast<const uint8_t*>(dK.p) + k_base * eb; a.v = static_cast<const uint8_t*>(dV.p) + v_base * eb; a.kv_hs = kv_hs; a.kv_rs = kv_rs;
+  if (o) a.o = dO.as<float>(); else a.o16 = dO.as<uint16_t>();
+  a.o_rs = o_rs; a.segs = dSeg.as<AttnSeg>(); a.n_segs = n_segs; a.max_len = max_len; a.n_kv_heads = n_kv_heads; a.scale_div = scale_div;
+  switch (launcher) {
+    case 0: KCHK(launch_attn_enc(a, nullptr)); break;
+    case 1: KCHK(launch_attn_prefill(a, group, kv_f32 != 0, nullptr)); break;
+    case 2: KCHK(launch_fattn_enc(a, nullptr)); break;
+    default: KCHK(launch_fattn_prefill(a, group, nullptr)); break;
+  }
+  int rep[12] = {0};
+  if (mfma) {
+    const FattnForm f = fattn_last_form();
+    const int r[12] = {1, f.dma, f.hd, f.group, f.causal, f.kv_f32, f.ksplit, f.ns, 0, f.grid_x, f.grid_y, f.grid_z};
+    memcpy(rep, r, sizeof rep);
+  } else {
+    const AttnForm f = attn_last_form();
+    const int r[12] = {0, 0, f.hd, f.group, f.causal, f.kv_f32, 1, 0, f.qpw, f.grid_x, f.grid_y, f.grid_z};
+    memcpy(rep, r, sizeof rep);
+  }
+  finish();
+  memcpy(form, rep, sizeof rep);
+  if (o) dO.fetch(o, "output"); else dO.fetch(o16, "bf16 output");
+  // K and V are inputs: the launch leaves every byte of them as it was
+  if (memcmp(to_host<uint8_t>(dK, (size_t)kv_elems * eb).data(), k, (size_t)kv_elems * eb) != 0) fail(std::string(what) + ": the launch changed K");
+  if (memcmp(to_host<uint8_t>(dV, (size_t)kv_elems * eb).data(), v, (size_t)kv_elems * eb) != 0) fail(std::string(what) + ": the launch changed V");
+  Q3A_CATCH(nullptr)
+}
+
 int32_t q3a_selftest_draft_accept(int32_t device, int32_t S, const int32_t* draft_ids, const int32_t* draft_off, const int32_t* prompt_lens,
                                   const int32_t* top_ids, const float* top_lp, int32_t out_stride, const uint16_t* embed, int32_t V, int32_t H,
                                   const float* norm_w, int32_t group_size, const float* cos_t, const float* sin_t, int32_t max_pos,

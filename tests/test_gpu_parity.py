@@ -477,6 +477,28 @@ def test_mfma_attention_matches_valu_attention(tiny_dir):
         assert rel_l2(a, b) <= 1e-2
 
 
+def test_mfma_attention_matches_valu_attention_in_every_row(tiny_dir):
+    """The comparison above, row by row on the decoder tap: dec_layer0 is the hidden state behind layer 0, [prompt rows][H] -- the
+    attention's own output per head is no tap, so each row is held to rel-L2 <= 1e-2 of its own norm, where the whole-tensor figure lets
+    one wrong query row pass.  (Per query row and head against float64: tests/test_gpu_seg_attn.py.)"""
+    clips = [synthetic.synthetic_clip(0, 9.3), synthetic.synthetic_clip(1, 2.17)]
+    taps = []
+    for valu in (False, True):
+        eng = HipEngine(tiny_dir, 0, valu_attention=valu, debug_taps=True, max_new_tokens=8)
+        eng.mel(clips)
+        eng.encode()
+        prompts = [HipEngine.build_prompt(eng.num_audio_tokens(len(c))) for c in clips]
+        eng.prefill(prompts)
+        rows = sum(len(p) for p in prompts)
+        taps.append(np.asarray(eng.debug_read("dec_layer0"), np.float64).reshape(rows, -1))
+        eng.close()
+    mfma, valu = taps
+    assert mfma.shape == valu.shape and np.isfinite(mfma).all() and np.isfinite(valu).all()
+    per_row = np.linalg.norm(mfma - valu, axis=1) / np.linalg.norm(valu, axis=1)
+    print(f"dec_layer0, {mfma.shape[0]} rows: worst row at rel-L2 {per_row.max():.2e} (row {int(per_row.argmax())}), whole tensor {rel_l2(mfma, valu):.2e}")
+    assert per_row.max() <= 1e-2
+
+
 def test_graph_replay_equals_eager(tiny_dir):
     clip = synthetic.synthetic_clip(4, 3.0)
     out = []
