@@ -339,15 +339,10 @@ __device__ __forceinline__ void gemv_epilogue(const GemvArgs& a, int g, const in
 // of the weights: x is back after one L2 round trip and the store / barrier / read-back run while the weights are in flight (stamped
 // timeline, profiles/gemv_down_handover_phase_probe.txt: issue 0.85 -> 0.19 us, span 2.02 -> 1.93 us).  Behind the weights the
 // hand-over starts when the last weight chunk has landed and stands exposed in front of the FMAs (span 2.21 us: it lost).
-// XP (an XL form: gate / up behind oproj_head_kernel): the vector handed over is x + x_parts[0] + ... + x_parts[n - 1], n <=
-// GEMV_X_PARTS_MAX = 4 -- the residual and o_proj's partial vectors, added in ascending order by the thread that hands its four columns
-// over.  All GEMV_X_PARTS_MAX + 1 requests go in one batch where the single x request stands (a vector past n is clamped to the last
-// one and not added).  Workgroup 0 also stores the sum to x_out, the residual the down projection and the next layer read: a buffer no
-// workgroup of this launch reads, so the store races with nothing.
-template <int PR, int KI, bool RMS, bool ATTN, int MF, bool XL, bool XP = false>
+// (Gate / up behind oproj_head_kernel, which also adds o_proj's partial vectors in its hand-over, is gemv1_xp_body below.)
+template <int PR, int KI, bool RMS, bool ATTN, int MF, bool XL>
 __device__ __forceinline__ void gemv1_body(const GemvArgs& a) {
   static_assert(!XL || !ATTN, "the merged attention vector already goes through LDS");
-  static_assert(!XP || (XL && RMS), "the partial vectors are added in the hand-over of the norm-fused XL form");
   constexpr bool XH = !RMS && !ATTN && KI > 4;
   constexpr bool XLDS = XL || XH;  // x is handed over through LDS (the norm weight, xl_w, only in the XL forms)
   static_assert(!XH || KI % 2 == 0, "the hand-over stores unguarded: its rounds of 1024 columns must end at KI * 512");
@@ -372,8 +367,6 @@ __device__ __forceinline__ void gemv1_body(const GemvArgs& a) {
   uint4 wq[KI][PR];
   constexpr int XLN = (KI + 1) / 2;  // 16-byte pieces of x per lane in the XL / XH forms (256 lanes x 4 floats = 1024 columns per round)
   float4 xl_rx[XLDS ? XLN : 1], xl_rw[(XL && RMS) ? XLN : 1];
-  constexpr int XPN = XP ? GEMV_X_PARTS_MAX : 1;
-  float4 xp_r[XP ? XLN : 1][XPN];
   auto request_x = [&]() {  // L2 hits
     if (ATTN) return;
     if constexpr (XLDS) {
@@ -381,11 +374,6 @@ __device__ __forceinline__ void gemv1_body(const GemvArgs& a) {
       for (int j = 0; j < XLN; ++j) {
         const int k = (tid + j * 256) * 4, kc = k < K ? k : 0;
         xl_rx[j] = *reinterpret_cast<const float4*>(a.x + kc);
-        if constexpr (XP) {
-#pragma unroll
-          for (int h = 0; h < XPN; ++h)
-            xp_r[j][h] = *reinterpret_cast<const float4*>(a.x_parts + (size_t)(h < a.x_nparts ? h : a.x_nparts - 1) * K + kc);
-        }
         if (RMS) xl_rw[j] = *reinterpret_cast<const float4*>(a.rms_w + kc);
       }
       return;
@@ -510,12 +498,6 @@ __device__ __forceinline__ void gemv1_body(const GemvArgs& a) {
       if (XH || k < KI * 512) {  // (XH: KI is even, the XLN rounds cover exactly KI * 512 columns)
         // element by element: as one aggregate copy (a memcpy from the private array to LDS) hipcc kept xl_rx[XLN > 1] in scratch
         float4 v = xl_rx[j];
-        if constexpr (XP) {
-#pragma unroll
-          for (int h = 0; h < XPN; ++h)
-            if (h < a.x_nparts) { v.x += xp_r[j][h].x; v.y += xp_r[j][h].y; v.z += xp_r[j][h].z; v.w += xp_r[j][h].w; }
-          if (blockIdx.x == 0 && k < K) *reinterpret_cast<float4*>(a.x_out + k) = v;
-        }
         *reinterpret_cast<float4*>(x_lds + k) = make_float4(v.x, v.y, v.z, v.w);
         if (RMS) *reinterpret_cast<float4*>(xl_w + k) = xl_rw[j];
       }
@@ -619,20 +601,137 @@ __global__ __launch_bounds__(256) void gemv1_kernel(const float* attn_pm, const 
   gemv1_body<PR, KI, RMS, ATTN, MF, XL>(a);
 }
 
-// The XP form (gate / up: mode 2, norm fused, K <= 1024).  Every vector the hand-over's one batch of requests is addressed with
-// stands in the head; the store of the sum (x_out) rides in the tail.
+// ---- gate / up behind oproj_head_kernel (the XP form: mode 2, norm fused, K <= 1024) ----------------------------------------
+// The vector the waves multiply is x + x_parts[0] + ... + x_parts[n - 1], n <= GEMV_X_PARTS_MAX = 4: the residual and o_proj's partial
+// vectors, added in ascending order; workgroup 0 also stores the sum to x_out, the residual the down projection and the next layer read
+// (a buffer no workgroup of this launch reads, so the store races with nothing).  A wave is the wave of gemv1_body<2, 2, true, false, 0,
+// true>: same rows per wave (g = blockIdx.x * NW + wave), lane / column plan, dot8 order, wave_sum_fast and rstd -- bit-identical
+// results whatever NW.  What NW changes is how many waves share one hand-over.  With four waves per workgroup (three workgroups per CU at
+// 0.6B) every CU pulled the six vectors of the hand-over -- x, four partial vectors, the norm weight, 4 KB each -- three times through its
+// load path, 72 KB in front of its 48 KB of weights, and loads return in order.  With NW = 12, one workgroup per CU, it pulls them once,
+// and two thirds of the waves request nothing but their weights.  The waves take roles:
+//   waves 0 .. 3   the 256 threads that own four columns each request x and the four partial vectors (5 requests), then their weights;
+//                  they add in registers as the four-wave form did and store the sum to LDS (and to x_out);
+//   waves 4 .. 7   request the norm weight of their four columns (1 request), then their weights, and store it to LDS;
+//   waves 8 ..     request their weights only.
+// One barrier, then every wave reads the sum and the norm weight back.  Each role is a straight-line program of its own behind ONE
+// scalar branch on the wave index at entry: no load sits under a branch that joins again in front of another request, so every role's
+// requests form one run in front of its first wait (9, 5 and 4: tests/test_gate_up_wide_isa.py).
+// Measured and not kept (profiles/gate_up_wide_*.txt, docs/HISTORY.md "Gate / up: twelve waves per workgroup"): the 6 x 256 pieces spread
+// evenly over all threads and added from LDS behind a second barrier, at 12 and at 6 waves -- a faster issue (0.72 -> 0.27 us) but the
+// summed vector 0.66 us later, a loss of 8 - 14 us per step.
+template <int PR, int KI, int NW, int ROLE>
+__device__ __forceinline__ void gemv1_xp_role(const GemvArgs& a, float* x_lds, float* xl_w) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  Q3A_STAMP_ENTRY(t_entry);
+  const int K = a.K;
+  const int g = blockIdx.x * NW + wave;
+  int prow[PR];
+  gemv_rows<PR>(a, g, prow);
+  bool kin[KI];
+  int kk[KI];
+#pragma unroll
+  for (int it = 0; it < KI; ++it) {
+    const int k = lane * 8 + it * 512;
+    kin[it] = k < K;
+    kk[it] = kin[it] ? k : 0;
+  }
+  float4 xr[KI][2], nr[KI][2];
+  uint4 wq[KI][PR];
+  const int hk = (tid & (KI * 128 - 1)) * 4, hkc = hk < K ? hk : 0;
+  float4 hx, hp[GEMV_X_PARTS_MAX], hw;
+  if constexpr (ROLE == 0) {  // L2 hits; a partial vector past n is clamped to the last one and not added, a column past K to column 0
+    hx = *reinterpret_cast<const float4*>(a.x + hkc);
+#pragma unroll
+    for (int h = 0; h < GEMV_X_PARTS_MAX; ++h)
+      hp[h] = *reinterpret_cast<const float4*>(a.x_parts + (size_t)(h < a.x_nparts ? h : a.x_nparts - 1) * K + hkc);
+  }
+  if constexpr (ROLE == 1) hw = *reinterpret_cast<const float4*>(a.rms_w + hkc);
+#pragma unroll
+  for (int it = 0; it < KI; ++it)  // the HBM stream: all KI * PR chunks of the wave's rows in flight at once
+#pragma unroll
+    for (int i = 0; i < PR; ++i) {
+      const int row = prow[i] >= 0 ? prow[i] : a.N - 1;
+      wq[it][i] = ld_stream16(a.W + (size_t)row * K + kk[it]);
+    }
+  float bv[PR];  // the bias rides behind the stream
+#pragma unroll
+  for (int i = 0; i < PR; ++i) bv[i] = a.bias ? a.bias[prow[i] >= 0 ? prow[i] : 0] : 0.f;
+  __builtin_amdgcn_sched_barrier(0);  // every request is issued before anything is waited for
+  Q3A_STAMP_AT(a.stamp, blockIdx.x, 1);  // every load requested
+  Q3A_STAMP_PUT(a.stamp, blockIdx.x, 0, t_entry);  // entry
+  Q3A_ARG(a.out); Q3A_ARG(a.x_out); Q3A_ARG(a.fast_math);
+  if constexpr (ROLE == 0) {
+    float4 v = hx;
+#pragma unroll
+    for (int h = 0; h < GEMV_X_PARTS_MAX; ++h)
+      if (h < a.x_nparts) { v.x += hp[h].x; v.y += hp[h].y; v.z += hp[h].z; v.w += hp[h].w; }
+    if (blockIdx.x == 0 && hk < K) *reinterpret_cast<float4*>(a.x_out + hk) = v;
+    *reinterpret_cast<float4*>(x_lds + hk) = make_float4(v.x, v.y, v.z, v.w);
+  }
+  if constexpr (ROLE == 1) *reinterpret_cast<float4*>(xl_w + hk) = make_float4(hw.x, hw.y, hw.z, hw.w);
+  __syncthreads();
+#pragma unroll
+  for (int it = 0; it < KI; ++it) {
+    xr[it][0] = *reinterpret_cast<const float4*>(x_lds + kk[it]);
+    xr[it][1] = *reinterpret_cast<const float4*>(x_lds + kk[it] + 4);
+    nr[it][0] = *reinterpret_cast<const float4*>(xl_w + kk[it]);
+    nr[it][1] = *reinterpret_cast<const float4*>(xl_w + kk[it] + 4);
+  }
+  Q3A_STAMP_AT(a.stamp, blockIdx.x, 2);  // the summed vector read back
+  float x[KI][8], acc[PR];
+  float ss = 0.f;
+#pragma unroll
+  for (int it = 0; it < KI; ++it) {
+    const float4 v0 = xr[it][0], v1 = xr[it][1];
+    const float xv[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) x[it][e] = (K == KI * 512 || kin[it]) ? xv[e] : 0.f;  // columns beyond K contribute nothing
+    const float4 w0 = nr[it][0], w1 = nr[it][1];
+    const float wv[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { ss += x[it][e] * x[it][e]; x[it][e] *= wv[e]; }
+  }
+#pragma unroll
+  for (int i = 0; i < PR; ++i) acc[i] = 0.f;
+#pragma unroll
+  for (int it = 0; it < KI; ++it)
+#pragma unroll
+    for (int i = 0; i < PR; ++i) acc[i] = dot8(wq[it][i], x[it], acc[i]);
+  if (wave == 0) asm volatile("" ::"v"(acc[0]));  // (the stamp below sits behind the FMAs of wave 0, i.e. behind its weights)
+  Q3A_STAMP_AT(a.stamp, blockIdx.x, 3);  // weights landed, dot products done
+  const float rstd = rstd_of(wave_sum_fast(ss) / (float)K + a.eps, a.fast_math != 0);  // a wave covers all of K
+#pragma unroll
+  for (int i = 0; i < PR; ++i) acc[i] = wave_sum_fast(acc[i]) * rstd + bv[i];
+  if (lane != 0) return;
+#pragma unroll
+  for (int i = 0; i + 1 < PR; i += 2)
+    if (prow[i] >= 0) a.out[g * (PR / 2) + (i >> 1)] = silu_sel(acc[i], a.fast_math != 0) * acc[i + 1];
+  Q3A_STAMP_AT(a.stamp, blockIdx.x, 4);  // reduced and stored
+}
+template <int PR, int KI, int NW>
+__device__ __forceinline__ void gemv1_xp_body(const GemvArgs& a) {
+  static_assert(KI == 2 && NW >= 8, "four waves own the KI * 128 sixteen-byte pieces of a vector; four more fetch the norm weight");
+  __shared__ __attribute__((aligned(16))) float x_lds[KI * 512], xl_w[KI * 512];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (wave < 4) gemv1_xp_role<PR, KI, NW, 0>(a, x_lds, xl_w);
+  else if (wave < 8) gemv1_xp_role<PR, KI, NW, 1>(a, x_lds, xl_w);
+  else gemv1_xp_role<PR, KI, NW, 2>(a, x_lds, xl_w);
+}
+// Every vector the hand-over's requests are addressed with stands in the head; the store of the sum (x_out) rides in the tail.
 struct GemvXpTail {
   float* out; float* x_out; int fast_math;
   Q3A_STAMP_FIELD
 };
-template <int PR, int KI>
-__global__ __launch_bounds__(256) void gemv1_xp_kernel(const uint16_t* W, const float* x, const float* rms_w, const float* x_parts,
-                                                       const float* bias, int N, int K, int x_nparts, float eps, GemvXpTail t) {
+constexpr int GEMV_XP_WAVES = 12;  // 3072 outputs at 0.6B: 256 workgroups, one per CU
+template <int PR, int KI, int NW>
+__global__ __launch_bounds__(NW * 64) void gemv1_xp_kernel(const uint16_t* W, const float* x, const float* rms_w, const float* x_parts,
+                                                           const float* bias, int N, int K, int x_nparts, float eps, GemvXpTail t) {
   GemvArgs a{};
   a.W = W; a.x = x; a.rms_w = rms_w; a.x_parts = x_parts; a.bias = bias; a.N = N; a.K = K; a.x_nparts = x_nparts; a.eps = eps; a.mode = 2;
   a.out = t.out; a.x_out = t.x_out; a.fast_math = t.fast_math;
   Q3A_STAMP_COPY(a, t);
-  gemv1_body<PR, KI, true, false, 0, true, true>(a);
+  gemv1_xp_body<PR, KI, NW>(a);
 }
 
 // ---- o_proj per column slice (one sequence, default mode) ---------------------------------------------------
@@ -1209,7 +1308,10 @@ void launch1k(const GemvArgs& a, hipStream_t s) {
           GemvXpTail t{};
           t.out = a.out; t.x_out = a.x_out; t.fast_math = a.fast_math;
           Q3A_STAMP_COPY(t, a);
-          hipLaunchKernelGGL((gemv1_xp_kernel<PR, KI>), grid, block, 0, s, a.W, a.x, a.rms_w, a.x_parts, a.bias, a.N, a.K, a.x_nparts, a.eps, t);
+          // one logical row (gate and up) per wave, GEMV_XP_WAVES waves per workgroup: rows past N / 2 are clamped and not stored
+          const dim3 xp_grid((a.N / 2 + GEMV_XP_WAVES - 1) / GEMV_XP_WAVES), xp_block(GEMV_XP_WAVES * 64);
+                    hipLaunchKernelGGL((gemv1_xp_kernel<PR, KI, GEMV_XP_WAVES>), xp_grid, xp_block, 0, s, a.W, a.x, a.rms_w, a.x_parts, a.bias, a.N, a.K, a.x_nparts,
+                             a.eps, t);
           return;
         }
       }
