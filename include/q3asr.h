@@ -544,7 +544,8 @@ int32_t q3a_parse_logit_bias(const char* text, const char* suppress_list, int32_
  * Refused (q3a_last_error): a negative, NaN or infinite temperature; min_p outside [0, 1]; an aligner engine; q3a_beam_begin /
  * q3a_beam_search_batch_ptrs while sampling is on.  q3a_score* and q3a_align* never see it.
  * Readable: q3a_debug_read(e, "sampling", ..) (uint32 [5]: on 0 / 1, temperature and min_p as fp32 bits, seed low, seed high).
- * Out of scope: top-k / top-p; sampling inside beam search; a group-level call (set it on each q3a_group_engine handle). */
+ * Out of scope: sampling inside beam search; a group-level call (set it on each q3a_group_engine handle).  (Top-k / top-p: their own
+ * section below.) */
 int32_t q3a_set_sampling(q3a_engine* e, float temperature, float min_p, uint64_t seed);
 /* Host function, no engine and no device: the random word of token j of sequence s at step t, by the code the kernel runs. */
 uint32_t q3a_sample_word(uint64_t seed, uint32_t s, uint32_t t, uint32_t j);
@@ -552,6 +553,52 @@ uint32_t q3a_sample_word(uint64_t seed, uint32_t s, uint32_t t, uint32_t j);
  * (log_softmax(l)[id]) and out_z [S] (the winning noisy score z_id); any may be null.  temperature > 0. */
 int32_t q3a_selftest_sample(int32_t device, const float* logits, int32_t S, int32_t V, float temperature, float min_p,
                             uint64_t seed, int32_t step, int32_t* out_ids, float* out_lp, float* out_z);
+
+/* ---- sampling filter: top-k and top-p (nucleus) inside the sampled step ----------------------------------------------------------------
+ * The two warpers a generate() user reaches for first, applied on the device between the sampler's row statistics and its draw.  All
+ * else is the sampling section's: l' are the stored (biased, sequence-biased, repetition-processed) fp32 logits of sequence s at a
+ * step, m their maximum, T > 0 the temperature.  NaN is outside the contract, as everywhere.
+ *   Kept set.  K = { j : l'_j >= tau, l'_j != -inf }, tau = max(tau_k, tau_p, tau_minp).  The threshold is a VALUE, never a rank: equal
+ *     values share their fate, and -0.0 and +0.0 are equal values.
+ *   Top-k.  top_k = 0 or top_k >= V is off (tau_k = -inf).  Otherwise tau_k is the top_k-th largest entry of the row, counted with
+ *     multiplicity, so every entry that ties the k-th value is kept (HuggingFace's scores < topk(scores, k)[0][..., -1]); with fewer
+ *     than top_k finite entries every finite entry is kept.  Integer counts only: exact, bit for bit.
+ *   Top-p.  top_p = 1 is off.  Otherwise, with K_k = { l' >= tau_k }, w_j = exp((l'_j - m) / T) on K_k, Z = sum w and G(v) = sum over
+ *     { j in K_k : l'_j > v } of w_j / Z -- the probability mass strictly above the value v, renormalised over the top-k set at
+ *     temperature T -- tau_p is the smallest row value v with G(v) < top_p.  The row maximum always qualifies (G = 0).
+ *   Min-p.  tau_minp = m + T ln(min_p), as in the sampling section; a ratio to the maximum, so it commutes with the other two.
+ *   Pinned meaning.  On tie-free rows K is exactly what HuggingFace's chain TemperatureLogitsWarper(T) -> TopKLogitsWarper(k) ->
+ *     TopPLogitsWarper(p) -> MinPLogitsWarper(min_p) leaves finite.  On ties HuggingFace's top-p cuts inside a run of equal values in
+ *     sort order; here the whole run is kept.
+ *   Tolerance.  Top-k is exact.  Top-p compares a sum of weights with top_p Z, so membership is specified up to a bound delta on
+ *     |G_device - G_exact|: tau_ref(top_p + delta) <= tau <= tau_ref(top_p - delta), the reference in float64, with delta = 1e-5.
+ *     Derivation, from the arithmetic: a weight is (uint64)(expf((l' - m) / T) 2^40), summed in integers.  A weight that does not
+ *     truncate to zero has |(l' - m) / T| < 28; the subtraction and the division each round once (2^-24 relative), so the argument
+ *     is off by at most 28 2^-23 = 3.4e-6, expf adds 2 ulp = 2.4e-7: a relative error of at most 3.6e-6 per weight.  Truncation
+ *     loses under 2^-40 per entry, under 2^17.2 2^-40 = 1.4e-7 of Z >= 1 over a row.  G is a ratio of two such sums: at most twice
+ *     the sum of the two, 7.5e-6; top_p Z itself is formed in fp64 (2^-53).  Rounded up: 1e-5.
+ *   The draw is unchanged: Gumbel-max over K with the same Philox words, so the id is distributed as the renormalised HuggingFace
+ *     distribution.  Log-probabilities stay those of the untempered l'.
+ *   Determinism.  tau, the kept count and the ids are bit-identical from run to run, graph replay and eager: counts and weights are
+ *     accumulated in integers, whose sums do not depend on the order of arrival.
+ * State: the setting persists until changed.  q3a_set_sampling_filter drops the decode state as q3a_set_sampling does.  It has an
+ * effect only while sampling is on: with temperature == 0 the engine runs the greedy launches whatever the filter says, and with
+ * (0, 1.0f) the sampled step enqueues exactly what it enqueues without this section.  On / off is part of the captured step's
+ * signature; top_k and top_p live in a device buffer the kernels read, so another value replays the same graph.  Buffers are
+ * allocated at the first setting that is not off and freed with the engine.  Cost: two launches in the sampled step while on.
+ * Refused (q3a_last_error; the engine stays usable): top_k < 0; top_p NaN or outside (0, 1]; an aligner engine.  Beam search, drafts
+ * and scoring keep the refusals and the indifference they have towards sampling.
+ * Readable without debug taps: q3a_debug_read(e, "sampling_filter", ..) (uint32 [3]: on 0 / 1, top_k, top_p as fp32 bits);
+ * "sample_threshold" (fp32 [S]: max(tau_k, tau_p) of the last step, a row value -- a zero as +0.0 -- or -inf) and "sample_kept"
+ * (int32 [S]: the entries >= that threshold), both after a step sampled with the filter on.
+ * Out of scope: typical / eta / epsilon sampling; min_tokens_to_keep > 1; per-utterance settings inside one batch; a filter inside
+ * beam search. */
+int32_t q3a_set_sampling_filter(q3a_engine* e, int32_t top_k, float top_p);   /* (0, 1.0f) = off */
+/* q3a_selftest_sample with the filter's threshold stage in it (run twice on one table, the second run handed out); also out_thr [S]
+ * (max(tau_k, tau_p)) and out_kept [S] (entries >= it); any output may be null.  (0, 1.0f) gives q3a_selftest_sample's ids and z. */
+int32_t q3a_selftest_sample_filter(int32_t device, const float* logits, int32_t S, int32_t V, float temperature, float min_p,
+                                   int32_t top_k, float top_p, uint64_t seed, int32_t step, int32_t* out_ids, float* out_lp,
+                                   float* out_z, float* out_thr, int32_t* out_kept);
 
 /* ---- repetition: a repetition penalty and a no-repeat n-gram ban inside the decode step ------------------------------------------------
  * The two history-dependent logits processors every generate() user reaches for, applied on the device to the stored logits of every

@@ -73,6 +73,11 @@ extern "C" {
     pub fn q3a_parse_logit_bias(text: *const c_char, suppress_list: *const c_char, ids: *mut i32, bias: *mut f32, cap: i32, n: *mut i32) -> i32;
     pub fn q3a_set_sampling(e: *mut q3a_engine, temperature: f32, min_p: f32, seed: u64) -> i32;
     pub fn q3a_sample_word(seed: u64, s: u32, t: u32, j: u32) -> u32;
+    // top-k / top-p inside the sampled step (include/q3asr.h "sampling filter")
+    pub fn q3a_set_sampling_filter(e: *mut q3a_engine, top_k: i32, top_p: f32) -> i32;
+    pub fn q3a_selftest_sample_filter(device: i32, logits: *const f32, s: i32, v: i32, temperature: f32, min_p: f32, top_k: i32, top_p: f32,
+                                      seed: u64, step: i32, out_ids: *mut i32, out_lp: *mut f32, out_z: *mut f32, out_thr: *mut f32,
+                                      out_kept: *mut i32) -> i32;
     // repetition penalty and no-repeat n-grams on the sequence's own generated ids (include/q3asr.h "repetition")
     pub fn q3a_set_repetition(e: *mut q3a_engine, repetition_penalty: f32, no_repeat_ngram_size: i32) -> i32;
     pub fn q3a_selftest_repeat(device: i32, logits: *const f32, s: i32, v: i32, hist: *const i32, stride: i32, lens: *const i32, p: f32, n: i32,
@@ -151,6 +156,15 @@ impl HipEngine {
         };
         if rc != 0 { bail!("{}", msg(unsafe { q3a_last_error(self.raw) })); }
         Ok((0..b).map(|i| ids[i * max_new..i * max_new + lens[i] as usize].iter().map(|&x| x as i64).collect()).collect())
+    }
+
+    /// Top-k / top-p for every later sampled generation call (q3a_set_sampling with a temperature > 0): keep the entries that reach the
+    /// `top_k`-th largest logit (0: off; ties kept), and of those the head whose probability reaches `top_p` (1.0: off).
+    pub fn set_sampling_filter(&self, top_k: usize, top_p: f32) -> Result<()> {
+        if top_k > i32::MAX as usize { bail!("set_sampling_filter: top_k does not fit an int32"); }
+        let rc = unsafe { q3a_set_sampling_filter(self.raw, top_k as i32, top_p) };
+        if rc != 0 { bail!("{}", msg(unsafe { q3a_last_error(self.raw) })); }
+        Ok(())
     }
 
     /// Repetition control for every later generation call: `repetition_penalty` (1.0: none) over the ids a sequence has generated,

@@ -24,7 +24,7 @@ SYMBOLS = [
     "q3a_align_text_ids", "q3a_fix_timestamps", "q3a_score", "q3a_score_batch_ptrs",
     "q3a_beam_search_batch_ptrs", "q3a_beam_begin", "q3a_beam_step", "q3a_beam_fetch", "q3a_selftest_beam_topk", "q3a_selftest_beam_advance",
     "q3a_selftest_kv_reorder", "q3a_set_logit_bias", "q3a_parse_logit_bias",
-    "q3a_set_sampling", "q3a_sample_word", "q3a_selftest_sample",
+    "q3a_set_sampling", "q3a_sample_word", "q3a_selftest_sample", "q3a_set_sampling_filter", "q3a_selftest_sample_filter",
     "q3a_set_repetition", "q3a_selftest_repeat",
     "q3a_set_sequence_bias", "q3a_selftest_seqbias", "q3a_parse_sequence_bias", "q3a_hotword_sequences", "q3a_banned_sequences",
     "q3a_selftest_gemm_launch", "q3a_selftest_qkrope_launch", "q3a_gemm256_split_rows",
@@ -162,6 +162,8 @@ def load() -> C.CDLL:
         "q3a_set_sampling": (i32, [P, C.c_float, C.c_float, u64]),
         "q3a_sample_word": (C.c_uint32, [u64, C.c_uint32, C.c_uint32, C.c_uint32]),
         "q3a_selftest_sample": (i32, [i32, f32p, i32, i32, C.c_float, C.c_float, u64, i32, i32p, f32p, f32p]),
+        "q3a_set_sampling_filter": (i32, [P, i32, C.c_float]),
+        "q3a_selftest_sample_filter": (i32, [i32, f32p, i32, i32, C.c_float, C.c_float, i32, C.c_float, u64, i32, i32p, f32p, f32p, f32p, i32p]),
         "q3a_set_repetition": (i32, [P, C.c_float, i32]),
         "q3a_selftest_repeat": (i32, [i32, f32p, i32, i32, i32p, i32, i32p, C.c_float, i32, f32p, i32p, f32p]),
         "q3a_set_sequence_bias": (i32, [P, i32p, i32p, f32p, i32]),

@@ -17,6 +17,8 @@
 // Q3A_SCORE_TEXT score does not; without them nothing changes.
 // Q3A_TEMPERATURE=<T> [Q3A_MIN_P=<p>] [Q3A_SEED=<n>] samples the transcription at ONE temperature (q3a_set_sampling; min_p 0 and seed
 // 0 when absent); a Q3A_BEAM search is then refused by the engine.  There is no temperature fallback here (no zlib).
+// Q3A_TOP_K=<k> and / or Q3A_TOP_P=<p> with Q3A_TEMPERATURE filter the sampled step (q3a_set_sampling_filter; 0 and 1 when absent);
+// without a Q3A_TEMPERATURE > 0 they are an error: nothing is sampled.
 // Q3A_REPETITION_PENALTY=<p> and / or Q3A_NO_REPEAT_NGRAM=<n> run the transcription under q3a_set_repetition (1 and 0 when absent); a
 // Q3A_BEAM search is then refused by the engine, a Q3A_SCORE_TEXT score never sees it.
 // Q3A_DRAFT_TEXT=<path of a UTF-8 file> with a `language` argument transcribes with that text as a draft (q3a_transcribe_draft_batch_ptrs:
@@ -95,6 +97,28 @@ static int set_sampling_from_env(q3a_engine* eng) {
   }
   if (q3a_set_sampling(eng, temperature, min_p, (uint64_t)seed) != 0) return die(std::string("Sampling failed: ") + q3a_last_error(eng));
   logf(1, "Sampling: temperature %s", t);
+  return 0;
+}
+
+// Q3A_TOP_K / Q3A_TOP_P: the sampled step's top-k / top-p filter, set before anything is generated
+static int set_sampling_filter_from_env(q3a_engine* eng) {
+  const char *k = getenv("Q3A_TOP_K"), *p = getenv("Q3A_TOP_P"), *t = getenv("Q3A_TEMPERATURE");
+  const bool have_k = k && *k, have_p = p && *p;
+  if (!have_k && !have_p) return 0;
+  char* end = nullptr;
+  if (!t || !*t || !(strtof(t, &end) > 0.f)) return die("Sampling filter failed: Q3A_TOP_K / Q3A_TOP_P need a Q3A_TEMPERATURE > 0 (nothing is sampled without it)");
+  long top_k = 0;
+  if (have_k) {
+    top_k = strtol(k, &end, 10);
+    if (end == k || *end || top_k < 0 || top_k > 0x7fffffffL) return die(std::string("Sampling filter failed: Q3A_TOP_K is not an integer >= 0: ") + k);
+  }
+  float top_p = 1.f;
+  if (have_p) {
+    top_p = strtof(p, &end);
+    if (end == p || *end) return die(std::string("Sampling filter failed: Q3A_TOP_P is not a number: ") + p);
+  }
+  if (q3a_set_sampling_filter(eng, (int32_t)top_k, top_p) != 0) return die(std::string("Sampling filter failed: ") + q3a_last_error(eng));
+  logf(1, "Sampling filter: top_k %s", std::to_string(top_k) + " top_p " + std::to_string(top_p));
   return 0;
 }
 
@@ -376,6 +400,7 @@ int main(int argc, char** argv) {
     logf(0, "warning: the checkpoint stores F16/F32 matrices; the HIP backend keeps matrices as bf16 (rounded to nearest-even)");
   if (set_logit_bias_from_env(eng) != 0) return 1;
   if (set_sampling_from_env(eng) != 0) return 1;
+  if (set_sampling_filter_from_env(eng) != 0) return 1;
   if (set_repetition_from_env(eng) != 0) return 1;
   logf(1, "Loading tokenizer...");
   q3a_tokenizer* tok = nullptr;

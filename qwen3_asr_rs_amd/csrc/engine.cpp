@@ -186,6 +186,7 @@ struct StepView {
   const int &k_parallel_groups, &k_skinny_q, &k_dattn_batched_min_wgs, &k_skinny_glu_hp3, &k_lm_head_prune, &k_oproj_by_head;  // knobs as latched per batch
   const bool& logit_bias_on_;  // q3a_set_logit_bias: a bias is set (changes only while the engine holds no decode state)
   const bool& sampling_on_;    // q3a_set_sampling: temperature > 0 (likewise)
+  const bool& sampling_filter_on_;  // q3a_set_sampling_filter: top_k != 0 or top_p != 1 (likewise; acts only while sampling is on)
   const bool& repetition_on_;  // q3a_set_repetition: a penalty != 1 or an n-gram size > 0 (likewise)
   const bool& sequence_bias_on_;  // q3a_set_sequence_bias: a list with at least one entry (likewise)
 
@@ -219,6 +220,10 @@ struct DecodeStep : StepView {
   // q3a_set_sampling: {temperature, min_p, seed low, seed high} as the sampler's kernels read them (a new setting needs no new graph),
   // and the clean (max, sum exp) pair of every 2048-logit chunk of every row [B][sample_chunks(vocab)]
   DevBuf samp_params, samp_max, samp_sum;
+  // q3a_set_sampling_filter: {top_k, top_p (fp32 bits), 0, 0} as the threshold stage reads them (a new setting needs no new graph); the
+  // stage's first-digit table per row, [B][SAMPLE_BUCKETS] uint64 weights then [B][SAMPLE_BUCKETS] uint32 counts, zero between steps;
+  // and what it leaves: [B] fp32 max(tau_k, tau_p), then [B] int32 entries kept by it
+  DevBuf samp_filter, samp_hist, samp_sel;
   DevBuf rep_params;  // q3a_set_repetition: {penalty (fp32 bits), n-gram size, 0, 0} as history_apply_kernel reads them (a new setting needs no new graph)
   DevBuf seq_bias;  // q3a_set_sequence_bias: the list's tables and counts, SEQBIAS_TABLE_WORDS words whatever the list (a new list needs no new graph); allocated by the first non-empty set
   DevBuf draft_accepted;  // draft verification (k_draft.hip): [2 B] first mismatch k per sequence, then its token -- one small D2H copy per prefill
@@ -230,7 +235,7 @@ struct DecodeStep : StepView {
                     &s.rope_cur, &s.rope_cos, &s.rope_sin, &s.n_done, &s.forced_tok,
                     &s.beam_cand_val, &s.beam_cand_idx, &s.beam_part_max, &s.beam_part_sum, &s.beam_topk_ids, &s.beam_topk_lp, &s.beam_score, &s.beam_finished,
                     &s.beam_parent, &s.beam_token, &s.beam_feed, &s.beam_hist_parent, &s.beam_hist_token, &s.beam_hist_lp, &s.beam_state, &s.beam_lo,
-                    &s.logit_bias, &s.samp_params, &s.samp_max, &s.samp_sum, &s.rep_params, &s.seq_bias, &s.draft_accepted})
+                    &s.logit_bias, &s.samp_params, &s.samp_max, &s.samp_sum, &s.samp_filter, &s.samp_hist, &s.samp_sel, &s.rep_params, &s.seq_bias, &s.draft_accepted})
       f(*b);
   }
 
@@ -399,7 +404,14 @@ struct DecodeStep : StepView {
     sa.chunk_max = samp_max.as<float>(); sa.chunk_sum = samp_sum.as<float>();
     f.part.sum = nullptr; f.c.out_lp = nullptr; f.n_part = sample_chunks(d.vocab);
     sa.part = f.part;
-    timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_sample(sa, stream)); });
+    if (!sampling_filter_on_) { timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_sample(sa, stream)); }); return; }
+    // top-k / top-p: the threshold stage between the sampler's two launches
+    if (!samp_filter.p || !samp_hist.p || !samp_sel.p) fail("sampling filter: on without its buffers");
+    SampleFilterArgs sf{};
+    sf.filter = samp_filter.as<uint32_t>(); sf.hist_mass = samp_hist.as<unsigned long long>();
+    sf.hist_cnt = reinterpret_cast<uint32_t*>(sf.hist_mass + (size_t)B * SAMPLE_BUCKETS);
+    sf.tau_sel = samp_sel.as<float>(); sf.kept = samp_sel.as<int>() + B;
+    timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_sample_filtered(sa, sf, stream)); });
   }
   // log_softmax(l')[id] of the drawn id, where the greedy step's log-probability would stand
   void enqueue_sample_logprob() {
@@ -781,6 +793,8 @@ struct q3a_engine : CallState {
   int logit_bias_finite_ = 0;   // its finite entries (the vocabulary while off): what a beam width is checked against
   bool sampling_on_ = false;    // q3a_set_sampling: temperature > 0, the step draws its ids (k_sample.hip; graph signature)
   uint32_t samp_words_[4] = {0, 0, 0, 0};  // what step.samp_params holds: temperature and min_p (fp32 bits), seed low / high
+  bool sampling_filter_on_ = false;  // q3a_set_sampling_filter: top_k != 0 or top_p != 1 (k_sample.hip; graph signature)
+  uint32_t samp_filter_words_[2] = {0, 0x3f800000u};  // what step.samp_filter holds: top_k, top_p (fp32 bits)
   bool logit_bias_eos_open_ = true;  // the logit bias leaves an EOS id finite (true while off): a sequence can always stop
   bool repetition_on_ = false;       // q3a_set_repetition: penalty != 1 or n-gram size > 0 (k_repeat.hip; graph signature)
   float rep_penalty_ = 1.f;          // what step.rep_params holds
@@ -793,7 +807,7 @@ struct q3a_engine : CallState {
   // ---- the captured decode step: its buffers and launches, and all it sees of the members above ----
   DecodeStep step{StepView{d, L, opts, arena, arena_flags, stream, chain_streams, join_ev, fork_ev, n_cu, host_prog_dev, prof, taps, lm_q, lm_qs, lm_q_cols,
                            B, max_ctx, max_new, gsize, live_nsplit_, live_kps_, attn_nsplit, min_P_, part_stride, beam_w(), kv_layer_elems, head_logits(),
-                           k_parallel_groups, k_skinny_q, k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, k_oproj_by_head, logit_bias_on_, sampling_on_, repetition_on_, sequence_bias_on_}};
+                           k_parallel_groups, k_skinny_q, k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, k_oproj_by_head, logit_bias_on_, sampling_on_, sampling_filter_on_, repetition_on_, sequence_bias_on_}};
 
   // (the mode rules are stated once, in StepView)
   bool precise() const { return step.precise(); }
@@ -1307,6 +1321,13 @@ struct q3a_engine : CallState {
     step.part_val.ensure((size_t)b * part_stride * 4); step.part_idx.ensure((size_t)b * part_stride * 4);
     if (token_lp()) { step.part_sum.ensure((size_t)b * part_stride * 4); step.out_lp.ensure((size_t)b * max_new * 4); }
     if (sampling_on_) { step.samp_max.ensure((size_t)b * sample_chunks(d.vocab) * 4); step.samp_sum.ensure((size_t)b * sample_chunks(d.vocab) * 4); }
+    if (sampling_on_ && sampling_filter_on_) {
+      // the threshold stage finds its table zero and leaves it zero.  The b rows are zeroed at every prefill all the same: a buffer
+      // that grew holds whatever the allocator gave it (at the old address too), and a step that ended between the histogram and the
+      // select would otherwise leave its counts there for the life of the buffer
+      step.samp_hist.ensure((size_t)b * SAMPLE_BUCKETS * 12); step.samp_sel.ensure((size_t)b * 8);
+      HIPCHK(hipMemsetAsync(step.samp_hist.p, 0, (size_t)b * SAMPLE_BUCKETS * 12, stream));
+    }
     {
       const size_t nblk4 = ((size_t)(d.vocab + 15) / 16 + 3) & ~size_t(3);  // lm_head_prune_blocks, rounded up for float4 reads
       step.blk_lo.ensure(nblk4 * 4); step.blk_hi.ensure(nblk4 * 4);
@@ -1708,8 +1729,8 @@ struct q3a_engine : CallState {
     });
     char buf[256];
     // (one field per latched knob, as latched: packing several into one integer let distinct settings collide -- ADVICE r5)
-    snprintf(buf, sizeof(buf), "%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.b%d.lb%d.sm%d.rp%d.sb%d/%d.%d/%d/%d/%p/%016llx", B, gsize, k_parallel_groups, k_skinny_q,
-             k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, k_oproj_by_head, (int)(min_P_ < 256), (int)head_logits(), (int)token_lp(), beam_w(), (int)logit_bias_on_, (int)sampling_on_, (int)repetition_on_, (int)sequence_bias_on_, live_nsplit_, live_kps_,
+    snprintf(buf, sizeof(buf), "%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.b%d.lb%d.sm%d.sf%d.rp%d.sb%d/%d.%d/%d/%d/%p/%016llx", B, gsize, k_parallel_groups, k_skinny_q,
+             k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, k_oproj_by_head, (int)(min_P_ < 256), (int)head_logits(), (int)token_lp(), beam_w(), (int)logit_bias_on_, (int)sampling_on_, (int)(sampling_on_ && sampling_filter_on_), (int)repetition_on_, (int)sequence_bias_on_, live_nsplit_, live_kps_,
              max_ctx, max_new, (const void*)arena, (unsigned long long)h);
     return buf;
   }
@@ -2017,6 +2038,25 @@ struct q3a_engine : CallState {
     HIPCHK(hipStreamSynchronize(stream));
     memcpy(samp_words_, w, 16);
     sampling_on_ = temperature > 0.f;
+  }
+  // Top-k / top-p (q3asr.h q3a_set_sampling_filter).  As q3a_set_sampling: the values live in a device buffer, on / off is part of
+  // the graph signature, no decode state afterwards.  The first setting that is not (0, 1) allocates the buffer.
+  void set_sampling_filter(int32_t top_k, float top_p) {
+    const char* what = "q3a_set_sampling_filter";
+    require_asr(what);
+    if (top_k < 0) fail(std::string(what) + ": top_k must be >= 0 (0 turns top-k off)");
+    if (!(top_p > 0.f && top_p <= 1.f)) fail(std::string(what) + ": top_p must lie in (0, 1] (1 turns top-p off)");
+    const bool on = top_k != 0 || top_p != 1.f;
+    uint32_t w[4] = {(uint32_t)top_k, 0u, 0u, 0u};
+    memcpy(&w[1], &top_p, 4);
+    drop_decode_state();
+    if (on) step.samp_filter.ensure(16);
+    if (step.samp_filter.p) {
+      HIPCHK(hipMemcpyAsync(step.samp_filter.p, w, 16, hipMemcpyHostToDevice, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+    }
+    memcpy(samp_filter_words_, w, 8);
+    sampling_filter_on_ = on;
   }
   void beam_sampling_check(const char* what) const {
     if (sampling_on_) fail(std::string(what) + ": sampling is on (q3a_set_sampling with temperature > 0); beam search selects deterministically -- turn it off first");
@@ -2455,6 +2495,14 @@ int32_t q3a_set_sampling(q3a_engine* e, float temperature, float min_p, uint64_t
   Q3A_CATCH(e)
 }
 
+int32_t q3a_set_sampling_filter(q3a_engine* e, int32_t top_k, float top_p) {
+  if (!e) return 1;
+  Q3A_TRY(e)
+  HIPCHK(hipSetDevice(e->device));
+  e->set_sampling_filter(top_k, top_p);
+  Q3A_CATCH(e)
+}
+
 int32_t q3a_set_repetition(q3a_engine* e, float repetition_penalty, int32_t no_repeat_ngram_size) {
   if (!e) return 1;
   Q3A_TRY(e)
@@ -2849,6 +2897,22 @@ int32_t q3a_debug_read(q3a_engine* e, const char* name, void* dst, uint64_t byte
     e->require_asr("q3a_debug_read: sampling");
     const uint32_t st[5] = {e->sampling_on_ ? 1u : 0u, e->samp_words_[0], e->samp_words_[1], e->samp_words_[2], e->samp_words_[3]};
     give(st, 20, false);
+    return 0;
+  }
+  if (strcmp(name, "sampling_filter") == 0) {  // {on, top_k, top_p bits} as last set
+    e->require_asr("q3a_debug_read: sampling_filter");
+    const uint32_t st[3] = {e->sampling_filter_on_ ? 1u : 0u, e->samp_filter_words_[0], e->samp_filter_words_[1]};
+    give(st, 12, false);
+    return 0;
+  }
+  if (strcmp(name, "sample_threshold") == 0 || strcmp(name, "sample_kept") == 0) {  // the threshold stage of the last sampled step
+    e->require_asr("q3a_debug_read: sample_threshold");
+    const size_t S = (size_t)e->B;
+    // (the decode state: a prefill under the setting has run and nothing has dropped it since -- a setter does -- so the values are this run's)
+    if (!(e->sampling_on_ && e->sampling_filter_on_) || !e->at(Stage::Decoding) || !e->step.samp_sel.p || S == 0 || e->step.samp_sel.cap < S * 8)
+      fail(std::string("q3a_debug_read: '") + name + "' needs a step sampled with q3a_set_sampling_filter on (no decode state under that setting)");
+    const bool kept = strcmp(name, "sample_kept") == 0;  // [S] thresholds, then [S] counts
+    give((const uint8_t*)e->step.samp_sel.p + (kept ? S * 4 : 0), S * 4, true);
     return 0;
   }
   if (strcmp(name, "repetition") == 0) {  // {on, penalty bits, n-gram size} as last set

@@ -4,7 +4,8 @@
 // the stored logits l' [S][V] (fp32, bias included) and the sequence's own out_ids, so it does not care which head form wrote the row,
 // and it keeps nothing from step to step: no trie, no match state, nothing to undo.  The history IS out_ids[s][0 .. t),
 // t = min(step_count[s], out_stride).  Both processors are phases of ONE kernel (the library's kernel count is pinned by
-// tests/test_kernarg_preload.py); a launch runs the phases of one processor, the other's arguments are null.
+// tests/test_kernarg_preload.py); a launch runs the phases of one processor, the other's arguments are null.  The sampled step's
+// top-k / top-p stage (sample_filter.h) runs as three more launches of it, one phase each, for the same reason.
 //
 //   history_apply_kernel   one workgroup of 256 threads per sequence.
 //     sequence bias (launch_seqbias_apply):
@@ -29,13 +30,15 @@
 // The rewritten row is l''; launch_argmax_partials (or launch_sample) and argmax_finalize then run on it unchanged.
 #include "dev.h"
 #include "kernels.h"
+#include "sample_filter.h"
 
 namespace q3a {
 
 namespace {
 
-__global__ __launch_bounds__(256) void history_apply_kernel(SeqBiasArgs sb, RepeatArgs a, int words, int hist_cap) {
+__global__ __launch_bounds__(256) void history_apply_kernel(SeqBiasArgs sb, RepeatArgs a, int words, int hist_cap, SampleStageArgs st) {
   extern __shared__ __attribute__((aligned(16))) uint32_t repeat_lds[];
+  if (st.phase) { sample_stage_phase(st, repeat_lds); return; }  // top-k / top-p: a launch of its own, none of the history's phases
   __shared__ int tail[SEQBIAS_MAX_LEN - 1];
   const int s = blockIdx.x, tid = threadIdx.x;
   if (sb.params) {  // (uniform: a kernel argument)
@@ -119,7 +122,7 @@ const char* launch_repeat_apply(const RepeatArgs& a, hipStream_t s) {
   if (!a.logits || !a.params || !a.out_ids || !a.step_count || a.out_stride < 1) return "repetition: null argument";
   const int words = (a.V + 31) / 32, hist_cap = a.out_stride < REPEAT_HIST_LDS ? a.out_stride : REPEAT_HIST_LDS;
   const size_t lds = ((size_t)((words + 3) & ~3) + (size_t)hist_cap) * 4;  // <= 32 KB + 16 KB
-  hipLaunchKernelGGL(history_apply_kernel, dim3(a.S), dim3(256), lds, s, SeqBiasArgs{}, a, words, hist_cap);
+  hipLaunchKernelGGL(history_apply_kernel, dim3(a.S), dim3(256), lds, s, SeqBiasArgs{}, a, words, hist_cap, SampleStageArgs{});
   return nullptr;
 }
 
@@ -128,7 +131,20 @@ const char* launch_seqbias_apply(const SeqBiasArgs& a, hipStream_t s) {
   if (a.V < 1) return "sequence bias: empty vocabulary";
   if (!a.logits || !a.params || !a.grp_target || !a.grp_begin || !a.ent_bias || !a.ent_pre_off || !a.pre_ids || !a.out_ids || !a.step_count || a.out_stride < 1)
     return "sequence bias: null argument";
-  hipLaunchKernelGGL(history_apply_kernel, dim3(a.S), dim3(256), 0, s, a, RepeatArgs{}, 0, 0);
+  hipLaunchKernelGGL(history_apply_kernel, dim3(a.S), dim3(256), 0, s, a, RepeatArgs{}, 0, 0, SampleStageArgs{});
+  return nullptr;
+}
+
+// Top-k / top-p (launch_sample_filtered, k_sample.hip): the histogram on the chunk grid, the select with one workgroup per row, the
+// filtered draw on the chunk grid -- the arguments were checked by the caller.
+const char* launch_sample_stage(const SampleArgs& a, const SampleFilterArgs& f, bool vec, hipStream_t s) {
+  SampleStageArgs st{1, vec ? 1 : 0, sample_chunks(a.V), a, f};
+  const dim3 grid(st.n_chunk, a.S);
+  hipLaunchKernelGGL(history_apply_kernel, grid, dim3(256), SAMPLE_HIST_LDS, s, SeqBiasArgs{}, RepeatArgs{}, 0, 0, st);
+  st.phase = 2;
+  hipLaunchKernelGGL(history_apply_kernel, dim3(a.S), dim3(256), SAMPLE_SELECT_LDS, s, SeqBiasArgs{}, RepeatArgs{}, 0, 0, st);
+  st.phase = 3;
+  hipLaunchKernelGGL(history_apply_kernel, grid, dim3(256), 0, s, SeqBiasArgs{}, RepeatArgs{}, 0, 0, st);
   return nullptr;
 }
 

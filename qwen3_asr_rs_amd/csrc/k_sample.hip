@@ -12,22 +12,14 @@
 //   sample_logprob_kernel  one wave per row, after finalize: (m, sum) of the row in a fixed order and lp = (l'_id - m) - log(sum) of the
 //                          id finalize chose, written where finalize would have put the greedy log-probability.
 // The tie rule is ArgmaxAcc's everywhere: the larger value, on equal values the smaller id.
+// With q3a_set_sampling_filter on (top-k / top-p) launch_sample_filtered runs sample_rowstat_kernel and then the
+// threshold stage and the filtered draw of sample_filter.h (phases of k_repeat.hip's kernel).  Off, none of that is enqueued.
 #include "argmax.h"
 #include "sample_rng.h"
 
 namespace q3a {
 
 namespace {
-
-// g = -log(-log u) of u = ((x >> 8) + 0.5) 2^-24.  With k = x >> 8 < 2^23 that u is an fp32 number; above, k + 0.5 needs 25 bits (and
-// the largest k would round to u = 1), but 1 - u = ((2^24 - k) - 0.5) 2^-24 is an fp32 number, and -log u = -log1p(-(1 - u)).
-__device__ __forceinline__ float gumbel_of(uint32_t x) {
-  const uint32_t k = x >> 8;
-  float nl;
-  if (k < (1u << 23)) nl = -logf(((float)k + 0.5f) * 0x1p-24f);
-  else nl = -log1pf(-(((float)(0x1000000u - k) - 0.5f) * 0x1p-24f));
-  return -logf(nl);
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void sample_rowstat_kernel(const float* __restrict__ logits, int V, int n_chunk,
@@ -176,6 +168,21 @@ const char* launch_sample(const SampleArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(sample_chunk_kernel<false>, grid, dim3(256), 0, s, a, nc);
   }
   return nullptr;
+}
+
+const char* launch_sample_filtered(const SampleArgs& a, const SampleFilterArgs& f, hipStream_t s) {
+  if (a.S <= 0) return nullptr;
+  if (a.V < 1) return "sample: empty vocabulary";
+  if (!a.logits || !a.params || !a.step_count || !a.chunk_max || !a.chunk_sum || !a.part.val) return "sample: null argument";
+  if (!f.filter || !f.hist_cnt || !f.hist_mass || !f.tau_sel || !f.kept) return "sample filter: null argument";
+  const int nc = sample_chunks(a.V);
+  if (const char* e = argmax_partials_check(a.part, nc)) return e;
+  if (a.part.sum) return "sample: the partials carry no log-sum channel";
+  const bool vec = a.V % 4 == 0 && ((uintptr_t)a.logits & 15) == 0;
+  const dim3 grid(nc, a.S);
+  if (vec) hipLaunchKernelGGL(sample_rowstat_kernel<true>, grid, dim3(256), 0, s, a.logits, a.V, nc, a.chunk_max, a.chunk_sum);
+  else hipLaunchKernelGGL(sample_rowstat_kernel<false>, grid, dim3(256), 0, s, a.logits, a.V, nc, a.chunk_max, a.chunk_sum);
+  return launch_sample_stage(a, f, vec, s);  // k_repeat.hip: the histogram, the select and the filtered draw
 }
 
 const char* launch_sample_logprob(const SampleLogprobArgs& a, hipStream_t s) {

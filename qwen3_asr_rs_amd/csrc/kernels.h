@@ -520,6 +520,21 @@ struct SampleArgs {
   ArgmaxPartials part;                 // (written) [S] rows x sample_chunks(V) partials, no log-sum channel
 };
 const char* launch_sample(const SampleArgs& a, hipStream_t s);
+// Top-k / top-p (q3asr.h "sampling filter").  launch_sample with two launches between its two: the threshold stage writes
+// tau_sel[s] = max(tau_k, tau_p) (a row value or -inf) and kept[s] = #{ j : l_j >= tau_sel[s], l_j != -inf }, and the kept set of the
+// noisy partials becomes { l >= max(m + T ln(min_p), tau_sel[s]), l != -inf }.  An exact radix select over the order-preserving
+// uint32 key of the logit: integer counts for top-k, fixed-point weights (uint64)(exp((l - m) / T) 2^40) for top-p.
+constexpr int SAMPLE_BUCKETS = 2048;  // the select's first digit: the top 11 bits of the key
+struct SampleFilterArgs {
+  const uint32_t* filter;              // device [4]: top_k, top_p (fp32 bits), 0, 0 -- as validated by the setter
+  uint32_t* hist_cnt;                  // [S][SAMPLE_BUCKETS] entries per first digit: ZERO on entry, zero again when the stage returns
+  unsigned long long* hist_mass;       // [S][SAMPLE_BUCKETS] their summed weights; likewise
+  float* tau_sel; int* kept;           // [S] (written)
+};
+const char* launch_sample_filtered(const SampleArgs& a, const SampleFilterArgs& f, hipStream_t s);
+// What launch_sample_filtered enqueues behind sample_rowstat: three launches of k_repeat.hip's kernel, one phase each (sample_filter.h).
+struct SampleStageArgs { int phase; int vec; int n_chunk; SampleArgs a; SampleFilterArgs f; };  // phase 0: not the sampler's launch
+const char* launch_sample_stage(const SampleArgs& a, const SampleFilterArgs& f, bool vec, hipStream_t s);
 // After launch_argmax_finalize: lp = (l_id - m) - log sum exp(l - m) of the id it chose (next_tok[s]), the sum merged in a fixed
 // order, written to out_lp[s][step_count[s] - 1] -- the entry finalize filled for this step; out_z[s] = the winning noisy score.
 struct SampleLogprobArgs {

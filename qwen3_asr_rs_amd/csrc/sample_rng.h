@@ -2,6 +2,9 @@
 // (k_sample.hip) and the host (q3a_sample_word) both compile, so a reference can reproduce the noise of any logit on its own.
 #pragma once
 #include <stdint.h>
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#endif
 
 #if defined(__HIPCC__)
 #define Q3A_HOST_DEVICE __host__ __device__
@@ -24,5 +27,17 @@ Q3A_HOST_DEVICE inline uint32_t sample_word(uint32_t seed_lo, uint32_t seed_hi, 
   }
   return c0;
 }
+
+#if defined(__HIPCC__)
+// g = -log(-log u) of u = ((x >> 8) + 0.5) 2^-24.  With k = x >> 8 < 2^23 that u is an fp32 number; above, k + 0.5 needs 25 bits (and
+// the largest k would round to u = 1), but 1 - u = ((2^24 - k) - 0.5) 2^-24 is an fp32 number, and -log u = -log1p(-(1 - u)).
+__device__ __forceinline__ float gumbel_of(uint32_t x) {
+  const uint32_t k = x >> 8;
+  float nl;
+  if (k < (1u << 23)) nl = -logf(((float)k + 0.5f) * 0x1p-24f);
+  else nl = -log1pf(-(((float)(0x1000000u - k) - 0.5f) * 0x1p-24f));
+  return -logf(nl);
+}
+#endif
 
 }  // namespace q3a

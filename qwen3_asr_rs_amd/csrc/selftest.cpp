@@ -288,6 +288,66 @@ int32_t q3a_selftest_sample(int32_t device, const float* logits, int32_t S, int3
   Q3A_CATCH(nullptr)
 }
 
+// the same tail with q3a_set_sampling_filter on: launch_sample_filtered in the place of launch_sample.  It runs the stage TWICE on one
+// table, as two steps of a decode do, and hands out the second run: the stage must leave its table as it found it.
+int32_t q3a_selftest_sample_filter(int32_t device, const float* logits, int32_t S, int32_t V, float temperature, float min_p, int32_t top_k,
+                                   float top_p, uint64_t seed, int32_t step, int32_t* out_ids, float* out_lp, float* out_z, float* out_thr,
+                                   int32_t* out_kept) {
+  Q3A_TRY(nullptr)
+  if (!logits || S < 1 || V < 1 || step < 0 || step > (1 << 20)) fail("q3a_selftest_sample_filter: bad argument");
+  if (!(temperature > 0.f) || !std::isfinite(temperature)) fail("q3a_selftest_sample_filter: temperature must be finite and > 0");
+  if (!(min_p >= 0.f && min_p <= 1.f)) fail("q3a_selftest_sample_filter: min_p must lie in [0, 1]");
+  if (top_k < 0) fail("q3a_selftest_sample_filter: top_k must be >= 0");
+  if (!(top_p > 0.f && top_p <= 1.f)) fail("q3a_selftest_sample_filter: top_p must lie in (0, 1]");
+  use_device(device);
+  const size_t Sz = S, nc = sample_chunks(V), stride = (size_t)step + 1;
+  constexpr int H = 4;
+  uint32_t w[4], fw[4] = {(uint32_t)top_k, 0u, 0u, 0u};
+  memcpy(&w[0], &temperature, 4); memcpy(&w[1], &min_p, 4); memcpy(&fw[1], &top_p, 4);
+  w[2] = (uint32_t)seed; w[3] = (uint32_t)(seed >> 32);
+  const DevBuf dLg = to_device(logits, Sz * V), dPar = to_device(w, 4), dFil = to_device(fw, 4);
+  const DevBuf dCm = room(Sz * nc * 4), dCs = room(Sz * nc * 4), dPv = room(Sz * nc * 4), dPi = room(Sz * nc * 4);
+  const DevBuf dHist = to_device(std::vector<uint32_t>(Sz * SAMPLE_BUCKETS * 3, 0u)), dSel = room(Sz * 8);
+  const DevBuf dEmb = to_device(std::vector<uint16_t>((size_t)V * H, 0)), dX = room(Sz * H * 4), dTok = room(Sz * 4);
+  const DevBuf dZ = room(Sz * 4);
+  std::vector<int> ids;
+  std::vector<float> lp;
+  for (int run = 0; run < 2; ++run) {
+    const DevBuf dSc = to_device(std::vector<int>(Sz, step)), dIds = to_device(std::vector<int>(Sz * stride, -1));
+    const DevBuf dLp = to_device(std::vector<float>(Sz * stride, 0.f));
+    const DevBuf dPos = to_device(std::vector<int>(Sz, 0)), dDone = to_device(std::vector<uint8_t>(Sz, 0));
+    SampleArgs sa{};
+    sa.logits = dLg.as<float>(); sa.S = S; sa.V = V; sa.params = dPar.as<uint32_t>(); sa.step_count = dSc.as<int>();
+    sa.chunk_max = dCm.as<float>(); sa.chunk_sum = dCs.as<float>();
+    sa.part = ArgmaxPartials{dPv.as<float>(), dPi.as<int>(), nullptr, (int)nc};
+    SampleFilterArgs sf{};
+    sf.filter = dFil.as<uint32_t>(); sf.hist_mass = dHist.as<unsigned long long>();
+    sf.hist_cnt = reinterpret_cast<uint32_t*>(sf.hist_mass + Sz * SAMPLE_BUCKETS);
+    sf.tau_sel = dSel.as<float>(); sf.kept = dSel.as<int>() + S;
+    KCHK(launch_sample_filtered(sa, sf, nullptr));
+    FinalizeArgs f{};
+    f.part = sa.part; f.n_part = (int)nc; f.V = V; f.advance = 1;
+    f.c = bare_commit(S, dTok, dIds.as<int>(), (int)stride, nullptr, dSc, dPos, dDone, dEmb.as<uint16_t>(), H, dX.as<float>(), kEos0, kEos1);
+    KCHK(launch_argmax_finalize(f, S, nullptr));
+    SampleLogprobArgs sl{};
+    sl.logits = sa.logits; sl.S = S; sl.V = V; sl.chunk_max = sa.chunk_max; sl.chunk_sum = sa.chunk_sum; sl.next_tok = f.c.next_tok;
+    sl.step_count = f.c.step_count; sl.out_lp = dLp.as<float>(); sl.out_stride = (int)stride; sl.part = sa.part; sl.out_z = dZ.as<float>();
+    KCHK(launch_sample_logprob(sl, nullptr));
+    finish();
+    ids = to_host<int>(dIds, Sz * stride);
+    lp = to_host<float>(dLp, Sz * stride);
+  }
+  for (size_t s = 0; s < Sz; ++s) {
+    if (out_ids) out_ids[s] = ids[s * stride + step];
+    if (out_lp) out_lp[s] = lp[s * stride + step];
+  }
+  if (out_z) to_host(out_z, dZ, Sz);
+  const std::vector<float> sel = to_host<float>(dSel, Sz * 2);
+  if (out_thr) memcpy(out_thr, sel.data(), Sz * 4);
+  if (out_kept) memcpy(out_kept, sel.data() + Sz, Sz * 4);
+  Q3A_CATCH(nullptr)
+}
+
 // a step's tail with q3a_set_repetition on, as the engine enqueues it without sampling: launch_repeat_apply on the stored rows, fresh
 // argmax partials (with the log-sum channel) over the rewritten rows, argmax_finalize on those
 int32_t q3a_selftest_repeat(int32_t device, const float* logits, int32_t S, int32_t V, const int32_t* hist, int32_t stride,

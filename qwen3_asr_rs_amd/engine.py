@@ -101,6 +101,21 @@ def check_sampling_args(temperature: float, min_p: float = 0.0, seed: int = 0) -
     return t, p, int(seed)
 
 
+def check_sampling_filter_args(top_k: int = 0, top_p: float = 1.0) -> Tuple[int, float]:
+    """The refusals of q3a_set_sampling_filter that need no engine (pure host function): top_k an integer >= 0 (0 = off) that fits an
+    int32, top_p in (0, 1] (1 = off).  Returns the two as the C call takes them."""
+    k = top_k
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not (0 <= int(k) < 1 << 31):
+        raise Q3aError(f"set_sampling_filter: top_k must be an integer >= 0 (0 turns top-k off), got {top_k!r}")
+    try:
+        p = float(top_p)
+    except (TypeError, ValueError):
+        raise Q3aError("set_sampling_filter: top_p must be a number")
+    if not (0.0 < p <= 1.0) or float(np.float32(p)) <= 0.0:
+        raise Q3aError(f"set_sampling_filter: top_p must lie in (0, 1] (1 turns top-p off), got {top_p!r}")
+    return int(k), p
+
+
 def check_repetition_args(repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0) -> Tuple[float, int]:
     """The refusals of q3a_set_repetition that need no engine (pure host function): repetition_penalty finite and > 0 (1 = no
     penalty), no_repeat_ngram_size an integer in [0, 32] (0 = no ban).  Returns the two as the C call takes them."""
@@ -374,6 +389,7 @@ class HipEngine:
         self._T: List[int] = []
         self.logit_bias_state: Tuple[Optional[dict], float] = (None, 0.0)  # what set_logit_bias was last given
         self.sampling_state: Tuple[float, float, int] = (0.0, 0.0, 0)  # what set_sampling was last given
+        self.sampling_filter_state: Tuple[int, float] = (0, 1.0)  # what set_sampling_filter was last given
         self.repetition_state: Tuple[float, int] = (1.0, 0)  # what set_repetition was last given
         self.sequence_bias_state: List[Tuple[tuple, float]] = []  # what set_sequence_bias was last given, as (ids, bias) pairs
 
@@ -727,6 +743,19 @@ class HipEngine:
         return {"active": bool(st[0]), "temperature": float(st[1:2].view(np.float32)[0]), "min_p": float(st[2:3].view(np.float32)[0]),
                 "seed": int(st[3]) | (int(st[4]) << 32)}
 
+    def set_sampling_filter(self, top_k: int = 0, top_p: float = 1.0):
+        """q3a_set_sampling_filter: while sampling is on, every step keeps only the entries >= the top_k-th largest logit (ties kept) and,
+        of those, the smallest head whose probability at the temperature reaches top_p (equal values share their fate) -- HuggingFace's
+        TopKLogitsWarper and TopPLogitsWarper as a value threshold, found on the device.  (0, 1.0) turns it off.  Drops the decode
+        state: prefill again before a stage-API step."""
+        k, p = check_sampling_filter_args(top_k, top_p)
+        self._chk(self._lib.q3a_set_sampling_filter(self._h, k, C.c_float(p)))
+        self.sampling_filter_state = (k, p)
+
+    def sampling_filter_stats(self) -> dict:
+        st = self.debug_read_raw("sampling_filter").view(np.uint32)
+        return {"active": bool(st[0]), "top_k": int(st[1]), "top_p": float(st[2:3].view(np.float32)[0])}
+
     # ---- repetition penalty / no-repeat n-grams ------------------------------------------------------------
     def set_repetition(self, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0):
         """q3a_set_repetition: every generation step divides the positive (multiplies the other) logits of the ids the sequence has
@@ -1010,7 +1039,8 @@ class AsrInference:
                    compression_ratio_threshold: float = 2.4, repetition_penalty: float = 1.0,
                    no_repeat_ngram_size: int = 0, draft=None, hotwords: Optional[Iterable[str]] = None,
                    hotword_boost: Optional[float] = None, hotword_start_boost: float = 0.0,
-                   banned_phrases: Optional[Iterable[str]] = None, sequence_bias=None) -> TranscribeResult:
+                   banned_phrases: Optional[Iterable[str]] = None, sequence_bias=None, top_k: int = 0,
+                   top_p: float = 1.0) -> TranscribeResult:
         """src/inference.rs:89-213.  `audio`: path to a WAV file or a 16 kHz float32 array.  beam_size > 1: a beam search of that
         width instead of the greedy loop; `alternatives` holds its hypotheses ordered by score / max(len, 1) ** length_penalty
         (float64 on the host; 0: the search's own order) and the result is the first of them.
@@ -1021,6 +1051,9 @@ class AsrInference:
         1.0) is Whisper's fallback (temperature_fallback): attempt k runs at temperatures[k] with seed + k, the first attempt with
         avg_logprob >= logprob_threshold and compression ratio <= compression_ratio_threshold is kept, else the last; it needs an
         engine created with token_logprobs=True.  The result's `temperature` is the one that was used.  Not with beam_size > 1.
+        top_k / top_p: anything but (0, 1.0) sets HipEngine.set_sampling_filter for this call and restores the engine's own setting
+        afterwards; every attempt of a temperature fallback runs under it (the greedy attempt ignores it).  Raises Q3aError when no
+        temperature of the call is > 0: a filter without sampling would do nothing.
         repetition_penalty / no_repeat_ngram_size: anything but (1.0, 0) sets HipEngine.set_repetition for this call and restores the
         engine's own setting afterwards; every attempt of a temperature fallback runs under the same setting.  Not with beam_size > 1.
         draft: a transcript that is probably mostly right -- a list of ids, an earlier TranscribeResult (its ids) or a string (score()'s
@@ -1047,6 +1080,9 @@ class AsrInference:
         temps = [float(t) for t in temperature] if fallback else [float(temperature)]
         for t in temps:
             check_sampling_args(t, min_p, seed)
+        filt_args = check_sampling_filter_args(top_k, top_p)
+        if filt_args != (0, 1.0) and not any(t > 0.0 for t in temps):
+            raise Q3aError("transcribe: top_k / top_p filter a sampled step: give a temperature > 0 with them")
         if fallback and not self.engine.token_logprobs:
             raise Q3aError("transcribe: a tuple of temperatures (fallback) decides on avg_logprob: create the engine with token_logprobs=True")
         if beam_size > 1 and any(t > 0.0 for t in temps):
@@ -1071,6 +1107,16 @@ class AsrInference:
                     return temperature_fallback(attempt, temps, seed, logprob_threshold, compression_ratio_threshold)[0]
                 finally:
                     eng.set_sampling(*before)
+        if filt_args != (0, 1.0):
+            inner_f, feng = run, self.engine
+
+            def run():
+                before = feng.sampling_filter_state
+                feng.set_sampling_filter(*filt_args)
+                try:
+                    return inner_f()
+                finally:
+                    feng.set_sampling_filter(*before)
         if rep_args != (1.0, 0):
             inner, reng = run, self.engine
 

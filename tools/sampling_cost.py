@@ -5,9 +5,11 @@ events).  Arms, their order rotated round by round:
     off     sampling off (the launches of an engine that never sampled; at one sequence the pruned lm_head argmax)
     t1      temperature 1, min_p 0: every finite logit gets its Philox word and its two logs
     t1minp  temperature 1, min_p 0.05: only the kept set does
+    t1k50 / t1p09 / t1k50p09  temperature 1 under q3a_set_sampling_filter: top_k 50, top_p 0.9, both (the threshold stage's two launches)
 
     python tools/sampling_cost.py --preset 0.6b --batch 1 --rounds 7
     python tools/sampling_cost.py --preset 0.6b --batch 32 --rounds 7
+    python tools/sampling_cost.py --batch 1 --arms off,t1,t1k50,t1p09,t1k50p09     # the filter's arms against the sampler's
     python tools/sampling_cost.py --rounds 1 --arms off        # no sampling call at all: the run a kernel trace compares launches on
 
 Prints one line per round and a summary: median us per step of each arm, the difference to `off` in percent and in us, pruned
@@ -22,7 +24,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-ARMS = {"t1": (1.0, 0.0), "t1minp": (1.0, 0.05)}
+ARMS = {"t1": (1.0, 0.0), "t1minp": (1.0, 0.05)}          # temperature, min_p
+FILTERS = {"t1k50": (50, 1.0), "t1p09": (0, 0.9), "t1k50p09": (50, 0.9)}   # top_k, top_p at temperature 1, min_p 0
 
 
 def main():
@@ -34,6 +37,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--arms", default="off,t1,t1minp")
     args = ap.parse_args()
+    unknown = [a for a in args.arms.split(",") if a and a != "off" and a not in ARMS and a not in FILTERS]
+    if unknown:
+        ap.error(f"unknown arm(s) {unknown}: choose from off, {', '.join(list(ARMS) + list(FILTERS))}")
     from qwen3_asr_rs_amd import synthetic
     from qwen3_asr_rs_amd.engine import HipEngine
     model_dir = f"/tmp/q3a_ckpt_{args.preset.replace('.', 'p')}"
@@ -43,14 +49,20 @@ def main():
     eng = HipEngine(model_dir, 0, max_new_tokens=max(N, 16))
     eng.upload_pcm(clips)
     names = [a for a in args.arms.split(",") if a]
-    state = {"set": False}
+    state = {"set": False, "filter": False}
 
     def stats():
         return eng.debug_read_raw("lm_head_prune_stats").view(np.int32).astype(np.int64)
 
     def run(arm):
+        if arm in FILTERS:
+            eng.set_sampling_filter(*FILTERS[arm])
+            state["filter"] = True
+        elif state["filter"]:  # (never called unless a filter arm ran: the other arms drive a library without the call)
+            eng.set_sampling_filter(0, 1.0)
+            state["filter"] = False
         if arm != "off":
-            eng.set_sampling(ARMS[arm][0], ARMS[arm][1], 17)
+            eng.set_sampling(*(ARMS[arm] if arm in ARMS else (1.0, 0.0)), 17)  # (a filter arm: temperature 1, min_p 0)
             state["set"] = True
         elif state["set"]:  # (never called when only `off` runs: the same tool then drives a library without the call)
             eng.set_sampling(0.0)
