@@ -591,8 +591,8 @@ int32_t q3a_selftest_sample(int32_t device, const float* logits, int32_t S, int3
  * Readable without debug taps: q3a_debug_read(e, "sampling_filter", ..) (uint32 [3]: on 0 / 1, top_k, top_p as fp32 bits);
  * "sample_threshold" (fp32 [S]: max(tau_k, tau_p) of the last step, a row value -- a zero as +0.0 -- or -inf) and "sample_kept"
  * (int32 [S]: the entries >= that threshold), both after a step sampled with the filter on.
- * Out of scope: typical / eta / epsilon sampling; min_tokens_to_keep > 1; per-utterance settings inside one batch; a filter inside
- * beam search. */
+ * Out of scope: typical / eta / epsilon sampling; min_tokens_to_keep > 1; a filter inside beam search.
+ * (per-utterance settings inside one batch: the "row options" section below.) */
 int32_t q3a_set_sampling_filter(q3a_engine* e, int32_t top_k, float top_p);   /* (0, 1.0f) = off */
 /* q3a_selftest_sample with the filter's threshold stage in it (run twice on one table, the second run handed out); also out_thr [S]
  * (max(tau_k, tau_p)) and out_kept [S] (entries >= it); any output may be null.  (0, 1.0f) gives q3a_selftest_sample's ids and z. */
@@ -683,7 +683,8 @@ int32_t q3a_selftest_repeat(int32_t device, const float* logits, int32_t S, int3
  * than the distinct targets of -inf entries plus, with an n-gram ban on, max_new_tokens -- the only way a row could run out of finite
  * logits -- refused by whichever of q3a_set_sequence_bias / q3a_set_logit_bias / q3a_set_repetition comes second.
  * Readable: q3a_debug_read(e, "sequence_bias", ..) (int32 [4]: on 0 / 1, entries, ids over all entries, distinct targets).
- * Out of scope: per-utterance lists inside one batch; subtracting a partial boost when a phrase is abandoned; sequence bias inside
+ * (per-utterance lists inside one batch: q3a_set_sequence_bias_lists in the "row options" section below.)
+ * Out of scope: subtracting a partial boost when a phrase is abandoned; sequence bias inside
  * beam search or under a draft (so not in StreamingTranscriber); matching over the prompt; boost values tuned on real weights (none
  * has been: q3a_hotword_sequences takes the boost from the caller). */
 
@@ -710,6 +711,69 @@ int32_t q3a_hotword_sequences(const q3a_tokenizer* t, const char* const* phrases
                               int32_t ids_cap, int32_t* lens, float* bias, int32_t cap, int32_t* n_ids, int32_t* n);
 int32_t q3a_banned_sequences(const q3a_tokenizer* t, const char* const* phrases, int32_t n_phrases, int32_t* ids, int32_t ids_cap, int32_t* lens,
                              float* bias, int32_t cap, int32_t* n_ids, int32_t* n);
+
+/* ---- row options: per-request decoding options inside one batch, read per row on the device -----------------------------------------
+ * A ROW TABLE gives sequence s of the next calls its own record of the settings the sections above hold once per engine: sampling,
+ * the sampling filter, repetition control and the sequence-bias list.  s is the index of the sequence in the batch, the same one that
+ * seeds the Philox counter.  A server can so put one caller's hotword list, another's temperature 0.8 / top_p 0.9 and a third's plain
+ * greedy request into one batch.
+ *   Row meaning.  Row s behaves exactly as the sections above define for an engine whose uniform setting is that row's record: the kept
+ *     set, the noise q3a_sample_word(seed_s, s, t, j), Gumbel-max, the tau rules, the penalty and the n-gram ban over the row's own
+ *     out_ids, the firing and summing rule of the row's own list, the processor order (sequence bias, repetition, then the choice), and
+ *     log-probabilities taken from the untempered l''.  Nothing there is redefined: params becomes params[s].
+ *   A greedy row (temperature 0) inside a step that samples another row: its id is the argmax of its l'' (larger value, then smaller
+ *     id) -- no noise, no filter, no division by T; "sample_threshold" reads -inf and "sample_kept" the count of finite entries; its
+ *     log-probability is log_softmax(l'')[id] from the sampler's row statistics; the id equals the id a never-sampling engine writes.
+ *   Rows that have nothing on.  (top_k, top_p) = (0, 1.0f) in a step where another row filters: tau = -inf, id and noisy score are the
+ *     bits of the unfiltered sampler.  (repetition_penalty, no_repeat_ngram_size) = (1.0f, 0): the repetition launch leaves the row
+ *     untouched.  sequence_list = -1: the sequence-bias launch leaves the row untouched.
+ *   Lists.  q3a_set_sequence_bias_lists uploads up to 256 lists, entries as q3a_set_sequence_bias takes them, list after list;
+ *     q3a_set_sequence_bias is the case of one list, and without a row table every row uses list 0 (so nothing changes for it).  The
+ *     limits are totals over all lists: E <= 4096 entries, 65536 ids, L <= 32.  The same sequence twice is refused within a list and
+ *     allowed across lists.  A target's group belongs to one list; the groups of a list are contiguous, and a directory of 257 words
+ *     behind the tables names each list's range.
+ *   State.  The table persists until cleared (n_rows = 0) or replaced; setting it drops the decode state, as every setter here does.
+ *     The uniform setters keep working while a table is set: their values are remembered, not read, and are in force again when the
+ *     table is cleared.  q3a_debug_read "sampling" / "sampling_filter" / "repetition" / "sequence_bias" keep their meaning (the uniform
+ *     values; "sequence_bias" counts over all lists); "row_options" returns the table as uploaded (n_rows records, nothing while clear).
+ *   Graph signature.  The switches sampling / filter / repetition / sequence bias are evaluated over ANY row, and one more says
+ *     whether a table is present.  The records live in a device buffer of [4][n_rows][4] words that the kernels read with a row stride
+ *     of 4 words instead of 0, so another table of the same switches replays the same graph.  With the table cleared the engine is back
+ *     on the launches, graphs, ids, log-probability bits and pruned-pass counts it had without one; "device_bytes" is level across
+ *     set / clear cycles after the first.
+ *   Cost.  A greedy row in a batch where any row samples pays the sampled step (its row is read by the sampler's launches).
+ * Refused (q3a_last_error; the engine stays usable): every value the uniform setters refuse, reported with the row index; a
+ * sequence_list outside [-1, n_lists), by whichever of the two setters comes second; n_rows < 0; an aligner engine; a prefill whose
+ * batch differs from n_rows (q3a_prefill, q3a_run_resident, q3a_transcribe_batch[_ptrs], the draft and beam entry points); beam search
+ * and draft verification while any row has something on (the refusals they have towards the uniform settings); the two
+ * run-out-of-finite-logits rules of the repetition and sequence-bias sections, applied per row with that row's n-gram size and the
+ * -inf targets of that row's list.  q3a_score* and q3a_align* never see the table: bit-identical with it set and cleared.
+ * Out of scope: logit-bias vectors per row (a [S][vocab] operand, see the logit-bias section); a forced language per row
+ * (lang_prefix_ids stays one per call); per-row max_new_tokens; temperature fallback inside a batched call; q3a_group_* (set the
+ * table on each q3a_group_engine handle); a Philox row index other than s. */
+typedef struct q3a_row_options {
+  float    temperature;          /* 0: this row takes the argmax (larger value, then smaller id) */
+  float    min_p;                /* [0, 1] */
+  uint64_t seed;
+  int32_t  top_k;  float top_p;  /* (0, 1.0f): no filter on this row */
+  float    repetition_penalty;   /* (1.0f, 0): identity on this row */
+  int32_t  no_repeat_ngram_size;
+  int32_t  sequence_list;        /* -1: none; else an index into the engine's sequence-bias lists */
+} q3a_row_options;
+int32_t q3a_set_row_options(q3a_engine* e, const q3a_row_options* rows, int32_t n_rows);   /* n_rows = 0 clears the table */
+/* entries as q3a_set_sequence_bias takes them, list after list: list_lens[n_lists] entries each.  n_lists = 0 clears. */
+int32_t q3a_set_sequence_bias_lists(q3a_engine* e, const int32_t* ids, const int32_t* lens, const float* bias,
+                                    const int32_t* list_lens, int32_t n_lists);
+/* The chain on its own (no model), in the order the engine enqueues it: sequence bias, repetition, then the sampler (with the filter
+ * stage if any row filters; run twice on one table as in q3a_selftest_sample_filter) or -- no row samples -- fresh argmax partials,
+ * then argmax_finalize and the log-probability.  logits [S][V], hist [S][stride] with lens [S] ids of history each: row s is at step
+ * lens[s].  rows [S] and the lists as the two setters take them.  -> out_logits [S][V] (l''), out_ids, out_lp, out_z (the winning
+ * noisy score; l''_id on a greedy row; written only when a row samples), out_thr, out_kept [S] (written only when a row filters); any
+ * output may be null.  The arguments are validated before a device is looked for. */
+int32_t q3a_selftest_row_options(int32_t device, const float* logits, int32_t S, int32_t V, const int32_t* hist, int32_t stride,
+                                 const int32_t* lens, const q3a_row_options* rows, const int32_t* seq_ids, const int32_t* seq_lens,
+                                 const float* seq_bias, const int32_t* list_lens, int32_t n_lists, float* out_logits, int32_t* out_ids,
+                                 float* out_lp, float* out_z, float* out_thr, int32_t* out_kept);
 
 /* A/B knobs for kernel experiments (process-wide atomics, read from the environment once; not part of the reference
  * interface).  The knobs that shape the decode step are latched per batch at the next prefill and are part of the captured

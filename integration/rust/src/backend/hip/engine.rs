@@ -89,6 +89,10 @@ extern "C" {
                                 out_ids: *mut i32, out_lp: *mut f32) -> i32;
     pub fn q3a_parse_sequence_bias(text: *const c_char, ids: *mut i32, ids_cap: i32, lens: *mut i32, bias: *mut f32, cap: i32,
                                    n_ids: *mut i32, n: *mut i32) -> i32;
+    // row options: per-request decoding options inside one batch (include/q3asr.h "row options")
+    pub fn q3a_set_row_options(e: *mut q3a_engine, rows: *const RowOptions, n_rows: i32) -> i32;
+    pub fn q3a_set_sequence_bias_lists(e: *mut q3a_engine, ids: *const i32, lens: *const i32, bias: *const f32, list_lens: *const i32,
+                                       n_lists: i32) -> i32;
     // beam search: n-best hypotheses with scores, selected on the device (include/q3asr.h "beam search")
     pub fn q3a_beam_search_batch_ptrs(e: *mut q3a_engine, pcm16k: *const *const f32, n_samples: *const i64, u: i32,
                                       lang_prefix_ids: *const i32, n_prefix: i32, width: i32, max_new: i32, out_ids: *mut i32, stride: i32,
@@ -185,6 +189,47 @@ impl HipEngine {
         let rc = unsafe { q3a_set_sequence_bias(self.raw, ids.as_ptr(), lens.as_ptr(), bias.as_ptr(), entries.len() as i32) };
         if rc != 0 { bail!("{}", msg(unsafe { q3a_last_error(self.raw) })); }
         Ok(())
+    }
+
+    /// Several sequence-bias lists at once, for the rows of a row table to choose from (`RowOptions::sequence_list`); without a row
+    /// table every sequence uses list 0.  An empty slice clears them.
+    pub fn set_sequence_bias_lists(&self, lists: &[&[(&[i32], f32)]]) -> Result<()> {
+        let ids: Vec<i32> = lists.iter().flat_map(|l| l.iter()).flat_map(|(q, _)| q.iter().copied()).collect();
+        let lens: Vec<i32> = lists.iter().flat_map(|l| l.iter()).map(|(q, _)| q.len() as i32).collect();
+        let bias: Vec<f32> = lists.iter().flat_map(|l| l.iter()).map(|(_, b)| *b).collect();
+        let list_lens: Vec<i32> = lists.iter().map(|l| l.len() as i32).collect();
+        let rc = unsafe { q3a_set_sequence_bias_lists(self.raw, ids.as_ptr(), lens.as_ptr(), bias.as_ptr(), list_lens.as_ptr(), lists.len() as i32) };
+        if rc != 0 { bail!("{}", msg(unsafe { q3a_last_error(self.raw) })); }
+        Ok(())
+    }
+
+    /// One record of decoding options per sequence of the next batches (sequence s of a call reads `rows[s]`); an empty slice clears
+    /// the table and the engine's uniform settings are in force again.  The next prefill must hold `rows.len()` sequences.
+    pub fn set_row_options(&self, rows: &[RowOptions]) -> Result<()> {
+        let rc = unsafe { q3a_set_row_options(self.raw, rows.as_ptr(), rows.len() as i32) };
+        if rc != 0 { bail!("{}", msg(unsafe { q3a_last_error(self.raw) })); }
+        Ok(())
+    }
+}
+
+/// `q3a_row_options`: what the uniform setters hold once per engine, for one sequence of a batch.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct RowOptions {
+    pub temperature: f32,
+    pub min_p: f32,
+    pub seed: u64,
+    pub top_k: i32,
+    pub top_p: f32,
+    pub repetition_penalty: f32,
+    pub no_repeat_ngram_size: i32,
+    pub sequence_list: i32,
+}
+
+impl Default for RowOptions {
+    /// A plain greedy row: nothing on, no list.
+    fn default() -> Self {
+        RowOptions { temperature: 0.0, min_p: 0.0, seed: 0, top_k: 0, top_p: 1.0, repetition_penalty: 1.0, no_repeat_ngram_size: 0, sequence_list: -1 }
     }
 }
 

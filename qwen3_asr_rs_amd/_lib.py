@@ -27,6 +27,7 @@ SYMBOLS = [
     "q3a_set_sampling", "q3a_sample_word", "q3a_selftest_sample", "q3a_set_sampling_filter", "q3a_selftest_sample_filter",
     "q3a_set_repetition", "q3a_selftest_repeat",
     "q3a_set_sequence_bias", "q3a_selftest_seqbias", "q3a_parse_sequence_bias", "q3a_hotword_sequences", "q3a_banned_sequences",
+    "q3a_set_row_options", "q3a_set_sequence_bias_lists", "q3a_selftest_row_options",
     "q3a_selftest_gemm_launch", "q3a_selftest_qkrope_launch", "q3a_gemm256_split_rows",
     "q3a_selftest_gemv_launch", "q3a_selftest_decode_attn_launch",
     "q3a_selftest_decode_attn_split_launch", "q3a_selftest_oproj_head_launch", "q3a_selftest_gemv_parts_launch",
@@ -63,6 +64,11 @@ class Timings(C.Structure):
 class IoTimings(C.Structure):
     _fields_ = [("stage_ms", C.c_float), ("h2d_ms", C.c_float), ("wall_ms", C.c_float), ("pieces", C.c_int32), ("threads", C.c_int32),
                 ("mode", C.c_int32)]
+
+
+class RowOptionsC(C.Structure):  # q3a_row_options
+    _fields_ = [("temperature", C.c_float), ("min_p", C.c_float), ("seed", C.c_uint64), ("top_k", C.c_int32), ("top_p", C.c_float),
+                ("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int32), ("sequence_list", C.c_int32)]
 
 
 KC_NAMES = ["gemv_qkv_gateup", "decode_attn", "argmax", "gemm", "norm", "other", "gemv_o_proj", "gemv_down", "gemv_lm_head"]
@@ -171,6 +177,10 @@ def load() -> C.CDLL:
         "q3a_parse_sequence_bias": (i32, [C.c_char_p, i32p, i32, i32p, f32p, i32, i32p, i32p]),
         "q3a_hotword_sequences": (i32, [P, C.POINTER(C.c_char_p), i32, C.c_float, C.c_float, i32p, i32, i32p, f32p, i32, i32p, i32p]),
         "q3a_banned_sequences": (i32, [P, C.POINTER(C.c_char_p), i32, i32p, i32, i32p, f32p, i32, i32p, i32p]),
+        "q3a_set_row_options": (i32, [P, C.POINTER(RowOptionsC), i32]),
+        "q3a_set_sequence_bias_lists": (i32, [P, i32p, i32p, f32p, i32p, i32]),
+        "q3a_selftest_row_options": (i32, [i32, f32p, i32, i32, i32p, i32, i32p, C.POINTER(RowOptionsC), i32p, i32p, f32p, i32p, i32, f32p, i32p, f32p, f32p,
+                                           f32p, i32p]),
         "q3a_selftest_gemm_launch": (i32, [i32, i32, i32, P, P, i32, i32, i32, i32, i32, i32, i32, i32, i32, P, P, i32, P, P, i32, P, i32]),
         "q3a_selftest_qkrope_launch": (i32, [i32, i32, i32, P, i32, P, i32, i32, P, P, P, P, P, P, C.c_float, P, P, i32, i32, i32, i32, i32, P, P, P]),
         "q3a_selftest_gemv_launch": (i32, [i32, i32, P, i32, i32, P, P, C.c_float, P, i32, P, P, P, P, i32, i32, P, P]),

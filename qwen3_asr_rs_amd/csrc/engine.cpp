@@ -105,16 +105,31 @@ Knobs& knobs() {
 }  // namespace q3a
 
 namespace q3a {
-// The list of q3a_set_sequence_bias as the sequence-bias phase of history_apply_kernel reads it (engine_internal.h; kernels.h SeqBiasArgs).
+// The lists of q3a_set_sequence_bias_lists (q3a_set_sequence_bias: one list) as the sequence-bias phase of history_apply_kernel reads
+// them (engine_internal.h; kernels.h SeqBiasArgs).  One list gives the words it always gave, plus the directory.
 SeqBiasTable seqbias_layout(const char* what_c, const int32_t* ids, const int32_t* lens, const float* bias, int n, int V) {
+  if (n < 0) fail(std::string(what_c) + ": bad argument");
+  return seqbias_layout_lists(what_c, ids, lens, bias, &n, n > 0 ? 1 : 0, V);
+}
+SeqBiasTable seqbias_layout_lists(const char* what_c, const int32_t* ids, const int32_t* lens, const float* bias, const int32_t* list_lens, int n_lists, int V) {
   const std::string what = what_c;
-  if (n < 0 || (n > 0 && (!ids || !lens || !bias))) fail(what + ": bad argument");
-  if (n > SEQBIAS_MAX_ENTRIES) fail(what + ": " + std::to_string(n) + " entries, more than " + std::to_string(SEQBIAS_MAX_ENTRIES));
-  struct Ent { int off, len, order; float bias; };
+  if (n_lists < 0 || (n_lists > 0 && !list_lens)) fail(what + ": bad argument");
+  if (n_lists > SEQBIAS_MAX_LISTS) fail(what + ": " + std::to_string(n_lists) + " lists, more than " + std::to_string(SEQBIAS_MAX_LISTS));
+  long n_l = 0;
+  for (int k = 0; k < n_lists; ++k) {
+    if (list_lens[k] < 0) fail(what + ": list " + std::to_string(k) + " has a negative length");
+    n_l += list_lens[k];
+  }
+  if (n_l > 0 && (!ids || !lens || !bias)) fail(what + ": bad argument");
+  if (n_l > SEQBIAS_MAX_ENTRIES) fail(what + ": " + std::to_string(n_l) + " entries, more than " + std::to_string(SEQBIAS_MAX_ENTRIES));
+  const int n = (int)n_l;
+  struct Ent { int off, len, order, list; float bias; };
   std::vector<Ent> ents;
-  std::set<std::vector<int32_t>> seen;
+  std::set<std::vector<int32_t>> seen;  // of the list being read: the same sequence in two lists is two entries
   long total = 0;
+  int list = 0, list_end = n_lists > 0 ? list_lens[0] : 0;
   for (int i = 0; i < n; ++i) {
+    while (i >= list_end) { list_end += list_lens[++list]; seen.clear(); }
     const int L = lens[i];
     if (L < 1) fail(what + ": entry " + std::to_string(i) + " is an empty sequence");
     if (L > SEQBIAS_MAX_LEN) fail(what + ": entry " + std::to_string(i) + " has " + std::to_string(L) + " ids, more than " + std::to_string(SEQBIAS_MAX_LEN));
@@ -126,36 +141,84 @@ SeqBiasTable seqbias_layout(const char* what_c, const int32_t* ids, const int32_
     if (!seen.insert(std::vector<int32_t>(ids + total, ids + total + L)).second) fail(what + ": entry " + std::to_string(i) + " repeats the sequence of an earlier entry");
     const float v = bias[i];
     if (std::isnan(v) || v == INFINITY) fail(what + ": the bias of entry " + std::to_string(i) + " is NaN or +inf (finite or -inf only)");
-    ents.push_back({(int)total, L, i, v});
+    ents.push_back({(int)total, L, i, list, v});
     total += L;
   }
-  // stable by target id, the one-token entry of a target (there is at most one) first, the longer ones in the caller's order
+  // list after list; inside a list stable by target id, the one-token entry of a target (there is at most one) first, the longer ones
+  // in the caller's order
   std::stable_sort(ents.begin(), ents.end(), [&](const Ent& a, const Ent& b) {
+    if (a.list != b.list) return a.list < b.list;
     const int ta = ids[a.off + a.len - 1], tb = ids[b.off + b.len - 1];
     return ta != tb ? ta < tb : (a.len == 1) > (b.len == 1);
   });
   SeqBiasTable t;
   t.words.assign(SEQBIAS_TABLE_WORDS, 0u);
+  t.list_entries.assign((size_t)n_lists, 0);
+  t.list_inf_targets.assign((size_t)n_lists, 0);
   uint32_t* const w = t.words.data();
-  int pre = 0, last_inf_target = -1;
+  int pre = 0, last_inf_target = -1, cur_list = -1;
   for (size_t e = 0; e < ents.size(); ++e) {
     const Ent& x = ents[e];
     const int target = ids[x.off + x.len - 1];
-    if (t.groups == 0 || (int)w[SEQBIAS_OFF_TARGET + t.groups - 1] != target) {
+    if (x.list != cur_list) {  // (a target's group belongs to one list: a new list starts a new group whatever its first target)
+      for (int k = cur_list + 1; k <= x.list; ++k) w[SEQBIAS_OFF_LISTS + k] = (uint32_t)t.groups;
+      last_inf_target = -1;
+    }
+    if (x.list != cur_list || (int)w[SEQBIAS_OFF_TARGET + t.groups - 1] != target) {
       w[SEQBIAS_OFF_TARGET + t.groups] = (uint32_t)target;
       w[SEQBIAS_OFF_BEGIN + t.groups] = (uint32_t)e;
       ++t.groups;
     }
+    cur_list = x.list;
+    ++t.list_entries[x.list];
     memcpy(&w[SEQBIAS_OFF_BIAS + e], &x.bias, 4);
     w[SEQBIAS_OFF_PRE_OFF + e] = (uint32_t)pre;
     for (int k = 0; k + 1 < x.len; ++k) w[SEQBIAS_OFF_PRE_IDS + pre++] = (uint32_t)ids[x.off + k];
-    if (x.bias == -INFINITY && target != last_inf_target) { ++t.inf_targets; last_inf_target = target; }
+    if (x.bias == -INFINITY && target != last_inf_target) { ++t.list_inf_targets[x.list]; last_inf_target = target; }
   }
+  for (int k = cur_list + 1; k <= SEQBIAS_MAX_LISTS; ++k) w[SEQBIAS_OFF_LISTS + k] = (uint32_t)t.groups;  // (lists behind the last entry: empty)
   w[SEQBIAS_OFF_BEGIN + t.groups] = (uint32_t)ents.size();
   w[SEQBIAS_OFF_PRE_OFF + ents.size()] = (uint32_t)pre;
-  t.entries = (int)ents.size(); t.ids = (int)total;
+  t.entries = (int)ents.size(); t.ids = (int)total; t.lists = n_lists;
+  t.inf_targets = n_lists > 0 ? t.list_inf_targets[0] : 0;
   w[0] = (uint32_t)t.groups; w[1] = (uint32_t)t.entries;
   return t;
+}
+
+// q3a_set_row_options' refusals that need no engine (engine_internal.h): every value a uniform setter refuses, with the row's index.
+void row_options_check(const char* what_c, const q3a_row_options* rows, int n_rows, int n_lists, int V) {
+  const std::string what = what_c;
+  if (n_rows < 0 || (n_rows > 0 && !rows)) fail(what + ": bad argument");
+  for (int r = 0; r < n_rows; ++r) {
+    const q3a_row_options& o = rows[r];
+    const std::string row = what + ": row " + std::to_string(r) + ": ";
+    if (!(o.temperature >= 0.f) || !std::isfinite(o.temperature)) fail(row + "temperature must be finite and >= 0 (0: this row takes the argmax)");
+    if (!(o.min_p >= 0.f && o.min_p <= 1.f)) fail(row + "min_p must lie in [0, 1]");
+    if (o.top_k < 0) fail(row + "top_k must be >= 0 (0 turns top-k off)");
+    if (!(o.top_p > 0.f && o.top_p <= 1.f)) fail(row + "top_p must lie in (0, 1] (1 turns top-p off)");
+    if (!std::isfinite(o.repetition_penalty) || !(o.repetition_penalty > 0.f)) fail(row + "repetition_penalty must be finite and > 0 (1 turns the penalty off)");
+    if (o.no_repeat_ngram_size < 0 || o.no_repeat_ngram_size > 32) fail(row + "no_repeat_ngram_size must lie in [0, 32] (0 turns the ban off)");
+    if (!(o.repetition_penalty == 1.f && o.no_repeat_ngram_size == 0) && V > REPEAT_MAX_VOCAB)
+      fail(row + "the vocabulary (" + std::to_string(V) + ") exceeds the " + std::to_string(REPEAT_MAX_VOCAB) + " ids the kernel's bitmap holds");
+    if (o.sequence_list < -1 || o.sequence_list >= n_lists)
+      fail(row + "sequence_list " + std::to_string(o.sequence_list) + " is outside [-1, " + std::to_string(n_lists) + ") (q3a_set_sequence_bias_lists sets the lists)");
+  }
+}
+// The table as the device holds it: four regions of [n_rows][4] words in the words of the uniform buffers (DecodeStep::row_opts).
+std::vector<uint32_t> row_options_words(const q3a_row_options* rows, int n_rows) {
+  std::vector<uint32_t> w((size_t)16 * n_rows, 0u);
+  for (int r = 0; r < n_rows; ++r) {
+    const q3a_row_options& o = rows[r];
+    uint32_t* const sp = &w[(size_t)(0 * n_rows + r) * 4];
+    uint32_t* const fl = &w[(size_t)(1 * n_rows + r) * 4];
+    uint32_t* const rp = &w[(size_t)(2 * n_rows + r) * 4];
+    memcpy(&sp[0], &o.temperature, 4); memcpy(&sp[1], &o.min_p, 4);
+    sp[2] = (uint32_t)o.seed; sp[3] = (uint32_t)(o.seed >> 32);
+    fl[0] = (uint32_t)o.top_k; memcpy(&fl[1], &o.top_p, 4);
+    memcpy(&rp[0], &o.repetition_penalty, 4); rp[1] = (uint32_t)o.no_repeat_ngram_size;
+    w[(size_t)(3 * n_rows + r) * 4] = (uint32_t)o.sequence_list;
+  }
+  return w;
 }
 }  // namespace q3a
 
@@ -189,6 +252,9 @@ struct StepView {
   const bool& sampling_filter_on_;  // q3a_set_sampling_filter: top_k != 0 or top_p != 1 (likewise; acts only while sampling is on)
   const bool& repetition_on_;  // q3a_set_repetition: a penalty != 1 or an n-gram size > 0 (likewise)
   const bool& sequence_bias_on_;  // q3a_set_sequence_bias: a list with at least one entry (likewise)
+  // q3a_set_row_options: a row table is set (likewise).  The four switches above then say "on for ANY row", and the kernels read
+  // row s's record from DecodeStep::row_opts instead of the uniform buffers
+  const bool& row_table_on_;
 
   bool precise() const { return opts.precise != 0; }
   bool token_lp() const { return opts.token_logprobs != 0; }
@@ -226,6 +292,10 @@ struct DecodeStep : StepView {
   DevBuf samp_filter, samp_hist, samp_sel;
   DevBuf rep_params;  // q3a_set_repetition: {penalty (fp32 bits), n-gram size, 0, 0} as history_apply_kernel reads them (a new setting needs no new graph)
   DevBuf seq_bias;  // q3a_set_sequence_bias: the list's tables and counts, SEQBIAS_TABLE_WORDS words whatever the list (a new list needs no new graph); allocated by the first non-empty set
+  // q3a_set_row_options: four regions of [B][4] words, one record per row each, as the kernels read the uniform buffers: sampling
+  // (samp_params), filter (samp_filter), repetition (rep_params), then {the row's sequence-bias list or -1, 0, 0, 0}.  Allocated by the
+  // first table and kept; another table of the same switches needs no new graph
+  DevBuf row_opts;
   DevBuf draft_accepted;  // draft verification (k_draft.hip): [2 B] first mismatch k per sequence, then its token -- one small D2H copy per prefill
   // f(buffer) for every DevBuf declared above, in declaration order (s: a DecodeStep, const or not).  The declarations of this
   // struct ARE the guarded set: tests/test_host.py::test_step_buffers_cover_the_captured_step compares this list with them.
@@ -235,8 +305,18 @@ struct DecodeStep : StepView {
                     &s.rope_cur, &s.rope_cos, &s.rope_sin, &s.n_done, &s.forced_tok,
                     &s.beam_cand_val, &s.beam_cand_idx, &s.beam_part_max, &s.beam_part_sum, &s.beam_topk_ids, &s.beam_topk_lp, &s.beam_score, &s.beam_finished,
                     &s.beam_parent, &s.beam_token, &s.beam_feed, &s.beam_hist_parent, &s.beam_hist_token, &s.beam_hist_lp, &s.beam_state, &s.beam_lo,
-                    &s.logit_bias, &s.samp_params, &s.samp_max, &s.samp_sum, &s.samp_filter, &s.samp_hist, &s.samp_sel, &s.rep_params, &s.seq_bias, &s.draft_accepted})
+                    &s.logit_bias, &s.samp_params, &s.samp_max, &s.samp_sum, &s.samp_filter, &s.samp_hist, &s.samp_sel, &s.rep_params, &s.seq_bias, &s.row_opts, &s.draft_accepted})
       f(*b);
+  }
+
+  // region r of row_opts (0 sampling, 1 filter, 2 repetition, 3 list) while a row table is set, else the uniform record; the words
+  // between two rows' records go to `stride` (kernels.h row_stride)
+  enum { kRowSampling = 0, kRowFilter = 1, kRowRepetition = 2, kRowList = 3, kRowRegions = 4 };
+  const uint32_t* row_words(int region, const DevBuf& uniform, int& stride) const {
+    stride = row_table_on_ ? 4 : 0;
+    if (!row_table_on_) return uniform.as<uint32_t>();
+    if (!row_opts.p || row_opts.cap < (size_t)kRowRegions * B * 16) fail("row options: a table without its buffer");
+    return row_opts.as<uint32_t>() + (size_t)region * B * 4;
   }
 
   void tap(const char* name, const void* ptr, size_t bytes) { taps.copy(opts.debug_taps, stream, name, ptr, bytes); }
@@ -383,6 +463,7 @@ struct DecodeStep : StepView {
     sa.logits = logits.as<float>(); sa.S = B; sa.V = d.vocab; seqbias_point(sa, seq_bias.p);
     sa.out_ids = out_ids.as<int>(); sa.out_stride = max_new; sa.step_count = step_count.as<int>();
     if (!seq_bias.p) fail("sequence bias: on without its tables");
+    if (row_table_on_) sa.row_list = reinterpret_cast<const int*>(row_words(kRowList, seq_bias, sa.row_stride));  // (else list 0 for every row)
     timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_seqbias_apply(sa, stream)); });
     return partials ? enqueue_rewritten_partials(part) : 0;
   }
@@ -391,7 +472,7 @@ struct DecodeStep : StepView {
   // included, take their place (the sampler writes its own instead).  Returns the partials per row finalize then merges.
   int enqueue_repetition(const ArgmaxPartials& part, bool partials) {
     RepeatArgs ra{};
-    ra.logits = logits.as<float>(); ra.S = B; ra.V = d.vocab; ra.params = rep_params.as<uint32_t>();
+    ra.logits = logits.as<float>(); ra.S = B; ra.V = d.vocab; ra.params = row_words(kRowRepetition, rep_params, ra.row_stride);
     ra.out_ids = out_ids.as<int>(); ra.out_stride = max_new; ra.step_count = step_count.as<int>();
     timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_repeat_apply(ra, stream)); });
     return partials ? enqueue_rewritten_partials(part) : 0;
@@ -400,15 +481,15 @@ struct DecodeStep : StepView {
   // ones into the same buffers -- no log-sum channel, the drawn id is not the maximum -- and finalize merges those instead.
   void enqueue_sampler(FinalizeArgs& f) {
     SampleArgs sa{};
-    sa.logits = logits.as<float>(); sa.S = B; sa.V = d.vocab; sa.params = samp_params.as<uint32_t>(); sa.step_count = step_count.as<int>();
+    sa.logits = logits.as<float>(); sa.S = B; sa.V = d.vocab; sa.params = row_words(kRowSampling, samp_params, sa.row_stride); sa.step_count = step_count.as<int>();
     sa.chunk_max = samp_max.as<float>(); sa.chunk_sum = samp_sum.as<float>();
     f.part.sum = nullptr; f.c.out_lp = nullptr; f.n_part = sample_chunks(d.vocab);
     sa.part = f.part;
     if (!sampling_filter_on_) { timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_sample(sa, stream)); }); return; }
     // top-k / top-p: the threshold stage between the sampler's two launches
-    if (!samp_filter.p || !samp_hist.p || !samp_sel.p) fail("sampling filter: on without its buffers");
+    if ((!row_table_on_ && !samp_filter.p) || !samp_hist.p || !samp_sel.p) fail("sampling filter: on without its buffers");
     SampleFilterArgs sf{};
-    sf.filter = samp_filter.as<uint32_t>(); sf.hist_mass = samp_hist.as<unsigned long long>();
+    sf.filter = row_words(kRowFilter, samp_filter, sf.row_stride); sf.hist_mass = samp_hist.as<unsigned long long>();
     sf.hist_cnt = reinterpret_cast<uint32_t*>(sf.hist_mass + (size_t)B * SAMPLE_BUCKETS);
     sf.tau_sel = samp_sel.as<float>(); sf.kept = samp_sel.as<int>() + B;
     timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_sample_filtered(sa, sf, stream)); });
@@ -803,11 +884,17 @@ struct q3a_engine : CallState {
   bool sequence_bias_on_ = false;       // q3a_set_sequence_bias: a list with at least one entry (k_repeat.hip; graph signature)
   int seq_bias_stats_[4] = {0, 0, 0, 0};  // of the list step.seq_bias holds: on, entries, ids over all entries, distinct targets
   int seq_bias_inf_targets_ = 0;        // distinct targets of its -inf entries (0 while off)
+  std::vector<int> seq_list_entries_, seq_list_inf_;  // per list of q3a_set_sequence_bias_lists: entries, distinct -inf targets
+  // q3a_set_row_options.  The four switches above are what the step runs under: the uniform setters' own while no table is set
+  // (uni_on_, in the order sampling, filter, repetition, sequence bias), "on for any row" while one is.
+  bool row_table_on_ = false;           // (graph signature)
+  std::vector<q3a_row_options> rows_;   // the table as uploaded (q3a_debug_read "row_options")
+  bool uni_on_[4] = {false, false, false, false};
 
   // ---- the captured decode step: its buffers and launches, and all it sees of the members above ----
   DecodeStep step{StepView{d, L, opts, arena, arena_flags, stream, chain_streams, join_ev, fork_ev, n_cu, host_prog_dev, prof, taps, lm_q, lm_qs, lm_q_cols,
                            B, max_ctx, max_new, gsize, live_nsplit_, live_kps_, attn_nsplit, min_P_, part_stride, beam_w(), kv_layer_elems, head_logits(),
-                           k_parallel_groups, k_skinny_q, k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, k_oproj_by_head, logit_bias_on_, sampling_on_, sampling_filter_on_, repetition_on_, sequence_bias_on_}};
+                           k_parallel_groups, k_skinny_q, k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, k_oproj_by_head, logit_bias_on_, sampling_on_, sampling_filter_on_, repetition_on_, sequence_bias_on_, row_table_on_}};
 
   // (the mode rules are stated once, in StepView)
   bool precise() const { return step.precise(); }
@@ -1729,8 +1816,8 @@ struct q3a_engine : CallState {
     });
     char buf[256];
     // (one field per latched knob, as latched: packing several into one integer let distinct settings collide -- ADVICE r5)
-    snprintf(buf, sizeof(buf), "%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.b%d.lb%d.sm%d.sf%d.rp%d.sb%d/%d.%d/%d/%d/%p/%016llx", B, gsize, k_parallel_groups, k_skinny_q,
-             k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, k_oproj_by_head, (int)(min_P_ < 256), (int)head_logits(), (int)token_lp(), beam_w(), (int)logit_bias_on_, (int)sampling_on_, (int)(sampling_on_ && sampling_filter_on_), (int)repetition_on_, (int)sequence_bias_on_, live_nsplit_, live_kps_,
+    snprintf(buf, sizeof(buf), "%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.b%d.lb%d.sm%d.sf%d.rp%d.sb%d.rt%d/%d.%d/%d/%d/%p/%016llx", B, gsize, k_parallel_groups, k_skinny_q,
+             k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, k_oproj_by_head, (int)(min_P_ < 256), (int)head_logits(), (int)token_lp(), beam_w(), (int)logit_bias_on_, (int)sampling_on_, (int)(sampling_on_ && sampling_filter_on_), (int)repetition_on_, (int)sequence_bias_on_, (int)row_table_on_, live_nsplit_, live_kps_,
              max_ctx, max_new, (const void*)arena, (unsigned long long)h);
     return buf;
   }
@@ -1954,7 +2041,8 @@ struct q3a_engine : CallState {
     const bool on = !(n == 0 && default_bias == 0.f);
     const bool eos_open = (kEos0 < V && b[kEos0] != -INFINITY) || (kEos1 < V && b[kEos1] != -INFINITY);
     repetition_bias_check(what, rep_ngram_, eos_open, finite);
-    sequence_bias_check(what, seq_bias_inf_targets_, default_bias == -INFINITY, finite, rep_ngram_);
+    if (!row_table_on_) sequence_bias_check(what, seq_bias_inf_targets_, default_bias == -INFINITY, finite, rep_ngram_);  // (list 0 for every row)
+    rows_finite_check(what, rows_, seq_list_inf_, default_bias == -INFINITY, finite, eos_open);
     drop_decode_state();
     HIPCHK(hipMemcpyAsync(step.logit_bias.p, b.data(), (size_t)V * 4, hipMemcpyHostToDevice, stream));
     HIPCHK(hipStreamSynchronize(stream));
@@ -1981,7 +2069,8 @@ struct q3a_engine : CallState {
     HIPCHK(hipMemcpyAsync(step.rep_params.p, w, 16, hipMemcpyHostToDevice, stream));
     HIPCHK(hipStreamSynchronize(stream));
     rep_penalty_ = penalty; rep_ngram_ = ngram;
-    repetition_on_ = on;
+    uni_on_[2] = on;
+    refresh_switches();
   }
   // the one way a row could run out of finite logits: an n-gram ban over a bias that forbids every EOS and leaves no more tokens
   // finite than a sequence may generate (asked by whichever of the two setters comes second)
@@ -1994,19 +2083,82 @@ struct q3a_engine : CallState {
   // fixed size the kernel reads, counts included, so another list replays the same graph; on / off is part of the graph signature.
   // The buffer is allocated by the first non-empty list and kept until the engine goes.  No decode state afterwards.
   void set_sequence_bias(const int32_t* ids, const int32_t* lens, const float* bias, int n) {
-    const char* what = "q3a_set_sequence_bias";
+    if (n < 0) fail("q3a_set_sequence_bias: bad argument");
+    set_sequence_bias_lists("q3a_set_sequence_bias", ids, lens, bias, &n, n > 0 ? 1 : 0);
+  }
+  // q3a_set_sequence_bias_lists: the same for several lists in the one buffer, its directory included (q3a_set_sequence_bias is the
+  // case of one list).  Without a row table every row reads list 0; with one, row s reads the list its record names.
+  void set_sequence_bias_lists(const char* what, const int32_t* ids, const int32_t* lens, const float* bias, const int32_t* list_lens, int n_lists) {
     require_asr(what);
-    const SeqBiasTable tb = seqbias_layout(what, ids, lens, bias, n, d.vocab);
-    sequence_bias_check(what, tb.inf_targets, logit_bias_allow_list_, logit_bias_finite_, rep_ngram_);
+    const SeqBiasTable tb = seqbias_layout_lists(what, ids, lens, bias, list_lens, n_lists, d.vocab);
+    // without a row table every row reads list 0: the uniform rule; with one the rule is asked row by row, and again for list 0 when
+    // the table is cleared
+    if (!row_table_on_) sequence_bias_check(what, tb.inf_targets, logit_bias_allow_list_, logit_bias_finite_, rep_ngram_);
+    for (size_t r = 0; r < rows_.size(); ++r)  // (the second of the two setters to come asks)
+      if (rows_[r].sequence_list >= n_lists)
+        fail(std::string(what) + ": row " + std::to_string(r) + " of the row table names sequence_list " + std::to_string(rows_[r].sequence_list) + ", outside [-1, " + std::to_string(n_lists) + ")");
+    rows_finite_check(what, rows_, tb.list_inf_targets, logit_bias_allow_list_, logit_bias_finite_, logit_bias_eos_open_);
     drop_decode_state();
     if (tb.entries > 0 || step.seq_bias.p) {  // (an engine that never had a list has no buffer, and clearing allocates none)
       step.seq_bias.ensure(SEQBIAS_TABLE_WORDS * 4);
       HIPCHK(hipMemcpyAsync(step.seq_bias.p, tb.words.data(), SEQBIAS_TABLE_WORDS * 4, hipMemcpyHostToDevice, stream));
       HIPCHK(hipStreamSynchronize(stream));
     }
-    sequence_bias_on_ = tb.entries > 0;
-    seq_bias_stats_[0] = sequence_bias_on_; seq_bias_stats_[1] = tb.entries; seq_bias_stats_[2] = tb.ids; seq_bias_stats_[3] = tb.groups;
+    uni_on_[3] = n_lists > 0 && tb.list_entries[0] > 0;
+    seq_bias_stats_[0] = uni_on_[3]; seq_bias_stats_[1] = tb.entries; seq_bias_stats_[2] = tb.ids; seq_bias_stats_[3] = tb.groups;
     seq_bias_inf_targets_ = tb.inf_targets;
+    seq_list_entries_ = tb.list_entries; seq_list_inf_ = tb.list_inf_targets;
+    refresh_switches();
+  }
+  // Row options (q3asr.h q3a_set_row_options).  The records go to step.row_opts in the words the uniform buffers hold, one per row
+  // and region, so the kernels read row s's record where they read the one record (row stride 4 instead of 0) and another table of
+  // the same switches replays the same graph.  n_rows = 0 clears: the uniform settings, remembered all along, are in force again.
+  void set_row_options(const q3a_row_options* rows, int n_rows) {
+    const char* what = "q3a_set_row_options";
+    require_asr(what);
+    row_options_check(what, rows, n_rows, (int)seq_list_entries_.size(), d.vocab);
+    const std::vector<q3a_row_options> table(rows, rows + n_rows);
+    rows_finite_check(what, table, seq_list_inf_, logit_bias_allow_list_, logit_bias_finite_, logit_bias_eos_open_);
+    // clearing puts every row back on list 0 under the uniform n-gram size: the rule no setter asked for it while the table was on
+    if (n_rows == 0 && row_table_on_) sequence_bias_check(what, seq_bias_inf_targets_, logit_bias_allow_list_, logit_bias_finite_, rep_ngram_);
+    drop_decode_state();
+    if (n_rows > 0) {
+      const std::vector<uint32_t> w = row_options_words(rows, n_rows);
+      step.row_opts.ensure(w.size() * 4);
+      HIPCHK(hipMemcpyAsync(step.row_opts.p, w.data(), w.size() * 4, hipMemcpyHostToDevice, stream));
+      HIPCHK(hipStreamSynchronize(stream));
+    }
+    rows_ = table;
+    row_table_on_ = n_rows > 0;
+    refresh_switches();
+  }
+  // the switches the step runs under (graph signature): the uniform setters' own, or "for any row" of the table
+  void refresh_switches() {
+    bool on[4] = {uni_on_[0], uni_on_[1], uni_on_[2], uni_on_[3]};
+    if (row_table_on_) {
+      on[0] = on[1] = on[2] = on[3] = false;
+      for (const q3a_row_options& r : rows_) {
+        on[0] |= r.temperature > 0.f;
+        on[1] |= r.temperature > 0.f && (r.top_k != 0 || r.top_p != 1.f);  // (a greedy row is not filtered)
+        on[2] |= !(r.repetition_penalty == 1.f && r.no_repeat_ngram_size == 0);
+        on[3] |= r.sequence_list >= 0 && seq_list_entries_[(size_t)r.sequence_list] > 0;
+      }
+    }
+    sampling_on_ = on[0]; sampling_filter_on_ = on[1]; repetition_on_ = on[2]; sequence_bias_on_ = on[3];
+  }
+  // the two run-out-of-finite-logits rules, row by row: each row's n-gram size and the -inf targets of its own list
+  void rows_finite_check(const char* what, const std::vector<q3a_row_options>& rows, const std::vector<int>& list_inf, bool allow_list, int finite, bool eos_open) const {
+    for (size_t r = 0; r < rows.size(); ++r) {
+      const std::string w = std::string(what) + ": row " + std::to_string(r);
+      const int k = rows[r].sequence_list, inf = k >= 0 && (size_t)k < list_inf.size() ? list_inf[(size_t)k] : 0;
+      repetition_bias_check(w.c_str(), rows[r].no_repeat_ngram_size, eos_open, finite);
+      sequence_bias_check(w.c_str(), inf, allow_list, finite, rows[r].no_repeat_ngram_size);
+    }
+  }
+  // a prefill under a row table serves exactly the table's rows
+  void row_table_batch_check(const char* what, int b) const {
+    if (row_table_on_ && b != (int)rows_.size())
+      fail(std::string(what) + ": a batch of " + std::to_string(b) + " sequences under a row table of " + std::to_string(rows_.size()) + " rows (q3a_set_row_options; n_rows = 0 clears it)");
   }
   // the one way a row could run out of finite logits under a sequence bias: -inf entries over an allow-list that leaves no more
   // tokens finite than those entries can take away, plus -- with an n-gram ban -- the tokens a sequence may generate (asked by
@@ -2037,7 +2189,8 @@ struct q3a_engine : CallState {
     HIPCHK(hipMemcpyAsync(step.samp_params.p, w, 16, hipMemcpyHostToDevice, stream));
     HIPCHK(hipStreamSynchronize(stream));
     memcpy(samp_words_, w, 16);
-    sampling_on_ = temperature > 0.f;
+    uni_on_[0] = temperature > 0.f;
+    refresh_switches();
   }
   // Top-k / top-p (q3asr.h q3a_set_sampling_filter).  As q3a_set_sampling: the values live in a device buffer, on / off is part of
   // the graph signature, no decode state afterwards.  The first setting that is not (0, 1) allocates the buffer.
@@ -2056,7 +2209,8 @@ struct q3a_engine : CallState {
       HIPCHK(hipStreamSynchronize(stream));
     }
     memcpy(samp_filter_words_, w, 8);
-    sampling_filter_on_ = on;
+    uni_on_[1] = on;
+    refresh_switches();
   }
   void beam_sampling_check(const char* what) const {
     if (sampling_on_) fail(std::string(what) + ": sampling is on (q3a_set_sampling with temperature > 0); beam search selects deterministically -- turn it off first");
@@ -2462,6 +2616,7 @@ int32_t q3a_beam_search_batch_ptrs(q3a_engine* e, const float* const* pcm16k, co
   e->beam_repetition_check("q3a_beam_search_batch");
   e->beam_sequence_bias_check("q3a_beam_search_batch");
   e->beam_bias_check("q3a_beam_search_batch", width);
+  e->row_table_batch_check("q3a_beam_search_batch", U * width);
   e->begin_call(false, true);  // every round selects on the stored logits
   // the W slots of an utterance are W ordinary sequences of the batch
   e->whole_path_front("q3a_beam_search_batch", pcm16k, n_samples, U, width, want, [&] { return e->asr_prompts(lang_prefix_ids, n_prefix); });
@@ -2519,6 +2674,22 @@ int32_t q3a_set_sequence_bias(q3a_engine* e, const int32_t* ids, const int32_t* 
   Q3A_CATCH(e)
 }
 
+int32_t q3a_set_sequence_bias_lists(q3a_engine* e, const int32_t* ids, const int32_t* lens, const float* bias, const int32_t* list_lens, int32_t n_lists) {
+  if (!e) return 1;
+  Q3A_TRY(e)
+  HIPCHK(hipSetDevice(e->device));
+  e->set_sequence_bias_lists("q3a_set_sequence_bias_lists", ids, lens, bias, list_lens, n_lists);
+  Q3A_CATCH(e)
+}
+
+int32_t q3a_set_row_options(q3a_engine* e, const q3a_row_options* rows, int32_t n_rows) {
+  if (!e) return 1;
+  Q3A_TRY(e)
+  HIPCHK(hipSetDevice(e->device));
+  e->set_row_options(rows, n_rows);
+  Q3A_CATCH(e)
+}
+
 int32_t q3a_upload_pcm(q3a_engine* e, const float* pcm16k, const int64_t* n_samples, int32_t B) {
   if (!e) return 1;
   Q3A_TRY(e)
@@ -2566,6 +2737,7 @@ int32_t q3a_prefill(q3a_engine* e, const int32_t* ids, const int32_t* lens, int3
   Q3A_TRY(e)
   e->require_asr("q3a_prefill");
   HIPCHK(hipSetDevice(e->device));
+  e->row_table_batch_check("q3a_prefill", B);
   e->begin_call(false, true);
   e->setup_prompts(ids, lens, B, e->opts.max_new_tokens);
   e->run_prefill();
@@ -2620,6 +2792,7 @@ int32_t q3a_run_resident(q3a_engine* e, const int32_t* lang_prefix_ids, int32_t 
   e->begin_call(fixed_new_tokens > 0, e->opts.debug_taps != 0);
   e->rewind(Stage::Batch);  // mel and encoder run again, on the PCM that is resident
   e->require(Stage::Batch, "q3a_run_resident: no batch uploaded");
+  e->row_table_batch_check("q3a_run_resident", e->B);
   // prompts and every table / buffer of the prefill + decode: host integers only (T[] of set_batch), before the batch's first kernel
   const auto pr = e->asr_prompts(lang_prefix_ids, n_prefix);
   e->setup_prompts(pr.first.data(), pr.second.data(), e->B, e->max_new_request(max_new, fixed_new_tokens), true);
@@ -2650,6 +2823,7 @@ int32_t q3a_transcribe_batch_ptrs(q3a_engine* e, const float* const* pcm16k, con
   if (!e) return 1;
   Q3A_TRY(e)
   e->require_asr("q3a_transcribe_batch");
+  e->row_table_batch_check("q3a_transcribe_batch", B);
   const auto w0 = std::chrono::steady_clock::now();
   e->begin_call(fixed_new_tokens > 0, e->opts.debug_taps != 0);
   e->whole_path_front("q3a_transcribe_batch", pcm16k, n_samples, B, 1, e->max_new_request(max_new, fixed_new_tokens),
@@ -2684,6 +2858,7 @@ int32_t q3a_prefill_draft(q3a_engine* e, const int32_t* prompt_ids, const int32_
   Q3A_TRY(e)
   const char* what = "q3a_prefill_draft";
   e->draft_check(what);
+  e->row_table_batch_check(what, B);
   if (!prompt_ids || !prompt_lens || !draft_lens || B < 1) fail(std::string(what) + ": bad argument");
   HIPCHK(hipSetDevice(e->device));
   e->require_encoded(what, B);
@@ -2709,6 +2884,7 @@ int32_t q3a_transcribe_draft_batch_ptrs(q3a_engine* e, const float* const* pcm16
   Q3A_TRY(e)
   const char* what = "q3a_transcribe_draft_batch";
   e->draft_check(what);
+  e->row_table_batch_check(what, B);
   if (!draft_lens || !out_lens || stride < 0 || (stride > 0 && !out_ids) || n_prefix < 0 || B < 1) fail(std::string(what) + ": bad argument");
   const auto w0 = std::chrono::steady_clock::now();
   e->begin_call(false, e->opts.debug_taps != 0);
@@ -2895,13 +3071,13 @@ int32_t q3a_debug_read(q3a_engine* e, const char* name, void* dst, uint64_t byte
   }
   if (strcmp(name, "sampling") == 0) {  // {on, temperature bits, min_p bits, seed low, seed high} as last set
     e->require_asr("q3a_debug_read: sampling");
-    const uint32_t st[5] = {e->sampling_on_ ? 1u : 0u, e->samp_words_[0], e->samp_words_[1], e->samp_words_[2], e->samp_words_[3]};
+    const uint32_t st[5] = {e->uni_on_[0] ? 1u : 0u, e->samp_words_[0], e->samp_words_[1], e->samp_words_[2], e->samp_words_[3]};
     give(st, 20, false);
     return 0;
   }
   if (strcmp(name, "sampling_filter") == 0) {  // {on, top_k, top_p bits} as last set
     e->require_asr("q3a_debug_read: sampling_filter");
-    const uint32_t st[3] = {e->sampling_filter_on_ ? 1u : 0u, e->samp_filter_words_[0], e->samp_filter_words_[1]};
+    const uint32_t st[3] = {e->uni_on_[1] ? 1u : 0u, e->samp_filter_words_[0], e->samp_filter_words_[1]};
     give(st, 12, false);
     return 0;
   }
@@ -2917,7 +3093,7 @@ int32_t q3a_debug_read(q3a_engine* e, const char* name, void* dst, uint64_t byte
   }
   if (strcmp(name, "repetition") == 0) {  // {on, penalty bits, n-gram size} as last set
     e->require_asr("q3a_debug_read: repetition");
-    uint32_t st[3] = {e->repetition_on_ ? 1u : 0u, 0u, (uint32_t)e->rep_ngram_};
+    uint32_t st[3] = {e->uni_on_[2] ? 1u : 0u, 0u, (uint32_t)e->rep_ngram_};
     memcpy(&st[1], &e->rep_penalty_, 4);
     give(st, 12, false);
     return 0;
@@ -2925,6 +3101,11 @@ int32_t q3a_debug_read(q3a_engine* e, const char* name, void* dst, uint64_t byte
   if (strcmp(name, "sequence_bias") == 0) {  // {on, entries, ids over all entries, distinct targets} of the list as last set
     e->require_asr("q3a_debug_read: sequence_bias");
     give(e->seq_bias_stats_, 16, false);
+    return 0;
+  }
+  if (strcmp(name, "row_options") == 0) {  // the table as uploaded: n_rows records of q3a_row_options (nothing while no table is set)
+    e->require_asr("q3a_debug_read: row_options");
+    give(e->rows_.data(), e->rows_.size() * sizeof(q3a_row_options), false);
     return 0;
   }
   if (strcmp(name, "logit_bias_stats") == 0) {

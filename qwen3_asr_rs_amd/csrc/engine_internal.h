@@ -58,12 +58,24 @@ struct DevBuf {
 // q3a_debug_read "sequence_bias" need to know of it.
 struct SeqBiasTable {
   std::vector<uint32_t> words;  // [SEQBIAS_TABLE_WORDS]
-  int groups = 0, entries = 0, ids = 0, inf_targets = 0;  // groups: distinct targets; inf_targets: distinct targets of -inf entries
+  int groups = 0, entries = 0, ids = 0, inf_targets = 0;  // groups: distinct targets; inf_targets: distinct targets of -inf entries (of list 0)
+  int lists = 0;                                          // totals above are over all lists
+  std::vector<int> list_entries, list_inf_targets;        // [lists] entries and distinct -inf targets of every list
 };
 // ids: the entries' ids one after the other, lens [n], bias [n] (n >= 0).  Entries are sorted stably by target id, the one-token
 // entry of a target first.  Throws with `what` in front on every refusal of the header's list that needs no engine: an id outside
 // [0, V), an empty or too long entry, too many entries or ids, a sequence given twice, a NaN or +inf bias.  engine.cpp
 SeqBiasTable seqbias_layout(const char* what, const int32_t* ids, const int32_t* lens, const float* bias, int n, int V);
+// The same for n_lists lists given one after the other, list_lens[k] entries each (q3a_set_sequence_bias_lists): the entries of a list
+// stay together, so its target groups are contiguous and the block's directory (SEQBIAS_OFF_LISTS) names their range; a sequence may
+// recur in another list, never inside one; the limits are totals over all lists.  One list lays out the words seqbias_layout does.
+SeqBiasTable seqbias_layout_lists(const char* what, const int32_t* ids, const int32_t* lens, const float* bias, const int32_t* list_lens, int n_lists, int V);
+
+// A row table of q3a_set_row_options (q3asr.h "row options").  row_options_check throws, `what` and the row's index in front, on every
+// value a uniform setter refuses and on a sequence_list outside [-1, n_lists); row_options_words
+// lays the records out as the kernels read them: regions sampling | filter | repetition | list, [n_rows][4] words each.  engine.cpp
+void row_options_check(const char* what, const q3a_row_options* rows, int n_rows, int n_lists, int V);
+std::vector<uint32_t> row_options_words(const q3a_row_options* rows, int n_rows);
 
 // e->err (e null: an entry point without an engine) and the calling thread's q3a_last_error(NULL); engine.cpp
 void set_error(q3a_engine* e, const char* msg);

@@ -10,8 +10,9 @@
 //   history_apply_kernel   one workgroup of 256 threads per sequence.
 //     sequence bias (launch_seqbias_apply):
 //                          0a. the last min(t, 31) ids of the history go to LDS (an entry has at most 32 ids, so 31 lead its target);
-//                          0b. thread g, stride 256 over the G target groups (G from device memory: another list replays the same
-//                             graph), walks its group's entries in the setter's order -- the one-token entry first, then the longer
+//                          0b. thread g, stride 256 over the target groups of the ROW'S list (the list index per row and the directory
+//                             list_begin from device memory, as G is: another list or row table replays the same graph), walks
+//                             its group's entries in the setter's order -- the one-token entry first, then the longer
 //                             ones as the caller gave them --, compares each entry's leading ids with the LDS tail and adds the bias
 //                             of every entry that fires to acc (0.0f at the start, one fp32 add each); if one fired, the ONE
 //                             read-modify-write row[target] += acc.  A target belongs to exactly one group and a group to exactly
@@ -49,7 +50,11 @@ __global__ __launch_bounds__(256) void history_apply_kernel(SeqBiasArgs sb, Repe
     if (tid < m) tail[tid] = h[t - m + tid];
     __syncthreads();
     const int G = min(sb.params[0], SEQBIAS_MAX_ENTRIES), E = min(sb.params[1], SEQBIAS_MAX_ENTRIES);
-    for (int g = tid; g < G; g += 256) {
+    // the row's own list k (workgroup-uniform): its groups are list_begin[k] .. list_begin[k + 1); no list (-1): nothing to walk
+    const int k = sb.row_list[(size_t)s * sb.row_stride];
+    const bool listed = (unsigned)k < (unsigned)SEQBIAS_MAX_LISTS;
+    const int g0 = listed ? max(sb.list_begin[k], 0) : 0, g1 = listed ? min(sb.list_begin[k + 1], G) : 0;
+    for (int g = g0 + tid; g < g1; g += 256) {
       const int target = sb.grp_target[g];
       const int e0 = max(sb.grp_begin[g], 0), e1 = min(sb.grp_begin[g + 1], E);
       float acc = 0.f;
@@ -71,8 +76,8 @@ __global__ __launch_bounds__(256) void history_apply_kernel(SeqBiasArgs sb, Repe
   uint32_t* const bits = repeat_lds;                                         // [words]
   int* const hist = reinterpret_cast<int*>(repeat_lds + ((words + 3) & ~3));  // [hist_cap] the first hist_cap ids of the history
   const int V = a.V;
-  const float p = __uint_as_float(a.params[0]);
-  const int n = (int)a.params[1];
+  const float p = __uint_as_float(a.params[(size_t)s * a.row_stride]);  // the row's own record (stride 0: the one record of all rows)
+  const int n = (int)a.params[(size_t)s * a.row_stride + 1];
   const int t = min(a.step_count[s], a.out_stride);
   if (t <= 0) return;  // (the whole workgroup: nothing generated yet, both repetition processors are the identity)
   const int* const h = a.out_ids + (size_t)s * a.out_stride;
@@ -129,7 +134,7 @@ const char* launch_repeat_apply(const RepeatArgs& a, hipStream_t s) {
 const char* launch_seqbias_apply(const SeqBiasArgs& a, hipStream_t s) {
   if (a.S <= 0) return nullptr;
   if (a.V < 1) return "sequence bias: empty vocabulary";
-  if (!a.logits || !a.params || !a.grp_target || !a.grp_begin || !a.ent_bias || !a.ent_pre_off || !a.pre_ids || !a.out_ids || !a.step_count || a.out_stride < 1)
+  if (!a.logits || !a.params || !a.grp_target || !a.grp_begin || !a.ent_bias || !a.ent_pre_off || !a.pre_ids || !a.list_begin || !a.row_list || !a.out_ids || !a.step_count || a.out_stride < 1)
     return "sequence bias: null argument";
   hipLaunchKernelGGL(history_apply_kernel, dim3(a.S), dim3(256), 0, s, a, RepeatArgs{}, 0, 0, SampleStageArgs{});
   return nullptr;

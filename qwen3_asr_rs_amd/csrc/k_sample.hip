@@ -91,18 +91,21 @@ __global__ __launch_bounds__(256) void sample_chunk_kernel(SampleArgs a, int n_c
       fs[q] = e < V ? row[e] : 0.f;
     }
   }
-  const float T = __uint_as_float(a.params[0]), min_p = __uint_as_float(a.params[1]);
-  const uint32_t seed_lo = a.params[2], seed_hi = a.params[3];
+  const uint32_t* const par = a.params + (size_t)s * a.row_stride;  // the row's own record (stride 0: the one record of all rows)
+  const float T = __uint_as_float(par[0]), min_p = __uint_as_float(par[1]);
+  const uint32_t seed_lo = par[2], seed_hi = par[3];
   const uint32_t t = (uint32_t)a.step_count[s];
   float m = -INFINITY;
   for (int x = lane; x < n_chunk; x += 64) m = fmaxf(m, a.chunk_max[(size_t)s * n_chunk + x]);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-  const float thr = m + T * logf(min_p);  // (min_p = 0: -inf, every finite logit is kept; min_p = 1: m itself)
+  // a greedy row of a row table (T = 0; workgroup-uniform): every finite entry, z = l itself -- 0 * ln(0) below would be NaN
+  const bool greedy = !(T > 0.f);
+  const float thr = greedy ? -INFINITY : m + T * logf(min_p);  // (min_p = 0: -inf, every finite logit is kept; min_p = 1: m itself)
   ArgmaxAcc<false> acc;
   auto visit = [&](float l, int e) {
     if (l >= thr && l != -INFINITY) {
-      const float z = fmaf(T, gumbel_of(sample_word(seed_lo, seed_hi, (uint32_t)s, t, (uint32_t)e)), l);
+      const float z = greedy ? l : fmaf(T, gumbel_of(sample_word(seed_lo, seed_hi, (uint32_t)s, t, (uint32_t)e)), l);
       acc.merge(z, e, 0.f);
     }
   };

@@ -515,6 +515,8 @@ inline int sample_chunks(int V) { return (V + SAMPLE_CHUNK - 1) / SAMPLE_CHUNK; 
 struct SampleArgs {
   const float* logits; int S; int V;
   const uint32_t* params;              // device [4]: temperature and min_p (fp32 bits), seed low and high word
+  int row_stride;                      // words between the records of two rows: 0 one record for all rows, 4 a record per row
+                                       // (q3asr.h "row options"); a row with temperature 0 takes the argmax of its finite entries
   const int* step_count;               // [S] the step t of each sequence (tokens it has generated so far)
   float* chunk_max; float* chunk_sum;  // [S][sample_chunks(V)] (written)
   ArgmaxPartials part;                 // (written) [S] rows x sample_chunks(V) partials, no log-sum channel
@@ -527,6 +529,7 @@ const char* launch_sample(const SampleArgs& a, hipStream_t s);
 constexpr int SAMPLE_BUCKETS = 2048;  // the select's first digit: the top 11 bits of the key
 struct SampleFilterArgs {
   const uint32_t* filter;              // device [4]: top_k, top_p (fp32 bits), 0, 0 -- as validated by the setter
+  int row_stride;                      // as SampleArgs::row_stride (the two agree); a row with (0, 1.0f) gets tau_sel = -inf
   uint32_t* hist_cnt;                  // [S][SAMPLE_BUCKETS] entries per first digit: ZERO on entry, zero again when the stage returns
   unsigned long long* hist_mass;       // [S][SAMPLE_BUCKETS] their summed weights; likewise
   float* tau_sel; int* kept;           // [S] (written)
@@ -556,19 +559,23 @@ constexpr int REPEAT_HIST_LDS = 4096;      // ids of a history kept in LDS (16 K
 struct RepeatArgs {
   float* logits; int S; int V;
   const uint32_t* params;              // device [4]: p (fp32 bits), n, 0, 0 -- as validated by the setter: p finite and > 0, 0 <= n <= 32
+  int row_stride;                      // words between the records of two rows: 0 one record for all rows, 4 a record per row
   const int* out_ids; int out_stride;  // [S][out_stride] the ids generated so far
   const int* step_count;               // [S]
 };
 const char* launch_repeat_apply(const RepeatArgs& a, hipStream_t s);
 
 // ---- sequence bias (k_repeat.hip: a mode of the same kernel) -----------------------------------------------------------------------------
-constexpr int SEQBIAS_MAX_ENTRIES = 4096;  // entries of a list (and so target groups)
+constexpr int SEQBIAS_MAX_ENTRIES = 4096;  // entries over all lists (and so target groups)
+constexpr int SEQBIAS_MAX_LISTS = 256;     // lists of q3a_set_sequence_bias_lists
 constexpr int SEQBIAS_MAX_LEN = 32;        // ids of one entry
 constexpr int SEQBIAS_MAX_IDS = 65536;     // ids over all entries
 // Per row s of logits [S][V] (fp32, row stride V), rewritten IN PLACE: with h = out_ids[s][0 .. t), t = min(step_count[s], out_stride),
 // an entry q_0 .. q_{L-1} fires iff t >= L - 1 and h[t - L + 1 .. t) == q_0 .. q_{L-2}; for every target id with a firing entry,
 // l_target += acc, acc = 0.0f + the biases of its firing entries in table order (one fp32 add each).  Entries are grouped by target:
 // group g owns entries grp_begin[g] .. grp_begin[g + 1), entry e the leading ids pre_ids[ent_pre_off[e] .. ent_pre_off[e + 1]).
+// Row s uses the groups of ITS list k = row_list[s * row_stride], list_begin[k] .. list_begin[k + 1) (k outside [0, SEQBIAS_MAX_LISTS):
+// none, the row is left as it is); q3a_set_sequence_bias is the case of one list, and without a row table every row reads list 0.
 // One launch, one workgroup per row; it runs before launch_repeat_apply / launch_argmax_partials / launch_sample.
 struct SeqBiasArgs {
   float* logits; int S; int V;
@@ -576,6 +583,8 @@ struct SeqBiasArgs {
   const int* grp_target; const int* grp_begin;   // [SEQBIAS_MAX_ENTRIES], [SEQBIAS_MAX_ENTRIES + 1]
   const float* ent_bias; const int* ent_pre_off; // [SEQBIAS_MAX_ENTRIES], [SEQBIAS_MAX_ENTRIES + 1]
   const int* pre_ids;                      // [SEQBIAS_MAX_IDS]
+  const int* list_begin;                   // [SEQBIAS_MAX_LISTS + 1] first group of every list (groups of one list are contiguous)
+  const int* row_list; int row_stride;     // the list of row s at row_list[s * row_stride]; stride 0: one word for all rows
   const int* out_ids; int out_stride;      // [S][out_stride] the ids generated so far
   const int* step_count;                   // [S]
 };
@@ -584,12 +593,15 @@ const char* launch_seqbias_apply(const SeqBiasArgs& a, hipStream_t s);
 // entries sorted stably by target id, the one-token entry of a target first.
 constexpr size_t SEQBIAS_OFF_TARGET = 4, SEQBIAS_OFF_BEGIN = SEQBIAS_OFF_TARGET + SEQBIAS_MAX_ENTRIES,
                  SEQBIAS_OFF_BIAS = SEQBIAS_OFF_BEGIN + SEQBIAS_MAX_ENTRIES + 1, SEQBIAS_OFF_PRE_OFF = SEQBIAS_OFF_BIAS + SEQBIAS_MAX_ENTRIES,
-                 SEQBIAS_OFF_PRE_IDS = SEQBIAS_OFF_PRE_OFF + SEQBIAS_MAX_ENTRIES + 1, SEQBIAS_TABLE_WORDS = SEQBIAS_OFF_PRE_IDS + SEQBIAS_MAX_IDS;
-// the kernel's table pointers into a device copy of that block (engine_internal.h seqbias_layout writes it)
+                 SEQBIAS_OFF_PRE_IDS = SEQBIAS_OFF_PRE_OFF + SEQBIAS_MAX_ENTRIES + 1, SEQBIAS_OFF_LISTS = SEQBIAS_OFF_PRE_IDS + SEQBIAS_MAX_IDS,
+                 SEQBIAS_TABLE_WORDS = SEQBIAS_OFF_LISTS + SEQBIAS_MAX_LISTS + 1;  // (the list directory behind pre_ids: no older offset moves)
+// the kernel's table pointers into a device copy of that block (engine_internal.h seqbias_layout writes it).  Every row reads list 0
+// (word 2 of the block's head is always 0) until the caller points row_list at a row table.
 inline void seqbias_point(SeqBiasArgs& a, const void* table_dev) {
   const int* const w = static_cast<const int*>(table_dev);
   a.params = w; a.grp_target = w + SEQBIAS_OFF_TARGET; a.grp_begin = w + SEQBIAS_OFF_BEGIN;
   a.ent_bias = reinterpret_cast<const float*>(w + SEQBIAS_OFF_BIAS); a.ent_pre_off = w + SEQBIAS_OFF_PRE_OFF; a.pre_ids = w + SEQBIAS_OFF_PRE_IDS;
+  a.list_begin = w + SEQBIAS_OFF_LISTS; a.row_list = w + 2; a.row_stride = 0;
 }
 
 }  // namespace q3a

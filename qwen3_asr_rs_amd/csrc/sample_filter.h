@@ -39,7 +39,7 @@ __device__ __forceinline__ float sel_row_max(const float* __restrict__ chunk_max
 
 template <bool VEC>
 __device__ __forceinline__ void sample_hist_phase(uint32_t* cnt, u64* mass, const float* __restrict__ logits, int V, int n_chunk, const uint32_t* __restrict__ params,
-                                                          const uint32_t* __restrict__ filter, const float* __restrict__ chunk_max,
+                                                          const uint32_t* __restrict__ filter, int row_stride, const float* __restrict__ chunk_max,
                                                           uint32_t* __restrict__ hist_cnt, u64* __restrict__ hist_mass) {
   const int s = blockIdx.y, c = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   const float* row = logits + (size_t)s * V;
@@ -60,8 +60,9 @@ __device__ __forceinline__ void sample_hist_phase(uint32_t* cnt, u64* mass, cons
     }
   }
   for (int b = tid; b < SAMPLE_BUCKETS; b += 256) { cnt[b] = 0u; mass[b] = 0ull; }
-  const float T = __uint_as_float(params[0]);
-  const bool weigh = __uint_as_float(filter[1]) < 1.f;  // top-p off: nobody reads the weights
+  const float T = __uint_as_float(params[(size_t)s * row_stride]);  // the row's own records (stride 0: the one record of all rows)
+  // top-p off: nobody reads the weights; a greedy row of a row table (T = 0) has no filter, and sel_weight divides by T
+  const bool weigh = __uint_as_float(filter[(size_t)s * row_stride + 1]) < 1.f && T > 0.f;
   const float m = sel_row_max(chunk_max, s, n_chunk, lane);
   __syncthreads();
 #pragma unroll
@@ -131,16 +132,17 @@ __device__ __forceinline__ SelWalk sel_walk(const uint32_t* cnt, const u64* mass
 }
 
 __device__ __forceinline__ void sample_select_phase(uint32_t* cnt0, u64* mass0, uint32_t* cnt1, u64* mass1, const float* __restrict__ logits, int V, int n_chunk, int vec, const uint32_t* __restrict__ params,
-                                                             const uint32_t* __restrict__ filter, const float* __restrict__ chunk_max,
+                                                             const uint32_t* __restrict__ filter, int row_stride, const float* __restrict__ chunk_max,
                                                              uint32_t* __restrict__ hist_cnt, u64* __restrict__ hist_mass,
                                                              float* __restrict__ tau_sel, int* __restrict__ kept) {
   __shared__ SelWalk walk;
   const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* row = logits + (size_t)s * V;
-  const float T = __uint_as_float(params[0]);
-  const uint32_t top_k = filter[0];
-  const float top_p = __uint_as_float(filter[1]);
-  const bool k_on = top_k >= 1u && top_k < (uint32_t)V, p_on = top_p < 1.f;
+  const float T = __uint_as_float(params[(size_t)s * row_stride]);  // the row's own records (stride 0: the one record of all rows)
+  const uint32_t top_k = filter[(size_t)s * row_stride];
+  const float top_p = __uint_as_float(filter[(size_t)s * row_stride + 1]);
+  // a greedy row of a row table (T = 0) is not filtered: its table is still read and zeroed, tau = -inf, kept = the finite count
+  const bool sampled = T > 0.f, k_on = sampled && top_k >= 1u && top_k < (uint32_t)V, p_on = sampled && top_p < 1.f;
   const float m = sel_row_max(chunk_max, s, n_chunk, lane);
   for (int b = tid; b < SEL_TABLE; b += 256) { cnt0[b] = 0u; mass0[b] = 0ull; }  // (the padding words too: nothing here is left unset)
   __syncthreads();
@@ -267,18 +269,21 @@ __device__ __forceinline__ void sample_chunk_filter_phase(const SampleArgs& a, i
       fs[q] = e < V ? row[e] : 0.f;
     }
   }
-  const float T = __uint_as_float(a.params[0]), min_p = __uint_as_float(a.params[1]);
-  const uint32_t seed_lo = a.params[2], seed_hi = a.params[3];
+  const uint32_t* const par = a.params + (size_t)s * a.row_stride;  // the row's own record (stride 0: the one record of all rows)
+  const float T = __uint_as_float(par[0]), min_p = __uint_as_float(par[1]);
+  const uint32_t seed_lo = par[2], seed_hi = par[3];
   const uint32_t t = (uint32_t)a.step_count[s];
   float m = -INFINITY;
   for (int x = lane; x < n_chunk; x += 64) m = fmaxf(m, a.chunk_max[(size_t)s * n_chunk + x]);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-  const float thr = fmaxf(m + T * logf(min_p), tau_sel[s]);  // tau = max(tau_minp, tau_k, tau_p): a value, never a rank
+  // a greedy row of a row table (T = 0; workgroup-uniform): every finite entry, z = l itself -- 0 * ln(0) below would be NaN
+  const bool greedy = !(T > 0.f);
+  const float thr = greedy ? -INFINITY : fmaxf(m + T * logf(min_p), tau_sel[s]);  // tau = max(tau_minp, tau_k, tau_p): a value, never a rank
   ArgmaxAcc<false> acc;
   auto visit = [&](float l, int e) {
     if (l >= thr && l != -INFINITY) {
-      const float z = fmaf(T, gumbel_of(sample_word(seed_lo, seed_hi, (uint32_t)s, t, (uint32_t)e)), l);
+      const float z = greedy ? l : fmaf(T, gumbel_of(sample_word(seed_lo, seed_hi, (uint32_t)s, t, (uint32_t)e)), l);
       acc.merge(z, e, 0.f);
     }
   };
@@ -313,13 +318,13 @@ __device__ __forceinline__ void sample_stage_phase(const SampleStageArgs& g, voi
   if (g.phase == 1) {
     u64* mass = reinterpret_cast<u64*>(lds);
     uint32_t* cnt = reinterpret_cast<uint32_t*>(mass + SAMPLE_BUCKETS);
-    if (g.vec) sample_hist_phase<true>(cnt, mass, a.logits, a.V, g.n_chunk, a.params, f.filter, a.chunk_max, f.hist_cnt, f.hist_mass);
-    else sample_hist_phase<false>(cnt, mass, a.logits, a.V, g.n_chunk, a.params, f.filter, a.chunk_max, f.hist_cnt, f.hist_mass);
+    if (g.vec) sample_hist_phase<true>(cnt, mass, a.logits, a.V, g.n_chunk, a.params, f.filter, a.row_stride, a.chunk_max, f.hist_cnt, f.hist_mass);
+    else sample_hist_phase<false>(cnt, mass, a.logits, a.V, g.n_chunk, a.params, f.filter, a.row_stride, a.chunk_max, f.hist_cnt, f.hist_mass);
   } else if (g.phase == 2) {
     u64* mass0 = reinterpret_cast<u64*>(lds);
     u64* mass1 = mass0 + SEL_TABLE;
     uint32_t* cnt0 = reinterpret_cast<uint32_t*>(mass1 + SEL_TABLE);
-    sample_select_phase(cnt0, mass0, cnt0 + SEL_TABLE, mass1, a.logits, a.V, g.n_chunk, g.vec, a.params, f.filter, a.chunk_max, f.hist_cnt, f.hist_mass,
+    sample_select_phase(cnt0, mass0, cnt0 + SEL_TABLE, mass1, a.logits, a.V, g.n_chunk, g.vec, a.params, f.filter, a.row_stride, a.chunk_max, f.hist_cnt, f.hist_mass,
                         f.tau_sel, f.kept);
   } else {
     if (g.vec) sample_chunk_filter_phase<true>(a, g.n_chunk, f.tau_sel);

@@ -443,6 +443,112 @@ int32_t q3a_selftest_seqbias(int32_t device, const float* logits, int32_t S, int
   Q3A_CATCH(nullptr)
 }
 
+// a step's tail under a row table (q3asr.h "row options"), in the order the engine enqueues it: the lists laid out by the setter's own
+// function and the records by row_options_words, launch_seqbias_apply and launch_repeat_apply with a row stride of 4 where a row has
+// them on, then the sampler (with the threshold stage if a row filters) or fresh argmax partials, argmax_finalize, the log-probability.
+// With a filter the sampler's part runs TWICE on one table, as two steps of a decode do: the stage must leave its table as it found it.
+int32_t q3a_selftest_row_options(int32_t device, const float* logits, int32_t S, int32_t V, const int32_t* hist, int32_t stride, const int32_t* lens,
+                                 const q3a_row_options* rows, const int32_t* seq_ids, const int32_t* seq_lens, const float* seq_bias,
+                                 const int32_t* list_lens, int32_t n_lists, float* out_logits, int32_t* out_ids, float* out_lp, float* out_z,
+                                 float* out_thr, int32_t* out_kept) {
+  Q3A_TRY(nullptr)
+  const char* what = "q3a_selftest_row_options";
+  if (!logits || !lens || !rows || S < 1 || V < 1 || stride < 0 || stride > (1 << 20) || (stride > 0 && !hist)) fail(std::string(what) + ": bad argument");
+  const SeqBiasTable tb = seqbias_layout_lists(what, seq_ids, seq_lens, seq_bias, list_lens, n_lists, V);
+  row_options_check(what, rows, S, n_lists, V);
+  const size_t Sz = S, pitch = (size_t)stride + 1;  // (one more column than any history: finalize writes the chosen id behind it)
+  std::vector<int> ids(Sz * pitch, -1);
+  bool sample = false, filter = false, repeat = false, seqb = false;
+  for (size_t s = 0; s < Sz; ++s) {
+    if (lens[s] < 0 || lens[s] > stride) fail(std::string(what) + ": a history length outside [0, stride]");
+    for (int i = 0; i < lens[s]; ++i) {
+      const int id = hist[s * stride + i];
+      if (id < 0 || id >= V) fail(std::string(what) + ": a history id outside the vocabulary");
+      ids[s * pitch + i] = id;
+    }
+    const q3a_row_options& o = rows[s];
+    sample |= o.temperature > 0.f;
+    filter |= o.temperature > 0.f && (o.top_k != 0 || o.top_p != 1.f);
+    repeat |= !(o.repetition_penalty == 1.f && o.no_repeat_ngram_size == 0);
+    seqb |= o.sequence_list >= 0 && tb.list_entries[(size_t)o.sequence_list] > 0;
+  }
+  use_device(device);
+  constexpr int H = 4, NP = 128;  // finalize embeds the chosen id: a token table of zeros, four columns wide
+  const size_t nc = sample_chunks(V), np = sample ? nc : (size_t)NP;
+  const DevBuf dLg = to_device(logits, Sz * V), dTab = to_device(tb.words), dRow = to_device(row_options_words(rows, S));
+  const uint32_t* const rw = dRow.as<uint32_t>();  // regions sampling | filter | repetition | list, [S][4] words each
+  const DevBuf dCm = room(Sz * nc * 4), dCs = room(Sz * nc * 4), dPv = room(Sz * np * 4), dPi = room(Sz * np * 4), dPs = room(Sz * np * 4);
+  const DevBuf dHist = to_device(std::vector<uint32_t>(Sz * SAMPLE_BUCKETS * 3, 0u)), dSel = room(Sz * 8);
+  const DevBuf dEmb = to_device(std::vector<uint16_t>((size_t)V * H, 0)), dX = room(Sz * H * 4), dTok = room(Sz * 4), dZ = room(Sz * 4);
+  {  // the rewriting kernels run once: they work in place, and both read only the history in front of lens[s]
+    const DevBuf dSc = to_device(lens, Sz), dIds = to_device(ids);
+    if (seqb) {
+      SeqBiasArgs sa{};
+      sa.logits = dLg.as<float>(); sa.S = S; sa.V = V; seqbias_point(sa, dTab.p);
+      sa.row_list = reinterpret_cast<const int*>(rw + 3 * Sz * 4); sa.row_stride = 4;
+      sa.out_ids = dIds.as<int>(); sa.out_stride = (int)pitch; sa.step_count = dSc.as<int>();
+      KCHK(launch_seqbias_apply(sa, nullptr));
+    }
+    if (repeat) {
+      RepeatArgs ra{};
+      ra.logits = dLg.as<float>(); ra.S = S; ra.V = V; ra.params = rw + 2 * Sz * 4; ra.row_stride = 4;
+      ra.out_ids = dIds.as<int>(); ra.out_stride = (int)pitch; ra.step_count = dSc.as<int>();
+      KCHK(launch_repeat_apply(ra, nullptr));
+    }
+    finish();
+  }
+  std::vector<int> tok;
+  std::vector<float> lp;
+  for (int run = 0; run < (filter ? 2 : 1); ++run) {
+    const DevBuf dSc = to_device(lens, Sz), dIds = to_device(ids), dLp = to_device(std::vector<float>(Sz * pitch, 0.f));
+    const DevBuf dPos = to_device(std::vector<int>(Sz, 0)), dDone = to_device(std::vector<uint8_t>(Sz, 0));
+    FinalizeArgs f{};
+    f.V = V; f.advance = 1;
+    SampleArgs sa{};
+    if (sample) {
+      sa.logits = dLg.as<float>(); sa.S = S; sa.V = V; sa.params = rw; sa.row_stride = 4; sa.step_count = dSc.as<int>();
+      sa.chunk_max = dCm.as<float>(); sa.chunk_sum = dCs.as<float>();
+      sa.part = ArgmaxPartials{dPv.as<float>(), dPi.as<int>(), nullptr, (int)nc};
+      if (filter) {
+        SampleFilterArgs sf{};
+        sf.filter = rw + Sz * 4; sf.row_stride = 4; sf.hist_mass = dHist.as<unsigned long long>();
+        sf.hist_cnt = reinterpret_cast<uint32_t*>(sf.hist_mass + Sz * SAMPLE_BUCKETS);
+        sf.tau_sel = dSel.as<float>(); sf.kept = dSel.as<int>() + S;
+        KCHK(launch_sample_filtered(sa, sf, nullptr));
+      } else {
+        KCHK(launch_sample(sa, nullptr));
+      }
+      f.part = sa.part; f.n_part = (int)nc;
+    } else {
+      f.part = ArgmaxPartials{dPv.as<float>(), dPi.as<int>(), dPs.as<float>(), NP}; f.n_part = NP;
+      KCHK(launch_argmax_partials(dLg.as<float>(), V, S, f.part, NP, nullptr));
+    }
+    f.c = bare_commit(S, dTok, dIds.as<int>(), (int)pitch, sample ? nullptr : dLp.as<float>(), dSc, dPos, dDone, dEmb.as<uint16_t>(), H, dX.as<float>(), kEos0, kEos1);
+    KCHK(launch_argmax_finalize(f, S, nullptr));
+    if (sample) {
+      SampleLogprobArgs sl{};
+      sl.logits = sa.logits; sl.S = S; sl.V = V; sl.chunk_max = sa.chunk_max; sl.chunk_sum = sa.chunk_sum; sl.next_tok = f.c.next_tok;
+      sl.step_count = f.c.step_count; sl.out_lp = dLp.as<float>(); sl.out_stride = (int)pitch; sl.part = sa.part; sl.out_z = dZ.as<float>();
+      KCHK(launch_sample_logprob(sl, nullptr));
+    }
+    finish();
+    tok = to_host<int>(dTok, Sz);
+    lp = to_host<float>(dLp, Sz * pitch);
+  }
+  if (out_logits) to_host(out_logits, dLg, Sz * V);
+  for (size_t s = 0; s < Sz; ++s) {
+    if (out_ids) out_ids[s] = tok[s];
+    if (out_lp) out_lp[s] = lp[s * pitch + lens[s]];
+  }
+  if (out_z && sample) to_host(out_z, dZ, Sz);
+  if (filter) {
+    const std::vector<float> sel = to_host<float>(dSel, Sz * 2);
+    if (out_thr) memcpy(out_thr, sel.data(), Sz * 4);
+    if (out_kept) memcpy(out_kept, sel.data() + Sz, Sz * 4);
+  }
+  Q3A_CATCH(nullptr)
+}
+
 int32_t q3a_selftest_gemv_launch(int32_t device, int32_t pruned, const uint16_t* w, int32_t N, int32_t K, const float* x, const float* rms_w, float eps,
                                  const float* bias, int32_t mode, const float* resid, const float* attn_pm, const float* attn_pl, const float* attn_po,
                                  int32_t attn_nsplit, int32_t attn_heads, float* out, int32_t* out_state) {

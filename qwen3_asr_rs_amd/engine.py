@@ -12,11 +12,12 @@ This module holds no arithmetic: every number is produced by the HIP kernels beh
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import math
 import os
 import zlib
 from dataclasses import dataclass
-from typing import Iterable, List, Mapping, Optional, Sequence, Tuple
+from typing import Any, Iterable, List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -182,6 +183,65 @@ def check_sequence_bias(entries, vocab: int):
     if len(ids) > SEQUENCE_BIAS_MAX_IDS:
         raise Q3aError(f"sequence_bias: {len(ids)} ids over all entries, more than {SEQUENCE_BIAS_MAX_IDS}")
     return np.asarray(ids, dtype=np.int32), np.asarray(lens, dtype=np.int32), np.asarray(bias, dtype=np.float32)
+
+
+SEQUENCE_BIAS_MAX_LISTS = 256
+
+
+@dataclasses.dataclass
+class RowOptions:
+    """The decoding options of ONE sequence of a batch (q3a_row_options; include/q3asr.h "row options"): what set_sampling,
+    set_sampling_filter, set_repetition and set_sequence_bias hold once per engine.  The defaults are a plain greedy row."""
+    temperature: float = 0.0
+    min_p: float = 0.0
+    seed: int = 0
+    top_k: int = 0
+    top_p: float = 1.0
+    repetition_penalty: float = 1.0
+    no_repeat_ngram_size: int = 0
+    sequence_bias: Any = None  # entries as set_sequence_bias takes them, or None
+
+
+def check_row_options(rows, vocab: int):
+    """The refusals of HipEngine.set_row_options that need no engine, each with the row's index, and the rows' lists collected:
+    returns (records, lists) -- records[s] = (temperature, min_p, seed, top_k, top_p, repetition_penalty, no_repeat_ngram_size,
+    list index or -1), lists = the distinct non-empty entry lists in the order rows first name them (equal lists share an index)."""
+    records, lists, index = [], [], {}
+    for s, r in enumerate(rows):
+        if not isinstance(r, RowOptions):
+            raise Q3aError(f"set_row_options: row {s} is not a RowOptions")
+        try:
+            t, mp, sd = check_sampling_args(r.temperature, r.min_p, r.seed)
+            k, tp = check_sampling_filter_args(r.top_k, r.top_p)
+            p, n = check_repetition_args(r.repetition_penalty, r.no_repeat_ngram_size)
+            pairs = _sequence_bias_pairs(r.sequence_bias)
+            check_sequence_bias(pairs, vocab)
+        except Q3aError as e:
+            raise Q3aError(f"set_row_options: row {s}: {e}") from None
+        li = -1
+        if pairs:
+            key = tuple(pairs)
+            if key not in index:
+                index[key] = len(lists)
+                lists.append(pairs)
+            li = index[key]
+        records.append((t, mp, sd, k, tp, p, n, li))
+    if len(lists) > SEQUENCE_BIAS_MAX_LISTS:
+        raise Q3aError(f"set_row_options: {len(lists)} distinct sequence-bias lists, more than {SEQUENCE_BIAS_MAX_LISTS}")
+    if sum(len(l) for l in lists) > SEQUENCE_BIAS_MAX_ENTRIES:
+        raise Q3aError(f"set_row_options: {sum(len(l) for l in lists)} entries over all lists, more than {SEQUENCE_BIAS_MAX_ENTRIES}")
+    if sum(len(q) for l in lists for q, _ in l) > SEQUENCE_BIAS_MAX_IDS:
+        raise Q3aError(f"set_row_options: more than {SEQUENCE_BIAS_MAX_IDS} ids over all lists")
+    return records, lists
+
+
+def check_sequence_bias_lists(lists, vocab: int):
+    """Several lists, one after the other, as q3a_set_sequence_bias_lists takes them: each checked as check_sequence_bias checks one
+    (a sequence may recur in another list), the limits over all of them."""
+    parts = [check_sequence_bias(l, vocab) for l in lists]
+    if not parts:
+        return np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.float32)
+    return tuple(np.concatenate([p[i] for p in parts]) for i in range(3))
 
 
 def _sequence_list_call(fn, *front) -> List[Tuple[tuple, float]]:
@@ -392,6 +452,7 @@ class HipEngine:
         self.sampling_filter_state: Tuple[int, float] = (0, 1.0)  # what set_sampling_filter was last given
         self.repetition_state: Tuple[float, int] = (1.0, 0)  # what set_repetition was last given
         self.sequence_bias_state: List[Tuple[tuple, float]] = []  # what set_sequence_bias was last given, as (ids, bias) pairs
+        self.row_options_state: Optional[List[RowOptions]] = None  # what set_row_options was last given (None: no row table)
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -782,6 +843,61 @@ class HipEngine:
         self._chk(self._lib.q3a_set_sequence_bias(self._h, _i32p(ids) if n else None, _i32p(lens) if n else None, _f32p(bias) if n else None, n))
         self.sequence_bias_state = _sequence_bias_pairs(entries)
 
+    # ---- row options: per-request settings inside one batch ------------------------------------------------------
+    def _set_sequence_bias_lists(self, lists):
+        flat = [e for l in lists for e in l]
+        ids, lens, bias = check_sequence_bias_lists(lists, self.dims.vocab_size)
+        ll = np.asarray([len(l) for l in lists], dtype=np.int32)
+        n = len(flat)
+        self._chk(self._lib.q3a_set_sequence_bias_lists(self._h, _i32p(ids) if n else None, _i32p(lens) if n else None, _f32p(bias) if n else None,
+                                                        _i32p(ll) if len(lists) else None, len(lists)))
+
+    def set_row_options(self, rows=None):
+        """q3a_set_row_options: `rows` holds one RowOptions per sequence of the next batches -- sequence s samples, filters, penalises
+        and biases by ITS record (a row with the defaults is a plain greedy row), on the device, in the same launches.  The rows'
+        distinct sequence_bias lists go to the engine as its lists (q3a_set_sequence_bias_lists; equal lists share an index).  None
+        or an empty list clears the table and puts back the list set_sequence_bias last gave: the uniform settings, remembered all
+        along, are in force again.  The next prefill must have len(rows) sequences.  Drops the decode state.  A refused table
+        leaves the engine without one."""
+        rows = list(rows) if rows is not None else []
+        if not rows:
+            self._clear_row_options()
+            return
+        records, lists = check_row_options(rows, self.dims.vocab_size)
+
+        def table(with_lists):
+            t = (_lib.RowOptionsC * len(records))()
+            for c, (tm, mp, sd, k, tp, p, n, li) in zip(t, records):
+                (c.temperature, c.min_p, c.seed, c.top_k, c.top_p, c.repetition_penalty, c.no_repeat_ngram_size,
+                 c.sequence_list) = (tm, mp, sd, k, tp, p, n, li if with_lists else -1)
+            return t
+        # neither setter may meet an index the other has not seen: the records without their lists, the lists, then the records
+        try:
+            self._chk(self._lib.q3a_set_row_options(self._h, table(False), len(records)))
+            self.row_options_state = [dataclasses.replace(r, sequence_bias=None) for r in rows]
+            self._set_sequence_bias_lists(lists)
+            self._chk(self._lib.q3a_set_row_options(self._h, table(True), len(records)))
+        except Q3aError:
+            self._clear_row_options()
+            raise
+        self.row_options_state = [dataclasses.replace(r) for r in rows]
+
+    def _clear_row_options(self):
+        if self.row_options_state is not None:
+            # the lists are the table's: rows that name none (so that no row names a list that goes), the engine's own list, no table
+            n = len(self.row_options_state)
+            off = (_lib.RowOptionsC * n)(*[_lib.RowOptionsC(0.0, 0.0, 0, 0, 1.0, 1.0, 0, -1)] * n)
+            self._chk(self._lib.q3a_set_row_options(self._h, off, n))
+            self.set_sequence_bias(self.sequence_bias_state)
+        self._chk(self._lib.q3a_set_row_options(self._h, None, 0))
+        self.row_options_state = None
+
+    def row_options_stats(self) -> dict:
+        raw = self.debug_read_raw("row_options")
+        n = raw.size // C.sizeof(_lib.RowOptionsC)
+        table = (_lib.RowOptionsC * n).from_buffer_copy(raw.tobytes()) if n else []
+        return {"active": n > 0, "rows": [{f: getattr(c, f) for f, _ in _lib.RowOptionsC._fields_} for c in table]}
+
     def sequence_bias_stats(self) -> dict:
         st = self.debug_read_raw("sequence_bias").view(np.int32)
         return {"active": bool(st[0]), "entries": int(st[1]), "ids": int(st[2]), "targets": int(st[3])}
@@ -1146,6 +1262,69 @@ class AsrInference:
             return run()
         finally:
             self.engine.set_logit_bias(*before)
+
+    _ROW_OPTION_KEYS = ("temperature", "min_p", "seed", "top_k", "top_p", "repetition_penalty", "no_repeat_ngram_size", "hotwords", "hotword_boost",
+                        "hotword_start_boost", "banned_phrases", "sequence_bias")
+
+    def transcribe_batch(self, audios, language: Optional[str] = None, max_new_tokens: int = 4096, options=None) -> List[TranscribeResult]:
+        """transcribe() for several audios in ONE batch, each with its own decoding options (HipEngine.set_row_options): `options` holds
+        one dict or None per audio, with transcribe's keys temperature (a number), min_p, seed, top_k, top_p, repetition_penalty,
+        no_repeat_ngram_size, hotwords, hotword_boost, hotword_start_boost, banned_phrases and sequence_bias.  None is a plain greedy
+        request.  The noise of a sampled row depends on its index in the batch.  `language` is one per call.  The engine's row table
+        and sequence-bias lists are restored afterwards.  Raises Q3aError for a tuple of temperatures (fallback decides per attempt,
+        not per row), beam_size, draft, the logit-bias arguments (one vector per engine) and top_k / top_p without a temperature > 0."""
+        audios = list(audios)
+        options = [None] * len(audios) if options is None else list(options)
+        if len(options) != len(audios):
+            raise Q3aError(f"transcribe_batch: {len(options)} option dict(s) for {len(audios)} audio(s)")
+        rows = []
+        for i, o in enumerate(options):
+            o = dict(o) if o is not None else {}
+            for key in ("beam_size", "draft"):
+                if key in o:
+                    raise Q3aError(f"transcribe_batch: options[{i}] has {key}: beam search and drafts do not run under per-row options")
+            for key in ("suppress_tokens", "logit_bias", "allowed_tokens"):
+                if key in o:
+                    raise Q3aError(f"transcribe_batch: options[{i}] has {key}: the logit bias is one vector per engine, not per row")
+            unknown = sorted(set(o) - set(self._ROW_OPTION_KEYS))
+            if unknown:
+                raise Q3aError(f"transcribe_batch: options[{i}] has unknown key(s) {unknown}")
+            t = o.get("temperature", 0.0)
+            if isinstance(t, (tuple, list)):
+                raise Q3aError(f"transcribe_batch: options[{i}] has a tuple of temperatures: the fallback is transcribe()'s, one audio at a time")
+            filt = check_sampling_filter_args(o.get("top_k", 0), o.get("top_p", 1.0))
+            t = check_sampling_args(t, o.get("min_p", 0.0), o.get("seed", 0))[0]
+            if filt != (0, 1.0) and not t > 0.0:
+                raise Q3aError(f"transcribe_batch: options[{i}]: top_k / top_p filter a sampled step: give a temperature > 0 with them")
+            entries = self._sequence_bias_entries(o.get("hotwords"), o.get("hotword_boost"), o.get("hotword_start_boost", 0.0),
+                                                  o.get("banned_phrases"), o.get("sequence_bias"))
+            rows.append(RowOptions(t, o.get("min_p", 0.0), o.get("seed", 0), filt[0], filt[1], o.get("repetition_penalty", 1.0),
+                                   o.get("no_repeat_ngram_size", 0), entries))
+        samples = [load_audio(os.fspath(a), 16000) if isinstance(a, (str, os.PathLike)) else np.asarray(a, dtype=np.float32) for a in audios]
+        prefix = None
+        if language is not None:
+            if self.tokenizer is None:
+                raise Q3aError("forcing a language needs tokenizer.json (src/inference.rs:246-251)")
+            prefix = self.tokenizer.encode("language " + capitalize_first(language))
+        eng = self.engine
+        before = eng.row_options_state
+        try:
+            eng.set_row_options(rows)
+            all_ids = eng.transcribe_batch(samples, prefix, max_new_tokens)
+            lps = eng.fetch_logprobs() if eng.token_logprobs else None
+        finally:
+            eng.set_row_options(before)
+        results = []
+        for i, ids in enumerate(all_ids):
+            raw = self.tokenizer.decode(ids, True) if self.tokenizer is not None else ""
+            lang, text = parse_asr_output(raw, language is not None)
+            res = TranscribeResult(text, lang, raw, ids)
+            res.temperature = rows[i].temperature
+            if lps is not None:
+                res.token_logprobs = [float(v) for v in lps[i]]
+                res.avg_logprob = float(np.mean(lps[i], dtype=np.float64)) if len(lps[i]) else None
+            results.append(res)
+        return results
 
     def _sequence_bias_entries(self, hotwords, hotword_boost, hotword_start_boost, banned_phrases, sequence_bias):
         """The call's sequence-bias entries, checked; None when none of the arguments was given."""

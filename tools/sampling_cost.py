@@ -6,11 +6,13 @@ events).  Arms, their order rotated round by round:
     t1      temperature 1, min_p 0: every finite logit gets its Philox word and its two logs
     t1minp  temperature 1, min_p 0.05: only the kept set does
     t1k50 / t1p09 / t1k50p09  temperature 1 under q3a_set_sampling_filter: top_k 50, top_p 0.9, both (the threshold stage's two launches)
+    rows    a row table (q3a_set_row_options) whose rows all carry the t1 record: the same launches reading a record per row
 
     python tools/sampling_cost.py --preset 0.6b --batch 1 --rounds 7
     python tools/sampling_cost.py --preset 0.6b --batch 32 --rounds 7
     python tools/sampling_cost.py --batch 1 --arms off,t1,t1k50,t1p09,t1k50p09     # the filter's arms against the sampler's
     python tools/sampling_cost.py --rounds 1 --arms off        # no sampling call at all: the run a kernel trace compares launches on
+    python tools/sampling_cost.py --batch 32 --arms t1,rows    # per-row records against the one record (Q3A_LIB: another build's t1)
 
 Prints one line per round and a summary: median us per step of each arm, the difference to `off` in percent and in us, pruned
 passes per arm at one sequence, and that `off` generated the same ids before and after the sampled arms ran."""
@@ -37,11 +39,11 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--arms", default="off,t1,t1minp")
     args = ap.parse_args()
-    unknown = [a for a in args.arms.split(",") if a and a != "off" and a not in ARMS and a not in FILTERS]
+    unknown = [a for a in args.arms.split(",") if a and a not in ("off", "rows") and a not in ARMS and a not in FILTERS]
     if unknown:
-        ap.error(f"unknown arm(s) {unknown}: choose from off, {', '.join(list(ARMS) + list(FILTERS))}")
+        ap.error(f"unknown arm(s) {unknown}: choose from off, rows, {', '.join(list(ARMS) + list(FILTERS))}")
     from qwen3_asr_rs_amd import synthetic
-    from qwen3_asr_rs_amd.engine import HipEngine
+    from qwen3_asr_rs_amd.engine import HipEngine, RowOptions
     model_dir = f"/tmp/q3a_ckpt_{args.preset.replace('.', 'p')}"
     synthetic.write_checkpoint(model_dir, args.preset, seed=0, shards=2 if args.preset == "1.7b" else 1, embed_scale=synthetic.PEAKED_EMBED_SCALE)
     N = args.new_tokens
@@ -49,19 +51,27 @@ def main():
     eng = HipEngine(model_dir, 0, max_new_tokens=max(N, 16))
     eng.upload_pcm(clips)
     names = [a for a in args.arms.split(",") if a]
-    state = {"set": False, "filter": False}
+    state = {"set": False, "filter": False, "rows": False}
 
     def stats():
         return eng.debug_read_raw("lm_head_prune_stats").view(np.int32).astype(np.int64)
 
     def run(arm):
+        if arm == "rows":
+            eng.set_row_options([RowOptions(temperature=ARMS["t1"][0], min_p=ARMS["t1"][1], seed=17)] * args.batch)
+            state["rows"] = True
+        elif state["rows"]:  # (never called unless the rows arm ran: the other arms drive a library without the call)
+            eng.set_row_options(None)
+            state["rows"] = False
         if arm in FILTERS:
             eng.set_sampling_filter(*FILTERS[arm])
             state["filter"] = True
         elif state["filter"]:  # (never called unless a filter arm ran: the other arms drive a library without the call)
             eng.set_sampling_filter(0, 1.0)
             state["filter"] = False
-        if arm != "off":
+        if arm == "rows":
+            pass  # (the uniform setting stays what it was: remembered, not read)
+        elif arm != "off":
             eng.set_sampling(*(ARMS[arm] if arm in ARMS else (1.0, 0.0)), 17)  # (a filter arm: temperature 1, min_p 0)
             state["set"] = True
         elif state["set"]:  # (never called when only `off` runs: the same tool then drives a library without the call)
@@ -72,7 +82,7 @@ def main():
         t = eng.timings()
         return t["decode_ms"] / max(1, t["decode_steps"]), eng.fetch_ids(N), int((stats() - s0)[1])
 
-    _, ids0, _ = run("off")
+    _, ids0, _ = run("off")  # (`off` before any setter ran calls none of them)
     for arm in names:  # warm-up: graph capture, caches
         run(arm)
     per, passes, ids = {a: [] for a in names}, {a: [] for a in names}, {}
