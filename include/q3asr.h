@@ -775,6 +775,46 @@ int32_t q3a_selftest_row_options(int32_t device, const float* logits, int32_t S,
                                  const float* seq_bias, const int32_t* list_lens, int32_t n_lists, float* out_logits, int32_t* out_ids,
                                  float* out_lp, float* out_z, float* out_thr, int32_t* out_kept);
 
+/* ---- top log-probabilities: the n best alternatives of every generated token, selected on the device -------------------------------
+ * What the engine nearly wrote: OpenAI's top_logprobs, per-word alternatives.  While n > 0, every step of the GENERATION paths that
+ * commits a token -- the prefill's head, which produces the first one, included -- also records the n best entries of that step's
+ * final row l'': the row after the logit bias, the sequence bias and repetition control, exactly the row the argmax or the sampler
+ * reads.  0 <= n <= 20; 0 is off and the default.  Each entry is (id, lp).
+ *   Order.  Larger logit first, then smaller id.  -0.0 and +0.0 are one value.  -inf is a legal logit: it ranks last, ordered by id
+ *     among itself, and has lp = -inf.  NaN is outside the contract.  This is the argmax's tie rule, so in a greedy run entry 0 is the
+ *     id that was written.
+ *   lp.  lp = (l''[v] - m) - log sum exp(l'' - m), m the row maximum, in fp32 with a fixed summation order: the untempered, unfiltered
+ *     distribution q3a_fetch_logprobs reports.  Under sampling the drawn id need not be among the entries.  Results are bit-identical
+ *     from run to run and between graph replay and the eager step.
+ *   Slot.  The entries of the step that wrote out_ids[s][t] stand at [s][t][0 .. n).  A row that is already done, or whose slot is >=
+ *     the run's stride (max_new), writes nothing: a finished row's entries do not change afterwards.  With teacher forcing
+ *     (q3a_set_next_tokens) they are still each step's own row's best entries.
+ *   Fetch.  q3a_fetch_top_logprobs: out_ids / out_lp are host [B][stride][n_stride]; for row b the steps 0 .. min(out_lens[b], stride)
+ *     and of each the entries 0 .. min(n, n_stride) are written, everything else is untouched.  out_lens as q3a_fetch_ids gives them.
+ *     Works after q3a_run_resident, q3a_transcribe_batch[_ptrs] and the stage API (q3a_prefill / q3a_decode_step).  Refused on an
+ *     engine whose last run had n == 0, before anything was generated, and after a setter has dropped the decode state.
+ * Independent of opts.token_logprobs.  While it is on, every lm_head form stores its logits and the one-sequence pruned argmax is not
+ * taken, as under q3a_set_repetition.  With n == 0 the engine is on the launches, graphs, ids, log-probability bits and pruned-pass
+ * counts of one that never had the setting.
+ * State: the setting persists until changed; q3a_set_top_logprobs drops the decode state as the other setters do.  On / off is part of
+ * the captured step's signature; n lives in a device word and the history has a fixed inner stride of 20, so another n > 0 replays the
+ * same graph.  Memory: [B][max_new][20] x (int32 + fp32), allocated by the first prefill under n > 0 and freed with the engine;
+ * "device_bytes" is level across set / clear / transcribe cycles after the first.
+ * The setting is uniform for the batch; it composes with a row table because it only reads the final row.  Group runs: set it on each
+ * q3a_group_engine handle.  q3a_score* and q3a_align* never see it: bit-identical with it on and off.
+ * Refused (q3a_last_error; the setting and the engine stay as they were): n outside [0, 20]; n above the vocabulary; an aligner
+ * engine; q3a_beam_begin / q3a_beam_search_batch_ptrs, q3a_prefill_draft and q3a_transcribe_draft_batch_ptrs while n > 0 (beam search
+ * re-orders rows, and accepted draft tokens never pass the step's head).
+ * Readable: q3a_debug_read(e, "top_logprobs", ..) (int32 [1]: n as last set).
+ * Out of scope: a per-row n; alternatives inside beam search; more than 20 entries. */
+int32_t q3a_set_top_logprobs(q3a_engine* e, int32_t n);
+int32_t q3a_fetch_top_logprobs(q3a_engine* e, int32_t* out_ids, float* out_lp, int32_t stride, int32_t n_stride, int32_t* out_lens);
+/* The two launches on their own (no model), as the engine enqueues them, TWICE on the same scratch: logits [S][V] host fp32, row s at
+ * step step_count[s] with done[s] -> the whole history out_ids / out_lp [S][stride][20] of the second run (ids -1 and lp 0 wherever
+ * nothing was written).  1 <= n <= min(20, V).  Fails if the second run differs from the first in any bit. */
+int32_t q3a_selftest_top_logprobs(int32_t device, const float* logits, int32_t S, int32_t V, int32_t n, const int32_t* step_count,
+                                  const uint8_t* done, int32_t stride, int32_t* out_ids, float* out_lp);
+
 /* A/B knobs for kernel experiments (process-wide atomics, read from the environment once; not part of the reference
  * interface).  The knobs that shape the decode step are latched per batch at the next prefill and are part of the captured
  * graph's signature, so changing one on a live engine re-captures instead of replaying a stale graph.  Keys:

@@ -93,6 +93,11 @@ extern "C" {
     pub fn q3a_set_row_options(e: *mut q3a_engine, rows: *const RowOptions, n_rows: i32) -> i32;
     pub fn q3a_set_sequence_bias_lists(e: *mut q3a_engine, ids: *const i32, lens: *const i32, bias: *const f32, list_lens: *const i32,
                                        n_lists: i32) -> i32;
+    // top log-probabilities: the n best alternatives of every generated token (include/q3asr.h "top log-probabilities")
+    pub fn q3a_set_top_logprobs(e: *mut q3a_engine, n: i32) -> i32;
+    pub fn q3a_fetch_top_logprobs(e: *mut q3a_engine, out_ids: *mut i32, out_lp: *mut f32, stride: i32, n_stride: i32, out_lens: *mut i32) -> i32;
+    pub fn q3a_selftest_top_logprobs(device: i32, logits: *const f32, s: i32, v: i32, n: i32, step_count: *const i32, done: *const u8,
+                                     stride: i32, out_ids: *mut i32, out_lp: *mut f32) -> i32;
     // beam search: n-best hypotheses with scores, selected on the device (include/q3asr.h "beam search")
     pub fn q3a_beam_search_batch_ptrs(e: *mut q3a_engine, pcm16k: *const *const f32, n_samples: *const i64, u: i32,
                                       lang_prefix_ids: *const i32, n_prefix: i32, width: i32, max_new: i32, out_ids: *mut i32, stride: i32,
@@ -209,6 +214,29 @@ impl HipEngine {
         let rc = unsafe { q3a_set_row_options(self.raw, rows.as_ptr(), rows.len() as i32) };
         if rc != 0 { bail!("{}", msg(unsafe { q3a_last_error(self.raw) })); }
         Ok(())
+    }
+
+    /// Top log-probabilities for every later generation call: while `n` > 0 (at most 20) every step also records the `n` best entries
+    /// of its final row -- larger logit first, then smaller id -- with their log-probabilities.  0 turns it off.
+    pub fn set_top_logprobs(&self, n: usize) -> Result<()> {
+        if n > 20 { bail!("set_top_logprobs: n must lie in [0, 20]"); }
+        let rc = unsafe { q3a_set_top_logprobs(self.raw, n as i32) };
+        if rc != 0 { bail!("{}", msg(unsafe { q3a_last_error(self.raw) })); }
+        Ok(())
+    }
+
+    /// What the last run of `batch` utterances recorded under `set_top_logprobs(n)`: per utterance and per generated id (at most
+    /// `max_new` of them, as `transcribe_batch` returned them) the `n` candidates of its step as (id, log-probability), best first.
+    pub fn fetch_top_logprobs(&self, batch: usize, max_new: usize, n: usize) -> Result<Vec<Vec<Vec<(i32, f32)>>>> {
+        let mut ids = vec![0i32; batch * max_new * n];
+        let mut lp = vec![0f32; batch * max_new * n];
+        let mut lens = vec![0i32; batch];
+        let rc = unsafe { q3a_fetch_top_logprobs(self.raw, ids.as_mut_ptr(), lp.as_mut_ptr(), max_new as i32, n as i32, lens.as_mut_ptr()) };
+        if rc != 0 { bail!("{}", msg(unsafe { q3a_last_error(self.raw) })); }
+        Ok((0..batch).map(|b| (0..(lens[b] as usize).min(max_new)).map(|t| {
+            let o = (b * max_new + t) * n;
+            (0..n).map(|k| (ids[o + k], lp[o + k])).collect()
+        }).collect()).collect())
     }
 }
 

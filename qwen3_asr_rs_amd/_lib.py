@@ -28,6 +28,7 @@ SYMBOLS = [
     "q3a_set_repetition", "q3a_selftest_repeat",
     "q3a_set_sequence_bias", "q3a_selftest_seqbias", "q3a_parse_sequence_bias", "q3a_hotword_sequences", "q3a_banned_sequences",
     "q3a_set_row_options", "q3a_set_sequence_bias_lists", "q3a_selftest_row_options",
+    "q3a_set_top_logprobs", "q3a_fetch_top_logprobs", "q3a_selftest_top_logprobs",
     "q3a_selftest_gemm_launch", "q3a_selftest_qkrope_launch", "q3a_gemm256_split_rows",
     "q3a_selftest_gemv_launch", "q3a_selftest_decode_attn_launch",
     "q3a_selftest_decode_attn_split_launch", "q3a_selftest_oproj_head_launch", "q3a_selftest_gemv_parts_launch",
@@ -171,6 +172,9 @@ def load() -> C.CDLL:
         "q3a_set_sampling_filter": (i32, [P, i32, C.c_float]),
         "q3a_selftest_sample_filter": (i32, [i32, f32p, i32, i32, C.c_float, C.c_float, i32, C.c_float, u64, i32, i32p, f32p, f32p, f32p, i32p]),
         "q3a_set_repetition": (i32, [P, C.c_float, i32]),
+        "q3a_set_top_logprobs": (i32, [P, i32]),
+        "q3a_fetch_top_logprobs": (i32, [P, i32p, f32p, i32, i32, i32p]),
+        "q3a_selftest_top_logprobs": (i32, [i32, f32p, i32, i32, i32, i32p, u8p, i32, i32p, f32p]),
         "q3a_selftest_repeat": (i32, [i32, f32p, i32, i32, i32p, i32, i32p, C.c_float, i32, f32p, i32p, f32p]),
         "q3a_set_sequence_bias": (i32, [P, i32p, i32p, f32p, i32]),
         "q3a_selftest_seqbias": (i32, [i32, f32p, i32, i32, i32p, i32, i32p, i32p, i32p, f32p, i32, f32p, i32p, f32p]),

@@ -32,6 +32,10 @@
 // (q3a_parse_sequence_bias).  The three are concatenated in that order (a sequence named twice keeps the larger bias) and set with
 // q3a_set_sequence_bias before anything is generated; the engine then refuses a Q3A_BEAM search and Q3A_DRAFT_TEXT, a
 // Q3A_SCORE_TEXT score never sees it.  '#' starts a comment in the phrase files too; without the variables nothing changes.
+// Q3A_TOP_LOGPROBS=<n> (1..20) records the n best candidates of every generated token (q3a_set_top_logprobs / q3a_fetch_top_logprobs)
+// and adds, after all the lines above, one stdout line per generated token: "Top <t>: <token text> | <candidate text> <probability> |
+// ..." with the n candidates best first (control characters, backslash and '|' escaped in the texts).  The setting is taken back before a Q3A_BEAM search, which
+// the engine refuses under it, as it refuses Q3A_DRAFT_TEXT.  Without the variable stdout and stderr are unchanged.
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -142,6 +146,36 @@ static int set_repetition_from_env(q3a_engine* eng) {
   logf(1, "Repetition control: penalty %s", have_p ? p : "1");
   logf(1, "Repetition control: no-repeat n-gram %s", have_n ? n : "0");
   return 0;
+}
+
+// Q3A_TOP_LOGPROBS: n, or 0 without the variable; -1 after an error was reported
+static int top_logprobs_from_env(q3a_engine* eng) {
+  const char* v = getenv("Q3A_TOP_LOGPROBS");
+  if (!v || !*v) return 0;
+  char* end = nullptr;
+  const long n = strtol(v, &end, 10);
+  if (end == v || *end || n < -1000 || n > 1000) { die(std::string("Top log-probabilities failed: Q3A_TOP_LOGPROBS is not an integer: ") + v); return -1; }
+  if (q3a_set_top_logprobs(eng, (int32_t)n) != 0) { die(std::string("Top log-probabilities failed: ") + q3a_last_error(eng)); return -1; }
+  return (int)n;
+}
+// one token's text for a line of its own: printable as it is, the rest escaped
+static std::string token_text(q3a_tokenizer* tok, int32_t id) {
+  int32_t need = 0;
+  q3a_tokenizer_decode(tok, &id, 1, 0, nullptr, 0, &need);
+  std::string s((size_t)need + 1, '\0');
+  q3a_tokenizer_decode(tok, &id, 1, 0, &s[0], need + 1, &need);
+  s.resize((size_t)need);
+  std::string out;
+  for (unsigned char c : s) {
+    if (c == '\n') out += "\\n";
+    else if (c == '\r') out += "\\r";
+    else if (c == '\t') out += "\\t";
+    else if (c == '\\') out += "\\\\";
+    else if (c == '|') out += "\\|";
+    else if (c < 0x20) { char b[8]; snprintf(b, sizeof(b), "\\x%02x", c); out += b; }
+    else out += (char)c;
+  }
+  return out;
 }
 
 static bool read_file(const char* path, std::string& text) {
@@ -402,6 +436,8 @@ int main(int argc, char** argv) {
   if (set_sampling_from_env(eng) != 0) return 1;
   if (set_sampling_filter_from_env(eng) != 0) return 1;
   if (set_repetition_from_env(eng) != 0) return 1;
+  const int top_n = top_logprobs_from_env(eng);
+  if (top_n < 0) return 1;
   logf(1, "Loading tokenizer...");
   q3a_tokenizer* tok = nullptr;
   const std::string tj = std::string(model_path) + "/tokenizer.json";
@@ -459,6 +495,16 @@ int main(int argc, char** argv) {
       return die(std::string("Transcription failed: ") + q3a_last_error(eng));
     lps.resize((size_t)lp_len);
   }
+  std::vector<int32_t> top_ids;
+  std::vector<float> top_lp;
+  if (top_n > 0) {  // read now, printed last: what follows may run the engine again
+    top_ids.resize((size_t)max_new * top_n);
+    top_lp.resize((size_t)max_new * top_n);
+    int32_t top_len = 0;
+    if (q3a_fetch_top_logprobs(eng, top_ids.data(), top_lp.data(), max_new, top_n, &top_len) != 0)
+      return die(std::string("Top log-probabilities failed: ") + q3a_last_error(eng));
+    if (q3a_set_top_logprobs(eng, 0) != 0) return die(std::string("Top log-probabilities failed: ") + q3a_last_error(eng));
+  }
   q3a_timings tm;
   q3a_stage_timings(eng, &tm);
   if (g_level >= 1) {
@@ -493,6 +539,17 @@ int main(int argc, char** argv) {
   if (rc == 0 && score_path && *score_path && language) rc = print_score(eng, tok, pcm, n, prefix, score_path);
   const char* aligner_dir = getenv("Q3A_ALIGNER");
   if (rc == 0 && aligner_dir && *aligner_dir) rc = print_word_times(aligner_dir, pcm, n, text.data(), language);
+  if (rc == 0 && top_n > 0) {
+    for (int32_t t = 0; t < len; ++t) {
+      std::string line = "Top " + std::to_string(t) + ": " + token_text(tok, ids[(size_t)t]);
+      for (int k = 0; k < top_n; ++k) {
+        char pr[32];
+        snprintf(pr, sizeof(pr), " %.6f", std::exp((double)top_lp[(size_t)t * top_n + k]));
+        line += " | " + token_text(tok, top_ids[(size_t)t * top_n + k]) + pr;
+      }
+      printf("%s\n", line.c_str());
+    }
+  }
   q3a_free(pcm);
   q3a_tokenizer_destroy(tok);
   q3a_engine_destroy(eng);

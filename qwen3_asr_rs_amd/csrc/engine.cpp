@@ -255,6 +255,7 @@ struct StepView {
   // q3a_set_row_options: a row table is set (likewise).  The four switches above then say "on for ANY row", and the kernels read
   // row s's record from DecodeStep::row_opts instead of the uniform buffers
   const bool& row_table_on_;
+  const bool& top_lp_on_;  // q3a_set_top_logprobs: n > 0 (likewise); n itself lives in DecodeStep::top_n, which the kernel reads
 
   bool precise() const { return opts.precise != 0; }
   bool token_lp() const { return opts.token_logprobs != 0; }
@@ -296,6 +297,10 @@ struct DecodeStep : StepView {
   // (samp_params), filter (samp_filter), repetition (rep_params), then {the row's sequence-bias list or -1, 0, 0, 0}.  Allocated by the
   // first table and kept; another table of the same switches needs no new graph
   DevBuf row_opts;
+  // q3a_set_top_logprobs: {n, 0, 0, 0} as the kernel reads it (another n > 0 needs no new graph); the scratch of a step, the chunks'
+  // candidates [B][sample_chunks(vocab)][TOP_LP_MAX] words and their (max, sum exp) pairs [B][sample_chunks(vocab)]; and the history
+  // [B][max_new][TOP_LP_MAX] ids and log-probabilities next to out_ids.  Allocated by the first prefill under n > 0
+  DevBuf top_n, top_cand, top_max, top_sum, top_ids, top_lp;
   DevBuf draft_accepted;  // draft verification (k_draft.hip): [2 B] first mismatch k per sequence, then its token -- one small D2H copy per prefill
   // f(buffer) for every DevBuf declared above, in declaration order (s: a DecodeStep, const or not).  The declarations of this
   // struct ARE the guarded set: tests/test_host.py::test_step_buffers_cover_the_captured_step compares this list with them.
@@ -305,7 +310,7 @@ struct DecodeStep : StepView {
                     &s.rope_cur, &s.rope_cos, &s.rope_sin, &s.n_done, &s.forced_tok,
                     &s.beam_cand_val, &s.beam_cand_idx, &s.beam_part_max, &s.beam_part_sum, &s.beam_topk_ids, &s.beam_topk_lp, &s.beam_score, &s.beam_finished,
                     &s.beam_parent, &s.beam_token, &s.beam_feed, &s.beam_hist_parent, &s.beam_hist_token, &s.beam_hist_lp, &s.beam_state, &s.beam_lo,
-                    &s.logit_bias, &s.samp_params, &s.samp_max, &s.samp_sum, &s.samp_filter, &s.samp_hist, &s.samp_sel, &s.rep_params, &s.seq_bias, &s.row_opts, &s.draft_accepted})
+                    &s.logit_bias, &s.samp_params, &s.samp_max, &s.samp_sum, &s.samp_filter, &s.samp_hist, &s.samp_sel, &s.rep_params, &s.seq_bias, &s.row_opts, &s.top_n, &s.top_cand, &s.top_max, &s.top_sum, &s.top_ids, &s.top_lp, &s.draft_accepted})
       f(*b);
   }
 
@@ -358,7 +363,7 @@ struct DecodeStep : StepView {
   void run_head(int advance) {
     const int S = B, H = d.hidden, V = d.vocab;
     const float* const hb = head_bias();
-    const bool sample = sampling_on_, repeat = repetition_on_, seqb = sequence_bias_on_, rewrite = repeat || seqb, store = head_logits_ || sample || rewrite;
+    const bool sample = sampling_on_, repeat = repetition_on_, seqb = sequence_bias_on_, rewrite = repeat || seqb, store = head_logits_ || sample || rewrite || top_lp_on_;
     tap("head_in", x_dec.p, (size_t)S * H * 4);  // (debug taps) last-layer residual rows the final norm + lm_head read
     const double wbytes = 2.0 * V * H;
     int n_part = 0;
@@ -419,6 +424,7 @@ struct DecodeStep : StepView {
     if (repeat) n_part = enqueue_repetition(part, !sample);
     FinalizeArgs f{};
     f.part = part; f.n_part = n_part; f.V = V; f.advance = advance; f.c = commit();
+    if (top_lp_on_) enqueue_top_logprobs(f.c);  // reads l'' only; step_count is still this id's slot, done still last step's
     if (sample) enqueue_sampler(f);
     timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_argmax_finalize(f, S, stream)); });
     if (sample && token_lp()) enqueue_sample_logprob();
@@ -476,6 +482,16 @@ struct DecodeStep : StepView {
     ra.out_ids = out_ids.as<int>(); ra.out_stride = max_new; ra.step_count = step_count.as<int>();
     timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_repeat_apply(ra, stream)); });
     return partials ? enqueue_rewritten_partials(part) : 0;
+  }
+  // Top log-probabilities (k_repeat.hip, top_logprobs.h): the n best entries of every live row of l'' into slot step_count[s] of the
+  // history.  Behind the last rewriting kernel, in front of the finalize, which advances step_count and sets done.
+  void enqueue_top_logprobs(const StepCommit& c) {  // c: what the finalize behind this launch commits into
+    if (!top_n.p || !top_cand.p || !top_max.p || !top_sum.p || !top_ids.p || !top_lp.p) fail("top log-probabilities: on without its buffers");
+    TopLpArgs a{};
+    a.logits = logits.as<float>(); a.S = B; a.V = d.vocab; a.n_dev = top_n.as<int>(); a.step_count = c.step_count; a.done = c.done;
+    a.cand = top_cand.as<unsigned long long>(); a.chunk_max = top_max.as<float>(); a.chunk_sum = top_sum.as<float>();
+    a.out_ids = top_ids.as<int>(); a.out_lp = top_lp.as<float>(); a.out_stride = max_new;
+    timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_top_logprobs(a, stream)); });
   }
   // Sampling (k_sample.hip), around the finalize of run_head.  The head's partials are done with: the sampler writes its own noisy
   // ones into the same buffers -- no log-sum channel, the drawn id is not the maximum -- and finalize merges those instead.
@@ -890,11 +906,14 @@ struct q3a_engine : CallState {
   bool row_table_on_ = false;           // (graph signature)
   std::vector<q3a_row_options> rows_;   // the table as uploaded (q3a_debug_read "row_options")
   bool uni_on_[4] = {false, false, false, false};
+  bool top_lp_on_ = false;              // q3a_set_top_logprobs: n > 0 (k_repeat.hip; graph signature)
+  int top_lp_n_ = 0;                    // n as last set: what step.top_n holds while it is allocated
+  int top_lp_run_n_ = 0;                // n the decode state was produced under (0: it has no history to fetch)
 
   // ---- the captured decode step: its buffers and launches, and all it sees of the members above ----
   DecodeStep step{StepView{d, L, opts, arena, arena_flags, stream, chain_streams, join_ev, fork_ev, n_cu, host_prog_dev, prof, taps, lm_q, lm_qs, lm_q_cols,
                            B, max_ctx, max_new, gsize, live_nsplit_, live_kps_, attn_nsplit, min_P_, part_stride, beam_w(), kv_layer_elems, head_logits(),
-                           k_parallel_groups, k_skinny_q, k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, k_oproj_by_head, logit_bias_on_, sampling_on_, sampling_filter_on_, repetition_on_, sequence_bias_on_, row_table_on_}};
+                           k_parallel_groups, k_skinny_q, k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, k_oproj_by_head, logit_bias_on_, sampling_on_, sampling_filter_on_, repetition_on_, sequence_bias_on_, row_table_on_, top_lp_on_}};
 
   // (the mode rules are stated once, in StepView)
   bool precise() const { return step.precise(); }
@@ -1415,6 +1434,18 @@ struct q3a_engine : CallState {
       step.samp_hist.ensure((size_t)b * SAMPLE_BUCKETS * 12); step.samp_sel.ensure((size_t)b * 8);
       HIPCHK(hipMemsetAsync(step.samp_hist.p, 0, (size_t)b * SAMPLE_BUCKETS * 12, stream));
     }
+    if (top_lp_on_) {
+      // the scratch is written before it is read, step by step; the history is cleared, so a slot no step wrote reads (0, 0.0)
+      const size_t nc = (size_t)sample_chunks(d.vocab), hist = (size_t)b * max_new * TOP_LP_MAX * 4;
+      step.top_n.ensure(16);
+      step.top_cand.ensure((size_t)b * nc * TOP_LP_MAX * 8); step.top_max.ensure((size_t)b * nc * 4); step.top_sum.ensure((size_t)b * nc * 4);
+      step.top_ids.ensure(hist); step.top_lp.ensure(hist);
+      const int w[4] = {top_lp_n_, 0, 0, 0};
+      HIPCHK(hipMemcpyAsync(step.top_n.p, w, 16, hipMemcpyHostToDevice, stream));  // (drained below, before w goes)
+      HIPCHK(hipMemsetAsync(step.top_ids.p, 0, hist, stream));
+      HIPCHK(hipMemsetAsync(step.top_lp.p, 0, hist, stream));
+    }
+    top_lp_run_n_ = top_lp_on_ ? top_lp_n_ : 0;
     {
       const size_t nblk4 = ((size_t)(d.vocab + 15) / 16 + 3) & ~size_t(3);  // lm_head_prune_blocks, rounded up for float4 reads
       step.blk_lo.ensure(nblk4 * 4); step.blk_hi.ensure(nblk4 * 4);
@@ -1747,6 +1778,7 @@ struct q3a_engine : CallState {
     if (sampling_on_) fail(std::string(what) + ": sampling is on (q3a_set_sampling with temperature > 0): a sampled id is not the argmax of its row -- turn it off first");
     if (repetition_on_) fail(std::string(what) + ": repetition control is on (q3a_set_repetition): its choice depends on the history, not on the row alone -- turn it off first");
     if (sequence_bias_on_) fail(std::string(what) + ": a sequence bias is on (q3a_set_sequence_bias): its choice depends on the history, not on the row alone -- turn it off first");
+    if (top_lp_on_) fail(std::string(what) + ": top log-probabilities are on (q3a_set_top_logprobs): accepted draft tokens never pass the step's head -- turn them off first");
     if (beam_w() > 0) fail(std::string(what) + ": a beam search owns the decode state (a new q3a_prefill returns to the greedy step)");
   }
   // prompts of dp (a kDrafted plan) already set up (setup_prompts over dp.ids / dp.lens).  acc [2 B]: k per utterance, then its token.
@@ -1814,10 +1846,10 @@ struct q3a_engine : CallState {
       uint64_t v = (uint64_t)(uintptr_t)sb.p;
       for (int i = 0; i < 8; ++i) { h ^= (v >> (8 * i)) & 0xff; h *= 1099511628211ull; }
     });
-    char buf[256];
+    char buf[320];
     // (one field per latched knob, as latched: packing several into one integer let distinct settings collide -- ADVICE r5)
-    snprintf(buf, sizeof(buf), "%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.b%d.lb%d.sm%d.sf%d.rp%d.sb%d.rt%d/%d.%d/%d/%d/%p/%016llx", B, gsize, k_parallel_groups, k_skinny_q,
-             k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, k_oproj_by_head, (int)(min_P_ < 256), (int)head_logits(), (int)token_lp(), beam_w(), (int)logit_bias_on_, (int)sampling_on_, (int)(sampling_on_ && sampling_filter_on_), (int)repetition_on_, (int)sequence_bias_on_, (int)row_table_on_, live_nsplit_, live_kps_,
+    snprintf(buf, sizeof(buf), "%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.%d.b%d.lb%d.sm%d.sf%d.rp%d.sb%d.rt%d.tl%d/%d.%d/%d/%d/%p/%016llx", B, gsize, k_parallel_groups, k_skinny_q,
+             k_dattn_batched_min_wgs, k_skinny_glu_hp3, k_lm_head_prune, k_oproj_by_head, (int)(min_P_ < 256), (int)head_logits(), (int)token_lp(), beam_w(), (int)logit_bias_on_, (int)sampling_on_, (int)(sampling_on_ && sampling_filter_on_), (int)repetition_on_, (int)sequence_bias_on_, (int)row_table_on_, (int)top_lp_on_, live_nsplit_, live_kps_,
              max_ctx, max_new, (const void*)arena, (unsigned long long)h);
     return buf;
   }
@@ -2172,6 +2204,43 @@ struct q3a_engine : CallState {
   void beam_sequence_bias_check(const char* what) const {
     if (sequence_bias_on_) fail(std::string(what) + ": a sequence bias is on (q3a_set_sequence_bias); beam slots reorder their histories -- turn it off first");
   }
+  // Top log-probabilities (q3asr.h q3a_set_top_logprobs).  n lives in a device word the kernel reads, so another n > 0 replays the
+  // same graph; on / off is part of the graph signature.  No decode state afterwards.  The buffers come with the next prefill.
+  void set_top_logprobs(int n) {
+    const char* what = "q3a_set_top_logprobs";
+    require_asr(what);
+    if (n < 0 || n > TOP_LP_MAX) fail(std::string(what) + ": n must lie in [0, " + std::to_string(TOP_LP_MAX) + "] (0 turns it off)");
+    if (n > d.vocab) fail(std::string(what) + ": n " + std::to_string(n) + " exceeds the vocabulary (" + std::to_string(d.vocab) + ")");
+    if (n > 0 && d.vocab > TOP_LP_MAX_VOCAB) fail(std::string(what) + ": the vocabulary (" + std::to_string(d.vocab) + ") exceeds the " + std::to_string(TOP_LP_MAX_VOCAB) + " ids the kernel's candidate table holds");
+    drop_decode_state();
+    top_lp_n_ = n;
+    top_lp_on_ = n > 0;
+  }
+  // the history of the last run: [B][stride][n_stride] on the host, row b's first min(out_lens[b], stride) steps, of each the first
+  // min(n, n_stride) entries
+  void fetch_top_logprobs(int32_t* out_i, float* out_l, int stride, int n_stride, int32_t* out_lens) {
+    const char* what = "q3a_fetch_top_logprobs";
+    require_asr(what);
+    if (!at(Stage::Decoding) || beam_w() > 0) fail(std::string(what) + ": nothing generated");
+    if (top_lp_run_n_ <= 0 || !step.top_ids.p || !step.top_lp.p) fail(std::string(what) + ": the last run had top log-probabilities off (q3a_set_top_logprobs)");
+    const size_t words = (size_t)B * max_new * TOP_LP_MAX;
+    std::vector<int> ids((size_t)B * max_new), ti(words);
+    std::vector<float> tl(words);
+    HIPCHK(hipMemcpy(ids.data(), step.out_ids.p, ids.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ti.data(), step.top_ids.p, words * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(tl.data(), step.top_lp.p, words * 4, hipMemcpyDeviceToHost));
+    generated_lens(ids, out_lens);
+    const int n = std::min(top_lp_run_n_, n_stride);
+    for (int s = 0; s < B; ++s)
+      for (int i = 0; i < std::min(out_lens[s], stride); ++i)
+        for (int k = 0; k < n; ++k) {
+          const size_t src = ((size_t)s * max_new + i) * TOP_LP_MAX + k, dst = ((size_t)s * stride + i) * n_stride + k;
+          out_i[dst] = ti[src]; out_l[dst] = tl[src];
+        }
+  }
+  void beam_top_logprobs_check(const char* what) const {
+    if (top_lp_on_) fail(std::string(what) + ": top log-probabilities are on (q3a_set_top_logprobs); beam search re-orders rows -- turn them off first");
+  }
   void beam_repetition_check(const char* what) const {
     if (repetition_on_) fail(std::string(what) + ": repetition control is on (q3a_set_repetition); beam slots reorder their histories -- turn it off first");
   }
@@ -2226,6 +2295,7 @@ struct q3a_engine : CallState {
     beam_check(what, W);
     beam_sampling_check(what);
     beam_repetition_check(what);
+    beam_top_logprobs_check(what);
     beam_sequence_bias_check(what);
     beam_bias_check(what, W);
     if (!head_logits() || pos_hi_ != *std::max_element(P.begin(), P.end()))
@@ -2614,6 +2684,7 @@ int32_t q3a_beam_search_batch_ptrs(q3a_engine* e, const float* const* pcm16k, co
   if (stride < want) fail("q3a_beam_search_batch: stride " + std::to_string(stride) + " is below max_new " + std::to_string(want));
   e->beam_sampling_check("q3a_beam_search_batch");
   e->beam_repetition_check("q3a_beam_search_batch");
+  e->beam_top_logprobs_check("q3a_beam_search_batch");
   e->beam_sequence_bias_check("q3a_beam_search_batch");
   e->beam_bias_check("q3a_beam_search_batch", width);
   e->row_table_batch_check("q3a_beam_search_batch", U * width);
@@ -2663,6 +2734,23 @@ int32_t q3a_set_repetition(q3a_engine* e, float repetition_penalty, int32_t no_r
   Q3A_TRY(e)
   HIPCHK(hipSetDevice(e->device));
   e->set_repetition(repetition_penalty, no_repeat_ngram_size);
+  Q3A_CATCH(e)
+}
+
+int32_t q3a_set_top_logprobs(q3a_engine* e, int32_t n) {
+  if (!e) return 1;
+  Q3A_TRY(e)
+  HIPCHK(hipSetDevice(e->device));
+  e->set_top_logprobs(n);
+  Q3A_CATCH(e)
+}
+
+int32_t q3a_fetch_top_logprobs(q3a_engine* e, int32_t* out_ids, float* out_lp, int32_t stride, int32_t n_stride, int32_t* out_lens) {
+  if (!e) return 1;
+  Q3A_TRY(e)
+  if (!out_lens || stride < 0 || n_stride < 0 || (stride > 0 && n_stride > 0 && (!out_ids || !out_lp))) fail("q3a_fetch_top_logprobs: bad argument");
+  HIPCHK(hipSetDevice(e->device));
+  e->fetch_top_logprobs(out_ids, out_lp, stride, n_stride, out_lens);
   Q3A_CATCH(e)
 }
 
@@ -3089,6 +3177,12 @@ int32_t q3a_debug_read(q3a_engine* e, const char* name, void* dst, uint64_t byte
       fail(std::string("q3a_debug_read: '") + name + "' needs a step sampled with q3a_set_sampling_filter on (no decode state under that setting)");
     const bool kept = strcmp(name, "sample_kept") == 0;  // [S] thresholds, then [S] counts
     give((const uint8_t*)e->step.samp_sel.p + (kept ? S * 4 : 0), S * 4, true);
+    return 0;
+  }
+  if (strcmp(name, "top_logprobs") == 0) {  // n as last set
+    e->require_asr("q3a_debug_read: top_logprobs");
+    const int32_t w[1] = {e->top_lp_n_};
+    give(w, 4, false);
     return 0;
   }
   if (strcmp(name, "repetition") == 0) {  // {on, penalty bits, n-gram size} as last set

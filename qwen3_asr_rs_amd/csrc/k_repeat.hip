@@ -5,7 +5,8 @@
 // and it keeps nothing from step to step: no trie, no match state, nothing to undo.  The history IS out_ids[s][0 .. t),
 // t = min(step_count[s], out_stride).  Both processors are phases of ONE kernel (the library's kernel count is pinned by
 // tests/test_kernarg_preload.py); a launch runs the phases of one processor, the other's arguments are null.  The sampled step's
-// top-k / top-p stage (sample_filter.h) runs as three more launches of it, one phase each, for the same reason.
+// top-k / top-p stage (sample_filter.h) runs as three more launches of it, one phase each, for the same reason, and the top
+// log-probabilities (top_logprobs.h) as two more.
 //
 //   history_apply_kernel   one workgroup of 256 threads per sequence.
 //     sequence bias (launch_seqbias_apply):
@@ -32,14 +33,16 @@
 #include "dev.h"
 #include "kernels.h"
 #include "sample_filter.h"
+#include "top_logprobs.h"
 
 namespace q3a {
 
 namespace {
 
-__global__ __launch_bounds__(256) void history_apply_kernel(SeqBiasArgs sb, RepeatArgs a, int words, int hist_cap, SampleStageArgs st) {
+__global__ __launch_bounds__(256) void history_apply_kernel(SeqBiasArgs sb, RepeatArgs a, int words, int hist_cap, SampleStageArgs st, TopLpArgs tl) {
   extern __shared__ __attribute__((aligned(16))) uint32_t repeat_lds[];
   if (st.phase) { sample_stage_phase(st, repeat_lds); return; }  // top-k / top-p: a launch of its own, none of the history's phases
+  if (tl.phase) { top_lp_stage_phase(tl, repeat_lds); return; }  // top log-probabilities: likewise
   __shared__ int tail[SEQBIAS_MAX_LEN - 1];
   const int s = blockIdx.x, tid = threadIdx.x;
   if (sb.params) {  // (uniform: a kernel argument)
@@ -127,7 +130,7 @@ const char* launch_repeat_apply(const RepeatArgs& a, hipStream_t s) {
   if (!a.logits || !a.params || !a.out_ids || !a.step_count || a.out_stride < 1) return "repetition: null argument";
   const int words = (a.V + 31) / 32, hist_cap = a.out_stride < REPEAT_HIST_LDS ? a.out_stride : REPEAT_HIST_LDS;
   const size_t lds = ((size_t)((words + 3) & ~3) + (size_t)hist_cap) * 4;  // <= 32 KB + 16 KB
-  hipLaunchKernelGGL(history_apply_kernel, dim3(a.S), dim3(256), lds, s, SeqBiasArgs{}, a, words, hist_cap, SampleStageArgs{});
+  hipLaunchKernelGGL(history_apply_kernel, dim3(a.S), dim3(256), lds, s, SeqBiasArgs{}, a, words, hist_cap, SampleStageArgs{}, TopLpArgs{});
   return nullptr;
 }
 
@@ -136,7 +139,7 @@ const char* launch_seqbias_apply(const SeqBiasArgs& a, hipStream_t s) {
   if (a.V < 1) return "sequence bias: empty vocabulary";
   if (!a.logits || !a.params || !a.grp_target || !a.grp_begin || !a.ent_bias || !a.ent_pre_off || !a.pre_ids || !a.list_begin || !a.row_list || !a.out_ids || !a.step_count || a.out_stride < 1)
     return "sequence bias: null argument";
-  hipLaunchKernelGGL(history_apply_kernel, dim3(a.S), dim3(256), 0, s, a, RepeatArgs{}, 0, 0, SampleStageArgs{});
+  hipLaunchKernelGGL(history_apply_kernel, dim3(a.S), dim3(256), 0, s, a, RepeatArgs{}, 0, 0, SampleStageArgs{}, TopLpArgs{});
   return nullptr;
 }
 
@@ -145,11 +148,26 @@ const char* launch_seqbias_apply(const SeqBiasArgs& a, hipStream_t s) {
 const char* launch_sample_stage(const SampleArgs& a, const SampleFilterArgs& f, bool vec, hipStream_t s) {
   SampleStageArgs st{1, vec ? 1 : 0, sample_chunks(a.V), a, f};
   const dim3 grid(st.n_chunk, a.S);
-  hipLaunchKernelGGL(history_apply_kernel, grid, dim3(256), SAMPLE_HIST_LDS, s, SeqBiasArgs{}, RepeatArgs{}, 0, 0, st);
+  hipLaunchKernelGGL(history_apply_kernel, grid, dim3(256), SAMPLE_HIST_LDS, s, SeqBiasArgs{}, RepeatArgs{}, 0, 0, st, TopLpArgs{});
   st.phase = 2;
-  hipLaunchKernelGGL(history_apply_kernel, dim3(a.S), dim3(256), SAMPLE_SELECT_LDS, s, SeqBiasArgs{}, RepeatArgs{}, 0, 0, st);
+  hipLaunchKernelGGL(history_apply_kernel, dim3(a.S), dim3(256), SAMPLE_SELECT_LDS, s, SeqBiasArgs{}, RepeatArgs{}, 0, 0, st, TopLpArgs{});
   st.phase = 3;
-  hipLaunchKernelGGL(history_apply_kernel, grid, dim3(256), 0, s, SeqBiasArgs{}, RepeatArgs{}, 0, 0, st);
+  hipLaunchKernelGGL(history_apply_kernel, grid, dim3(256), 0, s, SeqBiasArgs{}, RepeatArgs{}, 0, 0, st, TopLpArgs{});
+  return nullptr;
+}
+
+// Top log-probabilities: the chunk grid, then one workgroup per row with the chunks' candidates in LDS.
+const char* launch_top_logprobs(const TopLpArgs& a, hipStream_t s) {
+  if (a.S <= 0) return nullptr;
+  if (a.V < 1) return "top log-probabilities: empty vocabulary";
+  if (a.V > TOP_LP_MAX_VOCAB) return "top log-probabilities: the vocabulary exceeds the row phase's candidate table (819200 ids)";
+  if (!a.logits || !a.n_dev || !a.step_count || !a.done || !a.cand || !a.chunk_max || !a.chunk_sum || !a.out_ids || !a.out_lp || a.out_stride < 1)
+    return "top log-probabilities: null argument";
+  TopLpArgs t = a;
+  t.phase = 1; t.vec = a.V % 4 == 0 && ((uintptr_t)a.logits & 15) == 0 ? 1 : 0; t.n_chunk = sample_chunks(a.V);
+  hipLaunchKernelGGL(history_apply_kernel, dim3(t.n_chunk, a.S), dim3(256), 0, s, SeqBiasArgs{}, RepeatArgs{}, 0, 0, SampleStageArgs{}, t);
+  t.phase = 2;
+  hipLaunchKernelGGL(history_apply_kernel, dim3(a.S), dim3(256), (size_t)t.n_chunk * TOP_LP_MAX * 8, s, SeqBiasArgs{}, RepeatArgs{}, 0, 0, SampleStageArgs{}, t);
   return nullptr;
 }
 

@@ -549,6 +549,27 @@ struct SampleLogprobArgs {
 };
 const char* launch_sample_logprob(const SampleLogprobArgs& a, hipStream_t s);
 
+// ---- top log-probabilities (k_repeat.hip: two more phases of its kernel; top_logprobs.h) --------------------------
+constexpr int TOP_LP_MAX = 20;  // entries per step: the largest n, and the fixed inner stride of the history and of the candidates
+// Per row s of logits [S][V] (fp32, row stride V) that is not done and has a slot t = step_count[s] < out_stride: the n = min(*n_dev,
+// TOP_LP_MAX, V) best entries -- larger logit first, then smaller id; -0.0 and +0.0 one value; -inf last -- as out_ids / out_lp
+// [s][t][0 .. n), lp = (l - m) - log sum exp(l - m) in fp32 with a fixed summation order (-inf exactly where l is -inf).  Any other row
+// writes nothing.  Two launches: the chunk grid (candidates and (max, sum) per 2048-logit chunk), then one workgroup per row.  It only
+// reads the logits; it runs behind the step's last rewriting kernel and in front of launch_argmax_finalize, which advances step_count.
+struct TopLpArgs {
+  int phase; int vec; int n_chunk;     // phase 0: not this stage's launch (filled by launch_top_logprobs)
+  const float* logits; int S; int V;
+  const int* n_dev;                    // device [1]: n as last set (read by the kernel: another n > 0, the same launch)
+  const int* step_count;               // [S]
+  const uint8_t* done;                 // [S]
+  unsigned long long* cand;            // [S][sample_chunks(V)][TOP_LP_MAX] (written) the chunks' best entries as ordered words
+  float* chunk_max; float* chunk_sum;  // [S][sample_chunks(V)] (written)
+  int* out_ids; float* out_lp;         // [S][out_stride][TOP_LP_MAX] the history
+  int out_stride;
+};
+constexpr int TOP_LP_MAX_VOCAB = 400 * 2048;  // the row phase keeps every chunk's candidates in LDS (400 chunks x 20 x 8 bytes)
+const char* launch_top_logprobs(const TopLpArgs& a, hipStream_t s);
+
 // ---- repetition penalty and no-repeat n-grams (k_repeat.hip) -----------------------------------------------------
 constexpr int REPEAT_MAX_VOCAB = 1 << 18;  // ids the kernel's LDS bitmap holds (8192 words, 32 KB)
 constexpr int REPEAT_HIST_LDS = 4096;      // ids of a history kept in LDS (16 KB); a longer history is read in place beyond them

@@ -396,6 +396,40 @@ int32_t q3a_selftest_repeat(int32_t device, const float* logits, int32_t S, int3
   Q3A_CATCH(nullptr)
 }
 
+// the top log-probabilities of a step as the engine enqueues them (launch_top_logprobs on the stored rows), TWICE on the same scratch
+// and into two histories: the second run sees whatever the first left in the candidates and the chunk pairs.  out_ids / out_lp: the
+// whole [S][stride][TOP_LP_MAX] history of the second run (ids -1 and lp 0 where nothing was written); nonzero if the two differ.
+int32_t q3a_selftest_top_logprobs(int32_t device, const float* logits, int32_t S, int32_t V, int32_t n, const int32_t* step_count,
+                                  const uint8_t* done, int32_t stride, int32_t* out_ids, float* out_lp) {
+  Q3A_TRY(nullptr)
+  if (!logits || !step_count || !done || !out_ids || !out_lp || S < 1 || V < 1 || stride < 1 || stride > (1 << 16)) fail("q3a_selftest_top_logprobs: bad argument");
+  if (n < 1 || n > TOP_LP_MAX || n > V) fail("q3a_selftest_top_logprobs: n must lie in [1, min(20, V)]");
+  use_device(device);
+  const size_t Sz = S, nc = (size_t)sample_chunks(V), hist = Sz * stride * TOP_LP_MAX;
+  const DevBuf dLg = to_device(logits, Sz * V), dN = to_device(&n, 1), dSc = to_device(step_count, Sz), dDone = to_device(done, Sz);
+  const DevBuf dCand = room(Sz * nc * TOP_LP_MAX * 8), dMax = room(Sz * nc * 4), dSum = room(Sz * nc * 4);
+  // the scratch starts as all-ones words (NaN pairs, candidates above every real entry): what a run does not write itself shows
+  HIPCHK(hipMemset(dCand.p, 0xFF, Sz * nc * TOP_LP_MAX * 8));
+  HIPCHK(hipMemset(dMax.p, 0xFF, Sz * nc * 4));
+  HIPCHK(hipMemset(dSum.p, 0xFF, Sz * nc * 4));
+  std::vector<int> ids[2];
+  std::vector<float> lp[2];
+  for (int run = 0; run < 2; ++run) {
+    const DevBuf dIds = to_device(std::vector<int>(hist, -1)), dLp = to_device(std::vector<float>(hist, 0.f));
+    TopLpArgs a{};
+    a.logits = dLg.as<float>(); a.S = S; a.V = V; a.n_dev = dN.as<int>(); a.step_count = dSc.as<int>(); a.done = dDone.as<uint8_t>();
+    a.cand = dCand.as<unsigned long long>(); a.chunk_max = dMax.as<float>(); a.chunk_sum = dSum.as<float>();
+    a.out_ids = dIds.as<int>(); a.out_lp = dLp.as<float>(); a.out_stride = stride;
+    KCHK(launch_top_logprobs(a, nullptr));
+    finish();
+    ids[run] = to_host<int>(dIds, hist); lp[run] = to_host<float>(dLp, hist);
+  }
+  memcpy(out_ids, ids[1].data(), hist * 4);
+  memcpy(out_lp, lp[1].data(), hist * 4);
+  if (ids[0] != ids[1] || memcmp(lp[0].data(), lp[1].data(), hist * 4) != 0) fail("q3a_selftest_top_logprobs: the second run on the same scratch differs from the first");
+  Q3A_CATCH(nullptr)
+}
+
 // a step's tail with q3a_set_sequence_bias on, as the engine enqueues it without repetition control and without sampling: the list laid
 // out by the setter's own function, launch_seqbias_apply on the stored rows, fresh argmax partials (with the log-sum channel) over the
 // rewritten rows, argmax_finalize on those

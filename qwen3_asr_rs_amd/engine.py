@@ -132,6 +132,34 @@ def check_repetition_args(repetition_penalty: float = 1.0, no_repeat_ngram_size:
     return p, int(n)
 
 
+TOP_LOGPROBS_MAX = 20
+
+
+def check_top_logprobs_args(n: int = 0) -> int:
+    """The refusals of q3a_set_top_logprobs that need no engine (pure host function): n an integer in [0, 20] (0 = off).  Returns n as
+    the C call takes it.  (n above the vocabulary is the engine's refusal: it knows the vocabulary.)"""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not (0 <= int(n) <= TOP_LOGPROBS_MAX):
+        raise Q3aError(f"set_top_logprobs: n must be an integer in [0, {TOP_LOGPROBS_MAX}] (0 turns it off), got {n!r}")
+    return int(n)
+
+
+def check_top_logprobs_compat(top_logprobs: int, beam_size: int = 1, draft=None):
+    """What transcribe(top_logprobs=...) does not run with, decided on the host before the engine is touched."""
+    if top_logprobs and beam_size > 1:
+        raise Q3aError("transcribe: beam search reports no top log-probabilities (beam_size > 1 with top_logprobs): its slots re-order rows")
+    if top_logprobs and draft is not None:
+        raise Q3aError("transcribe: a draft cannot be verified with top log-probabilities (draft with top_logprobs): accepted tokens never pass the step's head")
+
+
+def uniform_top_logprobs(options) -> int:
+    """The one top_logprobs of a batch's option dicts (0 when none has the key).  The setting is uniform for a batch -- the history has
+    one inner stride and the step one n --, so dicts that disagree are refused."""
+    given = [check_top_logprobs_args((o or {}).get("top_logprobs", 0)) for o in options]
+    if len(set(given)) > 1:
+        raise ValueError(f"transcribe_batch: top_logprobs must be equal for all rows (the engine records one n per batch, not per row), got {given}")
+    return given[0] if given else 0
+
+
 SEQUENCE_BIAS_MAX_ENTRIES, SEQUENCE_BIAS_MAX_LEN, SEQUENCE_BIAS_MAX_IDS = 4096, 32, 65536
 
 
@@ -453,6 +481,7 @@ class HipEngine:
         self.repetition_state: Tuple[float, int] = (1.0, 0)  # what set_repetition was last given
         self.sequence_bias_state: List[Tuple[tuple, float]] = []  # what set_sequence_bias was last given, as (ids, bias) pairs
         self.row_options_state: Optional[List[RowOptions]] = None  # what set_row_options was last given (None: no row table)
+        self.top_logprobs_state: int = 0  # what set_top_logprobs was last given
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -565,6 +594,19 @@ class HipEngine:
         out = np.zeros((self.batch, stride), dtype=np.float32)
         self._chk(self._lib.q3a_fetch_logprobs(self._h, _f32p(out), stride, _i32p(lens)))
         return [out[b, :int(lens[b])].copy() for b in range(self.batch)]
+
+    def fetch_top_logprobs(self) -> List[Tuple[np.ndarray, np.ndarray]]:
+        """q3a_fetch_top_logprobs: per utterance (ids int32 [len][n], lp float32 [len][n]) -- for every id fetch_ids / transcribe_batch
+        returned for the last run or stage-API step, the n best entries of the row it was chosen from, best first, with their
+        natural-log probabilities.  Needs set_top_logprobs(n > 0) before the run."""
+        n = self.top_logprobs_state
+        lens = np.zeros(self.batch, dtype=np.int32)
+        self._chk(self._lib.q3a_fetch_top_logprobs(self._h, None, None, 0, 0, _i32p(lens)))  # lengths first (and the refusals)
+        stride = max(1, int(lens.max()) if len(lens) else 1)
+        ids = np.zeros((self.batch, stride, max(n, 1)), dtype=np.int32)
+        lp = np.zeros((self.batch, stride, max(n, 1)), dtype=np.float32)
+        self._chk(self._lib.q3a_fetch_top_logprobs(self._h, _i32p(ids), _f32p(lp), stride, max(n, 1), _i32p(lens)))
+        return [(ids[b, :int(lens[b]), :n].copy(), lp[b, :int(lens[b]), :n].copy()) for b in range(self.batch)]
 
     @staticmethod
     def _ptrs(clips: Sequence[np.ndarray]):
@@ -830,6 +872,19 @@ class HipEngine:
     def repetition_stats(self) -> dict:
         st = self.debug_read_raw("repetition").view(np.uint32)
         return {"active": bool(st[0]), "repetition_penalty": float(st[1:2].view(np.float32)[0]), "no_repeat_ngram_size": int(st[2])}
+
+    # ---- top log-probabilities -------------------------------------------------------------------------------
+    def set_top_logprobs(self, n: int = 0):
+        """q3a_set_top_logprobs: while n > 0 (at most 20) every generation step also records the n best entries of its final row --
+        larger logit first, then smaller id -- with their log-probabilities under the untempered, unfiltered distribution; read them
+        with fetch_top_logprobs.  0 turns it off.  Drops the decode state: prefill again before a stage-API step."""
+        n = check_top_logprobs_args(n)
+        self._chk(self._lib.q3a_set_top_logprobs(self._h, n))
+        self.top_logprobs_state = n
+
+    def top_logprobs_stats(self) -> dict:
+        n = int(self.debug_read_raw("top_logprobs").view(np.int32)[0])
+        return {"active": n > 0, "n": n}
 
     # ---- sequence bias: hotword boosts and banned phrases ------------------------------------------------------
     def set_sequence_bias(self, entries=None):
@@ -1105,6 +1160,15 @@ class Alternative:
 
 
 @dataclass
+class TokenCandidate:
+    """An entry of TranscribeResult.top_logprobs: a token the step could have written, its text (empty without a tokenizer) and its
+    natural-log probability under the step's final, untempered distribution."""
+    id: int
+    token: str
+    logprob: float
+
+
+@dataclass
 class TranscribeResult:
     """src/inference.rs:269-274 (+ the raw ids, which is where parity is pinned).  With an engine created with token_logprobs=True
     also the log-probability of every id and their mean (Whisper's avg_logprob; None when no token was generated)."""
@@ -1117,6 +1181,7 @@ class TranscribeResult:
     alternatives: Optional[List[Alternative]] = None  # beam_size > 1: the n-best list, best first (this result is its first entry)
     temperature: Optional[float] = None  # transcribe(temperature=...): the temperature of the attempt that was kept (0.0 = greedy)
     accepted_draft_tokens: Optional[int] = None  # transcribe(draft=...): leading ids of the draft the greedy loop would have written itself
+    top_logprobs: Optional[List[List[TokenCandidate]]] = None  # transcribe(top_logprobs=n): per id of `ids` the n best candidates of its step, best first
 
 
 @dataclass
@@ -1156,7 +1221,7 @@ class AsrInference:
                    no_repeat_ngram_size: int = 0, draft=None, hotwords: Optional[Iterable[str]] = None,
                    hotword_boost: Optional[float] = None, hotword_start_boost: float = 0.0,
                    banned_phrases: Optional[Iterable[str]] = None, sequence_bias=None, top_k: int = 0,
-                   top_p: float = 1.0) -> TranscribeResult:
+                   top_p: float = 1.0, top_logprobs: int = 0) -> TranscribeResult:
         """src/inference.rs:89-213.  `audio`: path to a WAV file or a 16 kHz float32 array.  beam_size > 1: a beam search of that
         width instead of the greedy loop; `alternatives` holds its hypotheses ordered by score / max(len, 1) ** length_penalty
         (float64 on the host; 0: the search's own order) and the result is the first of them.
@@ -1183,7 +1248,14 @@ class AsrInference:
         banned_phrases: phrases never to write -- the two tokenisations of each at -inf.  sequence_bias: entries given as ids, a
         mapping {tuple of ids: bias} or (ids, bias) pairs.  The three are concatenated in that order; a sequence named twice keeps the
         larger bias.  Composes with temperature, repetition_penalty, no_repeat_ngram_size and the logit-bias arguments; raises
-        Q3aError with beam_size > 1 or a draft."""
+        Q3aError with beam_size > 1 or a draft.
+        top_logprobs: n in [1, 20] sets HipEngine.set_top_logprobs for this call (the engine's own setting is restored afterwards) and
+        fills the result's `top_logprobs`: for every id of `ids` the n best candidates of the step that wrote it -- the row after the
+        logit bias, the sequence bias and repetition control, untempered and unfiltered --, best first.  In a greedy call the first
+        candidate is the id itself.  Composes with temperature (every attempt of a fallback; the kept attempt's candidates are
+        returned), repetition control, hotwords and the logit-bias arguments; raises Q3aError with beam_size > 1 or a draft."""
+        top_n = check_top_logprobs_args(top_logprobs)
+        check_top_logprobs_compat(top_n, beam_size, draft)
         seq_entries = self._sequence_bias_entries(hotwords, hotword_boost, hotword_start_boost, banned_phrases, sequence_bias)
         if seq_entries is not None and beam_size > 1:
             raise Q3aError("transcribe: beam search has no sequence bias (beam_size > 1 with hotwords / banned_phrases / sequence_bias)")
@@ -1253,6 +1325,16 @@ class AsrInference:
                     return inner_sb()
                 finally:
                     seng.set_sequence_bias(before)
+        if top_n:
+            inner_tl, teng = run, self.engine
+
+            def run():
+                before = teng.top_logprobs_state
+                teng.set_top_logprobs(top_n)
+                try:
+                    return inner_tl()
+                finally:
+                    teng.set_top_logprobs(before)
         if suppress_tokens is None and logit_bias is None and allowed_tokens is None:
             return run()
         ids, bias, default = compose_logit_bias(self.engine.dims.vocab_size, suppress_tokens, logit_bias, allowed_tokens)
@@ -1264,7 +1346,7 @@ class AsrInference:
             self.engine.set_logit_bias(*before)
 
     _ROW_OPTION_KEYS = ("temperature", "min_p", "seed", "top_k", "top_p", "repetition_penalty", "no_repeat_ngram_size", "hotwords", "hotword_boost",
-                        "hotword_start_boost", "banned_phrases", "sequence_bias")
+                        "hotword_start_boost", "banned_phrases", "sequence_bias", "top_logprobs")
 
     def transcribe_batch(self, audios, language: Optional[str] = None, max_new_tokens: int = 4096, options=None) -> List[TranscribeResult]:
         """transcribe() for several audios in ONE batch, each with its own decoding options (HipEngine.set_row_options): `options` holds
@@ -1272,11 +1354,14 @@ class AsrInference:
         no_repeat_ngram_size, hotwords, hotword_boost, hotword_start_boost, banned_phrases and sequence_bias.  None is a plain greedy
         request.  The noise of a sampled row depends on its index in the batch.  `language` is one per call.  The engine's row table
         and sequence-bias lists are restored afterwards.  Raises Q3aError for a tuple of temperatures (fallback decides per attempt,
-        not per row), beam_size, draft, the logit-bias arguments (one vector per engine) and top_k / top_p without a temperature > 0."""
+        not per row), beam_size, draft, the logit-bias arguments (one vector per engine) and top_k / top_p without a temperature > 0.
+        The key top_logprobs is the exception to "its own": the engine records one n per batch, so it may be given only if it is equal
+        for all rows (ValueError otherwise); the results then carry `top_logprobs` as transcribe's do."""
         audios = list(audios)
         options = [None] * len(audios) if options is None else list(options)
         if len(options) != len(audios):
             raise Q3aError(f"transcribe_batch: {len(options)} option dict(s) for {len(audios)} audio(s)")
+        top_n = uniform_top_logprobs(options)
         rows = []
         for i, o in enumerate(options):
             o = dict(o) if o is not None else {}
@@ -1307,13 +1392,20 @@ class AsrInference:
                 raise Q3aError("forcing a language needs tokenizer.json (src/inference.rs:246-251)")
             prefix = self.tokenizer.encode("language " + capitalize_first(language))
         eng = self.engine
-        before = eng.row_options_state
+        before, before_top = eng.row_options_state, eng.top_logprobs_state
+        tops = None
         try:
             eng.set_row_options(rows)
+            if top_n:
+                eng.set_top_logprobs(top_n)
             all_ids = eng.transcribe_batch(samples, prefix, max_new_tokens)
             lps = eng.fetch_logprobs() if eng.token_logprobs else None
+            if top_n:
+                tops = eng.fetch_top_logprobs()
         finally:
             eng.set_row_options(before)
+            if top_n:
+                eng.set_top_logprobs(before_top)
         results = []
         for i, ids in enumerate(all_ids):
             raw = self.tokenizer.decode(ids, True) if self.tokenizer is not None else ""
@@ -1323,8 +1415,15 @@ class AsrInference:
             if lps is not None:
                 res.token_logprobs = [float(v) for v in lps[i]]
                 res.avg_logprob = float(np.mean(lps[i], dtype=np.float64)) if len(lps[i]) else None
+            if tops is not None:
+                res.top_logprobs = self._candidates(*tops[i])
             results.append(res)
         return results
+
+    def _candidates(self, ids: np.ndarray, lp: np.ndarray) -> List[List[TokenCandidate]]:
+        """fetch_top_logprobs' arrays of one utterance as TokenCandidate lists, one list per generated id."""
+        text = (lambda i: self.tokenizer.decode([i], False)) if self.tokenizer is not None else (lambda i: "")
+        return [[TokenCandidate(int(i), text(int(i)), float(v)) for i, v in zip(row_i, row_l)] for row_i, row_l in zip(ids, lp)]
 
     def _sequence_bias_entries(self, hotwords, hotword_boost, hotword_start_boost, banned_phrases, sequence_bias):
         """The call's sequence-bias entries, checked; None when none of the arguments was given."""
@@ -1398,6 +1497,8 @@ class AsrInference:
             lp = self.engine.fetch_logprobs()[0]
             res.token_logprobs = [float(v) for v in lp]
             res.avg_logprob = float(np.mean(lp, dtype=np.float64)) if len(lp) else None
+        if self.engine.top_logprobs_state and beam_size <= 1 and draft_ids is None:
+            res.top_logprobs = self._candidates(*self.engine.fetch_top_logprobs()[0])
         return res
 
 

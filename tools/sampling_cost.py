@@ -7,12 +7,15 @@ events).  Arms, their order rotated round by round:
     t1minp  temperature 1, min_p 0.05: only the kept set does
     t1k50 / t1p09 / t1k50p09  temperature 1 under q3a_set_sampling_filter: top_k 50, top_p 0.9, both (the threshold stage's two launches)
     rows    a row table (q3a_set_row_options) whose rows all carry the t1 record: the same launches reading a record per row
+    top5 / top20  greedy under q3a_set_top_logprobs with n = 5 / 20: two more launches per step and the stored logits (at one sequence
+            the full lm_head GEMV in the place of the pruned argmax)
 
     python tools/sampling_cost.py --preset 0.6b --batch 1 --rounds 7
     python tools/sampling_cost.py --preset 0.6b --batch 32 --rounds 7
     python tools/sampling_cost.py --batch 1 --arms off,t1,t1k50,t1p09,t1k50p09     # the filter's arms against the sampler's
     python tools/sampling_cost.py --rounds 1 --arms off        # no sampling call at all: the run a kernel trace compares launches on
     python tools/sampling_cost.py --batch 32 --arms t1,rows    # per-row records against the one record (Q3A_LIB: another build's t1)
+    python tools/sampling_cost.py --batch 1 --arms off,top5,top20   # top log-probabilities against the greedy step
 
 Prints one line per round and a summary: median us per step of each arm, the difference to `off` in percent and in us, pruned
 passes per arm at one sequence, and that `off` generated the same ids before and after the sampled arms ran."""
@@ -28,6 +31,7 @@ sys.path.insert(0, ROOT)
 
 ARMS = {"t1": (1.0, 0.0), "t1minp": (1.0, 0.05)}          # temperature, min_p
 FILTERS = {"t1k50": (50, 1.0), "t1p09": (0, 0.9), "t1k50p09": (50, 0.9)}   # top_k, top_p at temperature 1, min_p 0
+TOPS = {"top5": 5, "top20": 20}                            # n of q3a_set_top_logprobs, greedy
 
 
 def main():
@@ -39,9 +43,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--arms", default="off,t1,t1minp")
     args = ap.parse_args()
-    unknown = [a for a in args.arms.split(",") if a and a not in ("off", "rows") and a not in ARMS and a not in FILTERS]
+    unknown = [a for a in args.arms.split(",") if a and a not in ("off", "rows") and a not in ARMS and a not in FILTERS and a not in TOPS]
     if unknown:
-        ap.error(f"unknown arm(s) {unknown}: choose from off, rows, {', '.join(list(ARMS) + list(FILTERS))}")
+        ap.error(f"unknown arm(s) {unknown}: choose from off, rows, {', '.join(list(ARMS) + list(FILTERS) + list(TOPS))}")
     from qwen3_asr_rs_amd import synthetic
     from qwen3_asr_rs_amd.engine import HipEngine, RowOptions
     model_dir = f"/tmp/q3a_ckpt_{args.preset.replace('.', 'p')}"
@@ -51,7 +55,7 @@ def main():
     eng = HipEngine(model_dir, 0, max_new_tokens=max(N, 16))
     eng.upload_pcm(clips)
     names = [a for a in args.arms.split(",") if a]
-    state = {"set": False, "filter": False, "rows": False}
+    state = {"set": False, "filter": False, "rows": False, "top": False}
 
     def stats():
         return eng.debug_read_raw("lm_head_prune_stats").view(np.int32).astype(np.int64)
@@ -63,6 +67,12 @@ def main():
         elif state["rows"]:  # (never called unless the rows arm ran: the other arms drive a library without the call)
             eng.set_row_options(None)
             state["rows"] = False
+        if arm in TOPS:
+            eng.set_top_logprobs(TOPS[arm])
+            state["top"] = True
+        elif state["top"]:  # (never called unless a top arm ran: the other arms drive a library without the call)
+            eng.set_top_logprobs(0)
+            state["top"] = False
         if arm in FILTERS:
             eng.set_sampling_filter(*FILTERS[arm])
             state["filter"] = True
@@ -71,7 +81,7 @@ def main():
             state["filter"] = False
         if arm == "rows":
             pass  # (the uniform setting stays what it was: remembered, not read)
-        elif arm != "off":
+        elif arm != "off" and arm not in TOPS:
             eng.set_sampling(*(ARMS[arm] if arm in ARMS else (1.0, 0.0)), 17)  # (a filter arm: temperature 1, min_p 0)
             state["set"] = True
         elif state["set"]:  # (never called when only `off` runs: the same tool then drives a library without the call)
@@ -106,7 +116,7 @@ def main():
         line += f"; off ids unchanged: {ids['off'] == ids0}"
     for a in names:
         if a != "off":
-            line += f"; {a}: ids differ from off: {ids[a] != ids0}"
+            line += f"; {a}: ids differ from off: {ids[a] != ids0}"  # (a top arm is greedy: its ids must NOT differ)
     print(line)
     eng.close()
 
