@@ -23,9 +23,9 @@ LIB_PATH = os.path.join(LIB_DIR, "libq3asr_hip.so")
 BIN_DIR = os.path.join(HERE, "bin")
 CLI_PATH = os.path.join(BIN_DIR, "asr")  # the reference's CLI (src/main.rs) on top of the C ABI
 
-SOURCES = ["engine.cpp", "selftest.cpp", "model.cpp", "k_gemm.hip", "k_mel.hip", "k_conv1.hip", "k_norm.hip", "k_attn.hip", "k_decode.hip", "k_gemv.hip", "k_dattn.hip", "k_fattn.hip", "k_skinny.hip", "k_gemm16.hip", "k_gemm256.hip", "k_peaks.hip", "k_align.hip", "k_beam.hip", "k_sample.hip", "k_repeat.hip", "k_draft.hip",
+SOURCES = ["engine.cpp", "selftest.cpp", "model.cpp", "k_gemm.hip", "k_mel.hip", "k_conv1.hip", "k_norm.hip", "k_attn.hip", "k_decode.hip", "k_gemv.hip", "k_dattn.hip", "k_fattn.hip", "k_skinny.hip", "k_gemm16.hip", "k_gemm256.hip", "k_peaks.hip", "k_align.hip", "k_beam.hip", "k_sample.hip", "k_repeat.hip", "k_toplp.hip", "k_draft.hip",
            "host_audio.cpp", "host_text.cpp", "host_abi.cpp", "host_align.cpp", "group.cpp", "ops.cpp", "k_ops.hip"]
-HEADERS = ["dev.h", "engine_internal.h", "kernels.h", "argmax.h", "step_commit.h", "sample_rng.h", "sample_filter.h", "top_logprobs.h", "model.h", "json.h", "host.h", "ops.h", "unicode_tables.h", os.path.join("..", "..", "include", "q3asr.h"),
+HEADERS = ["dev.h", "engine_internal.h", "kernels.h", "argmax.h", "step_commit.h", "sample_rng.h", "sample_filter.h", "model.h", "json.h", "host.h", "ops.h", "unicode_tables.h", os.path.join("..", "..", "include", "q3asr.h"),
            os.path.join("..", "..", "include", "q3asr_ops.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fno-slp-vectorize: hipcc's SLP vectoriser packs scalar fp32 code into v_pk_*_f32 with op_sel operand swaps, and a packed fp32

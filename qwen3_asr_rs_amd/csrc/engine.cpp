@@ -105,7 +105,7 @@ Knobs& knobs() {
 }  // namespace q3a
 
 namespace q3a {
-// The lists of q3a_set_sequence_bias_lists (q3a_set_sequence_bias: one list) as the sequence-bias phase of history_apply_kernel reads
+// The lists of q3a_set_sequence_bias_lists (q3a_set_sequence_bias: one list) as seqbias_apply_kernel (k_repeat.hip) reads
 // them (engine_internal.h; kernels.h SeqBiasArgs).  One list gives the words it always gave, plus the directory.
 SeqBiasTable seqbias_layout(const char* what_c, const int32_t* ids, const int32_t* lens, const float* bias, int n, int V) {
   if (n < 0) fail(std::string(what_c) + ": bad argument");
@@ -291,7 +291,7 @@ struct DecodeStep : StepView {
   // stage's first-digit table per row, [B][SAMPLE_BUCKETS] uint64 weights then [B][SAMPLE_BUCKETS] uint32 counts, zero between steps;
   // and what it leaves: [B] fp32 max(tau_k, tau_p), then [B] int32 entries kept by it
   DevBuf samp_filter, samp_hist, samp_sel;
-  DevBuf rep_params;  // q3a_set_repetition: {penalty (fp32 bits), n-gram size, 0, 0} as history_apply_kernel reads them (a new setting needs no new graph)
+  DevBuf rep_params;  // q3a_set_repetition: {penalty (fp32 bits), n-gram size, 0, 0} as repeat_apply_kernel reads them (a new setting needs no new graph)
   DevBuf seq_bias;  // q3a_set_sequence_bias: the list's tables and counts, SEQBIAS_TABLE_WORDS words whatever the list (a new list needs no new graph); allocated by the first non-empty set
   // q3a_set_row_options: four regions of [B][4] words, one record per row each, as the kernels read the uniform buffers: sampling
   // (samp_params), filter (samp_filter), repetition (rep_params), then {the row's sequence-bias list or -1, 0, 0, 0}.  Allocated by the
@@ -353,9 +353,9 @@ struct DecodeStep : StepView {
 
   // final norm + lm_head on x_dec -> logits (+ block argmax partials), then argmax/finalize.  While sampling is on every form
   // stores its logits (as with head_logits_), the sampler (k_sample.hip) replaces the head's partials with its own noisy ones, and
-  // finalize runs on those unchanged.  While q3a_set_repetition is on every form stores its logits too, history_apply_kernel
+  // finalize runs on those unchanged.  While q3a_set_repetition is on every form stores its logits too, repeat_apply_kernel
   // (k_repeat.hip) rewrites the stored rows in place (l' -> l''), and fresh partials over l'' (or the sampler) replace the head's.
-  // q3a_set_sequence_bias is the same arrangement one place earlier: the same kernel in its sequence-bias mode (k_repeat.hip) rewrites the stored rows
+  // q3a_set_sequence_bias is the same arrangement one place earlier: seqbias_apply_kernel (k_repeat.hip) rewrites the stored rows
   // first, repetition control then works on its result, and the fresh partials are computed once, after the last rewriting kernel.
   // With a logit bias every form below
   // works on l' = l + b: the GEMV heads and both passes of the pruned argmax through GemvArgs::bias, the gemm16 forms through
@@ -483,7 +483,7 @@ struct DecodeStep : StepView {
     timed(Q3A_KC_ARGMAX, 0, [&] { KCHK(launch_repeat_apply(ra, stream)); });
     return partials ? enqueue_rewritten_partials(part) : 0;
   }
-  // Top log-probabilities (k_repeat.hip, top_logprobs.h): the n best entries of every live row of l'' into slot step_count[s] of the
+  // Top log-probabilities (k_toplp.hip): the n best entries of every live row of l'' into slot step_count[s] of the
   // history.  Behind the last rewriting kernel, in front of the finalize, which advances step_count and sets done.
   void enqueue_top_logprobs(const StepCommit& c) {  // c: what the finalize behind this launch commits into
     if (!top_n.p || !top_cand.p || !top_max.p || !top_sum.p || !top_ids.p || !top_lp.p) fail("top log-probabilities: on without its buffers");
@@ -906,7 +906,7 @@ struct q3a_engine : CallState {
   bool row_table_on_ = false;           // (graph signature)
   std::vector<q3a_row_options> rows_;   // the table as uploaded (q3a_debug_read "row_options")
   bool uni_on_[4] = {false, false, false, false};
-  bool top_lp_on_ = false;              // q3a_set_top_logprobs: n > 0 (k_repeat.hip; graph signature)
+  bool top_lp_on_ = false;              // q3a_set_top_logprobs: n > 0 (k_toplp.hip; graph signature)
   int top_lp_n_ = 0;                    // n as last set: what step.top_n holds while it is allocated
   int top_lp_run_n_ = 0;                // n the decode state was produced under (0: it has no history to fetch)
 

@@ -1,15 +1,11 @@
 // The history-dependent logits processors on the device: sequence bias (include/q3asr.h "sequence bias") and the
 // repetition penalty with the no-repeat n-gram ban (include/q3asr.h "repetition") -- what a step with
-// q3a_set_sequence_bias / q3a_set_repetition on puts between the lm_head and the argmax partials (or the sampler).  The kernel reads only
-// the stored logits l' [S][V] (fp32, bias included) and the sequence's own out_ids, so it does not care which head form wrote the row,
-// and it keeps nothing from step to step: no trie, no match state, nothing to undo.  The history IS out_ids[s][0 .. t),
-// t = min(step_count[s], out_stride).  Both processors are phases of ONE kernel (the library's kernel count is pinned by
-// tests/test_kernarg_preload.py); a launch runs the phases of one processor, the other's arguments are null.  The sampled step's
-// top-k / top-p stage (sample_filter.h) runs as three more launches of it, one phase each, for the same reason, and the top
-// log-probabilities (top_logprobs.h) as two more.
+// q3a_set_sequence_bias / q3a_set_repetition on puts between the lm_head and the argmax partials (or the sampler).  Each kernel reads
+// only the stored logits l' [S][V] (fp32, bias included) and the sequence's own out_ids, so it does not care which head form wrote the
+// row, and it keeps nothing from step to step: no trie, no match state, nothing to undo.  The history IS out_ids[s][0 .. t),
+// t = min(step_count[s], out_stride).  One kernel per processor, one workgroup of 256 threads per sequence each.
 //
-//   history_apply_kernel   one workgroup of 256 threads per sequence.
-//     sequence bias (launch_seqbias_apply):
+//   seqbias_apply_kernel (launch_seqbias_apply):
 //                          0a. the last min(t, 31) ids of the history go to LDS (an entry has at most 32 ids, so 31 lead its target);
 //                          0b. thread g, stride 256 over the target groups of the ROW'S list (the list index per row and the directory
 //                             list_begin from device memory, as G is: another list or row table replays the same graph), walks
@@ -20,62 +16,59 @@
 //                             one thread: no atomic, no order dependence.  One-token entries fire at t = 0 too (the id the prefill
 //                             produces): nothing returns early here.  Every index formed from the tables is checked against the
 //                             table's capacity and the row's length before it is used.
-//     repetition (launch_repeat_apply), four phases with a barrier between them:
+//   repeat_apply_kernel (launch_repeat_apply), four steps with a barrier between them:
 //                          1. zero a ceil(V / 32)-word bitmap in LDS;
 //                          2. every thread reads its share of the history, keeps it in LDS and sets the id's bit (LDS atomic OR);
 //                          3. every thread walks its bitmap words and rewrites the set entries of the row in place, l / p where
 //                             l > 0 and l * p elsewhere -- one correctly rounded fp32 operation each (plain / and *, the build has no
 //                             fast-math flag), and the bitmap is what makes "once per distinct id" true;
 //                          4. thread i compares h[i .. i + n - 1) with the last n - 1 ids and stores -inf at h[i + n - 1] on a match.
-//                             Idempotent stores: colliding ones are harmless.  After phase 3's barrier, or the read-modify-write
+//                             Idempotent stores: colliding ones are harmless.  After step 3's barrier, or the read-modify-write
 //                             of the penalty could overwrite a ban.
 // The rewritten row is l''; launch_argmax_partials (or launch_sample) and argmax_finalize then run on it unchanged.
 #include "dev.h"
 #include "kernels.h"
-#include "sample_filter.h"
-#include "top_logprobs.h"
 
 namespace q3a {
 
 namespace {
 
-__global__ __launch_bounds__(256) void history_apply_kernel(SeqBiasArgs sb, RepeatArgs a, int words, int hist_cap, SampleStageArgs st, TopLpArgs tl) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t repeat_lds[];
-  if (st.phase) { sample_stage_phase(st, repeat_lds); return; }  // top-k / top-p: a launch of its own, none of the history's phases
-  if (tl.phase) { top_lp_stage_phase(tl, repeat_lds); return; }  // top log-probabilities: likewise
+__global__ __launch_bounds__(256) void seqbias_apply_kernel(SeqBiasArgs sb) {
   __shared__ int tail[SEQBIAS_MAX_LEN - 1];
   const int s = blockIdx.x, tid = threadIdx.x;
-  if (sb.params) {  // (uniform: a kernel argument)
-    const int V = sb.V, t = max(min(sb.step_count[s], sb.out_stride), 0);
-    const int m = min(t, SEQBIAS_MAX_LEN - 1);  // ids of the history an entry can ask about
-    const int* const h = sb.out_ids + (size_t)s * sb.out_stride;
-    float* const row = sb.logits + (size_t)s * V;
-    if (tid < m) tail[tid] = h[t - m + tid];
-    __syncthreads();
-    const int G = min(sb.params[0], SEQBIAS_MAX_ENTRIES), E = min(sb.params[1], SEQBIAS_MAX_ENTRIES);
-    // the row's own list k (workgroup-uniform): its groups are list_begin[k] .. list_begin[k + 1); no list (-1): nothing to walk
-    const int k = sb.row_list[(size_t)s * sb.row_stride];
-    const bool listed = (unsigned)k < (unsigned)SEQBIAS_MAX_LISTS;
-    const int g0 = listed ? max(sb.list_begin[k], 0) : 0, g1 = listed ? min(sb.list_begin[k + 1], G) : 0;
-    for (int g = g0 + tid; g < g1; g += 256) {
-      const int target = sb.grp_target[g];
-      const int e0 = max(sb.grp_begin[g], 0), e1 = min(sb.grp_begin[g + 1], E);
-      float acc = 0.f;
-      bool fired = false;
-      for (int e = e0; e < e1; ++e) {
-        const int off = sb.ent_pre_off[e], n = sb.ent_pre_off[e + 1] - off;  // the entry's L - 1 leading ids: pre_ids[off .. off + n)
-        if (n < 0 || n > m || off < 0 || off + n > SEQBIAS_MAX_IDS) continue;  // (n > m: t < L - 1, the entry cannot fire yet)
-        bool eq = true;
-        for (int k = 0; k < n; ++k) eq = eq && sb.pre_ids[off + k] == tail[m - n + k];
-        if (eq) {
-          acc += sb.ent_bias[e];
-          fired = true;
-        }
+  const int V = sb.V, t = max(min(sb.step_count[s], sb.out_stride), 0);
+  const int m = min(t, SEQBIAS_MAX_LEN - 1);  // ids of the history an entry can ask about
+  const int* const h = sb.out_ids + (size_t)s * sb.out_stride;
+  float* const row = sb.logits + (size_t)s * V;
+  if (tid < m) tail[tid] = h[t - m + tid];
+  __syncthreads();
+  const int G = min(sb.params[0], SEQBIAS_MAX_ENTRIES), E = min(sb.params[1], SEQBIAS_MAX_ENTRIES);
+  // the row's own list k (workgroup-uniform): its groups are list_begin[k] .. list_begin[k + 1); no list (-1): nothing to walk
+  const int k = sb.row_list[(size_t)s * sb.row_stride];
+  const bool listed = (unsigned)k < (unsigned)SEQBIAS_MAX_LISTS;
+  const int g0 = listed ? max(sb.list_begin[k], 0) : 0, g1 = listed ? min(sb.list_begin[k + 1], G) : 0;
+  for (int g = g0 + tid; g < g1; g += 256) {
+    const int target = sb.grp_target[g];
+    const int e0 = max(sb.grp_begin[g], 0), e1 = min(sb.grp_begin[g + 1], E);
+    float acc = 0.f;
+    bool fired = false;
+    for (int e = e0; e < e1; ++e) {
+      const int off = sb.ent_pre_off[e], n = sb.ent_pre_off[e + 1] - off;  // the entry's L - 1 leading ids: pre_ids[off .. off + n)
+      if (n < 0 || n > m || off < 0 || off + n > SEQBIAS_MAX_IDS) continue;  // (n > m: t < L - 1, the entry cannot fire yet)
+      bool eq = true;
+      for (int k = 0; k < n; ++k) eq = eq && sb.pre_ids[off + k] == tail[m - n + k];
+      if (eq) {
+        acc += sb.ent_bias[e];
+        fired = true;
       }
-      if (fired && (unsigned)target < (unsigned)V) row[target] = row[target] + acc;
     }
+    if (fired && (unsigned)target < (unsigned)V) row[target] = row[target] + acc;
   }
-  if (!a.params) return;  // (uniform)
+}
+
+__global__ __launch_bounds__(256) void repeat_apply_kernel(RepeatArgs a, int words, int hist_cap) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t repeat_lds[];
+  const int s = blockIdx.x, tid = threadIdx.x;
   uint32_t* const bits = repeat_lds;                                         // [words]
   int* const hist = reinterpret_cast<int*>(repeat_lds + ((words + 3) & ~3));  // [hist_cap] the first hist_cap ids of the history
   const int V = a.V;
@@ -130,7 +123,7 @@ const char* launch_repeat_apply(const RepeatArgs& a, hipStream_t s) {
   if (!a.logits || !a.params || !a.out_ids || !a.step_count || a.out_stride < 1) return "repetition: null argument";
   const int words = (a.V + 31) / 32, hist_cap = a.out_stride < REPEAT_HIST_LDS ? a.out_stride : REPEAT_HIST_LDS;
   const size_t lds = ((size_t)((words + 3) & ~3) + (size_t)hist_cap) * 4;  // <= 32 KB + 16 KB
-  hipLaunchKernelGGL(history_apply_kernel, dim3(a.S), dim3(256), lds, s, SeqBiasArgs{}, a, words, hist_cap, SampleStageArgs{}, TopLpArgs{});
+  hipLaunchKernelGGL(repeat_apply_kernel, dim3(a.S), dim3(256), lds, s, a, words, hist_cap);
   return nullptr;
 }
 
@@ -139,35 +132,7 @@ const char* launch_seqbias_apply(const SeqBiasArgs& a, hipStream_t s) {
   if (a.V < 1) return "sequence bias: empty vocabulary";
   if (!a.logits || !a.params || !a.grp_target || !a.grp_begin || !a.ent_bias || !a.ent_pre_off || !a.pre_ids || !a.list_begin || !a.row_list || !a.out_ids || !a.step_count || a.out_stride < 1)
     return "sequence bias: null argument";
-  hipLaunchKernelGGL(history_apply_kernel, dim3(a.S), dim3(256), 0, s, a, RepeatArgs{}, 0, 0, SampleStageArgs{}, TopLpArgs{});
-  return nullptr;
-}
-
-// Top-k / top-p (launch_sample_filtered, k_sample.hip): the histogram on the chunk grid, the select with one workgroup per row, the
-// filtered draw on the chunk grid -- the arguments were checked by the caller.
-const char* launch_sample_stage(const SampleArgs& a, const SampleFilterArgs& f, bool vec, hipStream_t s) {
-  SampleStageArgs st{1, vec ? 1 : 0, sample_chunks(a.V), a, f};
-  const dim3 grid(st.n_chunk, a.S);
-  hipLaunchKernelGGL(history_apply_kernel, grid, dim3(256), SAMPLE_HIST_LDS, s, SeqBiasArgs{}, RepeatArgs{}, 0, 0, st, TopLpArgs{});
-  st.phase = 2;
-  hipLaunchKernelGGL(history_apply_kernel, dim3(a.S), dim3(256), SAMPLE_SELECT_LDS, s, SeqBiasArgs{}, RepeatArgs{}, 0, 0, st, TopLpArgs{});
-  st.phase = 3;
-  hipLaunchKernelGGL(history_apply_kernel, grid, dim3(256), 0, s, SeqBiasArgs{}, RepeatArgs{}, 0, 0, st, TopLpArgs{});
-  return nullptr;
-}
-
-// Top log-probabilities: the chunk grid, then one workgroup per row with the chunks' candidates in LDS.
-const char* launch_top_logprobs(const TopLpArgs& a, hipStream_t s) {
-  if (a.S <= 0) return nullptr;
-  if (a.V < 1) return "top log-probabilities: empty vocabulary";
-  if (a.V > TOP_LP_MAX_VOCAB) return "top log-probabilities: the vocabulary exceeds the row phase's candidate table (819200 ids)";
-  if (!a.logits || !a.n_dev || !a.step_count || !a.done || !a.cand || !a.chunk_max || !a.chunk_sum || !a.out_ids || !a.out_lp || a.out_stride < 1)
-    return "top log-probabilities: null argument";
-  TopLpArgs t = a;
-  t.phase = 1; t.vec = a.V % 4 == 0 && ((uintptr_t)a.logits & 15) == 0 ? 1 : 0; t.n_chunk = sample_chunks(a.V);
-  hipLaunchKernelGGL(history_apply_kernel, dim3(t.n_chunk, a.S), dim3(256), 0, s, SeqBiasArgs{}, RepeatArgs{}, 0, 0, SampleStageArgs{}, t);
-  t.phase = 2;
-  hipLaunchKernelGGL(history_apply_kernel, dim3(a.S), dim3(256), (size_t)t.n_chunk * TOP_LP_MAX * 8, s, SeqBiasArgs{}, RepeatArgs{}, 0, 0, SampleStageArgs{}, t);
+  hipLaunchKernelGGL(seqbias_apply_kernel, dim3(a.S), dim3(256), 0, s, a);
   return nullptr;
 }
 

@@ -12,10 +12,12 @@
 //   sample_logprob_kernel  one wave per row, after finalize: (m, sum) of the row in a fixed order and lp = (l'_id - m) - log(sum) of the
 //                          id finalize chose, written where finalize would have put the greedy log-probability.
 // The tie rule is ArgmaxAcc's everywhere: the larger value, on equal values the smaller id.
-// With q3a_set_sampling_filter on (top-k / top-p) launch_sample_filtered runs sample_rowstat_kernel and then the
-// threshold stage and the filtered draw of sample_filter.h (phases of k_repeat.hip's kernel).  Off, none of that is enqueued.
-#include "argmax.h"
-#include "sample_rng.h"
+// With q3a_set_sampling_filter on (top-k / top-p) launch_sample_filtered runs sample_rowstat_kernel and then three
+// kernels around the device functions of sample_filter.h.  Off, none of them is enqueued.
+//   sample_hist_kernel          the chunk grid: the first-digit histogram of the row's keys (SAMPLE_HIST_LDS of dynamic LDS).
+//   sample_select_kernel        one workgroup per row: the radix select, tau_sel[s] and kept[s] (SAMPLE_SELECT_LDS).
+//   sample_chunk_filter_kernel  the chunk grid: sample_chunk_kernel with tau_sel[s] as one more threshold.
+#include "sample_filter.h"
 
 namespace q3a {
 
@@ -152,6 +154,28 @@ __global__ __launch_bounds__(64) void sample_logprob_kernel(SampleLogprobArgs a,
   }
 }
 
+template <bool VEC>
+__global__ __launch_bounds__(256) void sample_hist_kernel(SampleArgs a, SampleFilterArgs f, int n_chunk) {
+  extern __shared__ __attribute__((aligned(16))) u64 filter_lds[];
+  u64* const mass = filter_lds;
+  uint32_t* const cnt = reinterpret_cast<uint32_t*>(mass + SAMPLE_BUCKETS);
+  sample_hist_phase<VEC>(cnt, mass, a.logits, a.V, n_chunk, a.params, f.filter, a.row_stride, a.chunk_max, f.hist_cnt, f.hist_mass);
+}
+
+__global__ __launch_bounds__(256) void sample_select_kernel(SampleArgs a, SampleFilterArgs f, int n_chunk, int vec) {
+  extern __shared__ __attribute__((aligned(16))) u64 filter_lds[];
+  u64* const mass0 = filter_lds;
+  u64* const mass1 = mass0 + SEL_TABLE;
+  uint32_t* const cnt0 = reinterpret_cast<uint32_t*>(mass1 + SEL_TABLE);
+  sample_select_phase(cnt0, mass0, cnt0 + SEL_TABLE, mass1, a.logits, a.V, n_chunk, vec, a.params, f.filter, a.row_stride, a.chunk_max, f.hist_cnt, f.hist_mass,
+                      f.tau_sel, f.kept);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void sample_chunk_filter_kernel(SampleArgs a, int n_chunk, const float* __restrict__ tau_sel) {
+  sample_chunk_filter_phase<VEC>(a, n_chunk, tau_sel);
+}
+
 }  // namespace
 
 const char* launch_sample(const SampleArgs& a, hipStream_t s) {
@@ -183,9 +207,18 @@ const char* launch_sample_filtered(const SampleArgs& a, const SampleFilterArgs& 
   if (a.part.sum) return "sample: the partials carry no log-sum channel";
   const bool vec = a.V % 4 == 0 && ((uintptr_t)a.logits & 15) == 0;
   const dim3 grid(nc, a.S);
-  if (vec) hipLaunchKernelGGL(sample_rowstat_kernel<true>, grid, dim3(256), 0, s, a.logits, a.V, nc, a.chunk_max, a.chunk_sum);
-  else hipLaunchKernelGGL(sample_rowstat_kernel<false>, grid, dim3(256), 0, s, a.logits, a.V, nc, a.chunk_max, a.chunk_sum);
-  return launch_sample_stage(a, f, vec, s);  // k_repeat.hip: the histogram, the select and the filtered draw
+  // the rows' statistics, the histogram on the chunk grid, the select with one workgroup per row, the filtered draw on the chunk grid
+  if (vec) {
+    hipLaunchKernelGGL(sample_rowstat_kernel<true>, grid, dim3(256), 0, s, a.logits, a.V, nc, a.chunk_max, a.chunk_sum);
+    hipLaunchKernelGGL(sample_hist_kernel<true>, grid, dim3(256), SAMPLE_HIST_LDS, s, a, f, nc);
+  } else {
+    hipLaunchKernelGGL(sample_rowstat_kernel<false>, grid, dim3(256), 0, s, a.logits, a.V, nc, a.chunk_max, a.chunk_sum);
+    hipLaunchKernelGGL(sample_hist_kernel<false>, grid, dim3(256), SAMPLE_HIST_LDS, s, a, f, nc);
+  }
+  hipLaunchKernelGGL(sample_select_kernel, dim3(a.S), dim3(256), SAMPLE_SELECT_LDS, s, a, f, nc, vec ? 1 : 0);
+  if (vec) hipLaunchKernelGGL(sample_chunk_filter_kernel<true>, grid, dim3(256), 0, s, a, nc, f.tau_sel);
+  else hipLaunchKernelGGL(sample_chunk_filter_kernel<false>, grid, dim3(256), 0, s, a, nc, f.tau_sel);
+  return nullptr;
 }
 
 const char* launch_sample_logprob(const SampleLogprobArgs& a, hipStream_t s) {

@@ -1,15 +1,13 @@
 // Top log-probabilities (include/q3asr.h "top log-probabilities"): the n best entries of every row of the
-// step's final logits l'' with their log-probabilities, as device functions.  They run as two more phases of history_apply_kernel
-// (k_repeat.hip), as the sampling filter's do (sample_filter.h): the library's kernel count is pinned.  256 threads each.
-//   top_lp_chunk_phase   the chunk grid (ceil(V / 2048), S): the min(n, chunk) best of one 2048-logit chunk, and the chunk's
+// step's final logits l'' with their log-probabilities.  Two kernels of 256 threads, launched by launch_top_logprobs.
+//   top_lp_chunk_kernel  the chunk grid (ceil(V / 2048), S): the min(n, chunk) best of one 2048-logit chunk, and the chunk's
 //                        (max, sum exp(l - max)).
-//   top_lp_row_phase     one workgroup per row: folds the chunks' pairs into the row's (m, sum) in index order, picks the n best of
+//   top_lp_row_kernel    one workgroup per row: folds the chunks' pairs into the row's (m, sum) in index order, picks the n best of
 //                        the chunks' candidates and writes (id, lp) to slot step_count[s] of the history.
 // An entry is ONE 64-bit word (sel_key(l) << 32) | ~index: its unsigned order is "larger logit first, then smaller id", -0.0 and +0.0
 // share a key, -inf has the smallest key of all values.  Words of one row are distinct (the indices are), so the r-th best is the
 // largest word under the (r - 1)-th: a round is one maximum, nothing is removed and nothing depends on arrival order.  A real entry's
 // word is never 0 (no value's key is 0), so 0 stands for "no entry".  The row's n best are among the union of the chunks' n best.
-#pragma once
 #include "sample_filter.h"
 
 namespace q3a {
@@ -37,7 +35,7 @@ __device__ __forceinline__ float top_lp_wg_sum(float mine, float* red, int lane,
   return ((red[0] + red[1]) + red[2]) + red[3];
 }
 
-// n as the phases use it: the device word, clamped to what the buffers hold and the row has
+// n as the kernels use it: the device word, clamped to what the buffers hold and the row has
 __device__ __forceinline__ int top_lp_n(const TopLpArgs& a) { return max(min(min(a.n_dev[0], TOP_LP_MAX), a.V), 0); }
 // does row s record this step?  not when it is done, and not without a slot (workgroup-uniform)
 __device__ __forceinline__ bool top_lp_live(const TopLpArgs& a, int s, int& slot) {
@@ -46,7 +44,7 @@ __device__ __forceinline__ bool top_lp_live(const TopLpArgs& a, int s, int& slot
 }
 
 template <bool VEC>
-__device__ __forceinline__ void top_lp_chunk_phase(const TopLpArgs& a) {
+__global__ __launch_bounds__(256) void top_lp_chunk_kernel(TopLpArgs a, int n_chunk) {
   __shared__ u64 red[2][4];
   __shared__ float fred[4];
   const int s = blockIdx.y, c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -75,7 +73,7 @@ __device__ __forceinline__ void top_lp_chunk_phase(const TopLpArgs& a) {
       w[q] = e < V ? top_lp_word(f[q], e) : 0ull;
     }
   }
-  u64* const cand = a.cand + ((size_t)s * a.n_chunk + c) * TOP_LP_MAX;
+  u64* const cand = a.cand + ((size_t)s * n_chunk + c) * TOP_LP_MAX;
   u64 prev = ~0ull;
   float m = -INFINITY;
 #pragma nounroll
@@ -94,16 +92,16 @@ __device__ __forceinline__ void top_lp_chunk_phase(const TopLpArgs& a) {
   for (int q = 0; q < 8; ++q) sum += f[q] == -INFINITY ? 0.f : expf(f[q] - m);
   sum = top_lp_wg_sum(sum, fred, lane, wave);
   if (tid == 0) {
-    a.chunk_max[(size_t)s * a.n_chunk + c] = m;
-    a.chunk_sum[(size_t)s * a.n_chunk + c] = sum;
+    a.chunk_max[(size_t)s * n_chunk + c] = m;
+    a.chunk_sum[(size_t)s * n_chunk + c] = sum;
   }
 }
 
-// cand_lds: n_chunk * TOP_LP_MAX words of dynamic LDS
-__device__ __forceinline__ void top_lp_row_phase(const TopLpArgs& a, u64* cand_lds) {
+__global__ __launch_bounds__(256) void top_lp_row_kernel(TopLpArgs a, int n_chunk) {
+  extern __shared__ __attribute__((aligned(16))) u64 cand_lds[];  // n_chunk * TOP_LP_MAX words
   __shared__ u64 red[2][4];
   const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int V = a.V, n = top_lp_n(a), n_chunk = a.n_chunk;
+  const int V = a.V, n = top_lp_n(a);
   int slot;
   if (n == 0 || !top_lp_live(a, s, slot)) return;
   // (m, sum) of the row from the chunks' pairs: the maximum first (any order gives the same bits), then the rescaled sums in index
@@ -139,16 +137,20 @@ __device__ __forceinline__ void top_lp_row_phase(const TopLpArgs& a, u64* cand_l
   }
 }
 
-// One launch of the stage: phase 1 the chunk grid, phase 2 one workgroup per row.  `lds`: the launch's dynamic LDS.
-__device__ __forceinline__ void top_lp_stage_phase(const TopLpArgs& a, void* lds) {
-  if (a.phase == 1) {
-    if (a.vec) top_lp_chunk_phase<true>(a);
-    else top_lp_chunk_phase<false>(a);
-  } else {
-    top_lp_row_phase(a, reinterpret_cast<u64*>(lds));
-  }
-}
-
 }  // namespace
+
+// The chunk grid, then one workgroup per row with the chunks' candidates in LDS.
+const char* launch_top_logprobs(const TopLpArgs& a, hipStream_t s) {
+  if (a.S <= 0) return nullptr;
+  if (a.V < 1) return "top log-probabilities: empty vocabulary";
+  if (a.V > TOP_LP_MAX_VOCAB) return "top log-probabilities: the vocabulary exceeds the row kernel's candidate table (819200 ids)";
+  if (!a.logits || !a.n_dev || !a.step_count || !a.done || !a.cand || !a.chunk_max || !a.chunk_sum || !a.out_ids || !a.out_lp || a.out_stride < 1)
+    return "top log-probabilities: null argument";
+  const int nc = sample_chunks(a.V);
+  if (a.V % 4 == 0 && ((uintptr_t)a.logits & 15) == 0) hipLaunchKernelGGL(top_lp_chunk_kernel<true>, dim3(nc, a.S), dim3(256), 0, s, a, nc);
+  else hipLaunchKernelGGL(top_lp_chunk_kernel<false>, dim3(nc, a.S), dim3(256), 0, s, a, nc);
+  hipLaunchKernelGGL(top_lp_row_kernel, dim3(a.S), dim3(256), (size_t)nc * TOP_LP_MAX * 8, s, a, nc);
+  return nullptr;
+}
 
 }  // namespace q3a

@@ -535,9 +535,6 @@ struct SampleFilterArgs {
   float* tau_sel; int* kept;           // [S] (written)
 };
 const char* launch_sample_filtered(const SampleArgs& a, const SampleFilterArgs& f, hipStream_t s);
-// What launch_sample_filtered enqueues behind sample_rowstat: three launches of k_repeat.hip's kernel, one phase each (sample_filter.h).
-struct SampleStageArgs { int phase; int vec; int n_chunk; SampleArgs a; SampleFilterArgs f; };  // phase 0: not the sampler's launch
-const char* launch_sample_stage(const SampleArgs& a, const SampleFilterArgs& f, bool vec, hipStream_t s);
 // After launch_argmax_finalize: lp = (l_id - m) - log sum exp(l - m) of the id it chose (next_tok[s]), the sum merged in a fixed
 // order, written to out_lp[s][step_count[s] - 1] -- the entry finalize filled for this step; out_z[s] = the winning noisy score.
 struct SampleLogprobArgs {
@@ -549,7 +546,7 @@ struct SampleLogprobArgs {
 };
 const char* launch_sample_logprob(const SampleLogprobArgs& a, hipStream_t s);
 
-// ---- top log-probabilities (k_repeat.hip: two more phases of its kernel; top_logprobs.h) --------------------------
+// ---- top log-probabilities (k_toplp.hip) --------------------------------------------------------------------------
 constexpr int TOP_LP_MAX = 20;  // entries per step: the largest n, and the fixed inner stride of the history and of the candidates
 // Per row s of logits [S][V] (fp32, row stride V) that is not done and has a slot t = step_count[s] < out_stride: the n = min(*n_dev,
 // TOP_LP_MAX, V) best entries -- larger logit first, then smaller id; -0.0 and +0.0 one value; -inf last -- as out_ids / out_lp
@@ -557,7 +554,6 @@ constexpr int TOP_LP_MAX = 20;  // entries per step: the largest n, and the fixe
 // writes nothing.  Two launches: the chunk grid (candidates and (max, sum) per 2048-logit chunk), then one workgroup per row.  It only
 // reads the logits; it runs behind the step's last rewriting kernel and in front of launch_argmax_finalize, which advances step_count.
 struct TopLpArgs {
-  int phase; int vec; int n_chunk;     // phase 0: not this stage's launch (filled by launch_top_logprobs)
   const float* logits; int S; int V;
   const int* n_dev;                    // device [1]: n as last set (read by the kernel: another n > 0, the same launch)
   const int* step_count;               // [S]
@@ -567,10 +563,10 @@ struct TopLpArgs {
   int* out_ids; float* out_lp;         // [S][out_stride][TOP_LP_MAX] the history
   int out_stride;
 };
-constexpr int TOP_LP_MAX_VOCAB = 400 * 2048;  // the row phase keeps every chunk's candidates in LDS (400 chunks x 20 x 8 bytes)
+constexpr int TOP_LP_MAX_VOCAB = 400 * 2048;  // the row kernel keeps every chunk's candidates in LDS (400 chunks x 20 x 8 bytes)
 const char* launch_top_logprobs(const TopLpArgs& a, hipStream_t s);
 
-// ---- repetition penalty and no-repeat n-grams (k_repeat.hip) -----------------------------------------------------
+// ---- repetition penalty and no-repeat n-grams (k_repeat.hip: repeat_apply_kernel) --------------------------------
 constexpr int REPEAT_MAX_VOCAB = 1 << 18;  // ids the kernel's LDS bitmap holds (8192 words, 32 KB)
 constexpr int REPEAT_HIST_LDS = 4096;      // ids of a history kept in LDS (16 KB); a longer history is read in place beyond them
 // Per row s of logits [S][V] (fp32, row stride V), rewritten IN PLACE: with h = out_ids[s][0 .. t), t = min(step_count[s], out_stride),
@@ -586,7 +582,7 @@ struct RepeatArgs {
 };
 const char* launch_repeat_apply(const RepeatArgs& a, hipStream_t s);
 
-// ---- sequence bias (k_repeat.hip: a mode of the same kernel) -----------------------------------------------------------------------------
+// ---- sequence bias (k_repeat.hip: seqbias_apply_kernel) ----------------------------------------------------------
 constexpr int SEQBIAS_MAX_ENTRIES = 4096;  // entries over all lists (and so target groups)
 constexpr int SEQBIAS_MAX_LISTS = 256;     // lists of q3a_set_sequence_bias_lists
 constexpr int SEQBIAS_MAX_LEN = 32;        // ids of one entry

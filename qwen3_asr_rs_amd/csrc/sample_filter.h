@@ -1,6 +1,7 @@
 // Top-k / top-p of the sampled step (include/q3asr.h "sampling filter"): the threshold stage and the filtered
-// draw as device functions.  They run as phases of history_apply_kernel (k_repeat.hip), the kernel of the step's other logits
-// processors: the library's kernel count is pinned (tests/test_kernarg_preload.py), and a launch runs ONE phase.  256 threads each.
+// draw as device functions, 256 threads each.  k_sample.hip wraps each in a kernel of its own (sample_hist_kernel,
+// sample_select_kernel, sample_chunk_filter_kernel); the key, the row maximum and u64 are shared with the top log-probabilities
+// (k_toplp.hip), which is why this is a header.
 #pragma once
 #include "argmax.h"
 #include "sample_rng.h"
@@ -310,27 +311,8 @@ __device__ __forceinline__ void sample_chunk_filter_phase(const SampleArgs& a, i
   }
 }
 
-// One launch of the stage: phase 1 the histogram (chunk grid, 24 KB of LDS), 2 the select (one workgroup per row, 2 x 24.75 KB),
-// 3 the filtered draw (chunk grid).  `lds`: the launch's dynamic LDS.
-__device__ __forceinline__ void sample_stage_phase(const SampleStageArgs& g, void* lds) {
-  const SampleArgs& a = g.a;
-  const SampleFilterArgs& f = g.f;
-  if (g.phase == 1) {
-    u64* mass = reinterpret_cast<u64*>(lds);
-    uint32_t* cnt = reinterpret_cast<uint32_t*>(mass + SAMPLE_BUCKETS);
-    if (g.vec) sample_hist_phase<true>(cnt, mass, a.logits, a.V, g.n_chunk, a.params, f.filter, a.row_stride, a.chunk_max, f.hist_cnt, f.hist_mass);
-    else sample_hist_phase<false>(cnt, mass, a.logits, a.V, g.n_chunk, a.params, f.filter, a.row_stride, a.chunk_max, f.hist_cnt, f.hist_mass);
-  } else if (g.phase == 2) {
-    u64* mass0 = reinterpret_cast<u64*>(lds);
-    u64* mass1 = mass0 + SEL_TABLE;
-    uint32_t* cnt0 = reinterpret_cast<uint32_t*>(mass1 + SEL_TABLE);
-    sample_select_phase(cnt0, mass0, cnt0 + SEL_TABLE, mass1, a.logits, a.V, g.n_chunk, g.vec, a.params, f.filter, a.row_stride, a.chunk_max, f.hist_cnt, f.hist_mass,
-                        f.tau_sel, f.kept);
-  } else {
-    if (g.vec) sample_chunk_filter_phase<true>(a, g.n_chunk, f.tau_sel);
-    else sample_chunk_filter_phase<false>(a, g.n_chunk, f.tau_sel);
-  }
-}
+// Dynamic LDS of the two: the histogram's mass[SAMPLE_BUCKETS] then cnt[SAMPLE_BUCKETS] (24 KB); the select's mass0, mass1, cnt0, cnt1
+// of SEL_TABLE words each (2 x 24.75 KB).  The 64-bit tables come first: the launch's LDS is 16-byte aligned.
 constexpr size_t SAMPLE_HIST_LDS = (size_t)SAMPLE_BUCKETS * 12, SAMPLE_SELECT_LDS = (size_t)SEL_TABLE * 24;
 
 }  // namespace

@@ -1,4 +1,4 @@
-"""Top log-probabilities on the GPU (q3a_set_top_logprobs; top_logprobs.h as phases of history_apply_kernel): the two launches
+"""Top log-probabilities on the GPU (q3a_set_top_logprobs; k_toplp.hip): the two launches
 against the float64 reference through q3a_selftest_top_logprobs, every lm_head form feeding them, graph replay against the eager stage
 API, another n on the same graph, the way back to an engine that never had the setting, the composition with the other logits
 processors, ragged stops, a batch that grows and shrinks, the refusals and the device memory across cycles.
@@ -75,7 +75,7 @@ def test_kernels_against_the_reference(Vk):
 
 
 def test_kernels_at_the_real_vocabulary():
-    """V = 151936 once (75 chunks, 1500 candidates in the row phase): a random row, and a row whose 20 best stand in 20 chunks."""
+    """V = 151936 once (75 chunks, 1500 candidates in the row kernel): a random row, and a row whose 20 best stand in 20 chunks."""
     rows, at = T.big_rows()
     ids, lp = _selftest(rows, 20, [0, 1], [0, 0], 2)
     assert ids[1, 1].tolist() == at.tolist()
@@ -110,7 +110,7 @@ def test_hand_made_rows():
     print(f"[top logprobs] hand-made rows: largest |lp - log_softmax64| {worst:.2e}")
 
 
-# ---- 2. every head form stores what the phases read --------------------------------------------------------------------------
+# ---- 2. every head form stores what the two kernels read -------------------------------------------------------------------
 def _clips(n, seed0=40, base=1.0):
     return [synthetic.synthetic_clip(seed0 + i, base + 0.25 * (i % 4)) for i in range(n)]
 

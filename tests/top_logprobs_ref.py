@@ -7,7 +7,7 @@ import numpy as np
 from beam_ref import topk_ref
 
 INNER = 20                                   # the history's fixed inner stride, and the largest n
-CHUNK = 2048                                 # logits per workgroup of the chunk phase
+CHUNK = 2048                                 # logits per workgroup of the chunk kernel
 KERNEL_V = (20, 63, 2048, 2049, 4100, 6150)  # n itself, an odd size, one chunk, one entry more, three chunks (16-byte loads), four (scalar loads)
 BIG_V = 151936
 KERNEL_N = (1, 2, 8, 20)
